@@ -11,11 +11,11 @@ testroomopt.glb (44 866 triangles vs 46 252); "1920x1080" = 2 073 600 photons pe
 positions/lange_route.xml; SEED_0 = 0.  `--scene soup:T` swaps in a synthetic T-triangle scene that does not
 fit in L2.  `--route` makes the reference's own DEFAULT workload the headline instead: all 12 lamps
 of lange_route.xml x 10 iterations x ((2^25 / 12) & ~1) photons (raytracer.h:30-32, myapp.cpp:156-170); the
-default run reports it beside the headline (`route_workload`).
+`--full` run reports it beside the headline (`route_workload`).
 
 One STEP = one whole computation: ResetDosageMap, then per wave generate -> extend -> accumulate and Shade
 (computeDosage + dosageToColor), then a sync.  Inputs (scene, BVH) are resident in HBM before the timed region.
-Modes at N = 1 (`value` is the selected one's, the others are reported under `other_modes`):
+Modes at N = 1 (`value` is the selected one's, `--full` reports the others under `other_modes`):
   batched (default)   RayTracer::ComputeIterationsBatched -- an API EXTENSION the reference's caller does not have
                       (include/uvrt.h "batched tracing"): the waves traced first in fused launches of a few waves
                       each on two side streams, then accumulate + Shade replayed per wave on the context's stream
@@ -29,7 +29,14 @@ N > 1 (one process per GPU): STRONG scaling is the headline -- BASELINE configs[
 global-id range over the ranks ("pixel tiles"), each rank deposits into private int32 planes, ONE RCCL
 all-reduce of the planes per computation (native: uvrt_reduce_batch), then every rank replays accumulate +
 Shade; the dose is bit-identical to one GPU.  The WEAK figure (configs[4]: whole launches dealt to ranks, 8
-waves per GPU, one SUM/MAX reduction of the f64 maps) is measured in the same run and reported beside it.
+waves per GPU, one SUM/MAX reduction of the f64 maps) is measured with `--full` and reported beside it.
+
+A plain run sets up, warms up, times the `--steps` steps of the headline and prints the line; its dose CRC is checked
+against the committed oracle CRC where one exists.  Everything else (single computation, other modes and flavours,
+cold start, route workload, the roofline's timing and clock passes, the CPU baseline and the oracle comparisons, at
+N > 1 the other scaling) runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed --
+dose (f32), colour (f32, 9 per triangle), photon map and max photon map (f64) -- as DIR/<name>.npy, read right
+after the timed steps; beyond 64 MB in all, the same fixed, seeded sample of triangles is kept in every array.
 """
 from __future__ import annotations
 
@@ -218,6 +225,23 @@ class _Scene:
     pass
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write the per-triangle arrays of `outputs` (first axis = triangle) as out_dir/<name>.npy.  When they exceed `limit`
+    bytes in all, every array keeps the same fixed, seeded, sorted sample of triangles, so that two runs compare row for row."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    T = len(next(iter(outputs.values())))
+    row_bytes = sum(a.nbytes // max(len(a), 1) for a in outputs.values())
+    keep = min(T, (limit - (1 << 16)) // max(row_bytes, 1))         # room for the .npy headers
+    idx = None if keep >= T else np.sort(np.random.default_rng(seed).choice(T, size=keep, replace=False))
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64) and len(a) == T, name
+        np.save(os.path.join(out_dir, name + ".npy"), a if idx is None else a[idx])
+
+
 def issue_model_utilisation(m, rays, seconds, clock_hz=None):
     """Utilisation of each unit while `rays` rays are traced in `seconds` of wall time: the kernel's per-ray counts
     (profiles/extend_issue_model_*.json, made by tests/tools/stream_census.py: VALU issue cycles = trip counts x the static
@@ -340,10 +364,16 @@ def main():
     ap.add_argument("--route", action="store_true",
                     help="headline = the reference's default workload: 12 lamps x 10 iterations x ((2^25 / 12) & ~1) photons "
                          "(raytracer.h:30-32, positions/lange_route.xml, myapp.cpp:156-170)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure and check beside the headline: single computation, other modes and flavours, "
+                         "cold start, route workload, roofline, CPU baseline and oracle comparisons, at N > 1 the other "
+                         "scaling.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (dose, colour, photon maps) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--lean", action="store_true",
-                    help="profiling aid: only the headline mode (no other-mode, single-computation, cold or route leg), so "
-                         "that a kernel trace / PMC run holds nothing but the timed kind of launch")
+                    help="with --full, profiling aid: only the headline mode (no other-mode, single-computation, cold or route "
+                         "leg), so that a kernel trace / PMC run holds nothing but the timed kind of launch")
     ap.add_argument("--no-pipeline", action="store_true", help="one stream: launches do not overlap")
     ap.add_argument("--sort-bits", type=int, default=None)
     ap.add_argument("--variant", type=int, default=None)
@@ -615,6 +645,11 @@ def main():
     def crc(a):
         return "%08x" % zlib.crc32(a.tobytes())
 
+    def read_outputs():
+        """What a caller of the timed path receives after its last step: per-triangle dose, colour and the two f64 maps."""
+        return {"dose": rt.read_dosage(), "color": rt.ctx.read_color(),
+                "photon_map": rt.ctx.read_photon_map(0), "max_photon_map": rt.ctx.read_photon_map(1)}
+
     golden_path = os.path.join(ROOT, "tests", "golden", "bench_dose_crc.json")
     golden = json.load(open(golden_path)) if os.path.exists(golden_path) else {}
 
@@ -625,6 +660,7 @@ def main():
     ext_ms = ext_launches = None
     clock_mhz = None
     cold = route_leg = None
+    outputs = None
     timing_steps = max(1, min(3, args.steps))
     few = max(1, min(5, args.steps))
 
@@ -632,8 +668,9 @@ def main():
         headline = STEP[args.mode]
         elapsed = timed(headline, args.warmup, args.steps)
         # the result of the TIMED region itself (the last of its steps), read before anything else runs
+        outputs = read_outputs() if args.dump_outputs else None
         dose_timed = rt.read_dosage()
-        if not args.lean:
+        if args.full and not args.lean:
             # one computation on its own, bracketed by syncs (`value` is the steady-state rate of back-to-back
             # computations)
             single_ms = median_synced(headline, few)
@@ -716,7 +753,7 @@ def main():
                                 "buffers already allocated" % few}
                 configure(headline_lamps, args.photons, args.waves)
         # ---- the reference's default workload: 12 lamps x 10 iterations x 2 796 202 photons -----------------------
-        if default_config and not args.lean and len(all_lamps) > 1:
+        if args.full and default_config and not args.lean and len(all_lamps) > 1:
             configure(all_lamps, ROUTE_PHOTONS, ROUTE_ITERATIONS)
             n_route = rt.photonsPerLight
             rays_route = ROUTE_ITERATIONS * len(all_lamps) * n_route
@@ -752,53 +789,60 @@ def main():
             configure(headline_lamps, args.photons, args.waves)
         # timing pass for the roofline: the headline step with HIP events around the extend launches on their
         # stream (loop modes: launch pipelining off, so the kernels of neighbouring waves do not overlap)
-        if args.mode != "batched":
-            rt.ctx.set_pipeline(False)
-        rt.ctx.set_timing(True)
-        rt.ctx.extend_time_ms()                    # drop anything recorded so far
-        for _ in range(timing_steps):
-            headline()
-        sync_all()
-        ext_ms, ext_launches = rt.ctx.extend_time_ms()
-        rt.ctx.set_timing(False)
-        rt.ctx.set_pipeline(not args.no_pipeline)
-        rt.Sync()
-        # the shader clock UNDER THIS LOAD: a one-wave probe (s_memtime against the constant 100 MHz s_memrealtime) on a stream of
-        # its own while the headline steps run again exactly as they were timed; the clock moves between 2.0 and 2.4 GHz with the
-        # power the kernel draws, and the issue-rate peaks of the roofline move with it
-        clock_steps = max(2, min(10, args.steps))
-        span_us = int(0.8 * clock_steps * elapsed / args.steps * 1e6)
-        if span_us >= 1:
-            for _ in range(2):
-                headline()
-            rt.ctx.clock_probe_start(min(span_us, 1000000))
-            for _ in range(clock_steps):
+        if args.full:
+            if args.mode != "batched":
+                rt.ctx.set_pipeline(False)
+            rt.ctx.set_timing(True)
+            rt.ctx.extend_time_ms()                    # drop anything recorded so far
+            for _ in range(timing_steps):
                 headline()
             sync_all()
-            clock_mhz = rt.ctx.clock_probe_read()
+            ext_ms, ext_launches = rt.ctx.extend_time_ms()
+            rt.ctx.set_timing(False)
+            rt.ctx.set_pipeline(not args.no_pipeline)
+            rt.Sync()
+            # the shader clock UNDER THIS LOAD: a one-wave probe (s_memtime against the constant 100 MHz s_memrealtime) on a stream of
+            # its own while the headline steps run again exactly as they were timed; the clock moves between 2.0 and 2.4 GHz with the
+            # power the kernel draws, and the issue-rate peaks of the roofline move with it
+            clock_steps = max(2, min(10, args.steps))
+            span_us = int(0.8 * clock_steps * elapsed / args.steps * 1e6)
+            if span_us >= 1:
+                for _ in range(2):
+                    headline()
+                rt.ctx.clock_probe_start(min(span_us, 1000000))
+                for _ in range(clock_steps):
+                    headline()
+                sync_all()
+                clock_mhz = rt.ctx.clock_probe_read()
     else:
-        # strong: BASELINE configs[3]
-        rt.SetRayRange(rank, world)
-        rt.set_reduce_over_comm(native_comm)
-        el_s = timed(step_batched, args.warmup, args.steps)
-        dose_s = rt.read_dosage()
-        strong = {"value": round(rays_per_step * args.steps / el_s / 1e6, 2), "unit": "Mray/s",
-                  "ms_per_step": round(el_s / args.steps * 1e3, 4), "rays_per_step": rays_per_step, "scaling": "strong",
-                  "parallelism": "ray-range-sharded x%d, one int32 all-reduce of the count planes per computation (%s)"
-                                 % (world, "native RCCL, uvrt_reduce_batch" if native_comm else
-                                    "REHEARSAL: ranks share a GPU, gloo" if rehearsal else comm_note),
-                  "dose_crc32": crc(dose_s)}
+        # strong: BASELINE configs[3]; the scaling that is not the headline runs with --full only
+        if args.full or args.scaling == "strong":
+            rt.SetRayRange(rank, world)
+            rt.set_reduce_over_comm(native_comm)
+            el_s = timed(step_batched, args.warmup, args.steps)
+            if args.scaling == "strong":
+                outputs = read_outputs() if args.dump_outputs else None
+            dose_s = rt.read_dosage()
+            strong = {"value": round(rays_per_step * args.steps / el_s / 1e6, 2), "unit": "Mray/s",
+                      "ms_per_step": round(el_s / args.steps * 1e3, 4), "rays_per_step": rays_per_step, "scaling": "strong",
+                      "parallelism": "ray-range-sharded x%d, one int32 all-reduce of the count planes per computation (%s)"
+                                     % (world, "native RCCL, uvrt_reduce_batch" if native_comm else
+                                        "REHEARSAL: ranks share a GPU, gloo" if rehearsal else comm_note),
+                      "dose_crc32": crc(dose_s)}
         # weak: configs[4], same run
-        rt.SetRayRange(0, 1)
-        rt.set_reduce_over_comm(False)
-        rt.maxIterations = args.waves * world
-        reducer[0] = sharding.MapReducer(rt.ctx, device)
-        el_w = timed(step_weak, args.warmup, args.steps)
-        dose_w = rt.read_dosage()
-        weak = {"value": round(args.waves * world * n_launch * args.steps / el_w / 1e6, 2), "unit": "Mray/s",
-                "ms_per_step": round(el_w / args.steps * 1e3, 4), "rays_per_step": args.waves * world * n_launch,
-                "scaling": "weak", "parallelism": "launch-sharded x%d, one f64 SUM + MAX all-reduce of the maps" % world,
-                "dose_crc32": crc(dose_w)}
+        if args.full or args.scaling == "weak":
+            rt.SetRayRange(0, 1)
+            rt.set_reduce_over_comm(False)
+            rt.maxIterations = args.waves * world
+            reducer[0] = sharding.MapReducer(rt.ctx, device)
+            el_w = timed(step_weak, args.warmup, args.steps)
+            if args.scaling == "weak":
+                outputs = read_outputs() if args.dump_outputs else None
+            dose_w = rt.read_dosage()
+            weak = {"value": round(args.waves * world * n_launch * args.steps / el_w / 1e6, 2), "unit": "Mray/s",
+                    "ms_per_step": round(el_w / args.steps * 1e3, 4), "rays_per_step": args.waves * world * n_launch,
+                    "scaling": "weak", "parallelism": "launch-sharded x%d, one f64 SUM + MAX all-reduce of the maps" % world,
+                    "dose_crc32": crc(dose_w)}
         if args.scaling == "weak":
             elapsed, dose_timed, rays_per_step = el_w, dose_w, args.waves * world * n_launch
         else:
@@ -824,7 +868,7 @@ def main():
                                   ("flavour%d" % args.flavour) if args.seed_mode == 0 else "-")
         if args.route and args.seed_mode == 0:
             expected = golden.get("route_flavour%d" % args.flavour)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             orc = g.load_oracle()
             if oscene is None:
                 oscene = orc.Scene(glb)
@@ -844,7 +888,7 @@ def main():
                                   "against the committed oracle CRC instead")
         if expected is not None and crc_timed != expected:
             raise SystemExit("bench: dose CRC %s of the timed region differs from the committed %s" % (crc_timed, expected))
-        if census is None and os.path.exists(census_path()) and default_config:
+        if args.full and census is None and os.path.exists(census_path()) and default_config:
             census = json.load(open(census_path()))["per_launch_avg"]
         kernel_name = "k_extend6<2, false, true, %d>" % args.flavour
         roof = None
@@ -948,7 +992,8 @@ def main():
                                    if args.mode == "batched" else "the reference's host loop (myapp.cpp:156-165)"),
                        "launch_pipelining": bool(not args.no_pipeline), "flavour": args.flavour, "seed_mode": args.seed_mode,
                        "wide_bvh": bool(args.wide), "parallelism": par,
-                       "self_comm": bool(args.self_comm), "high_priority_stream": bool(args.high_priority_stream)},
+                       "self_comm": bool(args.self_comm), "high_priority_stream": bool(args.high_priority_stream),
+                       "full": bool(args.full)},
             # who reduced the count planes, and what RCCL itself says the communicator spans (ncclCommCount)
             "comm": ("native" if (native_comm or (args.self_comm and not self_torch)) else "torch" if torch_reduce else
                      "REHEARSAL (gloo; ranks share a GPU)" if rehearsal else None),
@@ -974,6 +1019,8 @@ def main():
             out["multi_gpu_check"] = {"dose_identical_on_all_ranks": ranks_agree, "photons_traced": rays_per_step}
             out["strong"] = strong
             out["weak"] = weak
+        if outputs is not None:
+            write_outputs(outputs, args.dump_outputs)
         print(json.dumps(out), flush=True)
     if world > 1:
         with Watchdog("final barrier"):

@@ -120,6 +120,28 @@ def test_bench_gpus_n_without_a_launcher_starts_children_and_reports_their_failu
     assert "exited non-zero" in out.stderr or out.stderr.count("needs a GPU") == 2
 
 
+def test_dumped_outputs_stay_under_the_limit_with_one_sample_for_every_array(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole; beyond the limit every array keeps the same fixed, sorted
+    sample of triangles, and the files stay under the limit."""
+    import numpy as np
+    import bench
+    T = 5000
+    outputs = {"dose": np.arange(T, dtype=np.float32), "color": np.repeat(np.arange(T, dtype=np.float32), 9).reshape(T, 9),
+               "photon_map": np.arange(T, dtype=np.float64)}
+    bench.write_outputs(outputs, str(tmp_path / "whole"))
+    for n, a in outputs.items():
+        assert np.array_equal(np.load(tmp_path / "whole" / (n + ".npy")), a)
+    limit = (1 << 16) + 1000 * 48
+    for tag in ("s1", "s2"):
+        bench.write_outputs(outputs, str(tmp_path / tag), limit=limit)
+    rows = np.load(tmp_path / "s1" / "dose.npy")
+    assert len(rows) == 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "photon_map.npy"), rows.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "s1" / "color.npy")[:, 4], rows)
+    assert np.array_equal(np.load(tmp_path / "s2" / "dose.npy"), rows)
+    assert sum(os.path.getsize(tmp_path / "s1" / (n + ".npy")) for n in outputs) <= limit
+
+
 def test_watchdog_ends_a_rank_that_waits_for_the_others_too_long():
     import subprocess
     import sys

@@ -29,7 +29,7 @@ def bench(args, ranks=1, port=29530):
 
 
 def test_two_rank_rehearsal_matches_single_rank():
-    common = ["--photons", "300000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--photons", "300000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"]
     one = bench(common + ["--waves", "6"])
     two = bench(common + ["--waves", "6"], ranks=2, port=29531)        # strong headline; weak: 2 ranks x 6 waves
     three = bench(common + ["--waves", "6", "--scaling", "weak"], ranks=3, port=29532)
@@ -58,7 +58,7 @@ def test_bench_starts_its_own_ranks_and_labels_the_rehearsal():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5"] + common,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--full"] + common,
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

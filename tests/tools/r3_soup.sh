@@ -5,8 +5,8 @@
 OUT=gpurun_out/${1:-r3d}
 T=${2:-300000}; STEPS=${3:-5}; WARM=${4:-2}
 mkdir -p $OUT
-timeout -k 10 600 python3 bench.py --scene soup:$T --steps $STEPS --warmup $WARM > $OUT/soup${T}_batched.json 2> $OUT/soup${T}_batched.err || { echo "soup $T batched failed"; tail -3 $OUT/soup${T}_batched.err; }
-timeout -k 10 600 python3 bench.py --scene soup:$T --mode loop --wide --steps $STEPS --warmup $WARM --no-cpu-baseline --lean > $OUT/soup${T}_wide_loop.json 2> $OUT/soup${T}_wide_loop.err || { echo "soup $T wide failed"; tail -3 $OUT/soup${T}_wide_loop.err; }
+timeout -k 10 600 python3 bench.py --full --scene soup:$T --steps $STEPS --warmup $WARM > $OUT/soup${T}_batched.json 2> $OUT/soup${T}_batched.err || { echo "soup $T batched failed"; tail -3 $OUT/soup${T}_batched.err; }
+timeout -k 10 600 python3 bench.py --full --scene soup:$T --mode loop --wide --steps $STEPS --warmup $WARM --no-cpu-baseline --lean > $OUT/soup${T}_wide_loop.json 2> $OUT/soup${T}_wide_loop.err || { echo "soup $T wide failed"; tail -3 $OUT/soup${T}_wide_loop.err; }
 python3 - <<PY
 import json
 for tag in ("batched", "wide_loop"):

@@ -9,5 +9,5 @@ UVRT_FUZZ_CASES=400 timeout -k 10 600 python -m pytest tests/test_gpu_fuzz.py -m
 timeout -k 10 400 python tests/tools/big_parity.py > $OUT/big_parity_flavour0.log 2>&1; echo "big parity fl0 rc=$?"; tail -3 $OUT/big_parity_flavour0.log
 FLAVOUR=2 timeout -k 10 400 python tests/tools/big_parity.py > $OUT/big_parity_flavour2.log 2>&1; echo "big parity fl2 rc=$?"; tail -3 $OUT/big_parity_flavour2.log
 python3 bench.py --steps 20 --warmup 5 --flavour 1 --seed-mode 1 --no-cpu-baseline --lean > $OUT/bench_reference_semantics.json 2> $OUT/bench_reference_semantics.err || echo "bench flavour 1 / seed mode 1 failed"
-python3 bench.py > $OUT/bench_noflags.json 2> $OUT/bench_noflags.err || echo "bench (no flags) failed"
+python3 bench.py --full > $OUT/bench_noflags.json 2> $OUT/bench_noflags.err || echo "bench (no flags) failed"
 cut -c1-160 $OUT/bench_noflags.json

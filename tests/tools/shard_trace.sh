@@ -10,7 +10,7 @@ for tag in default prio; do
   extra=""; [ $tag = prio ] && extra="--high-priority-stream"
   timeout -k 10 300 python3 bench.py --photons 259200 --steps 40 --warmup 5 --no-cpu-baseline --lean --self-comm $extra > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err || echo "bench $tag failed"
   timeout -k 10 300 python3 bench.py --photons 259200 --steps 40 --warmup 5 --no-cpu-baseline --lean $extra > $OUT/bench_${tag}_nocomm.json 2> $OUT/bench_${tag}_nocomm.err || echo "bench $tag nocomm failed"
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$tag -- python3 $REPO/bench.py --photons 259200 --steps 20 --warmup 5 --no-cpu-baseline --lean --self-comm $extra > $OUT/trace_$tag.log 2>&1) || echo "trace $tag failed"
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$tag -- python3 $REPO/bench.py --full --photons 259200 --steps 20 --warmup 5 --no-cpu-baseline --lean --self-comm $extra > $OUT/trace_$tag.log 2>&1) || echo "trace $tag failed"
   f=$(ls $OUT/trace_$tag/*/*kernel_trace.csv 2>/dev/null | head -1)
   [ -n "$f" ] && python3 tests/tools/trace_union.py $f 20 5 $OUT/union_$tag.txt && cat $OUT/union_$tag.txt
   [ -n "$f" ] && python3 - $f > $OUT/timeline_$tag.txt <<'PY'
