@@ -181,6 +181,65 @@ int uvrt_comm_info(uvrt_ctx* ctx, int32_t out4[4]);
 int uvrt_reduce_batch(uvrt_ctx* ctx);
 int uvrt_reduce_batch_group(uvrt_ctx** ctxs, int32_t n);
 
+/* ---- duration planning: the least total exposure that reaches a minimum dose ----
+ * The dose is linear in the lamp durations and the photon counts do not depend on them.  A planning computation
+ * traces I iterations over P candidate positions and captures, per position p and triangle t, the photons of p that
+ * hit t summed over the iterations: E[p][t] (exact uint32).  With N = I x photonsPerLight, s = lightIntensity x 0.1f
+ * and den_t = area_t x (float)N (f32, as computeDosage forms it), the model dose is
+ *     D_t(d) = s x sum_p E[p][t] x d_p / den_t        (f64)
+ * and uvrt_plan_solve finds durations d >= 0 of least sum with D_t(d) >= min_dose x (1 + margin) on every REQUIRED
+ * triangle: one that passes the caller's mask and has sum_p E[p][t] >= min_photons (> 0).  Rows it leaves out are
+ * reported as unreachable (no photon; or zero area), unresolved (0 < photons < min_photons) and masked out.  The solver
+ * works by cutting planes: the GPU evaluates every row under the current durations, the host picks the most violated
+ * rows from those values and the GPU gathers them; the host solves the LP restricted to the rows gathered so far (a
+ * warm-started simplex) and repeats until the certified gap is <= rel_gap or the round cap is reached.  The durations it
+ * returns are feasible in f64 after their rounding to f32 (and print back to themselves as "%.8g"), and a dual vector
+ * y >= 0 certifies LB = sum_t y_t / max_p (A^T y)_p <= OPT.  Calling sequence: uvrt_plan_begin -> per batch uvrt_trace_batch
+ * (-> uvrt_reduce_batch*) -> uvrt_plan_capture_batch -> uvrt_replay_batch -> ... -> uvrt_plan_solve.
+ * uvrt_set_scene drops the planning state. */
+enum { UVRT_PLAN_CONVERGED = 0, UVRT_PLAN_ITERATION_CAP = 1 };
+typedef struct {
+    float min_dose;                 /* m, mJ/cm^2 (the route's minimale_dosis); <= 0: every duration 0 */
+    float scaled_power;             /* s = lightIntensity * 0.1f (Shade's factor) */
+    int64_t photons_per_position;   /* N = iterations * photonsPerLight, Shade's divisor; <= 2^32 - 1 */
+    int32_t min_photons;            /* a triangle with fewer captured photons is "unresolved", not required */
+    int32_t max_iterations;         /* cap on the cutting-plane rounds (<= 0: 200) */
+    double margin;                  /* relative safety factor on m (1e-6 by default) */
+    double rel_gap;                 /* stop at (sum d - LB) / sum d <= rel_gap */
+    const uint8_t* mask;            /* uint8[T], 0 = not required; NULL: every triangle may be */
+    int32_t reserved[2];            /* 0 */
+} uvrt_plan_params;
+typedef struct {
+    int32_t status;                 /* UVRT_PLAN_CONVERGED (gap <= rel_gap) or UVRT_PLAN_ITERATION_CAP (still feasible) */
+    int32_t iterations;             /* cutting-plane rounds */
+    int32_t positions;              /* P */
+    int32_t used_positions;         /* durations > 0 */
+    int32_t required, unreachable, unresolved, masked_out;     /* triangle counts */
+    double area_required, area_unreachable, area_unresolved, area_masked_out;
+    double total_duration;          /* sum d (f64 over the f32 durations) */
+    double lower_bound;             /* LB <= OPT <= total_duration */
+    double gap;                     /* (total_duration - LB) / total_duration (0 when both are 0) */
+    double min_dose_ratio;          /* min over the required triangles of D_t(d) / m (+inf for an empty set) */
+} uvrt_plan_report;
+/* allocate and zero E for P in [1, 256] positions (P x T < 2^32); drops an earlier plan.  E (P x T x 4 bytes) stays
+ * allocated until uvrt_plan_end, uvrt_set_scene or uvrt_destroy. */
+int uvrt_plan_begin(uvrt_ctx* ctx, int32_t positions);
+/* add the count planes of the traced batch to E: launch k (logical order) goes to row position_of_launch[k].  Folds the
+ * batch first if needed; call it after uvrt_trace_batch (and any uvrt_reduce_batch*: it then captures the global counts)
+ * and before uvrt_replay_batch, which computes exactly what it would have without the capture. */
+int uvrt_plan_capture_batch(uvrt_ctx* ctx, const int32_t* position_of_launch, int32_t count);
+/* solve; durations_out: float[P]; synchronises.  UVRT_ERR_INVALID also when a captured count overflowed uint32. */
+int uvrt_plan_solve(uvrt_ctx* ctx, const uvrt_plan_params* params, float* durations_out, uvrt_plan_report* report);
+/* D_t(d) as f32 for any durations float[P], with s and N of the last uvrt_plan_solve; synchronises */
+int uvrt_plan_model_dose(uvrt_ctx* ctx, const float* durations, float* out, int32_t first, int32_t count);
+/* test hooks: row `position` of E; the required set of the last solve (1 = required); both synchronise */
+int uvrt_plan_read_exposure(uvrt_ctx* ctx, int32_t position, uint32_t* out, int32_t first, int32_t count);
+int uvrt_plan_read_required(uvrt_ctx* ctx, uint8_t* out, int32_t first, int32_t count);
+int uvrt_plan_end(uvrt_ctx* ctx);
+/* the smallest float >= v that "%.8g" (SaveRoute) prints back to itself through strtof (LoadRoute): how the solver rounds
+ * the durations it returns.  Host only, no GPU needed. */
+float uvrt_plan_round_trip_up(float v);
+
 /* ---- tuning knobs (results never depend on them) ---- */
 /* bits of the ray-coherence key used to order rays before extend; 0 = trace in gid order
  * (default), -1 = choose from n (about one wavefront of rays per key). */

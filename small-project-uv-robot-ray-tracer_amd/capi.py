@@ -81,7 +81,43 @@ SYMBOLS = [
     ("uvrt_clock_probe_read", C.c_int, [_vp, C.POINTER(C.c_double)]),
     ("uvrt_device_cus", C.c_int, [_vp]),
     ("uvrt_device_count", C.c_int, []),
+    ("uvrt_plan_begin", C.c_int, [_vp, _i32]),
+    ("uvrt_plan_capture_batch", C.c_int, [_vp, _vp, _i32]),
+    ("uvrt_plan_solve", C.c_int, [_vp, _vp, _vp, _vp]),
+    ("uvrt_plan_model_dose", C.c_int, [_vp, _vp, _vp, _i32, _i32]),
+    ("uvrt_plan_read_exposure", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_plan_read_required", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_plan_end", C.c_int, [_vp]),
+    ("uvrt_plan_round_trip_up", _f32, [_f32]),
 ]
+
+PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
+
+
+class PlanParams(C.Structure):
+    """uvrt_plan_params (include/uvrt.h)"""
+    _fields_ = [("min_dose", C.c_float), ("scaled_power", C.c_float), ("photons_per_position", C.c_int64),
+                ("min_photons", C.c_int32), ("max_iterations", C.c_int32), ("margin", C.c_double),
+                ("rel_gap", C.c_double), ("mask", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class PlanReport(C.Structure):
+    """uvrt_plan_report (include/uvrt.h)"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("positions", C.c_int32), ("used_positions", C.c_int32),
+                ("required", C.c_int32), ("unreachable", C.c_int32), ("unresolved", C.c_int32), ("masked_out", C.c_int32),
+                ("area_required", C.c_double), ("area_unreachable", C.c_double), ("area_unresolved", C.c_double),
+                ("area_masked_out", C.c_double), ("total_duration", C.c_double), ("lower_bound", C.c_double),
+                ("gap", C.c_double), ("min_dose_ratio", C.c_double)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["converged"] = d["status"] == PLAN_CONVERGED
+        return d
+
+
+def round_trip_up(v):
+    """the smallest float32 >= v that "%.8g" prints back to itself (how the planner rounds durations)"""
+    return np.float32(lib().uvrt_plan_round_trip_up(float(np.float32(v))))
 
 # uvrt_replay_op (include/uvrt.h)
 REPLAY_OP_DT = np.dtype([("duration", "<f4"), ("shade", "<i4"), ("which_map", "<i4"), ("photons_per_light", "<i4"),
@@ -370,6 +406,62 @@ class Ctx:
 
     def device_cus(self):
         return int(self._L.uvrt_device_cus(self._h))
+
+    # ---- duration planning ----
+    def plan_begin(self, positions):
+        self._ck(self._L.uvrt_plan_begin(self._h, int(positions)))
+        self._plan_p = int(positions)
+
+    def plan_capture_batch(self, positions_of_launches):
+        pos = np.ascontiguousarray(positions_of_launches, dtype=np.int32)
+        self._ck(self._L.uvrt_plan_capture_batch(self._h, _ptr(pos), pos.size))
+
+    def plan_solve(self, min_dose, scaled_power, photons_per_position, min_photons=16, margin=1e-6, rel_gap=1e-3,
+                   max_iterations=200, mask=None, positions=None):
+        """(durations float32[P], report dict); `positions` = P of uvrt_plan_begin (the output size)"""
+        prm = PlanParams()
+        prm.min_dose = float(np.float32(min_dose))
+        prm.scaled_power = float(np.float32(scaled_power))
+        prm.photons_per_position = int(photons_per_position)
+        prm.min_photons = int(min_photons)
+        prm.max_iterations = int(max_iterations)
+        prm.margin = float(margin)
+        prm.rel_gap = float(rel_gap)
+        keep = None
+        if mask is not None:
+            keep = np.ascontiguousarray(mask, dtype=np.uint8)
+            assert keep.size == self.T
+            prm.mask = keep.ctypes.data
+        if positions is None:
+            positions = getattr(self, "_plan_p", None)
+            if positions is None:
+                raise ValueError("plan_solve: give `positions` (P of uvrt_plan_begin) for a context this object did not begin")
+        out = np.zeros(int(positions), dtype=np.float32)
+        rep = PlanReport()
+        self._ck(self._L.uvrt_plan_solve(self._h, C.byref(prm), _ptr(out), C.byref(rep)))
+        return out, rep.as_dict()
+
+    def plan_model_dose(self, durations, first=0, count=None):
+        d = np.ascontiguousarray(durations, dtype=np.float32)
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float32)
+        self._ck(self._L.uvrt_plan_model_dose(self._h, _ptr(d), _ptr(out), int(first), int(count)))
+        return out
+
+    def plan_read_exposure(self, position, first=0, count=None):
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.uint32)
+        self._ck(self._L.uvrt_plan_read_exposure(self._h, int(position), _ptr(out), int(first), int(count)))
+        return out
+
+    def plan_read_required(self, first=0, count=None):
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.uint8)
+        self._ck(self._L.uvrt_plan_read_required(self._h, _ptr(out), int(first), int(count)))
+        return out.astype(bool)
+
+    def plan_end(self):
+        self._ck(self._L.uvrt_plan_end(self._h))
 
     def device_ptr(self, which):
         p, b = C.c_void_p(), C.c_int64()

@@ -136,6 +136,7 @@ void uvrt_destroy(uvrt_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     if (c->comm) uvrt_comm_destroy(c);       // first: it restores the lanes' plain streams
+    plan_drop(c);
     for (int l = 0; l < uvrt_ctx::MAXL; ++l) {
         if (c->side[l]) (void)hipStreamSynchronize(c->side[l]);
         for (DevBuf* b : {&c->xrays[l], &c->xrecs[l], &c->xcounts[l], &c->xovf[l]}) b->release();
@@ -391,6 +392,7 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     c->scene_force_exact = tiny_bound || huge_vertex;
     if ((rc = hot_reset(c, true))) return rc;         // statistics of the previous scene; the new scene's first slab
     HIP_TRY(hipStreamSynchronize(c->stream));
+    plan_drop(c);                                     // E is per scene
     // a batch of the previous scene is void; its buffers are sized per scene
     c->b_count = 0;
     c->b_is_folded = false;

@@ -203,6 +203,9 @@ struct uvrt_ctx {
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
+
+    // Duration planning (uvrt_plan.hip): exposure matrix, solver buffers; null when no plan is active
+    struct PlanState* plan = nullptr;
 };
 
 namespace uvrt_impl {
@@ -384,6 +387,8 @@ inline uint64_t perm_generation(const uvrt_ctx* c, const uint32_t* perm)
 }
 // drops every cached renumbering (a new scene); with `slab`, the first slab of the new scene is allocated at once
 int hot_reset(uvrt_ctx* c, bool slab);
+// frees the duration-planning state (a new scene, uvrt_plan_end, uvrt_destroy)  (uvrt_plan.hip)
+void plan_drop(uvrt_ctx* c);
 // (re)creates the side lanes' streams with `reserve` CUs masked out, one per XCD and mask word of 8 (0: plain streams)
 int set_lane_cu_mask(uvrt_ctx* c, int reserve);
 // the scene part of an ExtendParams

@@ -1,0 +1,591 @@
+// uvrt_plan.hip -- duration planning (include/uvrt.h "duration planning"): capture of the per-position exposure
+// E[p][t] from the folded planes of traced batches, the covering LP over it and its f64 repair and certificate.
+//
+// The LP in row-normalised form: A[i][p] = E[p][t_i] * r_i with r_i = s / (den_t * m') over the required rows t_i,
+//     minimise 1.d  subject to  A d >= 1, d >= 0.
+// It has few columns (P <= 256 positions) and many rows (every required triangle), and only about P rows are tight at
+// the optimum.  Solver: cutting planes.  The GPU evaluates A_i d for every row in f64 (k_plan_rowcheck); the host reads
+// the values back and picks the most violated rows, which the GPU gathers (k_plan_gather); the host solves the LP
+// restricted to the rows gathered so far (uvrt_plan_lp.h: warm-started simplex on its dual) and repeats until the
+// certified gap is <= rel_gap or a cap is reached.  The restricted dual y (zero on the other rows) is feasible for the
+// full dual once divided by max_p (A^T y)_p, so LB = sum y / max_p (A^T y)_p is a certified lower bound at every round.
+// Every result is bit-reproducible: no float atomics, fixed reduction orders, no dependence on the CU count.
+#include "uvrt_ctx.h"
+#include "uvrt_plan_lp.h"
+
+#include <algorithm>
+#include <limits>
+
+using namespace uvrt;
+using namespace uvrt_impl;
+
+namespace {
+
+constexpr int PLAN_MAX_P = 256;      // positions (uvrt_plan_begin; LDS copy of the durations in the row kernels): the
+                                     // restricted simplex is measured to solve within a second up to here
+
+struct CaptureParams {
+    uint32_t* E;
+    uint32_t* overflow;      // raised when a sum leaves uint32 (the global counts of a reduced batch included)
+    const int32_t* folded;
+    int32_t T, count;
+    int32_t row[MAX_BATCH], plane[MAX_BATCH];
+};
+
+// E[row_k][t] += folded plane of launch k (planes in physical order; several launches may share a row)
+__global__ __launch_bounds__(256) void k_plan_capture(CaptureParams p)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.T) return;
+    for (int k = 0; k < p.count; ++k) {
+        const int32_t v = p.folded[(int64_t)p.plane[k] * p.T + t];
+        uint32_t* e = p.E + (int64_t)p.row[k] * p.T + t;
+        const uint64_t sum = (uint64_t)*e + (uint32_t)v;
+        if (sum > 0xFFFFFFFFull) atomicOr(p.overflow, 1u);
+        *e = (uint32_t)sum;
+    }
+}
+
+// class of every triangle (0 required, 1 unreachable, 2 unresolved, 3 masked out), per block: counts and areas per class
+__global__ __launch_bounds__(256) void k_plan_classify(const uint32_t* __restrict__ E, int32_t P, int32_t T,
+                                                      const uint8_t* __restrict__ mask, const float* __restrict__ area,
+                                                      uint32_t min_photons, uint8_t* __restrict__ cls,
+                                                      int32_t* __restrict__ blk_cnt, double* __restrict__ blk_area)
+{
+    __shared__ int32_t s_cnt[4][4];
+    __shared__ double s_area[256];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int k = -1;
+    double a = 0;
+    if (t < T) {
+        uint64_t sum = 0;
+        for (int p = 0; p < P; ++p) sum += E[(int64_t)p * T + t];
+        const float at = area[t];
+        a = at;
+        if (mask && !mask[t]) k = 3;
+        else if (sum == 0 || !(at > 0.0f)) k = 1;      // no photon (or no area: no dose is defined)
+        else if (sum < min_photons) k = 2;
+        else k = 0;
+        cls[t] = (uint8_t)k;
+    }
+    for (int q = 0; q < 4; ++q) {
+        const uint64_t b = __builtin_amdgcn_ballot_w64(k == q);
+        if (lane == 0) s_cnt[w][q] = __popcll(b);
+    }
+    for (int q = 0; q < 4; ++q) {
+        s_area[threadIdx.x] = k == q ? a : 0.0;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) s_area[threadIdx.x] += s_area[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            blk_area[blockIdx.x * 4 + q] = s_area[0];
+            blk_cnt[blockIdx.x * 4 + q] = s_cnt[0][q] + s_cnt[1][q] + s_cnt[2][q] + s_cnt[3][q];
+        }
+        __syncthreads();
+    }
+}
+
+// the required rows in ascending triangle order (ballot + block offsets) and their scale r
+__global__ __launch_bounds__(256) void k_plan_compact(const uint32_t* __restrict__ E, int32_t P, int32_t T,
+                                                     const uint8_t* __restrict__ cls, const float* __restrict__ area,
+                                                     const int32_t* __restrict__ blk_off, float s, float Nf, double mprime,
+                                                     int32_t* __restrict__ rows, double* __restrict__ rd)
+{
+    __shared__ int32_t s_w[4];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const bool req = t < T && cls[t] == 0;
+    const uint64_t b = __builtin_amdgcn_ballot_w64(req);
+    if (lane == 0) s_w[w] = __popcll(b);
+    __syncthreads();
+    if (!req) return;
+    int off = blk_off[blockIdx.x];
+    for (int j = 0; j < w; ++j) off += s_w[j];
+    off += __popcll(b & ((1ull << lane) - 1ull));
+    const float den = area[t] * Nf;                               // computeDosage's f32 denominator
+    const double r = (double)s / ((double)den * mprime);
+    rows[off] = t;
+    rd[off] = r;
+}
+
+// row j of the gathered block: A[sel_j][p] = E[p][rows[sel_j]] * r_{sel_j} in f64
+__global__ __launch_bounds__(256) void k_plan_gather(const uint32_t* __restrict__ E, int32_t T, int32_t P,
+                                                    const int32_t* __restrict__ rows, const double* __restrict__ rd,
+                                                    const int64_t* __restrict__ sel, int32_t nsel, double* __restrict__ out)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= (int64_t)nsel * P) return;
+    const int64_t j = k / P, p = k % P, i = sel[j];
+    out[k] = (double)E[p * T + rows[i]] * rd[i];
+}
+
+// f64 check of durations d over the required rows: per block min_i A_i d (and A_i d per row); rows with A_i d = 0 raise
+// their best position (most photons, lowest index) to what covers the row alone (integer max of positive f64 bits:
+// order independent)
+__global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restrict__ E, int32_t T, int32_t P, int64_t NR,
+                                                      const int32_t* __restrict__ rows, const double* __restrict__ rd,
+                                                      const double* __restrict__ d, double* __restrict__ blk_min,
+                                                      unsigned long long* __restrict__ raise, int32_t* __restrict__ zero_rows,
+                                                      double* __restrict__ ratio)
+{
+    __shared__ double s_d[PLAN_MAX_P];
+    __shared__ double s_min[256];
+    for (int j = threadIdx.x; j < P; j += 256) s_d[j] = d[j];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double mn = std::numeric_limits<double>::infinity();
+    if (i < NR) {
+        const int64_t t = rows[i];
+        double ad = 0.0;
+        uint32_t best = 0;
+        int bp = 0;
+        for (int q = 0; q < P; ++q) {
+            const uint32_t e = E[(int64_t)q * T + t];
+            ad += (double)e * s_d[q];
+            if (e > best) { best = e; bp = q; }
+        }
+        ad *= rd[i];
+        mn = ad;
+        if (ratio) ratio[i] = ad;
+        if (ad == 0.0 && raise) {
+            const double need = 1.0 / ((double)best * rd[i]);
+            atomicMax(&raise[bp], (unsigned long long)__double_as_longlong(need));
+            atomicAdd(zero_rows, 1);
+        }
+    }
+    s_min[threadIdx.x] = mn;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_min[threadIdx.x] = fmin(s_min[threadIdx.x], s_min[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) blk_min[blockIdx.x] = s_min[0];
+}
+
+// D_t(d) = (float)(s * sum_p E[p][t] d_p / den_t), f64 sum in position order, computeDosage's f32 denominator
+__global__ __launch_bounds__(256) void k_plan_model_dose(const uint32_t* __restrict__ E, int32_t T, int32_t P,
+                                                        const double* __restrict__ d, const float* __restrict__ area,
+                                                        float Nf, float s, float* __restrict__ out, int32_t first, int32_t count)
+{
+    __shared__ double s_d[PLAN_MAX_P];
+    for (int j = threadIdx.x; j < P; j += 256) s_d[j] = d[j];
+    __syncthreads();
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    const int64_t t = (int64_t)first + j;
+    double acc = 0.0;
+    for (int q = 0; q < P; ++q) acc += (double)E[(int64_t)q * T + t] * s_d[q];
+    const double num = (double)s * acc;
+    const float den = area[t] * Nf;
+    out[j] = (float)(num / (double)den);
+}
+
+inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+}  // namespace
+
+struct PlanState {
+    int32_t P = 0;
+    DevBuf E;
+    std::vector<uint64_t> rays;          // rays of this context's launches captured per position (uint32 overflow guard)
+    int64_t captures = 0;
+    bool solved = false;
+    float s = 0, Nf = 0;                 // of the last solve (uvrt_plan_model_dose)
+    DevBuf overflow;                     // uint32 flag of k_plan_capture
+    DevBuf cls, mask, blk_cnt, blk_area, blk_off, rows, rd, dd, blk_min, raise, zrows, outf, ratio, sel, gath;
+    void release()
+    {
+        for (DevBuf* b : {&E, &overflow, &cls, &mask, &blk_cnt, &blk_area, &blk_off, &rows, &rd, &dd, &blk_min, &raise, &zrows,
+                          &outf, &ratio, &sel, &gath})
+            b->release();
+    }
+};
+
+namespace uvrt_impl {
+void plan_drop(uvrt_ctx* c)
+{
+    if (!c || !c->plan) return;
+    (void)hipStreamSynchronize(c->stream);
+    c->plan->release();
+    delete c->plan;
+    c->plan = nullptr;
+}
+}  // namespace uvrt_impl
+
+namespace {
+
+struct RowCheck { double min_ratio; int32_t zero_rows; };
+
+// k_plan_rowcheck of host durations d64; with `raise` the raise values come back in raise_out, with ratio_out A_i d per row
+int row_check(uvrt_ctx* c, PlanState& S, int64_t NR, const std::vector<double>& d64, bool raise,
+              RowCheck* out, std::vector<double>* raise_out, std::vector<double>* ratio_out = nullptr)
+{
+    const unsigned nbr = nblocks(NR, 256);
+    HIP_TRY(hipMemcpyAsync(S.dd.p, d64.data(), (size_t)S.P * 8, hipMemcpyHostToDevice, c->stream));
+    if (raise) {
+        HIP_TRY(hipMemsetAsync(S.raise.p, 0, (size_t)S.P * 8, c->stream));
+        HIP_TRY(hipMemsetAsync(S.zrows.p, 0, 4, c->stream));
+    }
+    hipLaunchKernelGGL(k_plan_rowcheck, dim3(nbr), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), c->T, S.P, NR,
+                       (const int32_t*)S.rows.as<int32_t>(), (const double*)S.rd.as<double>(), (const double*)S.dd.as<double>(),
+                       S.blk_min.as<double>(), raise ? S.raise.as<unsigned long long>() : nullptr,
+                       S.zrows.as<int32_t>(), ratio_out ? S.ratio.as<double>() : nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> mn(nbr);
+    if (ratio_out) {
+        ratio_out->resize((size_t)NR);
+        HIP_TRY(hipMemcpyAsync(ratio_out->data(), S.ratio.p, (size_t)NR * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(mn.data(), S.blk_min.p, (size_t)nbr * 8, hipMemcpyDeviceToHost, c->stream));
+    int32_t z = 0;
+    std::vector<unsigned long long> rb;
+    if (raise) {
+        rb.resize(S.P);
+        HIP_TRY(hipMemcpyAsync(&z, S.zrows.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(rb.data(), S.raise.p, (size_t)S.P * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->min_ratio = std::numeric_limits<double>::infinity();
+    for (unsigned b = 0; b < nbr; ++b) out->min_ratio = std::min(out->min_ratio, mn[b]);
+    out->zero_rows = z;
+    if (raise_out) {
+        raise_out->assign(S.P, 0.0);
+        for (int p = 0; p < S.P && raise; ++p) { double v; memcpy(&v, &rb[p], 8); (*raise_out)[p] = v; }
+    }
+    return UVRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// smallest float >= v that "%.8g" (SaveRoute) prints back to itself through strtof (LoadRoute's sscanf "%f")
+float uvrt_plan_round_trip_up(float v)
+{
+    if (!std::isfinite(v)) return v;
+    for (int k = 0; k < 256; ++k) {
+        char b[64];
+        snprintf(b, sizeof b, "%.8g", (double)v);
+        if (strtof(b, nullptr) == v) return v;
+        v = nextafterf(v, INFINITY);
+    }
+    return v;
+}
+
+int uvrt_plan_begin(uvrt_ctx* c, int32_t positions)
+{
+    if (!c || !c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_plan_begin: null context or no scene");
+    if (positions < 1 || positions > PLAN_MAX_P)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_begin: positions %d outside [1,%d]", positions, PLAN_MAX_P);
+    if ((uint64_t)positions * (uint64_t)c->T >= ((uint64_t)1 << 32))
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_begin: %d positions x %d triangles exceed 2^32 counters", positions, c->T);
+    if (int rc = set_device(c)) return rc;
+    plan_drop(c);
+    c->plan = new PlanState();
+    c->plan->P = positions;
+    c->plan->rays.assign(positions, 0);
+    if (int rc = c->plan->E.ensure((size_t)positions * (size_t)c->T * 4, true, c->stream)) { plan_drop(c); return rc; }
+    if (int rc = c->plan->overflow.ensure(4, true, c->stream)) { plan_drop(c); return rc; }
+    return UVRT_OK;
+}
+
+int uvrt_plan_end(uvrt_ctx* c)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_plan_end: null context");
+    if (int rc = set_device(c)) return rc;
+    plan_drop(c);
+    return UVRT_OK;
+}
+
+int uvrt_plan_capture_batch(uvrt_ctx* c, const int32_t* pos, int32_t count)
+{
+    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: no plan (uvrt_plan_begin)");
+    if (c->b_count <= 0) return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: no traced batch");
+    if (!pos || count != c->b_count)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: %d positions for a batch of %d launches", count, c->b_count);
+    PlanState& S = *c->plan;
+    std::vector<uint64_t> rays = S.rays;
+    for (int k = 0; k < count; ++k) {
+        if (pos[k] < 0 || pos[k] >= S.P)
+            return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: position %d of launch %d outside [0,%d)", pos[k], k, S.P);
+        rays[pos[k]] += (uint64_t)c->b_n;
+        if (rays[pos[k]] > 0xFFFFFFFFull)
+            return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: the photons of position %d would overflow the uint32 counts", pos[k]);
+        // (this context's rays only: after a reduce the global counts are checked by k_plan_capture itself)
+    }
+    if (int rc = uvrt_fold_batch(c)) return rc;          // set_device + join_all; a no-op after a reduce
+    CaptureParams p;
+    memset(&p, 0, sizeof p);
+    p.E = S.E.as<uint32_t>();
+    p.overflow = S.overflow.as<uint32_t>();
+    p.folded = c->bs[c->b_set].folded.as<int32_t>();
+    p.T = c->T;
+    p.count = count;
+    for (int k = 0; k < count; ++k) { p.row[k] = pos[k]; p.plane[k] = c->b_phys[k]; }
+    hipLaunchKernelGGL(k_plan_capture, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream, p);
+    HIP_TRY(hipGetLastError());
+    S.rays = rays;
+    ++S.captures;
+    return UVRT_OK;
+}
+
+int uvrt_plan_solve(uvrt_ctx* c, const uvrt_plan_params* prm, float* out, uvrt_plan_report* rep)
+{
+    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: no plan (uvrt_plan_begin)");
+    if (c->plan->captures == 0) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: nothing captured (uvrt_plan_capture_batch)");
+    if (!prm || !out || !rep) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: null argument");
+    if (prm->photons_per_position < 1 || prm->photons_per_position > (int64_t)0xFFFFFFFFll)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: %lld photons per position overflow the uint32 counts",
+                    (long long)prm->photons_per_position);
+    if (!(prm->scaled_power > 0.0f) || !std::isfinite(prm->scaled_power) || !std::isfinite(prm->min_dose) ||
+        !(prm->margin >= 0.0) || !(prm->rel_gap > 0.0))
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: scaled_power > 0, finite min_dose, margin >= 0 and rel_gap > 0 required");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    PlanState& S = *c->plan;
+    const int32_t T = c->T, P = S.P;
+    const unsigned nbt = nblocks(T, 256);
+    {
+        uint32_t of = 0;
+        HIP_TRY(hipMemcpyAsync(&of, S.overflow.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (of) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: a captured count overflowed uint32 (over 2^32 - 1 photons of one position)");
+    }
+    int rc;
+    memset(rep, 0, sizeof *rep);
+    rep->positions = P;
+
+    // ---- set-up: classes, exclusion statistics, the required rows
+    if ((rc = S.cls.ensure((size_t)T, false, c->stream))) return rc;
+    if ((rc = S.blk_cnt.ensure((size_t)nbt * 16, false, c->stream))) return rc;
+    if ((rc = S.blk_area.ensure((size_t)nbt * 32, false, c->stream))) return rc;
+    if ((rc = S.blk_off.ensure((size_t)nbt * 4, false, c->stream))) return rc;
+    const uint8_t* dmask = nullptr;
+    if (prm->mask) {
+        if ((rc = S.mask.ensure((size_t)T, false, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.mask.p, prm->mask, (size_t)T, hipMemcpyHostToDevice, c->stream));
+        dmask = S.mask.as<uint8_t>();
+    }
+    const uint32_t min_ph = (uint32_t)std::max(1, prm->min_photons);
+    hipLaunchKernelGGL(k_plan_classify, dim3(nbt), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), P, T, dmask,
+                       (const float*)c->area.as<float>(), min_ph, S.cls.as<uint8_t>(), S.blk_cnt.as<int32_t>(), S.blk_area.as<double>());
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> bc((size_t)nbt * 4), boff(nbt);
+    std::vector<double> ba((size_t)nbt * 4);
+    HIP_TRY(hipMemcpyAsync(bc.data(), S.blk_cnt.p, bc.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(ba.data(), S.blk_area.p, ba.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t cnt[4] = {0, 0, 0, 0};
+    double area[4] = {0, 0, 0, 0};
+    for (unsigned b = 0; b < nbt; ++b) {
+        boff[b] = (int32_t)cnt[0];
+        for (int q = 0; q < 4; ++q) { cnt[q] += bc[b * 4 + q]; area[q] += ba[b * 4 + q]; }
+    }
+    rep->required = (int32_t)cnt[0]; rep->unreachable = (int32_t)cnt[1];
+    rep->unresolved = (int32_t)cnt[2]; rep->masked_out = (int32_t)cnt[3];
+    rep->area_required = area[0]; rep->area_unreachable = area[1];
+    rep->area_unresolved = area[2]; rep->area_masked_out = area[3];
+    const int64_t NR = cnt[0];
+    const double m = prm->min_dose, mprime = m * (1.0 + prm->margin);
+    S.s = prm->scaled_power;
+    S.Nf = (float)prm->photons_per_position;
+    S.solved = true;
+    if (NR == 0 || !(m > 0.0)) {
+        for (int p = 0; p < P; ++p) out[p] = 0.0f;
+        rep->status = UVRT_PLAN_CONVERGED;
+        rep->min_dose_ratio = std::numeric_limits<double>::infinity();
+        return UVRT_OK;
+    }
+    const unsigned nbr = nblocks(NR, 256);
+    if ((rc = S.rows.ensure((size_t)NR * 4, false, c->stream))) return rc;
+    if ((rc = S.rd.ensure((size_t)NR * 8, false, c->stream))) return rc;
+    if ((rc = S.ratio.ensure((size_t)NR * 8, false, c->stream))) return rc;
+    for (DevBuf* b : {&S.dd, &S.raise})
+        if ((rc = b->ensure((size_t)P * 8, false, c->stream))) return rc;
+    if ((rc = S.blk_min.ensure((size_t)nbr * 8, false, c->stream))) return rc;
+    if ((rc = S.zrows.ensure(4, false, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(S.blk_off.p, boff.data(), (size_t)nbt * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_plan_compact, dim3(nbt), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), P, T,
+                       (const uint8_t*)S.cls.as<uint8_t>(), (const float*)c->area.as<float>(), (const int32_t*)S.blk_off.as<int32_t>(),
+                       S.s, S.Nf, mprime, S.rows.as<int32_t>(), S.rd.as<double>());
+    HIP_TRY(hipGetLastError());
+
+    // ---- cutting planes from the uniform plan: rows W gathered so far (AW: |W| x P, f64), exact LP over W, repeat
+    const int max_rounds = prm->max_iterations > 0 ? prm->max_iterations : 200;
+    const int per_round = std::max(64, 2 * P);
+    std::vector<double> d64(P), ratio, AW, best_d;
+    std::vector<int64_t> W;
+    std::vector<uint8_t> inW((size_t)NR, 0);
+    uvrt_plan_lp::RestrictedLP lp(P);
+    int64_t pivots = 0;
+    double best_ub = std::numeric_limits<double>::infinity(), best_lb = 0.0;
+    int it = 0;
+    {
+        std::vector<double> ones(P, 1.0);
+        RowCheck r1;
+        if ((rc = row_check(c, S, NR, ones, false, &r1, nullptr))) return rc;
+        for (int p = 0; p < P; ++p) d64[p] = r1.min_ratio > 0.0 ? 1.0 / r1.min_ratio : 1.0;
+    }
+    for (;;) {
+        RowCheck rck;
+        if ((rc = row_check(c, S, NR, d64, false, &rck, nullptr, &ratio))) return rc;
+        double sd = 0;
+        for (double v : d64) sd += v;
+        if (rck.min_ratio > 0.0 && sd / rck.min_ratio < best_ub) {
+            best_ub = sd / rck.min_ratio;
+            best_d = d64;
+            for (double& v : best_d) v /= rck.min_ratio;
+        }
+        if (std::isfinite(best_ub) && (best_ub - best_lb) <= prm->rel_gap * best_ub) break;
+        if (it >= max_rounds) break;
+        // the most violated rows not yet in W (round 0: the least covered ones under the uniform plan)
+        std::vector<int64_t> cand;
+        for (int64_t i = 0; i < NR; ++i)
+            if (!inW[i] && (it == 0 || ratio[i] < 1.0)) cand.push_back(i);
+        if (cand.empty()) break;          // d covers every row: the restricted optimum is global
+        const size_t take = std::min(cand.size(), (size_t)per_round);
+        std::partial_sort(cand.begin(), cand.begin() + take, cand.end(), [&](int64_t a, int64_t b) {
+            return ratio[a] < ratio[b] || (ratio[a] == ratio[b] && a < b);
+        });
+        cand.resize(take);
+        std::sort(cand.begin(), cand.end());
+        if ((rc = S.sel.ensure(take * 8, false, c->stream))) return rc;
+        if ((rc = S.gath.ensure(take * (size_t)P * 8, false, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.sel.p, cand.data(), take * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_plan_gather, dim3(nblocks((int64_t)take * P, 256)), dim3(256), 0, c->stream,
+                           (const uint32_t*)S.E.as<uint32_t>(), T, P, (const int32_t*)S.rows.as<int32_t>(),
+                           (const double*)S.rd.as<double>(), (const int64_t*)S.sel.as<int64_t>(), (int32_t)take, S.gath.as<double>());
+        HIP_TRY(hipGetLastError());
+        const size_t old = AW.size();
+        AW.resize(old + take * (size_t)P);
+        HIP_TRY(hipMemcpyAsync(AW.data() + old, S.gath.p, take * (size_t)P * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int64_t i : cand) { inW[i] = 1; W.push_back(i); }
+        lp.add_rows(AW.data() + old, (int64_t)take);
+        const bool solved = lp.solve(50 * (lp.rows() + P) + 1000, &pivots);
+        std::vector<double> yW;
+        lp.solution(&yW, &d64);                 // an interrupted solve still leaves a feasible basis: a certificate
+        // certificate of the restricted dual (zero on the rows outside W): LB = sum y / max_p (A^T y)_p, in f64
+        std::vector<double> g(P, 0.0);
+        double sy = 0;
+        for (size_t j = 0; j < W.size(); ++j) {
+            if (yW[j] == 0.0) continue;
+            sy += yW[j];
+            for (int p = 0; p < P; ++p) g[p] += AW[j * P + p] * yW[j];
+        }
+        const double gmax = *std::max_element(g.begin(), g.end());
+        if (gmax > 0.0) best_lb = std::max(best_lb, sy / gmax);
+        ++it;
+        if (!solved) {                          // pivot cap: keep what is certified, report the gap
+            RowCheck rlast;
+            if ((rc = row_check(c, S, NR, d64, false, &rlast, nullptr))) return rc;
+            double sl = 0;
+            for (double v : d64) sl += v;
+            if (rlast.min_ratio > 0.0 && sl / rlast.min_ratio < best_ub) {
+                best_ub = sl / rlast.min_ratio;
+                best_d = d64;
+                for (double& v : best_d) v /= rlast.min_ratio;
+            }
+            break;
+        }
+    }
+
+    // ---- repair (f64): cover rows without coverage by their best position, drop positions the plan does not need, scale
+    if (std::isfinite(best_ub)) d64 = best_d;
+    std::vector<double> dh(P);
+    {
+        double dmax = 0;
+        for (double v : d64) dmax = std::max(dmax, v);
+        for (double& v : d64) if (v <= 1e-7 * dmax) v = 0.0;
+    }
+    RowCheck rck{};
+    std::vector<double> raise;
+    for (int round = 0; round < 4; ++round) {
+        if ((rc = row_check(c, S, NR, d64, true, &rck, &raise))) return rc;
+        if (rck.zero_rows == 0) break;
+        for (int p = 0; p < P; ++p) d64[p] = std::max(d64[p], raise[p]);
+    }
+    if (rck.zero_rows != 0 || !(rck.min_ratio > 0.0)) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: repair left rows uncovered");
+    for (double& v : d64) v /= rck.min_ratio;
+    // f32, rounded up to values that survive SaveRoute / LoadRoute; re-checked in f64
+    std::vector<float> d32(P);
+    for (int round = 0; round < 8; ++round) {
+        for (int p = 0; p < P; ++p) {
+            float f = (float)d64[p];
+            if ((double)f < d64[p]) f = nextafterf(f, INFINITY);
+            d32[p] = d64[p] > 0.0 ? uvrt_plan_round_trip_up(f) : 0.0f;
+            dh[p] = d32[p];
+        }
+        if ((rc = row_check(c, S, NR, dh, false, &rck, nullptr))) return rc;
+        if (rck.min_ratio >= 1.0) break;
+        for (double& v : d64) v *= (1.0 / rck.min_ratio) * (1.0 + 1e-12);
+    }
+    if (!(rck.min_ratio >= 1.0)) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: the f32 durations do not reach the minimum");
+    double total = 0;
+    int used = 0;
+    for (int p = 0; p < P; ++p) { out[p] = d32[p]; total += d32[p]; used += d32[p] > 0.0f; }
+    rep->iterations = it;
+    rep->used_positions = used;
+    rep->total_duration = total;
+    rep->lower_bound = std::min(best_lb, total);
+    rep->gap = total > 0.0 ? (total - rep->lower_bound) / total : 0.0;
+    rep->status = rep->gap <= prm->rel_gap ? UVRT_PLAN_CONVERGED : UVRT_PLAN_ITERATION_CAP;
+    rep->min_dose_ratio = rck.min_ratio * (mprime / m);
+    return UVRT_OK;
+}
+
+int uvrt_plan_model_dose(uvrt_ctx* c, const float* durations, float* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan || !c->plan->solved) return fail(UVRT_ERR_INVALID, "uvrt_plan_model_dose: no solved plan");
+    if (!durations || !out || first < 0 || count < 0 || (int64_t)first + count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_model_dose: bad range");
+    if (count == 0) return UVRT_OK;
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    PlanState& S = *c->plan;
+    int rc;
+    if ((rc = S.dd.ensure((size_t)S.P * 8, false, c->stream))) return rc;
+    if ((rc = S.outf.ensure((size_t)c->T * 4, false, c->stream))) return rc;
+    std::vector<double> d(S.P);
+    for (int p = 0; p < S.P; ++p) d[p] = durations[p];
+    HIP_TRY(hipMemcpyAsync(S.dd.p, d.data(), (size_t)S.P * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_plan_model_dose, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(),
+                       c->T, S.P, (const double*)S.dd.as<double>(), (const float*)c->area.as<float>(), S.Nf, S.s, S.outf.as<float>(),
+                       first, count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, S.outf.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+int uvrt_plan_read_exposure(uvrt_ctx* c, int32_t position, uint32_t* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: no plan");
+    if (position < 0 || position >= c->plan->P)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: position %d outside [0,%d)", position, c->plan->P);
+    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: bad range");
+    if (count == 0) return UVRT_OK;
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->plan->E.as<uint32_t>() + (size_t)position * c->T + first, (size_t)count * 4,
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+int uvrt_plan_read_required(uvrt_ctx* c, uint8_t* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan || !c->plan->solved) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_required: no solved plan");
+    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_required: bad range");
+    if (count == 0) return UVRT_OK;
+    if (int rc = set_device(c)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->plan->cls.as<uint8_t>() + first, (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int32_t i = 0; i < count; ++i) out[i] = out[i] == 0 ? 1 : 0;
+    return UVRT_OK;
+}
+
+}  // extern "C"

@@ -58,6 +58,14 @@ SYMBOLS = [
     ("uvrt_host_rt_lamp_count", C.c_int, [_vp]),
     ("uvrt_host_rt_get_lamp", None, [_vp, C.c_int, C.POINTER(C.c_float)]),
     ("uvrt_host_rt_set_lamps", None, [_vp, C.POINTER(C.c_float), C.c_int]),
+    ("uvrt_host_rt_plan", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp,
+                                 C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
+                                       _vp, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_end_plan", None, [_vp]),
+    ("uvrt_host_rt_set_candidate_grid", None, [_vp, C.c_int, C.c_int, C.c_float]),
+    ("uvrt_host_grid_positions", None, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
+                                        C.POINTER(C.c_float)]),
     ("uvrt_host_rt_get", C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_double)]),
     ("uvrt_host_rt_set", C.c_int, [_vp, C.c_char_p, C.c_double]),
 ]
@@ -220,6 +228,24 @@ class RayTracer:
     def SetRayRange(self, rank, world): self._L.uvrt_host_rt_set_ray_range(self._h, int(rank), int(world))
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
 
+    def PlanDurations(self, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None):
+        """RayTracer::PlanDurations: one batched computation over the current positions from the current SEED with the
+        exposure captured, then the least durations that bring every required triangle to min_dose (default: the
+        route's minDosage).  They are written into the positions; returns (durations float32[P], report dict with
+        the starting "seed")."""
+        rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        self._L.uvrt_host_rt_plan(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons), float(margin),
+                                  float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))
+        return _plan_result(self, rep, seed)
+
+    def EndPlan(self):
+        """release the exposure matrix PlanDurations leaves on the device (model dose / required set read-backs)"""
+        self._L.uvrt_host_rt_end_plan(self._h)
+
+    def SetCandidateGrid(self, nx, nz, inset=0.5):
+        """replace the positions by an nx x nz grid over the mesh's x/z bounds, inset by `inset` metres"""
+        self._L.uvrt_host_rt_set_candidate_grid(self._h, int(nx), int(nz), float(inset))
+
     def lamps(self):
         out = []
         buf = (C.c_float * 3)()
@@ -244,6 +270,44 @@ def compute_iterations_batched_group(rts, iterations):
     """RayTracer::ComputeIterationsBatched over instances that share every launch by ray range (one process)."""
     arr = (C.c_void_p * len(rts))(*[rt._h for rt in rts])
     lib().uvrt_host_rt_compute_batched_group(arr, len(rts), int(iterations))
+
+
+def _mask_arg(mask, T):
+    if mask is None:
+        return None
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    if m.size != T:
+        raise ValueError("mask must have one entry per triangle")
+    return m
+
+
+def _addr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _plan_result(rt, rep, seed):
+    d = rep.as_dict()
+    d["seed"] = int(seed.value)
+    return np.array([l[2] for l in rt.lamps()], dtype=np.float32), d
+
+
+def plan_durations_group(rts, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None):
+    """RayTracer::PlanDurations over instances that share every launch by ray range (one process): every context
+    captures after the group reduce and solves on its own; the durations must agree."""
+    arr = (C.c_void_p * len(rts))(*[rt._h for rt in rts])
+    rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, rts[0].mesh.triangleCount)
+    lib().uvrt_host_rt_plan_group(arr, len(rts), -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                  float(margin), float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))
+    return _plan_result(rts[0], rep, seed)
+
+
+def grid_positions(bounds, nx, nz, inset=0.5):
+    """RayTracer::GridPositions: (x, z) of an nx x nz grid over bounds = (xmin, xmax, zmin, zmax) inset by `inset`,
+    x fastest; float32[nx * nz, 2]"""
+    out = (C.c_float * (2 * nx * nz))()
+    xmin, xmax, zmin, zmax = (float(v) for v in bounds)
+    lib().uvrt_host_grid_positions(xmin, xmax, zmin, zmax, int(nx), int(nz), float(inset), out)
+    return np.frombuffer(out, dtype=np.float32).reshape(nx * nz, 2).copy()
 
 
 class _BorrowedCtx(capi.Ctx):

@@ -111,6 +111,32 @@ void uvrt_host_rt_set_lamps(void* r, const float* xyd, int n)
     rt->UpdatePhotonsPerLight();
 }
 
+// duration planning: durations -> lightPositions, report -> *rep, starting SEED -> *seed
+void uvrt_host_rt_plan(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                       const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
+{
+    RayTracer::PlanOptions o;
+    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
+    o.maxIterations = max_iterations; o.mask = mask;
+    *rep = ((RayTracer*)r)->PlanDurations(o, seed);
+}
+void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
+                             int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
+{
+    std::vector<RayTracer*> g;
+    for (int i = 0; i < n; ++i) g.push_back((RayTracer*)rs[i]);
+    RayTracer::PlanOptions o;
+    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
+    o.maxIterations = max_iterations; o.mask = mask;
+    *rep = RayTracer::PlanDurations(g, o, seed);
+}
+void uvrt_host_rt_end_plan(void* r) { ((RayTracer*)r)->EndPlan(); }
+void uvrt_host_rt_set_candidate_grid(void* r, int nx, int nz, float inset) { ((RayTracer*)r)->SetCandidateGrid(nx, nz, inset); }
+void uvrt_host_grid_positions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz)
+{
+    RayTracer::GridPositions(xmin, xmax, zmin, zmax, nx, nz, inset, xz);
+}
+
 // scalar fields, by name (keeps the ctypes surface small)
 static int field(RayTracer* rt, const char* n, double* v, int set)
 {

@@ -9,6 +9,7 @@
 #include "../../include/uvrt.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -252,10 +253,101 @@ void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, i
         if (group.size() > 1) check(uvrt_reduce_batch_group(ctxs.data(), (int)ctxs.size()), "reduce_batch_group");
         for (RayTracer* rt : group) {
             if (group.size() == 1 && rt->reduceOverComm) check(uvrt_reduce_batch(rt->ctx), "reduce_batch");
+            if (rt->planCapture) {                       // launch j of the batch is position (done + j) % L
+                std::vector<int32_t> pos((size_t)cnt);
+                for (int j = 0; j < cnt; ++j) pos[j] = (int32_t)((done + j) % L);
+                check(uvrt_plan_capture_batch(rt->ctx, pos.data(), cnt), "plan_capture_batch");
+            }
             check(uvrt_replay_batch(rt->ctx, ops.data(), cnt, rt->mesh->triangleCount), "replay_batch");
         }
         done += cnt;
     }
+}
+
+uvrt_plan_report RayTracer::PlanDurations(const PlanOptions& opt, unsigned* seedOut)
+{
+    std::vector<RayTracer*> self{this};
+    return PlanDurations(self, opt, seedOut);
+}
+
+uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut)
+{
+    RayTracer* r0 = group[0];
+    const int L = (int)r0->lightPositions.size();
+    if (L == 0) fatal("PlanDurations: no positions");
+    if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
+        fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
+    uint32_t seed0 = 0;
+    check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
+    for (RayTracer* rt : group) {
+        check(uvrt_plan_begin(rt->ctx, L), "plan_begin");
+        rt->ClearBuffers(true);                              // ResetDosageMap without the route save
+        rt->currIterations = 0;
+        rt->launchIndex = 0;
+        rt->planCapture = true;
+    }
+    ComputeIterationsBatched(group, r0->maxIterations);
+    uvrt_plan_params prm;
+    memset(&prm, 0, sizeof prm);
+    prm.min_dose = opt.minDose >= 0.0f ? opt.minDose : r0->minDosage;
+    prm.scaled_power = r0->lightIntensity * 0.1f;                 // raytracer.cpp:113
+    prm.photons_per_position = (long long)r0->maxIterations * r0->photonsPerLight;   // photonMapSize / L at the end
+    prm.min_photons = opt.minPhotons;
+    prm.max_iterations = opt.maxIterations;
+    prm.margin = opt.margin;
+    prm.rel_gap = opt.relGap;
+    prm.mask = opt.mask;
+    uvrt_plan_report rep;
+    memset(&rep, 0, sizeof rep);
+    std::vector<float> d((size_t)L), d_other((size_t)L);
+    for (size_t r = 0; r < group.size(); ++r) {
+        RayTracer* rt = group[r];
+        rt->planCapture = false;
+        uvrt_plan_report rr;
+        check(uvrt_plan_solve(rt->ctx, &prm, r == 0 ? d.data() : d_other.data(), &rr), "plan_solve");
+        if (r == 0) rep = rr;
+        else if (memcmp(d.data(), d_other.data(), d.size() * 4) != 0) fatal("PlanDurations: the contexts of the group planned different durations");
+    }
+    for (RayTracer* rt : group)
+        for (int i = 0; i < L; ++i) rt->lightPositions[i].duration = d[i];
+    if (seedOut) *seedOut = seed0;
+    return rep;
+}
+
+void RayTracer::EndPlan() { check(uvrt_plan_end(ctx), "plan_end"); }
+
+void RayTracer::GridPositions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz)
+{
+    const float x0 = xmin + inset, x1 = xmax - inset, z0 = zmin + inset, z1 = zmax - inset;
+    for (int j = 0; j < nz; ++j)
+        for (int i = 0; i < nx; ++i) {
+            float* o = xz + 2 * ((size_t)j * nx + i);
+            o[0] = nx == 1 ? 0.5f * (x0 + x1) : x0 + (x1 - x0) * (float)i / (float)(nx - 1);
+            o[1] = nz == 1 ? 0.5f * (z0 + z1) : z0 + (z1 - z0) * (float)j / (float)(nz - 1);
+        }
+}
+
+void RayTracer::SetCandidateGrid(int nx, int nz, float inset)
+{
+    if (nx < 1 || nz < 1) fatal("SetCandidateGrid: nx and nz must be >= 1");
+    float xmin = INFINITY, xmax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
+    for (int i = 0; i < mesh->triangleCount; ++i) {
+        const Tri& t = mesh->triangles[i];
+        for (const auto* v : {&t.vertex0, &t.vertex1, &t.vertex2}) {
+            xmin = std::min(xmin, v->x); xmax = std::max(xmax, v->x);
+            zmin = std::min(zmin, v->z); zmax = std::max(zmax, v->z);
+        }
+    }
+    std::vector<float> xz((size_t)nx * nz * 2);
+    GridPositions(xmin, xmax, zmin, zmax, nx, nz, inset, xz.data());
+    lightPositions.clear();
+    for (int k = 0; k < nx * nz; ++k) {
+        LightPos lp;
+        lp.position = make_float2(xz[2 * k], xz[2 * k + 1]);
+        lp.duration = 1.0f;
+        lightPositions.push_back(lp);
+    }
+    UpdatePhotonsPerLight();
 }
 
 void RayTracer::Shade()                                      // raytracer.cpp:93-120

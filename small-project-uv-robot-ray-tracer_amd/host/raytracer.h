@@ -5,6 +5,7 @@
 #pragma once
 #include "template_types.h"
 #include "mesh.h"
+#include "../../include/uvrt.h"
 
 #include <string>
 #include <vector>
@@ -90,6 +91,29 @@ public:
     long long rangeFirst = 0, rangeCount = -1;      // -1: the whole launch
     bool reduceOverComm = false;                    // ctx has a communicator: all-reduce the planes of every batch
     void SetRayRange(int rank, int world);          // contiguous share of [0, photonsPerLight) for rank of world
+    // Duration planning (include/uvrt.h "duration planning"): one batched computation over the current
+    // lightPositions from the current SEED with the exposure captured, the covering LP solved, and the least
+    // durations that bring every required triangle to minDose written into lightPositions (positions the plan
+    // does not need keep their place with duration 0, so a recompute traces the same rays).  `group`: instances
+    // that share every launch by ray range; every context captures after the group reduce and solves on its own
+    // (identical durations).  minDose < 0: the route's minDosage.  Returns the solver's report; *seedOut is the
+    // SEED the computation started from.
+    struct PlanOptions {
+        float minDose = -1.0f;
+        int minPhotons = 16;
+        double margin = 1e-6, relGap = 1e-3;
+        int maxIterations = 200;       // cutting-plane rounds of the solver
+        const unsigned char* mask = nullptr;    // uint8[T], 0 = not required
+    };
+    uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
+    static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
+    // E (positions x triangles x 4 bytes) stays on the device after PlanDurations, for uvrt_plan_model_dose /
+    // uvrt_plan_read_required; EndPlan releases it (so do a new scene and the destructor)
+    void EndPlan();
+    // replaces lightPositions by an nx x nz grid over the mesh's x/z bounds inset by `inset` metres (duration 1)
+    void SetCandidateGrid(int nx, int nz, float inset);
+    static void GridPositions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz);
+    bool planCapture = false;                       // ComputeIterationsBatched captures every batch (PlanDurations)
     // The reference never reads the dose back; the headless build does.
     void ReadDosage(float* out, int first, int count);
     void Sync();                        // clFinish(Kernel::GetQueue()), myapp.cpp:165

@@ -17,10 +17,20 @@
 //            [--gpus N]                     one process, N contexts: every launch split by global-id range
 //                                           ("pixel tiles"), ONE RCCL all-reduce of the count planes per batch
 //                                           (contexts share a device when the box has fewer than N: no RCCL then)
+//            [--plan [MIN_DOSE]]            plan the durations (RayTracer::PlanDurations): least total time that brings every
+//                                           required triangle to MIN_DOSE mJ/cm^2 (default: the route's minimale_dosis);
+//                                           prints the report, --save-route saves the planned route, --dump the plan's model dose
+//            [--candidates grid:NX,NZ[,INSET]]  plan over an NX x NZ grid over the room's x/z bounds (inset, metres: 0.5)
+//            [--min-photons N]              triangles with fewer captured photons are "unresolved", not required (16)
+//            [--plan-verify]                recompute from the plan's SEED with the planned durations through the normal
+//                                           pipeline and count the required triangles below the minimum (exit 1 unless 0)
+//            [--verify-dump FILE]           the dose of that recompute (raw f32 or .npy)
+//            [--plan-holdout SEED]          the same from another SEED: area fraction at or above the minimum (informative)
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,12 +40,114 @@
 
 using namespace Tmpl8;
 
+namespace {
+
+void write_f32(const std::string& path, const std::vector<float>& v)
+{
+    std::ofstream f(path, std::ios::binary);
+    if (path.size() > 4 && path.substr(path.size() - 4) == ".npy") {
+        // NumPy format 1.0: magic, version, header length, dict padded to a 64-byte boundary
+        std::string hdr = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(v.size()) + ",), }";
+        while ((10 + hdr.size() + 1) % 64) hdr += ' ';
+        hdr += '\n';
+        const unsigned short hl = (unsigned short)hdr.size();
+        f.write("\x93NUMPY\x01\x00", 8);
+        f.write((const char*)&hl, 2);
+        f.write(hdr.data(), (std::streamsize)hdr.size());
+    }
+    f.write((const char*)v.data(), (std::streamsize)v.size() * 4);
+}
+
+// the route's computation from `seed` with the current durations (batched or per launch), dose read back
+std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
+{
+    if (uvrt_set_seed(rt.ctx, seed) != UVRT_OK) { fprintf(stderr, "set_seed: %s\n", uvrt_last_error()); exit(1); }
+    rt.ResetDosageMap();
+    rt.viewMode = dosage;
+    while (rt.currIterations < rt.maxIterations) {
+        if (batch > 0) {
+            RayTracer::ComputeIterationsBatched(std::vector<RayTracer*>{&rt}, std::min(batch, rt.maxIterations - rt.currIterations));
+        } else {
+            rt.ComputeDosageMap();
+            rt.Shade();
+            rt.currIterations++;
+        }
+    }
+    std::vector<float> dose(rt.mesh->triangleCount);
+    rt.ReadDosage(dose.data(), 0, rt.mesh->triangleCount);
+    return dose;
+}
+
+int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
+             const std::string& dump, const std::string& verifyDump)
+{
+    const int T = rt.mesh->triangleCount;
+    RayTracer::PlanOptions opt;
+    opt.minDose = minDose;
+    opt.minPhotons = minPhotons;
+    unsigned seed0 = 0;
+    const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
+    const float m = minDose >= 0.0f ? minDose : rt.minDosage;
+    printf("plan: %d positions, %d used, total duration %.9g (lower bound %.9g, gap %.3g), %s after %d iterations\n",
+           r.positions, r.used_positions, r.total_duration, r.lower_bound, r.gap,
+           r.status == UVRT_PLAN_CONVERGED ? "converged" : "iteration cap", r.iterations);
+    printf("plan: minimum %.9g mJ/cm^2 from SEED %u; required %d triangles (area %.6g), unreachable %d (area %.6g), "
+           "unresolved %d (area %.6g), masked out %d (area %.6g); min dose / minimum %.9g\n",
+           (double)m, seed0, r.required, r.area_required, r.unreachable, r.area_unreachable, r.unresolved, r.area_unresolved,
+           r.masked_out, r.area_masked_out, r.min_dose_ratio);
+    for (size_t i = 0; i < rt.lightPositions.size(); ++i)
+        if (rt.lightPositions[i].duration > 0.0f)
+            printf("plan: position %zu (%.6g, %.6g) duration %.9g\n", i, rt.lightPositions[i].position.x,
+                   rt.lightPositions[i].position.y, rt.lightPositions[i].duration);
+    std::vector<float> d(rt.lightPositions.size());
+    for (size_t i = 0; i < d.size(); ++i) d[i] = rt.lightPositions[i].duration;
+    std::vector<uint8_t> req(T);
+    if (uvrt_plan_read_required(rt.ctx, req.data(), 0, T) != UVRT_OK) { fprintf(stderr, "plan: %s\n", uvrt_last_error()); return 1; }
+    if (!dump.empty()) {
+        std::vector<float> model(T);
+        if (uvrt_plan_model_dose(rt.ctx, d.data(), model.data(), 0, T) != UVRT_OK) { fprintf(stderr, "plan: %s\n", uvrt_last_error()); return 1; }
+        write_f32(dump, model);
+    }
+    int rc = 0;
+    if (verify) {
+        const std::vector<float> dose = recompute(rt, seed0, batch);
+        int below = 0;
+        for (int t = 0; t < T; ++t) below += req[t] && !(dose[t] >= m);
+        printf("plan-verify: %d below minimum of %d required triangles (SEED %u)\n", below, r.required, seed0);
+        if (!verifyDump.empty()) write_f32(verifyDump, dose);
+        if (below) rc = 1;
+    }
+    if (holdout) {
+        const std::vector<float> dose = recompute(rt, holdoutSeed, batch);
+        double a_req = 0, a_ok = 0;
+        for (int t = 0; t < T; ++t) {
+            if (!req[t]) continue;
+            // the context's f32 area (k_prepare_scene: same operations, same order; this file builds with -ffp-contract=off)
+            const Tri& tr = rt.mesh->triangles[t];
+            const float ax = tr.vertex0.x - tr.vertex1.x, ay = tr.vertex0.y - tr.vertex1.y, az = tr.vertex0.z - tr.vertex1.z;
+            const float bx = tr.vertex0.x - tr.vertex2.x, by = tr.vertex0.y - tr.vertex2.y, bz = tr.vertex0.z - tr.vertex2.z;
+            const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+            const double a = std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0f;
+            a_req += a;
+            if (dose[t] >= m) a_ok += a;
+        }
+        printf("plan-holdout: SEED %u, area fraction at or above minimum %.6f\n", holdoutSeed, a_req > 0 ? a_ok / a_req : 1.0);
+    }
+    return rc;
+}
+
+}  // namespace
+
 int main(int argc, char** argv)
 {
     std::string room, routeDir = "positions/", route = "route", dump, saveRoute, ply;
     long long photons = -1;
     int iterations = -1, lamps = -1, device = 0, gpus = 1, batch = 0, flavour = 0;
-    bool calibrate = false;
+    bool calibrate = false, plan = false, planVerify = false, planHoldout = false;
+    float planMin = -1.0f, gridInset = 0.5f;
+    int minPhotons = 16, gridX = 0, gridZ = 0;
+    uint32_t holdoutSeed = 0;
+    std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
     ViewMode view = dosage;
     for (int i = 1; i < argc; ++i) {
@@ -55,6 +167,23 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--save-route")) { need(1); saveRoute = argv[++i]; }
         else if (!strcmp(argv[i], "--view")) { need(1); view = !strcmp(argv[++i], "maxpower") ? maxpower : dosage; }
         else if (!strcmp(argv[i], "--calibrate")) { need(3); calibrate = true; calP = (float)atof(argv[++i]); calH = (float)atof(argv[++i]); calD = (float)atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--plan")) {
+            plan = true;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) planMin = (float)atof(argv[++i]);
+        }
+        else if (!strcmp(argv[i], "--candidates")) {
+            need(1);
+            const char* v = argv[++i];
+            if (strncmp(v, "grid:", 5) != 0 || sscanf(v + 5, "%d,%d,%f", &gridX, &gridZ, &gridInset) < 2 || gridX < 1 || gridZ < 1 ||
+                gridX * gridZ > 256) {
+                fprintf(stderr, "--candidates grid:NX,NZ[,INSET] (NX x NZ <= 256)\n");
+                return 2;
+            }
+        }
+        else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
+        else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
+        else if (!strcmp(argv[i], "--plan-holdout")) { need(1); planHoldout = true; holdoutSeed = (uint32_t)strtoul(argv[++i], nullptr, 0); }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
@@ -80,6 +209,21 @@ int main(int argc, char** argv)
         std::cout << "Calibrated lamp power: " << rayTracer.lightIntensity << std::endl;
     }
 
+    if (plan) {
+        if (gpus != 1) { fprintf(stderr, "--plan runs on one context (--gpus 1)\n"); return 2; }
+        if (uvrt_set_flavour(rayTracer.ctx, flavour) != UVRT_OK) { fprintf(stderr, "--flavour: %s\n", uvrt_last_error()); return 2; }
+        if (gridX > 0) rayTracer.SetCandidateGrid(gridX, gridZ, gridInset);
+        rayTracer.ResetDosageMap();
+        rayTracer.viewMode = dosage;
+        const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump);
+        if (!saveRoute.empty()) {
+            char name[32];
+            strncpy(name, saveRoute.c_str(), 31);
+            name[31] = 0;
+            rayTracer.SaveRoute(name);
+        }
+        return rc;
+    }
     // --gpus N: further instances of the same RayTracer, one per context, each with its range of every launch
     std::vector<RayTracer*> group{&rayTracer};
     std::vector<RayTracer*> extra;

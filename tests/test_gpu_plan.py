@@ -1,0 +1,321 @@
+"""GPU: duration planning (include/uvrt.h "duration planning", RayTracer::PlanDurations): the captured exposure is
+exact, capture changes nothing, the planned durations hold in the unmodified pipeline, the solver's optimum and
+certificate check out against independent solvers, and the edges and errors behave."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GLB, GOLDEN, ROOT, ROUTE
+
+pytestmark = pytest.mark.gpu
+
+CLI = os.path.join(ROOT, "small-project-uv-robot-ray-tracer_amd", "uvrt_cli")
+PPL = 1 << 18          # photons per launch
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _rt(positions=None, iterations=2, ppl=PPL):
+    from uvrt_amd import host
+    rt = host.RayTracer(GLB, ROUTE, device=0)
+    if positions is not None:
+        rt.set_lamps(positions)
+    rt.photonCount = ppl * len(rt.lamps())
+    rt.maxIterations = iterations
+    return rt
+
+
+def _areas(rt):
+    """k_prepare_scene's f32 triangle areas"""
+    t = rt.mesh.tris()
+    v0, v1, v2 = t[:, 0:3], t[:, 4:7], t[:, 8:11]
+    a, b = v0 - v1, v0 - v2
+    cx = a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]
+    cy = a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]
+    cz = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    return np.sqrt(cx * cx + cy * cy + cz * cz) / np.float32(2.0)
+
+
+def _lp(rt):
+    """(E[P][T] float64, required mask, b_t of the required rows) of the last solve"""
+    P = len(rt.lamps())
+    E = np.stack([rt.ctx.plan_read_exposure(p) for p in range(P)]).astype(np.float64)
+    req = rt.ctx.plan_read_required()
+    return E, req
+
+
+def _rhs(rt, m, margin=1e-6):
+    N = rt.maxIterations * rt.photonsPerLight
+    den = (_areas(rt) * np.float32(N)).astype(np.float64)
+    s = float(np.float32(np.float32(rt.lightIntensity) * np.float32(0.1)))
+    return m * (1.0 + margin) * den / s
+
+
+def _recompute(rt, seed, batched):
+    rt.ctx.seed = seed
+    rt.ResetDosageMap()
+    if batched:
+        rt.ComputeIterationsBatched(rt.maxIterations)
+    else:
+        for _ in range(rt.maxIterations):
+            rt.ComputeDosageMap()
+            rt.Shade()
+            rt.currIterations = rt.currIterations + 1
+    return rt.read_dosage()
+
+
+def test_exposure_rows_equal_the_batch_planes_and_the_oracle(pkg, orc, oscene, oroute):
+    """3 positions x 2 iterations: row p of E = the sum of position p's folded planes = the oracle's per-launch counts."""
+    lamps = oroute["lamps"][:3]
+    comp = orc.Computation(oscene, lamps, PPL * 3, oroute["lightHeight"], oroute["lightLength"], oroute["lightIntensity"])
+    world = [tuple(float(x) for x in comp.lamp_world_pos(l)) for l in lamps]
+    c = pkg.capi.Ctx(0)
+    try:
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        c.resize_rays(PPL)
+        c.reset(True)
+        c.plan_begin(3)
+        order = [0, 1, 2, 0, 1, 2]
+        c.trace_batch([world[k] for k in order], oroute["lightLength"], 0, PPL)
+        planes = [c.read_batch_counts(k) for k in range(6)]
+        c.plan_capture_batch(order)
+        ops = np.zeros(6, dtype=pkg.capi.REPLAY_OP_DT)
+        for k in range(6):
+            ops[k] = (1.0, int(k % 3 == 2), 0, PPL, 45.0, 100.0, 0)
+        c.replay_batch(ops)
+        seed = 0
+        want = np.zeros((3, oscene.T), dtype=np.int64)
+        for k, p in enumerate(order):
+            rays, seed = orc.generate(0, PPL, world[p], np.float32(oroute["lightLength"]), seed)
+            temp = np.zeros(oscene.T, dtype=np.int32)
+            orc.extend(temp, oscene.tris, rays, oscene.nodes, oscene.triIdx)
+            assert np.array_equal(temp, planes[k])
+            want[p] += temp
+        for p in range(3):
+            got = c.plan_read_exposure(p)
+            assert np.array_equal(got.astype(np.int64), want[p])
+            assert np.array_equal(got.astype(np.int64), planes[p].astype(np.int64) + planes[p + 3])
+        assert want.sum() > 0
+    finally:
+        c.close()
+
+
+def test_capture_changes_nothing(pkg):
+    a, b = _rt(), _rt()
+    try:
+        a.ResetDosageMap()
+        a.ComputeIterationsBatched(2)
+        b.PlanDurations()          # the same computation (same SEED, the route's durations) with capture on
+        assert np.array_equal(bits(a.read_dosage()), bits(b.read_dosage()))
+        assert np.array_equal(bits(a.ctx.read_color()), bits(b.ctx.read_color()))
+        for w in (0, 1):
+            assert np.array_equal(a.ctx.read_photon_map(w).view(np.uint64), b.ctx.read_photon_map(w).view(np.uint64))
+    finally:
+        a.close()
+        b.close()
+
+
+def _check_optimality(rt, d, rep, m, rel_gap=1e-3):
+    E, req = _lp(rt)
+    b = _rhs(rt, m)[req]
+    A = E[:, req]                       # [P][R]
+    P = A.shape[0]
+    if P == 1:
+        opt = float(np.max(b / A[0]))
+    elif P == 2:
+        lo = float(np.max(np.where(A[1] == 0, b / np.where(A[0] > 0, A[0], np.inf), 0.0)))
+        def f(d0):
+            rest = np.where(A[1] > 0, (b - A[0] * d0) / np.where(A[1] > 0, A[1], 1.0), 0.0)
+            return d0 + max(0.0, float(rest.max()))
+        hi = float(np.max(b / np.where(A[0] > 0, A[0], np.inf)))
+        hi = max(hi, lo)
+        for _ in range(200):           # golden-section search of the convex objective
+            x1, x2 = lo + 0.382 * (hi - lo), lo + 0.618 * (hi - lo)
+            if f(x1) <= f(x2):
+                hi = x2
+            else:
+                lo = x1
+        opt = f(0.5 * (lo + hi))
+    else:
+        from scipy.optimize import linprog       # required: the independent optimum for P >= 3
+        r = linprog(np.ones(P), A_ub=-A.T, b_ub=-b, bounds=[(0, None)] * P, method="highs")
+        assert r.status == 0
+        opt = float(r.fun)
+    total = float(np.sum(d.astype(np.float64)))
+    assert abs(total - rep["total_duration"]) <= 1e-9 * total
+    assert rep["lower_bound"] <= opt * (1 + 1e-9) and opt <= total * (1 + 1e-9)
+    assert total <= opt * (1 + 2 * rel_gap)
+    assert rep["converged"] and rep["gap"] <= rel_gap
+    # feasible in the model, in f64
+    assert np.all(d.astype(np.float64) @ A >= b * (1 - 1e-12))
+
+
+@pytest.mark.parametrize("positions", ["route", "grid"])
+def test_plan_holds_in_the_pipeline_and_is_optimal(pkg, positions):
+    rt = _rt()
+    try:
+        if positions == "grid":
+            rt.SetCandidateGrid(4, 4, 0.5)
+            rt.photonCount = PPL * 16
+        m = float(np.float32(rt.minDosage))
+        d, rep = rt.PlanDurations()
+        assert rep["required"] > 0 and rep["min_dose_ratio"] >= 1.0
+        assert np.array_equal(np.array([l[2] for l in rt.lamps()], dtype=np.float32), d)
+        _check_optimality(rt, d, rep, m)
+        req = rt.ctx.plan_read_required()
+        model = rt.ctx.plan_model_dose(d)
+        doses = [_recompute(rt, rep["seed"], batched) for batched in (True, False)]
+        assert np.array_equal(bits(doses[0]), bits(doses[1]))
+        dose = doses[0]
+        assert np.all(dose[req] >= m), int((dose[req] < m).sum())
+        nz = (dose > 0) & np.isfinite(dose)
+        assert np.all(np.abs(model[nz].astype(np.float64) - dose[nz]) <= 1e-6 * dose[nz])
+        assert np.all(model[dose == 0] == 0)
+    finally:
+        rt.close()
+
+
+def test_largest_candidate_grid(pkg):
+    """16 x 16 = 256 candidates, the largest P uvrt_plan_begin accepts: optimal against HiGHS, holds in the pipeline;
+    EndPlan releases the exposure matrix."""
+    rt = _rt(iterations=1, ppl=1 << 16)
+    try:
+        rt.SetCandidateGrid(16, 16, 0.5)
+        rt.photonCount = 256 << 16
+        m = float(np.float32(rt.minDosage))
+        d, rep = rt.PlanDurations()
+        assert rep["positions"] == 256 and 0 < rep["used_positions"] < 256
+        _check_optimality(rt, d, rep, m)
+        req = rt.ctx.plan_read_required()
+        dose = _recompute(rt, rep["seed"], True)
+        assert np.all(dose[req] >= m), int((dose[req] < m).sum())
+        rt.EndPlan()
+        with pytest.raises(pkg.capi.UvrtError, match="error -1"):
+            rt.ctx.plan_model_dose(d)
+    finally:
+        rt.close()
+
+
+@pytest.mark.parametrize("npos", [1, 2])
+def test_small_plans_match_the_exact_optimum(pkg, npos):
+    rt = _rt()
+    try:
+        rt.set_lamps(rt.lamps()[3:3 + npos])
+        rt.photonCount = PPL * npos
+        m = float(np.float32(rt.minDosage))
+        d, rep = rt.PlanDurations()
+        _check_optimality(rt, d, rep, m)
+    finally:
+        rt.close()
+
+
+def test_solves_are_deterministic_and_contexts_of_a_group_agree(pkg):
+    from uvrt_amd import host
+    one = _rt(iterations=1)
+    g = [_rt(iterations=1), _rt(iterations=1)]
+    try:
+        d1, rep1 = one.PlanDurations()
+        prm = dict(min_dose=one.minDosage, scaled_power=np.float32(one.lightIntensity) * np.float32(0.1),
+                   photons_per_position=one.photonsPerLight, positions=len(d1))
+        again, _ = one.ctx.plan_solve(**prm)
+        twice, _ = one.ctx.plan_solve(**prm)
+        assert np.array_equal(bits(again), bits(d1)) and np.array_equal(bits(twice), bits(d1))
+        for r, rt in enumerate(g):
+            rt.SetRayRange(r, 2)
+        dg, repg = host.plan_durations_group(g)
+        assert np.array_equal(bits(dg), bits(d1)) and repg["seed"] == rep1["seed"] == 0
+        for rt in g:
+            assert np.array_equal(bits(np.array([l[2] for l in rt.lamps()], dtype=np.float32)), bits(d1))
+    finally:
+        for rt in [one] + g:
+            rt.close()
+
+
+def test_edges(pkg, tmp_path):
+    from uvrt_amd import host
+    rt = _rt(iterations=1)
+    try:
+        lamps = rt.lamps()[:2] + [(1e5, 1e5, 1.0)]      # the third candidate is far outside: it sees nothing
+        rt.set_lamps(lamps)
+        rt.photonCount = PPL * 3
+        d, rep = rt.PlanDurations()
+        assert not rt.ctx.plan_read_exposure(2).any() and d[2] == 0.0 and d[:2].sum() > 0
+        # unreachable: no photon from any position (or no area), with its f32 areas summed
+        E, req = _lp(rt)
+        area = _areas(rt).astype(np.float64)
+        unreach = (E.sum(axis=0) == 0) | ~(area > 0)
+        assert rep["unreachable"] == int(unreach.sum()) > 0
+        assert abs(rep["area_unreachable"] - float(area[unreach].sum())) <= 1e-9 * max(1.0, float(area.sum()))
+        assert rep["required"] + rep["unreachable"] + rep["unresolved"] + rep["masked_out"] == rt.mesh.triangleCount
+        # durations survive SaveRoute -> LoadRoute bit for bit
+        rt.set_route_dir(str(tmp_path) + os.sep)
+        rt.SaveRoute("planned")
+        back = host.RayTracer(init=False)
+        back.set_route_dir(str(tmp_path) + os.sep)
+        back.LoadRoute("planned")
+        assert np.array_equal(bits(np.array([l[2] for l in back.lamps()], dtype=np.float32)), bits(d))
+        back.close()
+        # min_dose 0: nothing to do; a mask that excludes everything: an empty required set
+        z, rz = rt.ctx.plan_solve(0.0, 45.0, rt.photonsPerLight, positions=3)
+        assert not z.any() and rz["converged"]
+        z, rz = rt.ctx.plan_solve(100.0, 45.0, rt.photonsPerLight, mask=np.zeros(rt.mesh.triangleCount, np.uint8),
+                                  positions=3)
+        assert not z.any() and rz["required"] == 0 and rz["masked_out"] == rt.mesh.triangleCount
+    finally:
+        rt.close()
+
+
+def test_invalid_calls(pkg, oscene):
+    c = pkg.capi.Ctx(0)
+    try:
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        c.resize_rays(4096)
+        c.reset(True)
+        for p in (0, 257):
+            with pytest.raises(pkg.capi.UvrtError, match="error -1"):
+                c.plan_begin(p)
+        c.plan_begin(2)
+        with pytest.raises(pkg.capi.UvrtError, match="error -1.*nothing captured"):
+            c.plan_solve(100.0, 45.0, 4096, positions=2)
+        with pytest.raises(pkg.capi.UvrtError, match="error -1.*no traced batch"):
+            c.plan_capture_batch([0])
+        c.trace_batch([(1.0, 1.0, 1.0), (2.0, 1.0, 2.0)], 1.0, 0, 4096)
+        with pytest.raises(pkg.capi.UvrtError, match="error -1.*position 2"):
+            c.plan_capture_batch([0, 2])
+        c.plan_capture_batch([0, 1])
+        with pytest.raises(pkg.capi.UvrtError, match="error -1.*overflow"):
+            c.plan_solve(100.0, 45.0, 1 << 32, positions=2)
+        ops = np.zeros(2, dtype=pkg.capi.REPLAY_OP_DT)
+        c.replay_batch(ops)
+        d, rep = c.plan_solve(100.0, 45.0, 4096, min_photons=1, positions=2)
+        assert rep["min_dose_ratio"] >= 1.0
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)      # drops the plan
+        with pytest.raises(pkg.capi.UvrtError, match="error -1"):
+            c.plan_model_dose(d)
+    finally:
+        c.close()
+
+
+def test_cli_plan_verify_and_replay_of_the_saved_route(tmp_path):
+    shutil.copy(os.path.join(GOLDEN, "lange_route.xml"), tmp_path / "lange_route.xml")
+    vd, dd, md = tmp_path / "verify.f32", tmp_path / "again.f32", tmp_path / "model.f32"
+    cmd = [CLI, "--room", GLB, "--route-dir", str(tmp_path), "--route", "lange_route", "--photons", str(16 * (1 << 17)),
+           "--iterations", "2", "--plan", "--candidates", "grid:4,4", "--plan-verify", "--verify-dump", str(vd),
+           "--dump", str(md), "--save-route", "planned"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "plan-verify: 0 below minimum" in out.stdout
+    assert (tmp_path / "planned.xml").exists()
+    again = subprocess.run([CLI, "--room", GLB, "--route-dir", str(tmp_path), "--route", "planned", "--dump", str(dd)],
+                           capture_output=True, text=True, timeout=300)
+    assert again.returncode == 0, again.stderr
+    v, a = np.fromfile(vd, dtype="<f4"), np.fromfile(dd, dtype="<f4")
+    assert v.size == a.size > 0 and np.array_equal(bits(v), bits(a))
+    model = np.fromfile(md, dtype="<f4")
+    nz = (v > 0) & np.isfinite(v)
+    assert np.all(np.abs(model[nz].astype(np.float64) - v[nz]) <= 1e-6 * v[nz])
