@@ -88,8 +88,8 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
     for (int l = 0; l < uvrt_ctx::MAXL; ++l) {
-        if (l > 0) HIP_TRY(hipStreamCreateWithFlags(&c->side[l], hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_tail[l], hipEventDisableTiming));
+        if (l > 0) HIP_TRY(hipStreamCreateWithFlags(&c->lanes[l].side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&c->lanes[l].ev_tail, hipEventDisableTiming));
     }
     HIP_TRY(hipEventCreateWithFlags(&c->ev_fence, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_mapfence, hipEventDisableTiming));
@@ -123,8 +123,9 @@ int uvrt_create(int device_id, uvrt_ctx** out)
         c->host_flag_dev = (uint32_t*)dp;
     }
 #endif
-    // 256 CUs x 16 workgroups x 256 threads x 16 entries: the largest persistent grid
-    if (!rc) rc = c->ovf_stack.ensure((size_t)OVF_MAX_ENTRIES * sizeof(uint32_t), false, c->stream);
+    // lane 0's overflow stack: 256 CUs x 16 workgroups x 256 threads x 24 entries, the largest persistent grid (side lanes
+    // get theirs, side_ovf_bytes(), with their first launch)
+    if (!rc) rc = c->lanes[0].ovf.ensure((size_t)OVF_MAX_ENTRIES * sizeof(uint32_t), false, c->stream);
     if (rc) { delete c; return rc; }
     *out = c;
     return UVRT_OK;
@@ -137,26 +138,24 @@ void uvrt_destroy(uvrt_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     if (c->comm) uvrt_comm_destroy(c);       // first: it restores the lanes' plain streams
     plan_drop(c);
-    for (int l = 0; l < uvrt_ctx::MAXL; ++l) {
-        if (c->side[l]) (void)hipStreamSynchronize(c->side[l]);
-        for (DevBuf* b : {&c->xrays[l], &c->xrecs[l], &c->xcounts[l], &c->xovf[l]}) b->release();
-        if (c->ev_tail[l]) (void)hipEventDestroy(c->ev_tail[l]);
-        if (c->side[l]) (void)hipStreamDestroy(c->side[l]);
+    for (Lane& L : c->lanes) {
+        if (L.side) (void)hipStreamSynchronize(L.side);
+        for (DevBuf* b : {&L.rays, &L.recs, &L.counts, &L.ovf, &L.recs4}) b->release();
+        if (L.ev_tail) (void)hipEventDestroy(L.ev_tail);
+        if (L.side) (void)hipStreamDestroy(L.side);
     }
     if (c->ev_fence) (void)hipEventDestroy(c->ev_fence);
     if (c->ev_mapfence) (void)hipEventDestroy(c->ev_mapfence);
     c->quads.release();
-    for (DevBuf& b : c->recs4) b.release();
     for (DevBuf& b : c->b_recs) b.release();
-    (void)hot_reset(c, false);
+    (void)hot_reset(c, false);            // (and the lanes' set-up scratch)
     for (auto& bset : c->bs) {
         for (DevBuf* b : {&bset.rays, &bset.planes, &bset.folded}) b->release();
         if (bset.free_ev) (void)hipEventDestroy(bset.free_ev);
     }
-    for (DevBuf* b : {&c->pairs, &c->recs, &c->perm, &c->ltris, &c->leaf_count, &c->area, &c->photon_map, &c->max_map,
-                      &c->counts, &c->dosage, &c->color, &c->rays, &c->keyrank, &c->sorted,
-                      &c->order, &c->hits, &c->hist, &c->bin_start, &c->export_buf,
-                      &c->ovf_stack, &c->error_flag})
+    for (DevBuf* b : {&c->pairs, &c->perm, &c->ltris, &c->leaf_count, &c->area, &c->photon_map, &c->max_map,
+                      &c->dosage, &c->color, &c->keyrank, &c->sorted,
+                      &c->order, &c->hits, &c->hist, &c->bin_start, &c->export_buf, &c->error_flag})
         b->release();
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->host_flag) (void)hipHostFree(c->host_flag);
@@ -323,9 +322,8 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     const bool resized = (T != c->T);
     int rc;
     if ((rc = c->pairs.ensure(std::max<size_t>(pairs.size(), 1) * sizeof(PairRec), false, c->stream))) return rc;
-    if ((rc = c->recs.ensure((pairs.size() + (size_t)T + 1) * 64, true, c->stream))) return rc;
-    for (int l = 1; l < c->nlanes; ++l)
-        if ((rc = c->xrecs[l].ensure((pairs.size() + (size_t)T + 1) * 64, true, c->stream))) return rc;
+    for (int l = 0; l < c->nlanes; ++l)
+        if ((rc = c->lanes[l].recs.ensure((pairs.size() + (size_t)T + 1) * 64, true, c->stream))) return rc;
     // + 16 bytes: the merged record fetch of the traversal reads 64 bytes at every leaf record
     if ((rc = c->ltris.ensure((size_t)T * sizeof(LeafTri) + 16, true, c->stream))) return rc;
     if ((rc = c->leaf_count.ensure((size_t)T * 4, false, c->stream))) return rc;
@@ -335,8 +333,8 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
         // The colour buffer stands for the GL vertex buffer of the caller's mesh (raytracer.cpp:37): a scene swap
         // does not touch it.  It only grows, so CalibratePower's detour over a 2-triangle scene
         // (raytracer.cpp:166-224, ClearBuffers(false)) leaves the room's colours as they were.
-        for (DevBuf* b : {&c->photon_map, &c->max_map, &c->counts, &c->xcounts[1], &c->xcounts[2], &c->xcounts[3],
-                          &c->dosage}) b->release();
+        for (DevBuf* b : {&c->photon_map, &c->max_map, &c->dosage}) b->release();
+        for (Lane& L : c->lanes) L.counts.release();
         if ((rc = c->photon_map.ensure((size_t)T * 8, true, c->stream))) return rc;
         if ((rc = c->max_map.ensure((size_t)T * 8, true, c->stream))) return rc;
         // 16 deposit replicas (two per XCD: a workgroup deposits into replica blockIdx % 16), at most 64 MiB in
@@ -346,9 +344,8 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
         int R = c->replicas_knob > 0 ? c->replicas_knob : 16;
         while (R > 1 && (size_t)R * (size_t)T * 4 > ((size_t)64 << 20)) R >>= 1;
         c->replicas = R;
-        if ((rc = c->counts.ensure((size_t)R * (size_t)T * 4, true, c->stream))) return rc;
-        for (int l = 1; l < c->nlanes; ++l)
-            if ((rc = c->xcounts[l].ensure((size_t)R * (size_t)T * 4, true, c->stream))) return rc;
+        for (int l = 0; l < c->nlanes; ++l)
+            if ((rc = c->lanes[l].counts.ensure((size_t)R * (size_t)T * 4, true, c->stream))) return rc;
         if ((rc = c->dosage.ensure((size_t)T * 4, true, c->stream))) return rc;
         if ((rc = c->color.ensure((size_t)T * 36, true, c->stream))) return rc;
     }
@@ -357,7 +354,7 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     if ((rc = c->quads.ensure(std::max<size_t>(quads.size(), 1) * sizeof(QuadRec), false, c->stream))) return rc;
     if (!quads.empty())
         HIP_TRY(hipMemcpyAsync(c->quads.p, quads.data(), quads.size() * sizeof(QuadRec), hipMemcpyHostToDevice, c->stream));
-    for (DevBuf& b : c->recs4) b.release();              // sized per scene; rebuilt on demand (uvrt_set_wide_bvh)
+    for (Lane& L : c->lanes) L.recs4.release();          // sized per scene; rebuilt on demand (uvrt_set_wide_bvh)
     HIP_TRY(hipMemcpyAsync(c->leaf_count.p, leaf_count.data(), (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
     // staging copies of the reference-layout arrays for the device-side preparation kernel
     DevBuf d_tris, d_idx;
@@ -368,9 +365,8 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     if (e1 == hipSuccess && e2 == hipSuccess) {
         launch_prepare_scene(d_tris.as<float4>(), d_idx.as<uint32_t>(), c->ltris.as<LeafTri>(),
                              c->area.as<float>(), T, c->stream);
-        launch_prepare_leaves6(c->ltris.as<LeafTri>(), c->recs.p, (int32_t)pairs.size(), T, c->stream);
-        for (int l = 1; l < c->nlanes; ++l)
-            launch_prepare_leaves6(c->ltris.as<LeafTri>(), c->xrecs[l].p, (int32_t)pairs.size(), T, c->stream);
+        for (int l = 0; l < c->nlanes; ++l)
+            launch_prepare_leaves6(c->ltris.as<LeafTri>(), c->lanes[l].recs.p, (int32_t)pairs.size(), T, c->stream);
         e1 = hipGetLastError();
         e2 = hipStreamSynchronize(c->stream);
     }
@@ -384,9 +380,7 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     c->npairs = (int32_t)pairs.size();
     c->nquads = (int32_t)quads.size();
     c->top_quads = top_quads;
-    for (int l = 0; l < uvrt_ctx::MAXL; ++l) c->recs4_valid[l] = false;
-    c->recs_valid = false;
-    for (int l = 0; l < uvrt_ctx::MAXL; ++l) c->xrecs_valid[l] = false;
+    for (Lane& L : c->lanes) { L.recs_tag.valid = false; L.recs4_tag.valid = false; }
     c->have_perm = false;
     c->have_scene = true;
     c->scene_force_exact = tiny_bound || huge_vertex;
@@ -407,15 +401,14 @@ int uvrt_resize_rays(uvrt_ctx* c, int64_t photon_count)
 {
     if (!c || photon_count < 0) return fail(UVRT_ERR_INVALID, "uvrt_resize_rays: bad argument");
     if (int rc = set_device(c)) return rc;
-    if (photon_count == c->capacity && c->rays.p && (!c->record_hits || c->hits.p)) { c->last_n = -1; return UVRT_OK; }
+    if (photon_count == c->capacity && c->lanes[0].rays.p && (!c->record_hits || c->hits.p)) { c->last_n = -1; return UVRT_OK; }
     if (int rcj = join_all(c)) return rcj;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->lane = 0;
     int rc;
     const size_t n = (size_t)photon_count;
-    if ((rc = c->rays.ensure(n * 16, false, c->stream))) return rc;
-    for (int l = 1; l < c->nlanes; ++l)
-        if ((rc = c->xrays[l].ensure(n * 16, false, c->stream))) return rc;
+    for (int l = 0; l < c->nlanes; ++l)
+        if ((rc = c->lanes[l].rays.ensure(n * 16, false, c->stream))) return rc;
     if ((rc = c->keyrank.ensure(n * 8, false, c->stream))) return rc;
     if ((rc = c->sorted.ensure(n * 16, false, c->stream))) return rc;
     if ((rc = c->order.ensure(n * 4, false, c->stream))) return rc;
@@ -430,20 +423,20 @@ int uvrt_reset(uvrt_ctx* c, int32_t reset_color)
     if (!c || !c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_reset: no scene");
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
-    launch_reset(c->photon_map.as<double>(), c->max_map.as<double>(), c->counts.as<int32_t>(),
+    launch_reset(c->photon_map.as<double>(), c->max_map.as<double>(), c->lanes[0].counts.as<int32_t>(),
                  c->replicas, c->T, c->color.as<float>(), reset_color, c->T, c->stream);
     HIP_TRY(hipGetLastError());
     // side-lane count buffers are zero unless an extend was never accumulated; only then must later
-    // generate / extend work on the side streams wait for this reset
+    // generate / extend work on the side streams wait for this reset (lane 0's: k_reset)
     bool dirty = false;
-    for (int l = 1; l < uvrt_ctx::MAXL; ++l) {
-        if (c->counts_dirty[l] && c->xcounts[l].p) {
-            HIP_TRY(hipMemsetAsync(c->xcounts[l].p, 0, c->xcounts[l].bytes, c->stream));
+    for (int l = 0; l < uvrt_ctx::MAXL; ++l) {
+        Lane& L = c->lanes[l];
+        if (l > 0 && L.counts_dirty && L.counts.p) {
+            HIP_TRY(hipMemsetAsync(L.counts.p, 0, L.counts.bytes, c->stream));
             dirty = true;
         }
-        c->counts_dirty[l] = false;
+        L.counts_dirty = false;
     }
-    c->counts_dirty[0] = false;
     if (c->b_count > 0) {     // a traced batch that was never replayed: drop its deposits
         if (c->b_is_folded) HIP_TRY(hipMemsetAsync(c->bs[c->b_set].folded.p, 0, c->bs[c->b_set].folded.bytes, c->stream));
         else HIP_TRY(hipMemsetAsync(c->bs[c->b_set].planes.p, 0, c->bs[c->b_set].planes.bytes, c->stream));
@@ -460,8 +453,7 @@ int uvrt_set_record_perm(uvrt_ctx* c, const uint32_t* perm, int32_t n)
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->recs_valid = false;
-    for (int l = 0; l < uvrt_ctx::MAXL; ++l) c->xrecs_valid[l] = false;
+    for (Lane& L : c->lanes) L.recs_tag.valid = false;
     if (!perm) { c->have_perm = false; return UVRT_OK; }
     if (n != c->npairs) return fail(UVRT_ERR_INVALID, "uvrt_set_record_perm: %d entries, the scene has %d inner nodes", n, c->npairs);
     std::vector<uint8_t> seen((size_t)n, 0);
@@ -484,7 +476,7 @@ int uvrt_read_record_perm(uvrt_ctx* c, uint32_t* out, int32_t n)
         return fail(UVRT_ERR_INVALID, "uvrt_read_record_perm: need a scene and n = its %d inner nodes", c ? c->npairs : 0);
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
-    const uint32_t* pm = c->have_perm ? c->perm.as<uint32_t>() : c->lane_perm[c->lane];
+    const uint32_t* pm = c->have_perm ? c->perm.as<uint32_t>() : cur_lane(c).perm;
     if (!pm) { for (int32_t i = 0; i < n; ++i) out[i] = (uint32_t)i; return UVRT_OK; }
     HIP_TRY(hipMemcpyAsync(out, pm, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -567,10 +559,10 @@ int uvrt_read_counts(uvrt_ctx* c, int32_t* out, int32_t first, int32_t count)
     if (c && c->have_scene) {
         if (int rc = set_device(c)) return rc;
         if (int rc = join_all(c)) return rc;
-        launch_fold_counts(lane_counts(c).as<int32_t>(), c->replicas, c->T, c->T, c->stream);
+        launch_fold_counts(cur_lane(c).counts.as<int32_t>(), c->replicas, c->T, c->T, c->stream);
         if (int rc = mark_fence(c)) return rc;
     }
-    return read_back(c, c ? lane_counts(c) : DevBuf(), 4, out, first, count, c ? c->T : 0, "uvrt_read_counts");
+    return read_back(c, c ? cur_lane(c).counts : DevBuf(), 4, out, first, count, c ? c->T : 0, "uvrt_read_counts");
 }
 int uvrt_read_photon_map(uvrt_ctx* c, int32_t which, double* out, int32_t first, int32_t count)
 {
@@ -608,8 +600,7 @@ int uvrt_set_hot_records(uvrt_ctx* c, int32_t mode)
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     c->hot_mode = mode;
-    c->recs_valid = false;
-    for (int l = 0; l < uvrt_ctx::MAXL; ++l) { c->xrecs_valid[l] = false; c->lane_perm[l] = nullptr; }
+    for (Lane& L : c->lanes) { L.recs_tag.valid = false; L.perm = nullptr; }
     return UVRT_OK;
 }
 
@@ -671,7 +662,7 @@ int uvrt_read_rays(uvrt_ctx* c, void* rays32, int64_t first, int64_t count)
     if (count == 0) return UVRT_OK;
     if (int rc = c->export_buf.ensure((size_t)count * 32, false, c->stream)) return rc;
     const uint2* hits = (c->last_extended && c->hits.p) ? c->hits.as<uint2>() : nullptr;
-    launch_export_rays(lane_rays(c).as<float4>(), hits, c->export_buf.p, c->ox, c->oz, first, count, c->stream);
+    launch_export_rays(cur_lane(c).rays.as<float4>(), hits, c->export_buf.p, c->ox, c->oz, first, count, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rays32, c->export_buf.p, (size_t)count * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -695,10 +686,11 @@ int uvrt_write_rays(uvrt_ctx* c, const void* rays32, int64_t n)
     if (int rc = join_all(c)) return rc;
     c->lane = 0;
     c->cur_pipelined = false;
-    HIP_TRY(hipMemcpyAsync(c->rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    Lane& L = c->lanes[0];
+    HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->recs_valid = false;
-    c->lane_perm[0] = nullptr;
+    L.recs_tag.valid = false;
+    L.perm = nullptr;
     c->last_n = n;
     c->last_first = 0;
     c->last_sorted = false;
@@ -721,8 +713,8 @@ int uvrt_device_ptr(uvrt_ctx* c, int32_t which, void** ptr, int64_t* bytes)
         case 0: b = &c->photon_map; elem = 8; break;
         case 1: b = &c->max_map; elem = 8; break;
         case 2:
-            b = &lane_counts(c); elem = 4;
-            launch_fold_counts(lane_counts(c).as<int32_t>(), c->replicas, c->T, c->T, c->stream);
+            b = &cur_lane(c).counts; elem = 4;
+            launch_fold_counts(b->as<int32_t>(), c->replicas, c->T, c->T, c->stream);
             break;
         case 3: b = &c->dosage; elem = 4; break;
         case 4: b = &c->color; elem = 36; break;

@@ -92,10 +92,9 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
             }
         }
         ggen[g] = perm_generation(c, gperm[g]);
-        if (g >= (int)c->b_recs_key.size() || c->b_recs_key[g].perm != gperm[g] || c->b_recs_key[g].gen != ggen[g] || memcmp(&c->b_recs_key[g].ox, &gx[g], 4) != 0 ||
-            memcmp(&c->b_recs_key[g].oz, &gz[g], 4) != 0 || is_fresh) {
+        if (g >= (int)c->b_recs_key.size() || !c->b_recs_key[g].holds(gx[g], gz[g], gperm[g], ggen[g]) || is_fresh) {
             recs_stale = true;
-            if (g < (int)c->b_recs_key.size()) c->b_recs_key[g].valid = false;
+            if (g < (int)c->b_recs_key.size()) c->b_recs_key[g].tag.valid = false;
         }
     }
     if (nfresh > 0)
@@ -119,15 +118,15 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
         }
         c->b_recs_key.resize(c->b_recs.size());
         for (int l = 1; l <= c->batch_lanes; ++l)
-            if ((rc = c->xovf[l].ensure((size_t)c->num_cus * 8 * 256 * 24 * sizeof(uint32_t), false, c->stream))) return rc;
+            if ((rc = c->lanes[l].ovf.ensure(side_ovf_bytes(c), false, c->stream))) return rc;
     }
     if (need_alloc || recs_stale) {
         // per-launch records of the lamp columns whose array holds something else
         for (int g = 0; g < ngroups; ++g) {
             uvrt_ctx::RecsKey& key = c->b_recs_key[g];
-            if (key.perm == gperm[g] && key.gen == ggen[g] && key.valid && memcmp(&key.ox, &gx[g], 4) == 0 && memcmp(&key.oz, &gz[g], 4) == 0) continue;
+            if (key.holds(gx[g], gz[g], gperm[g], ggen[g])) continue;
             launch_prepare_launch6(c->pairs.as<PairRec>(), c->b_recs[g].p, gx[g], gz[g], c->npairs, gperm[g], c->stream);
-            key.ox = gx[g]; key.oz = gz[g]; key.perm = gperm[g]; key.gen = ggen[g]; key.valid = true;
+            key = {{true, gx[g], gz[g]}, gperm[g], ggen[g]};
         }
         HIP_TRY(hipGetLastError());
         if (int rcf = mark_fence(c)) return rcf;         // the lanes' next work waits for the records
@@ -153,7 +152,7 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
             // the chunk's rays depend on nothing but their buffer: generate goes to the lane BEFORE the lane waits for the
             // context's stream (new records, a hot-record set-up), so it runs beside them
             hipStream_t ls = stream_of(c, c->lane);
-            if (c->lane != 0) c->side_used[c->lane] = true;
+            if (c->lane != 0) cur_lane(c).used = true;
             if (!lane_waited[c->lane]) {      // the set's previous occupant has been replayed (two batches back)
                 HIP_TRY(hipStreamWaitEvent(ls, S.free_ev, 0));
                 lane_waited[c->lane] = true;
@@ -177,58 +176,25 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
             launch_generate_batch(gq, ls);
             if (int rcl = lane_stream(c, &ls)) return rcl;      // extend: after the fence
             ExtendParams p;
-            memset(&p, 0, sizeof p);
-            p.scene.pairs = c->pairs.as<PairRec>();
-            p.scene.ltris = c->ltris.as<LeafTri>();
-            p.scene.leaf_count = c->leaf_count.as<uint32_t>();
-            p.scene.root_ref = c->root_ref;
-            p.scene.tri_count = c->T;
+            fill_launch(c, p, gx[g], gz[g]);
             p.rays = gq.rays;
-            {
-                const float ax = std::fabs(gx[g]), az = std::fabs(gz[g]);
-                const float tiny = 7.888609e-31f;   // 2^-100
-                p.force_exact = (c->scene_force_exact || (ax != 0.0f && ax < tiny) || (az != 0.0f && az < tiny) ||
-                                 !(ax <= 1e9f) || !(az <= 1e9f) || (c->variant >= 500 && c->variant < 600)) ? 1 : 0;
-            }
-            p.ovf_stack = lane_ovf(c).as<uint32_t>();
-            p.ovf_capacity = lane_ovf(c).bytes / sizeof(uint32_t);
-            p.num_cus = lane_cus(c);
-            p.flavour = c->flavour;
-            p.top_pairs = c->top_pairs;
             p.counts = S.planes.as<int32_t>() + (size_t)ph0 * plane_ints;
             p.count_replicas = R;
             p.count_stride = c->T;
-            p.error_flag = c->host_flag_dev ? c->host_flag_dev : c->error_flag.as<uint32_t>();
-            p.ox = gx[g];
-            p.oz = gz[g];
             p.n = (int64_t)kc * n_pad;
-            p.npairs = c->npairs;
             p.recs = c->b_recs[g].p;
             p.perm = gperm[g];
             p.recs_prepared = 1;
-            p.drain_merge = c->drain_merge;
-            p.refill_min = variant_refill_min(c->variant, (size_t)c->npairs + (size_t)c->T);
             p.plane_batches = (uint32_t)(n_pad / 64);
             p.plane_n = (uint32_t)n;
             p.plane_stride = (uint32_t)plane_ints;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (c->timing) {
-                if (c->ev_used == c->ev_pool.size()) {
-                    hipEvent_t a, b;
-                    HIP_TRY(hipEventCreate(&a));
-                    HIP_TRY(hipEventCreate(&b));
-                    c->ev_pool.emplace_back(a, b);
-                }
-                e0 = c->ev_pool[c->ev_used].first;
-                e1 = c->ev_pool[c->ev_used].second;
-                ++c->ev_used;
-                HIP_TRY(hipEventRecord(e0, ls));
-            }
+            hipEvent_t e1;
+            if (int rct = timing_start(c, ls, &e1)) return rct;
             if (!launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, c->pipeline ? 7 : 8), ls)) {
                 return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: variant %d needs a larger overflow-stack buffer", c->variant);
             }
             HIP_TRY(hipGetLastError());
-            if (c->timing) HIP_TRY(hipEventRecord(e1, ls));
+            if (e1) HIP_TRY(hipEventRecord(e1, ls));
         }
     }
 #ifdef UVRT_DEV_VARIANTS

@@ -88,11 +88,12 @@ int set_lane_cu_mask(uvrt_ctx* c, int reserve)
         }
     }
     for (int l = 1; l < uvrt_ctx::MAXL; ++l) {
-        if (c->side[l]) { (void)hipStreamSynchronize(c->side[l]); (void)hipStreamDestroy(c->side[l]); }
-        c->side[l] = fresh[l];
-        c->side_used[l] = false;
-        c->side_seen_fence[l] = 0;            // the new stream has seen no fence: it waits for the current ones at first use
-        c->side_seen_mapfence[l] = 0;
+        Lane& L = c->lanes[l];
+        if (L.side) { (void)hipStreamSynchronize(L.side); (void)hipStreamDestroy(L.side); }
+        L.side = fresh[l];
+        L.used = false;
+        L.seen_fence = 0;                     // the new stream has seen no fence: it waits for the current ones at first use
+        L.seen_mapfence = 0;
     }
     c->lanes_masked_cus = reserve;
     return UVRT_OK;
@@ -231,16 +232,16 @@ int uvrt_reduce_batch_group(uvrt_ctx** ctxs, int32_t n)
     uvrt_ctx* c0 = ctxs[0];
     if (int rc = set_device(c0)) return rc;
     for (int i = 1; i < n; ++i) {
-        HIP_TRY(hipEventRecord(ctxs[i]->ev_tail[0], ctxs[i]->stream));
-        HIP_TRY(hipStreamWaitEvent(c0->stream, ctxs[i]->ev_tail[0], 0));
+        HIP_TRY(hipEventRecord(ctxs[i]->lanes[0].ev_tail, ctxs[i]->stream));
+        HIP_TRY(hipStreamWaitEvent(c0->stream, ctxs[i]->lanes[0].ev_tail, 0));
         launch_add_counts(c0->bs[c0->b_set].folded.as<int32_t>(), ctxs[i]->bs[ctxs[i]->b_set].folded.as<int32_t>(), (int64_t)count, c0->stream);
     }
     HIP_TRY(hipGetLastError());
     for (int i = 1; i < n; ++i)
         HIP_TRY(hipMemcpyAsync(ctxs[i]->bs[ctxs[i]->b_set].folded.p, c0->bs[c0->b_set].folded.p, count * 4, hipMemcpyDeviceToDevice, c0->stream));
-    HIP_TRY(hipEventRecord(c0->ev_tail[0], c0->stream));
+    HIP_TRY(hipEventRecord(c0->lanes[0].ev_tail, c0->stream));
     for (int i = 1; i < n; ++i) {
-        HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, c0->ev_tail[0], 0));
+        HIP_TRY(hipStreamWaitEvent(ctxs[i]->stream, c0->lanes[0].ev_tail, 0));
     }
     return UVRT_OK;
 }

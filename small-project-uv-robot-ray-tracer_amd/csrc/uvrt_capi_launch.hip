@@ -13,7 +13,7 @@ int hot_reset(uvrt_ctx* c, bool slab)
     c->hot.clear();
     for (DevBuf& b : c->hot_slabs) b.release();
     c->hot_slabs.clear();
-    for (int l = 0; l < uvrt_ctx::MAXL; ++l) { c->hot_hist[l].release(); c->hot_list[l].release(); c->lane_perm[l] = nullptr; }
+    for (Lane& L : c->lanes) { L.hot_hist.release(); L.hot_list.release(); L.perm = nullptr; }
     if (!slab || c->npairs <= 128) return UVRT_OK;
     // the first slab and the lanes' scratch come with the scene: a new lamp position then costs no allocation
     c->hot_slabs.emplace_back();
@@ -21,8 +21,8 @@ int hot_reset(uvrt_ctx* c, bool slab)
     for (int l = 0; l < c->nlanes || l < 3; ++l) {
         // lane 0 (uvrt_trace_batch) sets up all new lamps of a batch in one launch: room for HS_GROUPS of them where that is small
         const size_t groups = (l == 0 && (size_t)c->npairs * 4 * HS_GROUPS <= ((size_t)64 << 20)) ? (size_t)HS_GROUPS : 1;
-        if (int rc = c->hot_hist[l].ensure(groups * (size_t)c->npairs * 4, true, c->stream)) return rc;
-        if (int rc = c->hot_list[l].ensure(groups * ((size_t)TOP6_MAX + 1) * 4, false, c->stream)) return rc;
+        if (int rc = c->lanes[l].hot_hist.ensure(groups * (size_t)c->npairs * 4, true, c->stream)) return rc;
+        if (int rc = c->lanes[l].hot_list.ensure(groups * ((size_t)TOP6_MAX + 1) * 4, false, c->stream)) return rc;
     }
     return UVRT_OK;
 }
@@ -73,11 +73,12 @@ int hot_lookup(uvrt_ctx* c, const float lamp[3], hipStream_t s, const uint32_t**
 int hot_build(uvrt_ctx* c, uvrt_ctx::HotEntry* const* entries, const uint32_t* seed_prev, const uint32_t* seed_next, int count,
               float light_length, hipStream_t s, int lane)
 {
+    Lane& L = c->lanes[lane];
     for (int k0 = 0; k0 < count; k0 += HS_GROUPS) {
         const int kc = std::min(HS_GROUPS, count - k0);
         // scratch of the set-up kernels, per launch lane: visit counters (zero between uses) and the hot lists
-        if (int rc = c->hot_hist[lane].ensure((size_t)kc * (size_t)c->npairs * 4, true, s)) return rc;
-        if (int rc = c->hot_list[lane].ensure((size_t)kc * ((size_t)TOP6_MAX + 1) * 4, false, s)) return rc;
+        if (int rc = L.hot_hist.ensure((size_t)kc * (size_t)c->npairs * 4, true, s)) return rc;
+        if (int rc = L.hot_list.ensure((size_t)kc * ((size_t)TOP6_MAX + 1) * 4, false, s)) return rc;
         HotSetupParams p;
         memset(&p, 0, sizeof p);
         p.pairs = c->pairs.as<PairRec>();
@@ -94,8 +95,8 @@ int hot_build(uvrt_ctx* c, uvrt_ctx::HotEntry* const* entries, const uint32_t* s
         p.npairs = c->npairs;
         p.keep = (int32_t)TOP6_MAX;
         p.count = kc;
-        p.hist = c->hot_hist[lane].as<uint32_t>();
-        p.hot_list = c->hot_list[lane].as<uint32_t>();
+        p.hist = L.hot_hist.as<uint32_t>();
+        p.hot_list = L.hot_list.as<uint32_t>();
         for (int k = 0; k < kc; ++k) {
             const uvrt_ctx::HotEntry* e = entries[k0 + k];
             p.perm[k] = e->perm;
@@ -169,21 +170,20 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
     // launch lane: alternate between the two streams / buffer sets when nothing stands against it
     {
         const bool pipe_ok = c->pipeline && c->nlanes > 1 && !c->record_hits && bits == 0 &&
-                             c->xrays[1].p;
+                             c->lanes[1].rays.p;
         c->prev_lane = c->lane;
         c->cur_pipelined = pipe_ok;
         if (pipe_ok) c->lane = (c->lane + 1) % c->nlanes;
         else { if (int rc = join_all(c)) return rc; c->lane = 0; }
-        if (c->lane != 0) {
-            // 8 workgroups per CU x 256 threads x 24 overflow entries (the largest grid a side lane runs)
-            if (int rc = c->xovf[c->lane].ensure((size_t)c->num_cus * 8 * 256 * 24 * sizeof(uint32_t), false, c->stream)) return rc;
-        }
+        if (c->lane != 0)
+            if (int rc = cur_lane(c).ovf.ensure(side_ovf_bytes(c), false, c->stream)) return rc;
     }
+    Lane& L = cur_lane(c);
     hipStream_t ls;
     if (int rc = lane_stream(c, &ls)) return rc;
     GenParams p;
     memset(&p, 0, sizeof p);
-    p.rays = lane_rays(c).as<float4>();
+    p.rays = L.rays.as<float4>();
     p.lx = lp[0]; p.ly = lp[1]; p.lz = lp[2];
     p.light_length = light_length;
     p.first_gid = first_gid;
@@ -208,23 +208,21 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
     }
     if (c->npairs > 0) {   // extend's per-launch records ride along in the same launch
         p.prep_pairs = c->pairs.as<PairRec>();
-        p.prep_recs = lane_recs(c).as<float4>();
+        p.prep_recs = L.recs.as<float4>();
         // launches too small to repay the statistics keep the breadth-first order
         const uint32_t* pm = c->have_perm ? c->perm.as<uint32_t>() : nullptr;
         if (!pm && n >= 16384)
             if (int rc = launch_perm(c, lp, light_length, seed_prev, seed_next, ls, c->lane, &pm)) return rc;
-        c->lane_perm[c->lane] = pm;
+        L.perm = pm;
         p.prep_perm = pm;
         p.prep_npairs = c->npairs;
     }
     launch_generate(p, ls);
     HIP_TRY(hipGetLastError());
-    (c->lane ? c->xrecs_valid[c->lane] : c->recs_valid) = p.prep_recs != nullptr;
-    (c->lane ? c->xrecs_ox[c->lane] : c->recs_ox) = lp[0];
-    (c->lane ? c->xrecs_oz[c->lane] : c->recs_oz) = lp[2];
-    if (p.keyrank) {
+    L.recs_tag = {p.prep_recs != nullptr, lp[0], lp[2]};
+    if (p.keyrank) {     // (ray ordering keeps the launch on lane 0)
         launch_scan_bins(c->hist.as<uint32_t>(), c->bin_start.as<uint32_t>(), 1 << bits, c->stream);
-        launch_scatter(c->rays.as<float4>(), c->keyrank.as<uint2>(), c->bin_start.as<uint32_t>(),
+        launch_scatter(L.rays.as<float4>(), c->keyrank.as<uint2>(), c->bin_start.as<uint32_t>(),
                        c->sorted.as<float4>(), c->order.as<uint32_t>(), n, c->stream);
         HIP_TRY(hipGetLastError());
     }
@@ -248,97 +246,51 @@ int uvrt_extend(uvrt_ctx* c, int64_t n)
     if (c->record_hits) {
         if (int rc = c->hits.ensure((size_t)c->capacity * 8, false, c->stream)) return rc;
     }
+    Lane& L = cur_lane(c);
     ExtendParams p;
-    memset(&p, 0, sizeof p);
-    p.scene.pairs = c->pairs.as<PairRec>();
-    p.scene.ltris = c->ltris.as<LeafTri>();
-    p.scene.leaf_count = c->leaf_count.as<uint32_t>();
-    p.scene.root_ref = c->root_ref;
-    p.scene.tri_count = c->T;
+    fill_launch(c, p, c->ox, c->oz);
     hipStream_t ls;
     if (int rc = lane_stream(c, &ls)) return rc;
-    p.rays = c->last_sorted ? c->sorted.as<float4>() : lane_rays(c).as<float4>();
-    {
-        // conditions of the reciprocal shortcut that are uniform over the launch (slab<>())
-        const float ax = std::fabs(c->ox), az = std::fabs(c->oz);
-        const float tiny = 7.888609e-31f;   // 2^-100
-        p.force_exact = (c->scene_force_exact || (ax != 0.0f && ax < tiny) || (az != 0.0f && az < tiny) ||
-                         !(ax <= 1e9f) || !(az <= 1e9f)) ? 1 : 0;
-    }
+    p.rays = c->last_sorted ? c->sorted.as<float4>() : L.rays.as<float4>();
     p.order = c->last_sorted ? c->order.as<uint32_t>() : nullptr;
     p.hits = c->record_hits ? c->hits.as<uint2>() : nullptr;
-    p.ovf_stack = lane_ovf(c).as<uint32_t>();
-    p.ovf_capacity = lane_ovf(c).bytes / sizeof(uint32_t);
-    p.num_cus = lane_cus(c);
-    p.flavour = c->flavour;
-    p.top_pairs = c->top_pairs;
-    p.counts = lane_counts(c).as<int32_t>();
+    p.counts = L.counts.as<int32_t>();
     p.count_replicas = c->replicas;
     p.count_stride = c->T;
-    p.error_flag = c->host_flag_dev ? c->host_flag_dev : c->error_flag.as<uint32_t>();
-    p.ox = c->ox;
-    p.oz = c->oz;
     p.n = n;
-    p.npairs = c->npairs;
-    p.recs = lane_recs(c).p;
-    p.perm = c->have_perm ? c->perm.as<uint32_t>() : c->lane_perm[c->lane];
-    {
-        const bool valid = c->lane ? c->xrecs_valid[c->lane] : c->recs_valid;
-        const float rox = c->lane ? c->xrecs_ox[c->lane] : c->recs_ox, roz = c->lane ? c->xrecs_oz[c->lane] : c->recs_oz;
-        p.recs_prepared = (valid && memcmp(&rox, &c->ox, 4) == 0 && memcmp(&roz, &c->oz, 4) == 0) ? 1 : 0;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        if (c->ev_used == c->ev_pool.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            c->ev_pool.emplace_back(a, b);
-        }
-        e0 = c->ev_pool[c->ev_used].first;
-        e1 = c->ev_pool[c->ev_used].second;
-        ++c->ev_used;
-        HIP_TRY(hipEventRecord(e0, ls));
-    }
+    p.recs = L.recs.p;
+    p.perm = c->have_perm ? c->perm.as<uint32_t>() : L.perm;
+    p.recs_prepared = L.recs_tag.matches(c->ox, c->oz) ? 1 : 0;
+    hipEvent_t e1;
+    if (int rc = timing_start(c, ls, &e1)) return rc;
     if (c->wide && c->nquads > 0) {
         // the opt-in 4-wide walk: its per-launch records are (re)made here when the lane's are for another lamp
-        DevBuf& r4 = c->recs4[c->lane];
-        if (!r4.p) {
-            if (int rc = r4.ensure(((size_t)2 * c->nquads + (size_t)c->T + 1) * 64, true, ls)) return rc;
-            launch_prepare_leaves6(c->ltris.as<LeafTri>(), r4.p, 2 * c->nquads, c->T, ls);
-            c->recs4_valid[c->lane] = false;
+        if (!L.recs4.p) {
+            if (int rc = L.recs4.ensure(((size_t)2 * c->nquads + (size_t)c->T + 1) * 64, true, ls)) return rc;
+            launch_prepare_leaves6(c->ltris.as<LeafTri>(), L.recs4.p, 2 * c->nquads, c->T, ls);
+            L.recs4_tag.valid = false;
         }
-        if (!c->recs4_valid[c->lane] || memcmp(&c->recs4_ox[c->lane], &c->ox, 4) != 0 || memcmp(&c->recs4_oz[c->lane], &c->oz, 4) != 0) {
-            launch_prepare_launch4(c->quads.as<QuadRec>(), r4.p, c->ox, c->oz, c->nquads, ls);
-            c->recs4_valid[c->lane] = true;
-            c->recs4_ox[c->lane] = c->ox;
-            c->recs4_oz[c->lane] = c->oz;
+        if (!L.recs4_tag.matches(c->ox, c->oz)) {
+            launch_prepare_launch4(c->quads.as<QuadRec>(), L.recs4.p, c->ox, c->oz, c->nquads, ls);
+            L.recs4_tag = {true, c->ox, c->oz};
         }
-        p.recs4 = r4.p;
+        p.recs4 = L.recs4.p;
         p.nquads = c->nquads;
         p.top_quads = c->top_quads;
         p.refill_min = 8;
-        if (c->variant >= 500 && c->variant < 600) p.force_exact = 1;
         if (!launch_extend4(p, 7, ls)) return fail(UVRT_ERR_INVALID, "uvrt_extend: overflow-stack buffer too small for the 4-wide kernel");
-        HIP_TRY(hipGetLastError());
-        if (c->timing) HIP_TRY(hipEventRecord(e1, ls));
-        c->counts_dirty[c->lane] = true;
-        c->last_extended = c->record_hits;
-        return UVRT_OK;
+    } else {
+        // default grid: 8 workgroups per CU on one stream (20 KB of LDS each: eight fit a CU); 7 when launches are
+        // pipelined over several streams -- the free slot per CU lets the first workgroups of the next launch and the
+        // small kernels around it (generate, accumulate, replay) run at once instead of queueing behind persistent waves
+        // (profiles/r02/r02_experiments.txt); with four launch lanes 4 per CU
+        const int per_cu_default = (c->cur_pipelined && c->nlanes >= 4) ? 4 : c->cur_pipelined ? 7 : 8;
+        if (!launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, per_cu_default), ls))
+            return fail(UVRT_ERR_INVALID, "uvrt_extend: variant %d needs a larger overflow-stack buffer than the context holds", c->variant);
     }
-    if (c->variant >= 500 && c->variant < 600) p.force_exact = 1;
-    p.refill_min = variant_refill_min(c->variant, (size_t)c->npairs + (size_t)c->T);
-    // default grid: 8 workgroups per CU on one stream (20 KB of LDS each: eight fit a CU); 7 when launches are
-    // pipelined over several streams -- the free slot per CU lets the first workgroups of the next launch and the
-    // small kernels around it (generate, accumulate, replay) run at once instead of queueing behind persistent waves
-    // (profiles/r02/r02_experiments.txt); with four launch lanes 4 per CU
-    const int per_cu_default = (c->cur_pipelined && c->nlanes >= 4) ? 4 : c->cur_pipelined ? 7 : 8;
-    p.drain_merge = c->drain_merge;
-    if (!launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, per_cu_default), ls))
-        return fail(UVRT_ERR_INVALID, "uvrt_extend: variant %d needs a larger overflow-stack buffer than the context holds", c->variant);
     HIP_TRY(hipGetLastError());
-    if (c->timing) HIP_TRY(hipEventRecord(e1, ls));
-    c->counts_dirty[c->lane] = true;
+    if (e1) HIP_TRY(hipEventRecord(e1, ls));
+    L.counts_dirty = true;
     c->last_extended = c->record_hits;
     return UVRT_OK;
 }
@@ -359,10 +311,10 @@ int uvrt_accumulate(uvrt_ctx* c, float time_step, int32_t tri_count)
         c->pend.valid = true;
         c->pend.lane = c->lane;
         c->pend.time_step = time_step;
-        c->counts_dirty[c->lane] = false;
+        cur_lane(c).counts_dirty = false;
         return UVRT_OK;
     }
-    launch_accumulate(c->photon_map.as<double>(), c->max_map.as<double>(), lane_counts(c).as<int32_t>(),
+    launch_accumulate(c->photon_map.as<double>(), c->max_map.as<double>(), cur_lane(c).counts.as<int32_t>(),
                       c->replicas, c->T, time_step, tri_count, ls);
     HIP_TRY(hipGetLastError());
     return UVRT_OK;
@@ -411,7 +363,7 @@ int uvrt_shade(uvrt_ctx* c, int32_t which, int32_t photons_per_light, float scal
         hipStream_t fs;
         if (int rc = lane_stream(c, &fs, true)) return rc;
         c->pend.valid = false;
-        launch_accumulate_shade(c->photon_map.as<double>(), c->max_map.as<double>(), lane_counts(c).as<int32_t>(), c->replicas,
+        launch_accumulate_shade(c->photon_map.as<double>(), c->max_map.as<double>(), cur_lane(c).counts.as<int32_t>(), c->replicas,
                                 c->T, c->pend.time_step, c->dosage.as<float>(), c->area.as<float>(), c->color.as<float>(),
                                 which == UVRT_MAP_SUM ? 0 : 1, photons_per_light, scaled_power, min_value, threshold_view,
                                 tri_count, fs);

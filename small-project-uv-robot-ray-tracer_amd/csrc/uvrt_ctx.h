@@ -5,8 +5,8 @@
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
-// (raytracer.h:50-53).  There is no CPU fallback: every entry point either runs on the GPU or
-// returns an error.
+// (raytracer.h:50-53), its per-launch state split over launch lanes (struct Lane).
+// There is no CPU fallback: every entry point either runs on the GPU or returns an error.
 #pragma once
 #include "../../include/uvrt.h"
 #include "uvrt_device.h"
@@ -51,9 +51,36 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// What an array of per-launch records is prepared for: the lamp column (ox, oz).  Compared bitwise, so that
+// -0.0f and 0.0f are different columns.
+struct RecsTag {
+    bool valid = false;
+    float ox = 0, oz = 0;
+    bool matches(float x, float z) const { return valid && memcmp(&ox, &x, 4) == 0 && memcmp(&oz, &z, 4) == 0; }
+};
+
+// A launch lane: a stream with its own ray, record, count and overflow-stack buffers.
+// Lane 0 runs on the context's stream, which uvrt_set_stream may replace: stream_of() is the one place that knows it.
+struct Lane {
+    hipStream_t side = nullptr;      // the lane's own stream (lanes 1..MAXL-1; null for lane 0)
+    hipEvent_t ev_tail = nullptr;    // tail of the lane's stream
+    bool used = false;               // the side stream holds work the main stream is not ordered after
+    uint64_t seen_fence = 0, seen_mapfence = 0;   // the last fence / map fence the side stream waits for
+    DevBuf rays, recs, counts;       // rays of the launch; records [0, npairs) per launch + leaf records; replicas x T deposits
+    DevBuf ovf;                      // traversal-stack entries 8..31 of every thread of the persistent grid
+    RecsTag recs_tag;                // what recs[0, npairs) is prepared for
+    bool counts_dirty = false;       // `counts` holds deposits that were not accumulated
+    DevBuf recs4;                    // 4-wide walk: [2 * nquads + T + 1] 64-byte units, per-launch form + leaf records
+    RecsTag recs4_tag;               // what the per-launch part of recs4 is prepared for
+    DevBuf hot_hist, hot_list;       // scratch of the hot-record set-up kernels (uvrt_hotset.hip)
+    const uint32_t* perm = nullptr;  // renumbering of the lane's current launch (set by uvrt_generate)
+};
+
 }  // namespace uvrt_impl
 
 using uvrt_impl::DevBuf;
+using uvrt_impl::Lane;
+using uvrt_impl::RecsTag;
 
 struct uvrt_ctx {
     int device = 0;
@@ -63,7 +90,7 @@ struct uvrt_ctx {
 
     // scene
     int32_t T = 0;
-    DevBuf pairs, recs, perm, ltris, leaf_count, area;
+    DevBuf pairs, perm, ltris, leaf_count, area;
     bool have_perm = false;      // the caller's own record renumbering (uvrt_set_record_perm)
     uint64_t perm_clock = 0;     // stamps every renumbering written into `perm` or a hot entry
     uint64_t perm_gen = 0;       // stamp of what `perm` holds
@@ -75,14 +102,11 @@ struct uvrt_ctx {
     int32_t replicas_knob = -1;  // -1: choose from T
 
     // per-triangle maps (raytracer.cpp:32-37)
-    DevBuf photon_map, max_map, counts, dosage, color;
+    DevBuf photon_map, max_map, dosage, color;
 
-    // rays
+    // rays (the launch's own rays are per launch lane)
     int64_t capacity = 0;
-    DevBuf rays, keyrank, sorted, order, hits, hist, bin_start, export_buf;
-    DevBuf ovf_stack;                          // traversal-stack entries 8..31 of every thread of the persistent grid
-    bool recs_valid = false;                   // recs[0, npairs) prepared for the lamp (recs_ox, recs_oz)
-    float recs_ox = 0, recs_oz = 0;
+    DevBuf keyrank, sorted, order, hits, hist, bin_start, export_buf;
     bool drain_merge = true;                   // k_extend6's workgroups pool the last rays of their waves (ExtendParams::drain_merge; developer knob UVRT_DRAIN_MERGE=0)
     bool scene_force_exact = false;            // a node bound too tiny / too large for the reciprocal shortcuts
     int32_t hist_bins = 0;
@@ -96,52 +120,42 @@ struct uvrt_ctx {
     // shade) alternate between the context's stream and an internal side stream, each with its own
     // ray, record, count and overflow-stack buffers, so that the next launch fills the wave slots the
     // draining launch frees.  The per-triangle maps are updated in launch order (event waits).
-    static constexpr int MAXL = 4;    // lane 0 = the context's stream and the buffers above
+    static constexpr int MAXL = 4;
+    Lane lanes[MAXL];                 // lane 0 runs on the context's stream, lanes 1.. on their side streams
     bool pipeline = true;             // uvrt_set_pipeline
     int nlanes = 2;                   // developer knob UVRT_LANES (1..MAXL): 3 gain ~1 %, 4 (with 4 workgroups
                                       // per CU) win only for long launch sequences (profiles/r01/r01_v6_experiments.txt)
     bool ext_touch = false;           // a count-buffer pointer was handed out since the last fence
     bool ext_touch_maps = false;      // a map / dose / colour pointer was handed out since the last map fence
-    bool counts_dirty[MAXL] = {};     // the lane's count buffer holds deposits that were not accumulated
     hipEvent_t ev_mapfence = nullptr; // on the main stream, after the last operation on the per-triangle maps
-    uint64_t mapfence_seq = 0, side_seen_mapfence[MAXL] = {};
+    uint64_t mapfence_seq = 0;
     int lane = 0;                     // lane of the current launch (uvrt_generate selects it)
     int prev_lane = 0;                // lane of the launch before it (the maps are updated in launch order)
     bool cur_pipelined = false;       // the current launch takes part in the lane rotation
-    hipStream_t side[MAXL] = {};      // [0] unused
-    bool side_used[MAXL] = {};        // the side stream holds work the main stream is not ordered after
     hipEvent_t ev_fence = nullptr;    // on the main stream, after the last context-wide operation
-    hipEvent_t ev_tail[MAXL] = {};    // tail of a lane's stream
-    uint64_t fence_seq = 0, side_seen_fence[MAXL] = {};
-    DevBuf xrays[MAXL], xrecs[MAXL], xcounts[MAXL], xovf[MAXL];   // [0] unused: lane 0 has rays, recs, counts, ovf_stack
-    bool xrecs_valid[MAXL] = {};
-    float xrecs_ox[MAXL] = {}, xrecs_oz[MAXL] = {};
+    uint64_t fence_seq = 0;
 
-    // Opt-in 4-wide collapse of the BVH (uvrt_set_wide_bvh, uvrt_extend4.hip)
+    // Opt-in 4-wide collapse of the BVH (uvrt_set_wide_bvh, uvrt_extend4.hip; per-launch records in Lane::recs4)
     bool wide = false;
     DevBuf quads;                         // [nquads] QuadRec, scene form
-    DevBuf recs4[MAXL];                   // per lane: [2 * nquads + T + 1] 64-byte units, per-launch form + leaf records
     int32_t nquads = 0;
     uint32_t top_quads = 0;
-    bool recs4_valid[MAXL] = {};          // recs4[l] hold the per-launch records of lamp column (recs4_ox, recs4_oz)
-    float recs4_ox[MAXL] = {}, recs4_oz[MAXL] = {};
 
     // Hot-record renumbering per lamp position (uvrt_hotset.hip): the records a lamp's photons visit most are
     // the ones the traversal serves from LDS.  Built on the device the first time a lamp is seen.
     // The renumberings live in slabs of HOT_SLAB entries (the first one allocated with the scene, so that a new lamp
     // costs no allocation); the visit counters and the hot list are scratch of the three set-up kernels, one set per
-    // launch lane (the kernels of one lamp run back to back on one stream and leave the counters zeroed).
+    // launch lane (Lane::hot_hist, hot_list: the kernels of one lamp run back to back on one stream and leave the
+    // counters zeroed).
     static constexpr int HOT_SLAB = 16, HOT_MAX = 64;
     struct HotEntry { float lamp[3]; uint32_t* perm; uint64_t stamp; hipEvent_t ready; uint64_t gen; };
     std::vector<HotEntry> hot;
     std::vector<DevBuf> hot_slabs;        // [ceil(entries / HOT_SLAB)]: HOT_SLAB x npairs uint32 each
-    DevBuf hot_hist[MAXL], hot_list[MAXL];
     int32_t hot_sample = 32768;           // photons of the launch whose visits are counted (developer knob UVRT_HOT_SAMPLE)
     int32_t hot_direct = 8192;            // records k_select_hot takes as candidates without a tree walk (developer knob UVRT_HOT_DIRECT; tests force the walk with it)
     int32_t hot_tail = 16;                // straggler rule of k_visit_stats (developer knob UVRT_HOT_TAIL, uvrt_hotset.hip)
     uint64_t hot_clock = 0;
     int32_t hot_mode = 1;                 // uvrt_set_hot_records: 1 = automatic (default), 0 = breadth-first order
-    const uint32_t* lane_perm[MAXL] = {}; // renumbering of the current launch of each lane (set by uvrt_generate)
 
     // Batched tracing (uvrt_trace_batch): the rays of up to MAX_BATCH launches side by side, one count
     // "plane" (replicas x T ints) per launch, one per-launch record array per distinct lamp.
@@ -156,7 +170,10 @@ struct uvrt_ctx {
     std::vector<DevBuf> b_recs;           // [group]
     // `gen` tells two renumberings apart that live at ONE address: the caller's buffer after another
     // uvrt_set_record_perm, a hot entry recycled for another lamp (perm_clock stamps every (re)written renumbering)
-    struct RecsKey { float ox = 0, oz = 0; const uint32_t* perm = nullptr; uint64_t gen = 0; bool valid = false; };
+    struct RecsKey {
+        RecsTag tag; const uint32_t* perm = nullptr; uint64_t gen = 0;
+        bool holds(float ox, float oz, const uint32_t* pm, uint64_t g) const { return tag.matches(ox, oz) && perm == pm && gen == g; }
+    };
     std::vector<RecsKey> b_recs_key;      // what b_recs[g] holds
     int32_t b_count = 0;                  // launches of the batch that has not been replayed (0: none)
     int64_t b_n = 0, b_npad = 0;
@@ -212,7 +229,10 @@ namespace uvrt_impl {
 using namespace uvrt;
 
 // ---- launch lanes ----
-inline hipStream_t stream_of(uvrt_ctx* c, int l) { return l == 0 ? c->stream : c->side[l]; }
+inline hipStream_t stream_of(uvrt_ctx* c, int l) { return l == 0 ? c->stream : c->lanes[l].side; }
+inline Lane& cur_lane(uvrt_ctx* c) { return c->lanes[c->lane]; }
+// a side lane's overflow stack: 8 workgroups per CU x 256 threads x 24 entries (the largest grid a side lane runs)
+inline size_t side_ovf_bytes(const uvrt_ctx* c) { return (size_t)c->num_cus * 8 * 256 * 24 * sizeof(uint32_t); }
 
 inline int set_device_only(uvrt_ctx* c)
 {
@@ -225,7 +245,7 @@ inline int flush_pending(uvrt_ctx* c)
     if (!c->pend.valid) return UVRT_OK;
     c->pend.valid = false;
     const int l = c->pend.lane;
-    launch_accumulate(c->photon_map.as<double>(), c->max_map.as<double>(), (l ? c->xcounts[l] : c->counts).as<int32_t>(),
+    launch_accumulate(c->photon_map.as<double>(), c->max_map.as<double>(), c->lanes[l].counts.as<int32_t>(),
                       c->replicas, c->T, c->pend.time_step, c->T, stream_of(c, l));
     HIP_TRY(hipGetLastError());
     return UVRT_OK;
@@ -241,10 +261,11 @@ inline int set_device(uvrt_ctx* c)
 inline int join_all(uvrt_ctx* c)
 {
     for (int l = 1; l < uvrt_ctx::MAXL; ++l) {
-        if (!c->side_used[l]) continue;
-        HIP_TRY(hipEventRecord(c->ev_tail[l], c->side[l]));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_tail[l], 0));
-        c->side_used[l] = false;
+        Lane& L = c->lanes[l];
+        if (!L.used) continue;
+        HIP_TRY(hipEventRecord(L.ev_tail, L.side));
+        HIP_TRY(hipStreamWaitEvent(c->stream, L.ev_tail, 0));
+        L.used = false;
     }
     return UVRT_OK;
 }
@@ -271,18 +292,18 @@ inline int lane_stream(uvrt_ctx* c, hipStream_t* out, bool maps = false)
     // external work enqueued on the main stream since a device pointer was handed out
     if (c->ext_touch) { c->ext_touch = false; if (int rc = mark_fence(c)) return rc; }
     if (c->ext_touch_maps) { c->ext_touch_maps = false; if (int rc = mark_map_fence(c)) return rc; }
-    const int l = c->lane;
-    if (l == 0) { *out = c->stream; return UVRT_OK; }
-    if (c->fence_seq != c->side_seen_fence[l]) {
-        HIP_TRY(hipStreamWaitEvent(c->side[l], c->ev_fence, 0));
-        c->side_seen_fence[l] = c->fence_seq;
+    if (c->lane == 0) { *out = stream_of(c, 0); return UVRT_OK; }
+    Lane& L = cur_lane(c);
+    if (c->fence_seq != L.seen_fence) {
+        HIP_TRY(hipStreamWaitEvent(L.side, c->ev_fence, 0));
+        L.seen_fence = c->fence_seq;
     }
-    if (maps && c->mapfence_seq != c->side_seen_mapfence[l]) {
-        HIP_TRY(hipStreamWaitEvent(c->side[l], c->ev_mapfence, 0));
-        c->side_seen_mapfence[l] = c->mapfence_seq;
+    if (maps && c->mapfence_seq != L.seen_mapfence) {
+        HIP_TRY(hipStreamWaitEvent(L.side, c->ev_mapfence, 0));
+        L.seen_mapfence = c->mapfence_seq;
     }
-    c->side_used[l] = true;
-    *out = c->side[l];
+    L.used = true;
+    *out = L.side;
     return UVRT_OK;
 }
 // the current lane's stream becomes ordered after everything the previous launch's lane holds (its
@@ -292,17 +313,13 @@ inline int order_after_previous(uvrt_ctx* c)
     const int l = c->lane, q = c->prev_lane;
     if (q == l) return UVRT_OK;
     if (l == 0) return join_all(c);
-    HIP_TRY(hipEventRecord(c->ev_tail[q], stream_of(c, q)));
-    HIP_TRY(hipStreamWaitEvent(c->side[l], c->ev_tail[q], 0));
-    c->side_used[l] = true;
+    HIP_TRY(hipEventRecord(c->lanes[q].ev_tail, stream_of(c, q)));
+    HIP_TRY(hipStreamWaitEvent(c->lanes[l].side, c->lanes[q].ev_tail, 0));
+    c->lanes[l].used = true;
     return UVRT_OK;
 }
 // compute units the persistent grid of a launch on the current lane is sized for
 inline int lane_cus(const uvrt_ctx* c) { return c->lane == 0 ? c->num_cus : c->num_cus - c->lanes_masked_cus; }
-inline DevBuf& lane_rays(uvrt_ctx* c) { return c->lane ? c->xrays[c->lane] : c->rays; }
-inline DevBuf& lane_recs(uvrt_ctx* c) { return c->lane ? c->xrecs[c->lane] : c->recs; }
-inline DevBuf& lane_counts(uvrt_ctx* c) { return c->lane ? c->xcounts[c->lane] : c->counts; }
-inline DevBuf& lane_ovf(uvrt_ctx* c) { return c->lane ? c->xovf[c->lane] : c->ovf_stack; }
 
 // work-item 0's RNG walk of cl/generate.cl:13-39 on the host (strict f32/f64, same order)
 inline uint32_t host_wang_hash(uint32_t s)
@@ -360,6 +377,15 @@ inline int variant_refill_min(int v, size_t records)
     if (!variant_is_knob(v)) return records >= ((size_t)1 << 20) ? 24 : 8;
     return v >= 1200 ? 56 : v >= 1100 ? 48 : v >= 1000 ? 40 : v >= 900 ? 32 : v >= 800 ? 4 : v >= 700 ? 24 : v >= 600 ? 8 : 16;
 }
+// IEEE divisions for a launch from lamp column (ox, oz): the conditions of the reciprocal shortcut that are uniform over
+// the launch (slab<>()), or variants 500-599
+inline int variant_force_exact(int v, bool scene_force_exact, float ox, float oz)
+{
+    const float ax = std::fabs(ox), az = std::fabs(oz);
+    const float tiny = 7.888609e-31f;   // 2^-100
+    return (scene_force_exact || (ax != 0.0f && ax < tiny) || (az != 0.0f && az < tiny) || !(ax <= 1e9f) || !(az <= 1e9f) ||
+            (v >= 500 && v < 600)) ? 1 : 0;
+}
 inline int variant_code6(int v) { return !variant_is_knob(v) ? 1 : v % 10; }   // default: LDS top cache, leaf period 2
 inline int variant_per_cu(int v, int dflt)
 {
@@ -399,6 +425,42 @@ inline void fill_scene(const uvrt_ctx* c, ExtendParams& p)
     p.scene.leaf_count = c->leaf_count.as<uint32_t>();
     p.scene.root_ref = c->root_ref;
     p.scene.tri_count = c->T;
+}
+// The launch-uniform part of an ExtendParams for a walk on the current lane from lamp column (ox, oz); the caller adds
+// the rays, counts, records, renumbering and (batched) planes
+inline void fill_launch(uvrt_ctx* c, ExtendParams& p, float ox, float oz)
+{
+    memset(&p, 0, sizeof p);
+    fill_scene(c, p);
+    p.force_exact = variant_force_exact(c->variant, c->scene_force_exact, ox, oz);
+    p.error_flag = c->host_flag_dev ? c->host_flag_dev : c->error_flag.as<uint32_t>();
+    p.flavour = c->flavour;
+    p.top_pairs = c->top_pairs;
+    p.ovf_stack = cur_lane(c).ovf.as<uint32_t>();
+    p.ovf_capacity = cur_lane(c).ovf.bytes / sizeof(uint32_t);
+    p.num_cus = lane_cus(c);
+    p.ox = ox;
+    p.oz = oz;
+    p.npairs = c->npairs;
+    p.drain_merge = c->drain_merge;
+    p.refill_min = variant_refill_min(c->variant, (size_t)c->npairs + (size_t)c->T);
+}
+// the next pair of the extend timing pool (uvrt_extend_time_ms) with its start recorded on `s`; *stop stays null
+// while timing is off
+inline int timing_start(uvrt_ctx* c, hipStream_t s, hipEvent_t* stop)
+{
+    *stop = nullptr;
+    if (!c->timing) return UVRT_OK;
+    if (c->ev_used == c->ev_pool.size()) {
+        hipEvent_t a, b;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        c->ev_pool.emplace_back(a, b);
+    }
+    const auto& ev = c->ev_pool[c->ev_used++];
+    HIP_TRY(hipEventRecord(ev.first, s));
+    *stop = ev.second;
+    return UVRT_OK;
 }
 
 }  // namespace uvrt_impl
