@@ -14,7 +14,8 @@
 //
 // Per trip a lane fetches ONE 128-byte record (= one L2 line: seven dwordx4 loads, eight lookups in one L1
 // line instead of two BVH2 records in two lines) and makes at most one descent and three pushes; a ray
-// needs about half the trips of the BVH2 walk.
+// needs about half the trips of the BVH2 walk.  The ray feed (refill, retire, exact-step flag, grid sizing) is
+// k_extend6's, in uvrt_traverse.h.
 #include "uvrt_traverse.h"
 
 namespace uvrt {
@@ -160,59 +161,20 @@ __global__ __launch_bounds__(256, 6) void k_extend4(ExtendParams p)
     L.sp = 0;
     uint32_t slot = 0;
     bool live = false;
-    unsigned long long special_mask = 0;
     int32_t* const my_counts = p.counts + (int64_t)(blockIdx.x % (unsigned)p.count_replicas) * p.count_stride;
-    uint32_t plane_off = 0;
-    const float plane_inv = p.plane_inv;
+    uint32_t plane_off = 0;                 // as in k_extend6: bit 31 = the ray needs the exact step
     const uint32_t wave = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t W = gridDim.x * 4u;
     uint32_t cursor = 0;
     const uint32_t chunk_end = p.chunk;
-    const uint32_t n32 = (uint32_t)p.n;
     uint32_t trip = 0;
 
     for (;;) {
         const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
         const int nidle = __popcll(idle_mask);
         if (cursor < chunk_end && nidle >= p.refill_min) {
-            bool spec = false;
-            if (L.cur == REF_DONE) {
-                if (RECORD && live && p.hits) {
-                    const uint32_t li = p.order ? p.order[slot] : slot;
-                    p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
-                }
-                if (L.po.y != 1e30f) atomicAdd(&my_counts[plane_off + L.triID], 1);
-                live = false;
-                L.po.y = 1e30f;
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32),
-                                      __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
-                const uint32_t v = cursor + rank;
-                const uint32_t gb = (v >> 6) * W + wave;
-                const uint32_t my = gb * 64u + (v & 63u);
-                uint32_t pl = (uint32_t)((float)gb * plane_inv);
-                int32_t within = (int32_t)(gb - pl * p.plane_batches);
-                if (within < 0) { --pl; within += (int32_t)p.plane_batches; }
-                else if ((uint32_t)within >= p.plane_batches) { ++pl; within -= (int32_t)p.plane_batches; }
-                if (v < chunk_end && my < n32 && (uint32_t)within * 64u + (v & 63u) < p.plane_n) {
-                    set_in_place(plane_off, pl * p.plane_stride);
-                    const float4 rec = p.rays[my];
-                    set_in_place(L.px, rec.x, FL == 2 ? rcp_raw(rec.x) : rcp_exact(rec.x));
-                    set_in_place(L.py, rec.y, FL == 2 ? rcp_raw(rec.y) : rcp_exact(rec.y));
-                    set_in_place(L.pz, rec.z, FL == 2 ? rcp_raw(rec.z) : rcp_exact(rec.z));
-                    set_in_place(L.po, rec.w, 1e30f);
-                    set_in_place(L.triID, 0u);
-                    if (RECORD) { slot = my; live = true; }
-                    set_in_place(L.sp, 0);
-                    set_in_place(L.cur, p.root_ref4);
-                    const float ay = fabsf(rec.w), adx = fabsf(rec.x), ady = fabsf(rec.y), adz = fabsf(rec.z);
-                    const float dmin = 8.6736174e-19f;
-                    spec = FL != 2 && (!(adx >= dmin) || !(ady >= dmin) || !(adz >= dmin) ||
-                           !(adx <= 1.0f) || !(ady <= 1.0f) || !(adz <= 1.0f) ||
-                           (ay != 0.0f && ay < 7.888609e-31f) || !(ay <= 1e9f) || p.force_exact != 0);
-                }
-            }
+            if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, p.root_ref4);
             cursor += (uint32_t)nidle;
-            special_mask = (special_mask & ~idle_mask) | __builtin_amdgcn_ballot_w64(spec);
         }
         const unsigned long long act = __builtin_amdgcn_ballot_w64(L.cur != REF_DONE);
         if (act == 0) {
@@ -221,13 +183,10 @@ __global__ __launch_bounds__(256, 6) void k_extend4(ExtendParams p)
         }
         const bool leaf_trip = (trip & 1u) == 0u || __builtin_amdgcn_ballot_w64(L.cur < REF_LEAF_BIT) == 0;
         ++trip;
-        step4<FL>(L, p, stack_base, s_top, 2u * top_quads, leaf_trip, (special_mask & act) != 0, act);
+        const bool exact = (__builtin_amdgcn_ballot_w64((int32_t)plane_off < 0) & act) != 0;
+        step4<FL>(L, p, stack_base, s_top, 2u * top_quads, leaf_trip, exact, act);
     }
-    if (RECORD && live && p.hits) {
-        const uint32_t li = p.order ? p.order[slot] : slot;
-        p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
-    }
-    if (L.po.y != 1e30f) atomicAdd(&my_counts[plane_off + L.triID], 1);
+    retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);
 }
 
 // per-launch node records: the lamp's x and z subtracted from the x / z bounds (extend.cl:31,35), leaf
@@ -256,19 +215,8 @@ bool launch_extend4(const ExtendParams& p0, int grid_per_cu, hipStream_t s)
 {
     if (p0.n <= 0) return true;
     ExtendParams p = p0;
-    const unsigned cus = p.num_cus > 0 ? (unsigned)p.num_cus : 256u;
-    unsigned grid = cus * (unsigned)grid_per_cu;
-    if (p.plane_batches == 0) {
-        p.plane_batches = (uint32_t)((p.n + 63) / 64);
-        p.plane_n = (uint32_t)p.n;
-        p.plane_stride = 0;
-    }
-    p.plane_inv = 1.0f / (float)p.plane_batches;
-    const unsigned need = (unsigned)((p.n + 255) / 256);
-    if (need < grid) grid = need;
-    const uint64_t waves = (uint64_t)grid * 4;
-    p.chunk = (uint32_t)((((uint64_t)p.n + waves - 1) / waves + 63) / 64 * 64);
-    if ((uint64_t)grid * 256 * (MAXS6 - PS6) > p.ovf_capacity) return false;
+    const unsigned grid = size_persistent_grid(p, grid_per_cu);
+    if (grid == 0) return false;
     p.root_ref4 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
                       ? p.scene.root_ref + 2u * (uint32_t)p.nquads : p.scene.root_ref;
     if (p.flavour == 2) {

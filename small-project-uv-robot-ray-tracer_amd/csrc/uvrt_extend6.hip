@@ -522,20 +522,6 @@ __device__ __forceinline__ int run7(Lane6& L, const ExtendParams& p, uint32_t st
     return code;
 }
 
-// A ray outside the proof conditions of the packed exact division (a direction component zero, NaN, > 1 or
-// < 2^-60; an origin height that is tiny but not zero, or huge): it runs the IEEE-division form of the step.
-// Range tests on the bit patterns: |x| in [lo, hi]  <=>  bits(|x|) - bits(lo) <= bits(hi) - bits(lo) as unsigned.
-__device__ __forceinline__ bool outside_proof_conditions(float4 rec)
-{
-    const uint32_t lo = 0x21800000u /* 2^-60 */, one = 0x3F800000u;
-    const uint32_t ux = (__float_as_uint(rec.x) & 0x7FFFFFFFu) - lo, uy = (__float_as_uint(rec.y) & 0x7FFFFFFFu) - lo,
-                   uz = (__float_as_uint(rec.z) & 0x7FFFFFFFu) - lo;
-    const uint32_t worst = max(max(ux, uy), uz);
-    const uint32_t uo = __float_as_uint(rec.w) & 0x7FFFFFFFu;                   // |origin y|
-    const uint32_t ylo = 0x0D800000u /* 2^-100 = 7.888609e-31f */, yhi = 0x4E6E6B28u /* 1e9f */;
-    return worst > one - lo || (uo != 0u && uo - ylo > yhi - ylo);
-}
-
 // The drain of a wave's last rays (its share of the launch is handed out, fewer and fewer lanes hold a ray, every trip still costs
 // a full trip) is the dearest part of a launch: 25 % of the trips of a 2 M-ray launch.  Once a wave is down to MERGE6_AT rays it
 // stops and waits for the other three waves of its workgroup to get there; then all four write their rays into LDS and wave 0 goes
@@ -551,20 +537,12 @@ __device__ __forceinline__ bool outside_proof_conditions(float4 rec)
 constexpr uint32_t MERGE6_AT = UVRT_MERGE6_AT, MERGE6_FIELDS = 14;
 static_assert(4 * MERGE6_AT <= 64, "the rays of four waves must fit one");
 constexpr uint32_t TOP6_KEEP = TOP6_MAX + 1 - (MERGE6_FIELDS * 64 * 4 + TOP6_STRIDE - 1) / TOP6_STRIDE;      // 120 records stay cached
-// ints from a wave's replica to the plane of a lane's ray (bit 31 of that register: the ray needs the exact step, see k_extend6)
-constexpr uint32_t PLANE_OFF6 = 0x7FFFFFFFu, SPECIAL6 = 0x80000000u;
 template <bool RECORD>
 __device__ __forceinline__ bool merge6(Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t& plane_off, uint32_t& stack_base,
                                        uint32_t& slot, bool& live, uint32_t* row0, uint32_t* xch)
 {
     // (few scalars at a time: the kernel's long-lived ones leave little room, and what does not fit is spilled for the whole loop)
-    if (L.cur == REF_DONE) {        // results of the rays these lanes finished since the last refill (extend.cl:94-98)
-        if (RECORD && live && p.hits) {
-            const uint32_t li = p.order ? p.order[slot] : slot;
-            p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
-        }
-        if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
-    }
+    if (L.cur == REF_DONE) retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);   // rays finished since the last refill
     // the wave's number in its workgroup comes from the lane's own stack rows (not yet anybody else's; threadIdx.x is not kept)
     {
         const uint32_t cnt = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(L.cur != REF_DONE));
@@ -643,7 +621,6 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     // conditions of the packed division) -- the wave's mask of such lanes is a ballot of that bit where it is needed, not a
     // register pair carried through the loop (the kernel runs at its scalar-register budget)
     uint32_t plane_off = 0;
-    const float plane_inv = p.plane_inv;
 
     // wave w traces the 64-ray batches w, w + W, w + 2W, ...: static ownership, no atomics, and batches
     // dealt round-robin so that ordered rays stay load-balanced
@@ -651,14 +628,13 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     const uint32_t W = gridDim.x * 4u;
     uint32_t cursor = 0;
     const uint32_t chunk_end = p.chunk;
-    const uint32_t n32 = (uint32_t)p.n;
     uint32_t trip = 0;
     unsigned long long km = ~0ull;          // all ones in a trip that visits leaves (every LEAFP-th)
     unsigned long long full;                // exec of the loop: all 64 lanes (the launch uses full workgroups)
     asm volatile("s_mov_b64 %0, exec" : "=s"(full));
     const uint32_t top_base = (uint32_t)(uintptr_t)s_top;
     // refill when this many lanes are idle; once the wave's sequence is exhausted only the all-idle exit is left
-    const int refill_c = p.refill_min;      // 1..64 (launch_extend6)
+    const int refill_c = p.refill_min;      // 1..64 (size_persistent_grid)
     int refill_at = refill_c;
     // (cursor == MERGED6 once the wave has been through the workgroup's drain merge (merge6), or from the end of its share on when
     //  the launch does without: the state costs no register of its own)
@@ -706,47 +682,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
                 const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
                 const int nidle = __popcll(idle_mask);
                 if (cursor < chunk_end) {
-                    bool spec = false;
-                    if (L.cur == REF_DONE) {
-                        // results of the rays these lanes finished since the last refill (extend.cl:94-98)
-                        if (RECORD && live && p.hits) {
-                            const uint32_t li = p.order ? p.order[slot] : slot;
-                            p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
-                        }
-                        if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
-                        live = false;
-                        L.po.y = 1e30f;
-                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32),
-                                              __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
-                        const uint32_t v = cursor + rank;
-                        const uint32_t gb = (v >> 6) * W + wave;                 // global 64-slot batch
-                        const uint32_t my = gb * 64u + (v & 63u);
-                        // plane (= launch of a batched trace) of the batch: gb / plane_batches, exact after one
-                        // correction step (gb < 2^24 is exact in f32, the rounded reciprocal is off by < 1)
-                        uint32_t pl = 0;
-                        int32_t within = (int32_t)gb;
-                        if (p.plane_stride != 0) {               // wave-uniform: a launch of its own is one plane
-                            pl = (uint32_t)((float)gb * plane_inv);
-                            within = (int32_t)(gb - pl * p.plane_batches);
-                            if (within < 0) { --pl; within += (int32_t)p.plane_batches; }
-                            else if ((uint32_t)within >= p.plane_batches) { ++pl; within -= (int32_t)p.plane_batches; }
-                        }
-                        if (v < chunk_end && my < n32 && (uint32_t)within * 64u + (v & 63u) < p.plane_n) {
-                            const float4 rec = p.rays[my];
-                            // y = RN32(1/d) (rcp_exact: exact for 2^-64 <= |d| < 2^64; other lanes are `spec`
-                            // and never use y); flavour 2: y = v_rcp_f32(d), used by every lane
-                            set_in_place(L.px, rec.x, FL == 2 ? rcp_raw(rec.x) : rcp_exact(rec.x));
-                            set_in_place(L.py, rec.y, FL == 2 ? rcp_raw(rec.y) : rcp_exact(rec.y));
-                            set_in_place(L.pz, rec.z, FL == 2 ? rcp_raw(rec.z) : rcp_exact(rec.z));
-                            set_in_place(L.po, rec.w, 1e30f);       // generate.cl:34-35
-                            set_in_place(L.triID, 0u);
-                            if (RECORD) { slot = my; live = true; }
-                            set_in_place(L.sp, 0);
-                            set_in_place(L.cur, root6);
-                            spec = FL != 2 && (outside_proof_conditions(rec) || p.force_exact != 0);
-                            set_in_place(plane_off, pl * p.plane_stride | (spec ? SPECIAL6 : 0u));
-                        }
-                    }
+                    if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
                     cursor += (uint32_t)nidle;
                     if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
                 } else if (TOP && cursor != MERGED6) {
@@ -788,47 +724,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
             unsigned long long tclk = __builtin_readcyclecounter();
 #endif
             if (cursor < chunk_end) {
-                bool spec = false;
-                if (L.cur == REF_DONE) {
-                    // results of the rays these lanes finished since the last refill (extend.cl:94-98)
-                    if (RECORD && live && p.hits) {
-                        const uint32_t li = p.order ? p.order[slot] : slot;
-                        p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
-                    }
-                    if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
-                    live = false;
-                    L.po.y = 1e30f;
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32),
-                                          __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
-                    const uint32_t v = cursor + rank;
-                    const uint32_t gb = (v >> 6) * W + wave;                 // global 64-slot batch
-                    const uint32_t my = gb * 64u + (v & 63u);
-                    // plane (= launch of a batched trace) of the batch: gb / plane_batches, exact after one
-                    // correction step (gb < 2^24 is exact in f32, the rounded reciprocal is off by < 1)
-                    uint32_t pl = 0;
-                    int32_t within = (int32_t)gb;
-                    if (p.plane_stride != 0) {               // wave-uniform: a launch of its own is one plane
-                        pl = (uint32_t)((float)gb * plane_inv);
-                        within = (int32_t)(gb - pl * p.plane_batches);
-                        if (within < 0) { --pl; within += (int32_t)p.plane_batches; }
-                        else if ((uint32_t)within >= p.plane_batches) { ++pl; within -= (int32_t)p.plane_batches; }
-                    }
-                    if (v < chunk_end && my < n32 && (uint32_t)within * 64u + (v & 63u) < p.plane_n) {
-                        const float4 rec = p.rays[my];
-                        // y = RN32(1/d) (rcp_exact: exact for 2^-64 <= |d| < 2^64; other lanes are `spec`
-                        // and never use y); flavour 2: y = v_rcp_f32(d), used by every lane
-                        set_in_place(L.px, rec.x, FL == 2 ? rcp_raw(rec.x) : rcp_exact(rec.x));
-                        set_in_place(L.py, rec.y, FL == 2 ? rcp_raw(rec.y) : rcp_exact(rec.y));
-                        set_in_place(L.pz, rec.z, FL == 2 ? rcp_raw(rec.z) : rcp_exact(rec.z));
-                        set_in_place(L.po, rec.w, 1e30f);       // generate.cl:34-35
-                        set_in_place(L.triID, 0u);
-                        if (RECORD) { slot = my; live = true; }
-                        set_in_place(L.sp, 0);
-                        set_in_place(L.cur, root6);
-                        spec = FL != 2 && (outside_proof_conditions(rec) || p.force_exact != 0);
-                        set_in_place(plane_off, pl * p.plane_stride | (spec ? SPECIAL6 : 0u));
-                    }
-                }
+                if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
                 cursor += (uint32_t)nidle;
                 if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
 #ifdef UVRT_TRIP_STATS
@@ -909,11 +805,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     }
 #endif
     // the wave's sequence is exhausted and every lane is idle: deposit what is still pending
-    if (RECORD && live && p.hits) {
-        const uint32_t li = p.order ? p.order[slot] : slot;
-        p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
-    }
-    if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);   // extend.cl:94-98
+    retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);
 }
 
 // Per-launch node-pair records recs[0, P): the lamp's x and z subtracted from the x / z bounds (the
@@ -964,20 +856,8 @@ bool launch_extend6(const ExtendParams& p0, int code, int grid_per_cu, hipStream
 {
     if (p0.n <= 0) return true;
     ExtendParams p = p0;
-    const unsigned cus = p.num_cus > 0 ? (unsigned)p.num_cus : 256u;
-    unsigned grid = cus * (unsigned)grid_per_cu;
-    if (p.plane_batches == 0) {      // one launch: a single plane that holds all n rays
-        p.plane_batches = (uint32_t)((p.n + 63) / 64);
-        p.plane_n = (uint32_t)p.n;
-        p.plane_stride = 0;
-    }
-    p.plane_inv = 1.0f / (float)p.plane_batches;
-    p.refill_min = p.refill_min < 1 ? 1 : (p.refill_min > 64 ? 64 : p.refill_min);
-    const unsigned need = (unsigned)((p.n + 255) / 256);
-    if (need < grid) grid = need;
-    const uint64_t waves = (uint64_t)grid * 4;
-    p.chunk = (uint32_t)((((uint64_t)p.n + waves - 1) / waves + 63) / 64 * 64);
-    if ((uint64_t)grid * 256 * (MAXS6 - PS6) > p.ovf_capacity) return false;
+    const unsigned grid = size_persistent_grid(p, grid_per_cu);
+    if (grid == 0) return false;
     // an inner root is translated through the renumbering by the kernel itself (perm lives on the device)
     p.root_ref6 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
                       ? p.scene.root_ref + (uint32_t)p.npairs : p.scene.root_ref;

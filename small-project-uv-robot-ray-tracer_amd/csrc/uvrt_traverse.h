@@ -1,6 +1,7 @@
 // uvrt_traverse.h -- device helpers shared by the traversal kernels (uvrt_extend6.hip: the reference's
 // BVH2 order; uvrt_extend4.hip: the opt-in 4-wide collapse): exact slab distances, box and triangle tests,
-// the per-lane ray state, the stack-overflow pointer.  See uvrt_extend6.hip's header for the arithmetic.
+// the per-lane ray state, the ray feed (refill, retire, grid sizing), the stack-overflow pointer.  See
+// uvrt_extend6.hip's header for the arithmetic.
 #pragma once
 #include "uvrt_device.h"
 
@@ -211,6 +212,101 @@ struct Lane6 {
     uint32_t cur;           // record reference: index | leaf bit + count code, REF_DONE = no ray
     int sp;
 };
+
+// ---- the persistent ray feed of k_extend6 and k_extend4 ----
+// ints from a wave's replica of the counts to the plane of a lane's ray (the kernels' plane_off; bit 31 of that register:
+// the ray needs the exact step)
+constexpr uint32_t PLANE_OFF6 = 0x7FFFFFFFu, SPECIAL6 = 0x80000000u;
+
+// A ray outside the proof conditions of the packed exact division (a direction component zero, NaN, > 1 or
+// < 2^-60; an origin height that is tiny but not zero, or huge): it runs the IEEE-division form of the step.
+// Range tests on the bit patterns: |x| in [lo, hi]  <=>  bits(|x|) - bits(lo) <= bits(hi) - bits(lo) as unsigned.
+__device__ __forceinline__ bool outside_proof_conditions(float4 rec)
+{
+    const uint32_t lo = 0x21800000u /* 2^-60 */, one = 0x3F800000u;
+    const uint32_t ux = (__float_as_uint(rec.x) & 0x7FFFFFFFu) - lo, uy = (__float_as_uint(rec.y) & 0x7FFFFFFFu) - lo,
+                   uz = (__float_as_uint(rec.z) & 0x7FFFFFFFu) - lo;
+    const uint32_t worst = max(max(ux, uy), uz);
+    const uint32_t uo = __float_as_uint(rec.w) & 0x7FFFFFFFu;                   // |origin y|
+    const uint32_t ylo = 0x0D800000u /* 2^-100 = 7.888609e-31f */, yhi = 0x4E6E6B28u /* 1e9f */;
+    return worst > one - lo || (uo != 0u && uo - ylo > yhi - ylo);
+}
+
+// The results of the ray a lane has finished (extend.cl:94-98): its hit record when one is pending (`live`), and its deposit
+// unless it hit nothing (dist == 1e30f).
+template <bool RECORD>
+__device__ __forceinline__ void retire_ray(const Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t plane_off,
+                                           uint32_t slot, bool live)
+{
+    if (RECORD && live && p.hits) {
+        const uint32_t li = p.order ? p.order[slot] : slot;
+        p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
+    }
+    if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
+}
+
+// The per-lane part of a refill, for an idle lane (L.cur == REF_DONE): retire its last ray, then take slot cursor + (rank among
+// the idle lanes) of the wave's sequence of 64-ray batches wave, wave + W, wave + 2W, ...  A slot beyond the wave's share, the
+// launch or its plane leaves the lane idle.  `root`: the kernel's root reference.
+template <bool RECORD, int FL>
+__device__ __forceinline__ void refill_lane(Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t& plane_off,
+                                            uint32_t& slot, bool& live, unsigned long long idle_mask, uint32_t cursor,
+                                            uint32_t wave, uint32_t W, uint32_t root)
+{
+    retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);
+    live = false;
+    L.po.y = 1e30f;
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
+    const uint32_t v = cursor + rank;
+    const uint32_t gb = (v >> 6) * W + wave;                 // global 64-slot batch
+    const uint32_t my = gb * 64u + (v & 63u);
+    // plane (= launch of a batched trace) of the batch: gb / plane_batches, exact after one
+    // correction step (gb < 2^24 is exact in f32, the rounded reciprocal is off by < 1)
+    uint32_t pl = 0;
+    int32_t within = (int32_t)gb;
+    if (p.plane_stride != 0) {               // wave-uniform: a launch of its own is one plane
+        pl = (uint32_t)((float)gb * p.plane_inv);
+        within = (int32_t)(gb - pl * p.plane_batches);
+        if (within < 0) { --pl; within += (int32_t)p.plane_batches; }
+        else if ((uint32_t)within >= p.plane_batches) { ++pl; within -= (int32_t)p.plane_batches; }
+    }
+    if (v < p.chunk && my < (uint32_t)p.n && (uint32_t)within * 64u + (v & 63u) < p.plane_n) {
+        const float4 rec = p.rays[my];
+        // y = RN32(1/d) (rcp_exact: exact for 2^-64 <= |d| < 2^64; other lanes are `spec`
+        // and never use y); flavour 2: y = v_rcp_f32(d), used by every lane
+        set_in_place(L.px, rec.x, FL == 2 ? rcp_raw(rec.x) : rcp_exact(rec.x));
+        set_in_place(L.py, rec.y, FL == 2 ? rcp_raw(rec.y) : rcp_exact(rec.y));
+        set_in_place(L.pz, rec.z, FL == 2 ? rcp_raw(rec.z) : rcp_exact(rec.z));
+        set_in_place(L.po, rec.w, 1e30f);       // generate.cl:34-35
+        set_in_place(L.triID, 0u);
+        if (RECORD) { slot = my; live = true; }
+        set_in_place(L.sp, 0);
+        set_in_place(L.cur, root);
+        const bool spec = FL != 2 && (outside_proof_conditions(rec) || p.force_exact != 0);
+        set_in_place(plane_off, pl * p.plane_stride | (spec ? SPECIAL6 : 0u));
+    }
+}
+
+// Persistent grid of a traversal launch (launch_extend6, launch_extend4): a single plane of all n rays unless the caller
+// batches planes, the refill threshold clamped to 1..64, at most grid_per_cu workgroups per CU and none beyond 256 rays
+// each, every wave's share `chunk` in whole 64-ray batches.  Returns the grid, or 0 when its overflow stacks would not fit.
+inline unsigned size_persistent_grid(ExtendParams& p, int grid_per_cu)
+{
+    const unsigned cus = p.num_cus > 0 ? (unsigned)p.num_cus : 256u;
+    unsigned grid = cus * (unsigned)grid_per_cu;
+    if (p.plane_batches == 0) {      // one launch: a single plane that holds all n rays
+        p.plane_batches = (uint32_t)((p.n + 63) / 64);
+        p.plane_n = (uint32_t)p.n;
+        p.plane_stride = 0;
+    }
+    p.plane_inv = 1.0f / (float)p.plane_batches;
+    p.refill_min = p.refill_min < 1 ? 1 : (p.refill_min > 64 ? 64 : p.refill_min);
+    const unsigned need = (unsigned)((p.n + 255) / 256);
+    if (need < grid) grid = need;
+    const uint64_t waves = (uint64_t)grid * 4;
+    p.chunk = (uint32_t)((((uint64_t)p.n + waves - 1) / waves + 63) / 64 * 64);
+    return (uint64_t)grid * 256 * (MAXS6 - PS6) > p.ovf_capacity ? 0u : grid;
+}
 
 // One traversal step of one lane (extend.cl:44-80): an inner node (both children tested, ordered,
 // descend / push / pop) or -- on a leaf trip -- a leaf (its triangles, pop).

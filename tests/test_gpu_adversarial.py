@@ -13,7 +13,7 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def run_both(pkg, orc, tris, nodes, idx, rays, variants=(0, 401, 501, 801, 405, 500)):
+def run_both(pkg, orc, tris, nodes, idx, rays, variants=(0, 401, 501, 801, 405, 500), wide=False):
     o_rays = rays.copy()
     o_rays["dist"] = np.float32(1e30)
     o_rays["triID"] = 0
@@ -27,6 +27,7 @@ def run_both(pkg, orc, tris, nodes, idx, rays, variants=(0, 401, 501, 801, 405, 
         c.set_scene(tris, nodes, idx)
         c.resize_rays(rays.size)
         c.set_record_hits(True)
+        c.set_wide_bvh(wide)
         for v in vs:
             c.set_variant(v)
             c.reset(False)
@@ -87,7 +88,8 @@ def test_zero_direction_components_and_origins_on_box_planes(pkg, orc, oscene):
 
 def test_outside_the_fast_path_conditions(pkg, orc, oscene):
     """|d| > 1, subnormal / tiny direction components and tiny non-zero origins: lanes take the
-    IEEE-division path; results still equal the oracle."""
+    IEEE-division path; results still equal the oracle, in the default walk and in the opt-in 4-wide one
+    (the room has no coincident geometry: no order-dependent ray is expected there)."""
     rng = np.random.default_rng(4)
     n = 4096
     a = rng.normal(size=(n, 3))
@@ -102,6 +104,7 @@ def test_outside_the_fast_path_conditions(pkg, orc, oscene):
     for origin in ((0.0, 0.0), (2.0 ** -110, -(2.0 ** -105)), (-0.255, -3.31)):
         rays = make_rays(d, origin, oys)
         run_both(pkg, orc, oscene.tris, oscene.nodes, oscene.triIdx, rays)
+        run_both(pkg, orc, oscene.tris, oscene.nodes, oscene.triIdx, rays, variants=(0,), wide=True)
 
 
 def test_big_leaf_scene(pkg, orc):

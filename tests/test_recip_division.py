@@ -132,7 +132,7 @@ def test_packed_three_instruction_division_equals_ieee_quotient(tmp_path):
 
 
 def test_proof_condition_range_tests_on_bit_patterns():
-    """uvrt_extend6.hip outside_proof_conditions(): the refill decides with unsigned range tests on the bit patterns
+    """uvrt_traverse.h outside_proof_conditions(): the refill decides with unsigned range tests on the bit patterns
     (|x| in [lo, hi] <=> bits(|x|) - bits(lo) <= bits(hi) - bits(lo)) which rays leave the packed exact division;
     this is the float-comparison form the proof conditions are stated in, restated both ways in numpy."""
     import itertools
