@@ -75,7 +75,8 @@ int uvrt_generate(uvrt_ctx* ctx, const float light_pos[3], float light_length,
                   int64_t first_gid, int64_t n);
 
 /* cl/extend.cl:85-99 over the n rays of the last uvrt_generate: closest hit through the BVH,
- * then one increment of tempPhotonMap[triID] per hit. */
+ * then one increment of tempPhotonMap[triID] per hit.  After uvrt_generate_sweep or uvrt_write_free_rays ("free rays"
+ * below) it runs the free-origin kernel instead. */
 int uvrt_extend(uvrt_ctx* ctx, int64_t n);
 
 /* cl/accumulate.cl:4-14 over tri_count triangles.  (A full-range accumulate is enqueued with the next call: a uvrt_shade
@@ -129,6 +130,30 @@ int uvrt_advance_seed(uvrt_ctx* ctx, const float light_pos[3], float light_lengt
 int uvrt_set_seed_mode(uvrt_ctx* ctx, int32_t mode);
 uint32_t uvrt_seed_next_mode(const float light_pos[3], float light_length, uint32_t seed_prev,
                              int32_t seed_mode);
+
+/* ---- free rays: every ray with an origin of its own ----
+ * uvrt_generate makes the rays of one lamp column and the default traversal kernel relies on it.  The two calls below make
+ * rays whose origins differ; the uvrt_extend that follows traces them with the free-origin kernel (same visit order, box
+ * test, triangle test and deposit: (dist, triID) and the counts are bit-identical to the CPU restatement in flavours 0 and
+ * 1) into the same tempPhotonMap, so uvrt_accumulate, uvrt_shade, uvrt_read_counts and uvrt_device_ptr work unchanged.
+ * Flavour 2 is refused (UVRT_ERR_INVALID) for such a launch; uvrt_set_wide_bvh and uvrt_set_sort_bits are ignored by it;
+ * uvrt_set_record_hits + uvrt_read_rays return every ray's own origin.  uvrt_trace_batch takes no sweeps.  The
+ * {orig.x, orig.z} array and the kernel's per-scene records are allocated by the first such call.
+ *
+ * uvrt_generate_sweep: generate for a lamp that moves from `from` to `to` at constant speed while it radiates.  Work-item
+ * gid runs generate.cl:13-35 with lightPos = from under the SEED semantics of uvrt_generate (mode 0: work-item 0 reads
+ * SEED_{k-1}, every other one SEED_k), then draws u = RandomFloat(&seed) and starts at
+ *     orig.c = from.c + u * (to.c - from.c)                                    for c = x, z
+ *     orig.y = (from.y + r1 * light_length) + u * (to.y - from.y)
+ * each fl(a + fl(u * fl(b - a))) in strict f32; the direction is generate's.  SEED_k is work-item 0's RNG state after the
+ * draw of u: a function of `from` and SEED_{k-1} only (uvrt_seed_next_sweep: host only, no GPU needed).  With
+ * uvrt_set_seed_mode(ctx, 1) the call fails with UVRT_ERR_INVALID: that mode models the race of generate.cl alone. */
+int uvrt_generate_sweep(uvrt_ctx* ctx, const float from[3], const float to[3], float light_length,
+                        int64_t first_gid, int64_t n);
+uint32_t uvrt_seed_next_sweep(const float from[3], float light_length, uint32_t seed_prev);
+/* Like uvrt_write_rays, but every 32-byte Ray record keeps its own orig.xyz: n host records become "the last generate".
+ * SEED is untouched. */
+int uvrt_write_free_rays(uvrt_ctx* ctx, const void* rays32, int64_t n);
 
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
@@ -305,7 +330,7 @@ int uvrt_set_variant(uvrt_ctx* ctx, int32_t variant);
 int uvrt_read_rays(uvrt_ctx* ctx, void* rays32, int64_t first, int64_t count);
 /* test hook: replace the rays of the "last generate" by n host records in the reference's 32-byte
  * Ray layout (dir, orig; dist/triID ignored).  All records must share orig.x and orig.z (rays of
- * one lamp, generate.cl:16).  SEED is untouched.  Lets tests feed adversarial rays (zero
+ * one lamp, generate.cl:16; uvrt_write_free_rays takes any origins).  SEED is untouched.  Lets tests feed adversarial rays (zero
  * direction components, origins on box planes) straight into uvrt_extend. */
 int uvrt_write_rays(uvrt_ctx* ctx, const void* rays32, int64_t n);
 int uvrt_read_counts(uvrt_ctx* ctx, int32_t* out, int32_t first, int32_t count);

@@ -71,6 +71,9 @@ SYMBOLS = [
     ("uvrt_set_wide_bvh", C.c_int, [_vp, _i32]),
     ("uvrt_read_rays", C.c_int, [_vp, _vp, _i64, _i64]),
     ("uvrt_write_rays", C.c_int, [_vp, _vp, _i64]),
+    ("uvrt_write_free_rays", C.c_int, [_vp, _vp, _i64]),
+    ("uvrt_generate_sweep", C.c_int, [_vp, _fp, _fp, _f32, _i64, _i64]),
+    ("uvrt_seed_next_sweep", _u32, [_fp, _f32, _u32]),
     ("uvrt_read_counts", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_read_photon_map", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_device_ptr", C.c_int, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
@@ -163,6 +166,11 @@ def _ptr(a):
 def seed_next(light_pos, light_length, seed_prev, seed_mode=0):
     return int(lib().uvrt_seed_next_mode(_f3(light_pos), float(np.float32(light_length)), int(seed_prev),
                                          int(seed_mode)))
+
+
+def seed_next_sweep(frm, light_length, seed_prev):
+    """the SEED a uvrt_generate_sweep from `frm` leaves behind (host only)"""
+    return int(lib().uvrt_seed_next_sweep(_f3(frm), float(np.float32(light_length)), int(seed_prev)))
 
 
 def comm_unique_id():
@@ -301,6 +309,16 @@ class Ctx:
     def write_rays(self, rays):
         rays = np.ascontiguousarray(rays, dtype=RAY_DT)
         self._ck(self._L.uvrt_write_rays(self._h, _ptr(rays), rays.size))
+
+    def write_free_rays(self, rays):
+        """rays with origins of their own: the next extend runs the free-origin kernel"""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DT)
+        self._ck(self._L.uvrt_write_free_rays(self._h, _ptr(rays), rays.size))
+
+    def generate_sweep(self, frm, to, light_length, first_gid, n):
+        """generate for a lamp that moves from `frm` to `to` while it radiates"""
+        self._ck(self._L.uvrt_generate_sweep(self._h, _f3(frm), _f3(to), float(np.float32(light_length)),
+                                             int(first_gid), int(n)))
 
     @property
     def seed(self):

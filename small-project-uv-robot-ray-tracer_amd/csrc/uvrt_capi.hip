@@ -140,13 +140,14 @@ void uvrt_destroy(uvrt_ctx* c)
     plan_drop(c);
     for (Lane& L : c->lanes) {
         if (L.side) (void)hipStreamSynchronize(L.side);
-        for (DevBuf* b : {&L.rays, &L.recs, &L.counts, &L.ovf, &L.recs4}) b->release();
+        for (DevBuf* b : {&L.rays, &L.recs, &L.counts, &L.ovf, &L.recs4, &L.oxz}) b->release();
         if (L.ev_tail) (void)hipEventDestroy(L.ev_tail);
         if (L.side) (void)hipStreamDestroy(L.side);
     }
     if (c->ev_fence) (void)hipEventDestroy(c->ev_fence);
     if (c->ev_mapfence) (void)hipEventDestroy(c->ev_mapfence);
     c->quads.release();
+    c->free_recs.release();
     for (DevBuf& b : c->b_recs) b.release();
     (void)hot_reset(c, false);            // (and the lanes' set-up scratch)
     for (auto& bset : c->bs) {
@@ -383,6 +384,8 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     for (Lane& L : c->lanes) { L.recs_tag.valid = false; L.recs4_tag.valid = false; }
     c->have_perm = false;
     c->have_scene = true;
+    c->free_recs.release();                           // sized per scene; rebuilt by the next free launch
+    c->free_recs_valid = false;
     c->scene_force_exact = tiny_bound || huge_vertex;
     if ((rc = hot_reset(c, true))) return rc;         // statistics of the previous scene; the new scene's first slab
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -413,6 +416,7 @@ int uvrt_resize_rays(uvrt_ctx* c, int64_t photon_count)
     if ((rc = c->sorted.ensure(n * 16, false, c->stream))) return rc;
     if ((rc = c->order.ensure(n * 4, false, c->stream))) return rc;
     if (c->record_hits && (rc = c->hits.ensure(n * 8, false, c->stream))) return rc;
+    for (Lane& L : c->lanes) L.oxz.release();         // [capacity]: back with the lane's next free launch
     c->capacity = photon_count;
     c->last_n = -1;
     return UVRT_OK;
@@ -662,7 +666,10 @@ int uvrt_read_rays(uvrt_ctx* c, void* rays32, int64_t first, int64_t count)
     if (count == 0) return UVRT_OK;
     if (int rc = c->export_buf.ensure((size_t)count * 32, false, c->stream)) return rc;
     const uint2* hits = (c->last_extended && c->hits.p) ? c->hits.as<uint2>() : nullptr;
-    launch_export_rays(cur_lane(c).rays.as<float4>(), hits, c->export_buf.p, c->ox, c->oz, first, count, c->stream);
+    if (c->last_free)
+        launch_export_free_rays(cur_lane(c).rays.as<float4>(), cur_lane(c).oxz.as<float2>(), hits, c->export_buf.p, first, count, c->stream);
+    else
+        launch_export_rays(cur_lane(c).rays.as<float4>(), hits, c->export_buf.p, c->ox, c->oz, first, count, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rays32, c->export_buf.p, (size_t)count * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -695,6 +702,7 @@ int uvrt_write_rays(uvrt_ctx* c, const void* rays32, int64_t n)
     c->last_first = 0;
     c->last_sorted = false;
     c->last_extended = false;
+    c->last_free = false;
     c->ox = hr[0].o[0];
     c->oz = hr[0].o[2];
     return UVRT_OK;

@@ -231,6 +231,7 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
     c->last_first = first_gid;
     c->last_sorted = p.keyrank != nullptr;
     c->last_extended = false;
+    c->last_free = false;
     c->ox = lp[0];
     c->oz = lp[2];
     return UVRT_OK;
@@ -243,6 +244,7 @@ int uvrt_extend(uvrt_ctx* c, int64_t n)
         return fail(UVRT_ERR_INVALID, "uvrt_extend: n = %lld does not match the last generate (%lld)",
                     (long long)n, (long long)c->last_n);
     if (int rc = set_device(c)) return rc;
+    if (c->last_free) return extend_free(c, n);      // rays with origins of their own: the free-origin kernel, whatever the walk / ordering knobs say
     if (c->record_hits) {
         if (int rc = c->hits.ensure((size_t)c->capacity * 8, false, c->stream)) return rc;
     }

@@ -2,6 +2,7 @@
 //   uvrt_capi.hip         context, scene, buffers, knobs, read-backs and test hooks
 //   uvrt_capi_launch.hip  the per-launch entry points (generate, extend, accumulate, shade) and the launch lanes
 //   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / fold / replay)
+//   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -74,6 +75,7 @@ struct Lane {
     RecsTag recs4_tag;               // what the per-launch part of recs4 is prepared for
     DevBuf hot_hist, hot_list;       // scratch of the hot-record set-up kernels (uvrt_hotset.hip)
     const uint32_t* perm = nullptr;  // renumbering of the lane's current launch (set by uvrt_generate)
+    DevBuf oxz;                      // {orig.x, orig.z} of free rays, [capacity]; allocated by the lane's first free launch
 };
 
 }  // namespace uvrt_impl
@@ -114,7 +116,10 @@ struct uvrt_ctx {
     int64_t last_first = 0;
     bool last_sorted = false;
     bool last_extended = false;
+    bool last_free = false;                    // the last generate made rays with origins of their own (uvrt_capi_free.hip)
     float ox = 0, oz = 0;
+    DevBuf free_recs;                          // the free-origin kernel's records, [npairs + T + 1] x 64 B: made on first use
+    bool free_recs_valid = false;              // ... for the current scene
 
     // Launch lanes: consecutive launches (generate -> extend -> accumulate ->
     // shade) alternate between the context's stream and an internal side stream, each with its own
@@ -445,6 +450,8 @@ inline void fill_launch(uvrt_ctx* c, ExtendParams& p, float ox, float oz)
     p.drain_merge = c->drain_merge;
     p.refill_min = variant_refill_min(c->variant, (size_t)c->npairs + (size_t)c->T);
 }
+// uvrt_extend for the free rays of the last uvrt_write_free_rays / uvrt_generate_sweep (uvrt_capi_free.hip)
+int extend_free(uvrt_ctx* c, int64_t n);
 // the next pair of the extend timing pool (uvrt_extend_time_ms) with its start recorded on `s`; *stop stays null
 // while timing is off
 inline int timing_start(uvrt_ctx* c, hipStream_t s, hipEvent_t* stop)

@@ -97,9 +97,10 @@ __device__ __forceinline__ float random_float(uint32_t& s)
 // cl/generate.cl:11-37 for work-item `gid`: returns {dir.xyz, orig.y} (orig.x / orig.z are the lamp's).
 // r0 = the first random float (position on the rod), (x, y) = the accepted disc sample: for the optional
 // coherence key of k_generate.  seed_mode: include/uvrt.h uvrt_set_seed_mode.
-__device__ __forceinline__ float4 generate_ray(float lx, float ly, float lz, float light_length, int64_t gid,
-                                               uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode,
-                                               float& r0, double& x, double& y)
+// `seed` returns the work-item's RNG state after its last draw (what a sweep goes on drawing from, uvrt_extend_free.hip).
+__device__ __forceinline__ float4 generate_ray_rng(float lx, float ly, float lz, float light_length, int64_t gid,
+                                                   uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode,
+                                                   float& r0, double& x, double& y, uint32_t& seed)
 {
     const int threadID = (int)gid;                       // generate.cl:11 (int threadID)
     const uint32_t SEED = (gid == 0 || seed_mode == 1) ? seed_prev : seed_next;
@@ -110,7 +111,7 @@ __device__ __forceinline__ float4 generate_ray(float lx, float ly, float lz, flo
     acc = acc + ly * 7.0f;
     acc = acc + lz * 11.0f;
     acc = acc + (float)(SEED >> 15);
-    uint32_t seed = wang_hash((seed_mode == 1 && acc < 0.0f) ? 0u : (uint32_t)(int64_t)acc);
+    seed = wang_hash((seed_mode == 1 && acc < 0.0f) ? 0u : (uint32_t)(int64_t)acc);
 
     r0 = random_float(seed);
     const float origy = ly + r0 * light_length;          // :16
@@ -125,6 +126,13 @@ __device__ __forceinline__ float4 generate_ray(float lx, float ly, float lz, flo
     }
     const double s = dirxzlength / sqrt(x * x + y * y);                   // :29
     return make_float4((float)(x * s), diry, (float)(y * s), origy);      // :31-37
+}
+__device__ __forceinline__ float4 generate_ray(float lx, float ly, float lz, float light_length, int64_t gid,
+                                               uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode,
+                                               float& r0, double& x, double& y)
+{
+    uint32_t seed;
+    return generate_ray_rng(lx, ly, lz, light_length, gid, seed_prev, seed_next, seed_mode, r0, x, y, seed);
 }
 
 // ---- the traversal kernel's LDS cache (uvrt_extend6.hip) ----
@@ -291,5 +299,31 @@ void launch_prepare_scene(const float4* tris64, const uint32_t* tri_idx, LeafTri
 void launch_clock_probe(unsigned long long* out2, unsigned long long ticks_100mhz, hipStream_t s);
 void launch_export_rays(const float4* rays, const uint2* hits, void* out32, float ox, float oz,
                         int64_t first, int64_t count, hipStream_t s);
+
+// ---- rays with origins of their own (uvrt_extend_free.hip) ----
+// The free-origin traversal's arguments: an ExtendParams as launch_extend6 takes it (rays = the 16-byte {dir.xyz, orig.y}
+// records, recs = the scene's free records, ox / oz unused) plus the rays' {orig.x, orig.z}.
+struct FreeParams {
+    ExtendParams e;
+    const float2* oxz;       // [n] in gid order
+};
+// a lamp that moves from `from` to `to` (include/uvrt.h uvrt_generate_sweep)
+struct SweepParams {
+    float4* rays;            // [n] dir.xyz, orig.y
+    float2* oxz;             // [n] orig.x, orig.z
+    float fx, fy, fz, tx, ty, tz;
+    float light_length;
+    int64_t first_gid, n;
+    uint32_t seed_prev, seed_next;
+};
+// The scene's free records, made once per scene: pair record i in the layout of prepare_record6 with the RAW bounds (a
+// ray subtracts its own origin) in breadth-first order, leaf references re-based; the leaf records follow at [npairs, npairs + T).
+void launch_prepare_free_records(const PairRec* pairs, const LeafTri* ltris, void* recs, int32_t npairs, int32_t T, hipStream_t s);
+// workgroups per CU the free kernel is resident with (its register allocation decides)
+constexpr int FREE_GRID_PER_CU = 8;
+bool launch_extend_free(const FreeParams& p, int grid_per_cu, hipStream_t s);
+void launch_generate_sweep(const SweepParams& p, hipStream_t s);
+void launch_export_free_rays(const float4* rays, const float2* oxz, const uint2* hits, void* out32, int64_t first,
+                             int64_t count, hipStream_t s);
 
 }  // namespace uvrt

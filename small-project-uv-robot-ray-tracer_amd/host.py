@@ -44,6 +44,7 @@ SYMBOLS = [
     ("uvrt_host_rt_clear_buffers", None, [_vp, C.c_int]),
     ("uvrt_host_rt_compute_dosage_map", None, [_vp]),
     ("uvrt_host_rt_compute_single", None, [_vp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]),
+    ("uvrt_host_rt_compute_segment", None, [_vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]),
     ("uvrt_host_rt_shade", None, [_vp]),
     ("uvrt_host_rt_add_lamp", None, [_vp]),
     ("uvrt_host_rt_calibrate", None, [_vp, C.c_float, C.c_float, C.c_float]),
@@ -73,7 +74,7 @@ SYMBOLS = [
 _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIterations",
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
-           "photonMapSize", "viewMode"}
+           "photonMapSize", "viewMode", "driveSpeed"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
                "photonMapSize", "viewMode"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
@@ -211,6 +212,9 @@ class RayTracer:
     def ComputeSingleLightDosageMap(self, lamp, photonsPerLight, triangleCount):
         self._L.uvrt_host_rt_compute_single(self._h, lamp[0], lamp[1], lamp[2], int(photonsPerLight),
                                             int(triangleCount))
+    def ComputeSegmentDosageMap(self, a, b, photonsPerLight, triangleCount):
+        """the dose of the drive from position a to position b ((x, z) pairs) at driveSpeed"""
+        self._L.uvrt_host_rt_compute_segment(self._h, a[0], a[1], b[0], b[1], int(photonsPerLight), int(triangleCount))
     def Shade(self): self._L.uvrt_host_rt_shade(self._h)
     def ResetDosageMap(self): self._L.uvrt_host_rt_reset_dosage_map(self._h)
     def ClearBuffers(self, resetColor): self._L.uvrt_host_rt_clear_buffers(self._h, int(bool(resetColor)))

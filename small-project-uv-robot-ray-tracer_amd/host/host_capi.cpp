@@ -69,6 +69,14 @@ void uvrt_host_rt_compute_single(void* r, float x, float y, float duration, int 
     lp.duration = duration;
     ((RayTracer*)r)->ComputeSingleLightDosageMap(lp, photons, tris);
 }
+void uvrt_host_rt_compute_segment(void* r, float ax, float ay, float bx, float by, int photons, int tris)
+{
+    LightPos a, b;
+    a.position = make_float2(ax, ay);
+    b.position = make_float2(bx, by);
+    a.duration = b.duration = 0.0f;
+    ((RayTracer*)r)->ComputeSegmentDosageMap(a, b, photons, tris);
+}
 void uvrt_host_rt_shade(void* r) { ((RayTracer*)r)->Shade(); }
 void uvrt_host_rt_add_lamp(void* r) { ((RayTracer*)r)->AddLamp(); }
 void uvrt_host_rt_calibrate(void* r, float p, float h, float d) { ((RayTracer*)r)->CalibratePower(p, h, d); }
@@ -145,7 +153,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(maxIterations, int) F(currIterations, int) F(lightIntensity, float) F(minDosage, float)
     F(minPower, float) F(photonsPerLight, int) F(compTime, float) F(progress, float)
     F(finishedComputation, bool) F(thresholdView, bool) F(startedComputation, bool)
-    F(calibratedPower, float) F(photonMapSize, int)
+    F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

@@ -168,6 +168,29 @@ void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66
 {
     for (LightPos& lightPosition : lightPositions)
         ComputeSingleLightDosageMap(lightPosition, photonsPerLight, mesh->triangleCount);
+    ComputeSegments();
+}
+
+void RayTracer::ComputeSegments()
+{
+    if (!(driveSpeed > 0.0f) || lightPositions.size() < 2) return;
+    for (size_t i = 0; i + 1 < lightPositions.size(); ++i)
+        ComputeSegmentDosageMap(lightPositions[i], lightPositions[i + 1], photonsPerLight, mesh->triangleCount);
+}
+
+void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount)
+{
+    if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
+    if (shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
+    // the lamp's feet, as at a stop (raytracer.cpp:77)
+    const float y = mesh->floorHeight + lightHeight;
+    const float from[3] = {a.position.x, y, a.position.y}, to[3] = {b.position.x, y, b.position.y};
+    const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
+    const float len = sqrtf(dx * dx + dz * dz);          // (a zero-length segment is traced too, with duration 0: the SEED chain stays regular)
+    check(uvrt_generate_sweep(ctx, from, to, lightLength, 0, photonsPerLight), "generate_sweep");
+    check(uvrt_extend(ctx, photonsPerLight), "extend");
+    check(uvrt_accumulate(ctx, len / driveSpeed, triangleCount), "accumulate");
+    // (no photonMapSize += photonsPerLight: Shade divides by the photons per SOURCE, raytracer.h driveSpeed)
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
@@ -204,6 +227,32 @@ void RayTracer::ComputeIterationsBatched(int iterations)
 void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, int iterations)
 {
     RayTracer* r0 = group[0];
+    bool driving = false;
+    for (RayTracer* rt : group) driving = driving || rt->driveSpeed > 0.0f;
+    if (driving) {
+        // The segments are not part of uvrt_trace_batch: per iteration the stops are batched without their Shade, the
+        // segments go through the per-launch path, then the Shade the last stop would have carried.  One instance only.
+        if (group.size() > 1) fatal("driveSpeed > 0 is not supported with a group of instances (ray-range sharding)");
+        if (r0->reduceOverComm) fatal("driveSpeed > 0 is not supported with reduceOverComm");
+        if (r0->shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
+        if (r0->planCapture) fatal("driveSpeed > 0 is not supported with duration planning");
+        if (r0->rangeCount >= 0) fatal("driveSpeed > 0 is not supported with a ray range");
+        for (int it = 0; it < iterations; ++it) {
+            TraceBatched(group, 1, false);
+            r0->ComputeSegments();
+            r0->Shade();
+            ++r0->currIterations;
+            r0->progress = 100.0f * (float)r0->currIterations / (float)r0->maxIterations;
+        }
+        return;
+    }
+    TraceBatched(group, iterations, true);
+}
+
+// `iterations` x L stops in batches of up to 64 launches; withShade: the last stop of an iteration carries its Shade
+void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool withShade)
+{
+    RayTracer* r0 = group[0];
     const int L = (int)r0->lightPositions.size();
     const long long total = (long long)iterations * L;
     const int kMax = 64;                                  // launches per uvrt_trace_batch
@@ -226,7 +275,7 @@ void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, i
                 op.duration = lp.duration;                                       // :84
                 rt->photonMapSize += rt->photonsPerLight;                         // :87
                 ++rt->launchIndex;
-                op.shade = li == L - 1;                                          // myapp.cpp:160
+                op.shade = withShade && li == L - 1;                             // myapp.cpp:160
                 if (rt->viewMode == maxpower) {                                  // raytracer.cpp:96-104
                     op.which_map = UVRT_MAP_MAX;
                     op.photons_per_light = rt->photonsPerLight;
@@ -275,6 +324,8 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     RayTracer* r0 = group[0];
     const int L = (int)r0->lightPositions.size();
     if (L == 0) fatal("PlanDurations: no positions");
+    for (RayTracer* rt : group)
+        if (rt->driveSpeed > 0.0f) fatal("PlanDurations: planning with driveSpeed > 0 is not supported (the plan models stops only)");
     if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
         fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
     uint32_t seed0 = 0;
@@ -451,6 +502,7 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
     o << "    <lamp_sterkte>" << float_str(lightIntensity) << "</lamp_sterkte>\n";
     o << "    <minimale_dosis>" << float_str(minDosage) << "</minimale_dosis>\n";
     o << "    <minimale_bestralingssterkte>" << float_str(minPower) << "</minimale_bestralingssterkte>\n";
+    if (driveSpeed > 0.0f) o << "    <rijsnelheid>" << float_str(driveSpeed) << "</rijsnelheid>\n";   // (not in the reference's files)
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
     if (lightPositions.empty()) o << "    <route/>\n";
@@ -484,6 +536,8 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("lamp_sterkte"))) to_float(trim(e->text), &lightIntensity);
     if ((e = root.child("minimale_dosis"))) to_float(trim(e->text), &minDosage);
     if ((e = root.child("minimale_bestralingssterkte"))) to_float(trim(e->text), &minPower);
+    driveSpeed = 0.0f;
+    if ((e = root.child("rijsnelheid"))) to_float(trim(e->text), &driveSpeed);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

@@ -114,6 +114,20 @@ public:
     void SetCandidateGrid(int nx, int nz, float inset);
     static void GridPositions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz);
     bool planCapture = false;                       // ComputeIterationsBatched captures every batch (PlanDurations)
+    // Dose while the robot drives.  driveSpeed (m/s) > 0: after the stops of an iteration ComputeDosageMap traces the
+    // segments 0->1, ..., L-2->L-1 between consecutive positions, the lamp radiating while it moves at that speed
+    // (include/uvrt.h uvrt_generate_sweep: photonsPerLight photons spread uniformly in time over the segment).  A segment
+    // of length len adds its counts with the duration len / driveSpeed, like a stop that stood so long, but NOT to
+    // photonMapSize: Shade's divisor photonMapSize / lightPositions.size() stays the photons per source.  The maximum
+    // map takes a segment's counts like any launch: there it means the mean irradiance over the segment.  0 (default)
+    // is the reference's behaviour, bit for bit.  Saved as <rijsnelheid> in route files when > 0.
+    float driveSpeed = 0;
+    // one segment: a and b are two positions (their durations are not used); len = sqrtf(dx*dx + dz*dz) in f32
+    void ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount);
+    void ComputeSegments();                         // the segments of one iteration, in order (nothing at driveSpeed 0)
+private:
+    static void TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool withShade);
+public:
     // The reference never reads the dose back; the headless build does.
     void ReadDosage(float* out, int first, int count);
     void Sync();                        // clFinish(Kernel::GetQueue()), myapp.cpp:165

@@ -26,6 +26,9 @@
 //                                           pipeline and count the required triangles below the minimum (exit 1 unless 0)
 //            [--verify-dump FILE]           the dose of that recompute (raw f32 or .npy)
 //            [--plan-holdout SEED]          the same from another SEED: area fraction at or above the minimum (informative)
+//            [--drive-speed V]              the lamp radiates while the robot drives between consecutive positions at V m/s
+//                                           (RayTracer::driveSpeed; default: the route's <rijsnelheid>, 0 = stops only);
+//                                           one context, no planning
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -144,7 +147,7 @@ int main(int argc, char** argv)
     long long photons = -1;
     int iterations = -1, lamps = -1, device = 0, gpus = 1, batch = 0, flavour = 0;
     bool calibrate = false, plan = false, planVerify = false, planHoldout = false;
-    float planMin = -1.0f, gridInset = 0.5f;
+    float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f;
     int minPhotons = 16, gridX = 0, gridZ = 0;
     uint32_t holdoutSeed = 0;
     std::string verifyDump;
@@ -180,6 +183,7 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (!strcmp(argv[i], "--drive-speed")) { need(1); driveSpeed = (float)atof(argv[++i]); if (!(driveSpeed >= 0.0f)) { fprintf(stderr, "--drive-speed must be >= 0\n"); return 2; } }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -187,6 +191,8 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
+    if (driveSpeed > 0.0f && plan) { fprintf(stderr, "--drive-speed cannot be combined with --plan (the plan models stops only)\n"); return 2; }
+    if (driveSpeed > 0.0f && gpus != 1) { fprintf(stderr, "--drive-speed runs on one context (--gpus 1)\n"); return 2; }
     if (!routeDir.empty() && routeDir.back() != '/') routeDir += '/';
 
     Mesh mesh;
@@ -202,6 +208,11 @@ int main(int argc, char** argv)
     if (lamps > 0 && lamps < (int)rayTracer.lightPositions.size()) rayTracer.lightPositions.resize(lamps);
     if (photons > 0) rayTracer.photonCount = (int)photons;
     if (iterations > 0) rayTracer.maxIterations = iterations;
+    if (driveSpeed >= 0.0f) rayTracer.driveSpeed = driveSpeed;
+    if (rayTracer.driveSpeed > 0.0f && (plan || gpus != 1)) {     // (the route file's own <rijsnelheid>)
+        fprintf(stderr, "the route drives at %g m/s: not supported with --plan or --gpus > 1 (give --drive-speed 0)\n", (double)rayTracer.driveSpeed);
+        return 2;
+    }
     rayTracer.UpdatePhotonsPerLight();
 
     if (calibrate) {
