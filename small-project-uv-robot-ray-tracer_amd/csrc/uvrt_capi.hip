@@ -98,6 +98,7 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     if (const char* e = getenv("UVRT_BATCH_CHUNK_MB")) { const long v = atol(e); if (v > 0) c->batch_chunk_bytes = (size_t)v << 20; }
 #ifdef UVRT_DEV_VARIANTS
     if (const char* e = getenv("UVRT_PROBE_SKIP_GENERATE")) c->probe_skip_generate = atoi(e);
+    if (const char* e = getenv("UVRT_NEARFAR_MINMAX")) c->nearfar_minmax = atoi(e) != 0;   // the checker / A-B partner of the sign-ordered block
 #endif
     if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
     if (const char* e = getenv("UVRT_BATCH_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL - 1) c->batch_lanes = v; }

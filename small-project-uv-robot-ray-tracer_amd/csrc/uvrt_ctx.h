@@ -110,6 +110,7 @@ struct uvrt_ctx {
     int64_t capacity = 0;
     DevBuf keyrank, sorted, order, hits, hist, bin_start, export_buf;
     bool drain_merge = true;                   // k_extend6's workgroups pool the last rays of their waves (ExtendParams::drain_merge; developer knob UVRT_DRAIN_MERGE=0)
+    bool nearfar_minmax = false;               // developer build: k_extend6's stream with the min/max near / far block (ExtendParams::nearfar_minmax; UVRT_NEARFAR_MINMAX=1)
     bool scene_force_exact = false;            // a node bound too tiny / too large for the reciprocal shortcuts
     int32_t hist_bins = 0;
     int64_t last_n = -1;
@@ -448,6 +449,7 @@ inline void fill_launch(uvrt_ctx* c, ExtendParams& p, float ox, float oz)
     p.oz = oz;
     p.npairs = c->npairs;
     p.drain_merge = c->drain_merge;
+    p.nearfar_minmax = c->nearfar_minmax;
     p.refill_min = variant_refill_min(c->variant, (size_t)c->npairs + (size_t)c->T);
 }
 // uvrt_extend for the free rays of the last uvrt_write_free_rays / uvrt_generate_sweep (uvrt_capi_free.hip)

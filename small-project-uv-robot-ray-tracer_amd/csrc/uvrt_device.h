@@ -59,6 +59,10 @@ struct SceneDev {
 // `perm` (or nullptr = identity) renumbers the pair records: record i is written at perm[i] and the
 // inner references are translated, so that the records the lamp's rays visit most form the prefix
 // that the kernel serves from LDS.
+__device__ __forceinline__ void ascending(float& lo, float& hi)
+{
+    if (hi < lo) { const float t = lo; lo = hi; hi = t; }
+}
 __device__ __forceinline__ void prepare_record6(const PairRec* __restrict__ pairs, float4* __restrict__ recs,
                                                 float ox, float oz, int32_t npairs, int src,
                                                 const uint32_t* __restrict__ perm)
@@ -68,9 +72,18 @@ __device__ __forceinline__ void prepare_record6(const PairRec* __restrict__ pair
     if (r0 >= REF_LEAF_BIT) r0 += (uint32_t)npairs; else if (perm) r0 = perm[r0];
     if (r1 >= REF_LEAF_BIT) r1 += (uint32_t)npairs; else if (perm) r1 = perm[r1];
     const int i = perm ? (int)perm[src] : src;
-    recs[i * 4 + 0] = make_float4(pr.c0min_ref0.x - ox, pr.c0max_ref1.x - ox, pr.c0min_ref0.z - oz, pr.c0max_ref1.z - oz);
-    recs[i * 4 + 1] = make_float4(pr.c1min.x - ox, pr.c1max.x - ox, pr.c1min.z - oz, pr.c1max.z - oz);
-    recs[i * 4 + 2] = make_float4(pr.c0min_ref0.y, pr.c0max_ref1.y, pr.c1min.y, pr.c1max.y);
+    float4 w0 = make_float4(pr.c0min_ref0.x - ox, pr.c0max_ref1.x - ox, pr.c0min_ref0.z - oz, pr.c0max_ref1.z - oz);
+    float4 w1 = make_float4(pr.c1min.x - ox, pr.c1max.x - ox, pr.c1min.z - oz, pr.c1max.z - oz);
+    float4 w2 = make_float4(pr.c0min_ref0.y, pr.c0max_ref1.y, pr.c1min.y, pr.c1max.y);
+    // every pair in ascending order: k_extend6's stream takes the nearer slab distance of a pair from the sign of the ray's
+    // direction alone.  A no-op for a box with min <= max; an inverted box keeps both values (every other consumer takes the
+    // min and the max of the pair's two distances); a pair with a NaN stays as it is.
+    ascending(w0.x, w0.y); ascending(w0.z, w0.w);
+    ascending(w1.x, w1.y); ascending(w1.z, w1.w);
+    ascending(w2.x, w2.y); ascending(w2.z, w2.w);
+    recs[i * 4 + 0] = w0;
+    recs[i * 4 + 1] = w1;
+    recs[i * 4 + 2] = w2;
     recs[i * 4 + 3] = make_float4(__uint_as_float(r0), __uint_as_float(r1), 0.f, 0.f);
 }
 
@@ -207,6 +220,7 @@ struct ExtendParams {
     uint32_t top_pairs;      // pair records [0, top_pairs) = the tree levels cached in LDS (<= TOP6_MAX)
     int32_t force_exact;     // scene or lamp position outside the fast path's proof conditions
     int32_t drain_merge;     // k_extend6: the four waves of a workgroup pool the last rays of their drains in one wave (merge6)
+    int32_t nearfar_minmax;  // k_extend6, developer build: the stream's min/max near / far block instead of the sign-ordered one
     int32_t flavour;         // 0 strict (canonical), 1 "ocl-amd" fused cross/dot in the triangle test
     const uint32_t* order;   // [n] trace slot -> local ray index, or nullptr (identity)
     uint2* hits;             // [n] by local ray index: (dist bits, triID), or nullptr

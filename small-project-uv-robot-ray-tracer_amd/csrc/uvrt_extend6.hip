@@ -14,7 +14,11 @@
 //    correctly rounded reciprocal for every binary32 in [2^-64, 2^64) (tests/tools/rcp_exhaustive.hip);
 //  * the x / z numerators a = b - o use the lamp's launch-uniform coordinates: k_prepare_launch6
 //    writes per-launch node-pair records with that subtraction applied, (min, max) of one axis of
-//    one child in a register pair;
+//    one child in a register pair, the smaller value first;
+//  * flavours 0 / 1: the nearer of a pair's two slab distances is known from the sign of the ray's
+//    direction component (ordered numerators, monotone division), so the lanes with a negative
+//    component exchange the pair's registers and the box block needs no two-input min / max
+//    (R7_ENTER_BOX_SIGN below);
 //  * ONE record array: pair records [0, P) and 64-byte leaf-triangle records [P, P + T) -- a child
 //    reference is its record index, so the fetch address is one shift-add for inner and leaf lanes;
 //  * the 175 most visited records of the lamp (two thirds of the node visits) are served from LDS;
@@ -383,7 +387,64 @@ __device__ __forceinline__ void step7(Lane6& L, const ExtendParams& p, uint32_t 
         "v_pk_mul_f32 v[46:47], v[46:47], %[pz] op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
         "v_pk_mul_f32 v[48:49], v[48:49], %[py] op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
         "v_pk_mul_f32 v[50:51], v[50:51], %[py] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
-#define R7_BODY(TRI, SLABS) \
+// The near / far block: the twelve slab distances of a node pair -> tmin / tmax of both children (v61 / v62, v63 / v54).
+//   MINMAX (flavour 2; the developer build's checker; what the committed issue models price): the nearer and the farther element of each pair as
+//     v_min_f32 / v_max_f32, twelve of them, then the two v_max3_f32 / v_min3_f32;
+//   SIGN (flavours 0 / 1): which element of a pair (t at the min bound, t at the max bound) is the nearer one is the sign of the
+//     ray's direction component -- the records hold every numerator pair in ascending order (prepare_record6) and correctly
+//     rounded division is monotone -- so each lane with a negative component exchanges the two registers of the pair
+//     (v_pk_mov_b32 op_sel:[1,0] under exec = inner lanes & negative lanes: 4 issue cycles, profiles/r07/r07_swap_calibration.txt;
+//     v_swap_b32 costs 8) BEFORE the divisions, and the block is the two v_max3_f32 / v_min3_f32 alone.  %[nx] %[ny] %[nz] are
+//     the wave's masks of lanes with a negative component (ballots taken before each entry: rays change between entries only).
+//     A lane with a zero, NaN or out-of-range component is `special` and never active in this stream.
+#define R7_ENTER_BOX \
+        "s_mov_b64 exec, %[m0]\n\t"   /* the box arithmetic under the inner lanes' mask: same issue cost, less switching power */
+#define R7_ENTER_BOX_SIGN \
+        "s_and_b64 exec, %[m0], %[nx]\n\t" \
+        "v_pk_mov_b32 v[40:41], v[40:41], v[40:41] op_sel:[1,0]\n\t" \
+        "v_pk_mov_b32 v[44:45], v[44:45], v[44:45] op_sel:[1,0]\n\t" \
+        "s_and_b64 exec, %[m0], %[nz]\n\t" \
+        "v_pk_mov_b32 v[42:43], v[42:43], v[42:43] op_sel:[1,0]\n\t" \
+        "v_pk_mov_b32 v[46:47], v[46:47], v[46:47] op_sel:[1,0]\n\t" \
+        "s_and_b64 exec, %[m0], %[ny]\n\t" \
+        "v_pk_mov_b32 v[48:49], v[48:49], v[48:49] op_sel:[1,0]\n\t" \
+        "v_pk_mov_b32 v[50:51], v[50:51], v[50:51] op_sel:[1,0]\n\t" \
+        R7_ENTER_BOX
+#define R7_NEARFAR_MINMAX \
+        "v_min_f32 v58, v40, v41\n\t" \
+        "v_min_f32 v59, v48, v49\n\t" \
+        "v_min_f32 v60, v42, v43\n\t" \
+        "v_max3_f32 v61, v58, v59, v60\n\t" \
+        "v_max_f32 v58, v40, v41\n\t" \
+        "v_max_f32 v59, v48, v49\n\t" \
+        "v_max_f32 v60, v42, v43\n\t" \
+        "v_min3_f32 v62, v58, v59, v60\n\t" \
+        "v_min_f32 v58, v44, v45\n\t" \
+        "v_min_f32 v59, v50, v51\n\t" \
+        "v_min_f32 v60, v46, v47\n\t" \
+        "v_max3_f32 v63, v58, v59, v60\n\t" \
+        "v_max_f32 v58, v44, v45\n\t" \
+        "v_max_f32 v59, v50, v51\n\t" \
+        "v_max_f32 v60, v46, v47\n\t" \
+        "v_min3_f32 v54, v58, v59, v60\n\t"
+#define R7_NEARFAR_SIGN \
+        "v_max3_f32 v61, v40, v48, v42\n\t" \
+        "v_min3_f32 v62, v41, v49, v43\n\t" \
+        "v_max3_f32 v63, v44, v50, v46\n\t" \
+        "v_min3_f32 v54, v45, v51, v47\n\t"
+// developer build: both blocks in one stream, chosen by the scalar %[mm] (the caller hands over empty sign masks with it)
+#define R7_NEARFAR_EITHER \
+        "s_cmp_lg_u32 %[mm], 0\n\t" \
+        "s_cbranch_scc1 20f\n\t" \
+        R7_NEARFAR_SIGN \
+        "s_branch 21f\n\t" \
+        "20:\n\t" \
+        R7_NEARFAR_MINMAX \
+        "21:\n\t"
+#define R7_BODY(TRI, SLABS) R7_BODY_(TRI, R7_ENTER_BOX, SLABS, R7_NEARFAR_MINMAX)
+#define R7_BODY_SIGN(TRI, SLABS) R7_BODY_(TRI, R7_ENTER_BOX_SIGN, SLABS, R7_NEARFAR_SIGN)
+#define R7_BODY_EITHER(TRI, SLABS) R7_BODY_(TRI, R7_ENTER_BOX_SIGN, SLABS, R7_NEARFAR_EITHER)
+#define R7_BODY_(TRI, ENTER_BOX, SLABS, NEARFAR) \
         "1:\n\t" \
         "v_cmp_lt_i32_e64 %[m0], -1, %[cur]\n\t" \
         "v_cmp_gt_i32_e64 %[m1], -1, %[cur]\n\t" \
@@ -436,24 +497,9 @@ __device__ __forceinline__ void step7(Lane6& L, const ExtendParams& p, uint32_t 
         "4:\n\t" \
         "s_cmp_eq_u64 %[m0], 0\n\t" \
         "s_cbranch_scc1 5f\n\t" \
-        "s_mov_b64 exec, %[m0]\n\t"   /* the box arithmetic under the inner lanes' mask: same issue cost, less switching power */ \
+        ENTER_BOX \
         SLABS \
-        "v_min_f32 v58, v40, v41\n\t" \
-        "v_min_f32 v59, v48, v49\n\t" \
-        "v_min_f32 v60, v42, v43\n\t" \
-        "v_max3_f32 v61, v58, v59, v60\n\t" \
-        "v_max_f32 v58, v40, v41\n\t" \
-        "v_max_f32 v59, v48, v49\n\t" \
-        "v_max_f32 v60, v42, v43\n\t" \
-        "v_min3_f32 v62, v58, v59, v60\n\t" \
-        "v_min_f32 v58, v44, v45\n\t" \
-        "v_min_f32 v59, v50, v51\n\t" \
-        "v_min_f32 v60, v46, v47\n\t" \
-        "v_max3_f32 v63, v58, v59, v60\n\t" \
-        "v_max_f32 v58, v44, v45\n\t" \
-        "v_max_f32 v59, v50, v51\n\t" \
-        "v_max_f32 v60, v46, v47\n\t" \
-        "v_min3_f32 v54, v58, v59, v60\n\t" \
+        NEARFAR \
         "v_cmpx_ge_f32_e64 %[m2], v62, v61\n\t" \
         "v_cmpx_lt_f32_e64 %[m2], v61, %[dist]\n\t" \
         "v_cmpx_gt_f32_e64 %[m2], v62, 0\n\t" \
@@ -489,17 +535,42 @@ __device__ __forceinline__ void step7(Lane6& L, const ExtendParams& p, uint32_t 
         "s_mov_b32 %[code], 2\n\t" \
         "9:"
 
-#define R7_OPERANDS \
+#define R7_OPERANDS_OUT \
         : [cur] "+v"(L.cur), [sp] "+v"(L.sp), [dist] "+v"(dist), [tri] "+v"(L.triID), [km] "+s"(km), [code] "=&s"(code), \
-          [m0] "=&s"(m0), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3), [m4] "=&s"(m4) \
+          [m0] "=&s"(m0), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3), [m4] "=&s"(m4)
+#define R7_OPERANDS_IN \
         : [px] "v"(L.px), [py] "v"(L.py), [pz] "v"(L.pz), [po] "v"(L.po), [dx] "v"(L.px.x), [dy] "v"(L.py.x), [dz] "v"(L.pz.x), \
           [oy] "v"(oy), [sb] "v"(stack_base), [tb] "s"(__builtin_amdgcn_readfirstlane(top_base)), [rb] "s"(p.recs), [spec] "s"(special_mask), \
-          [tp] "s"(top_pairs), [amin] "s"(active_min), [ox] "s"(p.ox), [oz] "s"(p.oz) \
+          [tp] "s"(top_pairs), [amin] "s"(active_min), [ox] "s"(p.ox), [oz] "s"(p.oz)
+#define R7_OPERANDS_SIGN , [nx] "s"(neg.x), [ny] "s"(neg.y), [nz] "s"(neg.z)
+#define R7_OPERANDS_END \
         : "memory", "scc", "vcc", R7_CLOBBERS
+#define R7_OPERANDS R7_OPERANDS_OUT R7_OPERANDS_IN R7_OPERANDS_END
+#ifdef UVRT_DEV_VARIANTS      // the developer build carries the min/max block beside the sign-ordered one (UVRT_NEARFAR_MINMAX=1)
+#define R7_BODY_PRODUCT R7_BODY_EITHER
+#define R7_OPERANDS_PRODUCT R7_OPERANDS_OUT R7_OPERANDS_IN R7_OPERANDS_SIGN, [mm] "s"(p.nearfar_minmax) R7_OPERANDS_END
+#else
+#define R7_BODY_PRODUCT R7_BODY_SIGN
+#define R7_OPERANDS_PRODUCT R7_OPERANDS_OUT R7_OPERANDS_IN R7_OPERANDS_SIGN R7_OPERANDS_END
+#endif
+
+// the wave's masks of lanes whose direction component is negative, per axis (run7's sign-ordered near / far block)
+struct NegMasks { unsigned long long x, y, z; };
+
+// developer build: the min/max block instead of the sign-ordered one (ExtendParams::nearfar_minmax)
+__device__ __forceinline__ bool nearfar_minmax(const ExtendParams& p)
+{
+#ifdef UVRT_DEV_VARIANTS
+    return p.nearfar_minmax != 0;
+#else
+    (void)p;
+    return false;
+#endif
+}
 
 template <int FL, int LEAFP>
 __device__ __forceinline__ int run7(Lane6& L, const ExtendParams& p, uint32_t stack_base, uint32_t top_base,
-                                    uint32_t top_pairs, unsigned long long special_mask, int& km,
+                                    uint32_t top_pairs, unsigned long long special_mask, const NegMasks& neg, int& km,
                                     unsigned long long full, int active_min)
 {
     static_assert(LEAFP == 2, "run7 visits leaves in every second trip");
@@ -511,13 +582,14 @@ __device__ __forceinline__ int run7(Lane6& L, const ExtendParams& p, uint32_t st
     float dist = L.po.y;
     const float oy = L.po.x;
     static_assert(PS6 == 8, "run7 compares the stack pointer with the literal PS6 - 1");
+    (void)neg;       // (flavour 2 keeps the min/max block: 0 * inf = NaN there, and it has no special lanes)
     (void)full;      // the loop's exec mask is all 64 lanes (full workgroups): the stream writes it as the literal -1, one register pair less
     if constexpr (FL == 2)
         asm volatile(R7_BODY(R7_TRI(R7_CROSS_OCL, R7_DOT_OCL, R7_NEWTON_NONE, R7_GO_A_SHIPPED, R7_GO_01_SHIPPED), R7_SLABS_SHIPPED) R7_OPERANDS);
     else if constexpr (FL == 1)
-        asm volatile(R7_BODY(R7_TRI(R7_CROSS_OCL, R7_DOT_OCL, R7_NEWTON_EXACT, R7_GO_A_STRICT, R7_GO_01_STRICT), R7_SLABS_EXACT) R7_OPERANDS);
+        asm volatile(R7_BODY_PRODUCT(R7_TRI(R7_CROSS_OCL, R7_DOT_OCL, R7_NEWTON_EXACT, R7_GO_A_STRICT, R7_GO_01_STRICT), R7_SLABS_EXACT) R7_OPERANDS_PRODUCT);
     else
-        asm volatile(R7_BODY(R7_TRI(R7_CROSS_STRICT, R7_DOT_STRICT, R7_NEWTON_EXACT, R7_GO_A_STRICT, R7_GO_01_STRICT), R7_SLABS_EXACT) R7_OPERANDS);
+        asm volatile(R7_BODY_PRODUCT(R7_TRI(R7_CROSS_STRICT, R7_DOT_STRICT, R7_NEWTON_EXACT, R7_GO_A_STRICT, R7_GO_01_STRICT), R7_SLABS_EXACT) R7_OPERANDS_PRODUCT);
     L.po.y = dist;
     return code;
 }
@@ -665,6 +737,13 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
             // (two call sites: a select between the two thresholds would drag `cursor` into a vector register)
             int why;
             const unsigned long long special_mask = FL == 2 ? 0ull : __builtin_amdgcn_ballot_w64((int32_t)plane_off < 0);
+            // lanes that exchange the elements of a slab pair (R7_ENTER_BOX_SIGN); rays change between entries only
+            NegMasks neg = {0ull, 0ull, 0ull};
+            if (FL != 2 && !nearfar_minmax(p)) {
+                neg.x = __builtin_amdgcn_ballot_w64(L.px.x < 0.0f);
+                neg.y = __builtin_amdgcn_ballot_w64(L.py.x < 0.0f);
+                neg.z = __builtin_amdgcn_ballot_w64(L.pz.x < 0.0f);
+            }
             // rays at which the stream comes back: enough idle lanes for a refill; the wave's share handed out: MERGE6_AT for the
             // drain merge, afterwards none.  ONE call site (each one gets its own registers for the lane state, and the loop then
             // copies it at every join), so the threshold is a value -- computed with scalar instructions spelled out: a C++ select
@@ -675,7 +754,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
                 "s_cmp_lt_u32 %[c], %[e]\n\t"
                 "s_cselect_b32 %[t], %[a], %[t]"
                 : [t] "=&s"(thr) : [c] "s"(cursor), [e] "s"(chunk_end), [a] "s"(64 - refill_c), [k] "n"(TOP ? MERGE6_AT : 0u) : "scc");
-            why = run7<FL, LEAFP>(L, p, stack_base, top_base, top_pairs, special_mask, kflag, full, thr);
+            why = run7<FL, LEAFP>(L, p, stack_base, top_base, top_pairs, special_mask, neg, kflag, full, thr);
             why = __builtin_amdgcn_readfirstlane(why);
             kflag = __builtin_amdgcn_readfirstlane(kflag);
             if (why == 1) {
