@@ -137,8 +137,9 @@ uint32_t uvrt_seed_next_mode(const float light_pos[3], float light_length, uint3
  * test, triangle test and deposit: (dist, triID) and the counts are bit-identical to the CPU restatement in flavours 0 and
  * 1) into the same tempPhotonMap, so uvrt_accumulate, uvrt_shade, uvrt_read_counts and uvrt_device_ptr work unchanged.
  * Flavour 2 is refused (UVRT_ERR_INVALID) for such a launch; uvrt_set_wide_bvh and uvrt_set_sort_bits are ignored by it;
- * uvrt_set_record_hits + uvrt_read_rays return every ray's own origin.  uvrt_trace_batch takes no sweeps.  The
- * {orig.x, orig.z} array and the kernel's per-scene records are allocated by the first such call.
+ * uvrt_set_record_hits + uvrt_read_rays return every ray's own origin.  uvrt_trace_batch_launches ("batched tracing"
+ * below) traces sweeps and stops side by side.  The {orig.x, orig.z} array and the kernel's per-scene records are
+ * allocated by the first such call.
  *
  * uvrt_generate_sweep: generate for a lamp that moves from `from` to `to` at constant speed while it radiates.  Work-item
  * gid runs generate.cl:13-35 with lightPos = from under the SEED semantics of uvrt_generate (mode 0: work-item 0 reads
@@ -178,6 +179,23 @@ typedef struct {
  * uvrt_generate would.  The deposits stay in the batch's planes until uvrt_replay_batch. */
 int uvrt_trace_batch(uvrt_ctx* ctx, const float* lamps, float light_length, int32_t count,
                      int64_t first_gid, int64_t n);
+/* uvrt_trace_batch for launches of either kind: launch k is a stop at launches[k].from, or a sweep from launches[k].from
+ * to launches[k].to (uvrt_generate_sweep).  The SEED chain advances in logical order, by uvrt_seed_next_mode at a stop and
+ * by uvrt_seed_next_sweep at a sweep; every launch has its own count plane, and fold, reduce, read, plan capture, replay and
+ * uvrt_device_ptr(ctx, 5, ...) work as after uvrt_trace_batch.  Stops are traced as uvrt_trace_batch traces them (a batch
+ * of stops only is that call); all sweeps of the batch share the scene's free-origin records and are traced by the
+ * free-origin kernel, several planes per kernel launch.  UVRT_ERR_INVALID, with nothing changed (SEED, the batch, the launch
+ * lanes): whatever uvrt_trace_batch refuses, a kind other than the two below, and a sweep under uvrt_set_seed_mode(ctx, 1)
+ * or uvrt_set_flavour(ctx, 2). */
+enum { UVRT_LAUNCH_STOP = 0, UVRT_LAUNCH_SWEEP = 1 };
+typedef struct {
+    float from[3];      /* the lamp's foot (a stop), or where the sweep starts */
+    float to[3];        /* where the sweep ends; ignored for a stop */
+    int32_t kind;       /* UVRT_LAUNCH_STOP / UVRT_LAUNCH_SWEEP */
+    int32_t reserved;   /* 0 */
+} uvrt_launch;
+int uvrt_trace_batch_launches(uvrt_ctx* ctx, const uvrt_launch* launches, float light_length,
+                              int32_t count, int64_t first_gid, int64_t n);
 /* per launch (logical order): accumulate.cl, then Shade where ops[k].shade is set; ends the batch */
 int uvrt_replay_batch(uvrt_ctx* ctx, const uvrt_replay_op* ops, int32_t count, int32_t tri_count);
 /* sum the deposit replicas of every plane into the int32[count][T] array the reduction works on */

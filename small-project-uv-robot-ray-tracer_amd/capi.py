@@ -46,6 +46,7 @@ SYMBOLS = [
     ("uvrt_set_seed", C.c_int, [_vp, _u32]),
     ("uvrt_seed_next", _u32, [_fp, _f32, _u32]),
     ("uvrt_trace_batch", C.c_int, [_vp, _fp, _f32, _i32, _i64, _i64]),
+    ("uvrt_trace_batch_launches", C.c_int, [_vp, _vp, _f32, _i32, _i64, _i64]),
     ("uvrt_replay_batch", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_fold_batch", C.c_int, [_vp]),
     ("uvrt_read_batch_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
@@ -125,6 +126,21 @@ def round_trip_up(v):
 # uvrt_replay_op (include/uvrt.h)
 REPLAY_OP_DT = np.dtype([("duration", "<f4"), ("shade", "<i4"), ("which_map", "<i4"), ("photons_per_light", "<i4"),
                          ("scaled_power", "<f4"), ("min_value", "<f4"), ("threshold_view", "<i4")])
+
+# uvrt_launch (include/uvrt.h)
+LAUNCH_STOP, LAUNCH_SWEEP = 0, 1
+LAUNCH_DT = np.dtype([("from", "<f4", (3,)), ("to", "<f4", (3,)), ("kind", "<i4"), ("reserved", "<i4")])
+
+
+def stop(at):
+    """a uvrt_launch: the lamp stands at `at`"""
+    return (tuple(at), (0.0, 0.0, 0.0), LAUNCH_STOP, 0)
+
+
+def sweep(frm, to):
+    """a uvrt_launch: the lamp moves from `frm` to `to` while it radiates"""
+    return (tuple(frm), tuple(to), LAUNCH_SWEEP, 0)
+
 
 _LIB = {}
 
@@ -334,6 +350,12 @@ class Ctx:
         lamps = np.ascontiguousarray(lamps, dtype=np.float32).reshape(-1, 3)
         self._ck(self._L.uvrt_trace_batch(self._h, lamps.ctypes.data_as(_fp), float(np.float32(light_length)),
                                           lamps.shape[0], int(first_gid), int(n)))
+
+    def trace_batch_launches(self, launches, light_length, first_gid, n):
+        """launches: array of LAUNCH_DT (or tuples in its field order: stop() / sweep()), in logical order"""
+        launches = np.ascontiguousarray(np.array(launches, dtype=LAUNCH_DT))
+        self._ck(self._L.uvrt_trace_batch_launches(self._h, _ptr(launches), float(np.float32(light_length)),
+                                                   launches.size, int(first_gid), int(n)))
 
     def replay_batch(self, ops, tri_count=None):
         """ops: array of REPLAY_OP_DT (or tuples in its field order), one per launch in logical order"""

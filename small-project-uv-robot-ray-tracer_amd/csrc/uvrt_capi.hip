@@ -152,7 +152,7 @@ void uvrt_destroy(uvrt_ctx* c)
     for (DevBuf& b : c->b_recs) b.release();
     (void)hot_reset(c, false);            // (and the lanes' set-up scratch)
     for (auto& bset : c->bs) {
-        for (DevBuf* b : {&bset.rays, &bset.planes, &bset.folded}) b->release();
+        for (DevBuf* b : {&bset.rays, &bset.planes, &bset.folded, &bset.oxz}) b->release();
         if (bset.free_ev) (void)hipEventDestroy(bset.free_ev);
     }
     for (DevBuf* b : {&c->pairs, &c->perm, &c->ltris, &c->leaf_count, &c->area, &c->photon_map, &c->max_map,

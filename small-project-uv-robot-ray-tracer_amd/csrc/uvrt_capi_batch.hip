@@ -5,17 +5,34 @@
 using namespace uvrt;
 using namespace uvrt_impl;
 
-extern "C" {
+namespace uvrt_impl {
 
-int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_t count, int64_t first_gid, int64_t n)
+// uvrt_trace_batch and uvrt_trace_batch_launches (`who` names the caller in the error texts): generate + extend for `count`
+// launches, stops grouped by lamp column and traced by k_extend6, sweeps as one further group traced by the plane-aware
+// k_extend_free.  Physical planes: the stops' groups first, then the sweeps in logical order.
+static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_length, int32_t count, int64_t first_gid,
+                          int64_t n, const char* who)
 {
-    if (!c || !lamps || !c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: null argument or no scene");
-    if (count <= 0 || count > MAX_BATCH) return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: count must be in [1,%d]", MAX_BATCH);
+    if (!c || !launches || !c->have_scene) return fail(UVRT_ERR_INVALID, "%s: null argument or no scene", who);
+    if (count <= 0 || count > MAX_BATCH) return fail(UVRT_ERR_INVALID, "%s: count must be in [1,%d]", who, MAX_BATCH);
     if (n <= 0 || first_gid < 0 || first_gid + n > (int64_t)INT32_MAX)
-        return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: bad global-id range");
-    if (c->b_count > 0) return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: the previous batch has not been replayed (uvrt_replay_batch)");
+        return fail(UVRT_ERR_INVALID, "%s: bad global-id range", who);
+    if (c->b_count > 0) return fail(UVRT_ERR_INVALID, "%s: the previous batch has not been replayed (uvrt_replay_batch)", who);
     if (c->record_hits || c->sort_bits != 0)
-        return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: per-ray hit records and ray ordering are per-launch features");
+        return fail(UVRT_ERR_INVALID, "%s: per-ray hit records and ray ordering are per-launch features", who);
+    int nsweeps = 0;
+    for (int k = 0; k < count; ++k) {
+        if (launches[k].kind != UVRT_LAUNCH_STOP && launches[k].kind != UVRT_LAUNCH_SWEEP)
+            return fail(UVRT_ERR_INVALID, "%s: launch %d: kind must be UVRT_LAUNCH_STOP or UVRT_LAUNCH_SWEEP", who, k);
+        nsweeps += launches[k].kind == UVRT_LAUNCH_SWEEP;
+    }
+    if (nsweeps > 0 && c->seed_mode != 0)
+        return fail(UVRT_ERR_INVALID, "%s: seed mode 1 models the SEED race of generate.cl only; a sweep needs "
+                    "uvrt_set_seed_mode(ctx, 0)", who);
+    if (nsweeps > 0 && c->flavour != 0 && c->flavour != 1)
+        return fail(UVRT_ERR_INVALID, "%s: rays with origins of their own are traced in flavours 0 and 1 only "
+                    "(uvrt_set_flavour %d)", who, c->flavour);
+    const int nstops = count - nsweeps;
     if (int rc = set_device(c)) return rc;
     const int64_t n_pad = (n + 63) / 64 * 64;
     // deposit replicas per plane: the contention on a hot triangle's counter grows with the rays per plane
@@ -26,33 +43,49 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
     int R = std::min(c->replicas, 12);
     if ((int64_t)R * 131072 > 2 * n) R = std::min(c->replicas, 8);
     if ((uint64_t)count * (uint64_t)n_pad >= ((uint64_t)1 << 30) || (uint64_t)count * (uint64_t)R * (uint64_t)c->T >= ((uint64_t)1 << 32))
-        return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: %d launches x %lld rays exceed one batch (2^30 ray slots, 2^32 counters)", count, (long long)n);
+        return fail(UVRT_ERR_INVALID, "%s: %d launches x %lld rays exceed one batch (2^30 ray slots, 2^32 counters)", who, count, (long long)n);
 
-    // group the launches by lamp column (x, z): the per-launch node-pair records depend on it only
+    // group the stops by lamp column (x, z): the per-launch node-pair records depend on it only
     int group_of[MAX_BATCH], ngroups = 0, gfirst[MAX_BATCH], gsize[MAX_BATCH] = {};
     float gx[MAX_BATCH], gz[MAX_BATCH];
     for (int k = 0; k < count; ++k) {
+        if (launches[k].kind != UVRT_LAUNCH_STOP) continue;
+        const float* lamp = launches[k].from;
         int g = 0;
         for (; g < ngroups; ++g)
-            if (memcmp(&gx[g], &lamps[3 * k], 4) == 0 && memcmp(&gz[g], &lamps[3 * k + 2], 4) == 0) break;
-        if (g == ngroups) { gx[g] = lamps[3 * k]; gz[g] = lamps[3 * k + 2]; ++ngroups; }
+            if (memcmp(&gx[g], &lamp[0], 4) == 0 && memcmp(&gz[g], &lamp[2], 4) == 0) break;
+        if (g == ngroups) { gx[g] = lamp[0]; gz[g] = lamp[2]; ++ngroups; }
         group_of[k] = g;
         ++gsize[g];
     }
     for (int g = 0, acc = 0; g < ngroups; ++g) { gfirst[g] = acc; acc += gsize[g]; }
-    GenBatchParams gp;
+    GenBatchParams gp;                  // the stops, by physical plane
     memset(&gp, 0, sizeof gp);
+    SweepBatchParams sp;                // the sweeps, by physical plane - nstops
+    memset(&sp, 0, sizeof sp);
+    int32_t phys[MAX_BATCH];            // committed (c->b_phys) with the batch
     uint32_t seed_after = c->seed;
     {
-        int fill[MAX_BATCH] = {};
+        int fill[MAX_BATCH] = {}, sfill = 0;
         uint32_t seed = c->seed;
         for (int k = 0; k < count; ++k) {                    // logical order: the SEED chain
-            const int g = group_of[k], ph = gfirst[g] + fill[g]++;
-            c->b_phys[k] = ph;
-            gp.lx[ph] = lamps[3 * k]; gp.ly[ph] = lamps[3 * k + 1]; gp.lz[ph] = lamps[3 * k + 2];
-            gp.seed_prev[ph] = seed;
-            seed = uvrt_seed_next_mode(&lamps[3 * k], light_length, seed, c->seed_mode);
-            gp.seed_next[ph] = seed;
+            const uvrt_launch& l = launches[k];
+            if (l.kind == UVRT_LAUNCH_STOP) {
+                const int g = group_of[k], ph = gfirst[g] + fill[g]++;
+                phys[k] = ph;
+                gp.lx[ph] = l.from[0]; gp.ly[ph] = l.from[1]; gp.lz[ph] = l.from[2];
+                gp.seed_prev[ph] = seed;
+                seed = uvrt_seed_next_mode(l.from, light_length, seed, c->seed_mode);
+                gp.seed_next[ph] = seed;
+            } else {
+                const int j = sfill++;
+                phys[k] = nstops + j;
+                sp.fx[j] = l.from[0]; sp.fy[j] = l.from[1]; sp.fz[j] = l.from[2];
+                sp.tx[j] = l.to[0]; sp.ty[j] = l.to[1]; sp.tz[j] = l.to[2];
+                sp.seed_prev[j] = seed;
+                seed = uvrt_seed_next_sweep(l.from, light_length, seed);
+                sp.seed_next[j] = seed;
+            }
         }
         seed_after = seed;              // committed with the batch: a failed call leaves the SEED chain where it was
     }
@@ -69,7 +102,8 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
     // growing a buffer needs the device idle (hipFree / hipMalloc); new per-launch records only need the context's stream
     // ordered after the lanes' earlier work -- no host synchronisation, so a new lamp position costs its kernels only
     const bool need_alloc = S.rays.bytes < (size_t)count * (size_t)n_pad * 16 || S.planes.bytes < (size_t)count * plane_alloc * 4 ||
-                            S.folded.bytes < (size_t)count * (size_t)c->T * 4 || (int)c->b_recs.size() < ngroups || !S.free_ev;
+                            S.folded.bytes < (size_t)count * (size_t)c->T * 4 || (int)c->b_recs.size() < ngroups || !S.free_ev ||
+                            S.oxz.bytes < (size_t)nsweeps * (size_t)n_pad * 8 || (nsweeps > 0 && !c->free_recs_valid);
     bool recs_stale = false;
     const uint32_t* gperm[MAX_BATCH] = {};
     uint64_t ggen[MAX_BATCH] = {};
@@ -109,6 +143,7 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
         if ((rc = S.rays.ensure((size_t)count * (size_t)n_pad * 16, false, c->stream))) return rc;
         if ((rc = S.planes.ensure((size_t)count * plane_alloc * 4, true, c->stream))) return rc;
         if ((rc = S.folded.ensure((size_t)count * (size_t)c->T * 4, true, c->stream))) return rc;
+        if ((rc = S.oxz.ensure((size_t)nsweeps * (size_t)n_pad * 8, false, c->stream))) return rc;      // (8 B of origin per photon of a sweep)
         if (grown) HIP_TRY(hipEventRecord(S.free_ev, c->stream));      // the zero fill is the set's "last replay"
         while ((int)c->b_recs.size() < ngroups) {
             DevBuf b;
@@ -127,6 +162,12 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
             if (key.holds(gx[g], gz[g], gperm[g], ggen[g])) continue;
             launch_prepare_launch6(c->pairs.as<PairRec>(), c->b_recs[g].p, gx[g], gz[g], c->npairs, gperm[g], c->stream);
             key = {{true, gx[g], gz[g]}, gperm[g], ggen[g]};
+        }
+        // the scene's free records, on first use (ensure_free_buffers, uvrt_capi_free.hip)
+        if (nsweeps > 0 && !c->free_recs_valid) {
+            if ((rc = c->free_recs.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream))) return rc;
+            launch_prepare_free_records(c->pairs.as<PairRec>(), c->ltris.as<LeafTri>(), c->free_recs.p, c->npairs, c->T, c->stream);
+            c->free_recs_valid = true;
         }
         HIP_TRY(hipGetLastError());
         if (int rcf = mark_fence(c)) return rcf;         // the lanes' next work waits for the records
@@ -191,11 +232,61 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
             hipEvent_t e1;
             if (int rct = timing_start(c, ls, &e1)) return rct;
             if (!launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, c->pipeline ? 7 : 8), ls)) {
-                return fail(UVRT_ERR_INVALID, "uvrt_trace_batch: variant %d needs a larger overflow-stack buffer", c->variant);
+                return fail(UVRT_ERR_INVALID, "%s: variant %d needs a larger overflow-stack buffer", who, c->variant);
             }
             HIP_TRY(hipGetLastError());
             if (e1) HIP_TRY(hipEventRecord(e1, ls));
         }
+    }
+    // The sweeps: one further group (the free records are the scene's, whatever the segment), in chunks of as many bytes --
+    // 16 B of ray plus 8 B of origin per photon -- over the same lanes in the same rotation.
+    const int per_sweep_chunk = (int)std::max<size_t>(1, c->batch_chunk_bytes / ((size_t)n_pad * 24));
+    for (int k0 = 0; k0 < nsweeps; k0 += per_sweep_chunk, ++chunk_index) {
+        const int kc = std::min(per_sweep_chunk, nsweeps - k0), ph0 = nstops + k0;
+        c->lane = c->pipeline ? 1 + (int)(c->b_chunks++ % (uint64_t)c->batch_lanes) : 0;
+        hipStream_t ls = stream_of(c, c->lane);
+        if (c->lane != 0) cur_lane(c).used = true;
+        if (!lane_waited[c->lane]) {
+            HIP_TRY(hipStreamWaitEvent(ls, S.free_ev, 0));
+            lane_waited[c->lane] = true;
+        }
+        SweepBatchParams sq;
+        memset(&sq, 0, sizeof sq);
+        sq.rays = S.rays.as<float4>() + (size_t)ph0 * (size_t)n_pad;
+        sq.oxz = S.oxz.as<float2>() + (size_t)k0 * (size_t)n_pad;
+        sq.n_pad = n_pad;
+        sq.first_gid = first_gid;
+        sq.n = n;
+        sq.light_length = light_length;
+        sq.count = kc;
+        for (int j = 0; j < kc; ++j) {
+            sq.fx[j] = sp.fx[k0 + j]; sq.fy[j] = sp.fy[k0 + j]; sq.fz[j] = sp.fz[k0 + j];
+            sq.tx[j] = sp.tx[k0 + j]; sq.ty[j] = sp.ty[k0 + j]; sq.tz[j] = sp.tz[k0 + j];
+            sq.seed_prev[j] = sp.seed_prev[k0 + j]; sq.seed_next[j] = sp.seed_next[k0 + j];
+        }
+#ifdef UVRT_DEV_VARIANTS
+        if (!(c->probe_skip_generate > 0 && c->probe_batches >= c->probe_skip_generate))
+#endif
+        launch_generate_sweep_batch(sq, ls);
+        if (int rcl = lane_stream(c, &ls)) return rcl;      // extend: after the fence
+        FreeParams fp;
+        fill_launch(c, fp.e, 0.0f, 0.0f);       // (force_exact: the scene's and the variant's conditions; the origins are per ray)
+        fp.e.rays = sq.rays;
+        fp.oxz = sq.oxz;
+        fp.e.counts = S.planes.as<int32_t>() + (size_t)ph0 * plane_ints;
+        fp.e.count_replicas = R;
+        fp.e.count_stride = c->T;
+        fp.e.n = (int64_t)kc * n_pad;
+        fp.e.recs = c->free_recs.p;
+        fp.e.plane_batches = (uint32_t)(n_pad / 64);
+        fp.e.plane_n = (uint32_t)n;
+        fp.e.plane_stride = (uint32_t)plane_ints;
+        hipEvent_t e1;
+        if (int rct = timing_start(c, ls, &e1)) return rct;
+        if (!launch_extend_free_planes(fp, variant_per_cu(c->variant, c->pipeline ? 7 : 8), ls))
+            return fail(UVRT_ERR_INVALID, "%s: the free-ray launch needs a larger overflow-stack buffer than the context holds", who);
+        HIP_TRY(hipGetLastError());
+        if (e1) HIP_TRY(hipEventRecord(e1, ls));
     }
 #ifdef UVRT_DEV_VARIANTS
     ++c->probe_batches;
@@ -211,7 +302,30 @@ int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_
     c->b_n = n;
     c->b_npad = n_pad;
     c->b_is_folded = false;
+    memcpy(c->b_phys, phys, sizeof(int32_t) * (size_t)count);
     return UVRT_OK;
+}
+
+}  // namespace uvrt_impl
+
+extern "C" {
+
+int uvrt_trace_batch(uvrt_ctx* c, const float* lamps, float light_length, int32_t count, int64_t first_gid, int64_t n)
+{
+    uvrt_launch launches[MAX_BATCH];
+    memset(launches, 0, sizeof launches);
+    if (lamps && count > 0 && count <= MAX_BATCH)
+        for (int k = 0; k < count; ++k) {
+            memcpy(launches[k].from, &lamps[3 * k], 12);
+            launches[k].kind = UVRT_LAUNCH_STOP;
+        }
+    return trace_launches(c, lamps ? launches : nullptr, light_length, count, first_gid, n, "uvrt_trace_batch");
+}
+
+int uvrt_trace_batch_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_length, int32_t count, int64_t first_gid,
+                              int64_t n)
+{
+    return trace_launches(c, launches, light_length, count, first_gid, n, "uvrt_trace_batch_launches");
 }
 
 int uvrt_fold_batch(uvrt_ctx* c)

@@ -1,7 +1,7 @@
 // uvrt_ctx.h -- the context behind the C ABI of include/uvrt.h, shared by the translation units that implement it:
 //   uvrt_capi.hip         context, scene, buffers, knobs, read-backs and test hooks
 //   uvrt_capi_launch.hip  the per-launch entry points (generate, extend, accumulate, shade) and the launch lanes
-//   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / fold / replay)
+//   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / uvrt_trace_batch_launches / fold / replay)
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
@@ -167,7 +167,8 @@ struct uvrt_ctx {
     // "plane" (replicas x T ints) per launch, one per-launch record array per distinct lamp.
     // two buffer sets: batch k + 1 is traced (on the launch lanes) into one while batch k is folded, reduced and
     // replayed (on the context's stream) out of the other
-    struct BatchSet { DevBuf rays, planes, folded; hipEvent_t free_ev = nullptr; };
+    // (oxz: the {orig.x, orig.z} of the batch's sweeps, [sweep][n_pad]; allocated by the first batch that holds one)
+    struct BatchSet { DevBuf rays, planes, folded, oxz; hipEvent_t free_ev = nullptr; };
     BatchSet bs[2];
     int b_set = 0;                        // the set of the traced batch (b_count > 0) / of the last one
     uint64_t b_chunks = 0;                // chunks traced so far: consecutive chunks alternate over the launch lanes

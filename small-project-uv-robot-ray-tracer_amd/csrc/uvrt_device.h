@@ -319,7 +319,7 @@ void launch_export_rays(const float4* rays, const uint2* hits, void* out32, floa
 // records, recs = the scene's free records, ox / oz unused) plus the rays' {orig.x, orig.z}.
 struct FreeParams {
     ExtendParams e;
-    const float2* oxz;       // [n] in gid order
+    const float2* oxz;       // [n] in gid order; batched (launch_extend_free_planes): [plane][n_pad], indexed like e.rays
 };
 // a lamp that moves from `from` to `to` (include/uvrt.h uvrt_generate_sweep)
 struct SweepParams {
@@ -337,6 +337,23 @@ void launch_prepare_free_records(const PairRec* pairs, const LeafTri* ltris, voi
 constexpr int FREE_GRID_PER_CU = 8;
 bool launch_extend_free(const FreeParams& p, int grid_per_cu, hipStream_t s);
 void launch_generate_sweep(const SweepParams& p, hipStream_t s);
+// batched tracing (include/uvrt.h uvrt_trace_batch_launches): the rays of up to MAX_BATCH sweeps side by side, as
+// GenBatchParams holds those of stops
+struct SweepBatchParams {
+    float4* rays;                      // [count][n_pad]
+    float2* oxz;                       // [count][n_pad]
+    int64_t n_pad;
+    int64_t first_gid, n;              // global ids [first_gid, first_gid + n) of EVERY sweep
+    float light_length;
+    int32_t count;
+    float fx[MAX_BATCH], fy[MAX_BATCH], fz[MAX_BATCH];       // `from` of physical plane p
+    float tx[MAX_BATCH], ty[MAX_BATCH], tz[MAX_BATCH];       // `to`
+    uint32_t seed_prev[MAX_BATCH], seed_next[MAX_BATCH];     // its place in the SEED chain
+};
+void launch_generate_sweep_batch(const SweepBatchParams& p, hipStream_t s);
+// the free-origin traversal over the planes of a batch: e.plane_batches / plane_n / plane_stride as launch_extend6 takes
+// them, every plane's deposits in its own count plane.  No hit records (a batch never records hits).
+bool launch_extend_free_planes(const FreeParams& p, int grid_per_cu, hipStream_t s);
 void launch_export_free_rays(const float4* rays, const float2* oxz, const uint2* hits, void* out32, int64_t first,
                              int64_t count, hipStream_t s);
 

@@ -13,6 +13,8 @@
 //  * the first levels of the tree (uvrt_set_scene's breadth-first prefix, <= 175 records) are served from LDS;
 //  * the box test, the triangle test and the deposit are uvrt_traverse.h's: slabs6 / box2_fast / box_fast / box_exact / tri6 /
 //    retire_ray.
+// Batched tracing (include/uvrt.h uvrt_trace_batch_launches) runs the instantiations with PLANES: the launch holds the planes of
+// several sweeps side by side, as k_extend6 holds those of several stops, and k_generate_sweep_batch makes their rays.
 // The trips are hipcc's code for the lane-mask form of the step (k_extend6's step7), not a hand-written stream: the general
 // step (IEEE divisions, stacks beyond LDS) is k_extend6's step6 with the numerators formed per ray.
 //
@@ -55,8 +57,10 @@ __device__ __forceinline__ bool origin_outside_window(float o)
     return uo != 0u && uo - lo > hi - lo;
 }
 
-// refill_lane (uvrt_traverse.h) for a launch of free rays: one plane, gid order, the origin's x / z from their own array
-template <bool RECORD>
+// refill_lane (uvrt_traverse.h) for a launch of free rays: gid order, the origin's x / z from their own array.
+// PLANES: the launch holds the planes of a batch -- the plane of the lane's 64-slot batch and its padding as refill_lane
+// finds them, the plane's offset beside the exact-step bit in plane_off.
+template <bool RECORD, bool PLANES>
 __device__ __forceinline__ void refill_free(LaneF& L, const FreeParams& fp, int32_t* my_counts, uint32_t& plane_off,
                                             uint32_t& slot, bool& live, unsigned long long idle_mask, uint32_t cursor,
                                             uint32_t wave, uint32_t W, uint32_t root)
@@ -67,8 +71,18 @@ __device__ __forceinline__ void refill_free(LaneF& L, const FreeParams& fp, int3
     L.po.y = 1e30f;
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
     const uint32_t v = cursor + rank;
-    const uint32_t my = ((v >> 6) * W + wave) * 64u + (v & 63u);
-    if (v < p.chunk && my < (uint32_t)p.n) {
+    const uint32_t gb = (v >> 6) * W + wave;                 // global 64-slot batch
+    const uint32_t my = gb * 64u + (v & 63u);
+    uint32_t pl = 0;
+    bool in_plane = true;
+    if (PLANES) {           // gb / plane_batches: exact after one correction step (refill_lane)
+        pl = (uint32_t)((float)gb * p.plane_inv);
+        int32_t within = (int32_t)(gb - pl * p.plane_batches);
+        if (within < 0) { --pl; within += (int32_t)p.plane_batches; }
+        else if ((uint32_t)within >= p.plane_batches) { ++pl; within -= (int32_t)p.plane_batches; }
+        in_plane = (uint32_t)within * 64u + (v & 63u) < p.plane_n;
+    }
+    if (v < p.chunk && my < (uint32_t)p.n && in_plane) {
         const float4 rec = p.rays[my];
         const float2 o = fp.oxz[my];
         set_in_place(L.px, rec.x, rcp_exact(rec.x));       // y = RN32(1/d); lanes outside its range are `spec` and never use it
@@ -82,7 +96,7 @@ __device__ __forceinline__ void refill_free(LaneF& L, const FreeParams& fp, int3
         set_in_place(L.cur, root);
         const bool spec = outside_proof_conditions(rec) || origin_outside_window(o.x) || origin_outside_window(o.y) ||
                           p.force_exact != 0;
-        set_in_place(plane_off, spec ? SPECIAL6 : 0u);
+        set_in_place(plane_off, (PLANES ? pl * p.plane_stride : 0u) | (spec ? SPECIAL6 : 0u));
     }
 }
 
@@ -284,7 +298,9 @@ __device__ __forceinline__ void step_free(LaneF& L, const ExtendParams& p, uint3
     }
 }
 
-template <bool RECORD, int FL>
+// PLANES: the launch holds the planes of a batch (uvrt_trace_batch_launches), one count plane per sweep; a batch never
+// records hits, so PLANES comes with RECORD = false
+template <bool RECORD, int FL, bool PLANES>
 __global__ __launch_bounds__(256, FREE_GRID_PER_CU) void k_extend_free(FreeParams fp)
 {
     static_assert(FL == 0 || FL == 1, "free rays: flavours 0 and 1");
@@ -309,7 +325,7 @@ __global__ __launch_bounds__(256, FREE_GRID_PER_CU) void k_extend_free(FreeParam
     uint32_t slot = 0;
     bool live = false;
     int32_t* const my_counts = p.counts + (int64_t)(blockIdx.x % (unsigned)p.count_replicas) * p.count_stride;
-    uint32_t plane_off = 0;         // bit 31: the lane's ray needs the exact step
+    uint32_t plane_off = 0;         // bit 31: the lane's ray needs the exact step; PLANES: below it, ints to the ray's plane
     const uint32_t wave = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t W = gridDim.x * 4u;
     uint32_t cursor = 0;
@@ -326,7 +342,7 @@ __global__ __launch_bounds__(256, FREE_GRID_PER_CU) void k_extend_free(FreeParam
         const int nidle = __popcll(idle_mask);
         if (nidle >= refill_at) {
             if (cursor < chunk_end) {
-                if (L.cur == REF_DONE) refill_free<RECORD>(L, fp, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, p.root_ref6);
+                if (L.cur == REF_DONE) refill_free<RECORD, PLANES>(L, fp, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, p.root_ref6);
                 cursor += (uint32_t)nidle;
                 if (cursor >= chunk_end) refill_at = 64;
             }
@@ -372,22 +388,43 @@ void launch_prepare_free_records(const PairRec* pairs, const LeafTri* ltris, voi
     launch_prepare_leaves6(ltris, recs, npairs, T, s);
 }
 
+// the persistent grid and the root reference of a free launch (0: its overflow stacks would not fit)
+static unsigned size_free_launch(ExtendParams& p, int grid_per_cu)
+{
+    p.order = nullptr;                      // gid order
+    const unsigned grid = size_persistent_grid(p, grid_per_cu < FREE_GRID_PER_CU ? grid_per_cu : FREE_GRID_PER_CU);
+    p.root_ref6 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
+                      ? p.scene.root_ref + (uint32_t)p.npairs : p.scene.root_ref;
+    return grid;
+}
+
 bool launch_extend_free(const FreeParams& p0, int grid_per_cu, hipStream_t s)
 {
     if (p0.e.n <= 0) return true;
     FreeParams fp = p0;
     ExtendParams& p = fp.e;
     p.plane_batches = 0;                    // one launch, one plane
-    p.order = nullptr;                      // gid order
-    const unsigned grid = size_persistent_grid(p, grid_per_cu < FREE_GRID_PER_CU ? grid_per_cu : FREE_GRID_PER_CU);
+    const unsigned grid = size_free_launch(p, grid_per_cu);
     if (grid == 0) return false;
-    p.root_ref6 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
-                      ? p.scene.root_ref + (uint32_t)p.npairs : p.scene.root_ref;
-#define UVRT_LFK(REC, FL) hipLaunchKernelGGL((k_extend_free<REC, FL>), dim3(grid), dim3(256), 0, s, fp)
+#define UVRT_LFK(REC, FL) hipLaunchKernelGGL((k_extend_free<REC, FL, false>), dim3(grid), dim3(256), 0, s, fp)
     if (p.flavour == 1) { if (p.hits) UVRT_LFK(true, 1); else UVRT_LFK(false, 1); }
     else if (p.flavour == 0) { if (p.hits) UVRT_LFK(true, 0); else UVRT_LFK(false, 0); }
     else return false;
 #undef UVRT_LFK
+    return true;
+}
+
+bool launch_extend_free_planes(const FreeParams& p0, int grid_per_cu, hipStream_t s)
+{
+    if (p0.e.n <= 0) return true;
+    FreeParams fp = p0;
+    ExtendParams& p = fp.e;
+    if (p.plane_batches == 0 || p.plane_stride == 0 || p.hits) return false;
+    const unsigned grid = size_free_launch(p, grid_per_cu);
+    if (grid == 0) return false;
+    if (p.flavour == 1) hipLaunchKernelGGL((k_extend_free<false, 1, true>), dim3(grid), dim3(256), 0, s, fp);
+    else if (p.flavour == 0) hipLaunchKernelGGL((k_extend_free<false, 0, true>), dim3(grid), dim3(256), 0, s, fp);
+    else return false;
     return true;
 }
 
@@ -412,6 +449,31 @@ void launch_generate_sweep(const SweepParams& p, hipStream_t s)
 {
     if (p.n <= 0) return;
     hipLaunchKernelGGL(k_generate_sweep, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p);
+}
+
+// k_generate_sweep for the sweeps of a batch: blockIdx.y is the plane, the arithmetic is the same
+__global__ __launch_bounds__(256) void k_generate_sweep_batch(SweepBatchParams p)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n) return;
+    const int k = blockIdx.y;
+    const float fx = p.fx[k], fy = p.fy[k], fz = p.fz[k];
+    float r0;
+    double x, y;
+    uint32_t seed;
+    const float4 ray = generate_ray_rng(fx, fy, fz, p.light_length, p.first_gid + i, p.seed_prev[k], p.seed_next[k], 0, r0, x, y, seed);
+    const float u = random_float(seed);
+    const float dx = p.tx[k] - fx, dy = p.ty[k] - fy, dz = p.tz[k] - fz;
+    const float ux = u * dx, uy = u * dy, uz = u * dz;
+    const int64_t at = (int64_t)k * p.n_pad + i;
+    p.rays[at] = make_float4(ray.x, ray.y, ray.z, ray.w + uy);
+    p.oxz[at] = make_float2(fx + ux, fz + uz);
+}
+
+void launch_generate_sweep_batch(const SweepBatchParams& p, hipStream_t s)
+{
+    if (p.n <= 0 || p.count <= 0) return;
+    hipLaunchKernelGGL(k_generate_sweep_batch, dim3((unsigned)((p.n + 255) / 256), (unsigned)p.count), dim3(256), 0, s, p);
 }
 
 // Test hook: the reference's 32-byte Ray records in gid order, every ray with its own origin

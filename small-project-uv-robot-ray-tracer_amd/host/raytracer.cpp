@@ -230,52 +230,62 @@ void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, i
     bool driving = false;
     for (RayTracer* rt : group) driving = driving || rt->driveSpeed > 0.0f;
     if (driving) {
-        // The segments are not part of uvrt_trace_batch: per iteration the stops are batched without their Shade, the
-        // segments go through the per-launch path, then the Shade the last stop would have carried.  One instance only.
-        if (group.size() > 1) fatal("driveSpeed > 0 is not supported with a group of instances (ray-range sharding)");
-        if (r0->reduceOverComm) fatal("driveSpeed > 0 is not supported with reduceOverComm");
+        // stops and segments go through uvrt_trace_batch_launches side by side; what stays per launch stays refused
+        for (RayTracer* rt : group)
+            if (!(rt->driveSpeed > 0.0f)) fatal("ComputeIterationsBatched: every instance of a group must drive (driveSpeed > 0) or none");
         if (r0->shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
         if (r0->planCapture) fatal("driveSpeed > 0 is not supported with duration planning");
-        if (r0->rangeCount >= 0) fatal("driveSpeed > 0 is not supported with a ray range");
-        for (int it = 0; it < iterations; ++it) {
-            TraceBatched(group, 1, false);
-            r0->ComputeSegments();
-            r0->Shade();
-            ++r0->currIterations;
-            r0->progress = 100.0f * (float)r0->currIterations / (float)r0->maxIterations;
-        }
-        return;
     }
-    TraceBatched(group, iterations, true);
+    TraceBatched(group, iterations, driving);
 }
 
-// `iterations` x L stops in batches of up to 64 launches; withShade: the last stop of an iteration carries its Shade
-void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool withShade)
+// `iterations` x (L stops [+ L - 1 segments when driving]) in batches of up to 64 launches; the last launch of an iteration
+// carries its Shade
+void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool driving)
 {
     RayTracer* r0 = group[0];
     const int L = (int)r0->lightPositions.size();
-    const long long total = (long long)iterations * L;
+    const int P = driving && L >= 2 ? 2 * L - 1 : L;      // launches per iteration (ComputeDosageMap: the stops, then ComputeSegments)
+    const long long total = (long long)iterations * P;
     const int kMax = 64;                                  // launches per uvrt_trace_batch
     std::vector<float> lamps((size_t)kMax * 3);
+    std::vector<uvrt_launch> launches((size_t)kMax);
     std::vector<uvrt_replay_op> ops((size_t)kMax);
     std::vector<uvrt_ctx*> ctxs;
     for (RayTracer* rt : group) ctxs.push_back(rt->ctx);
     long long done = 0;
     while (done < total) {
         int cnt = (int)std::min<long long>(kMax, total - done);
-        if (cnt < total - done && cnt >= L) cnt -= (int)((done + cnt) % L);    // end on an iteration where one fits
+        if (cnt < total - done && cnt >= P) cnt -= (int)((done + cnt) % P);    // end on an iteration where one fits
         for (RayTracer* rt : group) {
+            const float y = rt->mesh->floorHeight + rt->lightHeight;             // raytracer.cpp:77
             for (int j = 0; j < cnt; ++j) {
-                const int li = (int)((done + j) % L);
-                const LightPos& lp = rt->lightPositions[li];
-                lamps[3 * j + 0] = lp.position.x;                                // raytracer.cpp:77
-                lamps[3 * j + 1] = rt->mesh->floorHeight + rt->lightHeight;
-                lamps[3 * j + 2] = lp.position.y;
+                const int pos = (int)((done + j) % P);
                 uvrt_replay_op& op = ops[j];
-                op.duration = lp.duration;                                       // :84
-                rt->photonMapSize += rt->photonsPerLight;                         // :87
-                ++rt->launchIndex;
-                op.shade = withShade && li == L - 1;                             // myapp.cpp:160
+                uvrt_launch& ln = launches[j];
+                memset(&ln, 0, sizeof ln);
+                if (pos < L) {
+                    const LightPos& lp = rt->lightPositions[pos];
+                    lamps[3 * j + 0] = lp.position.x;
+                    lamps[3 * j + 1] = y;
+                    lamps[3 * j + 2] = lp.position.y;
+                    memcpy(ln.from, &lamps[3 * j], 12);
+                    ln.kind = UVRT_LAUNCH_STOP;
+                    op.duration = lp.duration;                                   // :84
+                    rt->photonMapSize += rt->photonsPerLight;                     // :87
+                    ++rt->launchIndex;
+                } else {                                                         // ComputeSegmentDosageMap
+                    const LightPos& a = rt->lightPositions[pos - L];
+                    const LightPos& b = rt->lightPositions[pos - L + 1];
+                    ln.from[0] = a.position.x; ln.from[1] = y; ln.from[2] = a.position.y;
+                    ln.to[0] = b.position.x; ln.to[1] = y; ln.to[2] = b.position.y;
+                    ln.kind = UVRT_LAUNCH_SWEEP;
+                    const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
+                    const float len = sqrtf(dx * dx + dz * dz);
+                    op.duration = len / rt->driveSpeed;
+                    // (no photonMapSize += photonsPerLight: Shade divides by the photons per SOURCE, raytracer.h driveSpeed)
+                }
+                op.shade = pos == P - 1;                                         // myapp.cpp:160
                 if (rt->viewMode == maxpower) {                                  // raytracer.cpp:96-104
                     op.which_map = UVRT_MAP_MAX;
                     op.photons_per_light = rt->photonsPerLight;
@@ -294,15 +304,16 @@ void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iteration
                 }
             }
             const long long n = rt->rangeCount < 0 ? rt->photonsPerLight : rt->rangeCount;
-            if (n > 0)
-                check(uvrt_trace_batch(rt->ctx, lamps.data(), rt->lightLength, cnt, rt->rangeFirst, n), "trace_batch");
+            if (n <= 0) fatal("ComputeIterationsBatched: an empty ray range (more ranks than photons)");
+            if (P != L)
+                check(uvrt_trace_batch_launches(rt->ctx, launches.data(), rt->lightLength, cnt, rt->rangeFirst, n), "trace_batch_launches");
             else
-                fatal("ComputeIterationsBatched: an empty ray range (more ranks than photons)");
+                check(uvrt_trace_batch(rt->ctx, lamps.data(), rt->lightLength, cnt, rt->rangeFirst, n), "trace_batch");
         }
         if (group.size() > 1) check(uvrt_reduce_batch_group(ctxs.data(), (int)ctxs.size()), "reduce_batch_group");
         for (RayTracer* rt : group) {
             if (group.size() == 1 && rt->reduceOverComm) check(uvrt_reduce_batch(rt->ctx), "reduce_batch");
-            if (rt->planCapture) {                       // launch j of the batch is position (done + j) % L
+            if (rt->planCapture) {                       // launch j of the batch is position (done + j) % L (planning never drives)
                 std::vector<int32_t> pos((size_t)cnt);
                 for (int j = 0; j < cnt; ++j) pos[j] = (int32_t)((done + j) % L);
                 check(uvrt_plan_capture_batch(rt->ctx, pos.data(), cnt), "plan_capture_batch");

@@ -121,12 +121,15 @@ public:
     // photonMapSize: Shade's divisor photonMapSize / lightPositions.size() stays the photons per source.  The maximum
     // map takes a segment's counts like any launch: there it means the mean irradiance over the segment.  0 (default)
     // is the reference's behaviour, bit for bit.  Saved as <rijsnelheid> in route files when > 0.
+    // ComputeIterationsBatched traces an iteration's L stops and L - 1 segments as 2L - 1 logical launches of
+    // uvrt_trace_batch_launches (the Shade rides on the last), so a group of instances, a ray range and reduceOverComm
+    // work with driving as they do without; launch sharding (shardWorld > 1) and planning refuse it.
     float driveSpeed = 0;
     // one segment: a and b are two positions (their durations are not used); len = sqrtf(dx*dx + dz*dz) in f32
     void ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount);
     void ComputeSegments();                         // the segments of one iteration, in order (nothing at driveSpeed 0)
 private:
-    static void TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool withShade);
+    static void TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool driving);
 public:
     // The reference never reads the dose back; the headless build does.
     void ReadDosage(float* out, int first, int count);
