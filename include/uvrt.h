@@ -239,7 +239,9 @@ int uvrt_reduce_batch_group(uvrt_ctx** ctxs, int32_t n);
  * returns are feasible in f64 after their rounding to f32 (and print back to themselves as "%.8g"), and a dual vector
  * y >= 0 certifies LB = sum_t y_t / max_p (A^T y)_p <= OPT.  Calling sequence: uvrt_plan_begin -> per batch uvrt_trace_batch
  * (-> uvrt_reduce_batch*) -> uvrt_plan_capture_batch -> uvrt_replay_batch -> ... -> uvrt_plan_solve.
- * uvrt_set_scene drops the planning state. */
+ * uvrt_set_scene drops the planning state.  A "position" is any launch whose count plane is a column of E: the sweeps of
+ * uvrt_trace_batch_launches are captured like stops, and uvrt_plan_solve_bounded (below) plans with columns whose
+ * duration is given in advance -- a route that radiates while it drives. */
 enum { UVRT_PLAN_CONVERGED = 0, UVRT_PLAN_ITERATION_CAP = 1 };
 typedef struct {
     float min_dose;                 /* m, mJ/cm^2 (the route's minimale_dosis); <= 0: every duration 0 */
@@ -275,10 +277,45 @@ int uvrt_plan_capture_batch(uvrt_ctx* ctx, const int32_t* position_of_launch, in
 int uvrt_plan_solve(uvrt_ctx* ctx, const uvrt_plan_params* params, float* durations_out, uvrt_plan_report* report);
 /* D_t(d) as f32 for any durations float[P], with s and N of the last uvrt_plan_solve; synchronises */
 int uvrt_plan_model_dose(uvrt_ctx* ctx, const float* durations, float* out, int32_t first, int32_t count);
-/* test hooks: row `position` of E; the required set of the last solve (1 = required); both synchronise */
+/* test hooks: row `position` of E; the required set of the last solve (1 = required; after a bounded solve: active or
+ * met by the bounds); both synchronise */
 int uvrt_plan_read_exposure(uvrt_ctx* ctx, int32_t position, uint32_t* out, int32_t first, int32_t count);
 int uvrt_plan_read_required(uvrt_ctx* ctx, uint8_t* out, int32_t first, int32_t count);
 int uvrt_plan_end(uvrt_ctx* ctx);
+/* ---- bounded solve: columns with a value given in advance (a route that radiates while it drives) ----
+ * d_p >= lower[p] on every column, and a FIXED column is no variable at all: d_p = lower[p].  With x = lower + e the
+ * solver minimises sum e over the free columns subject to sum_{free p} E[p][t] r_t e_p >= rho_t = 1 - base_t on the
+ * ACTIVE rows, r_t = s / (den_t m'), base_t = (sum_p E[p][t] lower[p]) r_t (f64, ascending p); divided by rho_t that is
+ * the homogeneous covering LP of uvrt_plan_solve with the row scale r_t / rho_t (rho_t clamped from below to 1e-9:
+ * clamping upward only tightens the LP).  Every triangle gets one class, tested in this order:
+ *   3 masked out; 1 unreachable (no photon of any column, or no area); 2 unresolved (fewer than min_photons);
+ *   4 met by the bounds (base_t >= 1); 5 short (below m' at `lower` and no free column reaches it: left out, reported);
+ *   0 active.  `required` of the report = classes 0 and 4 (what uvrt_plan_read_required marks); short rows are not.
+ * With min_dose <= 0 every class 0 / 4 / 5 row is class 4 and durations_out = lower.
+ * Result: a fixed column returns lower[p] bit for bit, so does a free column whose e_p is 0; otherwise the smallest
+ * uvrt_plan_round_trip_up value >= lower[p] + e_p.  The final check is in x-space, in f64, over the required rows:
+ * (sum_p E[p][t] out_p) r_t >= 1, and min_dose_ratio comes from it.  Report: positions = P, used_positions = columns
+ * with out > 0, total_duration = sum out, lower_bound = lower_total + the residual LP's certified bound,
+ * gap = (total - lower_bound) / (total - lower_total) (0 when that denominator is 0).
+ * bounds == NULL, or all-zero `lower` without a fixed column, is uvrt_plan_solve bit for bit (classes 0-3).
+ * UVRT_ERR_INVALID, nothing changed: a negative, NaN or infinite lower[p], and whatever uvrt_plan_solve refuses. */
+typedef struct {
+    const float*   lower;   /* float[P]: d_p >= lower[p]; finite, >= 0.  NULL: all 0 */
+    const uint8_t* fixed;   /* uint8[P]: != 0 -> d_p = lower[p] exactly, not a variable.  NULL: none */
+    int32_t reserved[2];    /* 0 */
+} uvrt_plan_bounds;
+typedef struct {
+    int32_t fixed_columns, free_columns;
+    int32_t met_by_lower;   /* rows that D_t(lower) already brings to m' */
+    int32_t short_rows;     /* rows below m' at `lower` that no free column reaches: left out, reported */
+    double  area_met_by_lower, area_short;
+    double  lower_total;    /* sum of lower (f64 over the f32 values) */
+    int32_t reserved[2];
+} uvrt_plan_bounds_report;
+int uvrt_plan_solve_bounded(uvrt_ctx* ctx, const uvrt_plan_params* params, const uvrt_plan_bounds* bounds,
+                            float* durations_out, uvrt_plan_report* report, uvrt_plan_bounds_report* bounds_report /* may be NULL */);
+/* test hook: the class of every triangle in the last solve (0-3 after uvrt_plan_solve); synchronises */
+int uvrt_plan_read_classes(uvrt_ctx* ctx, uint8_t* out, int32_t first, int32_t count);
 /* the smallest float >= v that "%.8g" (SaveRoute) prints back to itself through strtof (LoadRoute): how the solver rounds
  * the durations it returns.  Host only, no GPU needed. */
 float uvrt_plan_round_trip_up(float v);

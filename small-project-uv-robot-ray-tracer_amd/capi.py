@@ -92,6 +92,8 @@ SYMBOLS = [
     ("uvrt_plan_read_exposure", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_plan_read_required", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_plan_end", C.c_int, [_vp]),
+    ("uvrt_plan_solve_bounded", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("uvrt_plan_read_classes", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_plan_round_trip_up", _f32, [_f32]),
 ]
 
@@ -117,6 +119,25 @@ class PlanReport(C.Structure):
         d = {name: getattr(self, name) for name, _ in self._fields_}
         d["converged"] = d["status"] == PLAN_CONVERGED
         return d
+
+
+class PlanBounds(C.Structure):
+    """uvrt_plan_bounds (include/uvrt.h)"""
+    _fields_ = [("lower", C.c_void_p), ("fixed", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+class PlanBoundsReport(C.Structure):
+    """uvrt_plan_bounds_report (include/uvrt.h)"""
+    _fields_ = [("fixed_columns", C.c_int32), ("free_columns", C.c_int32), ("met_by_lower", C.c_int32),
+                ("short_rows", C.c_int32), ("area_met_by_lower", C.c_double), ("area_short", C.c_double),
+                ("lower_total", C.c_double), ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+# classes of uvrt_plan_read_classes
+PLAN_ACTIVE, PLAN_UNREACHABLE, PLAN_UNRESOLVED, PLAN_MASKED_OUT, PLAN_MET_BY_LOWER, PLAN_SHORT = range(6)
 
 
 def round_trip_up(v):
@@ -459,6 +480,18 @@ class Ctx:
     def plan_solve(self, min_dose, scaled_power, photons_per_position, min_photons=16, margin=1e-6, rel_gap=1e-3,
                    max_iterations=200, mask=None, positions=None):
         """(durations float32[P], report dict); `positions` = P of uvrt_plan_begin (the output size)"""
+        return self._plan_solve(False, None, None, min_dose, scaled_power, photons_per_position, min_photons, margin,
+                                rel_gap, max_iterations, mask, positions)
+
+    def plan_solve_bounded(self, min_dose, scaled_power, photons_per_position, min_photons=16, margin=1e-6, rel_gap=1e-3,
+                           max_iterations=200, mask=None, positions=None, lower=None, fixed=None):
+        """uvrt_plan_solve_bounded: durations >= lower (float32[P]), the columns with fixed[p] != 0 exactly lower[p];
+        (durations float32[P], report dict, bounds report dict).  lower = fixed = None passes no bounds at all."""
+        return self._plan_solve(True, lower, fixed, min_dose, scaled_power, photons_per_position, min_photons, margin,
+                                rel_gap, max_iterations, mask, positions)
+
+    def _plan_solve(self, bounded, lower, fixed, min_dose, scaled_power, photons_per_position, min_photons, margin, rel_gap,
+                    max_iterations, mask, positions):
         prm = PlanParams()
         prm.min_dose = float(np.float32(min_dose))
         prm.scaled_power = float(np.float32(scaled_power))
@@ -478,8 +511,21 @@ class Ctx:
                 raise ValueError("plan_solve: give `positions` (P of uvrt_plan_begin) for a context this object did not begin")
         out = np.zeros(int(positions), dtype=np.float32)
         rep = PlanReport()
-        self._ck(self._L.uvrt_plan_solve(self._h, C.byref(prm), _ptr(out), C.byref(rep)))
-        return out, rep.as_dict()
+        if not bounded:
+            self._ck(self._L.uvrt_plan_solve(self._h, C.byref(prm), _ptr(out), C.byref(rep)))
+            return out, rep.as_dict()
+        bnd, brep, low, fix = PlanBounds(), PlanBoundsReport(), None, None
+        if lower is not None:
+            low = np.ascontiguousarray(lower, dtype=np.float32)
+            assert low.size == int(positions)
+            bnd.lower = low.ctypes.data
+        if fixed is not None:
+            fix = np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.uint8)
+            assert fix.size == int(positions)
+            bnd.fixed = fix.ctypes.data
+        self._ck(self._L.uvrt_plan_solve_bounded(self._h, C.byref(prm), None if low is None and fix is None else C.byref(bnd),
+                                                 _ptr(out), C.byref(rep), C.byref(brep)))
+        return out, rep.as_dict(), brep.as_dict()
 
     def plan_model_dose(self, durations, first=0, count=None):
         d = np.ascontiguousarray(durations, dtype=np.float32)
@@ -499,6 +545,13 @@ class Ctx:
         out = np.empty(count, dtype=np.uint8)
         self._ck(self._L.uvrt_plan_read_required(self._h, _ptr(out), int(first), int(count)))
         return out.astype(bool)
+
+    def plan_read_classes(self, first=0, count=None):
+        """the class of every triangle in the last solve (PLAN_ACTIVE ... PLAN_SHORT), uint8"""
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.uint8)
+        self._ck(self._L.uvrt_plan_read_classes(self._h, _ptr(out), int(first), int(count)))
+        return out
 
     def plan_end(self):
         self._ck(self._L.uvrt_plan_end(self._h))

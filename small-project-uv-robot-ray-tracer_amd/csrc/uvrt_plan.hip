@@ -10,6 +10,11 @@
 // certified gap is <= rel_gap or a cap is reached.  The restricted dual y (zero on the other rows) is feasible for the
 // full dual once divided by max_p (A^T y)_p, so LB = sum y / max_p (A^T y)_p is a certified lower bound at every round.
 // Every result is bit-reproducible: no float atomics, fixed reduction orders, no dependence on the CU count.
+//
+// Bounded solve (uvrt_plan_solve_bounded): d_p >= lower[p], fixed columns d_p = lower[p].  With x = lower + e and
+// base_t = (sum_p E[p][t] lower[p]) r_t the residual problem  min 1.e  s.t.  sum_{free p} E[p][t] r_t e_p >= rho_t = 1 - base_t
+// on the ACTIVE rows (base_t < 1 and a free column reaches t) is the same homogeneous LP with the row scale r_t / rho_t and
+// without the fixed columns: the <true> instantiations of the row kernels, the same host loop.
 #include "uvrt_ctx.h"
 #include "uvrt_plan_lp.h"
 
@@ -21,6 +26,7 @@ using namespace uvrt_impl;
 
 namespace {
 
+constexpr double PLAN_RHO_MIN = 1e-9; // floor of a bounded solve's rho_t = 1 - base_t (what it costs)
 constexpr int PLAN_MAX_P = 256;      // positions (uvrt_plan_begin; LDS copy of the durations in the row kernels): the
                                      // restricted simplex is measured to solve within a second up to here
 
@@ -46,34 +52,71 @@ __global__ __launch_bounds__(256) void k_plan_capture(CaptureParams p)
     }
 }
 
-// class of every triangle (0 required, 1 unreachable, 2 unresolved, 3 masked out), per block: counts and areas per class
+// what a bounded solve adds to the row kernels: the lower bounds (as f64), the fixed columns and the row scale's terms
+struct BoundsDev {
+    const double* lower;     // f64[P]
+    const uint8_t* fixed;    // uint8[P]
+    float s, Nf;
+    double mprime;
+    int32_t all_met;         // min_dose <= 0: every row that would be class 0, 4 or 5 is class 4
+};
+
+// class of every triangle (0 required, 1 unreachable, 2 unresolved, 3 masked out), per block: counts and areas per class.
+// B (bounded solve): a row of class 0 splits into 4 (met by the bounds: base_t >= 1), 5 (short: no free column reaches it)
+// and 0 (active), whose rho_t = max(1 - base_t, PLAN_RHO_MIN) goes to rho[t]; base_t in f64, columns in ascending order.
+template <bool B>
 __global__ __launch_bounds__(256) void k_plan_classify(const uint32_t* __restrict__ E, int32_t P, int32_t T,
                                                       const uint8_t* __restrict__ mask, const float* __restrict__ area,
                                                       uint32_t min_photons, uint8_t* __restrict__ cls,
-                                                      int32_t* __restrict__ blk_cnt, double* __restrict__ blk_area)
+                                                      int32_t* __restrict__ blk_cnt, double* __restrict__ blk_area,
+                                                      BoundsDev bd, double* __restrict__ rho)
 {
-    __shared__ int32_t s_cnt[4][4];
+    constexpr int NC = B ? 6 : 4;
+    __shared__ int32_t s_cnt[4][NC];
     __shared__ double s_area[256];
+    __shared__ double s_low[B ? PLAN_MAX_P : 1];
+    __shared__ uint8_t s_fix[B ? PLAN_MAX_P : 1];
+    if (B) {
+        for (int j = threadIdx.x; j < P; j += 256) { s_low[j] = bd.lower[j]; s_fix[j] = bd.fixed[j]; }
+        __syncthreads();
+    }
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int k = -1;
     double a = 0;
     if (t < T) {
-        uint64_t sum = 0;
-        for (int p = 0; p < P; ++p) sum += E[(int64_t)p * T + t];
+        uint64_t sum = 0, fre = 0;
+        double base = 0.0;
+        for (int p = 0; p < P; ++p) {
+            const uint32_t e = E[(int64_t)p * T + t];
+            sum += e;
+            if (B) {
+                if (!s_fix[p]) fre += e;
+                base += (double)e * s_low[p];
+            }
+        }
         const float at = area[t];
         a = at;
         if (mask && !mask[t]) k = 3;
         else if (sum == 0 || !(at > 0.0f)) k = 1;      // no photon (or no area: no dose is defined)
         else if (sum < min_photons) k = 2;
-        else k = 0;
+        else if (!B) k = 0;
+        else if (bd.all_met) k = 4;
+        else {
+            const float den = at * bd.Nf;                             // computeDosage's f32 denominator
+            const double r = (double)bd.s / ((double)den * bd.mprime);
+            const double b = base * r;
+            if (b >= 1.0) k = 4;
+            else if (fre == 0) k = 5;
+            else { k = 0; rho[t] = fmax(1.0 - b, PLAN_RHO_MIN); }
+        }
         cls[t] = (uint8_t)k;
     }
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NC; ++q) {
         const uint64_t b = __builtin_amdgcn_ballot_w64(k == q);
         if (lane == 0) s_cnt[w][q] = __popcll(b);
     }
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < NC; ++q) {
         s_area[threadIdx.x] = k == q ? a : 0.0;
         __syncthreads();
         for (int o = 128; o > 0; o >>= 1) {
@@ -81,18 +124,20 @@ __global__ __launch_bounds__(256) void k_plan_classify(const uint32_t* __restric
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            blk_area[blockIdx.x * 4 + q] = s_area[0];
-            blk_cnt[blockIdx.x * 4 + q] = s_cnt[0][q] + s_cnt[1][q] + s_cnt[2][q] + s_cnt[3][q];
+            blk_area[blockIdx.x * NC + q] = s_area[0];
+            blk_cnt[blockIdx.x * NC + q] = s_cnt[0][q] + s_cnt[1][q] + s_cnt[2][q] + s_cnt[3][q];
         }
         __syncthreads();
     }
 }
 
-// the required rows in ascending triangle order (ballot + block offsets) and their scale r
+// the required (B: the active) rows in ascending triangle order (ballot + block offsets) and their scale r (B: r / rho)
+template <bool B>
 __global__ __launch_bounds__(256) void k_plan_compact(const uint32_t* __restrict__ E, int32_t P, int32_t T,
                                                      const uint8_t* __restrict__ cls, const float* __restrict__ area,
                                                      const int32_t* __restrict__ blk_off, float s, float Nf, double mprime,
-                                                     int32_t* __restrict__ rows, double* __restrict__ rd)
+                                                     int32_t* __restrict__ rows, double* __restrict__ rd,
+                                                     const double* __restrict__ rho)
 {
     __shared__ int32_t s_w[4];
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -108,32 +153,40 @@ __global__ __launch_bounds__(256) void k_plan_compact(const uint32_t* __restrict
     const float den = area[t] * Nf;                               // computeDosage's f32 denominator
     const double r = (double)s / ((double)den * mprime);
     rows[off] = t;
-    rd[off] = r;
+    rd[off] = B ? r / rho[t] : r;
 }
 
-// row j of the gathered block: A[sel_j][p] = E[p][rows[sel_j]] * r_{sel_j} in f64
+// row j of the gathered block: A[sel_j][p] = E[p][rows[sel_j]] * r_{sel_j} in f64; B: P counts the free columns only
+// and cols[p] is the p-th of them (the fixed columns never reach the simplex)
+template <bool B>
 __global__ __launch_bounds__(256) void k_plan_gather(const uint32_t* __restrict__ E, int32_t T, int32_t P,
                                                     const int32_t* __restrict__ rows, const double* __restrict__ rd,
-                                                    const int64_t* __restrict__ sel, int32_t nsel, double* __restrict__ out)
+                                                    const int64_t* __restrict__ sel, int32_t nsel, double* __restrict__ out,
+                                                    const int32_t* __restrict__ cols)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= (int64_t)nsel * P) return;
-    const int64_t j = k / P, p = k % P, i = sel[j];
+    const int64_t j = k / P, p = B ? (int64_t)cols[k % P] : k % P, i = sel[j];
     out[k] = (double)E[p * T + rows[i]] * rd[i];
 }
 
 // f64 check of durations d over the required rows: per block min_i A_i d (and A_i d per row); rows with A_i d = 0 raise
 // their best position (most photons, lowest index) to what covers the row alone (integer max of positive f64 bits:
-// order independent)
+// order independent).  B: the fixed columns are left out of the sum and of the choice of the best position.
+template <bool B>
 __global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restrict__ E, int32_t T, int32_t P, int64_t NR,
                                                       const int32_t* __restrict__ rows, const double* __restrict__ rd,
                                                       const double* __restrict__ d, double* __restrict__ blk_min,
                                                       unsigned long long* __restrict__ raise, int32_t* __restrict__ zero_rows,
-                                                      double* __restrict__ ratio)
+                                                      double* __restrict__ ratio, const uint8_t* __restrict__ fixed)
 {
     __shared__ double s_d[PLAN_MAX_P];
     __shared__ double s_min[256];
-    for (int j = threadIdx.x; j < P; j += 256) s_d[j] = d[j];
+    __shared__ uint8_t s_fix[B ? PLAN_MAX_P : 1];
+    for (int j = threadIdx.x; j < P; j += 256) {
+        s_d[j] = d[j];
+        if (B) s_fix[j] = fixed[j];
+    }
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double mn = std::numeric_limits<double>::infinity();
@@ -143,6 +196,7 @@ __global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restric
         uint32_t best = 0;
         int bp = 0;
         for (int q = 0; q < P; ++q) {
+            if (B && s_fix[q]) continue;
             const uint32_t e = E[(int64_t)q * T + t];
             ad += (double)e * s_d[q];
             if (e > best) { best = e; bp = q; }
@@ -155,6 +209,34 @@ __global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restric
             atomicMax(&raise[bp], (unsigned long long)__double_as_longlong(need));
             atomicAdd(zero_rows, 1);
         }
+    }
+    s_min[threadIdx.x] = mn;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_min[threadIdx.x] = fmin(s_min[threadIdx.x], s_min[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) blk_min[blockIdx.x] = s_min[0];
+}
+
+// the bounded solve's final check, in x-space: per block the minimum over the required rows (classes 0 and 4) of
+// (sum_p E[p][t] x_p) * r_t, every column in ascending order, in f64
+__global__ __launch_bounds__(256) void k_plan_xcheck(const uint32_t* __restrict__ E, int32_t T, int32_t P,
+                                                    const uint8_t* __restrict__ cls, const float* __restrict__ area,
+                                                    float s, float Nf, double mprime, const double* __restrict__ x,
+                                                    double* __restrict__ blk_min)
+{
+    __shared__ double s_x[PLAN_MAX_P];
+    __shared__ double s_min[256];
+    for (int j = threadIdx.x; j < P; j += 256) s_x[j] = x[j];
+    __syncthreads();
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    double mn = std::numeric_limits<double>::infinity();
+    if (t < T && (cls[t] == 0 || cls[t] == 4)) {
+        double acc = 0.0;
+        for (int q = 0; q < P; ++q) acc += (double)E[(int64_t)q * T + t] * s_x[q];
+        const float den = area[t] * Nf;
+        mn = acc * ((double)s / ((double)den * mprime));
     }
     s_min[threadIdx.x] = mn;
     __syncthreads();
@@ -196,10 +278,11 @@ struct PlanState {
     float s = 0, Nf = 0;                 // of the last solve (uvrt_plan_model_dose)
     DevBuf overflow;                     // uint32 flag of k_plan_capture
     DevBuf cls, mask, blk_cnt, blk_area, blk_off, rows, rd, dd, blk_min, raise, zrows, outf, ratio, sel, gath;
+    DevBuf lowd, fixd, rho, cols, xmin;  // bounded solve: lower as f64[P], fixed uint8[P], rho f64[T], the free columns, k_plan_xcheck
     void release()
     {
         for (DevBuf* b : {&E, &overflow, &cls, &mask, &blk_cnt, &blk_area, &blk_off, &rows, &rd, &dd, &blk_min, &raise, &zrows,
-                          &outf, &ratio, &sel, &gath})
+                          &outf, &ratio, &sel, &gath, &lowd, &fixd, &rho, &cols, &xmin})
             b->release();
     }
 };
@@ -220,7 +303,8 @@ namespace {
 struct RowCheck { double min_ratio; int32_t zero_rows; };
 
 // k_plan_rowcheck of host durations d64; with `raise` the raise values come back in raise_out, with ratio_out A_i d per row
-int row_check(uvrt_ctx* c, PlanState& S, int64_t NR, const std::vector<double>& d64, bool raise,
+// (bounded: the fixed columns of S.fixd are left out)
+int row_check(uvrt_ctx* c, PlanState& S, bool bounded, int64_t NR, const std::vector<double>& d64, bool raise,
               RowCheck* out, std::vector<double>* raise_out, std::vector<double>* ratio_out = nullptr)
 {
     const unsigned nbr = nblocks(NR, 256);
@@ -229,10 +313,12 @@ int row_check(uvrt_ctx* c, PlanState& S, int64_t NR, const std::vector<double>& 
         HIP_TRY(hipMemsetAsync(S.raise.p, 0, (size_t)S.P * 8, c->stream));
         HIP_TRY(hipMemsetAsync(S.zrows.p, 0, 4, c->stream));
     }
-    hipLaunchKernelGGL(k_plan_rowcheck, dim3(nbr), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), c->T, S.P, NR,
+    hipLaunchKernelGGL(bounded ? k_plan_rowcheck<true> : k_plan_rowcheck<false>, dim3(nbr), dim3(256), 0, c->stream,
+                       (const uint32_t*)S.E.as<uint32_t>(), c->T, S.P, NR,
                        (const int32_t*)S.rows.as<int32_t>(), (const double*)S.rd.as<double>(), (const double*)S.dd.as<double>(),
                        S.blk_min.as<double>(), raise ? S.raise.as<unsigned long long>() : nullptr,
-                       S.zrows.as<int32_t>(), ratio_out ? S.ratio.as<double>() : nullptr);
+                       S.zrows.as<int32_t>(), ratio_out ? S.ratio.as<double>() : nullptr,
+                       bounded ? (const uint8_t*)S.fixd.as<uint8_t>() : nullptr);
     HIP_TRY(hipGetLastError());
     std::vector<double> mn(nbr);
     if (ratio_out) {
@@ -257,6 +343,27 @@ int row_check(uvrt_ctx* c, PlanState& S, int64_t NR, const std::vector<double>& 
     }
     return UVRT_OK;
 }
+
+// k_plan_xcheck of host durations x (every column): the minimum over the required rows of D_t(x) / m'
+int x_check(uvrt_ctx* c, PlanState& S, double mprime, const std::vector<double>& x, double* min_ratio)
+{
+    const unsigned nbt = nblocks(c->T, 256);
+    if (int rc = S.xmin.ensure((size_t)nbt * 8, false, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(S.dd.p, x.data(), (size_t)S.P * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_plan_xcheck, dim3(nbt), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), c->T, S.P,
+                       (const uint8_t*)S.cls.as<uint8_t>(), (const float*)c->area.as<float>(), S.s, S.Nf, mprime,
+                       (const double*)S.dd.as<double>(), S.xmin.as<double>());
+    HIP_TRY(hipGetLastError());
+    std::vector<double> mn(nbt);
+    HIP_TRY(hipMemcpyAsync(mn.data(), S.xmin.p, (size_t)nbt * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *min_ratio = std::numeric_limits<double>::infinity();
+    for (unsigned b = 0; b < nbt; ++b) *min_ratio = std::min(*min_ratio, mn[b]);
+    return UVRT_OK;
+}
+
+int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
+               uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 
 }  // namespace
 
@@ -334,207 +441,13 @@ int uvrt_plan_capture_batch(uvrt_ctx* c, const int32_t* pos, int32_t count)
 
 int uvrt_plan_solve(uvrt_ctx* c, const uvrt_plan_params* prm, float* out, uvrt_plan_report* rep)
 {
-    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: no plan (uvrt_plan_begin)");
-    if (c->plan->captures == 0) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: nothing captured (uvrt_plan_capture_batch)");
-    if (!prm || !out || !rep) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: null argument");
-    if (prm->photons_per_position < 1 || prm->photons_per_position > (int64_t)0xFFFFFFFFll)
-        return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: %lld photons per position overflow the uint32 counts",
-                    (long long)prm->photons_per_position);
-    if (!(prm->scaled_power > 0.0f) || !std::isfinite(prm->scaled_power) || !std::isfinite(prm->min_dose) ||
-        !(prm->margin >= 0.0) || !(prm->rel_gap > 0.0))
-        return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: scaled_power > 0, finite min_dose, margin >= 0 and rel_gap > 0 required");
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    PlanState& S = *c->plan;
-    const int32_t T = c->T, P = S.P;
-    const unsigned nbt = nblocks(T, 256);
-    {
-        uint32_t of = 0;
-        HIP_TRY(hipMemcpyAsync(&of, S.overflow.p, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (of) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: a captured count overflowed uint32 (over 2^32 - 1 photons of one position)");
-    }
-    int rc;
-    memset(rep, 0, sizeof *rep);
-    rep->positions = P;
+    return plan_solve(c, "uvrt_plan_solve", prm, nullptr, out, rep, nullptr);
+}
 
-    // ---- set-up: classes, exclusion statistics, the required rows
-    if ((rc = S.cls.ensure((size_t)T, false, c->stream))) return rc;
-    if ((rc = S.blk_cnt.ensure((size_t)nbt * 16, false, c->stream))) return rc;
-    if ((rc = S.blk_area.ensure((size_t)nbt * 32, false, c->stream))) return rc;
-    if ((rc = S.blk_off.ensure((size_t)nbt * 4, false, c->stream))) return rc;
-    const uint8_t* dmask = nullptr;
-    if (prm->mask) {
-        if ((rc = S.mask.ensure((size_t)T, false, c->stream))) return rc;
-        HIP_TRY(hipMemcpyAsync(S.mask.p, prm->mask, (size_t)T, hipMemcpyHostToDevice, c->stream));
-        dmask = S.mask.as<uint8_t>();
-    }
-    const uint32_t min_ph = (uint32_t)std::max(1, prm->min_photons);
-    hipLaunchKernelGGL(k_plan_classify, dim3(nbt), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), P, T, dmask,
-                       (const float*)c->area.as<float>(), min_ph, S.cls.as<uint8_t>(), S.blk_cnt.as<int32_t>(), S.blk_area.as<double>());
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> bc((size_t)nbt * 4), boff(nbt);
-    std::vector<double> ba((size_t)nbt * 4);
-    HIP_TRY(hipMemcpyAsync(bc.data(), S.blk_cnt.p, bc.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(ba.data(), S.blk_area.p, ba.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    int64_t cnt[4] = {0, 0, 0, 0};
-    double area[4] = {0, 0, 0, 0};
-    for (unsigned b = 0; b < nbt; ++b) {
-        boff[b] = (int32_t)cnt[0];
-        for (int q = 0; q < 4; ++q) { cnt[q] += bc[b * 4 + q]; area[q] += ba[b * 4 + q]; }
-    }
-    rep->required = (int32_t)cnt[0]; rep->unreachable = (int32_t)cnt[1];
-    rep->unresolved = (int32_t)cnt[2]; rep->masked_out = (int32_t)cnt[3];
-    rep->area_required = area[0]; rep->area_unreachable = area[1];
-    rep->area_unresolved = area[2]; rep->area_masked_out = area[3];
-    const int64_t NR = cnt[0];
-    const double m = prm->min_dose, mprime = m * (1.0 + prm->margin);
-    S.s = prm->scaled_power;
-    S.Nf = (float)prm->photons_per_position;
-    S.solved = true;
-    if (NR == 0 || !(m > 0.0)) {
-        for (int p = 0; p < P; ++p) out[p] = 0.0f;
-        rep->status = UVRT_PLAN_CONVERGED;
-        rep->min_dose_ratio = std::numeric_limits<double>::infinity();
-        return UVRT_OK;
-    }
-    const unsigned nbr = nblocks(NR, 256);
-    if ((rc = S.rows.ensure((size_t)NR * 4, false, c->stream))) return rc;
-    if ((rc = S.rd.ensure((size_t)NR * 8, false, c->stream))) return rc;
-    if ((rc = S.ratio.ensure((size_t)NR * 8, false, c->stream))) return rc;
-    for (DevBuf* b : {&S.dd, &S.raise})
-        if ((rc = b->ensure((size_t)P * 8, false, c->stream))) return rc;
-    if ((rc = S.blk_min.ensure((size_t)nbr * 8, false, c->stream))) return rc;
-    if ((rc = S.zrows.ensure(4, false, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(S.blk_off.p, boff.data(), (size_t)nbt * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_plan_compact, dim3(nbt), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), P, T,
-                       (const uint8_t*)S.cls.as<uint8_t>(), (const float*)c->area.as<float>(), (const int32_t*)S.blk_off.as<int32_t>(),
-                       S.s, S.Nf, mprime, S.rows.as<int32_t>(), S.rd.as<double>());
-    HIP_TRY(hipGetLastError());
-
-    // ---- cutting planes from the uniform plan: rows W gathered so far (AW: |W| x P, f64), exact LP over W, repeat
-    const int max_rounds = prm->max_iterations > 0 ? prm->max_iterations : 200;
-    const int per_round = std::max(64, 2 * P);
-    std::vector<double> d64(P), ratio, AW, best_d;
-    std::vector<int64_t> W;
-    std::vector<uint8_t> inW((size_t)NR, 0);
-    uvrt_plan_lp::RestrictedLP lp(P);
-    int64_t pivots = 0;
-    double best_ub = std::numeric_limits<double>::infinity(), best_lb = 0.0;
-    int it = 0;
-    {
-        std::vector<double> ones(P, 1.0);
-        RowCheck r1;
-        if ((rc = row_check(c, S, NR, ones, false, &r1, nullptr))) return rc;
-        for (int p = 0; p < P; ++p) d64[p] = r1.min_ratio > 0.0 ? 1.0 / r1.min_ratio : 1.0;
-    }
-    for (;;) {
-        RowCheck rck;
-        if ((rc = row_check(c, S, NR, d64, false, &rck, nullptr, &ratio))) return rc;
-        double sd = 0;
-        for (double v : d64) sd += v;
-        if (rck.min_ratio > 0.0 && sd / rck.min_ratio < best_ub) {
-            best_ub = sd / rck.min_ratio;
-            best_d = d64;
-            for (double& v : best_d) v /= rck.min_ratio;
-        }
-        if (std::isfinite(best_ub) && (best_ub - best_lb) <= prm->rel_gap * best_ub) break;
-        if (it >= max_rounds) break;
-        // the most violated rows not yet in W (round 0: the least covered ones under the uniform plan)
-        std::vector<int64_t> cand;
-        for (int64_t i = 0; i < NR; ++i)
-            if (!inW[i] && (it == 0 || ratio[i] < 1.0)) cand.push_back(i);
-        if (cand.empty()) break;          // d covers every row: the restricted optimum is global
-        const size_t take = std::min(cand.size(), (size_t)per_round);
-        std::partial_sort(cand.begin(), cand.begin() + take, cand.end(), [&](int64_t a, int64_t b) {
-            return ratio[a] < ratio[b] || (ratio[a] == ratio[b] && a < b);
-        });
-        cand.resize(take);
-        std::sort(cand.begin(), cand.end());
-        if ((rc = S.sel.ensure(take * 8, false, c->stream))) return rc;
-        if ((rc = S.gath.ensure(take * (size_t)P * 8, false, c->stream))) return rc;
-        HIP_TRY(hipMemcpyAsync(S.sel.p, cand.data(), take * 8, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_plan_gather, dim3(nblocks((int64_t)take * P, 256)), dim3(256), 0, c->stream,
-                           (const uint32_t*)S.E.as<uint32_t>(), T, P, (const int32_t*)S.rows.as<int32_t>(),
-                           (const double*)S.rd.as<double>(), (const int64_t*)S.sel.as<int64_t>(), (int32_t)take, S.gath.as<double>());
-        HIP_TRY(hipGetLastError());
-        const size_t old = AW.size();
-        AW.resize(old + take * (size_t)P);
-        HIP_TRY(hipMemcpyAsync(AW.data() + old, S.gath.p, take * (size_t)P * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int64_t i : cand) { inW[i] = 1; W.push_back(i); }
-        lp.add_rows(AW.data() + old, (int64_t)take);
-        const bool solved = lp.solve(50 * (lp.rows() + P) + 1000, &pivots);
-        std::vector<double> yW;
-        lp.solution(&yW, &d64);                 // an interrupted solve still leaves a feasible basis: a certificate
-        // certificate of the restricted dual (zero on the rows outside W): LB = sum y / max_p (A^T y)_p, in f64
-        std::vector<double> g(P, 0.0);
-        double sy = 0;
-        for (size_t j = 0; j < W.size(); ++j) {
-            if (yW[j] == 0.0) continue;
-            sy += yW[j];
-            for (int p = 0; p < P; ++p) g[p] += AW[j * P + p] * yW[j];
-        }
-        const double gmax = *std::max_element(g.begin(), g.end());
-        if (gmax > 0.0) best_lb = std::max(best_lb, sy / gmax);
-        ++it;
-        if (!solved) {                          // pivot cap: keep what is certified, report the gap
-            RowCheck rlast;
-            if ((rc = row_check(c, S, NR, d64, false, &rlast, nullptr))) return rc;
-            double sl = 0;
-            for (double v : d64) sl += v;
-            if (rlast.min_ratio > 0.0 && sl / rlast.min_ratio < best_ub) {
-                best_ub = sl / rlast.min_ratio;
-                best_d = d64;
-                for (double& v : best_d) v /= rlast.min_ratio;
-            }
-            break;
-        }
-    }
-
-    // ---- repair (f64): cover rows without coverage by their best position, drop positions the plan does not need, scale
-    if (std::isfinite(best_ub)) d64 = best_d;
-    std::vector<double> dh(P);
-    {
-        double dmax = 0;
-        for (double v : d64) dmax = std::max(dmax, v);
-        for (double& v : d64) if (v <= 1e-7 * dmax) v = 0.0;
-    }
-    RowCheck rck{};
-    std::vector<double> raise;
-    for (int round = 0; round < 4; ++round) {
-        if ((rc = row_check(c, S, NR, d64, true, &rck, &raise))) return rc;
-        if (rck.zero_rows == 0) break;
-        for (int p = 0; p < P; ++p) d64[p] = std::max(d64[p], raise[p]);
-    }
-    if (rck.zero_rows != 0 || !(rck.min_ratio > 0.0)) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: repair left rows uncovered");
-    for (double& v : d64) v /= rck.min_ratio;
-    // f32, rounded up to values that survive SaveRoute / LoadRoute; re-checked in f64
-    std::vector<float> d32(P);
-    for (int round = 0; round < 8; ++round) {
-        for (int p = 0; p < P; ++p) {
-            float f = (float)d64[p];
-            if ((double)f < d64[p]) f = nextafterf(f, INFINITY);
-            d32[p] = d64[p] > 0.0 ? uvrt_plan_round_trip_up(f) : 0.0f;
-            dh[p] = d32[p];
-        }
-        if ((rc = row_check(c, S, NR, dh, false, &rck, nullptr))) return rc;
-        if (rck.min_ratio >= 1.0) break;
-        for (double& v : d64) v *= (1.0 / rck.min_ratio) * (1.0 + 1e-12);
-    }
-    if (!(rck.min_ratio >= 1.0)) return fail(UVRT_ERR_INVALID, "uvrt_plan_solve: the f32 durations do not reach the minimum");
-    double total = 0;
-    int used = 0;
-    for (int p = 0; p < P; ++p) { out[p] = d32[p]; total += d32[p]; used += d32[p] > 0.0f; }
-    rep->iterations = it;
-    rep->used_positions = used;
-    rep->total_duration = total;
-    rep->lower_bound = std::min(best_lb, total);
-    rep->gap = total > 0.0 ? (total - rep->lower_bound) / total : 0.0;
-    rep->status = rep->gap <= prm->rel_gap ? UVRT_PLAN_CONVERGED : UVRT_PLAN_ITERATION_CAP;
-    rep->min_dose_ratio = rck.min_ratio * (mprime / m);
-    return UVRT_OK;
+int uvrt_plan_solve_bounded(uvrt_ctx* c, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
+                            uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
+{
+    return plan_solve(c, "uvrt_plan_solve_bounded", prm, bounds, out, rep, brep);
 }
 
 int uvrt_plan_model_dose(uvrt_ctx* c, const float* durations, float* out, int32_t first, int32_t count)
@@ -584,8 +497,334 @@ int uvrt_plan_read_required(uvrt_ctx* c, uint8_t* out, int32_t first, int32_t co
     if (int rc = set_device(c)) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->plan->cls.as<uint8_t>() + first, (size_t)count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int32_t i = 0; i < count; ++i) out[i] = out[i] == 0 ? 1 : 0;
+    for (int32_t i = 0; i < count; ++i) out[i] = out[i] == 0 || out[i] == 4 ? 1 : 0;     // a bounded solve: active or met by the bounds
+    return UVRT_OK;
+}
+
+int uvrt_plan_read_classes(uvrt_ctx* c, uint8_t* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan || !c->plan->solved) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_classes: no solved plan");
+    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_classes: bad range");
+    if (count == 0) return UVRT_OK;
+    if (int rc = set_device(c)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->plan->cls.as<uint8_t>() + first, (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return UVRT_OK;
 }
 
 }  // extern "C"
+
+namespace {
+
+// uvrt_plan_solve (bounds == nullptr) and uvrt_plan_solve_bounded.  Bounds that bind nothing (all-zero lower, no fixed
+// column) take the unbounded instantiations of every kernel: the same arithmetic, bit for bit.
+int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
+               uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
+{
+    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "%s: no plan (uvrt_plan_begin)", who);
+    if (c->plan->captures == 0) return fail(UVRT_ERR_INVALID, "%s: nothing captured (uvrt_plan_capture_batch)", who);
+    if (!prm || !out || !rep) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
+    if (prm->photons_per_position < 1 || prm->photons_per_position > (int64_t)0xFFFFFFFFll)
+        return fail(UVRT_ERR_INVALID, "%s: %lld photons per position overflow the uint32 counts", who,
+                    (long long)prm->photons_per_position);
+    if (!(prm->scaled_power > 0.0f) || !std::isfinite(prm->scaled_power) || !std::isfinite(prm->min_dose) ||
+        !(prm->margin >= 0.0) || !(prm->rel_gap > 0.0))
+        return fail(UVRT_ERR_INVALID, "%s: scaled_power > 0, finite min_dose, margin >= 0 and rel_gap > 0 required", who);
+    PlanState& S = *c->plan;
+    const int32_t T = c->T, P = S.P;
+    // ---- the bounds: lower as f64, the fixed flags, the free columns in ascending order
+    std::vector<double> low(P, 0.0);
+    std::vector<uint8_t> fix(P, 0);
+    std::vector<int32_t> cols;
+    bool bounded = false;
+    double lower_total = 0.0;
+    for (int p = 0; p < P && bounds; ++p) {
+        if (bounds->lower) {
+            const float l = bounds->lower[p];
+            if (!std::isfinite(l) || !(l >= 0.0f))
+                return fail(UVRT_ERR_INVALID, "%s: lower[%d] must be finite and >= 0", who, p);
+            low[p] = l;
+            lower_total += l;
+            bounded = bounded || l != 0.0f;
+        }
+        if (bounds->fixed && bounds->fixed[p]) { fix[p] = 1; bounded = true; }
+    }
+    for (int p = 0; p < P; ++p)
+        if (!fix[p]) cols.push_back(p);
+    const int32_t PF = (int32_t)cols.size();              // the columns the simplex sees (P when unbounded)
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    const unsigned nbt = nblocks(T, 256);
+    {
+        uint32_t of = 0;
+        HIP_TRY(hipMemcpyAsync(&of, S.overflow.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (of) return fail(UVRT_ERR_INVALID, "%s: a captured count overflowed uint32 (over 2^32 - 1 photons of one position)", who);
+    }
+    int rc;
+    memset(rep, 0, sizeof *rep);
+    rep->positions = P;
+    if (brep) {
+        memset(brep, 0, sizeof *brep);
+        brep->fixed_columns = P - PF;
+        brep->free_columns = PF;
+        brep->lower_total = lower_total;
+    }
+
+    // ---- set-up: classes, exclusion statistics, the required rows
+    const int NC = bounded ? 6 : 4;
+    const double m = prm->min_dose, mprime = m * (1.0 + prm->margin);
+    if ((rc = S.cls.ensure((size_t)T, false, c->stream))) return rc;
+    if ((rc = S.blk_cnt.ensure((size_t)nbt * NC * 4, false, c->stream))) return rc;
+    if ((rc = S.blk_area.ensure((size_t)nbt * NC * 8, false, c->stream))) return rc;
+    if ((rc = S.blk_off.ensure((size_t)nbt * 4, false, c->stream))) return rc;
+    const uint8_t* dmask = nullptr;
+    if (prm->mask) {
+        if ((rc = S.mask.ensure((size_t)T, false, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.mask.p, prm->mask, (size_t)T, hipMemcpyHostToDevice, c->stream));
+        dmask = S.mask.as<uint8_t>();
+    }
+    BoundsDev bd;
+    memset(&bd, 0, sizeof bd);
+    if (bounded) {
+        if ((rc = S.lowd.ensure((size_t)P * 8, false, c->stream))) return rc;
+        if ((rc = S.fixd.ensure((size_t)P, false, c->stream))) return rc;
+        if ((rc = S.cols.ensure((size_t)std::max(PF, 1) * 4, false, c->stream))) return rc;
+        if ((rc = S.rho.ensure((size_t)T * 8, false, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.lowd.p, low.data(), (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(S.fixd.p, fix.data(), (size_t)P, hipMemcpyHostToDevice, c->stream));
+        if (PF > 0) HIP_TRY(hipMemcpyAsync(S.cols.p, cols.data(), (size_t)PF * 4, hipMemcpyHostToDevice, c->stream));
+        bd.lower = S.lowd.as<double>();
+        bd.fixed = S.fixd.as<uint8_t>();
+        bd.s = prm->scaled_power;
+        bd.Nf = (float)prm->photons_per_position;
+        bd.mprime = mprime;
+        bd.all_met = !(m > 0.0);
+    }
+    const uint32_t min_ph = (uint32_t)std::max(1, prm->min_photons);
+    hipLaunchKernelGGL(bounded ? k_plan_classify<true> : k_plan_classify<false>, dim3(nbt), dim3(256), 0, c->stream,
+                       (const uint32_t*)S.E.as<uint32_t>(), P, T, dmask, (const float*)c->area.as<float>(), min_ph,
+                       S.cls.as<uint8_t>(), S.blk_cnt.as<int32_t>(), S.blk_area.as<double>(), bd,
+                       bounded ? S.rho.as<double>() : nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> bc((size_t)nbt * NC), boff(nbt);
+    std::vector<double> ba((size_t)nbt * NC);
+    HIP_TRY(hipMemcpyAsync(bc.data(), S.blk_cnt.p, bc.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(ba.data(), S.blk_area.p, ba.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t cnt[6] = {0, 0, 0, 0, 0, 0};
+    double area[6] = {0, 0, 0, 0, 0, 0};
+    for (unsigned b = 0; b < nbt; ++b) {
+        boff[b] = (int32_t)cnt[0];
+        for (int q = 0; q < NC; ++q) { cnt[q] += bc[b * NC + q]; area[q] += ba[b * NC + q]; }
+    }
+    rep->required = (int32_t)(cnt[0] + cnt[4]); rep->unreachable = (int32_t)cnt[1];
+    rep->unresolved = (int32_t)cnt[2]; rep->masked_out = (int32_t)cnt[3];
+    rep->area_required = bounded ? area[0] + area[4] : area[0]; rep->area_unreachable = area[1];
+    rep->area_unresolved = area[2]; rep->area_masked_out = area[3];
+    if (brep) {
+        brep->met_by_lower = (int32_t)cnt[4]; brep->short_rows = (int32_t)cnt[5];
+        brep->area_met_by_lower = area[4]; brep->area_short = area[5];
+    }
+    const int64_t NR = cnt[0];                  // the rows of the LP: the required ones (bounded: the active ones)
+    S.s = prm->scaled_power;
+    S.Nf = (float)prm->photons_per_position;
+    S.solved = true;
+    if (NR == 0 || !(m > 0.0)) {
+        if (!bounded) {
+            for (int p = 0; p < P; ++p) out[p] = 0.0f;
+            rep->status = UVRT_PLAN_CONVERGED;
+            rep->min_dose_ratio = std::numeric_limits<double>::infinity();
+            return UVRT_OK;
+        }
+        // the bounds meet every required row (or there is none): out = lower
+        double total = 0, minx = std::numeric_limits<double>::infinity();
+        int used = 0;
+        for (int p = 0; p < P; ++p) { out[p] = (float)low[p]; total += low[p]; used += low[p] > 0.0; }
+        if (m > 0.0 && cnt[4] > 0) {
+            if ((rc = S.dd.ensure((size_t)P * 8, false, c->stream))) return rc;
+            if ((rc = x_check(c, S, mprime, low, &minx))) return rc;
+        }
+        rep->used_positions = used;
+        rep->total_duration = total;
+        rep->lower_bound = total;
+        rep->status = UVRT_PLAN_CONVERGED;
+        rep->min_dose_ratio = m > 0.0 ? minx * (mprime / m) : minx;
+        return UVRT_OK;
+    }
+    const unsigned nbr = nblocks(NR, 256);
+    if ((rc = S.rows.ensure((size_t)NR * 4, false, c->stream))) return rc;
+    if ((rc = S.rd.ensure((size_t)NR * 8, false, c->stream))) return rc;
+    if ((rc = S.ratio.ensure((size_t)NR * 8, false, c->stream))) return rc;
+    for (DevBuf* b : {&S.dd, &S.raise})
+        if ((rc = b->ensure((size_t)P * 8, false, c->stream))) return rc;
+    if ((rc = S.blk_min.ensure((size_t)nbr * 8, false, c->stream))) return rc;
+    if ((rc = S.zrows.ensure(4, false, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(S.blk_off.p, boff.data(), (size_t)nbt * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(bounded ? k_plan_compact<true> : k_plan_compact<false>, dim3(nbt), dim3(256), 0, c->stream,
+                       (const uint32_t*)S.E.as<uint32_t>(), P, T,
+                       (const uint8_t*)S.cls.as<uint8_t>(), (const float*)c->area.as<float>(), (const int32_t*)S.blk_off.as<int32_t>(),
+                       S.s, S.Nf, mprime, S.rows.as<int32_t>(), S.rd.as<double>(),
+                       bounded ? (const double*)S.rho.as<double>() : nullptr);
+    HIP_TRY(hipGetLastError());
+
+    // ---- cutting planes from the uniform plan: rows W gathered so far (AW: |W| x PF, f64), exact LP over W, repeat.
+    // d64 holds every column (a fixed one stays 0: the row kernels skip it); the simplex sees the PF free ones.
+    const int max_rounds = prm->max_iterations > 0 ? prm->max_iterations : 200;
+    const int per_round = std::max(64, 2 * PF);
+    std::vector<double> d64(P, 0.0), dlp, ratio, AW, best_d;
+    std::vector<int64_t> W;
+    std::vector<uint8_t> inW((size_t)NR, 0);
+    uvrt_plan_lp::RestrictedLP lp(PF);
+    int64_t pivots = 0;
+    double best_ub = std::numeric_limits<double>::infinity(), best_lb = 0.0;
+    int it = 0;
+    {
+        std::vector<double> ones(P, 1.0);
+        RowCheck r1;
+        if ((rc = row_check(c, S, bounded, NR, ones, false, &r1, nullptr))) return rc;
+        for (int p : cols) d64[p] = r1.min_ratio > 0.0 ? 1.0 / r1.min_ratio : 1.0;
+    }
+    for (;;) {
+        RowCheck rck;
+        if ((rc = row_check(c, S, bounded, NR, d64, false, &rck, nullptr, &ratio))) return rc;
+        double sd = 0;
+        for (double v : d64) sd += v;
+        if (rck.min_ratio > 0.0 && sd / rck.min_ratio < best_ub) {
+            best_ub = sd / rck.min_ratio;
+            best_d = d64;
+            for (double& v : best_d) v /= rck.min_ratio;
+        }
+        if (std::isfinite(best_ub) && (best_ub - best_lb) <= prm->rel_gap * best_ub) break;
+        if (it >= max_rounds) break;
+        // the most violated rows not yet in W (round 0: the least covered ones under the uniform plan)
+        std::vector<int64_t> cand;
+        for (int64_t i = 0; i < NR; ++i)
+            if (!inW[i] && (it == 0 || ratio[i] < 1.0)) cand.push_back(i);
+        if (cand.empty()) break;          // d covers every row: the restricted optimum is global
+        const size_t take = std::min(cand.size(), (size_t)per_round);
+        std::partial_sort(cand.begin(), cand.begin() + take, cand.end(), [&](int64_t a, int64_t b) {
+            return ratio[a] < ratio[b] || (ratio[a] == ratio[b] && a < b);
+        });
+        cand.resize(take);
+        std::sort(cand.begin(), cand.end());
+        if ((rc = S.sel.ensure(take * 8, false, c->stream))) return rc;
+        if ((rc = S.gath.ensure(take * (size_t)PF * 8, false, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.sel.p, cand.data(), take * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(bounded ? k_plan_gather<true> : k_plan_gather<false>, dim3(nblocks((int64_t)take * PF, 256)), dim3(256), 0,
+                           c->stream, (const uint32_t*)S.E.as<uint32_t>(), T, PF, (const int32_t*)S.rows.as<int32_t>(),
+                           (const double*)S.rd.as<double>(), (const int64_t*)S.sel.as<int64_t>(), (int32_t)take, S.gath.as<double>(),
+                           bounded ? (const int32_t*)S.cols.as<int32_t>() : nullptr);
+        HIP_TRY(hipGetLastError());
+        const size_t old = AW.size();
+        AW.resize(old + take * (size_t)PF);
+        HIP_TRY(hipMemcpyAsync(AW.data() + old, S.gath.p, take * (size_t)PF * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int64_t i : cand) { inW[i] = 1; W.push_back(i); }
+        lp.add_rows(AW.data() + old, (int64_t)take);
+        const bool solved = lp.solve(50 * (lp.rows() + PF) + 1000, &pivots);
+        std::vector<double> yW;
+        lp.solution(&yW, &dlp);                 // an interrupted solve still leaves a feasible basis: a certificate
+        for (int f = 0; f < PF; ++f) d64[cols[f]] = dlp[f];
+        // certificate of the restricted dual (zero on the rows outside W): LB = sum y / max_p (A^T y)_p, in f64
+        std::vector<double> g(PF, 0.0);
+        double sy = 0;
+        for (size_t j = 0; j < W.size(); ++j) {
+            if (yW[j] == 0.0) continue;
+            sy += yW[j];
+            for (int p = 0; p < PF; ++p) g[p] += AW[j * PF + p] * yW[j];
+        }
+        const double gmax = *std::max_element(g.begin(), g.end());
+        if (gmax > 0.0) best_lb = std::max(best_lb, sy / gmax);
+        ++it;
+        if (!solved) {                          // pivot cap: keep what is certified, report the gap
+            RowCheck rlast;
+            if ((rc = row_check(c, S, bounded, NR, d64, false, &rlast, nullptr))) return rc;
+            double sl = 0;
+            for (double v : d64) sl += v;
+            if (rlast.min_ratio > 0.0 && sl / rlast.min_ratio < best_ub) {
+                best_ub = sl / rlast.min_ratio;
+                best_d = d64;
+                for (double& v : best_d) v /= rlast.min_ratio;
+            }
+            break;
+        }
+    }
+
+    // ---- repair (f64): cover rows without coverage by their best position, drop positions the plan does not need, scale
+    if (std::isfinite(best_ub)) d64 = best_d;
+    std::vector<double> dh(P);
+    {
+        double dmax = 0;
+        for (double v : d64) dmax = std::max(dmax, v);
+        for (double& v : d64) if (v <= 1e-7 * dmax) v = 0.0;
+    }
+    RowCheck rck{};
+    std::vector<double> raise;
+    for (int round = 0; round < 4; ++round) {
+        if ((rc = row_check(c, S, bounded, NR, d64, true, &rck, &raise))) return rc;
+        if (rck.zero_rows == 0) break;
+        for (int p = 0; p < P; ++p) d64[p] = std::max(d64[p], raise[p]);
+    }
+    if (rck.zero_rows != 0 || !(rck.min_ratio > 0.0)) return fail(UVRT_ERR_INVALID, "%s: repair left rows uncovered", who);
+    for (double& v : d64) v /= rck.min_ratio;
+    std::vector<float> d32(P);
+    double min_ratio = 0.0;
+    if (!bounded) {
+        // f32, rounded up to values that survive SaveRoute / LoadRoute; re-checked in f64
+        for (int round = 0; round < 8; ++round) {
+            for (int p = 0; p < P; ++p) {
+                float f = (float)d64[p];
+                if ((double)f < d64[p]) f = nextafterf(f, INFINITY);
+                d32[p] = d64[p] > 0.0 ? uvrt_plan_round_trip_up(f) : 0.0f;
+                dh[p] = d32[p];
+            }
+            if ((rc = row_check(c, S, false, NR, dh, false, &rck, nullptr))) return rc;
+            if (rck.min_ratio >= 1.0) break;
+            for (double& v : d64) v *= (1.0 / rck.min_ratio) * (1.0 + 1e-12);
+        }
+        if (!(rck.min_ratio >= 1.0)) return fail(UVRT_ERR_INVALID, "%s: the f32 durations do not reach the minimum", who);
+        min_ratio = rck.min_ratio;
+    } else {
+        // x = lower + e in f32: lower itself where e is 0, else rounded up as above; checked in x-space over the required
+        // rows, every column counted.  A miss rescales the excess the f32 values carry by what the active rows lack.
+        for (int round = 0; round < 8; ++round) {
+            for (int p = 0; p < P; ++p) {
+                d32[p] = (float)low[p];
+                if (d64[p] > 0.0) {
+                    const double x = low[p] + d64[p];
+                    float f = (float)x;
+                    if ((double)f < x) f = nextafterf(f, INFINITY);
+                    d32[p] = uvrt_plan_round_trip_up(f);
+                }
+                dh[p] = d32[p];
+            }
+            if ((rc = x_check(c, S, mprime, dh, &min_ratio))) return rc;
+            if (min_ratio >= 1.0) break;
+            for (int p = 0; p < P; ++p) dh[p] = fix[p] ? 0.0 : dh[p] - low[p];
+            if ((rc = row_check(c, S, true, NR, dh, false, &rck, nullptr))) return rc;
+            const double up = (rck.min_ratio > 0.0 && rck.min_ratio < 1.0 ? 1.0 / rck.min_ratio : 1.0) * (1.0 + 1e-9);
+            for (int p = 0; p < P; ++p) d64[p] = std::max(d64[p], dh[p]) * up;
+        }
+        if (!(min_ratio >= 1.0)) return fail(UVRT_ERR_INVALID, "%s: the f32 durations do not reach the minimum", who);
+    }
+    double total = 0;
+    int used = 0;
+    for (int p = 0; p < P; ++p) { out[p] = d32[p]; total += d32[p]; used += d32[p] > 0.0f; }
+    rep->iterations = it;
+    rep->used_positions = used;
+    rep->total_duration = total;
+    if (!bounded) {
+        rep->lower_bound = std::min(best_lb, total);
+        rep->gap = total > 0.0 ? (total - rep->lower_bound) / total : 0.0;
+    } else {
+        const double excess = total - lower_total;       // what the residual LP decides
+        rep->lower_bound = lower_total + std::min(best_lb, excess);
+        rep->gap = excess > 0.0 ? (total - rep->lower_bound) / excess : 0.0;
+    }
+    rep->status = rep->gap <= prm->rel_gap ? UVRT_PLAN_CONVERGED : UVRT_PLAN_ITERATION_CAP;
+    rep->min_dose_ratio = min_ratio * (mprime / m);
+    return UVRT_OK;
+}
+
+}  // namespace

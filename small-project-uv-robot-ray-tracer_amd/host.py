@@ -63,6 +63,8 @@ SYMBOLS = [
                                  C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
+    ("uvrt_host_rt_plan_segments", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     ("uvrt_host_rt_end_plan", None, [_vp]),
     ("uvrt_host_rt_set_candidate_grid", None, [_vp, C.c_int, C.c_int, C.c_float]),
     ("uvrt_host_grid_positions", None, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
@@ -236,7 +238,9 @@ class RayTracer:
         """RayTracer::PlanDurations: one batched computation over the current positions from the current SEED with the
         exposure captured, then the least durations that bring every required triangle to min_dose (default: the
         route's minDosage).  They are written into the positions; returns (durations float32[P], report dict with
-        the starting "seed")."""
+        the starting "seed").  With driveSpeed > 0 (2 to 128 positions) the segments between consecutive positions are
+        fixed columns of the plan at the time the drive takes: the dict then also carries the fields of the bounds
+        report (capi.PlanBoundsReport) and "segment_durations" (float32[P - 1])."""
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
         self._L.uvrt_host_rt_plan(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons), float(margin),
                                   float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))
@@ -292,6 +296,13 @@ def _addr(a):
 def _plan_result(rt, rep, seed):
     d = rep.as_dict()
     d["seed"] = int(seed.value)
+    brep = capi.PlanBoundsReport()
+    rt._L.uvrt_host_rt_plan_bounds(rt._h, C.byref(brep))
+    if brep.fixed_columns > 0:        # a driving plan: the segments were fixed columns
+        d.update(brep.as_dict())
+        seg = (C.c_float * brep.fixed_columns)()
+        n = rt._L.uvrt_host_rt_plan_segments(rt._h, seg, brep.fixed_columns)
+        d["segment_durations"] = np.frombuffer(seg, dtype=np.float32)[:n].copy()
     return np.array([l[2] for l in rt.lamps()], dtype=np.float32), d
 
 

@@ -138,6 +138,14 @@ void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, 
     o.maxIterations = max_iterations; o.mask = mask;
     *rep = RayTracer::PlanDurations(g, o, seed);
 }
+// of the last PlanDurations: the bounds report and the segment columns (returns their number; copies at most n)
+void uvrt_host_rt_plan_bounds(void* r, uvrt_plan_bounds_report* out) { *out = ((RayTracer*)r)->planBounds; }
+int uvrt_host_rt_plan_segments(void* r, float* out, int n)
+{
+    const std::vector<float>& s = ((RayTracer*)r)->planSegmentDurations;
+    for (int i = 0; i < n && i < (int)s.size(); ++i) out[i] = s[i];
+    return (int)s.size();
+}
 void uvrt_host_rt_end_plan(void* r) { ((RayTracer*)r)->EndPlan(); }
 void uvrt_host_rt_set_candidate_grid(void* r, int nx, int nz, float inset) { ((RayTracer*)r)->SetCandidateGrid(nx, nz, inset); }
 void uvrt_host_grid_positions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz)

@@ -234,7 +234,6 @@ void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, i
         for (RayTracer* rt : group)
             if (!(rt->driveSpeed > 0.0f)) fatal("ComputeIterationsBatched: every instance of a group must drive (driveSpeed > 0) or none");
         if (r0->shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
-        if (r0->planCapture) fatal("driveSpeed > 0 is not supported with duration planning");
     }
     TraceBatched(group, iterations, driving);
 }
@@ -313,9 +312,9 @@ void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iteration
         if (group.size() > 1) check(uvrt_reduce_batch_group(ctxs.data(), (int)ctxs.size()), "reduce_batch_group");
         for (RayTracer* rt : group) {
             if (group.size() == 1 && rt->reduceOverComm) check(uvrt_reduce_batch(rt->ctx), "reduce_batch");
-            if (rt->planCapture) {                       // launch j of the batch is position (done + j) % L (planning never drives)
+            if (rt->planCapture) {                       // launch j of the batch is column (done + j) % P: the stops, then the segments
                 std::vector<int32_t> pos((size_t)cnt);
-                for (int j = 0; j < cnt; ++j) pos[j] = (int32_t)((done + j) % L);
+                for (int j = 0; j < cnt; ++j) pos[j] = (int32_t)((done + j) % P);
                 check(uvrt_plan_capture_batch(rt->ctx, pos.data(), cnt), "plan_capture_batch");
             }
             check(uvrt_replay_batch(rt->ctx, ops.data(), cnt, rt->mesh->triangleCount), "replay_batch");
@@ -335,14 +334,16 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     RayTracer* r0 = group[0];
     const int L = (int)r0->lightPositions.size();
     if (L == 0) fatal("PlanDurations: no positions");
-    for (RayTracer* rt : group)
-        if (rt->driveSpeed > 0.0f) fatal("PlanDurations: planning with driveSpeed > 0 is not supported (the plan models stops only)");
+    // a driving route: the L - 1 segments are further columns of E, fixed at the time the drive takes (raytracer.h)
+    const bool driving = r0->driveSpeed > 0.0f && L >= 2;
+    if (driving && L > 128) fatal("PlanDurations: a driving plan takes at most 128 positions (2L - 1 <= 256 columns)");
+    const int cols = driving ? 2 * L - 1 : L;
     if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
         fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
     uint32_t seed0 = 0;
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
     for (RayTracer* rt : group) {
-        check(uvrt_plan_begin(rt->ctx, L), "plan_begin");
+        check(uvrt_plan_begin(rt->ctx, cols), "plan_begin");
         rt->ClearBuffers(true);                              // ResetDosageMap without the route save
         rt->currIterations = 0;
         rt->launchIndex = 0;
@@ -361,17 +362,40 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     prm.mask = opt.mask;
     uvrt_plan_report rep;
     memset(&rep, 0, sizeof rep);
-    std::vector<float> d((size_t)L), d_other((size_t)L);
+    std::vector<float> d((size_t)cols), d_other((size_t)cols), lower((size_t)cols, 0.0f);
+    std::vector<uint8_t> fixed((size_t)cols, 0);
+    for (int k = 0; driving && k + 1 < L; ++k) {             // the f32 duration TraceBatched gives the segment's replay op
+        const LightPos& a = r0->lightPositions[k];
+        const LightPos& b = r0->lightPositions[k + 1];
+        const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
+        const float len = sqrtf(dx * dx + dz * dz);
+        lower[L + k] = len / r0->driveSpeed;
+        fixed[L + k] = 1;
+    }
+    uvrt_plan_bounds bounds;
+    memset(&bounds, 0, sizeof bounds);
+    bounds.lower = lower.data();
+    bounds.fixed = fixed.data();
+    uvrt_plan_bounds_report brep;
+    memset(&brep, 0, sizeof brep);
+    brep.free_columns = L;
     for (size_t r = 0; r < group.size(); ++r) {
         RayTracer* rt = group[r];
         rt->planCapture = false;
         uvrt_plan_report rr;
-        check(uvrt_plan_solve(rt->ctx, &prm, r == 0 ? d.data() : d_other.data(), &rr), "plan_solve");
+        float* dr = r == 0 ? d.data() : d_other.data();
+        if (driving) check(uvrt_plan_solve_bounded(rt->ctx, &prm, &bounds, dr, &rr, r == 0 ? &brep : nullptr), "plan_solve_bounded");
+        else check(uvrt_plan_solve(rt->ctx, &prm, dr, &rr), "plan_solve");
         if (r == 0) rep = rr;
         else if (memcmp(d.data(), d_other.data(), d.size() * 4) != 0) fatal("PlanDurations: the contexts of the group planned different durations");
     }
-    for (RayTracer* rt : group)
+    if (driving && memcmp(d.data() + L, lower.data() + L, (size_t)(L - 1) * 4) != 0)
+        fatal("PlanDurations: the solver changed the duration of a segment");
+    for (RayTracer* rt : group) {
         for (int i = 0; i < L; ++i) rt->lightPositions[i].duration = d[i];
+        rt->planBounds = brep;
+        rt->planSegmentDurations.assign(d.begin() + L, d.end());
+    }
     if (seedOut) *seedOut = seed0;
     return rep;
 }

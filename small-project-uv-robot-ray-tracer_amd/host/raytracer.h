@@ -114,6 +114,15 @@ public:
     void SetCandidateGrid(int nx, int nz, float inset);
     static void GridPositions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz);
     bool planCapture = false;                       // ComputeIterationsBatched captures every batch (PlanDurations)
+    // Planning a route that drives (driveSpeed > 0, at least 2 positions, at most 128): E gets 2L - 1 columns, the stops
+    // 0..L-1 and segment k -> k+1 as column L + k, and uvrt_plan_solve_bounded plans the stops (free, lower bound 0) with
+    // every segment FIXED at the f32 time len / driveSpeed its replay op carries (zero-length segments included): the
+    // plan counts what the drive delivers and says which rows only the drive reaches.  planBounds is that solve's
+    // bounds report (met_by_lower: rows the drive alone brings to the minimum; short_rows: rows no stop reaches and the
+    // drive leaves below it) and planSegmentDurations the segment columns as solved (= lower, bit for bit, or fatal);
+    // after a plan without driving: no fixed column, L free ones, no segment.
+    uvrt_plan_bounds_report planBounds{};
+    std::vector<float> planSegmentDurations;
     // Dose while the robot drives.  driveSpeed (m/s) > 0: after the stops of an iteration ComputeDosageMap traces the
     // segments 0->1, ..., L-2->L-1 between consecutive positions, the lamp radiating while it moves at that speed
     // (include/uvrt.h uvrt_generate_sweep: photonsPerLight photons spread uniformly in time over the segment).  A segment
@@ -123,7 +132,7 @@ public:
     // is the reference's behaviour, bit for bit.  Saved as <rijsnelheid> in route files when > 0.
     // ComputeIterationsBatched traces an iteration's L stops and L - 1 segments as 2L - 1 logical launches of
     // uvrt_trace_batch_launches (the Shade rides on the last), so a group of instances, a ray range and reduceOverComm
-    // work with driving as they do without; launch sharding (shardWorld > 1) and planning refuse it.
+    // work with driving as they do without, PlanDurations included; launch sharding (shardWorld > 1) refuses it.
     float driveSpeed = 0;
     // one segment: a and b are two positions (their durations are not used); len = sqrtf(dx*dx + dz*dz) in f32
     void ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount);

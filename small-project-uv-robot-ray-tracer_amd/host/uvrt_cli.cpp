@@ -28,7 +28,13 @@
 //            [--plan-holdout SEED]          the same from another SEED: area fraction at or above the minimum (informative)
 //            [--drive-speed V]              the lamp radiates while the robot drives between consecutive positions at V m/s
 //                                           (RayTracer::driveSpeed; default: the route's <rijsnelheid>, 0 = stops only);
-//                                           one context, no planning
+//                                           one context; with --plan use --plan-drive
+//            [--plan-drive V]               plan (as --plan) for a route driven at V m/s: the segments between consecutive
+//                                           positions are fixed columns of the plan at the time the drive takes, so the stops
+//                                           only add what the drive leaves missing; sets the route's speed (--save-route
+//                                           writes <rijsnelheid>); 0 forces a stops-only plan of a route file that drives.
+//                                           A route file whose own <rijsnelheid> is > 0 is planned with driving under --plan.
+//                                           At most 128 positions, one context.
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -94,6 +100,11 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     printf("plan: %d positions, %d used, total duration %.9g (lower bound %.9g, gap %.3g), %s after %d iterations\n",
            r.positions, r.used_positions, r.total_duration, r.lower_bound, r.gap,
            r.status == UVRT_PLAN_CONVERGED ? "converged" : "iteration cap", r.iterations);
+    if (rt.planBounds.fixed_columns > 0)
+        printf("plan: driving at %.9g m/s: drive time %.9g s over %d segments; %d rows met by the drive alone (area %.6g), "
+               "%d short rows no stop reaches (area %.6g)\n", (double)rt.driveSpeed, rt.planBounds.lower_total,
+               rt.planBounds.fixed_columns, rt.planBounds.met_by_lower, rt.planBounds.area_met_by_lower,
+               rt.planBounds.short_rows, rt.planBounds.area_short);
     printf("plan: minimum %.9g mJ/cm^2 from SEED %u; required %d triangles (area %.6g), unreachable %d (area %.6g), "
            "unresolved %d (area %.6g), masked out %d (area %.6g); min dose / minimum %.9g\n",
            (double)m, seed0, r.required, r.area_required, r.unreachable, r.area_unreachable, r.unresolved, r.area_unresolved,
@@ -102,8 +113,9 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
         if (rt.lightPositions[i].duration > 0.0f)
             printf("plan: position %zu (%.6g, %.6g) duration %.9g\n", i, rt.lightPositions[i].position.x,
                    rt.lightPositions[i].position.y, rt.lightPositions[i].duration);
-    std::vector<float> d(rt.lightPositions.size());
+    std::vector<float> d(rt.lightPositions.size());           // every column of the plan: the stops, then the segments
     for (size_t i = 0; i < d.size(); ++i) d[i] = rt.lightPositions[i].duration;
+    if (rt.planBounds.fixed_columns > 0) d.insert(d.end(), rt.planSegmentDurations.begin(), rt.planSegmentDurations.end());
     std::vector<uint8_t> req(T);
     if (uvrt_plan_read_required(rt.ctx, req.data(), 0, T) != UVRT_OK) { fprintf(stderr, "plan: %s\n", uvrt_last_error()); return 1; }
     if (!dump.empty()) {
@@ -147,7 +159,7 @@ int main(int argc, char** argv)
     long long photons = -1;
     int iterations = -1, lamps = -1, device = 0, gpus = 1, batch = 0, flavour = 0;
     bool calibrate = false, plan = false, planVerify = false, planHoldout = false;
-    float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f;
+    float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f, planDrive = -1.0f;
     int minPhotons = 16, gridX = 0, gridZ = 0;
     uint32_t holdoutSeed = 0;
     std::string verifyDump;
@@ -184,6 +196,7 @@ int main(int argc, char** argv)
             }
         }
         else if (!strcmp(argv[i], "--drive-speed")) { need(1); driveSpeed = (float)atof(argv[++i]); if (!(driveSpeed >= 0.0f)) { fprintf(stderr, "--drive-speed must be >= 0\n"); return 2; } }
+        else if (!strcmp(argv[i], "--plan-drive")) { need(1); plan = true; planDrive = (float)atof(argv[++i]); if (!(planDrive >= 0.0f)) { fprintf(stderr, "--plan-drive must be >= 0\n"); return 2; } }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -191,7 +204,8 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
-    if (driveSpeed > 0.0f && plan) { fprintf(stderr, "--drive-speed cannot be combined with --plan (the plan models stops only)\n"); return 2; }
+    if (driveSpeed > 0.0f && plan) { fprintf(stderr, "--drive-speed cannot be combined with --plan (plan a driving route with --plan-drive V)\n"); return 2; }
+    if (planDrive > 0.0f && gpus != 1) { fprintf(stderr, "--plan-drive runs on one context (--gpus 1)\n"); return 2; }
     if (driveSpeed > 0.0f && gpus != 1) { fprintf(stderr, "--drive-speed runs on one context (--gpus 1)\n"); return 2; }
     if (!routeDir.empty() && routeDir.back() != '/') routeDir += '/';
 
@@ -209,8 +223,9 @@ int main(int argc, char** argv)
     if (photons > 0) rayTracer.photonCount = (int)photons;
     if (iterations > 0) rayTracer.maxIterations = iterations;
     if (driveSpeed >= 0.0f) rayTracer.driveSpeed = driveSpeed;
-    if (rayTracer.driveSpeed > 0.0f && (plan || gpus != 1)) {     // (the route file's own <rijsnelheid>)
-        fprintf(stderr, "the route drives at %g m/s: not supported with --plan or --gpus > 1 (give --drive-speed 0)\n", (double)rayTracer.driveSpeed);
+    if (planDrive >= 0.0f) rayTracer.driveSpeed = planDrive;
+    if (rayTracer.driveSpeed > 0.0f && gpus != 1) {               // (the route file's own <rijsnelheid>)
+        fprintf(stderr, "the route drives at %g m/s: not supported with --gpus > 1 (give --drive-speed 0)\n", (double)rayTracer.driveSpeed);
         return 2;
     }
     rayTracer.UpdatePhotonsPerLight();
@@ -224,6 +239,10 @@ int main(int argc, char** argv)
         if (gpus != 1) { fprintf(stderr, "--plan runs on one context (--gpus 1)\n"); return 2; }
         if (uvrt_set_flavour(rayTracer.ctx, flavour) != UVRT_OK) { fprintf(stderr, "--flavour: %s\n", uvrt_last_error()); return 2; }
         if (gridX > 0) rayTracer.SetCandidateGrid(gridX, gridZ, gridInset);
+        if (rayTracer.driveSpeed > 0.0f && rayTracer.lightPositions.size() > 128) {
+            fprintf(stderr, "a driving plan takes at most 128 positions (%zu given)\n", rayTracer.lightPositions.size());
+            return 2;
+        }
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump);
