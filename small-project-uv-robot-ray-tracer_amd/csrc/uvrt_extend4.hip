@@ -15,7 +15,7 @@
 // Per trip a lane fetches ONE 128-byte record (= one L2 line: seven dwordx4 loads, eight lookups in one L1
 // line instead of two BVH2 records in two lines) and makes at most one descent and three pushes; a ray
 // needs about half the trips of the BVH2 walk.  The ray feed (refill, retire, exact-step flag, grid sizing) is
-// k_extend6's, in uvrt_traverse.h.
+// uvrt_traverse.h's, the one k_extend6 and k_extend_free use.
 #include "uvrt_traverse.h"
 
 namespace uvrt {
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256, 6) void k_extend4(ExtendParams p)
         const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
         const int nidle = __popcll(idle_mask);
         if (cursor < chunk_end && nidle >= p.refill_min) {
-            if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, p.root_ref4);
+            if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, p.root_ref4);
             cursor += (uint32_t)nidle;
         }
         const unsigned long long act = __builtin_amdgcn_ballot_w64(L.cur != REF_DONE);

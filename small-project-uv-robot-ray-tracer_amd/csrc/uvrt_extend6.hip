@@ -28,247 +28,13 @@
 // Lanes or launches outside the proof conditions (direction component zero, > 1 or < 2^-60, tiny or
 // huge origin / scene bounds) run the EXACT instantiation of the step: IEEE divisions and OpenCL's
 // select-form min/max, as the reference writes them.
+//
+// The step in C++ -- step6 (the general step) and step7 (the common trip in its lane-mask form) -- is in
+// uvrt_traverse.h: k_extend_free (uvrt_extend_free.hip) calls the same two functions with its own lane type.
+// This file holds the hand-written stream of the common trips (run7), the drain merge and the kernel's loop.
 #include "uvrt_traverse.h"
 
 namespace uvrt {
-
-// `exact` is wave-uniform: the record fetch and the descend / push / pop logic are common, only the
-// arithmetic of the box and triangle tests differs.
-template <bool TOP, int FL>
-__device__ __forceinline__ void step6(Lane6& L, const ExtendParams& p, uint32_t stack_base,
-                                      const float4* s_top, uint32_t top_pairs, bool leaf_trip, bool exact,
-                                      unsigned long long m_act /* lanes holding a ray */)
-{
-    const uint32_t cur = L.cur;
-    const bool is_inner = cur < REF_LEAF_BIT;
-    const bool is_leaf = (cur >= REF_LEAF_BIT) & (cur != REF_DONE) & leaf_trip;
-    const uint32_t idx = cur & REF_FIRST_MASK;          // record index (inner indices are < 2^27 too)
-    // ONE asm block fetches the 64-byte record of every stepping lane -- from the LDS top-of-tree
-    // cache or from global memory, chosen by exec masks -- and the lane's stack top, so that both
-    // sources write the same registers (hipcc otherwise merges the two branches with v_mov chains).
-    v4f w0, w1, w2, w3;
-    uint32_t spec_top = REF_DONE;                       // stays REF_DONE when the stack is empty
-    // stack entry sp - 1 of this lane (lanes with sp == 0 are masked off); entry sp is 1024 bytes on
-    const uint32_t sa = stack_base + ((uint32_t)L.sp << 10);
-    {
-        // lane masks from single comparisons, combined as 64-bit integers (SALU): a ballot of a
-        // compound condition would go through a v_cndmask / v_cmp pair
-        const unsigned long long m_in = __builtin_amdgcn_ballot_w64(cur < REF_LEAF_BIT);
-        const unsigned long long m_top = TOP ? __builtin_amdgcn_ballot_w64(cur < top_pairs) : 0ull;
-        const unsigned long long m_sp = __builtin_amdgcn_ballot_w64(L.sp > 0);
-        const unsigned long long m_go = m_in | (leaf_trip ? (m_act & ~m_in) : 0ull);
-        const unsigned long long m_glob = m_go & ~m_top;
-        const unsigned long long m_stk = m_go & m_sp;
-        // LDS copy of record r at byte TOP6_STRIDE * r
-        const uint32_t a0 = (uint32_t)(uintptr_t)s_top + cur * TOP6_STRIDE;
-        // byte offset of the record: the shift drops the leaf flag and count bits of a reference
-        // (record indices are < 2^26: uvrt_capi.hip checks P + T), the base address is scalar
-        const uint32_t roff = cur << 6;
-        unsigned long long save;
-        asm volatile("s_mov_b64 %[save], exec\n\t"
-                     "s_mov_b64 exec, %[mstk]\n\t"
-                     "ds_read_b32 %[st], %[sa]\n\t"
-                     "s_mov_b64 exec, %[mtop]\n\t"
-                     "ds_read_b128 %[w0], %[a0]\n\t"
-                     "ds_read_b128 %[w1], %[a0] offset:16\n\t"
-                     "ds_read_b128 %[w2], %[a0] offset:32\n\t"
-                     "ds_read_b128 %[w3], %[a0] offset:48\n\t"
-                     "s_mov_b64 exec, %[mglob]\n\t"
-                     "global_load_dwordx4 %[w0], %[ro], %[rb]\n\t"
-                     "global_load_dwordx4 %[w1], %[ro], %[rb] offset:16\n\t"
-                     "global_load_dwordx4 %[w2], %[ro], %[rb] offset:32\n\t"
-                     "global_load_dwordx4 %[w3], %[ro], %[rb] offset:48\n\t"
-                     "s_mov_b64 exec, %[save]\n\t"
-                     "s_waitcnt vmcnt(0) lgkmcnt(0)"
-                     : [w0] "=&v"(w0), [w1] "=&v"(w1), [w2] "=&v"(w2), [w3] "=&v"(w3), [st] "+v"(spec_top),
-                       [save] "=&s"(save)
-                     : [a0] "v"(a0), [sa] "v"(sa), [ro] "v"(roff), [rb] "s"(p.recs),
-                       [mtop] "s"(m_top), [mglob] "s"(m_glob), [mstk] "s"(m_stk)
-                     : "memory");
-    }
-    bool need_pop = is_leaf;
-    if (is_inner) {
-        float d0, d1;
-        bool h0, h1;
-        if (FL == 2) {        // "shipped flags": t = (b - o) * v_rcp_f32(d) for every lane (there is no other form of it)
-            h0 = box_shipped(w0.x, w0.y, w2.x - L.po.x, w2.y - L.po.x, w0.z, w0.w, L.px.y, L.py.y, L.pz.y, L.po.y, d0);
-            h1 = box_shipped(w1.x, w1.y, w2.z - L.po.x, w2.w - L.po.x, w1.z, w1.w, L.px.y, L.py.y, L.pz.y, L.po.y, d1);
-        } else if (exact) {
-            h0 = box_exact(w0.x, w0.y, w2.x - L.po.x, w2.y - L.po.x, w0.z, w0.w, L.px.x, L.py.x, L.pz.x, L.po.y, d0);
-            h1 = box_exact(w1.x, w1.y, w2.z - L.po.x, w2.w - L.po.x, w1.z, w1.w, L.px.x, L.py.x, L.pz.x, L.po.y, d1);
-        } else {
-            v2f x0 = __builtin_shufflevector(w0, w0, 0, 1), z0 = __builtin_shufflevector(w0, w0, 2, 3);
-            v2f x1 = __builtin_shufflevector(w1, w1, 0, 1), z1 = __builtin_shufflevector(w1, w1, 2, 3);
-            v2f y0 = __builtin_shufflevector(w2, w2, 0, 1), y1 = __builtin_shufflevector(w2, w2, 2, 3);
-            slabs6(x0, y0, z0, L.px, L.py, L.pz, L.po);
-            h0 = box_fast(x0, y0, z0, L.po.y, d0);
-            slabs6(x1, y1, z1, L.px, L.py, L.pz, L.po);
-            h1 = box_fast(x1, y1, z1, L.po.y, d1);
-        }
-        // extend.cl:56-76 with dist = 1e30f for a missed child: nearer first, farther pushed
-        // dist1 > dist2 of extend.cl:61 with 1e30f standing for a miss: child 1 first iff it is hit and
-        // child 0 is missed or farther (a hit distance is < dist <= 1e30f, so the sentinel never ties)
-        const bool sw = h1 & (!h0 | (d0 > d1));
-        const uint32_t r0 = __float_as_uint(w3.x), r1 = __float_as_uint(w3.y);
-        const uint32_t nearer = sw ? r1 : r0, farther = sw ? r0 : r1;
-        if (h0 & h1) {
-            if (L.sp < PS6) asm volatile("ds_write_b32 %0, %1 offset:1024" : : "v"(sa), "v"(farther) : "memory");
-            else if (L.sp < MAXS6) ovf_ptr(p, stack_base)[L.sp - PS6] = farther;
-            else *p.error_flag = 1u;
-            L.sp = L.sp < MAXS6 ? L.sp + 1 : L.sp;
-        }
-        need_pop = !(h0 | h1);
-        L.cur = nearer;
-    }
-    // extend.cl:48-55 -- AFTER the inner-node block (other lanes): the triangles of a leaf with several of them
-    // are fetched when the node records' registers are free again
-    if (is_leaf) {
-        uint32_t count = (cur >> REF_COUNT_SHIFT) & 15u;
-        const uint32_t first = idx - (uint32_t)p.npairs;
-        if (count == 15u) count = p.scene.leaf_count[first];
-        float dist = L.po.y;
-        tri6<FL>(p.ox, L.po.x, p.oz, L.px.x, L.py.x, L.pz.x, dist, L.triID,
-             make_float4(w0.x, w0.y, w0.z, w0.w), make_float4(w1.x, w1.y, w1.z, w1.w),
-             make_float4(w2.x, w2.y, w2.z, w2.w), exact);
-        for (uint32_t i = 1; i < count; ++i) {
-            const float4* lt = (const float4*)p.recs + ((size_t)idx + i) * 4;
-            tri6<FL>(p.ox, L.po.x, p.oz, L.px.x, L.py.x, L.pz.x, dist, L.triID, lt[0], lt[1], lt[2], exact);
-        }
-        L.po.y = dist;
-    }
-    if (need_pop) {
-        uint32_t popped = spec_top;                        // REF_DONE when the stack is empty
-        if (L.sp > PS6) popped = ovf_ptr(p, stack_base)[L.sp - 1 - PS6];
-        L.cur = popped;
-        L.sp = (int)__builtin_elementwise_sub_sat((uint32_t)L.sp, 1u);
-    }
-}
-
-// The same step for the common case -- no lane needs the IEEE-division form, no lane's stack has left LDS -- with
-// the control flow written as lane masks instead of divergent branches.  Scalar issue is the dearest resource of
-// this kernel (one instruction per cycle per CU, shared by 32 waves: 32 extra scalar instructions per trip cost
-// 17 % of the launch, profiles/r02/r02_experiments.txt), and hipcc spends ~70 of them per trip on exec bookkeeping
-// for `if (inner) {...} if (both hit) {push} if (none hit) {pop}`.  Here the caller hands over the lane masks of
-// the trip (one vector comparison each), the box arithmetic runs for ALL lanes (a vector instruction costs the
-// same whatever its exec mask; lanes that do not stand at an inner node compute on stale registers and are
-// masked out of the results), the hit tests narrow exec themselves (v_cmpx), and descend / push / pop are
-// exec-masked instructions of one asm block.
-//   m_in: lanes at an inner node, m_leaf: lanes that visit their leaf in this trip, m_top: lanes whose record is
-//   in the LDS cache, full: the exec mask of the loop (all 64 lanes)
-template <bool TOP, int FL>
-__device__ __forceinline__ void step7(Lane6& L, const ExtendParams& p, uint32_t stack_base, uint32_t top_base,
-                                      unsigned long long m_in, unsigned long long m_leaf, unsigned long long m_top,
-                                      unsigned long long full
-#ifdef UVRT_TRIP_STATS
-                                      , uint32_t (&clk)[4]
-#define UVRT_CLK(i, t0) do { const unsigned long long t1_ = __builtin_readcyclecounter(); clk[i] += (uint32_t)(t1_ - t0); t0 = t1_; } while (0)
-#else
-#define UVRT_CLK(i, t0) do { } while (0)
-#endif
-                                      )
-{
-    const uint32_t cur = L.cur;
-    v4f w0, w1, w2, w3;
-    uint32_t spec_top;
-#ifdef UVRT_TRIP_STATS
-    unsigned long long tclk = __builtin_readcyclecounter();
-#endif
-    const uint32_t sa = stack_base + ((uint32_t)L.sp << 10);
-    {
-        const unsigned long long m_glob = (m_in | m_leaf) & ~m_top;
-        const uint32_t a0 = __umul24(cur, TOP6_STRIDE) + top_base;      // only used by lanes in m_top
-        const uint32_t roff = cur << 6;
-        // the stack top is read by every lane: entry -1 of a lane's LDS stack is a row that always holds REF_DONE
-        asm volatile("ds_read_b32 %[st], %[sa]\n\t"
-                     "s_mov_b64 exec, %[mtop]\n\t"
-                     "ds_read_b128 %[w0], %[a0]\n\t"
-                     "ds_read_b128 %[w1], %[a0] offset:16\n\t"
-                     "ds_read_b128 %[w2], %[a0] offset:32\n\t"
-                     "ds_read_b128 %[w3], %[a0] offset:48\n\t"
-                     "s_mov_b64 exec, %[mglob]\n\t"
-                     "global_load_dwordx4 %[w0], %[ro], %[rb]\n\t"
-                     "global_load_dwordx4 %[w1], %[ro], %[rb] offset:16\n\t"
-                     "global_load_dwordx4 %[w2], %[ro], %[rb] offset:32\n\t"
-                     "global_load_dwordx4 %[w3], %[ro], %[rb] offset:48\n\t"
-                     "s_mov_b64 exec, %[full]\n\t"
-                     "s_waitcnt vmcnt(0) lgkmcnt(0)"
-                     : [w0] "=&v"(w0), [w1] "=&v"(w1), [w2] "=&v"(w2), [w3] "=&v"(w3), [st] "=&v"(spec_top)
-                     : [a0] "v"(a0), [sa] "v"(sa), [ro] "v"(roff), [rb] "s"(p.recs), [mtop] "s"(m_top), [mglob] "s"(m_glob),
-                       [full] "s"(full)
-                     : "memory");
-    }
-    UVRT_CLK(0, tclk);
-    if (m_leaf != 0) {                                       // wave-uniform; m_leaf != 0 means: a leaf trip
-        if ((int32_t)cur < -1) {                             // at a leaf (REF_DONE is -1): extend.cl:48-55
-            const uint32_t idx = cur & REF_FIRST_MASK;
-            uint32_t count = (cur >> REF_COUNT_SHIFT) & 15u;
-            const uint32_t first = idx - (uint32_t)p.npairs;
-            if (count == 15u) count = p.scene.leaf_count[first];
-            float dist = L.po.y;
-            tri6<FL>(p.ox, L.po.x, p.oz, L.px.x, L.py.x, L.pz.x, dist, L.triID,
-                      make_float4(w0.x, w0.y, w0.z, w0.w), make_float4(w1.x, w1.y, w1.z, w1.w),
-                      make_float4(w2.x, w2.y, w2.z, w2.w), false);
-            for (uint32_t i = 1; i < count; ++i) {
-                const float4* lt = (const float4*)p.recs + ((size_t)idx + i) * 4;
-                tri6<FL>(p.ox, L.po.x, p.oz, L.px.x, L.py.x, L.pz.x, dist, L.triID, lt[0], lt[1], lt[2], false);
-            }
-            L.po.y = dist;
-        }
-    }
-    UVRT_CLK(1, tclk);
-    if (m_in != 0) {            // wave-uniform: a trip with no lane at an inner node skips the box arithmetic
-        v2f x0 = __builtin_shufflevector(w0, w0, 0, 1), z0 = __builtin_shufflevector(w0, w0, 2, 3);
-        v2f x1 = __builtin_shufflevector(w1, w1, 0, 1), z1 = __builtin_shufflevector(w1, w1, 2, 3);
-        v2f y0 = __builtin_shufflevector(w2, w2, 0, 1), y1 = __builtin_shufflevector(w2, w2, 2, 3);
-        if (FL == 2) {
-            slabs6s(x0, y0, z0, L.px, L.py, L.pz, L.po);
-            slabs6s(x1, y1, z1, L.px, L.py, L.pz, L.po);
-        } else {
-            slabs6(x0, y0, z0, L.px, L.py, L.pz, L.po);
-            slabs6(x1, y1, z1, L.px, L.py, L.pz, L.po);
-        }
-        float n0, f0, n1, f1;
-        box2_fast(x0, y0, z0, x1, y1, z1, n0, f0, n1, f1);
-        // extend.cl:36-38,56-76: hit = tmax >= tmin && tmin < dist && tmax > 0 per child; child 1 first iff it is hit
-        // and child 0 is missed or farther; both hit: the farther one is pushed; none hit (or a leaf visited): pop
-        unsigned long long h0, h1, t;
-        asm volatile("s_mov_b64 exec, %[min]\n\t"
-                     "v_cmpx_ge_f32_e64 %[h0], %[f0], %[n0]\n\t"
-                     "v_cmpx_lt_f32_e64 %[h0], %[n0], %[dist]\n\t"
-                     "v_cmpx_gt_f32_e64 %[h0], %[f0], 0\n\t"            // h0 = exec = inner lanes whose child 0 is hit
-                     "s_mov_b64 exec, %[min]\n\t"
-                     "v_cmpx_ge_f32_e64 %[h1], %[f1], %[n1]\n\t"
-                     "v_cmpx_lt_f32_e64 %[h1], %[n1], %[dist]\n\t"
-                     "v_cmpx_gt_f32_e64 %[h1], %[f1], 0\n\t"            // h1 likewise
-                     "v_cmp_gt_f32 vcc, %[n0], %[n1]\n\t"               // (under exec = h1)
-                     "s_andn2_b64 %[t], %[h1], %[h0]\n\t"
-                     "s_or_b64 %[t], %[t], vcc\n\t"                     // t = child 1 first
-                     "s_and_b64 exec, %[h0], %[h1]\n\t"                 // both hit: push the farther, sp + 1
-                     "v_cndmask_b32 %[n1], %[r1], %[r0], %[t]\n\t"
-                     "ds_write_b32 %[sa], %[n1] offset:1024\n\t"
-                     "v_add_u32 %[sp], 1, %[sp]\n\t"
-                     "s_or_b64 exec, %[h0], %[h1]\n\t"                  // any hit: descend into the nearer
-                     "v_cndmask_b32 %[cur], %[r0], %[r1], %[t]\n\t"
-                     "s_andn2_b64 %[t], %[min], exec\n\t"
-                     "s_or_b64 exec, %[t], %[mleaf]\n\t"                // none hit, or a leaf was visited: pop
-                     "v_mov_b32 %[cur], %[st]\n\t"
-                     "v_sub_u32 %[sp], %[sp], 1 clamp\n\t"
-                     "s_mov_b64 exec, %[full]"
-                     : [n1] "+v"(n1), [cur] "+v"(L.cur), [sp] "+v"(L.sp), [h0] "=&s"(h0), [h1] "=&s"(h1), [t] "=&s"(t)
-                     : [n0] "v"(n0), [f0] "v"(f0), [f1] "v"(f1), [dist] "v"(L.po.y), [r0] "v"(w3.x), [r1] "v"(w3.y), [sa] "v"(sa),
-                       [st] "v"(spec_top), [min] "s"(m_in), [mleaf] "s"(m_leaf), [full] "s"(full)
-                     : "vcc", "memory");
-    } else {
-        // only leaves were visited: pop them
-        asm volatile("s_mov_b64 exec, %[mleaf]\n\t"
-                     "v_mov_b32 %[cur], %[st]\n\t"
-                     "v_sub_u32 %[sp], %[sp], 1 clamp\n\t"
-                     "s_mov_b64 exec, %[full]"
-                     : [cur] "+v"(L.cur), [sp] "+v"(L.sp)
-                     : [st] "v"(spec_top), [mleaf] "s"(m_leaf), [full] "s"(full));
-    }
-    UVRT_CLK(2, tclk);
-}
 
 // ---- the common trips as ONE hand-written instruction stream ------------------------------------------------
 // run7 executes common trips (what step7 does for one) back to back until something else has to happen and says
@@ -662,6 +428,17 @@ __device__ __forceinline__ bool merge6(Lane6& L, const ExtendParams& p, int32_t*
     return true;
 }
 
+#ifdef UVRT_TRIP_STATS
+// step7's clock in the statistics build: the cycles between its laps, summed into the kernel's clk[]
+struct TripClock {
+    static constexpr bool RUNS = true;
+    uint32_t* clk;
+    unsigned long long t0;
+    __device__ __forceinline__ void start() { t0 = __builtin_readcyclecounter(); }
+    __device__ __forceinline__ void lap(int i) { const unsigned long long t1 = __builtin_readcyclecounter(); clk[i] += (uint32_t)(t1 - t0); t0 = t1; }
+};
+#endif
+
 template <int LEAFP, bool RECORD, bool TOP, int FL>
 __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
 {
@@ -720,7 +497,10 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     uint32_t st_s_in = 0, st_s_leaf = 0, st_s_both = 0, st_g_exact = 0, st_g_other = 0, st_tris = 0;
     uint32_t clk4 = 0;                // cycles in the general step
     uint32_t clk[4] = {0, 0, 0, 0};   // cycles in: record fetch (issue to data), leaf tests, box tests + descend, refill
+    TripClock trip_clock = {clk, 0ull};
     const unsigned long long t_begin = __builtin_readcyclecounter();
+#else
+    NoClock trip_clock;
 #endif
 
 #ifdef UVRT_TRIP_STATS
@@ -761,7 +541,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
                 const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
                 const int nidle = __popcll(idle_mask);
                 if (cursor < chunk_end) {
-                    if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
+                    if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
                     cursor += (uint32_t)nidle;
                     if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
                 } else if (TOP && cursor != MERGED6) {
@@ -803,7 +583,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
             unsigned long long tclk = __builtin_readcyclecounter();
 #endif
             if (cursor < chunk_end) {
-                if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
+                if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
                 cursor += (uint32_t)nidle;
                 if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
 #ifdef UVRT_TRIP_STATS
@@ -866,11 +646,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
             ++st_slow;
 #endif
         } else
-#ifdef UVRT_TRIP_STATS
-            step7<TOP, FL>(L, p, stack_base, top_base, m_in, m_lf & kme, m_top, full, clk);
-#else
-            step7<TOP, FL>(L, p, stack_base, top_base, m_in, m_lf & kme, m_top, full);
-#endif
+            step7<TOP, FL>(L, p, stack_base, top_base, m_in, m_lf & kme, m_top, full, trip_clock);
     }
 #ifdef UVRT_TRIP_STATS
     if ((threadIdx.x & 63) == 0) {

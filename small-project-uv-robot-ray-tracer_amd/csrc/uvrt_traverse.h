@@ -1,6 +1,8 @@
 // uvrt_traverse.h -- device helpers shared by the traversal kernels (uvrt_extend6.hip: the reference's
-// BVH2 order; uvrt_extend4.hip: the opt-in 4-wide collapse): exact slab distances, box and triangle tests,
-// the per-lane ray state, the ray feed (refill, retire, grid sizing), the stack-overflow pointer.  See
+// BVH2 order for the rays of one lamp column; uvrt_extend_free.hip: the same for rays of any origin;
+// uvrt_extend4.hip: the opt-in 4-wide collapse): exact slab distances, box and triangle tests, the
+// per-lane ray state, the ray feed (refill, retire, grid sizing), the stack-overflow pointer, and the
+// BVH2 traversal step itself (step6 / step7: ONE function each for k_extend6 and k_extend_free).  See
 // uvrt_extend6.hip's header for the arithmetic.
 #pragma once
 #include "uvrt_device.h"
@@ -206,6 +208,7 @@ __device__ __forceinline__ void set_in_place(v2f& dst, float lo, float hi)
 }
 
 struct Lane6 {
+    static constexpr bool OWN_XZ = false;   // x / z of the origin are the launch's (p.ox, p.oz); the records hold b - o
     v2f px, py, pz;         // {d, RN32(1/d)} per axis
     v2f po;                 // {origin y, dist}
     uint32_t triID;
@@ -213,7 +216,31 @@ struct Lane6 {
     int sp;
 };
 
-// ---- the persistent ray feed of k_extend6 and k_extend4 ----
+// the lane of a ray that carries its own origin (k_extend_free): the records hold the raw bounds, a step forms b - o
+struct LaneF : Lane6 {
+    static constexpr bool OWN_XZ = true;
+    v2f oxz;                // {origin x, origin z}
+};
+
+// x / z of the origin of a lane's ray, for the triangle test (asked for where it is used: a copy made at the top of a step
+// changes the order of hipcc's instructions)
+__device__ __forceinline__ float origin_x(const Lane6&, const ExtendParams& p) { return p.ox; }
+__device__ __forceinline__ float origin_z(const Lane6&, const ExtendParams& p) { return p.oz; }
+__device__ __forceinline__ float origin_x(const LaneF& L, const ExtendParams&) { return L.oxz.x; }
+__device__ __forceinline__ float origin_z(const LaneF& L, const ExtendParams&) { return L.oxz.y; }
+
+// a = b - o for the x and z (min, max) pairs of both children
+__device__ __forceinline__ void sub_xz(v2f& x0, v2f& z0, v2f& x1, v2f& z1, v2f oxz)
+{
+    asm("v_pk_add_f32 %[x0], %[x0], %[o] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[z0], %[z0], %[o] op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[x1], %[x1], %[o] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %[z1], %[z1], %[o] op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]"
+        : [x0] "+v"(x0), [z0] "+v"(z0), [x1] "+v"(x1), [z1] "+v"(z1)
+        : [o] "v"(oxz));
+}
+
+// ---- the persistent ray feed of k_extend6, k_extend4 and k_extend_free ----
 // ints from a wave's replica of the counts to the plane of a lane's ray (the kernels' plane_off; bit 31 of that register:
 // the ray needs the exact step)
 constexpr uint32_t PLANE_OFF6 = 0x7FFFFFFFu, SPECIAL6 = 0x80000000u;
@@ -232,6 +259,14 @@ __device__ __forceinline__ bool outside_proof_conditions(float4 rec)
     return worst > one - lo || (uo != 0u && uo - ylo > yhi - ylo);
 }
 
+// |o| zero or in [2^-100, 1e9]: the window outside_proof_conditions applies to the origin's y
+__device__ __forceinline__ bool origin_outside_window(float o)
+{
+    const uint32_t uo = __float_as_uint(o) & 0x7FFFFFFFu;
+    const uint32_t lo = 0x0D800000u /* 2^-100 */, hi = 0x4E6E6B28u /* 1e9f */;
+    return uo != 0u && uo - lo > hi - lo;
+}
+
 // The results of the ray a lane has finished (extend.cl:94-98): its hit record when one is pending (`live`), and its deposit
 // unless it hit nothing (dist == 1e30f).
 template <bool RECORD>
@@ -245,13 +280,18 @@ __device__ __forceinline__ void retire_ray(const Lane6& L, const ExtendParams& p
     if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
 }
 
+// Does a launch hold the planes of a batch (include/uvrt.h uvrt_trace_batch_launches)?  k_extend6 / k_extend4 ask the launch
+// (p.plane_stride != 0: one kernel serves both); k_extend_free is compiled for either answer.
+enum PlaneMode { PLANES_ASK, PLANES_NONE, PLANES_ALL };
+
 // The per-lane part of a refill, for an idle lane (L.cur == REF_DONE): retire its last ray, then take slot cursor + (rank among
 // the idle lanes) of the wave's sequence of 64-ray batches wave, wave + W, wave + 2W, ...  A slot beyond the wave's share, the
-// launch or its plane leaves the lane idle.  `root`: the kernel's root reference.
-template <bool RECORD, int FL>
-__device__ __forceinline__ void refill_lane(Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t& plane_off,
-                                            uint32_t& slot, bool& live, unsigned long long idle_mask, uint32_t cursor,
-                                            uint32_t wave, uint32_t W, uint32_t root)
+// launch or its plane leaves the lane idle.  `root`: the kernel's root reference; `oxz`: the rays' {origin x, origin z}, read for
+// a lane that carries them (LaneF).
+template <bool RECORD, int FL, PlaneMode PM = PLANES_ASK, class LaneT>
+__device__ __forceinline__ void refill_lane(LaneT& L, const ExtendParams& p, const float2* oxz, int32_t* my_counts,
+                                            uint32_t& plane_off, uint32_t& slot, bool& live, unsigned long long idle_mask,
+                                            uint32_t cursor, uint32_t wave, uint32_t W, uint32_t root)
 {
     retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);
     live = false;
@@ -264,25 +304,35 @@ __device__ __forceinline__ void refill_lane(Lane6& L, const ExtendParams& p, int
     // correction step (gb < 2^24 is exact in f32, the rounded reciprocal is off by < 1)
     uint32_t pl = 0;
     int32_t within = (int32_t)gb;
-    if (p.plane_stride != 0) {               // wave-uniform: a launch of its own is one plane
+    if (PM == PLANES_ASK ? p.plane_stride != 0 : PM == PLANES_ALL) {        // wave-uniform: a launch of its own is one plane
         pl = (uint32_t)((float)gb * p.plane_inv);
         within = (int32_t)(gb - pl * p.plane_batches);
         if (within < 0) { --pl; within += (int32_t)p.plane_batches; }
         else if ((uint32_t)within >= p.plane_batches) { ++pl; within -= (int32_t)p.plane_batches; }
     }
-    if (v < p.chunk && my < (uint32_t)p.n && (uint32_t)within * 64u + (v & 63u) < p.plane_n) {
+    // The slot is a ray of its plane, not the plane's padding.  A kernel compiled for its answer has that settled before the
+    // other two tests; a kernel that asks the launch tests it last.  (The place decides the order of hipcc's instructions.)
+    const auto in_plane = [&] { return (uint32_t)within * 64u + (v & 63u) < p.plane_n; };
+    const bool settled = PM == PLANES_NONE || (PM == PLANES_ALL && in_plane());
+    if (v < p.chunk && my < (uint32_t)p.n && (PM == PLANES_ASK ? in_plane() : settled)) {
         const float4 rec = p.rays[my];
+        float2 o = make_float2(0.f, 0.f);
+        if constexpr (LaneT::OWN_XZ) o = oxz[my];
         // y = RN32(1/d) (rcp_exact: exact for 2^-64 <= |d| < 2^64; other lanes are `spec`
         // and never use y); flavour 2: y = v_rcp_f32(d), used by every lane
         set_in_place(L.px, rec.x, FL == 2 ? rcp_raw(rec.x) : rcp_exact(rec.x));
         set_in_place(L.py, rec.y, FL == 2 ? rcp_raw(rec.y) : rcp_exact(rec.y));
         set_in_place(L.pz, rec.z, FL == 2 ? rcp_raw(rec.z) : rcp_exact(rec.z));
         set_in_place(L.po, rec.w, 1e30f);       // generate.cl:34-35
+        if constexpr (LaneT::OWN_XZ) set_in_place(L.oxz, o.x, o.y);
         set_in_place(L.triID, 0u);
         if (RECORD) { slot = my; live = true; }
         set_in_place(L.sp, 0);
         set_in_place(L.cur, root);
-        const bool spec = FL != 2 && (outside_proof_conditions(rec) || p.force_exact != 0);
+        // (an own x / z origin outside the window of the origin's y: uvrt_extend_free.hip's header)
+        bool outside = outside_proof_conditions(rec);
+        if constexpr (LaneT::OWN_XZ) outside = outside || origin_outside_window(o.x) || origin_outside_window(o.y);
+        const bool spec = FL != 2 && (outside || p.force_exact != 0);
         set_in_place(plane_off, pl * p.plane_stride | (spec ? SPECIAL6 : 0u));
     }
 }
@@ -308,8 +358,6 @@ inline unsigned size_persistent_grid(ExtendParams& p, int grid_per_cu)
     return (uint64_t)grid * 256 * (MAXS6 - PS6) > p.ovf_capacity ? 0u : grid;
 }
 
-// One traversal step of one lane (extend.cl:44-80): an inner node (both children tested, ordered,
-// descend / push / pop) or -- on a leaf trip -- a leaf (its triangles, pop).
 // Stack entries 8..31 of this thread live in global memory (0.02 % of pushes on the test room).  The
 // pointer is rebuilt from scratch where it is needed -- opaque to the compiler, which would otherwise
 // keep it in two VGPRs (or a scratch slot) across the whole loop.
@@ -343,6 +391,250 @@ __device__ __forceinline__ uint32_t lane_rank_in_exec()
 __device__ __forceinline__ uint32_t* ovf_ptr(const ExtendParams& p, uint32_t stack_base)
 {
     return p.ovf_stack + ((size_t)blockIdx.x * 256 + ((stack_base >> 2) & 255u)) * (MAXS6 - PS6);
+}
+
+// ---- the BVH2 traversal step of k_extend6 (Lane6) and k_extend_free (LaneF) ----
+// One traversal step of one lane (extend.cl:44-80): an inner node (both children tested, ordered,
+// descend / push / pop) or -- on a leaf trip -- a leaf (its triangles, pop).
+// The general step: any mix of lanes, stacks beyond LDS, and -- `exact`, wave-uniform -- the IEEE-division form of the box and
+// triangle arithmetic; the record fetch and the descend / push / pop logic are common to both forms.
+// A lane with its own x / z origin forms the x / z numerators b - o per ray, as every lane does for y (the same single f32
+// subtraction as extend.cl:31,35), and hands that origin to the triangle test.
+template <bool TOP, int FL, class LaneT>
+__device__ __forceinline__ void step6(LaneT& L, const ExtendParams& p, uint32_t stack_base,
+                                      const float4* s_top, uint32_t top_pairs, bool leaf_trip, bool exact,
+                                      unsigned long long m_act /* lanes holding a ray */)
+{
+    const uint32_t cur = L.cur;
+    const bool is_inner = cur < REF_LEAF_BIT;
+    const bool is_leaf = (cur >= REF_LEAF_BIT) & (cur != REF_DONE) & leaf_trip;
+    const uint32_t idx = cur & REF_FIRST_MASK;          // record index (inner indices are < 2^27 too)
+    // ONE asm block fetches the 64-byte record of every stepping lane -- from the LDS top-of-tree
+    // cache or from global memory, chosen by exec masks -- and the lane's stack top, so that both
+    // sources write the same registers (hipcc otherwise merges the two branches with v_mov chains).
+    v4f w0, w1, w2, w3;
+    uint32_t spec_top = REF_DONE;                       // stays REF_DONE when the stack is empty
+    // stack entry sp - 1 of this lane (lanes with sp == 0 are masked off); entry sp is 1024 bytes on
+    const uint32_t sa = stack_base + ((uint32_t)L.sp << 10);
+    {
+        // lane masks from single comparisons, combined as 64-bit integers (SALU): a ballot of a
+        // compound condition would go through a v_cndmask / v_cmp pair
+        const unsigned long long m_in = __builtin_amdgcn_ballot_w64(cur < REF_LEAF_BIT);
+        const unsigned long long m_top = TOP ? __builtin_amdgcn_ballot_w64(cur < top_pairs) : 0ull;
+        const unsigned long long m_sp = __builtin_amdgcn_ballot_w64(L.sp > 0);
+        const unsigned long long m_go = m_in | (leaf_trip ? (m_act & ~m_in) : 0ull);
+        const unsigned long long m_glob = m_go & ~m_top;
+        const unsigned long long m_stk = m_go & m_sp;
+        // LDS copy of record r at byte TOP6_STRIDE * r
+        const uint32_t a0 = (uint32_t)(uintptr_t)s_top + cur * TOP6_STRIDE;
+        // byte offset of the record: the shift drops the leaf flag and count bits of a reference
+        // (record indices are < 2^26: uvrt_capi.hip checks P + T), the base address is scalar
+        const uint32_t roff = cur << 6;
+        unsigned long long save;
+        asm volatile("s_mov_b64 %[save], exec\n\t"
+                     "s_mov_b64 exec, %[mstk]\n\t"
+                     "ds_read_b32 %[st], %[sa]\n\t"
+                     "s_mov_b64 exec, %[mtop]\n\t"
+                     "ds_read_b128 %[w0], %[a0]\n\t"
+                     "ds_read_b128 %[w1], %[a0] offset:16\n\t"
+                     "ds_read_b128 %[w2], %[a0] offset:32\n\t"
+                     "ds_read_b128 %[w3], %[a0] offset:48\n\t"
+                     "s_mov_b64 exec, %[mglob]\n\t"
+                     "global_load_dwordx4 %[w0], %[ro], %[rb]\n\t"
+                     "global_load_dwordx4 %[w1], %[ro], %[rb] offset:16\n\t"
+                     "global_load_dwordx4 %[w2], %[ro], %[rb] offset:32\n\t"
+                     "global_load_dwordx4 %[w3], %[ro], %[rb] offset:48\n\t"
+                     "s_mov_b64 exec, %[save]\n\t"
+                     "s_waitcnt vmcnt(0) lgkmcnt(0)"
+                     : [w0] "=&v"(w0), [w1] "=&v"(w1), [w2] "=&v"(w2), [w3] "=&v"(w3), [st] "+v"(spec_top),
+                       [save] "=&s"(save)
+                     : [a0] "v"(a0), [sa] "v"(sa), [ro] "v"(roff), [rb] "s"(p.recs),
+                       [mtop] "s"(m_top), [mglob] "s"(m_glob), [mstk] "s"(m_stk)
+                     : "memory");
+    }
+    bool need_pop = is_leaf;
+    if (is_inner) {
+        float d0, d1;
+        bool h0, h1;
+        // the x / z numerators of the forms that take scalars: the record's value (already b - o), or b - the lane's own origin
+        const auto ax = [&](float b) { return LaneT::OWN_XZ ? b - origin_x(L, p) : b; };
+        const auto az = [&](float b) { return LaneT::OWN_XZ ? b - origin_z(L, p) : b; };
+        if (FL == 2) {        // "shipped flags": t = (b - o) * v_rcp_f32(d) for every lane (there is no other form of it)
+            h0 = box_shipped(ax(w0.x), ax(w0.y), w2.x - L.po.x, w2.y - L.po.x, az(w0.z), az(w0.w), L.px.y, L.py.y, L.pz.y, L.po.y, d0);
+            h1 = box_shipped(ax(w1.x), ax(w1.y), w2.z - L.po.x, w2.w - L.po.x, az(w1.z), az(w1.w), L.px.y, L.py.y, L.pz.y, L.po.y, d1);
+        } else if (exact) {
+            h0 = box_exact(ax(w0.x), ax(w0.y), w2.x - L.po.x, w2.y - L.po.x, az(w0.z), az(w0.w), L.px.x, L.py.x, L.pz.x, L.po.y, d0);
+            h1 = box_exact(ax(w1.x), ax(w1.y), w2.z - L.po.x, w2.w - L.po.x, az(w1.z), az(w1.w), L.px.x, L.py.x, L.pz.x, L.po.y, d1);
+        } else {
+            v2f x0 = __builtin_shufflevector(w0, w0, 0, 1), z0 = __builtin_shufflevector(w0, w0, 2, 3);
+            v2f x1 = __builtin_shufflevector(w1, w1, 0, 1), z1 = __builtin_shufflevector(w1, w1, 2, 3);
+            v2f y0 = __builtin_shufflevector(w2, w2, 0, 1), y1 = __builtin_shufflevector(w2, w2, 2, 3);
+            if constexpr (LaneT::OWN_XZ) sub_xz(x0, z0, x1, z1, L.oxz);
+            slabs6(x0, y0, z0, L.px, L.py, L.pz, L.po);
+            h0 = box_fast(x0, y0, z0, L.po.y, d0);
+            slabs6(x1, y1, z1, L.px, L.py, L.pz, L.po);
+            h1 = box_fast(x1, y1, z1, L.po.y, d1);
+        }
+        // extend.cl:56-76 with dist = 1e30f for a missed child: nearer first, farther pushed
+        // dist1 > dist2 of extend.cl:61 with 1e30f standing for a miss: child 1 first iff it is hit and
+        // child 0 is missed or farther (a hit distance is < dist <= 1e30f, so the sentinel never ties)
+        const bool sw = h1 & (!h0 | (d0 > d1));
+        const uint32_t r0 = __float_as_uint(w3.x), r1 = __float_as_uint(w3.y);
+        const uint32_t nearer = sw ? r1 : r0, farther = sw ? r0 : r1;
+        if (h0 & h1) {
+            if (L.sp < PS6) asm volatile("ds_write_b32 %0, %1 offset:1024" : : "v"(sa), "v"(farther) : "memory");
+            else if (L.sp < MAXS6) ovf_ptr(p, stack_base)[L.sp - PS6] = farther;
+            else *p.error_flag = 1u;
+            L.sp = L.sp < MAXS6 ? L.sp + 1 : L.sp;
+        }
+        need_pop = !(h0 | h1);
+        L.cur = nearer;
+    }
+    // extend.cl:48-55 -- AFTER the inner-node block (other lanes): the triangles of a leaf with several of them
+    // are fetched when the node records' registers are free again
+    if (is_leaf) {
+        uint32_t count = (cur >> REF_COUNT_SHIFT) & 15u;
+        const uint32_t first = idx - (uint32_t)p.npairs;
+        if (count == 15u) count = p.scene.leaf_count[first];
+        float dist = L.po.y;
+        tri6<FL>(origin_x(L, p), L.po.x, origin_z(L, p), L.px.x, L.py.x, L.pz.x, dist, L.triID,
+             make_float4(w0.x, w0.y, w0.z, w0.w), make_float4(w1.x, w1.y, w1.z, w1.w),
+             make_float4(w2.x, w2.y, w2.z, w2.w), exact);
+        for (uint32_t i = 1; i < count; ++i) {
+            const float4* lt = (const float4*)p.recs + ((size_t)idx + i) * 4;
+            tri6<FL>(origin_x(L, p), L.po.x, origin_z(L, p), L.px.x, L.py.x, L.pz.x, dist, L.triID, lt[0], lt[1], lt[2], exact);
+        }
+        L.po.y = dist;
+    }
+    if (need_pop) {
+        uint32_t popped = spec_top;                        // REF_DONE when the stack is empty
+        if (L.sp > PS6) popped = ovf_ptr(p, stack_base)[L.sp - 1 - PS6];
+        L.cur = popped;
+        L.sp = (int)__builtin_elementwise_sub_sat((uint32_t)L.sp, 1u);
+    }
+}
+
+// The same step for the common case -- no lane needs the IEEE-division form, no lane's stack has left LDS -- with
+// the control flow written as lane masks instead of divergent branches.  Scalar issue is the dearest resource of
+// this kernel (one instruction per cycle per CU, shared by 32 waves: 32 extra scalar instructions per trip cost
+// 17 % of the launch, profiles/r02/r02_experiments.txt), and hipcc spends ~70 of them per trip on exec bookkeeping
+// for `if (inner) {...} if (both hit) {push} if (none hit) {pop}`.  Here the caller hands over the lane masks of
+// the trip (one vector comparison each), the box arithmetic runs for ALL lanes (a vector instruction costs the
+// same whatever its exec mask; lanes that do not stand at an inner node compute on stale registers and are
+// masked out of the results), the hit tests narrow exec themselves (v_cmpx), and descend / push / pop are
+// exec-masked instructions of one asm block.
+//   m_in: lanes at an inner node, m_leaf: lanes that visit their leaf in this trip, m_top: lanes whose record is
+//   in the LDS cache, full: the exec mask of the loop (all 64 lanes), clk: takes the cycles of the trip's three parts in a
+//   build that asks where they go (k_extend6's TripClock under UVRT_TRIP_STATS); by default there is none.  (`if constexpr`,
+//   not an empty member function: a call that is inlined away later still changes the order of hipcc's instructions)
+struct NoClock {
+    static constexpr bool RUNS = false;
+};
+template <bool TOP, int FL, class LaneT, class ClockT = NoClock>
+__device__ __forceinline__ void step7(LaneT& L, const ExtendParams& p, uint32_t stack_base, uint32_t top_base,
+                                      unsigned long long m_in, unsigned long long m_leaf, unsigned long long m_top,
+                                      unsigned long long full, ClockT clk = ClockT())
+{
+    const uint32_t cur = L.cur;
+    v4f w0, w1, w2, w3;
+    uint32_t spec_top;
+    if constexpr (ClockT::RUNS) clk.start();
+    const uint32_t sa = stack_base + ((uint32_t)L.sp << 10);
+    {
+        const unsigned long long m_glob = (m_in | m_leaf) & ~m_top;
+        const uint32_t a0 = __umul24(cur, TOP6_STRIDE) + top_base;      // only used by lanes in m_top
+        const uint32_t roff = cur << 6;
+        // the stack top is read by every lane: entry -1 of a lane's LDS stack is a row that always holds REF_DONE
+        asm volatile("ds_read_b32 %[st], %[sa]\n\t"
+                     "s_mov_b64 exec, %[mtop]\n\t"
+                     "ds_read_b128 %[w0], %[a0]\n\t"
+                     "ds_read_b128 %[w1], %[a0] offset:16\n\t"
+                     "ds_read_b128 %[w2], %[a0] offset:32\n\t"
+                     "ds_read_b128 %[w3], %[a0] offset:48\n\t"
+                     "s_mov_b64 exec, %[mglob]\n\t"
+                     "global_load_dwordx4 %[w0], %[ro], %[rb]\n\t"
+                     "global_load_dwordx4 %[w1], %[ro], %[rb] offset:16\n\t"
+                     "global_load_dwordx4 %[w2], %[ro], %[rb] offset:32\n\t"
+                     "global_load_dwordx4 %[w3], %[ro], %[rb] offset:48\n\t"
+                     "s_mov_b64 exec, %[full]\n\t"
+                     "s_waitcnt vmcnt(0) lgkmcnt(0)"
+                     : [w0] "=&v"(w0), [w1] "=&v"(w1), [w2] "=&v"(w2), [w3] "=&v"(w3), [st] "=&v"(spec_top)
+                     : [a0] "v"(a0), [sa] "v"(sa), [ro] "v"(roff), [rb] "s"(p.recs), [mtop] "s"(m_top), [mglob] "s"(m_glob),
+                       [full] "s"(full)
+                     : "memory");
+    }
+    if constexpr (ClockT::RUNS) clk.lap(0);
+    if (m_leaf != 0) {                                       // wave-uniform; m_leaf != 0 means: a leaf trip
+        if ((int32_t)cur < -1) {                             // at a leaf (REF_DONE is -1): extend.cl:48-55
+            const uint32_t idx = cur & REF_FIRST_MASK;
+            uint32_t count = (cur >> REF_COUNT_SHIFT) & 15u;
+            const uint32_t first = idx - (uint32_t)p.npairs;
+            if (count == 15u) count = p.scene.leaf_count[first];
+            float dist = L.po.y;
+            tri6<FL>(origin_x(L, p), L.po.x, origin_z(L, p), L.px.x, L.py.x, L.pz.x, dist, L.triID,
+                      make_float4(w0.x, w0.y, w0.z, w0.w), make_float4(w1.x, w1.y, w1.z, w1.w),
+                      make_float4(w2.x, w2.y, w2.z, w2.w), false);
+            for (uint32_t i = 1; i < count; ++i) {
+                const float4* lt = (const float4*)p.recs + ((size_t)idx + i) * 4;
+                tri6<FL>(origin_x(L, p), L.po.x, origin_z(L, p), L.px.x, L.py.x, L.pz.x, dist, L.triID, lt[0], lt[1], lt[2], false);
+            }
+            L.po.y = dist;
+        }
+    }
+    if constexpr (ClockT::RUNS) clk.lap(1);
+    if (m_in != 0) {            // wave-uniform: a trip with no lane at an inner node skips the box arithmetic
+        v2f x0 = __builtin_shufflevector(w0, w0, 0, 1), z0 = __builtin_shufflevector(w0, w0, 2, 3);
+        v2f x1 = __builtin_shufflevector(w1, w1, 0, 1), z1 = __builtin_shufflevector(w1, w1, 2, 3);
+        v2f y0 = __builtin_shufflevector(w2, w2, 0, 1), y1 = __builtin_shufflevector(w2, w2, 2, 3);
+        if constexpr (LaneT::OWN_XZ) sub_xz(x0, z0, x1, z1, L.oxz);
+        if (FL == 2) {
+            slabs6s(x0, y0, z0, L.px, L.py, L.pz, L.po);
+            slabs6s(x1, y1, z1, L.px, L.py, L.pz, L.po);
+        } else {
+            slabs6(x0, y0, z0, L.px, L.py, L.pz, L.po);
+            slabs6(x1, y1, z1, L.px, L.py, L.pz, L.po);
+        }
+        float n0, f0, n1, f1;
+        box2_fast(x0, y0, z0, x1, y1, z1, n0, f0, n1, f1);
+        // extend.cl:36-38,56-76: hit = tmax >= tmin && tmin < dist && tmax > 0 per child; child 1 first iff it is hit
+        // and child 0 is missed or farther; both hit: the farther one is pushed; none hit (or a leaf visited): pop
+        unsigned long long h0, h1, t;
+        asm volatile("s_mov_b64 exec, %[min]\n\t"
+                     "v_cmpx_ge_f32_e64 %[h0], %[f0], %[n0]\n\t"
+                     "v_cmpx_lt_f32_e64 %[h0], %[n0], %[dist]\n\t"
+                     "v_cmpx_gt_f32_e64 %[h0], %[f0], 0\n\t"            // h0 = exec = inner lanes whose child 0 is hit
+                     "s_mov_b64 exec, %[min]\n\t"
+                     "v_cmpx_ge_f32_e64 %[h1], %[f1], %[n1]\n\t"
+                     "v_cmpx_lt_f32_e64 %[h1], %[n1], %[dist]\n\t"
+                     "v_cmpx_gt_f32_e64 %[h1], %[f1], 0\n\t"            // h1 likewise
+                     "v_cmp_gt_f32 vcc, %[n0], %[n1]\n\t"               // (under exec = h1)
+                     "s_andn2_b64 %[t], %[h1], %[h0]\n\t"
+                     "s_or_b64 %[t], %[t], vcc\n\t"                     // t = child 1 first
+                     "s_and_b64 exec, %[h0], %[h1]\n\t"                 // both hit: push the farther, sp + 1
+                     "v_cndmask_b32 %[n1], %[r1], %[r0], %[t]\n\t"
+                     "ds_write_b32 %[sa], %[n1] offset:1024\n\t"
+                     "v_add_u32 %[sp], 1, %[sp]\n\t"
+                     "s_or_b64 exec, %[h0], %[h1]\n\t"                  // any hit: descend into the nearer
+                     "v_cndmask_b32 %[cur], %[r0], %[r1], %[t]\n\t"
+                     "s_andn2_b64 %[t], %[min], exec\n\t"
+                     "s_or_b64 exec, %[t], %[mleaf]\n\t"                // none hit, or a leaf was visited: pop
+                     "v_mov_b32 %[cur], %[st]\n\t"
+                     "v_sub_u32 %[sp], %[sp], 1 clamp\n\t"
+                     "s_mov_b64 exec, %[full]"
+                     : [n1] "+v"(n1), [cur] "+v"(L.cur), [sp] "+v"(L.sp), [h0] "=&s"(h0), [h1] "=&s"(h1), [t] "=&s"(t)
+                     : [n0] "v"(n0), [f0] "v"(f0), [f1] "v"(f1), [dist] "v"(L.po.y), [r0] "v"(w3.x), [r1] "v"(w3.y), [sa] "v"(sa),
+                       [st] "v"(spec_top), [min] "s"(m_in), [mleaf] "s"(m_leaf), [full] "s"(full)
+                     : "vcc", "memory");
+    } else {
+        // only leaves were visited: pop them
+        asm volatile("s_mov_b64 exec, %[mleaf]\n\t"
+                     "v_mov_b32 %[cur], %[st]\n\t"
+                     "v_sub_u32 %[sp], %[sp], 1 clamp\n\t"
+                     "s_mov_b64 exec, %[full]"
+                     : [cur] "+v"(L.cur), [sp] "+v"(L.sp)
+                     : [st] "v"(spec_top), [mleaf] "s"(m_leaf), [full] "s"(full));
+    }
+    if constexpr (ClockT::RUNS) clk.lap(2);
 }
 
 }  // namespace uvrt

@@ -4,9 +4,7 @@
 
 Extracts the gfx950 code objects from the .hip_fatbin section of both libraries (one uncompressed offload bundle per
 translation unit), disassembles them with llvm-objdump -d and compares every kernel's instruction sequence (addresses,
-encodings and comments dropped).  One line per kernel: identical / DIFFERENT / NEW / GONE and its instruction count.
-k_extend_free<RECORD, FL, false> is compared with the k_extend_free<RECORD, FL> of a build from before the third
-template parameter."""
+encodings and comments dropped).  One line per kernel: identical / DIFFERENT / NEW / GONE and its instruction count."""
 import subprocess, sys, re, os, struct, tempfile
 LLVM = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'llvm', 'bin') + os.sep
 MAGIC=b'__CLANG_OFFLOAD_BUNDLE__'
@@ -41,8 +39,6 @@ def kernels(lib):
                 if ins!='...': ks[cur].append(ins)
     return ks
 a=kernels(sys.argv[1]); b=kernels(sys.argv[2])
-# k_extend_free<RECORD, FL> gained a third parameter: <RECORD, FL, false> is the old instantiation
-b={n.replace('ELb0EEEvNS_10FreeParamsE','EEEvNS_10FreeParamsE') if n.startswith('_ZN4uvrt13k_extend_free') else n:v for n,v in b.items()}
 dem=lambda n: subprocess.run(['c++filt',n],capture_output=True,text=True).stdout.strip()
 for n in sorted(set(a)|set(b)):
     if n.endswith('.kd') or n.startswith('__'): continue
