@@ -156,6 +156,49 @@ uint32_t uvrt_seed_next_sweep(const float from[3], float light_length, uint32_t 
  * SEED is untouched. */
 int uvrt_write_free_rays(uvrt_ctx* ctx, const void* rays32, int64_t n);
 
+/* ---- shadow rays and the direct gather ----
+ * A photon count does not reach the dim triangles: half the test room receives no photon of 2^21.  The gather turns the
+ * question round -- stand on each triangle and ask how much of the lamp it sees -- and needs an occlusion query for it: a ray
+ * with a maximum distance that stops at its first hit.  The shadow-ray kernel is the free-origin traversal with dist preset
+ * to tmax, ended by the first accepted hit: exactly what extend.cl answers for a ray whose `dist` is preset (flavours 0 and 1;
+ * flavour 2 is refused).  Every call below runs on the context's stream behind all outstanding launches, leaves SEED and
+ * tempPhotonMap untouched and drops "the last generate": uvrt_extend / uvrt_read_rays before the next generate return
+ * UVRT_ERR_INVALID.  The arrays and the scene's free records are allocated on first use.
+ *
+ * uvrt_gather_direct, for triangle t (index into tris64) of [first_tri, first_tri + tri_count) and sample s < S, j = t*S + s:
+ *     rng = WangHash(j ^ WangHash(seed));  u_h, u_m, a, b = RandomFloat(&rng) x 4       (cl/tools.cl:2-4)
+ *     if (a + b > 1) { a = 1 - a; b = 1 - b; }      p = (v0 + a*e1) + b*e2,  e1 = v1 - v0, e2 = v2 - v0        (f32)
+ *     o = uvrt_generate_sweep's origin with r1 := u_h and u := u_m  (from == to: a stop)
+ *     d = p - o,  r = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z),  dir = d / r,  tmax = r * (1 - 2^-10)
+ * (the factor keeps the target triangle from shadowing itself; a sample with r not finite or not > 0 is not traced and weighs
+ * 0).  The weight, in f64: n = cross(e1, e2), nn = |n|, D = (double)d, R2 = D.D, R = sqrt(R2),
+ *     w = |n.D| / (nn * (R2*R) * 12.566370614359172)
+ * and expected[t] = (double)photons_equiv * (0.5*nn) * (sum_s (occluded ? 0 : w) / (double)S), 0 where nn == 0: the expected
+ * tempPhotonMap entry of a launch of photons_equiv photons.  Every operator one rounding, the sum in sample order, no
+ * atomics: a pure function of the arguments, whatever the capacity (triangles go in chunks of floor(capacity / S)) or the
+ * split into ranges.  A triangle that no BVH leaf holds has no estimate (0), as it has no photon.
+ * UVRT_ERR_INVALID with nothing changed: flavour 2, no scene, a range outside [0, T], a limit of the struct, a null argument. */
+/* test / interop hook: n 32-byte Ray records, rec.dist = tmax; out[i] = 1 when some triangle is hit with
+ * 0.0001f < t < tmax.  Uploads, traces, reads back; synchronises.  n <= capacity. */
+int uvrt_occluded(uvrt_ctx* ctx, const void* rays32, int64_t n, uint8_t* out);
+typedef struct {
+    float from[3], to[3];    /* from == to: a stop */
+    float light_length;
+    int32_t samples;         /* S in [1, 4096]; S <= capacity; T*S < 2^31 */
+    uint32_t seed;
+    int32_t photons_equiv;   /* N > 0: Shade's divisor for maps fed by this plane */
+    int32_t reserved[2];
+} uvrt_gather_params;
+/* writes expected[first_tri .. first_tri + tri_count) */
+int uvrt_gather_direct(uvrt_ctx* ctx, const uvrt_gather_params* params, int32_t first_tri, int32_t tri_count);
+/* cl/accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]: photonMap += expected * (double)timeStep,
+ * maxPhotonMap = max(maxPhotonMap, expected), then expected = 0.  An accumulate that uvrt_accumulate has deferred is
+ * completed first, so the maps see launch order; uvrt_shade / uvrt_compute_dosage then work unchanged with
+ * photons_per_light = photons_equiv, and one map may mix photon launches and gather launches. */
+int uvrt_accumulate_expected(uvrt_ctx* ctx, float time_step, int32_t tri_count);
+/* the expected plane, any range; synchronises.  uvrt_set_scene zeroes the plane. */
+int uvrt_read_expected(uvrt_ctx* ctx, double* out, int32_t first, int32_t count);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).
@@ -394,7 +437,8 @@ int uvrt_read_photon_map(uvrt_ctx* ctx, int32_t which_map, double* out, int32_t 
 /* raw device pointers of the per-triangle arrays, for zero-copy wrapping (e.g. as torch
  * tensors handed to an RCCL collective).  which: 0 photonMap f64[T], 1 maxPhotonMap f64[T],
  * 2 tempPhotonMap i32[T], 3 dosageMap f32[T], 4 colour f32[9T], 5 the folded planes i32[launches][T] of the
- * traced batch (for a caller that brings its own collective; uvrt_reduce_batch is the native one).
+ * traced batch (for a caller that brings its own collective; uvrt_reduce_batch is the native one), 6 the direct gather's
+ * expected plane f64[T].
  * The call is also the ordering point for external work on these arrays: it orders the context's
  * stream after every outstanding launch (with launch pipelining some sit on the library's second
  * stream) and makes the library's next work on the arrays wait for whatever the caller enqueues on

@@ -75,6 +75,10 @@ SYMBOLS = [
     ("uvrt_write_free_rays", C.c_int, [_vp, _vp, _i64]),
     ("uvrt_generate_sweep", C.c_int, [_vp, _fp, _fp, _f32, _i64, _i64]),
     ("uvrt_seed_next_sweep", _u32, [_fp, _f32, _u32]),
+    ("uvrt_occluded", C.c_int, [_vp, _vp, _i64, _vp]),
+    ("uvrt_gather_direct", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_accumulate_expected", C.c_int, [_vp, _f32, _i32]),
+    ("uvrt_read_expected", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_read_counts", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_read_photon_map", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_device_ptr", C.c_int, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
@@ -98,6 +102,12 @@ SYMBOLS = [
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
+
+
+class GatherParams(C.Structure):
+    """uvrt_gather_params (include/uvrt.h)"""
+    _fields_ = [("from_", C.c_float * 3), ("to", C.c_float * 3), ("light_length", C.c_float), ("samples", C.c_int32),
+                ("seed", C.c_uint32), ("photons_equiv", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class PlanParams(C.Structure):
@@ -356,6 +366,36 @@ class Ctx:
         """generate for a lamp that moves from `frm` to `to` while it radiates"""
         self._ck(self._L.uvrt_generate_sweep(self._h, _f3(frm), _f3(to), float(np.float32(light_length)),
                                              int(first_gid), int(n)))
+
+    # ---- shadow rays and the direct gather ----
+    def occluded(self, rays):
+        """uint8[n]: 1 where some triangle is hit with 0.0001f < t < rays["dist"] (the ray's tmax)"""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DT)
+        out = np.zeros(rays.size, dtype=np.uint8)
+        self._ck(self._L.uvrt_occluded(self._h, _ptr(rays), rays.size, _ptr(out)))
+        return out
+
+    def gather_direct(self, frm, to, light_length, samples, seed, photons_equiv, first_tri=0, tri_count=None):
+        """expected[first_tri, +tri_count) = the expected tempPhotonMap entries of a launch of photons_equiv photons"""
+        prm = GatherParams()
+        prm.from_ = _f3(frm)
+        prm.to = _f3(to)
+        prm.light_length = float(np.float32(light_length))
+        prm.samples = int(samples)
+        prm.seed = int(seed)
+        prm.photons_equiv = int(photons_equiv)
+        self._ck(self._L.uvrt_gather_direct(self._h, C.byref(prm), int(first_tri),
+                                            self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    def accumulate_expected(self, time_step, tri_count=None):
+        self._ck(self._L.uvrt_accumulate_expected(self._h, float(np.float32(time_step)),
+                                                  self.T if tri_count is None else int(tri_count)))
+
+    def read_expected(self, first=0, count=None):
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float64)
+        self._ck(self._L.uvrt_read_expected(self._h, _ptr(out), int(first), int(count)))
+        return out
 
     @property
     def seed(self):

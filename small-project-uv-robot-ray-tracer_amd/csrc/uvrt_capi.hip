@@ -149,6 +149,7 @@ void uvrt_destroy(uvrt_ctx* c)
     if (c->ev_mapfence) (void)hipEventDestroy(c->ev_mapfence);
     c->quads.release();
     c->free_recs.release();
+    for (DevBuf* b : {&c->g_oxz, &c->g_tmax, &c->g_occ, &c->g_w, &c->g_tris, &c->expected}) b->release();
     for (DevBuf& b : c->b_recs) b.release();
     (void)hot_reset(c, false);            // (and the lanes' set-up scratch)
     for (auto& bset : c->bs) {
@@ -387,6 +388,9 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     c->have_scene = true;
     c->free_recs.release();                           // sized per scene; rebuilt by the next free launch
     c->free_recs_valid = false;
+    c->g_tris.release();                              // the gather's triangles and its plane: per scene, back (zeroed) on next use
+    c->g_tris_valid = false;
+    c->expected.release();
     c->scene_force_exact = tiny_bound || huge_vertex;
     if ((rc = hot_reset(c, true))) return rc;         // statistics of the previous scene; the new scene's first slab
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -732,7 +736,11 @@ int uvrt_device_ptr(uvrt_ctx* c, int32_t which, void** ptr, int64_t* bytes)
             if (int rc = uvrt_fold_batch(c)) return rc;
             b = &c->bs[c->b_set].folded; elem = 4 * (size_t)c->b_count;
             break;
-        default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..5");
+        case 6:
+            if (int rc = ensure_expected(c)) return rc;
+            b = &c->expected; elem = 8;
+            break;
+        default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..6");
     }
     *ptr = b->p;
     *bytes = (int64_t)((size_t)c->T * elem);

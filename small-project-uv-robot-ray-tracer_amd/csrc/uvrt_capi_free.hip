@@ -7,12 +7,10 @@ using namespace uvrt_impl;
 
 namespace uvrt_impl {
 
-// The scene's free records (made once per scene, on the first free launch) and the current lane's {orig.x, orig.z} array
-// (made on the lane's first free launch): callers that never trace free rays pay for neither.
-static int ensure_free_buffers(uvrt_ctx* c, hipStream_t ls)
+// The scene's free records, made once per scene by the first launch that needs them (a free launch, a shadow-ray launch):
+// callers that never trace such rays do not pay for them.
+int ensure_free_records(uvrt_ctx* c)
 {
-    Lane& L = cur_lane(c);
-    if (int rc = L.oxz.ensure((size_t)std::max<int64_t>(c->capacity, 1) * 8, false, ls)) return rc;
     if (!c->free_recs_valid) {
         // on the context's stream, behind everything outstanding; the lanes' later work waits for it (mark_fence)
         if (int rc = join_all(c)) return rc;
@@ -23,6 +21,14 @@ static int ensure_free_buffers(uvrt_ctx* c, hipStream_t ls)
         c->free_recs_valid = true;
     }
     return UVRT_OK;
+}
+
+// ... and the current lane's {orig.x, orig.z} array, made on the lane's first free launch
+static int ensure_free_buffers(uvrt_ctx* c, hipStream_t ls)
+{
+    Lane& L = cur_lane(c);
+    if (int rc = L.oxz.ensure((size_t)std::max<int64_t>(c->capacity, 1) * 8, false, ls)) return rc;
+    return ensure_free_records(c);
 }
 
 int extend_free(uvrt_ctx* c, int64_t n)

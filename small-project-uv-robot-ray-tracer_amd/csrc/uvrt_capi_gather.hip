@@ -1,0 +1,178 @@
+// uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
+// uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected (uvrt_occlude.hip's kernels)
+#include "uvrt_ctx.h"
+
+using namespace uvrt;
+using namespace uvrt_impl;
+
+namespace uvrt_impl {
+
+int ensure_expected(uvrt_ctx* c)
+{
+    if (c->expected.p) return UVRT_OK;
+    if (int rc = c->expected.ensure((size_t)c->T * 8, true, c->stream)) return rc;
+    return UVRT_OK;
+}
+
+// Everything a shadow-ray launch works on, on the context's stream behind all outstanding work: lane 0's ray buffer, the
+// scene's free records, every ray's {orig.x, orig.z}, tmax and answer.  The rays of "the last generate" are gone after it; the
+// launch lane of the last generate stays the current one, so its deposits (tempPhotonMap) are still what uvrt_accumulate,
+// uvrt_read_counts and uvrt_device_ptr see.
+static int begin_shadow_launch(uvrt_ctx* c)
+{
+    if (int rc = join_all(c)) return rc;
+    c->last_n = -1;                         // lane 0's rays are about to be overwritten
+    c->last_extended = false;
+    c->last_free = false;
+    if (int rc = ensure_free_records(c)) return rc;
+    const size_t cap = (size_t)std::max<int64_t>(c->capacity, 1);
+    if (int rc = c->g_oxz.ensure(cap * 8, false, c->stream)) return rc;
+    if (int rc = c->g_tmax.ensure(cap * 4, false, c->stream)) return rc;
+    if (int rc = c->g_occ.ensure(cap, false, c->stream)) return rc;
+    return UVRT_OK;
+}
+
+// k_occlude_free over the first n rays of lane 0 (rays, oxz, g_tmax -> g_occ) on the context's stream
+static int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who)
+{
+    Lane& L = c->lanes[0];
+    OccludeParams op;
+    fill_launch(c, op.e, 0.0f, 0.0f);       // (force_exact: the scene's and the variant's conditions; the origins are per ray)
+    op.e.ovf_stack = L.ovf.as<uint32_t>();  // lane 0's, like its rays: this launch runs on the context's stream
+    op.e.ovf_capacity = L.ovf.bytes / sizeof(uint32_t);
+    op.e.num_cus = c->num_cus;
+    op.e.rays = L.rays.as<float4>();
+    op.oxz = c->g_oxz.as<float2>();
+    op.tmax = c->g_tmax.as<float>();
+    op.occluded = c->g_occ.as<uint8_t>();
+    op.e.n = n;
+    op.e.recs = c->free_recs.p;
+    hipEvent_t e1;
+    if (int rc = timing_start(c, c->stream, &e1)) return rc;
+    if (!launch_occlude_free(op, variant_per_cu(c->variant, 8), c->stream))
+        return fail(UVRT_ERR_INVALID, "%s: the shadow-ray launch needs a larger overflow-stack buffer than the context holds", who);
+    HIP_TRY(hipGetLastError());
+    if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
+    return UVRT_OK;
+}
+
+}  // namespace uvrt_impl
+
+extern "C" {
+
+int uvrt_occluded(uvrt_ctx* c, const void* rays32, int64_t n, uint8_t* out)
+{
+    if (!c || !rays32 || !out) return fail(UVRT_ERR_INVALID, "uvrt_occluded: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_occluded: no scene");
+    if (c->flavour != 0 && c->flavour != 1)
+        return fail(UVRT_ERR_INVALID, "uvrt_occluded: shadow rays are traced in flavours 0 and 1 only (uvrt_set_flavour %d)", c->flavour);
+    if (n < 0 || n > c->capacity)
+        return fail(UVRT_ERR_INVALID, "uvrt_occluded: n = %lld exceeds the ray capacity %lld (uvrt_resize_rays)", (long long)n,
+                    (long long)c->capacity);
+    if (n == 0) return UVRT_OK;
+    if (int rc = set_device(c)) return rc;
+    struct HostRay { float d[3], o[3], dist; uint32_t tri; };
+    const HostRay* hr = (const HostRay*)rays32;
+    std::vector<float> packed((size_t)n * 4), oxz((size_t)n * 2), tmax((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        packed[4 * i + 0] = hr[i].d[0]; packed[4 * i + 1] = hr[i].d[1];
+        packed[4 * i + 2] = hr[i].d[2]; packed[4 * i + 3] = hr[i].o[1];
+        oxz[2 * i + 0] = hr[i].o[0]; oxz[2 * i + 1] = hr[i].o[2];
+        tmax[i] = hr[i].dist;
+    }
+    if (int rc = begin_shadow_launch(c)) return rc;
+    Lane& L = c->lanes[0];
+    HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->g_oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->g_tmax.p, tmax.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (int rc = trace_shadow_rays(c, n, "uvrt_occluded")) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->g_occ.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first_tri, int32_t tri_count)
+{
+    if (!c || !prm) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: no scene");
+    if (c->flavour != 0 && c->flavour != 1)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: shadow rays are traced in flavours 0 and 1 only (uvrt_set_flavour %d)", c->flavour);
+    if (first_tri < 0 || tri_count < 0 || (int64_t)first_tri + tri_count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: triangles [%d, +%d) outside [0, %d]", first_tri, tri_count, c->T);
+    const int32_t S = prm->samples;
+    if (S < 1 || S > 4096) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: samples = %d must be in [1, 4096]", S);
+    if ((int64_t)S > c->capacity)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: samples = %d exceed the ray capacity %lld (uvrt_resize_rays)", S, (long long)c->capacity);
+    if ((int64_t)c->T * S >= ((int64_t)1 << 31))
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: %d triangles x %d samples do not fit 2^31 sample numbers", c->T, S);
+    if (prm->photons_equiv <= 0) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: photons_equiv must be > 0");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = begin_shadow_launch(c)) return rc;
+    const size_t cap = (size_t)c->capacity;
+    if (int rc = c->g_w.ensure(cap * 8, false, c->stream)) return rc;
+    if (int rc = ensure_expected(c)) return rc;
+    if (!c->g_tris_valid) {
+        if (int rc = c->g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
+        launch_gather_tris(c->ltris.as<LeafTri>(), c->g_tris.as<float4>(), c->T, c->stream);
+        HIP_TRY(hipGetLastError());
+        c->g_tris_valid = true;
+    }
+    Lane& L = c->lanes[0];
+    GatherGenParams g;
+    memset(&g, 0, sizeof g);
+    g.gtris = c->g_tris.as<float4>();
+    g.rays = L.rays.as<float4>();
+    g.oxz = c->g_oxz.as<float2>();
+    g.tmax = c->g_tmax.as<float>();
+    g.w = c->g_w.as<double>();
+    g.fx = prm->from[0]; g.fy = prm->from[1]; g.fz = prm->from[2];
+    g.tx = prm->to[0]; g.ty = prm->to[1]; g.tz = prm->to[2];
+    g.light_length = prm->light_length;
+    g.seed_hash = host_wang_hash(prm->seed);
+    g.samples = S;
+    // chunks of floor(capacity / S) triangles: a triangle's samples never straddle two of them, so the chunking shows in no bit
+    const int32_t per_chunk = (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX);
+    for (int32_t done = 0; done < tri_count; done += per_chunk) {
+        const int32_t cnt = std::min(per_chunk, tri_count - done);
+        g.first_tri = first_tri + done;
+        g.tri_count = cnt;
+        launch_gather_generate(g, c->stream);
+        HIP_TRY(hipGetLastError());
+        if (int rc = trace_shadow_rays(c, (int64_t)cnt * S, "uvrt_gather_direct")) return rc;
+        launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->expected.as<double>(), g.first_tri, cnt, S,
+                             prm->photons_equiv, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return UVRT_OK;
+}
+
+int uvrt_accumulate_expected(uvrt_ctx* c, float time_step, int32_t tri_count)
+{
+    if (!c || !c->have_scene || tri_count < 0 || tri_count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_accumulate_expected: bad tri_count");
+    if (int rc = set_device(c)) return rc;       // (an accumulate that uvrt_accumulate has deferred goes first: launch order)
+    if (int rc = join_all(c)) return rc;
+    if (int rc = ensure_expected(c)) return rc;
+    c->ext_touch_maps = false;                   // (on the context's stream, behind the caller's work: the fence below covers it)
+    launch_accumulate_expected(c->photon_map.as<double>(), c->max_map.as<double>(), c->expected.as<double>(), time_step,
+                               tri_count, c->stream);
+    HIP_TRY(hipGetLastError());
+    return mark_map_fence(c);                    // later accumulate / Shade work on a side lane waits for it
+}
+
+int uvrt_read_expected(uvrt_ctx* c, double* out, int32_t first, int32_t count)
+{
+    if (!c || !out) return fail(UVRT_ERR_INVALID, "uvrt_read_expected: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_read_expected: no scene");
+    if (first < 0 || count < 0 || (int64_t)first + count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_read_expected: range [%d,+%d) outside [0,%d)", first, count, c->T);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    if (int rc = ensure_expected(c)) return rc;
+    if (count == 0) return UVRT_OK;
+    HIP_TRY(hipMemcpyAsync(out, (const char*)c->expected.p + (size_t)first * 8, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+}  // extern "C"

@@ -357,4 +357,34 @@ bool launch_extend_free_planes(const FreeParams& p, int grid_per_cu, hipStream_t
 void launch_export_free_rays(const float4* rays, const float2* oxz, const uint2* hits, void* out32, int64_t first,
                              int64_t count, hipStream_t s);
 
+// ---- shadow rays and the direct gather (uvrt_occlude.hip; include/uvrt.h "shadow rays and the direct gather") ----
+// The occlusion traversal's arguments: a FreeParams (counts, hits and planes unused) plus every ray's tmax and the byte it
+// answers with: occluded[i] = some triangle is hit with 0.0001f < t < tmax[i].
+struct OccludeParams {
+    ExtendParams e;
+    const float2* oxz;       // [n] orig.x, orig.z
+    const float* tmax;       // [n]
+    uint8_t* occluded;       // [n]
+};
+bool launch_occlude_free(const OccludeParams& p, int grid_per_cu, hipStream_t s);
+// the triangles by ORIGINAL id, 3 x float4 each: v0, e1 = v1 - v0, e2 = v2 - v0 (the leaf records' own values, scattered by
+// their id; a triangle no leaf holds stays zero: no area, no estimate)
+void launch_gather_tris(const LeafTri* ltris, float4* gtris, int32_t T, hipStream_t s);
+struct GatherGenParams {
+    const float4* gtris;
+    float4* rays;            // [tri_count * samples] dir.xyz, orig.y
+    float2* oxz;             // orig.x, orig.z
+    float* tmax;
+    double* w;               // the sample's weight (0 for a sample that is not traced)
+    float fx, fy, fz, tx, ty, tz;
+    float light_length;
+    uint32_t seed_hash;      // WangHash(seed)
+    int32_t first_tri, tri_count, samples;
+};
+void launch_gather_generate(const GatherGenParams& p, hipStream_t s);
+void launch_gather_reduce(const float4* gtris, const double* w, const uint8_t* occluded, double* expected, int32_t first_tri,
+                          int32_t tri_count, int32_t samples, int32_t photons_equiv, hipStream_t s);
+// accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]; the plane is zeroed like tempPhotonMap
+void launch_accumulate_expected(double* photon_map, double* max_map, double* expected, float time_step, int32_t T, hipStream_t s);
+
 }  // namespace uvrt

@@ -76,9 +76,9 @@ SYMBOLS = [
 _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIterations",
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
-           "photonMapSize", "viewMode", "driveSpeed"}
+           "photonMapSize", "viewMode", "driveSpeed", "gatherSamples"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
-               "photonMapSize", "viewMode"}
+               "photonMapSize", "viewMode", "gatherSamples"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 

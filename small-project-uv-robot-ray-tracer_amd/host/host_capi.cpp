@@ -161,7 +161,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(maxIterations, int) F(currIterations, int) F(lightIntensity, float) F(minDosage, float)
     F(minPower, float) F(photonsPerLight, int) F(compTime, float) F(progress, float)
     F(finishedComputation, bool) F(thresholdView, bool) F(startedComputation, bool)
-    F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float)
+    F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

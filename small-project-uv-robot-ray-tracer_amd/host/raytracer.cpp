@@ -178,6 +178,22 @@ void RayTracer::ComputeSegments()
         ComputeSegmentDosageMap(lightPositions[i], lightPositions[i + 1], photonsPerLight, mesh->triangleCount);
 }
 
+// one launch of the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
+void RayTracer::GatherLaunch(const float from[3], const float to[3], float duration, int photonsPerLight, int triangleCount)
+{
+    if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
+    uvrt_gather_params g;
+    memset(&g, 0, sizeof g);
+    memcpy(g.from, from, 12);
+    memcpy(g.to, to, 12);
+    g.light_length = lightLength;
+    g.samples = gatherSamples;
+    g.seed = gatherLaunches++;
+    g.photons_equiv = photonsPerLight;
+    check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+    check(uvrt_accumulate_expected(ctx, duration, triangleCount), "accumulate_expected");
+}
+
 void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount)
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
@@ -187,6 +203,7 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
     const float from[3] = {a.position.x, y, a.position.y}, to[3] = {b.position.x, y, b.position.y};
     const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
     const float len = sqrtf(dx * dx + dz * dz);          // (a zero-length segment is traced too, with duration 0: the SEED chain stays regular)
+    if (gatherSamples > 0) { GatherLaunch(from, to, len / driveSpeed, photonsPerLight, triangleCount); return; }
     check(uvrt_generate_sweep(ctx, from, to, lightLength, 0, photonsPerLight), "generate_sweep");
     check(uvrt_extend(ctx, photonsPerLight), "extend");
     check(uvrt_accumulate(ctx, len / driveSpeed, triangleCount), "accumulate");
@@ -197,6 +214,12 @@ void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLig
 {
     // raytracer.cpp:77 -- lamp foot in world space; the y sum is one f32 addition
     const float lp[3] = {lightPos.position.x, mesh->floorHeight + lightHeight, lightPos.position.y};
+    if (gatherSamples > 0) {
+        GatherLaunch(lp, lp, lightPos.duration, photonsPerLight, triangleCount);
+        ++launchIndex;
+        photonMapSize += photonsPerLight;                               // :87
+        return;
+    }
     const bool mine = shardWorld <= 1 || (launchIndex % shardWorld) == shardRank;
     ++launchIndex;
     if (mine) {
@@ -227,6 +250,8 @@ void RayTracer::ComputeIterationsBatched(int iterations)
 void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, int iterations)
 {
     RayTracer* r0 = group[0];
+    for (RayTracer* rt : group)
+        if (rt->gatherSamples > 0) fatal("gatherSamples > 0 is not supported by ComputeIterationsBatched (the direct gather runs launch by launch: ComputeDosageMap)");
     bool driving = false;
     for (RayTracer* rt : group) driving = driving || rt->driveSpeed > 0.0f;
     if (driving) {
@@ -334,6 +359,8 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     RayTracer* r0 = group[0];
     const int L = (int)r0->lightPositions.size();
     if (L == 0) fatal("PlanDurations: no positions");
+    for (RayTracer* rt : group)
+        if (rt->gatherSamples > 0) fatal("PlanDurations: gatherSamples > 0 is not supported (the exposure matrix holds photon counts)");
     // a driving route: the L - 1 segments are further columns of E, fixed at the time the drive takes (raytracer.h)
     const bool driving = r0->driveSpeed > 0.0f && L >= 2;
     if (driving && L > 128) fatal("PlanDurations: a driving plan takes at most 128 positions (2L - 1 <= 256 columns)");
@@ -459,6 +486,7 @@ void RayTracer::ResetDosageMap()                             // raytracer.cpp:12
     finishedComputation = false;
     currIterations = 0;
     launchIndex = 0;
+    gatherLaunches = 0;
     ClearBuffers(true);
 }
 
@@ -538,6 +566,7 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
     o << "    <minimale_dosis>" << float_str(minDosage) << "</minimale_dosis>\n";
     o << "    <minimale_bestralingssterkte>" << float_str(minPower) << "</minimale_bestralingssterkte>\n";
     if (driveSpeed > 0.0f) o << "    <rijsnelheid>" << float_str(driveSpeed) << "</rijsnelheid>\n";   // (not in the reference's files)
+    if (gatherSamples > 0) o << "    <gather_samples>" << gatherSamples << "</gather_samples>\n";                  // (likewise)
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
     if (lightPositions.empty()) o << "    <route/>\n";
@@ -573,6 +602,8 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("minimale_bestralingssterkte"))) to_float(trim(e->text), &minPower);
     driveSpeed = 0.0f;
     if ((e = root.child("rijsnelheid"))) to_float(trim(e->text), &driveSpeed);
+    gatherSamples = 0;
+    if ((e = root.child("gather_samples"))) to_int(trim(e->text), &gatherSamples);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

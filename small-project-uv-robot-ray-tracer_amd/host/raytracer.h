@@ -137,7 +137,18 @@ public:
     // one segment: a and b are two positions (their durations are not used); len = sqrtf(dx*dx + dz*dz) in f32
     void ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount);
     void ComputeSegments();                         // the segments of one iteration, in order (nothing at driveSpeed 0)
+    // The direct gather in place of photon counting (include/uvrt.h "shadow rays and the direct gather").  gatherSamples
+    // = S > 0: every stop of ComputeDosageMap is uvrt_gather_direct over all triangles (S samples each, photons_equiv =
+    // photonsPerLight, seed = the number of gather launches since ResetDosageMap) followed by
+    // uvrt_accumulate_expected(duration) instead of generate -> extend -> accumulate; photonMapSize advances as before, so
+    // Shade is unchanged.  ComputeSegmentDosageMap does the same with from != to (and photonMapSize stays, as with
+    // photons).  0 (default) is the reference's behaviour, bit for bit.  Saved as <gather_samples> in route files when
+    // > 0.  ComputeIterationsBatched, launch sharding (shardWorld > 1) and PlanDurations refuse it: the gather runs per
+    // launch, on one context, and the planner's exposure matrix holds photon counts.
+    int gatherSamples = 0;
+    unsigned gatherLaunches = 0;                    // gather launches since ResetDosageMap: the next launch's seed
 private:
+    void GatherLaunch(const float from[3], const float to[3], float duration, int photonsPerLight, int triangleCount);
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool driving);
 public:
     // The reference never reads the dose back; the headless build does.

@@ -35,6 +35,11 @@
 //                                           writes <rijsnelheid>); 0 forces a stops-only plan of a route file that drives.
 //                                           A route file whose own <rijsnelheid> is > 0 is planned with driving under --plan.
 //                                           At most 128 positions, one context.
+//            [--gather S]                   the direct gather in place of photon counting (RayTracer::gatherSamples; default:
+//                                           the route's <gather_samples>, 0 = photons): every stop and every driven segment
+//                                           is S shadow rays per triangle towards the lamp, so the dim triangles that no photon
+//                                           reaches get an estimate too; one context, launch by launch: refused with --batch,
+//                                           --gpus > 1, --plan and --plan-drive
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -160,7 +165,7 @@ int main(int argc, char** argv)
     int iterations = -1, lamps = -1, device = 0, gpus = 1, batch = 0, flavour = 0;
     bool calibrate = false, plan = false, planVerify = false, planHoldout = false;
     float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f, planDrive = -1.0f;
-    int minPhotons = 16, gridX = 0, gridZ = 0;
+    int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1;
     uint32_t holdoutSeed = 0;
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -197,6 +202,7 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(argv[i], "--drive-speed")) { need(1); driveSpeed = (float)atof(argv[++i]); if (!(driveSpeed >= 0.0f)) { fprintf(stderr, "--drive-speed must be >= 0\n"); return 2; } }
         else if (!strcmp(argv[i], "--plan-drive")) { need(1); plan = true; planDrive = (float)atof(argv[++i]); if (!(planDrive >= 0.0f)) { fprintf(stderr, "--plan-drive must be >= 0\n"); return 2; } }
+        else if (!strcmp(argv[i], "--gather")) { need(1); gather = atoi(argv[++i]); if (gather < 0 || gather > 4096) { fprintf(stderr, "--gather must be in [0, 4096]\n"); return 2; } }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -207,6 +213,9 @@ int main(int argc, char** argv)
     if (driveSpeed > 0.0f && plan) { fprintf(stderr, "--drive-speed cannot be combined with --plan (plan a driving route with --plan-drive V)\n"); return 2; }
     if (planDrive > 0.0f && gpus != 1) { fprintf(stderr, "--plan-drive runs on one context (--gpus 1)\n"); return 2; }
     if (driveSpeed > 0.0f && gpus != 1) { fprintf(stderr, "--drive-speed runs on one context (--gpus 1)\n"); return 2; }
+    if (gather > 0 && batch > 0) { fprintf(stderr, "--gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
+    if (gather > 0 && gpus != 1) { fprintf(stderr, "--gather runs on one context (--gpus 1)\n"); return 2; }
+    if (gather > 0 && plan) { fprintf(stderr, "--gather cannot be combined with --plan / --plan-drive (the planner's exposure matrix holds photon counts)\n"); return 2; }
     if (!routeDir.empty() && routeDir.back() != '/') routeDir += '/';
 
     Mesh mesh;
@@ -226,6 +235,11 @@ int main(int argc, char** argv)
     if (planDrive >= 0.0f) rayTracer.driveSpeed = planDrive;
     if (rayTracer.driveSpeed > 0.0f && gpus != 1) {               // (the route file's own <rijsnelheid>)
         fprintf(stderr, "the route drives at %g m/s: not supported with --gpus > 1 (give --drive-speed 0)\n", (double)rayTracer.driveSpeed);
+        return 2;
+    }
+    if (gather >= 0) rayTracer.gatherSamples = gather;
+    if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
+        fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
         return 2;
     }
     rayTracer.UpdatePhotonsPerLight();
