@@ -198,6 +198,9 @@ int uvrt_gather_direct(uvrt_ctx* ctx, const uvrt_gather_params* params, int32_t 
 int uvrt_accumulate_expected(uvrt_ctx* ctx, float time_step, int32_t tri_count);
 /* the expected plane, any range; synchronises.  uvrt_set_scene zeroes the plane. */
 int uvrt_read_expected(uvrt_ctx* ctx, double* out, int32_t first, int32_t count);
+/* test / interop hook: copies host values into expected[first .. first + count); synchronises.  What the direct gather
+ * writes is one irradiance estimate; a caller may capture an estimate of their own (uvrt_plan_capture_expected). */
+int uvrt_write_expected(uvrt_ctx* ctx, const double* in, int32_t first, int32_t count);
 
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
@@ -359,6 +362,30 @@ int uvrt_plan_solve_bounded(uvrt_ctx* ctx, const uvrt_plan_params* params, const
                             float* durations_out, uvrt_plan_report* report, uvrt_plan_bounds_report* bounds_report /* may be NULL */);
 /* test hook: the class of every triangle in the last solve (0-3 after uvrt_plan_solve); synchronises */
 int uvrt_plan_read_classes(uvrt_ctx* ctx, uint8_t* out, int32_t first, int32_t count);
+/* ---- planning from the direct gather: an exposure matrix of expected values ----
+ * A plan is of one kind, fixed when it begins: COUNTS (uvrt_plan_begin, E[p][t] uint32 photon counts) or EXPECTED
+ * (uvrt_plan_begin_expected, X[p][t] f64: the expected tempPhotonMap entries the direct gather writes, so the triangles no
+ * photon reaches get a row too).  uvrt_plan_solve, uvrt_plan_solve_bounded, uvrt_plan_model_dose, uvrt_plan_read_required,
+ * uvrt_plan_read_classes and uvrt_plan_end work on either kind: for an expected plan every formula above holds with X[p][t]
+ * in place of (double)E[p][t].  The row sum that classes a triangle, sum_p X[p][t], and the sum over the free columns are
+ * f64 sums in ascending p: "unreachable" when the sum is 0 (or no area), "unresolved" when it is < (double)min_photons,
+ * "short" when the free-column sum is 0; the best position of a row is the one with the largest X, lowest index on ties.
+ * Calling sequence: uvrt_plan_begin_expected -> per launch uvrt_gather_direct -> uvrt_plan_capture_expected(column) ->
+ * uvrt_accumulate_expected -> ... -> uvrt_plan_solve*.  The caller owns the bookkeeping: the photons_equiv of the planes
+ * captured into one column must sum to photons_per_position of the solve.  The plan is as good as the estimator: see
+ * DESIGN.md 12 for the scatter of a row at S samples.
+ * uvrt_plan_begin_expected: uvrt_plan_begin with X as double[P][T], zeroed; the same limits; drops a plan of either kind. */
+int uvrt_plan_begin_expected(uvrt_ctx* ctx, int32_t positions);
+/* X[position][t] += expected[t] for every t (one f64 addition per entry, no atomics) on the context's stream behind all
+ * outstanding work; the expected plane stays as it is, so the uvrt_accumulate_expected that follows computes what it would
+ * have without the capture.  A sum that is not finite or is negative raises a flag on the device (the analogue of the
+ * uint32 overflow flag): uvrt_plan_solve* then returns UVRT_ERR_INVALID. */
+int uvrt_plan_capture_expected(uvrt_ctx* ctx, int32_t position);
+/* test hook: row `position` of X; synchronises */
+int uvrt_plan_read_exposure_expected(uvrt_ctx* ctx, int32_t position, double* out, int32_t first, int32_t count);
+/* UVRT_ERR_INVALID with nothing changed: uvrt_plan_capture_batch / uvrt_plan_read_exposure on an expected plan,
+ * uvrt_plan_capture_expected / uvrt_plan_read_exposure_expected on a counts plan or without a plan, a position outside
+ * [0, P), a null pointer. */
 /* the smallest float >= v that "%.8g" (SaveRoute) prints back to itself through strtof (LoadRoute): how the solver rounds
  * the durations it returns.  Host only, no GPU needed. */
 float uvrt_plan_round_trip_up(float v);

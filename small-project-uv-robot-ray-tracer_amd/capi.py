@@ -79,6 +79,7 @@ SYMBOLS = [
     ("uvrt_gather_direct", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_accumulate_expected", C.c_int, [_vp, _f32, _i32]),
     ("uvrt_read_expected", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_write_expected", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_read_counts", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_read_photon_map", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_device_ptr", C.c_int, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i64)]),
@@ -99,6 +100,9 @@ SYMBOLS = [
     ("uvrt_plan_solve_bounded", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("uvrt_plan_read_classes", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_plan_round_trip_up", _f32, [_f32]),
+    ("uvrt_plan_begin_expected", C.c_int, [_vp, _i32]),
+    ("uvrt_plan_capture_expected", C.c_int, [_vp, _i32]),
+    ("uvrt_plan_read_exposure_expected", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -397,6 +401,11 @@ class Ctx:
         self._ck(self._L.uvrt_read_expected(self._h, _ptr(out), int(first), int(count)))
         return out
 
+    def write_expected(self, values, first=0):
+        """host values into expected[first, first + len(values))"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        self._ck(self._L.uvrt_write_expected(self._h, _ptr(v), int(first), int(v.size)))
+
     @property
     def seed(self):
         s = C.c_uint32()
@@ -512,6 +521,21 @@ class Ctx:
     def plan_begin(self, positions):
         self._ck(self._L.uvrt_plan_begin(self._h, int(positions)))
         self._plan_p = int(positions)
+
+    def plan_begin_expected(self, positions):
+        """a plan whose exposure matrix holds f64 expected counts (the direct gather's plane) instead of photon counts"""
+        self._ck(self._L.uvrt_plan_begin_expected(self._h, int(positions)))
+        self._plan_p = int(positions)
+
+    def plan_capture_expected(self, position):
+        """X[position] += the expected plane (which stays as it is)"""
+        self._ck(self._L.uvrt_plan_capture_expected(self._h, int(position)))
+
+    def plan_read_exposure_expected(self, position, first=0, count=None):
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float64)
+        self._ck(self._L.uvrt_plan_read_exposure_expected(self._h, int(position), _ptr(out), int(first), int(count)))
+        return out
 
     def plan_capture_batch(self, positions_of_launches):
         pos = np.ascontiguousarray(positions_of_launches, dtype=np.int32)

@@ -1,5 +1,5 @@
 // uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
-// uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected (uvrt_occlude.hip's kernels)
+// uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected, uvrt_write_expected (uvrt_occlude.hip's kernels)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
@@ -171,6 +171,21 @@ int uvrt_read_expected(uvrt_ctx* c, double* out, int32_t first, int32_t count)
     if (int rc = ensure_expected(c)) return rc;
     if (count == 0) return UVRT_OK;
     HIP_TRY(hipMemcpyAsync(out, (const char*)c->expected.p + (size_t)first * 8, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+int uvrt_write_expected(uvrt_ctx* c, const double* in, int32_t first, int32_t count)
+{
+    if (!c || !in) return fail(UVRT_ERR_INVALID, "uvrt_write_expected: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_write_expected: no scene");
+    if (first < 0 || count < 0 || (int64_t)first + count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_write_expected: range [%d,+%d) outside [0,%d)", first, count, c->T);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    if (int rc = ensure_expected(c)) return rc;
+    if (count == 0) return UVRT_OK;
+    HIP_TRY(hipMemcpyAsync((char*)c->expected.p + (size_t)first * 8, in, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return UVRT_OK;
 }

@@ -15,6 +15,11 @@
 // base_t = (sum_p E[p][t] lower[p]) r_t the residual problem  min 1.e  s.t.  sum_{free p} E[p][t] r_t e_p >= rho_t = 1 - base_t
 // on the ACTIVE rows (base_t < 1 and a free column reaches t) is the same homogeneous LP with the row scale r_t / rho_t and
 // without the fixed columns: the <true> instantiations of the row kernels, the same host loop.
+//
+// Two kinds of plan, fixed at its begin: E holds uint32 photon counts (uvrt_plan_begin, uvrt_plan_capture_batch) or f64
+// expected counts of the direct gather (uvrt_plan_begin_expected, uvrt_plan_capture_expected).  The row kernels and the
+// host loop take the element type ET as a template argument and do the same arithmetic on (double)E[p][t]; only the row
+// sums that class a triangle differ: exact uint64 for counts, f64 in ascending p for expected values.
 #include "uvrt_ctx.h"
 #include "uvrt_plan_lp.h"
 
@@ -52,6 +57,22 @@ __global__ __launch_bounds__(256) void k_plan_capture(CaptureParams p)
     }
 }
 
+// X[t] += expected[t] on one row of an expected plan (X points at the row); a sum that is not finite or is negative raises
+// `bad`, the analogue of the uint32 overflow flag
+__global__ __launch_bounds__(256) void k_plan_capture_expected(double* __restrict__ X, const double* __restrict__ expected,
+                                                              int32_t T, uint32_t* __restrict__ bad)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const double sum = X[t] + expected[t];
+    if (!(sum >= 0.0) || sum == std::numeric_limits<double>::infinity()) atomicOr(bad, 1u);
+    X[t] = sum;
+}
+
+// the type a row of E is summed in when k_plan_classify classes it
+template <typename ET> struct RowSum { using type = uint64_t; };
+template <> struct RowSum<double> { using type = double; };
+
 // what a bounded solve adds to the row kernels: the lower bounds (as f64), the fixed columns and the row scale's terms
 struct BoundsDev {
     const double* lower;     // f64[P]
@@ -64,8 +85,8 @@ struct BoundsDev {
 // class of every triangle (0 required, 1 unreachable, 2 unresolved, 3 masked out), per block: counts and areas per class.
 // B (bounded solve): a row of class 0 splits into 4 (met by the bounds: base_t >= 1), 5 (short: no free column reaches it)
 // and 0 (active), whose rho_t = max(1 - base_t, PLAN_RHO_MIN) goes to rho[t]; base_t in f64, columns in ascending order.
-template <bool B>
-__global__ __launch_bounds__(256) void k_plan_classify(const uint32_t* __restrict__ E, int32_t P, int32_t T,
+template <bool B, typename ET>
+__global__ __launch_bounds__(256) void k_plan_classify(const ET* __restrict__ E, int32_t P, int32_t T,
                                                       const uint8_t* __restrict__ mask, const float* __restrict__ area,
                                                       uint32_t min_photons, uint8_t* __restrict__ cls,
                                                       int32_t* __restrict__ blk_cnt, double* __restrict__ blk_area,
@@ -85,10 +106,10 @@ __global__ __launch_bounds__(256) void k_plan_classify(const uint32_t* __restric
     int k = -1;
     double a = 0;
     if (t < T) {
-        uint64_t sum = 0, fre = 0;
+        typename RowSum<ET>::type sum = 0, fre = 0;
         double base = 0.0;
         for (int p = 0; p < P; ++p) {
-            const uint32_t e = E[(int64_t)p * T + t];
+            const ET e = E[(int64_t)p * T + t];
             sum += e;
             if (B) {
                 if (!s_fix[p]) fre += e;
@@ -131,7 +152,8 @@ __global__ __launch_bounds__(256) void k_plan_classify(const uint32_t* __restric
     }
 }
 
-// the required (B: the active) rows in ascending triangle order (ballot + block offsets) and their scale r (B: r / rho)
+// the required (B: the active) rows in ascending triangle order (ballot + block offsets) and their scale r (B: r / rho);
+// E is not read, so one kernel serves both element types
 template <bool B>
 __global__ __launch_bounds__(256) void k_plan_compact(const uint32_t* __restrict__ E, int32_t P, int32_t T,
                                                      const uint8_t* __restrict__ cls, const float* __restrict__ area,
@@ -158,8 +180,8 @@ __global__ __launch_bounds__(256) void k_plan_compact(const uint32_t* __restrict
 
 // row j of the gathered block: A[sel_j][p] = E[p][rows[sel_j]] * r_{sel_j} in f64; B: P counts the free columns only
 // and cols[p] is the p-th of them (the fixed columns never reach the simplex)
-template <bool B>
-__global__ __launch_bounds__(256) void k_plan_gather(const uint32_t* __restrict__ E, int32_t T, int32_t P,
+template <bool B, typename ET>
+__global__ __launch_bounds__(256) void k_plan_gather(const ET* __restrict__ E, int32_t T, int32_t P,
                                                     const int32_t* __restrict__ rows, const double* __restrict__ rd,
                                                     const int64_t* __restrict__ sel, int32_t nsel, double* __restrict__ out,
                                                     const int32_t* __restrict__ cols)
@@ -171,10 +193,10 @@ __global__ __launch_bounds__(256) void k_plan_gather(const uint32_t* __restrict_
 }
 
 // f64 check of durations d over the required rows: per block min_i A_i d (and A_i d per row); rows with A_i d = 0 raise
-// their best position (most photons, lowest index) to what covers the row alone (integer max of positive f64 bits:
+// their best position (largest E, lowest index) to what covers the row alone (integer max of positive f64 bits:
 // order independent).  B: the fixed columns are left out of the sum and of the choice of the best position.
-template <bool B>
-__global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restrict__ E, int32_t T, int32_t P, int64_t NR,
+template <bool B, typename ET>
+__global__ __launch_bounds__(256) void k_plan_rowcheck(const ET* __restrict__ E, int32_t T, int32_t P, int64_t NR,
                                                       const int32_t* __restrict__ rows, const double* __restrict__ rd,
                                                       const double* __restrict__ d, double* __restrict__ blk_min,
                                                       unsigned long long* __restrict__ raise, int32_t* __restrict__ zero_rows,
@@ -193,11 +215,11 @@ __global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restric
     if (i < NR) {
         const int64_t t = rows[i];
         double ad = 0.0;
-        uint32_t best = 0;
+        ET best = 0;
         int bp = 0;
         for (int q = 0; q < P; ++q) {
             if (B && s_fix[q]) continue;
-            const uint32_t e = E[(int64_t)q * T + t];
+            const ET e = E[(int64_t)q * T + t];
             ad += (double)e * s_d[q];
             if (e > best) { best = e; bp = q; }
         }
@@ -221,7 +243,8 @@ __global__ __launch_bounds__(256) void k_plan_rowcheck(const uint32_t* __restric
 
 // the bounded solve's final check, in x-space: per block the minimum over the required rows (classes 0 and 4) of
 // (sum_p E[p][t] x_p) * r_t, every column in ascending order, in f64
-__global__ __launch_bounds__(256) void k_plan_xcheck(const uint32_t* __restrict__ E, int32_t T, int32_t P,
+template <typename ET>
+__global__ __launch_bounds__(256) void k_plan_xcheck(const ET* __restrict__ E, int32_t T, int32_t P,
                                                     const uint8_t* __restrict__ cls, const float* __restrict__ area,
                                                     float s, float Nf, double mprime, const double* __restrict__ x,
                                                     double* __restrict__ blk_min)
@@ -248,7 +271,8 @@ __global__ __launch_bounds__(256) void k_plan_xcheck(const uint32_t* __restrict_
 }
 
 // D_t(d) = (float)(s * sum_p E[p][t] d_p / den_t), f64 sum in position order, computeDosage's f32 denominator
-__global__ __launch_bounds__(256) void k_plan_model_dose(const uint32_t* __restrict__ E, int32_t T, int32_t P,
+template <typename ET>
+__global__ __launch_bounds__(256) void k_plan_model_dose(const ET* __restrict__ E, int32_t T, int32_t P,
                                                         const double* __restrict__ d, const float* __restrict__ area,
                                                         float Nf, float s, float* __restrict__ out, int32_t first, int32_t count)
 {
@@ -271,12 +295,13 @@ inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / 
 
 struct PlanState {
     int32_t P = 0;
+    bool expected = false;               // E holds f64 expected counts (uvrt_plan_begin_expected), not uint32 photon counts
     DevBuf E;
     std::vector<uint64_t> rays;          // rays of this context's launches captured per position (uint32 overflow guard)
     int64_t captures = 0;
     bool solved = false;
     float s = 0, Nf = 0;                 // of the last solve (uvrt_plan_model_dose)
-    DevBuf overflow;                     // uint32 flag of k_plan_capture
+    DevBuf overflow;                     // uint32 flag of k_plan_capture / k_plan_capture_expected
     DevBuf cls, mask, blk_cnt, blk_area, blk_off, rows, rd, dd, blk_min, raise, zrows, outf, ratio, sel, gath;
     DevBuf lowd, fixd, rho, cols, xmin;  // bounded solve: lower as f64[P], fixed uint8[P], rho f64[T], the free columns, k_plan_xcheck
     void release()
@@ -304,6 +329,7 @@ struct RowCheck { double min_ratio; int32_t zero_rows; };
 
 // k_plan_rowcheck of host durations d64; with `raise` the raise values come back in raise_out, with ratio_out A_i d per row
 // (bounded: the fixed columns of S.fixd are left out)
+template <typename ET>
 int row_check(uvrt_ctx* c, PlanState& S, bool bounded, int64_t NR, const std::vector<double>& d64, bool raise,
               RowCheck* out, std::vector<double>* raise_out, std::vector<double>* ratio_out = nullptr)
 {
@@ -313,8 +339,8 @@ int row_check(uvrt_ctx* c, PlanState& S, bool bounded, int64_t NR, const std::ve
         HIP_TRY(hipMemsetAsync(S.raise.p, 0, (size_t)S.P * 8, c->stream));
         HIP_TRY(hipMemsetAsync(S.zrows.p, 0, 4, c->stream));
     }
-    hipLaunchKernelGGL(bounded ? k_plan_rowcheck<true> : k_plan_rowcheck<false>, dim3(nbr), dim3(256), 0, c->stream,
-                       (const uint32_t*)S.E.as<uint32_t>(), c->T, S.P, NR,
+    hipLaunchKernelGGL((bounded ? k_plan_rowcheck<true, ET> : k_plan_rowcheck<false, ET>), dim3(nbr), dim3(256), 0, c->stream,
+                       (const ET*)S.E.as<ET>(), c->T, S.P, NR,
                        (const int32_t*)S.rows.as<int32_t>(), (const double*)S.rd.as<double>(), (const double*)S.dd.as<double>(),
                        S.blk_min.as<double>(), raise ? S.raise.as<unsigned long long>() : nullptr,
                        S.zrows.as<int32_t>(), ratio_out ? S.ratio.as<double>() : nullptr,
@@ -345,12 +371,13 @@ int row_check(uvrt_ctx* c, PlanState& S, bool bounded, int64_t NR, const std::ve
 }
 
 // k_plan_xcheck of host durations x (every column): the minimum over the required rows of D_t(x) / m'
+template <typename ET>
 int x_check(uvrt_ctx* c, PlanState& S, double mprime, const std::vector<double>& x, double* min_ratio)
 {
     const unsigned nbt = nblocks(c->T, 256);
     if (int rc = S.xmin.ensure((size_t)nbt * 8, false, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(S.dd.p, x.data(), (size_t)S.P * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_plan_xcheck, dim3(nbt), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(), c->T, S.P,
+    hipLaunchKernelGGL(k_plan_xcheck<ET>, dim3(nbt), dim3(256), 0, c->stream, (const ET*)S.E.as<ET>(), c->T, S.P,
                        (const uint8_t*)S.cls.as<uint8_t>(), (const float*)c->area.as<float>(), S.s, S.Nf, mprime,
                        (const double*)S.dd.as<double>(), S.xmin.as<double>());
     HIP_TRY(hipGetLastError());
@@ -362,8 +389,36 @@ int x_check(uvrt_ctx* c, PlanState& S, double mprime, const std::vector<double>&
     return UVRT_OK;
 }
 
+template <typename ET>
+int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
+                 uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
+
 int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
-               uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
+               uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
+{
+    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "%s: no plan (uvrt_plan_begin)", who);
+    return c->plan->expected ? plan_solve_t<double>(c, who, prm, bounds, out, rep, brep)
+                             : plan_solve_t<uint32_t>(c, who, prm, bounds, out, rep, brep);
+}
+
+// uvrt_plan_begin (uint32 counts) and uvrt_plan_begin_expected (f64 expected counts)
+int plan_begin(uvrt_ctx* c, const char* who, int32_t positions, bool expected)
+{
+    if (!c || !c->have_scene) return fail(UVRT_ERR_INVALID, "%s: null context or no scene", who);
+    if (positions < 1 || positions > PLAN_MAX_P)
+        return fail(UVRT_ERR_INVALID, "%s: positions %d outside [1,%d]", who, positions, PLAN_MAX_P);
+    if ((uint64_t)positions * (uint64_t)c->T >= ((uint64_t)1 << 32))
+        return fail(UVRT_ERR_INVALID, "%s: %d positions x %d triangles exceed 2^32 counters", who, positions, c->T);
+    if (int rc = set_device(c)) return rc;
+    plan_drop(c);
+    c->plan = new PlanState();
+    c->plan->P = positions;
+    c->plan->expected = expected;
+    c->plan->rays.assign(positions, 0);
+    if (int rc = c->plan->E.ensure((size_t)positions * (size_t)c->T * (expected ? 8 : 4), true, c->stream)) { plan_drop(c); return rc; }
+    if (int rc = c->plan->overflow.ensure(4, true, c->stream)) { plan_drop(c); return rc; }
+    return UVRT_OK;
+}
 
 }  // namespace
 
@@ -382,22 +437,9 @@ float uvrt_plan_round_trip_up(float v)
     return v;
 }
 
-int uvrt_plan_begin(uvrt_ctx* c, int32_t positions)
-{
-    if (!c || !c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_plan_begin: null context or no scene");
-    if (positions < 1 || positions > PLAN_MAX_P)
-        return fail(UVRT_ERR_INVALID, "uvrt_plan_begin: positions %d outside [1,%d]", positions, PLAN_MAX_P);
-    if ((uint64_t)positions * (uint64_t)c->T >= ((uint64_t)1 << 32))
-        return fail(UVRT_ERR_INVALID, "uvrt_plan_begin: %d positions x %d triangles exceed 2^32 counters", positions, c->T);
-    if (int rc = set_device(c)) return rc;
-    plan_drop(c);
-    c->plan = new PlanState();
-    c->plan->P = positions;
-    c->plan->rays.assign(positions, 0);
-    if (int rc = c->plan->E.ensure((size_t)positions * (size_t)c->T * 4, true, c->stream)) { plan_drop(c); return rc; }
-    if (int rc = c->plan->overflow.ensure(4, true, c->stream)) { plan_drop(c); return rc; }
-    return UVRT_OK;
-}
+int uvrt_plan_begin(uvrt_ctx* c, int32_t positions) { return plan_begin(c, "uvrt_plan_begin", positions, false); }
+
+int uvrt_plan_begin_expected(uvrt_ctx* c, int32_t positions) { return plan_begin(c, "uvrt_plan_begin_expected", positions, true); }
 
 int uvrt_plan_end(uvrt_ctx* c)
 {
@@ -410,6 +452,7 @@ int uvrt_plan_end(uvrt_ctx* c)
 int uvrt_plan_capture_batch(uvrt_ctx* c, const int32_t* pos, int32_t count)
 {
     if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: no plan (uvrt_plan_begin)");
+    if (c->plan->expected) return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: the plan holds expected values (uvrt_plan_capture_expected)");
     if (c->b_count <= 0) return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: no traced batch");
     if (!pos || count != c->b_count)
         return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_batch: %d positions for a batch of %d launches", count, c->b_count);
@@ -435,6 +478,24 @@ int uvrt_plan_capture_batch(uvrt_ctx* c, const int32_t* pos, int32_t count)
     hipLaunchKernelGGL(k_plan_capture, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream, p);
     HIP_TRY(hipGetLastError());
     S.rays = rays;
+    ++S.captures;
+    return UVRT_OK;
+}
+
+int uvrt_plan_capture_expected(uvrt_ctx* c, int32_t position)
+{
+    if (!c || !c->plan || !c->plan->expected)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_expected: no plan of expected values (uvrt_plan_begin_expected)");
+    PlanState& S = *c->plan;
+    if (position < 0 || position >= S.P)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_expected: position %d outside [0,%d)", position, S.P);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    if (int rc = ensure_expected(c)) return rc;
+    hipLaunchKernelGGL(k_plan_capture_expected, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream,
+                       S.E.as<double>() + (size_t)position * c->T, (const double*)c->expected.as<double>(), c->T,
+                       S.overflow.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
     ++S.captures;
     return UVRT_OK;
 }
@@ -465,9 +526,14 @@ int uvrt_plan_model_dose(uvrt_ctx* c, const float* durations, float* out, int32_
     std::vector<double> d(S.P);
     for (int p = 0; p < S.P; ++p) d[p] = durations[p];
     HIP_TRY(hipMemcpyAsync(S.dd.p, d.data(), (size_t)S.P * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_plan_model_dose, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(),
-                       c->T, S.P, (const double*)S.dd.as<double>(), (const float*)c->area.as<float>(), S.Nf, S.s, S.outf.as<float>(),
-                       first, count);
+    if (S.expected)
+        hipLaunchKernelGGL(k_plan_model_dose<double>, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const double*)S.E.as<double>(),
+                           c->T, S.P, (const double*)S.dd.as<double>(), (const float*)c->area.as<float>(), S.Nf, S.s, S.outf.as<float>(),
+                           first, count);
+    else
+        hipLaunchKernelGGL(k_plan_model_dose<uint32_t>, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(),
+                           c->T, S.P, (const double*)S.dd.as<double>(), (const float*)c->area.as<float>(), S.Nf, S.s, S.outf.as<float>(),
+                           first, count);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, S.outf.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -477,6 +543,7 @@ int uvrt_plan_model_dose(uvrt_ctx* c, const float* durations, float* out, int32_
 int uvrt_plan_read_exposure(uvrt_ctx* c, int32_t position, uint32_t* out, int32_t first, int32_t count)
 {
     if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: no plan");
+    if (c->plan->expected) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: the plan holds expected values (uvrt_plan_read_exposure_expected)");
     if (position < 0 || position >= c->plan->P)
         return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: position %d outside [0,%d)", position, c->plan->P);
     if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: bad range");
@@ -484,6 +551,23 @@ int uvrt_plan_read_exposure(uvrt_ctx* c, int32_t position, uint32_t* out, int32_
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->plan->E.as<uint32_t>() + (size_t)position * c->T + first, (size_t)count * 4,
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+int uvrt_plan_read_exposure_expected(uvrt_ctx* c, int32_t position, double* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan || !c->plan->expected)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: no plan of expected values (uvrt_plan_begin_expected)");
+    if (position < 0 || position >= c->plan->P)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: position %d outside [0,%d)", position, c->plan->P);
+    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: bad range");
+    if (count == 0) return UVRT_OK;
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->plan->E.as<double>() + (size_t)position * c->T + first, (size_t)count * 8,
                            hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return UVRT_OK;
@@ -518,10 +602,10 @@ namespace {
 
 // uvrt_plan_solve (bounds == nullptr) and uvrt_plan_solve_bounded.  Bounds that bind nothing (all-zero lower, no fixed
 // column) take the unbounded instantiations of every kernel: the same arithmetic, bit for bit.
-int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
-               uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
+template <typename ET>
+int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
+                 uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
 {
-    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "%s: no plan (uvrt_plan_begin)", who);
     if (c->plan->captures == 0) return fail(UVRT_ERR_INVALID, "%s: nothing captured (uvrt_plan_capture_batch)", who);
     if (!prm || !out || !rep) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
     if (prm->photons_per_position < 1 || prm->photons_per_position > (int64_t)0xFFFFFFFFll)
@@ -559,6 +643,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
         uint32_t of = 0;
         HIP_TRY(hipMemcpyAsync(&of, S.overflow.p, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
+        if (of && c->plan->expected) return fail(UVRT_ERR_INVALID, "%s: a captured expected value is not finite or is negative", who);
         if (of) return fail(UVRT_ERR_INVALID, "%s: a captured count overflowed uint32 (over 2^32 - 1 photons of one position)", who);
     }
     int rc;
@@ -602,8 +687,8 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
         bd.all_met = !(m > 0.0);
     }
     const uint32_t min_ph = (uint32_t)std::max(1, prm->min_photons);
-    hipLaunchKernelGGL(bounded ? k_plan_classify<true> : k_plan_classify<false>, dim3(nbt), dim3(256), 0, c->stream,
-                       (const uint32_t*)S.E.as<uint32_t>(), P, T, dmask, (const float*)c->area.as<float>(), min_ph,
+    hipLaunchKernelGGL((bounded ? k_plan_classify<true, ET> : k_plan_classify<false, ET>), dim3(nbt), dim3(256), 0, c->stream,
+                       (const ET*)S.E.as<ET>(), P, T, dmask, (const float*)c->area.as<float>(), min_ph,
                        S.cls.as<uint8_t>(), S.blk_cnt.as<int32_t>(), S.blk_area.as<double>(), bd,
                        bounded ? S.rho.as<double>() : nullptr);
     HIP_TRY(hipGetLastError());
@@ -643,7 +728,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
         for (int p = 0; p < P; ++p) { out[p] = (float)low[p]; total += low[p]; used += low[p] > 0.0; }
         if (m > 0.0 && cnt[4] > 0) {
             if ((rc = S.dd.ensure((size_t)P * 8, false, c->stream))) return rc;
-            if ((rc = x_check(c, S, mprime, low, &minx))) return rc;
+            if ((rc = x_check<ET>(c, S, mprime, low, &minx))) return rc;
         }
         rep->used_positions = used;
         rep->total_duration = total;
@@ -682,12 +767,12 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
     {
         std::vector<double> ones(P, 1.0);
         RowCheck r1;
-        if ((rc = row_check(c, S, bounded, NR, ones, false, &r1, nullptr))) return rc;
+        if ((rc = row_check<ET>(c, S, bounded, NR, ones, false, &r1, nullptr))) return rc;
         for (int p : cols) d64[p] = r1.min_ratio > 0.0 ? 1.0 / r1.min_ratio : 1.0;
     }
     for (;;) {
         RowCheck rck;
-        if ((rc = row_check(c, S, bounded, NR, d64, false, &rck, nullptr, &ratio))) return rc;
+        if ((rc = row_check<ET>(c, S, bounded, NR, d64, false, &rck, nullptr, &ratio))) return rc;
         double sd = 0;
         for (double v : d64) sd += v;
         if (rck.min_ratio > 0.0 && sd / rck.min_ratio < best_ub) {
@@ -711,8 +796,8 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
         if ((rc = S.sel.ensure(take * 8, false, c->stream))) return rc;
         if ((rc = S.gath.ensure(take * (size_t)PF * 8, false, c->stream))) return rc;
         HIP_TRY(hipMemcpyAsync(S.sel.p, cand.data(), take * 8, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(bounded ? k_plan_gather<true> : k_plan_gather<false>, dim3(nblocks((int64_t)take * PF, 256)), dim3(256), 0,
-                           c->stream, (const uint32_t*)S.E.as<uint32_t>(), T, PF, (const int32_t*)S.rows.as<int32_t>(),
+        hipLaunchKernelGGL((bounded ? k_plan_gather<true, ET> : k_plan_gather<false, ET>), dim3(nblocks((int64_t)take * PF, 256)), dim3(256), 0,
+                           c->stream, (const ET*)S.E.as<ET>(), T, PF, (const int32_t*)S.rows.as<int32_t>(),
                            (const double*)S.rd.as<double>(), (const int64_t*)S.sel.as<int64_t>(), (int32_t)take, S.gath.as<double>(),
                            bounded ? (const int32_t*)S.cols.as<int32_t>() : nullptr);
         HIP_TRY(hipGetLastError());
@@ -739,7 +824,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
         ++it;
         if (!solved) {                          // pivot cap: keep what is certified, report the gap
             RowCheck rlast;
-            if ((rc = row_check(c, S, bounded, NR, d64, false, &rlast, nullptr))) return rc;
+            if ((rc = row_check<ET>(c, S, bounded, NR, d64, false, &rlast, nullptr))) return rc;
             double sl = 0;
             for (double v : d64) sl += v;
             if (rlast.min_ratio > 0.0 && sl / rlast.min_ratio < best_ub) {
@@ -762,7 +847,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
     RowCheck rck{};
     std::vector<double> raise;
     for (int round = 0; round < 4; ++round) {
-        if ((rc = row_check(c, S, bounded, NR, d64, true, &rck, &raise))) return rc;
+        if ((rc = row_check<ET>(c, S, bounded, NR, d64, true, &rck, &raise))) return rc;
         if (rck.zero_rows == 0) break;
         for (int p = 0; p < P; ++p) d64[p] = std::max(d64[p], raise[p]);
     }
@@ -779,7 +864,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
                 d32[p] = d64[p] > 0.0 ? uvrt_plan_round_trip_up(f) : 0.0f;
                 dh[p] = d32[p];
             }
-            if ((rc = row_check(c, S, false, NR, dh, false, &rck, nullptr))) return rc;
+            if ((rc = row_check<ET>(c, S, false, NR, dh, false, &rck, nullptr))) return rc;
             if (rck.min_ratio >= 1.0) break;
             for (double& v : d64) v *= (1.0 / rck.min_ratio) * (1.0 + 1e-12);
         }
@@ -799,10 +884,10 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
                 }
                 dh[p] = d32[p];
             }
-            if ((rc = x_check(c, S, mprime, dh, &min_ratio))) return rc;
+            if ((rc = x_check<ET>(c, S, mprime, dh, &min_ratio))) return rc;
             if (min_ratio >= 1.0) break;
             for (int p = 0; p < P; ++p) dh[p] = fix[p] ? 0.0 : dh[p] - low[p];
-            if ((rc = row_check(c, S, true, NR, dh, false, &rck, nullptr))) return rc;
+            if ((rc = row_check<ET>(c, S, true, NR, dh, false, &rck, nullptr))) return rc;
             const double up = (rck.min_ratio > 0.0 && rck.min_ratio < 1.0 ? 1.0 / rck.min_ratio : 1.0) * (1.0 + 1e-9);
             for (int p = 0; p < P; ++p) d64[p] = std::max(d64[p], dh[p]) * up;
         }

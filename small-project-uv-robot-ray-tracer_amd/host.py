@@ -61,6 +61,8 @@ SYMBOLS = [
     ("uvrt_host_rt_set_lamps", None, [_vp, C.POINTER(C.c_float), C.c_int]),
     ("uvrt_host_rt_plan", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp,
                                  C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp,
+                                        C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -234,14 +236,23 @@ class RayTracer:
     def SetRayRange(self, rank, world): self._L.uvrt_host_rt_set_ray_range(self._h, int(rank), int(world))
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
 
-    def PlanDurations(self, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None):
+    def PlanDurations(self, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None,
+                      gather_samples=0):
         """RayTracer::PlanDurations: one batched computation over the current positions from the current SEED with the
         exposure captured, then the least durations that bring every required triangle to min_dose (default: the
         route's minDosage).  They are written into the positions; returns (durations float32[P], report dict with
         the starting "seed").  With driveSpeed > 0 (2 to 128 positions) the segments between consecutive positions are
         fixed columns of the plan at the time the drive takes: the dict then also carries the fields of the bounds
-        report (capi.PlanBoundsReport) and "segment_durations" (float32[P - 1])."""
+        report (capi.PlanBoundsReport) and "segment_durations" (float32[P - 1]).  gather_samples = S > 0 plans from the
+        direct gather instead (PlanOptions::gatherSamples): the launches of a gatherSamples = S run, launch by launch, into
+        an exposure matrix of f64 expected counts (ctx.plan_read_exposure_expected), so triangles no photon reaches are
+        planned for too; the plan is as good as the estimator."""
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if gather_samples:
+            self._L.uvrt_host_rt_plan_gather(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                             float(margin), float(rel_gap), int(max_iterations), _addr(keep),
+                                             int(gather_samples), C.byref(rep), C.byref(seed))
+            return _plan_result(self, rep, seed)
         self._L.uvrt_host_rt_plan(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons), float(margin),
                                   float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))
         return _plan_result(self, rep, seed)

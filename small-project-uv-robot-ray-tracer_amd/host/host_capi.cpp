@@ -128,6 +128,15 @@ void uvrt_host_rt_plan(void* r, float min_dose, int min_photons, double margin, 
     o.maxIterations = max_iterations; o.mask = mask;
     *rep = ((RayTracer*)r)->PlanDurations(o, seed);
 }
+// the same with PlanOptions::gatherSamples: > 0 plans from the direct gather
+void uvrt_host_rt_plan_gather(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                              const unsigned char* mask, int gather_samples, uvrt_plan_report* rep, unsigned* seed)
+{
+    RayTracer::PlanOptions o;
+    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
+    o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
+    *rep = ((RayTracer*)r)->PlanDurations(o, seed);
+}
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {

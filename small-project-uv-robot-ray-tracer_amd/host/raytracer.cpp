@@ -191,6 +191,7 @@ void RayTracer::GatherLaunch(const float from[3], const float to[3], float durat
     g.seed = gatherLaunches++;
     g.photons_equiv = photonsPerLight;
     check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+    if (planGatherColumn >= 0) check(uvrt_plan_capture_expected(ctx, planGatherColumn), "plan_capture_expected");
     check(uvrt_accumulate_expected(ctx, duration, triangleCount), "accumulate_expected");
 }
 
@@ -369,14 +370,41 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
     uint32_t seed0 = 0;
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
-    for (RayTracer* rt : group) {
-        check(uvrt_plan_begin(rt->ctx, cols), "plan_begin");
-        rt->ClearBuffers(true);                              // ResetDosageMap without the route save
-        rt->currIterations = 0;
-        rt->launchIndex = 0;
-        rt->planCapture = true;
+    if (opt.gatherSamples > 0) {
+        // the launches of ComputeDosageMap with gatherSamples = S, launch by launch, every plane captured into its column
+        if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
+        if (r0->shardWorld > 1 || r0->reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
+        check(uvrt_plan_begin_expected(r0->ctx, cols), "plan_begin_expected");
+        r0->ClearBuffers(true);                              // ResetDosageMap without the route save
+        r0->currIterations = 0;
+        r0->launchIndex = 0;
+        r0->gatherLaunches = 0;
+        r0->gatherSamples = opt.gatherSamples;
+        const int T = r0->mesh->triangleCount;
+        for (int it = 0; it < r0->maxIterations; ++it) {
+            for (int i = 0; i < L; ++i) {
+                r0->planGatherColumn = i;
+                r0->ComputeSingleLightDosageMap(r0->lightPositions[i], r0->photonsPerLight, T);
+            }
+            for (int k = 0; driving && k + 1 < L; ++k) {
+                r0->planGatherColumn = L + k;
+                r0->ComputeSegmentDosageMap(r0->lightPositions[k], r0->lightPositions[k + 1], r0->photonsPerLight, T);
+            }
+            r0->Shade();
+            ++r0->currIterations;
+        }
+        r0->planGatherColumn = -1;
+        r0->gatherSamples = 0;
+    } else {
+        for (RayTracer* rt : group) {
+            check(uvrt_plan_begin(rt->ctx, cols), "plan_begin");
+            rt->ClearBuffers(true);                          // ResetDosageMap without the route save
+            rt->currIterations = 0;
+            rt->launchIndex = 0;
+            rt->planCapture = true;
+        }
+        ComputeIterationsBatched(group, r0->maxIterations);
     }
-    ComputeIterationsBatched(group, r0->maxIterations);
     uvrt_plan_params prm;
     memset(&prm, 0, sizeof prm);
     prm.min_dose = opt.minDose >= 0.0f ? opt.minDose : r0->minDosage;

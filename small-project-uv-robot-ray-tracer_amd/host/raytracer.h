@@ -104,6 +104,14 @@ public:
         double margin = 1e-6, relGap = 1e-3;
         int maxIterations = 200;       // cutting-plane rounds of the solver
         const unsigned char* mask = nullptr;    // uint8[T], 0 = not required
+        // S > 0: plan from the direct gather (include/uvrt.h "planning from the direct gather").  PlanDurations then runs,
+        // on this one context, exactly the launches ComputeDosageMap runs with gatherSamples = S for maxIterations
+        // iterations (every stop, then every segment when driving; seed = the launch counter from 0, photons_equiv =
+        // photonsPerLight; Shade after every iteration), each as uvrt_gather_direct -> uvrt_plan_capture_expected(column)
+        // -> uvrt_accumulate_expected(duration), into an exposure matrix of f64 expected counts; columns, bounds and N =
+        // maxIterations x photonsPerLight as for a counts plan.  A group of more than one instance, shardWorld > 1 and
+        // reduceOverComm are fatal.  0: photon counts (RayTracer::gatherSamples > 0 stays fatal there).
+        int gatherSamples = 0;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -144,10 +152,12 @@ public:
     // Shade is unchanged.  ComputeSegmentDosageMap does the same with from != to (and photonMapSize stays, as with
     // photons).  0 (default) is the reference's behaviour, bit for bit.  Saved as <gather_samples> in route files when
     // > 0.  ComputeIterationsBatched, launch sharding (shardWorld > 1) and PlanDurations refuse it: the gather runs per
-    // launch, on one context, and the planner's exposure matrix holds photon counts.
+    // launch, on one context, and a counts plan's exposure matrix holds photon counts.  To plan from the gather leave this
+    // at 0 and give PlanOptions::gatherSamples: the plan is then as good as the estimator.
     int gatherSamples = 0;
     unsigned gatherLaunches = 0;                    // gather launches since ResetDosageMap: the next launch's seed
 private:
+    int planGatherColumn = -1;                      // >= 0: GatherLaunch captures its plane into this column (PlanDurations)
     void GatherLaunch(const float from[3], const float to[3], float duration, int photonsPerLight, int triangleCount);
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool driving);
 public:

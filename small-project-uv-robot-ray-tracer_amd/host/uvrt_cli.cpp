@@ -40,6 +40,14 @@
 //                                           is S shadow rays per triangle towards the lamp, so the dim triangles that no photon
 //                                           reaches get an estimate too; one context, launch by launch: refused with --batch,
 //                                           --gpus > 1, --plan and --plan-drive
+//            [--plan-gather S]              plan (as --plan; with --plan MIN for that minimum, with --plan-drive V for a driven
+//                                           route) with the exposure from the direct gather, S in [1, 4096] shadow rays per
+//                                           triangle and launch (RayTracer::PlanOptions::gatherSamples): the triangles no photon
+//                                           reaches are planned for too.  --candidates, --min-photons, --dump and --verify-dump
+//                                           work as with --plan; --plan-verify recomputes with gatherSamples = S; --save-route
+//                                           saves the planned route with <gather_samples>S.  The plan is as good as the
+//                                           estimator: raise S or the margin for a tighter one.  One context,
+//                                           launch by launch: refused with --gather, --batch, --gpus > 1 and --plan-holdout
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -93,14 +101,19 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 }
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
-             const std::string& dump, const std::string& verifyDump)
+             const std::string& dump, const std::string& verifyDump, int planGather)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
     opt.minDose = minDose;
     opt.minPhotons = minPhotons;
+    opt.gatherSamples = planGather;
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
+    if (planGather > 0) {
+        rt.gatherSamples = planGather;       // the planned route is a gather route: --plan-verify and --save-route
+        printf("plan: exposure from the direct gather, %d samples per triangle and launch\n", planGather);
+    }
     const float m = minDose >= 0.0f ? minDose : rt.minDosage;
     printf("plan: %d positions, %d used, total duration %.9g (lower bound %.9g, gap %.3g), %s after %d iterations\n",
            r.positions, r.used_positions, r.total_duration, r.lower_bound, r.gap,
@@ -165,7 +178,7 @@ int main(int argc, char** argv)
     int iterations = -1, lamps = -1, device = 0, gpus = 1, batch = 0, flavour = 0;
     bool calibrate = false, plan = false, planVerify = false, planHoldout = false;
     float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f, planDrive = -1.0f;
-    int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1;
+    int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1, planGather = 0;
     uint32_t holdoutSeed = 0;
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -203,6 +216,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--drive-speed")) { need(1); driveSpeed = (float)atof(argv[++i]); if (!(driveSpeed >= 0.0f)) { fprintf(stderr, "--drive-speed must be >= 0\n"); return 2; } }
         else if (!strcmp(argv[i], "--plan-drive")) { need(1); plan = true; planDrive = (float)atof(argv[++i]); if (!(planDrive >= 0.0f)) { fprintf(stderr, "--plan-drive must be >= 0\n"); return 2; } }
         else if (!strcmp(argv[i], "--gather")) { need(1); gather = atoi(argv[++i]); if (gather < 0 || gather > 4096) { fprintf(stderr, "--gather must be in [0, 4096]\n"); return 2; } }
+        else if (!strcmp(argv[i], "--plan-gather")) { need(1); plan = true; planGather = atoi(argv[++i]); if (planGather < 1 || planGather > 4096) { fprintf(stderr, "--plan-gather must be in [1, 4096]\n"); return 2; } }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -210,6 +224,10 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
+    if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
+    if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
+    if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
+    if (planGather > 0 && planHoldout) { fprintf(stderr, "--plan-gather cannot be combined with --plan-holdout (a gather plan has no holdout seeds)\n"); return 2; }
     if (driveSpeed > 0.0f && plan) { fprintf(stderr, "--drive-speed cannot be combined with --plan (plan a driving route with --plan-drive V)\n"); return 2; }
     if (planDrive > 0.0f && gpus != 1) { fprintf(stderr, "--plan-drive runs on one context (--gpus 1)\n"); return 2; }
     if (driveSpeed > 0.0f && gpus != 1) { fprintf(stderr, "--drive-speed runs on one context (--gpus 1)\n"); return 2; }
@@ -259,7 +277,7 @@ int main(int argc, char** argv)
         }
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
-        const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump);
+        const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather);
         if (!saveRoute.empty()) {
             char name[32];
             strncpy(name, saveRoute.c_str(), 31);
