@@ -22,6 +22,18 @@ int fail(int code, const char* fmt, ...)
 
 }  // namespace uvrt_impl
 
+// (the streams are idle: uvrt_destroy has waited for them; a failed uvrt_create has enqueued zero fills only, which hipFree waits for)
+uvrt_ctx::~uvrt_ctx()
+{
+    plan_drop(this);
+    (void)hot_reset(this, false);
+    for (hipEvent_t e : {ev_fence, ev_mapfence}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+    if (host_flag) (void)hipHostFree(host_flag);
+    if (probe_stream) (void)hipStreamDestroy(probe_stream);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+}
+
 extern "C" {
 
 const char* uvrt_last_error(void) { return g_err.c_str(); }
@@ -75,7 +87,7 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(UVRT_ERR_NO_DEVICE, "uvrt_create: device %d is %s, this library is built for gfx950 only",
                     device_id, prop.gcnArchName);
-    uvrt_ctx* c = new uvrt_ctx();
+    std::unique_ptr<uvrt_ctx> c(new uvrt_ctx());      // every error return below destroys what it has made so far
     c->device = device_id;
     c->hot.reserve(uvrt_ctx::HOT_MAX);         // entries are referred to by pointer while their set-up is pending
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -106,29 +118,20 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     if (const char* e = getenv("UVRT_HOT_SAMPLE")) { const int v = atoi(e); if (v >= 256 && v <= (1 << 20)) c->hot_sample = v; }
     if (const char* e = getenv("UVRT_HOT_DIRECT")) { const int v = atoi(e); if (v >= 0 && v <= 8192) c->hot_direct = v; }
     if (const char* e = getenv("UVRT_HOT_TAIL")) { const int v = atoi(e); if (v >= 0 && v < 64) c->hot_tail = v; }
-    int rc = c->error_flag.ensure(256, true, c->stream);      // (a developer build keeps trip statistics behind the flag)
+    if (int rc = c->error_flag.ensure(256, true, c->stream)) return rc;      // (a developer build keeps trip statistics behind the flag)
 #ifndef UVRT_TRIP_STATS
     // the stack-overflow flag lives in pinned host memory the kernels can write: uvrt_sync reads it after the stream sync
     // instead of copying a device word back (a pageable 4-byte copy cost every sync ~10 us)
-    if (!rc) {
-        void* hp = nullptr;
-        void* dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-            if (hp) (void)hipHostFree(hp);
-            delete c;
-            return fail(UVRT_ERR_HIP, "uvrt_create: cannot allocate the pinned error flag");
-        }
-        memset(hp, 0, 64);
-        c->host_flag = (uint32_t*)hp;
-        c->host_flag_dev = (uint32_t*)dp;
-    }
+    void* dp = nullptr;
+    HIP_TRY(hipHostMalloc((void**)&c->host_flag, 64, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer(&dp, c->host_flag, 0));
+    memset(c->host_flag, 0, 64);
+    c->host_flag_dev = (uint32_t*)dp;
 #endif
     // lane 0's overflow stack: 256 CUs x 16 workgroups x 256 threads x 24 entries, the largest persistent grid (side lanes
     // get theirs, side_ovf_bytes(), with their first launch)
-    if (!rc) rc = c->lanes[0].ovf.ensure((size_t)OVF_MAX_ENTRIES * sizeof(uint32_t), false, c->stream);
-    if (rc) { delete c; return rc; }
-    *out = c;
+    if (int rc = c->lanes[0].ovf.ensure((size_t)OVF_MAX_ENTRIES * sizeof(uint32_t), false, c->stream)) return rc;
+    *out = c.release();
     return UVRT_OK;
 }
 
@@ -136,35 +139,11 @@ void uvrt_destroy(uvrt_ctx* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    // nothing is freed while a stream may still run work that reads it
     (void)hipStreamSynchronize(c->stream);
+    for (Lane& L : c->lanes) if (L.side) (void)hipStreamSynchronize(L.side);
+    if (c->probe_stream) (void)hipStreamSynchronize(c->probe_stream);
     if (c->comm) uvrt_comm_destroy(c);       // first: it restores the lanes' plain streams
-    plan_drop(c);
-    for (Lane& L : c->lanes) {
-        if (L.side) (void)hipStreamSynchronize(L.side);
-        for (DevBuf* b : {&L.rays, &L.recs, &L.counts, &L.ovf, &L.recs4, &L.oxz}) b->release();
-        if (L.ev_tail) (void)hipEventDestroy(L.ev_tail);
-        if (L.side) (void)hipStreamDestroy(L.side);
-    }
-    if (c->ev_fence) (void)hipEventDestroy(c->ev_fence);
-    if (c->ev_mapfence) (void)hipEventDestroy(c->ev_mapfence);
-    c->quads.release();
-    c->free_recs.release();
-    for (DevBuf* b : {&c->g_oxz, &c->g_tmax, &c->g_occ, &c->g_w, &c->g_tris, &c->expected}) b->release();
-    for (DevBuf& b : c->b_recs) b.release();
-    (void)hot_reset(c, false);            // (and the lanes' set-up scratch)
-    for (auto& bset : c->bs) {
-        for (DevBuf* b : {&bset.rays, &bset.planes, &bset.folded, &bset.oxz}) b->release();
-        if (bset.free_ev) (void)hipEventDestroy(bset.free_ev);
-    }
-    for (DevBuf* b : {&c->pairs, &c->perm, &c->ltris, &c->leaf_count, &c->area, &c->photon_map, &c->max_map,
-                      &c->dosage, &c->color, &c->keyrank, &c->sorted,
-                      &c->order, &c->hits, &c->hist, &c->bin_start, &c->export_buf, &c->error_flag})
-        b->release();
-    for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    if (c->host_flag) (void)hipHostFree(c->host_flag);
-    if (c->probe_stream) { (void)hipStreamSynchronize(c->probe_stream); (void)hipStreamDestroy(c->probe_stream); }
-    c->probe_out.release();
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
@@ -360,23 +339,19 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     for (Lane& L : c->lanes) L.recs4.release();          // sized per scene; rebuilt on demand (uvrt_set_wide_bvh)
     HIP_TRY(hipMemcpyAsync(c->leaf_count.p, leaf_count.data(), (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
     // staging copies of the reference-layout arrays for the device-side preparation kernel
-    DevBuf d_tris, d_idx;
-    if ((rc = d_tris.ensure((size_t)T * 64, false, c->stream))) return rc;
-    if ((rc = d_idx.ensure((size_t)T * 4, false, c->stream))) { d_tris.release(); return rc; }
-    hipError_t e1 = hipMemcpyAsync(d_tris.p, tris64, (size_t)T * 64, hipMemcpyHostToDevice, c->stream);
-    hipError_t e2 = hipMemcpyAsync(d_idx.p, tri_idx, (size_t)T * 4, hipMemcpyHostToDevice, c->stream);
-    if (e1 == hipSuccess && e2 == hipSuccess) {
+    {
+        DevBuf d_tris, d_idx;
+        if ((rc = d_tris.ensure((size_t)T * 64, false, c->stream))) return rc;
+        if ((rc = d_idx.ensure((size_t)T * 4, false, c->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_tris.p, tris64, (size_t)T * 64, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_idx.p, tri_idx, (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
         launch_prepare_scene(d_tris.as<float4>(), d_idx.as<uint32_t>(), c->ltris.as<LeafTri>(),
                              c->area.as<float>(), T, c->stream);
         for (int l = 0; l < c->nlanes; ++l)
             launch_prepare_leaves6(c->ltris.as<LeafTri>(), c->lanes[l].recs.p, (int32_t)pairs.size(), T, c->stream);
-        e1 = hipGetLastError();
-        e2 = hipStreamSynchronize(c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    d_tris.release();
-    d_idx.release();
-    if (e1 != hipSuccess) return fail(UVRT_ERR_HIP, "uvrt_set_scene: %s", hipGetErrorString(e1));
-    if (e2 != hipSuccess) return fail(UVRT_ERR_HIP, "uvrt_set_scene: %s", hipGetErrorString(e2));
     c->T = T;
     c->root_ref = root_ref;
     c->top_pairs = top_pairs;
@@ -398,7 +373,6 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     // a batch of the previous scene is void; its buffers are sized per scene
     c->b_count = 0;
     c->b_is_folded = false;
-    for (DevBuf& b : c->b_recs) b.release();
     c->b_recs.clear();
     c->b_recs_key.clear();
     for (auto& bset : c->bs) for (DevBuf* b : {&bset.planes, &bset.folded}) b->release();
@@ -409,7 +383,7 @@ int uvrt_resize_rays(uvrt_ctx* c, int64_t photon_count)
 {
     if (!c || photon_count < 0) return fail(UVRT_ERR_INVALID, "uvrt_resize_rays: bad argument");
     if (int rc = set_device(c)) return rc;
-    if (photon_count == c->capacity && c->lanes[0].rays.p && (!c->record_hits || c->hits.p)) { c->last_n = -1; return UVRT_OK; }
+    if (photon_count == c->capacity && c->lanes[0].rays.p && (!c->record_hits || c->hits.p)) { c->last = {}; return UVRT_OK; }
     if (int rcj = join_all(c)) return rcj;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->lane = 0;
@@ -423,7 +397,7 @@ int uvrt_resize_rays(uvrt_ctx* c, int64_t photon_count)
     if (c->record_hits && (rc = c->hits.ensure(n * 8, false, c->stream))) return rc;
     for (Lane& L : c->lanes) L.oxz.release();         // [capacity]: back with the lane's next free launch
     c->capacity = photon_count;
-    c->last_n = -1;
+    c->last = {};
     return UVRT_OK;
 }
 
@@ -472,8 +446,7 @@ int uvrt_set_record_perm(uvrt_ctx* c, const uint32_t* perm, int32_t n)
     }
     if (n == 0) { c->have_perm = false; return UVRT_OK; }
     if (int rc = c->perm.ensure((size_t)n * 4, false, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->perm.p, perm, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = copy_sync(c, c->perm.p, perm, (size_t)n * 4, hipMemcpyHostToDevice)) return rc;
     c->have_perm = true;
     c->perm_gen = ++c->perm_clock;       // same address, another renumbering: records prepared from the old one are stale
     return UVRT_OK;
@@ -487,9 +460,7 @@ int uvrt_read_record_perm(uvrt_ctx* c, uint32_t* out, int32_t n)
     if (int rc = join_all(c)) return rc;
     const uint32_t* pm = c->have_perm ? c->perm.as<uint32_t>() : cur_lane(c).perm;
     if (!pm) { for (int32_t i = 0; i < n; ++i) out[i] = (uint32_t)i; return UVRT_OK; }
-    HIP_TRY(hipMemcpyAsync(out, pm, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return copy_sync(c, out, pm, (size_t)n * 4, hipMemcpyDeviceToHost);
 }
 
 int uvrt_sync(uvrt_ctx* c)
@@ -540,28 +511,23 @@ int uvrt_sync(uvrt_ctx* c)
     return UVRT_OK;
 }
 
-static int read_back(uvrt_ctx* c, const DevBuf& b, size_t elem, void* out, int64_t first, int64_t count,
-                     int64_t limit, const char* what)
+// a range of one of the context's per-triangle arrays
+static int read_back(uvrt_ctx* c, const DevBuf* b, size_t elem, void* out, int64_t first, int64_t count, const char* what)
 {
-    if (!c || !out || first < 0 || count < 0 || first + count > limit)
+    const int64_t limit = c ? c->T : 0;
+    if (!c || !range_ok(out, first, count, limit))
         return fail(UVRT_ERR_INVALID, "%s: range [%lld,+%lld) outside [0,%lld)", what, (long long)first,
                     (long long)count, (long long)limit);
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    if (count == 0) return UVRT_OK;
-    HIP_TRY(hipMemcpyAsync(out, (const char*)b.p + (size_t)first * elem, (size_t)count * elem,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return range_copy(c, b->p, elem, out, first, count, hipMemcpyDeviceToHost);
 }
 
 int uvrt_read_dosage(uvrt_ctx* c, float* out, int32_t first, int32_t count)
 {
-    return read_back(c, c ? c->dosage : DevBuf(), 4, out, first, count, c ? c->T : 0, "uvrt_read_dosage");
+    return read_back(c, c ? &c->dosage : nullptr, 4, out, first, count, "uvrt_read_dosage");
 }
 int uvrt_read_color(uvrt_ctx* c, float* out9, int32_t first, int32_t count)
 {
-    return read_back(c, c ? c->color : DevBuf(), 36, out9, first, count, c ? c->T : 0, "uvrt_read_color");
+    return read_back(c, c ? &c->color : nullptr, 36, out9, first, count, "uvrt_read_color");
 }
 int uvrt_read_counts(uvrt_ctx* c, int32_t* out, int32_t first, int32_t count)
 {
@@ -571,14 +537,14 @@ int uvrt_read_counts(uvrt_ctx* c, int32_t* out, int32_t first, int32_t count)
         launch_fold_counts(cur_lane(c).counts.as<int32_t>(), c->replicas, c->T, c->T, c->stream);
         if (int rc = mark_fence(c)) return rc;
     }
-    return read_back(c, c ? cur_lane(c).counts : DevBuf(), 4, out, first, count, c ? c->T : 0, "uvrt_read_counts");
+    return read_back(c, c ? &cur_lane(c).counts : nullptr, 4, out, first, count, "uvrt_read_counts");
 }
 int uvrt_read_photon_map(uvrt_ctx* c, int32_t which, double* out, int32_t first, int32_t count)
 {
     if (which != UVRT_MAP_SUM && which != UVRT_MAP_MAX)
         return fail(UVRT_ERR_INVALID, "uvrt_read_photon_map: which_map must be 0 or 1");
-    return read_back(c, c ? (which == UVRT_MAP_SUM ? c->photon_map : c->max_map) : DevBuf(), 8, out, first,
-                     count, c ? c->T : 0, "uvrt_read_photon_map");
+    return read_back(c, c ? (which == UVRT_MAP_SUM ? &c->photon_map : &c->max_map) : nullptr, 8, out, first,
+                     count, "uvrt_read_photon_map");
 }
 
 int uvrt_get_seed(uvrt_ctx* c, uint32_t* seed)
@@ -664,21 +630,19 @@ int uvrt_set_timing(uvrt_ctx* c, int32_t on)
 
 int uvrt_read_rays(uvrt_ctx* c, void* rays32, int64_t first, int64_t count)
 {
-    if (!c || !rays32 || c->last_n < 0 || first < 0 || count < 0 || first + count > c->last_n)
+    if (!c || !rays32 || c->last.n < 0 || first < 0 || count < 0 || first + count > c->last.n)
         return fail(UVRT_ERR_INVALID, "uvrt_read_rays: range outside the last generate");
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     if (count == 0) return UVRT_OK;
     if (int rc = c->export_buf.ensure((size_t)count * 32, false, c->stream)) return rc;
-    const uint2* hits = (c->last_extended && c->hits.p) ? c->hits.as<uint2>() : nullptr;
-    if (c->last_free)
+    const uint2* hits = (c->last.extended && c->hits.p) ? c->hits.as<uint2>() : nullptr;
+    if (c->last.free_rays)
         launch_export_free_rays(cur_lane(c).rays.as<float4>(), cur_lane(c).oxz.as<float2>(), hits, c->export_buf.p, first, count, c->stream);
     else
         launch_export_rays(cur_lane(c).rays.as<float4>(), hits, c->export_buf.p, c->ox, c->oz, first, count, c->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rays32, c->export_buf.p, (size_t)count * 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return copy_sync(c, rays32, c->export_buf.p, (size_t)count * 32, hipMemcpyDeviceToHost);
 }
 
 int uvrt_write_rays(uvrt_ctx* c, const void* rays32, int64_t n)
@@ -686,28 +650,20 @@ int uvrt_write_rays(uvrt_ctx* c, const void* rays32, int64_t n)
     if (!c || !rays32 || n <= 0 || n > c->capacity)
         return fail(UVRT_ERR_INVALID, "uvrt_write_rays: n must be in (0, capacity]");
     if (int rc = set_device(c)) return rc;
-    struct HostRay { float d[3], o[3], dist; uint32_t tri; };
     const HostRay* hr = (const HostRay*)rays32;
-    std::vector<float> packed((size_t)n * 4);
-    for (int64_t i = 0; i < n; ++i) {
+    for (int64_t i = 0; i < n; ++i)
         if (memcmp(&hr[i].o[0], &hr[0].o[0], 4) != 0 || memcmp(&hr[i].o[2], &hr[0].o[2], 4) != 0)
             return fail(UVRT_ERR_INVALID, "uvrt_write_rays: record %lld has a different orig.x/orig.z", (long long)i);
-        packed[4 * i + 0] = hr[i].d[0]; packed[4 * i + 1] = hr[i].d[1];
-        packed[4 * i + 2] = hr[i].d[2]; packed[4 * i + 3] = hr[i].o[1];
-    }
+    std::vector<float> packed;
+    unpack_rays(hr, n, packed);
     if (int rc = join_all(c)) return rc;
     c->lane = 0;
     c->cur_pipelined = false;
     Lane& L = c->lanes[0];
-    HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = copy_sync(c, L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice)) return rc;
     L.recs_tag.valid = false;
     L.perm = nullptr;
-    c->last_n = n;
-    c->last_first = 0;
-    c->last_sorted = false;
-    c->last_extended = false;
-    c->last_free = false;
+    c->last = {n, 0, false, false, false};
     c->ox = hr[0].o[0];
     c->oz = hr[0].o[2];
     return UVRT_OK;
@@ -772,7 +728,7 @@ int uvrt_extend_time_ms(uvrt_ctx* c, double* ms, int64_t* launches)
     double total = 0;
     for (size_t i = 0; i < c->ev_used; ++i) {
         float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, c->ev_pool[i].first, c->ev_pool[i].second));
+        HIP_TRY(hipEventElapsedTime(&t, c->ev_pool[2 * i], c->ev_pool[2 * i + 1]));
         total += t;
     }
     *ms = total;

@@ -149,7 +149,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             DevBuf b;
             if ((rc = b.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream))) return rc;
             launch_prepare_leaves6(c->ltris.as<LeafTri>(), b.p, c->npairs, c->T, c->stream);
-            c->b_recs.push_back(b);
+            c->b_recs.push_back(std::move(b));
         }
         c->b_recs_key.resize(c->b_recs.size());
         for (int l = 1; l <= c->batch_lanes; ++l)
@@ -163,12 +163,9 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             launch_prepare_launch6(c->pairs.as<PairRec>(), c->b_recs[g].p, gx[g], gz[g], c->npairs, gperm[g], c->stream);
             key = {{true, gx[g], gz[g]}, gperm[g], ggen[g]};
         }
-        // the scene's free records, on first use (ensure_free_buffers, uvrt_capi_free.hip)
-        if (nsweeps > 0 && !c->free_recs_valid) {
-            if ((rc = c->free_recs.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream))) return rc;
-            launch_prepare_free_records(c->pairs.as<PairRec>(), c->ltris.as<LeafTri>(), c->free_recs.p, c->npairs, c->T, c->stream);
-            c->free_recs_valid = true;
-        }
+        // the scene's free records, on first use (the lanes are joined above, the fence below covers them)
+        if (nsweeps > 0 && !c->free_recs_valid)
+            if ((rc = make_free_records(c))) return rc;
         HIP_TRY(hipGetLastError());
         if (int rcf = mark_fence(c)) return rcf;         // the lanes' next work waits for the records
     }
@@ -183,21 +180,36 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         uvrt_ctx* c; int lane; uint64_t chunks; bool armed;
         ~LaneGuard() { if (armed) { c->lane = lane; c->b_chunks = chunks; } }
     } guard{c, c->lane, c->b_chunks, true};
-    int chunk_index = 0;
+    // The lane of the next chunk.  Two SIDE lanes in turn: the context's own stream carries the fold / reduce / replay of the
+    // previous batch, which a chunk enqueued there would have to wait for.  The chunk's rays depend on nothing but their
+    // buffer: generate goes to the lane's stream (*ls) BEFORE the lane waits for the context's stream (lane_stream: new
+    // records, a hot-record set-up), so it runs beside them.
+    auto next_chunk_lane = [&](hipStream_t* ls) -> int {
+        c->lane = c->pipeline ? 1 + (int)(c->b_chunks++ % (uint64_t)c->batch_lanes) : 0;
+        *ls = stream_of(c, c->lane);
+        if (c->lane != 0) cur_lane(c).used = true;
+        if (!lane_waited[c->lane]) {      // the set's previous occupant has been replayed (two batches back)
+            HIP_TRY(hipStreamWaitEvent(*ls, S.free_ev, 0));
+            lane_waited[c->lane] = true;
+        }
+        return UVRT_OK;
+    };
+    // what the fused extend of a chunk of kc planes from physical plane ph0 on gets besides its rays and records
+    auto set_planes = [&](ExtendParams& p, int ph0, int kc) {
+        p.counts = S.planes.as<int32_t>() + (size_t)ph0 * plane_ints;
+        p.count_replicas = R;
+        p.count_stride = c->T;
+        p.n = (int64_t)kc * n_pad;
+        p.plane_batches = (uint32_t)(n_pad / 64);
+        p.plane_n = (uint32_t)n;
+        p.plane_stride = (uint32_t)plane_ints;
+    };
+    const int per_cu = variant_per_cu(c->variant, c->pipeline ? 7 : 8);
     for (int g = 0; g < ngroups; ++g) {
-        for (int k0 = 0; k0 < gsize[g]; k0 += per_chunk, ++chunk_index) {
+        for (int k0 = 0; k0 < gsize[g]; k0 += per_chunk) {
             const int kc = std::min(per_chunk, gsize[g] - k0), ph0 = gfirst[g] + k0;
-            // two SIDE lanes in turn: the context's own stream carries the fold / reduce / replay of the previous batch,
-            // which a chunk enqueued there would have to wait for
-            c->lane = c->pipeline ? 1 + (int)(c->b_chunks++ % (uint64_t)c->batch_lanes) : 0;
-            // the chunk's rays depend on nothing but their buffer: generate goes to the lane BEFORE the lane waits for the
-            // context's stream (new records, a hot-record set-up), so it runs beside them
-            hipStream_t ls = stream_of(c, c->lane);
-            if (c->lane != 0) cur_lane(c).used = true;
-            if (!lane_waited[c->lane]) {      // the set's previous occupant has been replayed (two batches back)
-                HIP_TRY(hipStreamWaitEvent(ls, S.free_ev, 0));
-                lane_waited[c->lane] = true;
-            }
+            hipStream_t ls;
+            if (int rcl = next_chunk_lane(&ls)) return rcl;
             GenBatchParams gq;
             memset(&gq, 0, sizeof gq);
             gq.rays = S.rays.as<float4>() + (size_t)ph0 * (size_t)n_pad;
@@ -219,37 +231,21 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             ExtendParams p;
             fill_launch(c, p, gx[g], gz[g]);
             p.rays = gq.rays;
-            p.counts = S.planes.as<int32_t>() + (size_t)ph0 * plane_ints;
-            p.count_replicas = R;
-            p.count_stride = c->T;
-            p.n = (int64_t)kc * n_pad;
+            set_planes(p, ph0, kc);
             p.recs = c->b_recs[g].p;
             p.perm = gperm[g];
             p.recs_prepared = 1;
-            p.plane_batches = (uint32_t)(n_pad / 64);
-            p.plane_n = (uint32_t)n;
-            p.plane_stride = (uint32_t)plane_ints;
-            hipEvent_t e1;
-            if (int rct = timing_start(c, ls, &e1)) return rct;
-            if (!launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, c->pipeline ? 7 : 8), ls)) {
-                return fail(UVRT_ERR_INVALID, "%s: variant %d needs a larger overflow-stack buffer", who, c->variant);
-            }
-            HIP_TRY(hipGetLastError());
-            if (e1) HIP_TRY(hipEventRecord(e1, ls));
+            if (int rct = timed_launch(c, ls, who, "the stops' launch", [&] { return launch_extend6(p, variant_code6(c->variant), per_cu, ls); }))
+                return rct;
         }
     }
     // The sweeps: one further group (the free records are the scene's, whatever the segment), in chunks of as many bytes --
     // 16 B of ray plus 8 B of origin per photon -- over the same lanes in the same rotation.
     const int per_sweep_chunk = (int)std::max<size_t>(1, c->batch_chunk_bytes / ((size_t)n_pad * 24));
-    for (int k0 = 0; k0 < nsweeps; k0 += per_sweep_chunk, ++chunk_index) {
+    for (int k0 = 0; k0 < nsweeps; k0 += per_sweep_chunk) {
         const int kc = std::min(per_sweep_chunk, nsweeps - k0), ph0 = nstops + k0;
-        c->lane = c->pipeline ? 1 + (int)(c->b_chunks++ % (uint64_t)c->batch_lanes) : 0;
-        hipStream_t ls = stream_of(c, c->lane);
-        if (c->lane != 0) cur_lane(c).used = true;
-        if (!lane_waited[c->lane]) {
-            HIP_TRY(hipStreamWaitEvent(ls, S.free_ev, 0));
-            lane_waited[c->lane] = true;
-        }
+        hipStream_t ls;
+        if (int rcl = next_chunk_lane(&ls)) return rcl;
         SweepBatchParams sq;
         memset(&sq, 0, sizeof sq);
         sq.rays = S.rays.as<float4>() + (size_t)ph0 * (size_t)n_pad;
@@ -273,20 +269,10 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         fill_launch(c, fp.e, 0.0f, 0.0f);       // (force_exact: the scene's and the variant's conditions; the origins are per ray)
         fp.e.rays = sq.rays;
         fp.oxz = sq.oxz;
-        fp.e.counts = S.planes.as<int32_t>() + (size_t)ph0 * plane_ints;
-        fp.e.count_replicas = R;
-        fp.e.count_stride = c->T;
-        fp.e.n = (int64_t)kc * n_pad;
+        set_planes(fp.e, ph0, kc);
         fp.e.recs = c->free_recs.p;
-        fp.e.plane_batches = (uint32_t)(n_pad / 64);
-        fp.e.plane_n = (uint32_t)n;
-        fp.e.plane_stride = (uint32_t)plane_ints;
-        hipEvent_t e1;
-        if (int rct = timing_start(c, ls, &e1)) return rct;
-        if (!launch_extend_free_planes(fp, variant_per_cu(c->variant, c->pipeline ? 7 : 8), ls))
-            return fail(UVRT_ERR_INVALID, "%s: the free-ray launch needs a larger overflow-stack buffer than the context holds", who);
-        HIP_TRY(hipGetLastError());
-        if (e1) HIP_TRY(hipEventRecord(e1, ls));
+        if (int rct = timed_launch(c, ls, who, "the free-ray launch", [&] { return launch_extend_free_planes(fp, per_cu, ls); }))
+            return rct;
     }
 #ifdef UVRT_DEV_VARIANTS
     ++c->probe_batches;
@@ -295,7 +281,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     c->seed = seed_after;
     c->lane = 0;
     c->cur_pipelined = false;
-    c->last_n = -1;                      // the per-launch generate/extend pairing starts afresh
+    c->last = {};                        // the per-launch generate/extend pairing starts afresh
     c->b_set = set;
     c->b_repl = R;
     c->b_count = count;
@@ -391,12 +377,8 @@ int uvrt_read_batch_counts(uvrt_ctx* c, int32_t launch, int32_t* out, int32_t fi
     if (!c || c->b_count <= 0 || launch < 0 || launch >= c->b_count)
         return fail(UVRT_ERR_INVALID, "uvrt_read_batch_counts: no such launch in the traced batch");
     if (int rc = uvrt_fold_batch(c)) return rc;
-    if (!out || first < 0 || count < 0 || first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_read_batch_counts: bad range");
-    if (count == 0) return UVRT_OK;
-    HIP_TRY(hipMemcpyAsync(out, c->bs[c->b_set].folded.as<int32_t>() + (size_t)c->b_phys[launch] * c->T + first, (size_t)count * 4,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    if (!range_ok(out, first, count, c->T)) return fail(UVRT_ERR_INVALID, "uvrt_read_batch_counts: bad range");
+    return range_copy(c, c->bs[c->b_set].folded.as<int32_t>() + (size_t)c->b_phys[launch] * c->T, 4, out, first, count, hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

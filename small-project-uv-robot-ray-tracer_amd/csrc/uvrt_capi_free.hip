@@ -9,18 +9,22 @@ namespace uvrt_impl {
 
 // The scene's free records, made once per scene by the first launch that needs them (a free launch, a shadow-ray launch):
 // callers that never trace such rays do not pay for them.
+int make_free_records(uvrt_ctx* c)
+{
+    if (int rc = c->free_recs.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream)) return rc;
+    launch_prepare_free_records(c->pairs.as<PairRec>(), c->ltris.as<LeafTri>(), c->free_recs.p, c->npairs, c->T, c->stream);
+    c->free_recs_valid = true;
+    return UVRT_OK;
+}
+
 int ensure_free_records(uvrt_ctx* c)
 {
-    if (!c->free_recs_valid) {
-        // on the context's stream, behind everything outstanding; the lanes' later work waits for it (mark_fence)
-        if (int rc = join_all(c)) return rc;
-        if (int rc = c->free_recs.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream)) return rc;
-        launch_prepare_free_records(c->pairs.as<PairRec>(), c->ltris.as<LeafTri>(), c->free_recs.p, c->npairs, c->T, c->stream);
-        HIP_TRY(hipGetLastError());
-        if (int rc = mark_fence(c)) return rc;
-        c->free_recs_valid = true;
-    }
-    return UVRT_OK;
+    if (c->free_recs_valid) return UVRT_OK;
+    // on the context's stream, behind everything outstanding; the lanes' later work waits for it (mark_fence)
+    if (int rc = join_all(c)) return rc;
+    if (int rc = make_free_records(c)) return rc;
+    HIP_TRY(hipGetLastError());
+    return mark_fence(c);
 }
 
 // ... and the current lane's {orig.x, orig.z} array, made on the lane's first free launch
@@ -53,16 +57,13 @@ int extend_free(uvrt_ctx* c, int64_t n)
     fp.e.count_stride = c->T;
     fp.e.n = n;
     fp.e.recs = c->free_recs.p;
-    hipEvent_t e1;
-    if (int rc = timing_start(c, ls, &e1)) return rc;
     // the grid knob of uvrt_set_variant applies; the leaf period / cache code does not (one kernel)
     const int per_cu_default = (c->cur_pipelined && c->nlanes >= 4) ? 4 : c->cur_pipelined ? 7 : 8;
-    if (!launch_extend_free(fp, variant_per_cu(c->variant, per_cu_default), ls))
-        return fail(UVRT_ERR_INVALID, "uvrt_extend: the free-ray launch needs a larger overflow-stack buffer than the context holds");
-    HIP_TRY(hipGetLastError());
-    if (e1) HIP_TRY(hipEventRecord(e1, ls));
+    if (int rc = timed_launch(c, ls, "uvrt_extend", "the free-ray launch",
+                              [&] { return launch_extend_free(fp, variant_per_cu(c->variant, per_cu_default), ls); }))
+        return rc;
     L.counts_dirty = true;
-    c->last_extended = c->record_hits;
+    c->last.extended = c->record_hits;
     return UVRT_OK;
 }
 
@@ -84,27 +85,16 @@ int uvrt_write_free_rays(uvrt_ctx* c, const void* rays32, int64_t n)
         return fail(UVRT_ERR_INVALID, "uvrt_write_free_rays: n must be in (0, capacity]");
     if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_write_free_rays: no scene");
     if (int rc = set_device(c)) return rc;
-    struct HostRay { float d[3], o[3], dist; uint32_t tri; };
-    const HostRay* hr = (const HostRay*)rays32;
-    std::vector<float> packed((size_t)n * 4), oxz((size_t)n * 2);
-    for (int64_t i = 0; i < n; ++i) {
-        packed[4 * i + 0] = hr[i].d[0]; packed[4 * i + 1] = hr[i].d[1];
-        packed[4 * i + 2] = hr[i].d[2]; packed[4 * i + 3] = hr[i].o[1];
-        oxz[2 * i + 0] = hr[i].o[0]; oxz[2 * i + 1] = hr[i].o[2];
-    }
+    std::vector<float> packed, oxz;
+    unpack_rays((const HostRay*)rays32, n, packed, &oxz);
     if (int rc = join_all(c)) return rc;
     c->lane = 0;
     c->cur_pipelined = false;
     if (int rc = ensure_free_buffers(c, c->stream)) return rc;
     Lane& L = c->lanes[0];
     HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(L.oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->last_n = n;
-    c->last_first = 0;
-    c->last_sorted = false;
-    c->last_extended = false;
-    c->last_free = true;
+    if (int rc = copy_sync(c, L.oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice)) return rc;
+    c->last = {n, 0, false, false, true};
     return UVRT_OK;
 }
 
@@ -124,15 +114,7 @@ int uvrt_generate_sweep(uvrt_ctx* c, const float from[3], const float to[3], flo
     const uint32_t seed_prev = c->seed;
     const uint32_t seed_next = uvrt_seed_next_sweep(from, light_length, seed_prev);
     // launch lane: as uvrt_generate chooses it (ray ordering does not apply to free rays)
-    {
-        const bool pipe_ok = c->pipeline && c->nlanes > 1 && !c->record_hits && c->lanes[1].rays.p;
-        c->prev_lane = c->lane;
-        c->cur_pipelined = pipe_ok;
-        if (pipe_ok) c->lane = (c->lane + 1) % c->nlanes;
-        else { if (int rc = join_all(c)) return rc; c->lane = 0; }
-        if (c->lane != 0)
-            if (int rc = cur_lane(c).ovf.ensure(side_ovf_bytes(c), false, c->stream)) return rc;
-    }
+    if (int rc = next_launch_lane(c, true)) return rc;
     hipStream_t ls;
     if (int rc = lane_stream(c, &ls)) return rc;
     if (int rc = ensure_free_buffers(c, ls)) return rc;
@@ -152,11 +134,7 @@ int uvrt_generate_sweep(uvrt_ctx* c, const float from[3], const float to[3], flo
     launch_generate_sweep(p, ls);
     HIP_TRY(hipGetLastError());
     c->seed = seed_next;
-    c->last_n = n;
-    c->last_first = first_gid;
-    c->last_sorted = false;
-    c->last_extended = false;
-    c->last_free = true;
+    c->last = {n, first_gid, false, false, true};
     return UVRT_OK;
 }
 

@@ -9,9 +9,7 @@ namespace uvrt_impl {
 
 int ensure_expected(uvrt_ctx* c)
 {
-    if (c->expected.p) return UVRT_OK;
-    if (int rc = c->expected.ensure((size_t)c->T * 8, true, c->stream)) return rc;
-    return UVRT_OK;
+    return c->expected.ensure((size_t)c->T * 8, true, c->stream);      // (nothing to do once it is there)
 }
 
 // Everything a shadow-ray launch works on, on the context's stream behind all outstanding work: lane 0's ray buffer, the
@@ -21,9 +19,7 @@ int ensure_expected(uvrt_ctx* c)
 static int begin_shadow_launch(uvrt_ctx* c)
 {
     if (int rc = join_all(c)) return rc;
-    c->last_n = -1;                         // lane 0's rays are about to be overwritten
-    c->last_extended = false;
-    c->last_free = false;
+    c->last = {};                           // lane 0's rays are about to be overwritten
     if (int rc = ensure_free_records(c)) return rc;
     const size_t cap = (size_t)std::max<int64_t>(c->capacity, 1);
     if (int rc = c->g_oxz.ensure(cap * 8, false, c->stream)) return rc;
@@ -47,13 +43,8 @@ static int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who)
     op.occluded = c->g_occ.as<uint8_t>();
     op.e.n = n;
     op.e.recs = c->free_recs.p;
-    hipEvent_t e1;
-    if (int rc = timing_start(c, c->stream, &e1)) return rc;
-    if (!launch_occlude_free(op, variant_per_cu(c->variant, 8), c->stream))
-        return fail(UVRT_ERR_INVALID, "%s: the shadow-ray launch needs a larger overflow-stack buffer than the context holds", who);
-    HIP_TRY(hipGetLastError());
-    if (e1) HIP_TRY(hipEventRecord(e1, c->stream));
-    return UVRT_OK;
+    return timed_launch(c, c->stream, who, "the shadow-ray launch",
+                        [&] { return launch_occlude_free(op, variant_per_cu(c->variant, 8), c->stream); });
 }
 
 }  // namespace uvrt_impl
@@ -71,24 +62,15 @@ int uvrt_occluded(uvrt_ctx* c, const void* rays32, int64_t n, uint8_t* out)
                     (long long)c->capacity);
     if (n == 0) return UVRT_OK;
     if (int rc = set_device(c)) return rc;
-    struct HostRay { float d[3], o[3], dist; uint32_t tri; };
-    const HostRay* hr = (const HostRay*)rays32;
-    std::vector<float> packed((size_t)n * 4), oxz((size_t)n * 2), tmax((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        packed[4 * i + 0] = hr[i].d[0]; packed[4 * i + 1] = hr[i].d[1];
-        packed[4 * i + 2] = hr[i].d[2]; packed[4 * i + 3] = hr[i].o[1];
-        oxz[2 * i + 0] = hr[i].o[0]; oxz[2 * i + 1] = hr[i].o[2];
-        tmax[i] = hr[i].dist;
-    }
+    std::vector<float> packed, oxz, tmax;
+    unpack_rays((const HostRay*)rays32, n, packed, &oxz, &tmax);
     if (int rc = begin_shadow_launch(c)) return rc;
     Lane& L = c->lanes[0];
     HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->g_oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->g_tmax.p, tmax.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (int rc = trace_shadow_rays(c, n, "uvrt_occluded")) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->g_occ.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return copy_sync(c, out, c->g_occ.p, (size_t)n, hipMemcpyDeviceToHost);
 }
 
 int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first_tri, int32_t tri_count)
@@ -160,34 +142,26 @@ int uvrt_accumulate_expected(uvrt_ctx* c, float time_step, int32_t tri_count)
     return mark_map_fence(c);                    // later accumulate / Shade work on a side lane waits for it
 }
 
+// uvrt_read_expected / uvrt_write_expected: a range of the expected plane (made, zeroed, by whichever call comes first)
+static int expected_range(uvrt_ctx* c, const char* who, void* host, int32_t first, int32_t count, hipMemcpyKind kind)
+{
+    if (!c || !host) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
+    if (!range_ok(host, first, count, c->T))
+        return fail(UVRT_ERR_INVALID, "%s: range [%d,+%d) outside [0,%d)", who, first, count, c->T);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = ensure_expected(c)) return rc;
+    return range_copy(c, c->expected.p, 8, host, first, count, kind);
+}
+
 int uvrt_read_expected(uvrt_ctx* c, double* out, int32_t first, int32_t count)
 {
-    if (!c || !out) return fail(UVRT_ERR_INVALID, "uvrt_read_expected: null argument");
-    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_read_expected: no scene");
-    if (first < 0 || count < 0 || (int64_t)first + count > c->T)
-        return fail(UVRT_ERR_INVALID, "uvrt_read_expected: range [%d,+%d) outside [0,%d)", first, count, c->T);
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    if (int rc = ensure_expected(c)) return rc;
-    if (count == 0) return UVRT_OK;
-    HIP_TRY(hipMemcpyAsync(out, (const char*)c->expected.p + (size_t)first * 8, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return expected_range(c, "uvrt_read_expected", out, first, count, hipMemcpyDeviceToHost);
 }
 
 int uvrt_write_expected(uvrt_ctx* c, const double* in, int32_t first, int32_t count)
 {
-    if (!c || !in) return fail(UVRT_ERR_INVALID, "uvrt_write_expected: null argument");
-    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_write_expected: no scene");
-    if (first < 0 || count < 0 || (int64_t)first + count > c->T)
-        return fail(UVRT_ERR_INVALID, "uvrt_write_expected: range [%d,+%d) outside [0,%d)", first, count, c->T);
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    if (int rc = ensure_expected(c)) return rc;
-    if (count == 0) return UVRT_OK;
-    HIP_TRY(hipMemcpyAsync((char*)c->expected.p + (size_t)first * 8, in, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return expected_range(c, "uvrt_write_expected", const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
 }
 
 }  // extern "C"

@@ -11,7 +11,6 @@ int hot_reset(uvrt_ctx* c, bool slab)
 {
     for (auto& h : c->hot) (void)hipEventDestroy(h.ready);
     c->hot.clear();
-    for (DevBuf& b : c->hot_slabs) b.release();
     c->hot_slabs.clear();
     for (Lane& L : c->lanes) { L.hot_hist.release(); L.hot_list.release(); L.perm = nullptr; }
     if (!slab || c->npairs <= 128) return UVRT_OK;
@@ -167,17 +166,8 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
 
     int bits = c->sort_bits < 0 ? auto_sort_bits(n) : c->sort_bits;
     if (bits > 20) bits = 20;
-    // launch lane: alternate between the two streams / buffer sets when nothing stands against it
-    {
-        const bool pipe_ok = c->pipeline && c->nlanes > 1 && !c->record_hits && bits == 0 &&
-                             c->lanes[1].rays.p;
-        c->prev_lane = c->lane;
-        c->cur_pipelined = pipe_ok;
-        if (pipe_ok) c->lane = (c->lane + 1) % c->nlanes;
-        else { if (int rc = join_all(c)) return rc; c->lane = 0; }
-        if (c->lane != 0)
-            if (int rc = cur_lane(c).ovf.ensure(side_ovf_bytes(c), false, c->stream)) return rc;
-    }
+    // launch lane: alternate between the two streams / buffer sets when nothing stands against it (ray ordering does)
+    if (int rc = next_launch_lane(c, bits == 0)) return rc;
     Lane& L = cur_lane(c);
     hipStream_t ls;
     if (int rc = lane_stream(c, &ls)) return rc;
@@ -227,11 +217,7 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
         HIP_TRY(hipGetLastError());
     }
     c->seed = seed_next;
-    c->last_n = n;
-    c->last_first = first_gid;
-    c->last_sorted = p.keyrank != nullptr;
-    c->last_extended = false;
-    c->last_free = false;
+    c->last = {n, first_gid, p.keyrank != nullptr, false, false};
     c->ox = lp[0];
     c->oz = lp[2];
     return UVRT_OK;
@@ -240,11 +226,11 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
 int uvrt_extend(uvrt_ctx* c, int64_t n)
 {
     if (!c || !c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_extend: no scene");
-    if (c->last_n < 0 || n != c->last_n)
+    if (c->last.n < 0 || n != c->last.n)
         return fail(UVRT_ERR_INVALID, "uvrt_extend: n = %lld does not match the last generate (%lld)",
-                    (long long)n, (long long)c->last_n);
+                    (long long)n, (long long)c->last.n);
     if (int rc = set_device(c)) return rc;
-    if (c->last_free) return extend_free(c, n);      // rays with origins of their own: the free-origin kernel, whatever the walk / ordering knobs say
+    if (c->last.free_rays) return extend_free(c, n);      // rays with origins of their own: the free-origin kernel, whatever the walk / ordering knobs say
     if (c->record_hits) {
         if (int rc = c->hits.ensure((size_t)c->capacity * 8, false, c->stream)) return rc;
     }
@@ -253,8 +239,8 @@ int uvrt_extend(uvrt_ctx* c, int64_t n)
     fill_launch(c, p, c->ox, c->oz);
     hipStream_t ls;
     if (int rc = lane_stream(c, &ls)) return rc;
-    p.rays = c->last_sorted ? c->sorted.as<float4>() : L.rays.as<float4>();
-    p.order = c->last_sorted ? c->order.as<uint32_t>() : nullptr;
+    p.rays = c->last.sorted ? c->sorted.as<float4>() : L.rays.as<float4>();
+    p.order = c->last.sorted ? c->order.as<uint32_t>() : nullptr;
     p.hits = c->record_hits ? c->hits.as<uint2>() : nullptr;
     p.counts = L.counts.as<int32_t>();
     p.count_replicas = c->replicas;
@@ -263,37 +249,40 @@ int uvrt_extend(uvrt_ctx* c, int64_t n)
     p.recs = L.recs.p;
     p.perm = c->have_perm ? c->perm.as<uint32_t>() : L.perm;
     p.recs_prepared = L.recs_tag.matches(c->ox, c->oz) ? 1 : 0;
-    hipEvent_t e1;
-    if (int rc = timing_start(c, ls, &e1)) return rc;
     if (c->wide && c->nquads > 0) {
         // the opt-in 4-wide walk: its per-launch records are (re)made here when the lane's are for another lamp
-        if (!L.recs4.p) {
+        const bool new_recs4 = !L.recs4.p;
+        if (new_recs4)
             if (int rc = L.recs4.ensure(((size_t)2 * c->nquads + (size_t)c->T + 1) * 64, true, ls)) return rc;
-            launch_prepare_leaves6(c->ltris.as<LeafTri>(), L.recs4.p, 2 * c->nquads, c->T, ls);
-            L.recs4_tag.valid = false;
-        }
-        if (!L.recs4_tag.matches(c->ox, c->oz)) {
-            launch_prepare_launch4(c->quads.as<QuadRec>(), L.recs4.p, c->ox, c->oz, c->nquads, ls);
-            L.recs4_tag = {true, c->ox, c->oz};
-        }
         p.recs4 = L.recs4.p;
         p.nquads = c->nquads;
         p.top_quads = c->top_quads;
         p.refill_min = 8;
-        if (!launch_extend4(p, 7, ls)) return fail(UVRT_ERR_INVALID, "uvrt_extend: overflow-stack buffer too small for the 4-wide kernel");
+        if (int rc = timed_launch(c, ls, "uvrt_extend", "the 4-wide kernel", [&] {
+                if (new_recs4) {
+                    launch_prepare_leaves6(c->ltris.as<LeafTri>(), L.recs4.p, 2 * c->nquads, c->T, ls);
+                    L.recs4_tag.valid = false;
+                }
+                if (!L.recs4_tag.matches(c->ox, c->oz)) {
+                    launch_prepare_launch4(c->quads.as<QuadRec>(), L.recs4.p, c->ox, c->oz, c->nquads, ls);
+                    L.recs4_tag = {true, c->ox, c->oz};
+                }
+                return launch_extend4(p, 7, ls);
+            }))
+            return rc;
     } else {
         // default grid: 8 workgroups per CU on one stream (20 KB of LDS each: eight fit a CU); 7 when launches are
         // pipelined over several streams -- the free slot per CU lets the first workgroups of the next launch and the
         // small kernels around it (generate, accumulate, replay) run at once instead of queueing behind persistent waves
         // (profiles/r02/r02_experiments.txt); with four launch lanes 4 per CU
         const int per_cu_default = (c->cur_pipelined && c->nlanes >= 4) ? 4 : c->cur_pipelined ? 7 : 8;
-        if (!launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, per_cu_default), ls))
-            return fail(UVRT_ERR_INVALID, "uvrt_extend: variant %d needs a larger overflow-stack buffer than the context holds", c->variant);
+        if (int rc = timed_launch(c, ls, "uvrt_extend", "the launch", [&] {
+                return launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, per_cu_default), ls);
+            }))
+            return rc;
     }
-    HIP_TRY(hipGetLastError());
-    if (e1) HIP_TRY(hipEventRecord(e1, ls));
     L.counts_dirty = true;
-    c->last_extended = c->record_hits;
+    c->last.extended = c->record_hits;
     return UVRT_OK;
 }
 

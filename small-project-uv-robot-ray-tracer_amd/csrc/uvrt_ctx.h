@@ -9,6 +9,15 @@
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
 // (raytracer.h:50-53), its per-launch state split over launch lanes (struct Lane).
 // There is no CPU fallback: every entry point either runs on the GPU or returns an error.
+//
+// Who owns what.  A DevBuf owns its allocation, a Lane its side stream and tail event, a BatchSet its free event, the
+// context the rest (~uvrt_ctx).  A member added to one of these structs is released with it: there is no list to extend.
+// Buffers are named for release only where a SUBSET is dropped on purpose: per scene (uvrt_set_scene, hot_reset), per
+// capacity (uvrt_resize_rays).
+// Destruction order.  No destructor waits for a stream, so nothing may be deleted while a stream can still run work that
+// reads it: uvrt_destroy makes the device current, waits for the context's stream, the side streams and the probe's,
+// destroys the communicator (which puts the lanes' plain streams back) and only then deletes the context.  plan_drop waits
+// for the context's stream itself: it also runs in the middle of a context's life.
 #pragma once
 #include "../../include/uvrt.h"
 #include "uvrt_device.h"
@@ -17,6 +26,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -33,9 +43,13 @@ int fail(int code, const char* fmt, ...);   // sets g_err, returns code
                                      hipGetErrorString(e_), __FILE__, __LINE__);        \
     } while (0)
 
+// A device allocation and its owner: move-only, freed by its destructor (so a struct of them needs no release list).
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    ~DevBuf() { release(); }
     // Zeroing is enqueued on `s`, the stream every kernel of the context runs on (the
     // context's stream is non-blocking, so a null-stream hipMemset would not be ordered
     // against it).
@@ -77,6 +91,7 @@ struct Lane {
     DevBuf hot_hist, hot_list;       // scratch of the hot-record set-up kernels (uvrt_hotset.hip)
     const uint32_t* perm = nullptr;  // renumbering of the lane's current launch (set by uvrt_generate)
     DevBuf oxz;                      // {orig.x, orig.z} of free rays, [capacity]; allocated by the lane's first free launch
+    ~Lane() { if (ev_tail) (void)hipEventDestroy(ev_tail); if (side) (void)hipStreamDestroy(side); }
 };
 
 }  // namespace uvrt_impl
@@ -114,11 +129,9 @@ struct uvrt_ctx {
     bool nearfar_minmax = false;               // developer build: k_extend6's stream with the min/max near / far block (ExtendParams::nearfar_minmax; UVRT_NEARFAR_MINMAX=1)
     bool scene_force_exact = false;            // a node bound too tiny / too large for the reciprocal shortcuts
     int32_t hist_bins = 0;
-    int64_t last_n = -1;
-    int64_t last_first = 0;
-    bool last_sorted = false;
-    bool last_extended = false;
-    bool last_free = false;                    // the last generate made rays with origins of their own (uvrt_capi_free.hip)
+    // the rays of the last generate (or write): what uvrt_extend and uvrt_read_rays work on (n = -1: none; free_rays: with
+    // origins of their own, uvrt_capi_free.hip).  Assigned whole.
+    struct LastRays { int64_t n = -1, first = 0; bool sorted = false, extended = false, free_rays = false; } last;
     float ox = 0, oz = 0;
     DevBuf free_recs;                          // the free-origin kernel's records, [npairs + T + 1] x 64 B: made on first use
     bool free_recs_valid = false;              // ... for the current scene
@@ -174,7 +187,7 @@ struct uvrt_ctx {
     // two buffer sets: batch k + 1 is traced (on the launch lanes) into one while batch k is folded, reduced and
     // replayed (on the context's stream) out of the other
     // (oxz: the {orig.x, orig.z} of the batch's sweeps, [sweep][n_pad]; allocated by the first batch that holds one)
-    struct BatchSet { DevBuf rays, planes, folded, oxz; hipEvent_t free_ev = nullptr; };
+    struct BatchSet { DevBuf rays, planes, folded, oxz; hipEvent_t free_ev = nullptr; ~BatchSet() { if (free_ev) (void)hipEventDestroy(free_ev); } };
     BatchSet bs[2];
     int b_set = 0;                        // the set of the traced batch (b_count > 0) / of the last one
     uint64_t b_chunks = 0;                // chunks traced so far: consecutive chunks alternate over the launch lanes
@@ -231,11 +244,15 @@ struct uvrt_ctx {
     hipStream_t probe_stream = nullptr;        // uvrt_clock_probe_start's own stream (created on first use)
     DevBuf probe_out;                          // {shader ticks, 100 MHz ticks}
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used = 0;
+    std::vector<hipEvent_t> ev_pool;           // start / stop pairs: launch i is timed by events 2 i and 2 i + 1
+    size_t ev_used = 0;                        // pairs in use
 
     // Duration planning (uvrt_plan.hip): exposure matrix, solver buffers; null when no plan is active
     struct PlanState* plan = nullptr;
+
+    // what no member destroys by itself (uvrt_capi.hip): the plan, the hot entries' and the fences' events, the timing
+    // pool, the pinned flag, the probe's stream and the context's own
+    ~uvrt_ctx();
 };
 
 namespace uvrt_impl {
@@ -331,8 +348,59 @@ inline int order_after_previous(uvrt_ctx* c)
     c->lanes[l].used = true;
     return UVRT_OK;
 }
+// The launch lane of a new per-launch generate: the next one in the rotation when the launch may take part in it
+// (`may_pipeline`: what the caller's kind of launch adds to the context's own conditions), else lane 0 behind everything.
+inline int next_launch_lane(uvrt_ctx* c, bool may_pipeline)
+{
+    const bool pipe_ok = may_pipeline && c->pipeline && c->nlanes > 1 && !c->record_hits && c->lanes[1].rays.p;
+    c->prev_lane = c->lane;
+    c->cur_pipelined = pipe_ok;
+    if (pipe_ok) c->lane = (c->lane + 1) % c->nlanes;
+    else { if (int rc = join_all(c)) return rc; c->lane = 0; }
+    return c->lane == 0 ? UVRT_OK : cur_lane(c).ovf.ensure(side_ovf_bytes(c), false, c->stream);
+}
 // compute units the persistent grid of a launch on the current lane is sized for
 inline int lane_cus(const uvrt_ctx* c) { return c->lane == 0 ? c->num_cus : c->num_cus - c->lanes_masked_cus; }
+
+// bytes between the host and the device over the context's stream, waited for
+inline int copy_sync(uvrt_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind)
+{
+    if (bytes == 0) return UVRT_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+inline bool range_ok(const void* host, int64_t first, int64_t count, int64_t limit)
+{
+    return host && first >= 0 && count >= 0 && first + count <= limit;
+}
+// Elements [first, first + count) of a device array of `elem`-byte elements to the host (hipMemcpyDeviceToHost) or from it,
+// behind everything the context has outstanding.  The caller has checked the range (range_ok).
+inline int range_copy(uvrt_ctx* c, void* base, size_t elem, void* host, int64_t first, int64_t count, hipMemcpyKind kind)
+{
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    char* dev = (char*)base + (size_t)first * elem;
+    return kind == hipMemcpyDeviceToHost ? copy_sync(c, host, dev, (size_t)count * elem, kind)
+                                         : copy_sync(c, dev, host, (size_t)count * elem, kind);
+}
+
+// A ray as the ABI hands it over (raytracer.h Ray, 32 bytes) and its split into the device's arrays: {dir, orig.y} per ray
+// and, for rays with origins of their own, {orig.x, orig.z} and the distance
+struct HostRay { float d[3], o[3], dist; uint32_t tri; };
+inline void unpack_rays(const HostRay* hr, int64_t n, std::vector<float>& packed, std::vector<float>* oxz = nullptr,
+                        std::vector<float>* tmax = nullptr)
+{
+    packed.resize((size_t)n * 4);
+    if (oxz) oxz->resize((size_t)n * 2);
+    if (tmax) tmax->resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        packed[4 * i + 0] = hr[i].d[0]; packed[4 * i + 1] = hr[i].d[1];
+        packed[4 * i + 2] = hr[i].d[2]; packed[4 * i + 3] = hr[i].o[1];
+        if (oxz) { (*oxz)[2 * i + 0] = hr[i].o[0]; (*oxz)[2 * i + 1] = hr[i].o[2]; }
+        if (tmax) (*tmax)[i] = hr[i].dist;
+    }
+}
 
 // work-item 0's RNG walk of cl/generate.cl:13-39 on the host (strict f32/f64, same order)
 inline uint32_t host_wang_hash(uint32_t s)
@@ -426,7 +494,7 @@ inline uint64_t perm_generation(const uvrt_ctx* c, const uint32_t* perm)
 }
 // drops every cached renumbering (a new scene); with `slab`, the first slab of the new scene is allocated at once
 int hot_reset(uvrt_ctx* c, bool slab);
-// frees the duration-planning state (a new scene, uvrt_plan_end, uvrt_destroy)  (uvrt_plan.hip)
+// waits for the context's stream and deletes the duration-planning state (a new scene, uvrt_plan_end, ~uvrt_ctx)  (uvrt_plan.hip)
 void plan_drop(uvrt_ctx* c);
 // (re)creates the side lanes' streams with `reserve` CUs masked out, one per XCD and mask word of 8 (0: plain streams)
 int set_lane_cu_mask(uvrt_ctx* c, int reserve);
@@ -461,8 +529,10 @@ inline void fill_launch(uvrt_ctx* c, ExtendParams& p, float ox, float oz)
 }
 // uvrt_extend for the free rays of the last uvrt_write_free_rays / uvrt_generate_sweep (uvrt_capi_free.hip)
 int extend_free(uvrt_ctx* c, int64_t n);
-// the scene's free records, made on first use (uvrt_capi_free.hip)
+// the scene's free records, made on first use (uvrt_capi_free.hip); make_free_records is its enqueue part for a caller that
+// has joined the lanes and marks the fence itself (uvrt_trace_batch)
 int ensure_free_records(uvrt_ctx* c);
+int make_free_records(uvrt_ctx* c);
 // the expected plane of the direct gather, f64[T]: allocated and zeroed on first use (uvrt_capi_gather.hip)
 int ensure_expected(uvrt_ctx* c);
 // the next pair of the extend timing pool (uvrt_extend_time_ms) with its start recorded on `s`; *stop stays null
@@ -471,15 +541,28 @@ inline int timing_start(uvrt_ctx* c, hipStream_t s, hipEvent_t* stop)
 {
     *stop = nullptr;
     if (!c->timing) return UVRT_OK;
-    if (c->ev_used == c->ev_pool.size()) {
-        hipEvent_t a, b;
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        c->ev_pool.emplace_back(a, b);
+    while (c->ev_pool.size() < 2 * (c->ev_used + 1)) {      // (the pool owns an event from the moment it exists)
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        c->ev_pool.push_back(e);
     }
-    const auto& ev = c->ev_pool[c->ev_used++];
-    HIP_TRY(hipEventRecord(ev.first, s));
-    *stop = ev.second;
+    const size_t i = c->ev_used++;
+    HIP_TRY(hipEventRecord(c->ev_pool[2 * i], s));
+    *stop = c->ev_pool[2 * i + 1];
+    return UVRT_OK;
+}
+// A traversal launch on `s` between the events of a timing pair.  `launch` enqueues it and returns false when its grid needs
+// more overflow-stack entries than the lane's buffer holds; `what` names the launch in that error.
+template <class Launch>
+inline int timed_launch(uvrt_ctx* c, hipStream_t s, const char* who, const char* what, Launch&& launch)
+{
+    hipEvent_t stop;
+    if (int rc = timing_start(c, s, &stop)) return rc;
+    if (!launch())
+        return fail(UVRT_ERR_INVALID, "%s: %s with variant %d needs a larger overflow-stack buffer than the context holds", who,
+                    what, c->variant);
+    HIP_TRY(hipGetLastError());
+    if (stop) HIP_TRY(hipEventRecord(stop, s));
     return UVRT_OK;
 }
 

@@ -304,12 +304,6 @@ struct PlanState {
     DevBuf overflow;                     // uint32 flag of k_plan_capture / k_plan_capture_expected
     DevBuf cls, mask, blk_cnt, blk_area, blk_off, rows, rd, dd, blk_min, raise, zrows, outf, ratio, sel, gath;
     DevBuf lowd, fixd, rho, cols, xmin;  // bounded solve: lower as f64[P], fixed uint8[P], rho f64[T], the free columns, k_plan_xcheck
-    void release()
-    {
-        for (DevBuf* b : {&E, &overflow, &cls, &mask, &blk_cnt, &blk_area, &blk_off, &rows, &rd, &dd, &blk_min, &raise, &zrows,
-                          &outf, &ratio, &sel, &gath, &lowd, &fixd, &rho, &cols, &xmin})
-            b->release();
-    }
 };
 
 namespace uvrt_impl {
@@ -317,7 +311,6 @@ void plan_drop(uvrt_ctx* c)
 {
     if (!c || !c->plan) return;
     (void)hipStreamSynchronize(c->stream);
-    c->plan->release();
     delete c->plan;
     c->plan = nullptr;
 }
@@ -326,6 +319,29 @@ void plan_drop(uvrt_ctx* c)
 namespace {
 
 struct RowCheck { double min_ratio; int32_t zero_rows; };
+
+// the minimum over the per-block minima of a row kernel
+double min_of(const std::vector<double>& blk)
+{
+    double mn = std::numeric_limits<double>::infinity();
+    for (double v : blk) mn = std::min(mn, v);
+    return mn;
+}
+
+// the smallest f32 >= x that survives SaveRoute / LoadRoute
+float round_up_f32(double x)
+{
+    float f = (float)x;
+    if ((double)f < x) f = nextafterf(f, INFINITY);
+    return uvrt_plan_round_trip_up(f);
+}
+
+// the element type of the plan's exposure matrix: f(ET()) with ET = double (expected counts) or uint32_t (photon counts)
+template <class F>
+int with_element_type(const PlanState& S, F&& f)
+{
+    return S.expected ? f(double()) : f(uint32_t());
+}
 
 // k_plan_rowcheck of host durations d64; with `raise` the raise values come back in raise_out, with ratio_out A_i d per row
 // (bounded: the fixed columns of S.fixd are left out)
@@ -360,8 +376,7 @@ int row_check(uvrt_ctx* c, PlanState& S, bool bounded, int64_t NR, const std::ve
         HIP_TRY(hipMemcpyAsync(rb.data(), S.raise.p, (size_t)S.P * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    out->min_ratio = std::numeric_limits<double>::infinity();
-    for (unsigned b = 0; b < nbr; ++b) out->min_ratio = std::min(out->min_ratio, mn[b]);
+    out->min_ratio = min_of(mn);
     out->zero_rows = z;
     if (raise_out) {
         raise_out->assign(S.P, 0.0);
@@ -384,8 +399,7 @@ int x_check(uvrt_ctx* c, PlanState& S, double mprime, const std::vector<double>&
     std::vector<double> mn(nbt);
     HIP_TRY(hipMemcpyAsync(mn.data(), S.xmin.p, (size_t)nbt * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    *min_ratio = std::numeric_limits<double>::infinity();
-    for (unsigned b = 0; b < nbt; ++b) *min_ratio = std::min(*min_ratio, mn[b]);
+    *min_ratio = min_of(mn);
     return UVRT_OK;
 }
 
@@ -397,8 +411,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
                uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
 {
     if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "%s: no plan (uvrt_plan_begin)", who);
-    return c->plan->expected ? plan_solve_t<double>(c, who, prm, bounds, out, rep, brep)
-                             : plan_solve_t<uint32_t>(c, who, prm, bounds, out, rep, brep);
+    return with_element_type(*c->plan, [&](auto et) { return plan_solve_t<decltype(et)>(c, who, prm, bounds, out, rep, brep); });
 }
 
 // uvrt_plan_begin (uint32 counts) and uvrt_plan_begin_expected (f64 expected counts)
@@ -526,18 +539,15 @@ int uvrt_plan_model_dose(uvrt_ctx* c, const float* durations, float* out, int32_
     std::vector<double> d(S.P);
     for (int p = 0; p < S.P; ++p) d[p] = durations[p];
     HIP_TRY(hipMemcpyAsync(S.dd.p, d.data(), (size_t)S.P * 8, hipMemcpyHostToDevice, c->stream));
-    if (S.expected)
-        hipLaunchKernelGGL(k_plan_model_dose<double>, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const double*)S.E.as<double>(),
+    with_element_type(S, [&](auto et) {
+        using ET = decltype(et);
+        hipLaunchKernelGGL(k_plan_model_dose<ET>, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const ET*)S.E.as<ET>(),
                            c->T, S.P, (const double*)S.dd.as<double>(), (const float*)c->area.as<float>(), S.Nf, S.s, S.outf.as<float>(),
                            first, count);
-    else
-        hipLaunchKernelGGL(k_plan_model_dose<uint32_t>, dim3(nblocks(count, 256)), dim3(256), 0, c->stream, (const uint32_t*)S.E.as<uint32_t>(),
-                           c->T, S.P, (const double*)S.dd.as<double>(), (const float*)c->area.as<float>(), S.Nf, S.s, S.outf.as<float>(),
-                           first, count);
+        return UVRT_OK;
+    });
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, S.outf.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return copy_sync(c, out, S.outf.p, (size_t)count * 4, hipMemcpyDeviceToHost);
 }
 
 int uvrt_plan_read_exposure(uvrt_ctx* c, int32_t position, uint32_t* out, int32_t first, int32_t count)
@@ -546,14 +556,8 @@ int uvrt_plan_read_exposure(uvrt_ctx* c, int32_t position, uint32_t* out, int32_
     if (c->plan->expected) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: the plan holds expected values (uvrt_plan_read_exposure_expected)");
     if (position < 0 || position >= c->plan->P)
         return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: position %d outside [0,%d)", position, c->plan->P);
-    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: bad range");
-    if (count == 0) return UVRT_OK;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->plan->E.as<uint32_t>() + (size_t)position * c->T + first, (size_t)count * 4,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    if (!range_ok(out, first, count, c->T)) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure: bad range");
+    return range_copy(c, c->plan->E.as<uint32_t>() + (size_t)position * c->T, 4, out, first, count, hipMemcpyDeviceToHost);
 }
 
 int uvrt_plan_read_exposure_expected(uvrt_ctx* c, int32_t position, double* out, int32_t first, int32_t count)
@@ -562,49 +566,66 @@ int uvrt_plan_read_exposure_expected(uvrt_ctx* c, int32_t position, double* out,
         return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: no plan of expected values (uvrt_plan_begin_expected)");
     if (position < 0 || position >= c->plan->P)
         return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: position %d outside [0,%d)", position, c->plan->P);
-    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T)
-        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: bad range");
-    if (count == 0) return UVRT_OK;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->plan->E.as<double>() + (size_t)position * c->T + first, (size_t)count * 8,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    if (!range_ok(out, first, count, c->T)) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: bad range");
+    return range_copy(c, c->plan->E.as<double>() + (size_t)position * c->T, 8, out, first, count, hipMemcpyDeviceToHost);
+}
+
+// a range of the last solve's row classes
+static int read_classes(uvrt_ctx* c, const char* who, uint8_t* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan || !c->plan->solved) return fail(UVRT_ERR_INVALID, "%s: no solved plan", who);
+    if (!range_ok(out, first, count, c->T)) return fail(UVRT_ERR_INVALID, "%s: bad range", who);
+    return range_copy(c, c->plan->cls.p, 1, out, first, count, hipMemcpyDeviceToHost);
 }
 
 int uvrt_plan_read_required(uvrt_ctx* c, uint8_t* out, int32_t first, int32_t count)
 {
-    if (!c || !c->plan || !c->plan->solved) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_required: no solved plan");
-    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_required: bad range");
-    if (count == 0) return UVRT_OK;
-    if (int rc = set_device(c)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->plan->cls.as<uint8_t>() + first, (size_t)count, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = read_classes(c, "uvrt_plan_read_required", out, first, count)) return rc;
     for (int32_t i = 0; i < count; ++i) out[i] = out[i] == 0 || out[i] == 4 ? 1 : 0;     // a bounded solve: active or met by the bounds
     return UVRT_OK;
 }
 
 int uvrt_plan_read_classes(uvrt_ctx* c, uint8_t* out, int32_t first, int32_t count)
 {
-    if (!c || !c->plan || !c->plan->solved) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_classes: no solved plan");
-    if (!out || first < 0 || count < 0 || (int64_t)first + count > c->T) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_classes: bad range");
-    if (count == 0) return UVRT_OK;
-    if (int rc = set_device(c)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->plan->cls.as<uint8_t>() + first, (size_t)count, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return UVRT_OK;
+    return read_classes(c, "uvrt_plan_read_classes", out, first, count);
 }
 
 }  // extern "C"
 
 namespace {
 
-// uvrt_plan_solve (bounds == nullptr) and uvrt_plan_solve_bounded.  Bounds that bind nothing (all-zero lower, no fixed
-// column) take the unbounded instantiations of every kernel: the same arithmetic, bit for bit.
-template <typename ET>
-int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
-                 uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
+// uvrt_plan_solve (bounds == nullptr) and uvrt_plan_solve_bounded, in stages; what one stage leaves for the next is a member.
+// Bounds that bind nothing (all-zero lower, no fixed column) take the unbounded instantiations of every kernel: the same
+// arithmetic, bit for bit.
+struct Solve {
+    uvrt_ctx* c; const char* who; const uvrt_plan_params* prm; const uvrt_plan_bounds* bounds;      // the call's arguments
+    float* out; uvrt_plan_report* rep; uvrt_plan_bounds_report* brep;
+    PlanState& S = *c->plan;
+    const int32_t T = c->T, P = S.P;
+    const unsigned nbt = nblocks(T, 256);
+    // the bounds: lower as f64, the fixed flags, the free columns in ascending order
+    std::vector<double> low = std::vector<double>(P, 0.0);
+    std::vector<uint8_t> fix = std::vector<uint8_t>(P, 0);
+    std::vector<int32_t> cols;
+    int32_t PF = 0;                       // the columns the simplex sees (P when unbounded)
+    bool bounded = false;
+    double lower_total = 0.0;
+    double m = 0.0, mprime = 0.0;         // the minimum dose, and with the margin
+    int64_t NR = 0;                       // the rows of the LP: the required ones (bounded: the active ones)
+    bool done = false;                    // classify_rows left nothing for the LP to decide: out and the report are final
+    std::vector<double> d64 = std::vector<double>(P, 0.0);   // a duration per column (bounded: the excess over lower)
+    double best_lb = 0.0;
+    int it = 0;                           // rounds of cutting planes
+
+    int check_arguments();
+    template <typename ET> int classify_rows();
+    template <typename ET> int cutting_planes();
+    template <typename ET> int repair();
+    template <typename ET> int round_to_f32();
+};
+
+// the arguments, the bounds, the captures' overflow flag; clears the reports
+int Solve::check_arguments()
 {
     if (c->plan->captures == 0) return fail(UVRT_ERR_INVALID, "%s: nothing captured (uvrt_plan_capture_batch)", who);
     if (!prm || !out || !rep) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
@@ -614,14 +635,6 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
     if (!(prm->scaled_power > 0.0f) || !std::isfinite(prm->scaled_power) || !std::isfinite(prm->min_dose) ||
         !(prm->margin >= 0.0) || !(prm->rel_gap > 0.0))
         return fail(UVRT_ERR_INVALID, "%s: scaled_power > 0, finite min_dose, margin >= 0 and rel_gap > 0 required", who);
-    PlanState& S = *c->plan;
-    const int32_t T = c->T, P = S.P;
-    // ---- the bounds: lower as f64, the fixed flags, the free columns in ascending order
-    std::vector<double> low(P, 0.0);
-    std::vector<uint8_t> fix(P, 0);
-    std::vector<int32_t> cols;
-    bool bounded = false;
-    double lower_total = 0.0;
     for (int p = 0; p < P && bounds; ++p) {
         if (bounds->lower) {
             const float l = bounds->lower[p];
@@ -635,10 +648,9 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
     }
     for (int p = 0; p < P; ++p)
         if (!fix[p]) cols.push_back(p);
-    const int32_t PF = (int32_t)cols.size();              // the columns the simplex sees (P when unbounded)
+    PF = (int32_t)cols.size();
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
-    const unsigned nbt = nblocks(T, 256);
     {
         uint32_t of = 0;
         HIP_TRY(hipMemcpyAsync(&of, S.overflow.p, 4, hipMemcpyDeviceToHost, c->stream));
@@ -646,7 +658,6 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
         if (of && c->plan->expected) return fail(UVRT_ERR_INVALID, "%s: a captured expected value is not finite or is negative", who);
         if (of) return fail(UVRT_ERR_INVALID, "%s: a captured count overflowed uint32 (over 2^32 - 1 photons of one position)", who);
     }
-    int rc;
     memset(rep, 0, sizeof *rep);
     rep->positions = P;
     if (brep) {
@@ -655,10 +666,17 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
         brep->free_columns = PF;
         brep->lower_total = lower_total;
     }
+    return UVRT_OK;
+}
 
-    // ---- set-up: classes, exclusion statistics, the required rows
+// classes, exclusion statistics, the required rows compacted
+template <typename ET>
+int Solve::classify_rows()
+{
+    int rc;
     const int NC = bounded ? 6 : 4;
-    const double m = prm->min_dose, mprime = m * (1.0 + prm->margin);
+    m = prm->min_dose;
+    mprime = m * (1.0 + prm->margin);
     if ((rc = S.cls.ensure((size_t)T, false, c->stream))) return rc;
     if ((rc = S.blk_cnt.ensure((size_t)nbt * NC * 4, false, c->stream))) return rc;
     if ((rc = S.blk_area.ensure((size_t)nbt * NC * 8, false, c->stream))) return rc;
@@ -711,11 +729,12 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
         brep->met_by_lower = (int32_t)cnt[4]; brep->short_rows = (int32_t)cnt[5];
         brep->area_met_by_lower = area[4]; brep->area_short = area[5];
     }
-    const int64_t NR = cnt[0];                  // the rows of the LP: the required ones (bounded: the active ones)
+    NR = cnt[0];
     S.s = prm->scaled_power;
     S.Nf = (float)prm->photons_per_position;
     S.solved = true;
     if (NR == 0 || !(m > 0.0)) {
+        done = true;
         if (!bounded) {
             for (int p = 0; p < P; ++p) out[p] = 0.0f;
             rep->status = UVRT_PLAN_CONVERGED;
@@ -752,18 +771,32 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
                        S.s, S.Nf, mprime, S.rows.as<int32_t>(), S.rd.as<double>(),
                        bounded ? (const double*)S.rho.as<double>() : nullptr);
     HIP_TRY(hipGetLastError());
+    return UVRT_OK;
+}
 
-    // ---- cutting planes from the uniform plan: rows W gathered so far (AW: |W| x PF, f64), exact LP over W, repeat.
-    // d64 holds every column (a fixed one stays 0: the row kernels skip it); the simplex sees the PF free ones.
+// Cutting planes from the uniform plan: rows W gathered so far (AW: |W| x PF, f64), exact LP over W, repeat.
+// d64 holds every column (a fixed one stays 0: the row kernels skip it); the simplex sees the PF free ones.
+template <typename ET>
+int Solve::cutting_planes()
+{
+    int rc;
     const int max_rounds = prm->max_iterations > 0 ? prm->max_iterations : 200;
     const int per_round = std::max(64, 2 * PF);
-    std::vector<double> d64(P, 0.0), dlp, ratio, AW, best_d;
+    std::vector<double> dlp, ratio, AW, best_d;
     std::vector<int64_t> W;
     std::vector<uint8_t> inW((size_t)NR, 0);
     uvrt_plan_lp::RestrictedLP lp(PF);
     int64_t pivots = 0;
-    double best_ub = std::numeric_limits<double>::infinity(), best_lb = 0.0;
-    int it = 0;
+    double best_ub = std::numeric_limits<double>::infinity();
+    auto offer = [&](double min_ratio) {      // d64, scaled to cover its least covered row, is the plan to beat
+        double sd = 0;
+        for (double v : d64) sd += v;
+        if (min_ratio > 0.0 && sd / min_ratio < best_ub) {
+            best_ub = sd / min_ratio;
+            best_d = d64;
+            for (double& v : best_d) v /= min_ratio;
+        }
+    };
     {
         std::vector<double> ones(P, 1.0);
         RowCheck r1;
@@ -773,13 +806,7 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
     for (;;) {
         RowCheck rck;
         if ((rc = row_check<ET>(c, S, bounded, NR, d64, false, &rck, nullptr, &ratio))) return rc;
-        double sd = 0;
-        for (double v : d64) sd += v;
-        if (rck.min_ratio > 0.0 && sd / rck.min_ratio < best_ub) {
-            best_ub = sd / rck.min_ratio;
-            best_d = d64;
-            for (double& v : best_d) v /= rck.min_ratio;
-        }
+        offer(rck.min_ratio);
         if (std::isfinite(best_ub) && (best_ub - best_lb) <= prm->rel_gap * best_ub) break;
         if (it >= max_rounds) break;
         // the most violated rows not yet in W (round 0: the least covered ones under the uniform plan)
@@ -825,20 +852,19 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
         if (!solved) {                          // pivot cap: keep what is certified, report the gap
             RowCheck rlast;
             if ((rc = row_check<ET>(c, S, bounded, NR, d64, false, &rlast, nullptr))) return rc;
-            double sl = 0;
-            for (double v : d64) sl += v;
-            if (rlast.min_ratio > 0.0 && sl / rlast.min_ratio < best_ub) {
-                best_ub = sl / rlast.min_ratio;
-                best_d = d64;
-                for (double& v : best_d) v /= rlast.min_ratio;
-            }
+            offer(rlast.min_ratio);
             break;
         }
     }
-
-    // ---- repair (f64): cover rows without coverage by their best position, drop positions the plan does not need, scale
     if (std::isfinite(best_ub)) d64 = best_d;
-    std::vector<double> dh(P);
+    return UVRT_OK;
+}
+
+// repair (f64): cover rows without coverage by their best position, drop positions the plan does not need, scale
+template <typename ET>
+int Solve::repair()
+{
+    int rc;
     {
         double dmax = 0;
         for (double v : d64) dmax = std::max(dmax, v);
@@ -853,17 +879,21 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
     }
     if (rck.zero_rows != 0 || !(rck.min_ratio > 0.0)) return fail(UVRT_ERR_INVALID, "%s: repair left rows uncovered", who);
     for (double& v : d64) v /= rck.min_ratio;
+    return UVRT_OK;
+}
+
+// f32 durations, rounded up to values that survive SaveRoute / LoadRoute and re-checked in f64; the report
+template <typename ET>
+int Solve::round_to_f32()
+{
+    int rc;
+    std::vector<double> dh(P);
     std::vector<float> d32(P);
+    RowCheck rck{};
     double min_ratio = 0.0;
     if (!bounded) {
-        // f32, rounded up to values that survive SaveRoute / LoadRoute; re-checked in f64
         for (int round = 0; round < 8; ++round) {
-            for (int p = 0; p < P; ++p) {
-                float f = (float)d64[p];
-                if ((double)f < d64[p]) f = nextafterf(f, INFINITY);
-                d32[p] = d64[p] > 0.0 ? uvrt_plan_round_trip_up(f) : 0.0f;
-                dh[p] = d32[p];
-            }
+            for (int p = 0; p < P; ++p) dh[p] = d32[p] = d64[p] > 0.0 ? round_up_f32(d64[p]) : 0.0f;
             if ((rc = row_check<ET>(c, S, false, NR, dh, false, &rck, nullptr))) return rc;
             if (rck.min_ratio >= 1.0) break;
             for (double& v : d64) v *= (1.0 / rck.min_ratio) * (1.0 + 1e-12);
@@ -874,16 +904,7 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
         // x = lower + e in f32: lower itself where e is 0, else rounded up as above; checked in x-space over the required
         // rows, every column counted.  A miss rescales the excess the f32 values carry by what the active rows lack.
         for (int round = 0; round < 8; ++round) {
-            for (int p = 0; p < P; ++p) {
-                d32[p] = (float)low[p];
-                if (d64[p] > 0.0) {
-                    const double x = low[p] + d64[p];
-                    float f = (float)x;
-                    if ((double)f < x) f = nextafterf(f, INFINITY);
-                    d32[p] = uvrt_plan_round_trip_up(f);
-                }
-                dh[p] = d32[p];
-            }
+            for (int p = 0; p < P; ++p) dh[p] = d32[p] = d64[p] > 0.0 ? round_up_f32(low[p] + d64[p]) : (float)low[p];
             if ((rc = x_check<ET>(c, S, mprime, dh, &min_ratio))) return rc;
             if (min_ratio >= 1.0) break;
             for (int p = 0; p < P; ++p) dh[p] = fix[p] ? 0.0 : dh[p] - low[p];
@@ -910,6 +931,19 @@ int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, cons
     rep->status = rep->gap <= prm->rel_gap ? UVRT_PLAN_CONVERGED : UVRT_PLAN_ITERATION_CAP;
     rep->min_dose_ratio = min_ratio * (mprime / m);
     return UVRT_OK;
+}
+
+template <typename ET>
+int plan_solve_t(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const uvrt_plan_bounds* bounds, float* out,
+                 uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
+{
+    Solve v{c, who, prm, bounds, out, rep, brep};
+    if (int rc = v.check_arguments()) return rc;
+    if (int rc = v.template classify_rows<ET>()) return rc;
+    if (v.done) return UVRT_OK;
+    if (int rc = v.template cutting_planes<ET>()) return rc;
+    if (int rc = v.template repair<ET>()) return rc;
+    return v.template round_to_f32<ET>();
 }
 
 }  // namespace
