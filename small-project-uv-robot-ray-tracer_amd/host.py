@@ -16,6 +16,10 @@ _LIB = None
 NODE_DT = np.dtype([("minx", "<f4"), ("miny", "<f4"), ("minz", "<f4"), ("leftFirst", "<i4"),
                     ("maxx", "<f4"), ("maxy", "<f4"), ("maxz", "<f4"), ("triCount", "<i4")])
 
+# RouteLaunch (host/raytracer.h): one launch of an iteration of a route; kind is capi.LAUNCH_STOP / capi.LAUNCH_SWEEP
+ROUTE_LAUNCH_DT = np.dtype([("from", "<f4", 3), ("to", "<f4", 3), ("duration", "<f4"), ("kind", "<i4"), ("column", "<i4"),
+                            ("reserved", "<i4")])
+
 VIEW_DOSAGE, VIEW_MAXPOWER, VIEW_TEXTURE = 0, 1, 2
 
 _vp = C.c_void_p
@@ -71,6 +75,7 @@ SYMBOLS = [
     ("uvrt_host_rt_set_candidate_grid", None, [_vp, C.c_int, C.c_int, C.c_float]),
     ("uvrt_host_grid_positions", None, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
                                         C.POINTER(C.c_float)]),
+    ("uvrt_host_route_launches", C.c_int, [_vp, C.c_int, C.c_float, C.c_float, _vp, C.c_int]),
     ("uvrt_host_rt_get", C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_double)]),
     ("uvrt_host_rt_set", C.c_int, [_vp, C.c_char_p, C.c_double]),
 ]
@@ -334,6 +339,17 @@ def grid_positions(bounds, nx, nz, inset=0.5):
     xmin, xmax, zmin, zmax = (float(v) for v in bounds)
     lib().uvrt_host_grid_positions(xmin, xmax, zmin, zmax, int(nx), int(nz), float(inset), out)
     return np.frombuffer(out, dtype=np.float32).reshape(nx * nz, 2).copy()
+
+
+def route_launches(lamps, y, drive_speed):
+    """RayTracer::RouteLaunches: the launches of one iteration over lamps = (x, z, duration) triples with the lamp's foot
+    at height y: the stops, then (drive_speed > 0, two positions or more) the segments; ROUTE_LAUNCH_DT[P]"""
+    xzd = np.ascontiguousarray(lamps, dtype=np.float32).reshape(-1, 3)
+    L = lib()
+    n = L.uvrt_host_route_launches(xzd.ctypes.data, len(xzd), float(y), float(drive_speed), None, 0)
+    out = np.zeros(n, dtype=ROUTE_LAUNCH_DT)
+    L.uvrt_host_route_launches(xzd.ctypes.data, len(xzd), float(y), float(drive_speed), out.ctypes.data, n)
+    return out
 
 
 class _BorrowedCtx(capi.Ctx):

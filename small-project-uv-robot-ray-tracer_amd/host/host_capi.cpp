@@ -2,10 +2,40 @@
 // drive the C++ host layer through ctypes.  Plumbing only; no arithmetic lives here.
 #include "raytracer.h"
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
 using namespace Tmpl8;
+
+namespace {
+
+// a route file's name as SaveRoute / LoadRoute take it: at most 31 characters
+void copy_name(char out[32], const char* name)
+{
+    strncpy(out, name, 31);
+    out[31] = 0;
+}
+
+std::vector<LightPos> positions(const float* xyd, int n)
+{
+    std::vector<LightPos> out;
+    for (int i = 0; i < n; ++i) out.push_back({make_float2(xyd[3 * i], xyd[3 * i + 1]), xyd[3 * i + 2]});
+    return out;
+}
+
+std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>((RayTracer**)rs, (RayTracer**)rs + n); }
+
+RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                                    const unsigned char* mask, int gather_samples)
+{
+    RayTracer::PlanOptions o;
+    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
+    o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
+    return o;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -36,26 +66,20 @@ void* uvrt_host_rt_new(void) { return new RayTracer(); }
 void uvrt_host_rt_free(void* r) { delete (RayTracer*)r; }
 void uvrt_host_rt_set_route_dir(void* r, const char* dir) { ((RayTracer*)r)->routeDir = dir; }
 void uvrt_host_rt_set_default_route(void* r, const char* name)
-{
-    RayTracer* rt = (RayTracer*)r;
-    strncpy(rt->defaultRouteFile, name, 31);
-    rt->defaultRouteFile[31] = 0;
-}
+{ copy_name(((RayTracer*)r)->defaultRouteFile, name); }
 void uvrt_host_rt_set_device(void* r, int dev) { ((RayTracer*)r)->deviceId = dev; }
 void uvrt_host_rt_set_auto_save(void* r, int on) { ((RayTracer*)r)->autoSaveRoute = on != 0; }
 void uvrt_host_rt_init(void* r, void* mesh) { ((RayTracer*)r)->Init((Mesh*)mesh); }
 void uvrt_host_rt_load_route(void* r, const char* name)
 {
     char buf[32];
-    strncpy(buf, name, 31);
-    buf[31] = 0;
+    copy_name(buf, name);
     ((RayTracer*)r)->LoadRoute(buf);
 }
 void uvrt_host_rt_save_route(void* r, const char* name)
 {
     char buf[32];
-    strncpy(buf, name, 31);
-    buf[31] = 0;
+    copy_name(buf, name);
     ((RayTracer*)r)->SaveRoute(buf);
 }
 void uvrt_host_rt_update_photons_per_light(void* r) { ((RayTracer*)r)->UpdatePhotonsPerLight(); }
@@ -64,18 +88,11 @@ void uvrt_host_rt_clear_buffers(void* r, int reset_color) { ((RayTracer*)r)->Cle
 void uvrt_host_rt_compute_dosage_map(void* r) { ((RayTracer*)r)->ComputeDosageMap(); }
 void uvrt_host_rt_compute_single(void* r, float x, float y, float duration, int photons, int tris)
 {
-    LightPos lp;
-    lp.position = make_float2(x, y);
-    lp.duration = duration;
-    ((RayTracer*)r)->ComputeSingleLightDosageMap(lp, photons, tris);
+    ((RayTracer*)r)->ComputeSingleLightDosageMap({make_float2(x, y), duration}, photons, tris);
 }
 void uvrt_host_rt_compute_segment(void* r, float ax, float ay, float bx, float by, int photons, int tris)
 {
-    LightPos a, b;
-    a.position = make_float2(ax, ay);
-    b.position = make_float2(bx, by);
-    a.duration = b.duration = 0.0f;
-    ((RayTracer*)r)->ComputeSegmentDosageMap(a, b, photons, tris);
+    ((RayTracer*)r)->ComputeSegmentDosageMap({make_float2(ax, ay), 0.0f}, {make_float2(bx, by), 0.0f}, photons, tris);
 }
 void uvrt_host_rt_shade(void* r) { ((RayTracer*)r)->Shade(); }
 void uvrt_host_rt_add_lamp(void* r) { ((RayTracer*)r)->AddLamp(); }
@@ -93,9 +110,7 @@ void uvrt_host_rt_set_shard(void* r, int rank, int world)
 void uvrt_host_rt_compute_batched(void* r, int iterations) { ((RayTracer*)r)->ComputeIterationsBatched(iterations); }
 void uvrt_host_rt_compute_batched_group(void** rs, int n, int iterations)
 {
-    std::vector<RayTracer*> g;
-    for (int i = 0; i < n; ++i) g.push_back((RayTracer*)rs[i]);
-    RayTracer::ComputeIterationsBatched(g, iterations);
+    RayTracer::ComputeIterationsBatched(group(rs, n), iterations);
 }
 void uvrt_host_rt_set_ray_range(void* r, int rank, int world) { ((RayTracer*)r)->SetRayRange(rank, world); }
 void uvrt_host_rt_set_reduce_over_comm(void* r, int on) { ((RayTracer*)r)->reduceOverComm = on != 0; }
@@ -109,43 +124,35 @@ void uvrt_host_rt_get_lamp(void* r, int i, float* xyd)
 void uvrt_host_rt_set_lamps(void* r, const float* xyd, int n)
 {
     RayTracer* rt = (RayTracer*)r;
-    rt->lightPositions.clear();
-    for (int i = 0; i < n; ++i) {
-        LightPos lp;
-        lp.position = make_float2(xyd[3 * i], xyd[3 * i + 1]);
-        lp.duration = xyd[3 * i + 2];
-        rt->lightPositions.push_back(lp);
-    }
+    rt->lightPositions = positions(xyd, n);
     rt->UpdatePhotonsPerLight();
+}
+// RayTracer::RouteLaunches of L positions (x, z, duration): returns the count, writes at most `max` 40-byte RouteLaunch records
+int uvrt_host_route_launches(const float* xzd, int L, float y, float drive_speed, void* out, int max)
+{
+    static_assert(sizeof(RouteLaunch) == 40, "the record host.ROUTE_LAUNCH_DT describes");
+    const std::vector<RouteLaunch> list = RayTracer::RouteLaunches(positions(xzd, L), y, drive_speed);
+    const size_t n = std::min(list.size(), (size_t)std::max(max, 0));
+    if (n) memcpy(out, list.data(), n * sizeof(RouteLaunch));
+    return (int)list.size();
 }
 
 // duration planning: durations -> lightPositions, report -> *rep, starting SEED -> *seed
 void uvrt_host_rt_plan(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
                        const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
-    RayTracer::PlanOptions o;
-    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
-    o.maxIterations = max_iterations; o.mask = mask;
-    *rep = ((RayTracer*)r)->PlanDurations(o, seed);
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, 0), seed);
 }
 // the same with PlanOptions::gatherSamples: > 0 plans from the direct gather
 void uvrt_host_rt_plan_gather(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
                               const unsigned char* mask, int gather_samples, uvrt_plan_report* rep, unsigned* seed)
 {
-    RayTracer::PlanOptions o;
-    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
-    o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
-    *rep = ((RayTracer*)r)->PlanDurations(o, seed);
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples), seed);
 }
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
-    std::vector<RayTracer*> g;
-    for (int i = 0; i < n; ++i) g.push_back((RayTracer*)rs[i]);
-    RayTracer::PlanOptions o;
-    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
-    o.maxIterations = max_iterations; o.mask = mask;
-    *rep = RayTracer::PlanDurations(g, o, seed);
+    *rep = RayTracer::PlanDurations(group(rs, n), plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, 0), seed);
 }
 // of the last PlanDurations: the bounds report and the segment columns (returns their number; copies at most n)
 void uvrt_host_rt_plan_bounds(void* r, uvrt_plan_bounds_report* out) { *out = ((RayTracer*)r)->planBounds; }

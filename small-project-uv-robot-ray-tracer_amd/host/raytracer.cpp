@@ -137,10 +137,7 @@ RayTracer::~RayTracer()
 
 void RayTracer::AddLamp()                                    // raytracer.cpp:3-10
 {
-    LightPos initLightPos;
-    initLightPos.position = make_float2(0.0f, 0.0f);
-    initLightPos.duration = 1;
-    lightPositions.push_back(initLightPos);
+    lightPositions.push_back({make_float2(0.0f, 0.0f), 1.0f});
     UpdatePhotonsPerLight();
 }
 
@@ -164,74 +161,81 @@ void RayTracer::UpdatePhotonsPerLight()                      // raytracer.cpp:61
     photonsPerLight = (int)(photonCount / lightPositions.size()) & ~1;
 }
 
+std::vector<RouteLaunch> RayTracer::RouteLaunches(const std::vector<LightPos>& positions, float y, float driveSpeed)
+{
+    const size_t L = positions.size();
+    std::vector<RouteLaunch> list;
+    for (size_t i = 0; i < L; ++i) {                         // raytracer.cpp:77 -- the lamp's foot in world space
+        const LightPos& p = positions[i];
+        list.push_back({{p.position.x, y, p.position.y}, {0.0f, 0.0f, 0.0f}, p.duration, UVRT_LAUNCH_STOP, (int)i, 0});
+    }
+    if (!(driveSpeed > 0.0f) || L < 2) return list;
+    for (size_t k = 0; k + 1 < L; ++k) {
+        const LightPos &a = positions[k], &b = positions[k + 1];
+        const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
+        const float len = sqrtf(dx * dx + dz * dz);
+        list.push_back({{a.position.x, y, a.position.y}, {b.position.x, y, b.position.y}, len / driveSpeed, UVRT_LAUNCH_SWEEP, (int)(L + k), 0});
+    }
+    return list;
+}
+
+std::vector<RouteLaunch> RayTracer::Launches() const
+{
+    return RouteLaunches(lightPositions, mesh->floorHeight + lightHeight, driveSpeed);   // the y sum is one f32 addition
+}
+
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    for (LightPos& lightPosition : lightPositions)
-        ComputeSingleLightDosageMap(lightPosition, photonsPerLight, mesh->triangleCount);
-    ComputeSegments();
+    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, -1);
 }
 
 void RayTracer::ComputeSegments()
 {
-    if (!(driveSpeed > 0.0f) || lightPositions.size() < 2) return;
-    for (size_t i = 0; i + 1 < lightPositions.size(); ++i)
-        ComputeSegmentDosageMap(lightPositions[i], lightPositions[i + 1], photonsPerLight, mesh->triangleCount);
+    for (const RouteLaunch& l : Launches())
+        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, -1);
 }
 
-// one launch of the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
-void RayTracer::GatherLaunch(const float from[3], const float to[3], float duration, int photonsPerLight, int triangleCount)
+void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int captureColumn)
 {
-    if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
-    uvrt_gather_params g;
-    memset(&g, 0, sizeof g);
-    memcpy(g.from, from, 12);
-    memcpy(g.to, to, 12);
-    g.light_length = lightLength;
-    g.samples = gatherSamples;
-    g.seed = gatherLaunches++;
-    g.photons_equiv = photonsPerLight;
-    check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
-    if (planGatherColumn >= 0) check(uvrt_plan_capture_expected(ctx, planGatherColumn), "plan_capture_expected");
-    check(uvrt_accumulate_expected(ctx, duration, triangleCount), "accumulate_expected");
+    const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
+    if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
+    if (samples > 0) {
+        // the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
+        if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
+        uvrt_gather_params g;
+        memset(&g, 0, sizeof g);
+        memcpy(g.from, l.from, 12);
+        memcpy(g.to, sweep ? l.to : l.from, 12);             // from == to: a stop
+        g.light_length = lightLength;
+        g.samples = samples;
+        g.seed = gatherLaunches++;
+        g.photons_equiv = photons;
+        check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+        if (captureColumn >= 0) check(uvrt_plan_capture_expected(ctx, captureColumn), "plan_capture_expected");
+        check(uvrt_accumulate_expected(ctx, l.duration, triangleCount), "accumulate_expected");
+    } else if (shardWorld <= 1 || (launchIndex % shardWorld) == shardRank) {
+        if (sweep) check(uvrt_generate_sweep(ctx, l.from, l.to, lightLength, 0, photons), "generate_sweep");
+        else check(uvrt_generate(ctx, l.from, lightLength, 0, photons), "generate");   // :78-80
+        check(uvrt_extend(ctx, photons), "extend");                                    // :82
+        check(uvrt_accumulate(ctx, l.duration, triangleCount), "accumulate");          // :84-85
+    } else {
+        // another rank traces this launch; keep generate.cl's program-scope SEED in step
+        check(uvrt_advance_seed(ctx, l.from, lightLength), "advance_seed");
+    }
+    if (sweep) return;           // Shade divides by the photons per SOURCE (raytracer.h driveSpeed): a sweep adds none
+    ++launchIndex;
+    photonMapSize += photons;                                // :87
 }
 
 void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount)
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
-    if (shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
-    // the lamp's feet, as at a stop (raytracer.cpp:77)
-    const float y = mesh->floorHeight + lightHeight;
-    const float from[3] = {a.position.x, y, a.position.y}, to[3] = {b.position.x, y, b.position.y};
-    const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
-    const float len = sqrtf(dx * dx + dz * dz);          // (a zero-length segment is traced too, with duration 0: the SEED chain stays regular)
-    if (gatherSamples > 0) { GatherLaunch(from, to, len / driveSpeed, photonsPerLight, triangleCount); return; }
-    check(uvrt_generate_sweep(ctx, from, to, lightLength, 0, photonsPerLight), "generate_sweep");
-    check(uvrt_extend(ctx, photonsPerLight), "extend");
-    check(uvrt_accumulate(ctx, len / driveSpeed, triangleCount), "accumulate");
-    // (no photonMapSize += photonsPerLight: Shade divides by the photons per SOURCE, raytracer.h driveSpeed)
+    RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples, -1);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
-    // raytracer.cpp:77 -- lamp foot in world space; the y sum is one f32 addition
-    const float lp[3] = {lightPos.position.x, mesh->floorHeight + lightHeight, lightPos.position.y};
-    if (gatherSamples > 0) {
-        GatherLaunch(lp, lp, lightPos.duration, photonsPerLight, triangleCount);
-        ++launchIndex;
-        photonMapSize += photonsPerLight;                               // :87
-        return;
-    }
-    const bool mine = shardWorld <= 1 || (launchIndex % shardWorld) == shardRank;
-    ++launchIndex;
-    if (mine) {
-        check(uvrt_generate(ctx, lp, lightLength, 0, photonsPerLight), "generate");   // :78-80
-        check(uvrt_extend(ctx, photonsPerLight), "extend");                           // :82
-        check(uvrt_accumulate(ctx, lightPos.duration, triangleCount), "accumulate");  // :84-85
-    } else {
-        // another rank traces this launch; keep generate.cl's program-scope SEED in step
-        check(uvrt_advance_seed(ctx, lp, lightLength), "advance_seed");
-    }
-    photonMapSize += photonsPerLight;                                   // :87
+    RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples, -1);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -261,89 +265,67 @@ void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, i
             if (!(rt->driveSpeed > 0.0f)) fatal("ComputeIterationsBatched: every instance of a group must drive (driveSpeed > 0) or none");
         if (r0->shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
     }
-    TraceBatched(group, iterations, driving);
+    TraceBatched(group, iterations);
 }
 
-// `iterations` x (L stops [+ L - 1 segments when driving]) in batches of up to 64 launches; the last launch of an iteration
-// carries its Shade
-void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool driving)
+// `iterations` x the route's launches in batches of up to 64; the last launch of an iteration carries its Shade
+void RayTracer::TraceBatched(const std::vector<RayTracer*>& group, int iterations)
 {
-    RayTracer* r0 = group[0];
-    const int L = (int)r0->lightPositions.size();
-    const int P = driving && L >= 2 ? 2 * L - 1 : L;      // launches per iteration (ComputeDosageMap: the stops, then ComputeSegments)
+    std::vector<std::vector<RouteLaunch>> lists;             // built once per call; every instance's from its own fields
+    for (RayTracer* rt : group) lists.push_back(rt->Launches());
+    const int P = (int)lists[0].size();                      // launches per iteration
+    const bool sweeps = P > 0 && lists[0].back().kind == UVRT_LAUNCH_SWEEP;
     const long long total = (long long)iterations * P;
     const int kMax = 64;                                  // launches per uvrt_trace_batch
     std::vector<float> lamps((size_t)kMax * 3);
     std::vector<uvrt_launch> launches((size_t)kMax);
-    std::vector<uvrt_replay_op> ops((size_t)kMax);
+    std::vector<std::vector<uvrt_replay_op>> ops(group.size(), std::vector<uvrt_replay_op>((size_t)kMax));
     std::vector<uvrt_ctx*> ctxs;
     for (RayTracer* rt : group) ctxs.push_back(rt->ctx);
     long long done = 0;
     while (done < total) {
         int cnt = (int)std::min<long long>(kMax, total - done);
         if (cnt < total - done && cnt >= P) cnt -= (int)((done + cnt) % P);    // end on an iteration where one fits
-        for (RayTracer* rt : group) {
-            const float y = rt->mesh->floorHeight + rt->lightHeight;             // raytracer.cpp:77
+        for (size_t r = 0; r < group.size(); ++r) {
+            RayTracer* rt = group[r];
             for (int j = 0; j < cnt; ++j) {
                 const int pos = (int)((done + j) % P);
-                uvrt_replay_op& op = ops[j];
+                const RouteLaunch& l = lists[r][pos];
                 uvrt_launch& ln = launches[j];
                 memset(&ln, 0, sizeof ln);
-                if (pos < L) {
-                    const LightPos& lp = rt->lightPositions[pos];
-                    lamps[3 * j + 0] = lp.position.x;
-                    lamps[3 * j + 1] = y;
-                    lamps[3 * j + 2] = lp.position.y;
-                    memcpy(ln.from, &lamps[3 * j], 12);
-                    ln.kind = UVRT_LAUNCH_STOP;
-                    op.duration = lp.duration;                                   // :84
+                memcpy(ln.from, l.from, 12);
+                memcpy(ln.to, l.to, 12);
+                ln.kind = l.kind;
+                memcpy(&lamps[3 * j], l.from, 12);
+                if (l.kind == UVRT_LAUNCH_STOP) {
                     rt->photonMapSize += rt->photonsPerLight;                     // :87
                     ++rt->launchIndex;
-                } else {                                                         // ComputeSegmentDosageMap
-                    const LightPos& a = rt->lightPositions[pos - L];
-                    const LightPos& b = rt->lightPositions[pos - L + 1];
-                    ln.from[0] = a.position.x; ln.from[1] = y; ln.from[2] = a.position.y;
-                    ln.to[0] = b.position.x; ln.to[1] = y; ln.to[2] = b.position.y;
-                    ln.kind = UVRT_LAUNCH_SWEEP;
-                    const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
-                    const float len = sqrtf(dx * dx + dz * dz);
-                    op.duration = len / rt->driveSpeed;
-                    // (no photonMapSize += photonsPerLight: Shade divides by the photons per SOURCE, raytracer.h driveSpeed)
                 }
-                op.shade = pos == P - 1;                                         // myapp.cpp:160
-                if (rt->viewMode == maxpower) {                                  // raytracer.cpp:96-104
-                    op.which_map = UVRT_MAP_MAX;
-                    op.photons_per_light = rt->photonsPerLight;
-                    op.scaled_power = rt->lightIntensity * 100;
-                    op.min_value = rt->minPower;
-                } else {                                                         // :106-116
-                    op.which_map = UVRT_MAP_SUM;
-                    op.photons_per_light = rt->photonMapSize / (int)rt->lightPositions.size();
-                    op.scaled_power = rt->lightIntensity * 0.1f;
-                    op.min_value = rt->minDosage;
-                }
-                op.threshold_view = rt->thresholdView;
-                if (op.shade) {                                                  // myapp.cpp:162-163
+                const ShadeArguments sh = rt->ShadeArgs();                       // (after the launch's photonMapSize +=)
+                const bool shade = pos == P - 1;                                 // myapp.cpp:160
+                ops[r][j] = {l.duration, shade, sh.which_map, sh.photons_per_light, sh.scaled_power, sh.min_value, rt->thresholdView};
+                if (shade) {                                                     // myapp.cpp:162-163
                     ++rt->currIterations;
                     rt->progress = 100.0f * (float)rt->currIterations / (float)rt->maxIterations;
                 }
             }
             const long long n = rt->rangeCount < 0 ? rt->photonsPerLight : rt->rangeCount;
             if (n <= 0) fatal("ComputeIterationsBatched: an empty ray range (more ranks than photons)");
-            if (P != L)
+            if (sweeps)
                 check(uvrt_trace_batch_launches(rt->ctx, launches.data(), rt->lightLength, cnt, rt->rangeFirst, n), "trace_batch_launches");
             else
                 check(uvrt_trace_batch(rt->ctx, lamps.data(), rt->lightLength, cnt, rt->rangeFirst, n), "trace_batch");
         }
         if (group.size() > 1) check(uvrt_reduce_batch_group(ctxs.data(), (int)ctxs.size()), "reduce_batch_group");
-        for (RayTracer* rt : group) {
+        for (size_t r = 0; r < group.size(); ++r) {
+            RayTracer* rt = group[r];
             if (group.size() == 1 && rt->reduceOverComm) check(uvrt_reduce_batch(rt->ctx), "reduce_batch");
-            if (rt->planCapture) {                       // launch j of the batch is column (done + j) % P: the stops, then the segments
+            if (rt->planCapture) {                       // launch j of the batch is column (done + j) % P
                 std::vector<int32_t> pos((size_t)cnt);
                 for (int j = 0; j < cnt; ++j) pos[j] = (int32_t)((done + j) % P);
                 check(uvrt_plan_capture_batch(rt->ctx, pos.data(), cnt), "plan_capture_batch");
             }
-            check(uvrt_replay_batch(rt->ctx, ops.data(), cnt, rt->mesh->triangleCount), "replay_batch");
+            check(uvrt_replay_batch(rt->ctx, ops[r].data(), cnt, rt->mesh->triangleCount), "replay_batch");
         }
         done += cnt;
     }
@@ -355,56 +337,42 @@ uvrt_plan_report RayTracer::PlanDurations(const PlanOptions& opt, unsigned* seed
     return PlanDurations(self, opt, seedOut);
 }
 
-uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut)
+// capture from photon counts: one batched computation on every instance of the group
+void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols)
+{
+    for (RayTracer* rt : group) {
+        check(uvrt_plan_begin(rt->ctx, cols), "plan_begin");
+        rt->ClearBuffers(true);                              // ResetDosageMap without the route save
+        rt->currIterations = 0;
+        rt->launchIndex = 0;
+        rt->planCapture = true;
+    }
+    ComputeIterationsBatched(group, group[0]->maxIterations);
+    for (RayTracer* rt : group) rt->planCapture = false;
+}
+
+// capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
+void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples)
+{
+    if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
+    check(uvrt_plan_begin_expected(ctx, (int)list.size()), "plan_begin_expected");
+    ClearBuffers(true);                                      // ResetDosageMap without the route save
+    currIterations = 0;
+    launchIndex = 0;
+    gatherLaunches = 0;
+    for (int it = 0; it < maxIterations; ++it) {
+        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, l.column);
+        Shade();
+        ++currIterations;
+    }
+}
+
+// every instance solves on its own; the durations must agree, and a sweep's column must come back as it went in
+std::vector<float> RayTracer::PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
+                                        uvrt_plan_report* rep, uvrt_plan_bounds_report* brep)
 {
     RayTracer* r0 = group[0];
-    const int L = (int)r0->lightPositions.size();
-    if (L == 0) fatal("PlanDurations: no positions");
-    for (RayTracer* rt : group)
-        if (rt->gatherSamples > 0) fatal("PlanDurations: gatherSamples > 0 is not supported (the exposure matrix holds photon counts)");
-    // a driving route: the L - 1 segments are further columns of E, fixed at the time the drive takes (raytracer.h)
-    const bool driving = r0->driveSpeed > 0.0f && L >= 2;
-    if (driving && L > 128) fatal("PlanDurations: a driving plan takes at most 128 positions (2L - 1 <= 256 columns)");
-    const int cols = driving ? 2 * L - 1 : L;
-    if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
-        fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
-    uint32_t seed0 = 0;
-    check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
-    if (opt.gatherSamples > 0) {
-        // the launches of ComputeDosageMap with gatherSamples = S, launch by launch, every plane captured into its column
-        if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
-        if (r0->shardWorld > 1 || r0->reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
-        check(uvrt_plan_begin_expected(r0->ctx, cols), "plan_begin_expected");
-        r0->ClearBuffers(true);                              // ResetDosageMap without the route save
-        r0->currIterations = 0;
-        r0->launchIndex = 0;
-        r0->gatherLaunches = 0;
-        r0->gatherSamples = opt.gatherSamples;
-        const int T = r0->mesh->triangleCount;
-        for (int it = 0; it < r0->maxIterations; ++it) {
-            for (int i = 0; i < L; ++i) {
-                r0->planGatherColumn = i;
-                r0->ComputeSingleLightDosageMap(r0->lightPositions[i], r0->photonsPerLight, T);
-            }
-            for (int k = 0; driving && k + 1 < L; ++k) {
-                r0->planGatherColumn = L + k;
-                r0->ComputeSegmentDosageMap(r0->lightPositions[k], r0->lightPositions[k + 1], r0->photonsPerLight, T);
-            }
-            r0->Shade();
-            ++r0->currIterations;
-        }
-        r0->planGatherColumn = -1;
-        r0->gatherSamples = 0;
-    } else {
-        for (RayTracer* rt : group) {
-            check(uvrt_plan_begin(rt->ctx, cols), "plan_begin");
-            rt->ClearBuffers(true);                          // ResetDosageMap without the route save
-            rt->currIterations = 0;
-            rt->launchIndex = 0;
-            rt->planCapture = true;
-        }
-        ComputeIterationsBatched(group, r0->maxIterations);
-    }
+    const size_t cols = list.size(), L = r0->lightPositions.size();
     uvrt_plan_params prm;
     memset(&prm, 0, sizeof prm);
     prm.min_dose = opt.minDose >= 0.0f ? opt.minDose : r0->minDosage;
@@ -415,37 +383,54 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     prm.margin = opt.margin;
     prm.rel_gap = opt.relGap;
     prm.mask = opt.mask;
-    uvrt_plan_report rep;
-    memset(&rep, 0, sizeof rep);
-    std::vector<float> d((size_t)cols), d_other((size_t)cols), lower((size_t)cols, 0.0f);
-    std::vector<uint8_t> fixed((size_t)cols, 0);
-    for (int k = 0; driving && k + 1 < L; ++k) {             // the f32 duration TraceBatched gives the segment's replay op
-        const LightPos& a = r0->lightPositions[k];
-        const LightPos& b = r0->lightPositions[k + 1];
-        const float dx = b.position.x - a.position.x, dz = b.position.y - a.position.y;
-        const float len = sqrtf(dx * dx + dz * dz);
-        lower[L + k] = len / r0->driveSpeed;
-        fixed[L + k] = 1;
-    }
+    // the bounds: a stop is free from 0, a sweep fixed at the duration its launch is accumulated with
+    std::vector<float> lower(cols, 0.0f);
+    std::vector<uint8_t> fixed(cols, 0);
+    for (const RouteLaunch& l : list)
+        if (l.kind == UVRT_LAUNCH_SWEEP) { lower[l.column] = l.duration; fixed[l.column] = 1; }
     uvrt_plan_bounds bounds;
     memset(&bounds, 0, sizeof bounds);
     bounds.lower = lower.data();
     bounds.fixed = fixed.data();
-    uvrt_plan_bounds_report brep;
-    memset(&brep, 0, sizeof brep);
-    brep.free_columns = L;
+    memset(brep, 0, sizeof *brep);
+    brep->free_columns = (int)L;
+    std::vector<float> d(cols), d_other(cols);
     for (size_t r = 0; r < group.size(); ++r) {
         RayTracer* rt = group[r];
-        rt->planCapture = false;
         uvrt_plan_report rr;
         float* dr = r == 0 ? d.data() : d_other.data();
-        if (driving) check(uvrt_plan_solve_bounded(rt->ctx, &prm, &bounds, dr, &rr, r == 0 ? &brep : nullptr), "plan_solve_bounded");
+        if (cols > L) check(uvrt_plan_solve_bounded(rt->ctx, &prm, &bounds, dr, &rr, r == 0 ? brep : nullptr), "plan_solve_bounded");
         else check(uvrt_plan_solve(rt->ctx, &prm, dr, &rr), "plan_solve");
-        if (r == 0) rep = rr;
+        if (r == 0) *rep = rr;
         else if (memcmp(d.data(), d_other.data(), d.size() * 4) != 0) fatal("PlanDurations: the contexts of the group planned different durations");
     }
-    if (driving && memcmp(d.data() + L, lower.data() + L, (size_t)(L - 1) * 4) != 0)
-        fatal("PlanDurations: the solver changed the duration of a segment");
+    if (memcmp(d.data() + L, lower.data() + L, (cols - L) * 4) != 0) fatal("PlanDurations: the solver changed the duration of a segment");
+    return d;
+}
+
+uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut)
+{
+    RayTracer* r0 = group[0];
+    const int L = (int)r0->lightPositions.size();
+    if (L == 0) fatal("PlanDurations: no positions");
+    for (RayTracer* rt : group)
+        if (rt->gatherSamples > 0) fatal("PlanDurations: gatherSamples > 0 is not supported (the exposure matrix holds photon counts)");
+    // the columns of E are the route's launches: on a driving route the L - 1 segments follow the stops (raytracer.h)
+    const std::vector<RouteLaunch> list = r0->Launches();
+    if ((int)list.size() > L && L > 128) fatal("PlanDurations: a driving plan takes at most 128 positions (2L - 1 <= 256 columns)");
+    if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
+        fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
+    uint32_t seed0 = 0;
+    check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
+    if (opt.gatherSamples > 0) {
+        if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
+        r0->PlanCaptureGather(list, opt.gatherSamples);
+    } else {
+        PlanCaptureCounts(group, (int)list.size());
+    }
+    uvrt_plan_report rep;
+    uvrt_plan_bounds_report brep;
+    const std::vector<float> d = PlanSolve(group, opt, list, &rep, &brep);
     for (RayTracer* rt : group) {
         for (int i = 0; i < L; ++i) rt->lightPositions[i].duration = d[i];
         rt->planBounds = brep;
@@ -482,26 +467,23 @@ void RayTracer::SetCandidateGrid(int nx, int nz, float inset)
     std::vector<float> xz((size_t)nx * nz * 2);
     GridPositions(xmin, xmax, zmin, zmax, nx, nz, inset, xz.data());
     lightPositions.clear();
-    for (int k = 0; k < nx * nz; ++k) {
-        LightPos lp;
-        lp.position = make_float2(xz[2 * k], xz[2 * k + 1]);
-        lp.duration = 1.0f;
-        lightPositions.push_back(lp);
-    }
+    for (int k = 0; k < nx * nz; ++k) lightPositions.push_back({make_float2(xz[2 * k], xz[2 * k + 1]), 1.0f});
     UpdatePhotonsPerLight();
+}
+
+RayTracer::ShadeArguments RayTracer::ShadeArgs() const       // raytracer.cpp:96-116
+{
+    // only the photons of one iteration; x100: W/m^2 -> microW/cm^2
+    if (viewMode == maxpower) return {UVRT_MAP_MAX, photonsPerLight, lightIntensity * 100, minPower};
+    // x0.1: J/m^2 -> mJ/cm^2
+    return {UVRT_MAP_SUM, photonMapSize / (int)lightPositions.size(), lightIntensity * 0.1f, minDosage};
 }
 
 void RayTracer::Shade()                                      // raytracer.cpp:93-120
 {
-    if (viewMode == maxpower) {
-        // only the photons of one iteration; x100: W/m^2 -> microW/cm^2
-        check(uvrt_shade(ctx, UVRT_MAP_MAX, photonsPerLight, lightIntensity * 100, minPower, thresholdView,
-                         mesh->triangleCount), "computeDosage + dosageToColor");
-    } else {
-        // x0.1: J/m^2 -> mJ/cm^2
-        check(uvrt_shade(ctx, UVRT_MAP_SUM, photonMapSize / (int)lightPositions.size(), lightIntensity * 0.1f,
-                         minDosage, thresholdView, mesh->triangleCount), "computeDosage + dosageToColor");
-    }
+    const ShadeArguments a = ShadeArgs();
+    check(uvrt_shade(ctx, a.which_map, a.photons_per_light, a.scaled_power, a.min_value, thresholdView, mesh->triangleCount),
+          "computeDosage + dosageToColor");
 }
 
 void RayTracer::ResetDosageMap()                             // raytracer.cpp:122-131

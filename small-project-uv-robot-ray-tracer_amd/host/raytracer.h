@@ -21,6 +21,15 @@ struct LightPos {              // raytracer.h:5-9
 
 enum ViewMode { dosage, maxpower, texture };   // raytracer.h:11
 
+// one launch of an iteration of a route (RayTracer::RouteLaunches); `to` is all zero at a stop
+struct RouteLaunch {
+    float from[3], to[3];
+    float duration;
+    int kind;                  // UVRT_LAUNCH_STOP / UVRT_LAUNCH_SWEEP
+    int column;
+    int reserved;              // 0: the record is 40 bytes (uvrt_host_route_launches)
+};
+
 class RayTracer {
 public:
     RayTracer() = default;
@@ -104,13 +113,11 @@ public:
         double margin = 1e-6, relGap = 1e-3;
         int maxIterations = 200;       // cutting-plane rounds of the solver
         const unsigned char* mask = nullptr;    // uint8[T], 0 = not required
-        // S > 0: plan from the direct gather (include/uvrt.h "planning from the direct gather").  PlanDurations then runs,
-        // on this one context, exactly the launches ComputeDosageMap runs with gatherSamples = S for maxIterations
-        // iterations (every stop, then every segment when driving; seed = the launch counter from 0, photons_equiv =
-        // photonsPerLight; Shade after every iteration), each as uvrt_gather_direct -> uvrt_plan_capture_expected(column)
-        // -> uvrt_accumulate_expected(duration), into an exposure matrix of f64 expected counts; columns, bounds and N =
-        // maxIterations x photonsPerLight as for a counts plan.  A group of more than one instance, shardWorld > 1 and
-        // reduceOverComm are fatal.  0: photon counts (RayTracer::gatherSamples > 0 stays fatal there).
+        // S > 0: plan from the direct gather (include/uvrt.h "planning from the direct gather"): on this one context, the
+        // launches ComputeDosageMap runs with gatherSamples = S for maxIterations iterations (seed = the launch counter from 0,
+        // Shade after every iteration), every plane captured into its launch's column of an exposure matrix of f64 expected
+        // counts; columns, bounds and N = maxIterations x photonsPerLight as for a counts plan.  A group of more than one
+        // instance, shardWorld > 1 and reduceOverComm are fatal.  0: photon counts (RayTracer::gatherSamples > 0 is fatal).
         int gatherSamples = 0;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -122,27 +129,30 @@ public:
     void SetCandidateGrid(int nx, int nz, float inset);
     static void GridPositions(float xmin, float xmax, float zmin, float zmax, int nx, int nz, float inset, float* xz);
     bool planCapture = false;                       // ComputeIterationsBatched captures every batch (PlanDurations)
-    // Planning a route that drives (driveSpeed > 0, at least 2 positions, at most 128): E gets 2L - 1 columns, the stops
-    // 0..L-1 and segment k -> k+1 as column L + k, and uvrt_plan_solve_bounded plans the stops (free, lower bound 0) with
-    // every segment FIXED at the f32 time len / driveSpeed its replay op carries (zero-length segments included): the
-    // plan counts what the drive delivers and says which rows only the drive reaches.  planBounds is that solve's
-    // bounds report (met_by_lower: rows the drive alone brings to the minimum; short_rows: rows no stop reaches and the
-    // drive leaves below it) and planSegmentDurations the segment columns as solved (= lower, bit for bit, or fatal);
-    // after a plan without driving: no fixed column, L free ones, no segment.
+    // Planning a route that drives (RouteLaunches has segments; at most 128 positions): E has one column per launch, and
+    // uvrt_plan_solve_bounded plans the stops (free, lower bound 0) with every segment FIXED at its launch's duration: the
+    // plan counts what the drive delivers and says which rows only the drive reaches.  planBounds is that solve's bounds
+    // report (met_by_lower: rows the drive alone brings to the minimum; short_rows: rows no stop reaches and the drive
+    // leaves below it) and planSegmentDurations the segment columns as solved (= the list's, bit for bit, or fatal); after
+    // a plan without driving: no fixed column, L free ones, no segment.
     uvrt_plan_bounds_report planBounds{};
     std::vector<float> planSegmentDurations;
-    // Dose while the robot drives.  driveSpeed (m/s) > 0: after the stops of an iteration ComputeDosageMap traces the
-    // segments 0->1, ..., L-2->L-1 between consecutive positions, the lamp radiating while it moves at that speed
-    // (include/uvrt.h uvrt_generate_sweep: photonsPerLight photons spread uniformly in time over the segment).  A segment
-    // of length len adds its counts with the duration len / driveSpeed, like a stop that stood so long, but NOT to
-    // photonMapSize: Shade's divisor photonMapSize / lightPositions.size() stays the photons per source.  The maximum
-    // map takes a segment's counts like any launch: there it means the mean irradiance over the segment.  0 (default)
-    // is the reference's behaviour, bit for bit.  Saved as <rijsnelheid> in route files when > 0.
-    // ComputeIterationsBatched traces an iteration's L stops and L - 1 segments as 2L - 1 logical launches of
-    // uvrt_trace_batch_launches (the Shade rides on the last), so a group of instances, a ray range and reduceOverComm
-    // work with driving as they do without, PlanDurations included; launch sharding (shardWorld > 1) refuses it.
+    // Dose while the robot drives.  driveSpeed (m/s) > 0: after the stops of an iteration come the segments between
+    // consecutive positions, the lamp radiating while it moves at that speed (include/uvrt.h uvrt_generate_sweep:
+    // photonsPerLight photons spread uniformly in time over the segment).  A segment adds its counts with the time the drive
+    // takes, like a stop that stood so long, but NOT to photonMapSize: Shade's divisor photonMapSize / lightPositions.size()
+    // stays the photons per source.  The maximum map takes a segment's counts like any launch: there it means the mean
+    // irradiance over the segment.  0 (default) is the reference's behaviour, bit for bit.  Saved as <rijsnelheid> in route
+    // files when > 0.  A group of instances, a ray range and reduceOverComm work with driving as they do without,
+    // PlanDurations included; launch sharding (shardWorld > 1) refuses it.
     float driveSpeed = 0;
-    // one segment: a and b are two positions (their durations are not used); len = sqrtf(dx*dx + dz*dz) in f32
+    // The launches of one iteration, in order; ComputeDosageMap, ComputeIterationsBatched and PlanDurations all walk this
+    // one list.  The L stops: from = {x, y, z}, the position's own duration, column i.  Then, iff driveSpeed > 0 (NaN and
+    // negative: no) and L >= 2, the L - 1 segments k -> k+1: from and to at the same y, duration len / driveSpeed with len =
+    // sqrtf(dx*dx + dz*dz) in f32, column L + k (a zero-length segment is traced too, with duration 0: the SEED chain stays
+    // regular).  y is the lamp's foot, the caller's single f32 sum mesh->floorHeight + lightHeight (raytracer.cpp:77).
+    static std::vector<RouteLaunch> RouteLaunches(const std::vector<LightPos>& positions, float y, float driveSpeed);
+    // one segment: a and b are two positions (their durations are not used)
     void ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount);
     void ComputeSegments();                         // the segments of one iteration, in order (nothing at driveSpeed 0)
     // The direct gather in place of photon counting (include/uvrt.h "shadow rays and the direct gather").  gatherSamples
@@ -157,9 +167,19 @@ public:
     int gatherSamples = 0;
     unsigned gatherLaunches = 0;                    // gather launches since ResetDosageMap: the next launch's seed
 private:
-    int planGatherColumn = -1;                      // >= 0: GatherLaunch captures its plane into this column (PlanDurations)
-    void GatherLaunch(const float from[3], const float to[3], float duration, int photonsPerLight, int triangleCount);
-    static void TraceBatched(const std::vector<RayTracer*>& group, int iterations, bool driving);
+    std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
+    // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with samples > 0 the direct
+    // gather -> accumulate_expected, its plane first captured into column captureColumn of a plan when that is >= 0.
+    // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
+    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int captureColumn);
+    struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
+    ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
+    static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
+    // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
+    static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
+    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples);
+    static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
+                                        uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:
     // The reference never reads the dose back; the headless build does.
     void ReadDosage(float* out, int first, int count);

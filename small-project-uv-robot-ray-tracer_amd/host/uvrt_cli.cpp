@@ -80,6 +80,16 @@ void write_f32(const std::string& path, const std::vector<float>& v)
     f.write((const char*)v.data(), (std::streamsize)v.size() * 4);
 }
 
+// --save-route: the first 31 characters of the name, as SaveRoute takes it
+void save_route(RayTracer& rt, const std::string& name)
+{
+    if (name.empty()) return;
+    char buf[32];
+    strncpy(buf, name.c_str(), 31);
+    buf[31] = 0;
+    rt.SaveRoute(buf);
+}
+
 // the route's computation from `seed` with the current durations (batched or per launch), dose read back
 std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 {
@@ -278,12 +288,7 @@ int main(int argc, char** argv)
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather);
-        if (!saveRoute.empty()) {
-            char name[32];
-            strncpy(name, saveRoute.c_str(), 31);
-            name[31] = 0;
-            rayTracer.SaveRoute(name);
-        }
+        save_route(rayTracer, saveRoute);
         return rc;
     }
     // --gpus N: further instances of the same RayTracer, one per context, each with its range of every launch
@@ -354,20 +359,7 @@ int main(int argc, char** argv)
     printf("dose: sum %.6f, %d of %d triangles non-zero, dose[0..3] = %.9g %.9g %.9g %.9g\n", sum, nonzero,
            mesh.triangleCount, dose[0], dose.size() > 1 ? dose[1] : 0.f, dose.size() > 2 ? dose[2] : 0.f,
            dose.size() > 3 ? dose[3] : 0.f);
-    if (!dump.empty()) {
-        std::ofstream f(dump, std::ios::binary);
-        if (dump.size() > 4 && dump.substr(dump.size() - 4) == ".npy") {
-            // NumPy format 1.0: magic, version, header length, dict padded to a 64-byte boundary
-            std::string hdr = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(dose.size()) + ",), }";
-            while ((10 + hdr.size() + 1) % 64) hdr += ' ';
-            hdr += '\n';
-            const unsigned short hl = (unsigned short)hdr.size();
-            f.write("\x93NUMPY\x01\x00", 8);
-            f.write((const char*)&hl, 2);
-            f.write(hdr.data(), (std::streamsize)hdr.size());
-        }
-        f.write((const char*)dose.data(), (std::streamsize)dose.size() * 4);
-    }
+    if (!dump.empty()) write_f32(dump, dose);
     if (!ply.empty()) {
         std::vector<float> color((size_t)mesh.triangleCount * 9);
         if (uvrt_read_color(rayTracer.ctx, color.data(), 0, mesh.triangleCount) != UVRT_OK) {
@@ -401,11 +393,6 @@ int main(int argc, char** argv)
         if (memcmp(other.data(), dose.data(), dose.size() * 4) != 0) { fprintf(stderr, "rank doses differ\n"); return 1; }
         delete rt;
     }
-    if (!saveRoute.empty()) {
-        char name[32];
-        strncpy(name, saveRoute.c_str(), 31);
-        name[31] = 0;
-        rayTracer.SaveRoute(name);                           // myapp.cpp:298
-    }
+    save_route(rayTracer, saveRoute);                        // myapp.cpp:298
     return 0;
 }
