@@ -189,6 +189,22 @@ typedef struct {
     int32_t photons_equiv;   /* N > 0: Shade's divisor for maps fed by this plane */
     int32_t reserved[2];
 } uvrt_gather_params;
+/* The gather sampling mode: how u_h and u_m above are formed.  A property of the context like uvrt_set_flavour: it survives
+ * uvrt_set_scene, needs no device work and is read by uvrt_gather_direct alone (uvrt_occluded, the photon path and the plan
+ * calls never look at it).  UVRT_GATHER_INDEPENDENT (default) is the rule above, bit for bit.  UVRT_GATHER_STRATIFIED keeps
+ * the four draws, their order, (a, b) and everything after the origin, and replaces the two lamp coordinates of sample s:
+ *     rng = WangHash(j ^ WangHash(seed));  xi_h, xi_m, a, b = RandomFloat(&rng) x 4      (xi_m is drawn and discarded)
+ *     u_h = fl( fl((float)s + xi_h) / (float)S )                   jittered stratum s of the rod: u_h in [s/S, (s+1)/S]
+ *     h_t = WangHash(t ^ WangHash(seed ^ 0x9E3779B9u))
+ *     k   = s * 0x9E3779B9u + h_t                                  (uint32, wraps)
+ *     u_m = (float)(k >> 8) * 2^-24                                exact: the golden-ratio Weyl sequence, rotated per triangle
+ * The rod's visibility behind an occluder's edge is close to monotone in height, so one sample per stratum takes most of the
+ * binary-visibility scatter out of a triangle's estimate; every stratum is uniform and h_t is a hash, so the
+ * estimate is unbiased in the sense the independent one is.  With S = 1 at a stop both modes give the same bits (u_h =
+ * fl(fl(0 + xi_h) / 1) = xi_h and u_m multiplies a zero segment).  Another value: UVRT_ERR_INVALID, the mode unchanged. */
+enum { UVRT_GATHER_INDEPENDENT = 0, UVRT_GATHER_STRATIFIED = 1 };
+int uvrt_set_gather_sampling(uvrt_ctx* ctx, int32_t mode);
+int uvrt_get_gather_sampling(uvrt_ctx* ctx, int32_t* mode);
 /* writes expected[first_tri .. first_tri + tri_count) */
 int uvrt_gather_direct(uvrt_ctx* ctx, const uvrt_gather_params* params, int32_t first_tri, int32_t tri_count);
 /* cl/accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]: photonMap += expected * (double)timeStep,

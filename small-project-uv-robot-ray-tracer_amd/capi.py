@@ -77,6 +77,8 @@ SYMBOLS = [
     ("uvrt_seed_next_sweep", _u32, [_fp, _f32, _u32]),
     ("uvrt_occluded", C.c_int, [_vp, _vp, _i64, _vp]),
     ("uvrt_gather_direct", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_set_gather_sampling", C.c_int, [_vp, _i32]),
+    ("uvrt_get_gather_sampling", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_accumulate_expected", C.c_int, [_vp, _f32, _i32]),
     ("uvrt_read_expected", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_write_expected", C.c_int, [_vp, _vp, _i32, _i32]),
@@ -461,6 +463,15 @@ class Ctx:
 
     def set_seed_mode(self, mode):
         self._ck(self._L.uvrt_set_seed_mode(self._h, int(mode)))
+
+    def set_gather_sampling(self, mode):
+        """how gather_direct places its samples on the lamp: 0 independent (default), 1 stratified (include/uvrt.h)"""
+        self._ck(self._L.uvrt_set_gather_sampling(self._h, int(mode)))
+
+    def get_gather_sampling(self):
+        m = _i32()
+        self._ck(self._L.uvrt_get_gather_sampling(self._h, C.byref(m)))
+        return int(m.value)
 
     def set_sort_bits(self, bits):
         self._ck(self._L.uvrt_set_sort_bits(self._h, int(bits)))

@@ -1,5 +1,6 @@
 // uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
-// uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected, uvrt_write_expected (uvrt_occlude.hip's kernels)
+// uvrt_occluded, uvrt_set_gather_sampling, uvrt_get_gather_sampling, uvrt_gather_direct, uvrt_accumulate_expected,
+// uvrt_read_expected, uvrt_write_expected (uvrt_occlude.hip's kernels)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
@@ -73,6 +74,22 @@ int uvrt_occluded(uvrt_ctx* c, const void* rays32, int64_t n, uint8_t* out)
     return copy_sync(c, out, c->g_occ.p, (size_t)n, hipMemcpyDeviceToHost);
 }
 
+int uvrt_set_gather_sampling(uvrt_ctx* c, int32_t mode)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_set_gather_sampling: null context");
+    if (mode != UVRT_GATHER_INDEPENDENT && mode != UVRT_GATHER_STRATIFIED)
+        return fail(UVRT_ERR_INVALID, "uvrt_set_gather_sampling: mode must be 0 (independent) or 1 (stratified), not %d", mode);
+    c->gather_sampling = mode;
+    return UVRT_OK;
+}
+
+int uvrt_get_gather_sampling(uvrt_ctx* c, int32_t* mode)
+{
+    if (!c || !mode) return fail(UVRT_ERR_INVALID, "uvrt_get_gather_sampling: null argument");
+    *mode = c->gather_sampling;
+    return UVRT_OK;
+}
+
 int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first_tri, int32_t tri_count)
 {
     if (!c || !prm) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: null argument");
@@ -112,6 +129,8 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     g.light_length = prm->light_length;
     g.seed_hash = host_wang_hash(prm->seed);
     g.samples = S;
+    g.seed = prm->seed;
+    g.mode = c->gather_sampling;
     // chunks of floor(capacity / S) triangles: a triangle's samples never straddle two of them, so the chunking shows in no bit
     const int32_t per_chunk = (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX);
     for (int32_t done = 0; done < tri_count; done += per_chunk) {

@@ -221,6 +221,7 @@ struct uvrt_ctx {
     bool record_hits = false;
     int32_t variant = 0;
     int32_t flavour = 0;
+    int32_t gather_sampling = 0;   // uvrt_set_gather_sampling: read by uvrt_gather_direct alone
 #ifdef UVRT_DEV_VARIANTS
     // timing-only probe of the developer build (UVRT_PROBE_SKIP_GENERATE=n): after n uvrt_trace_batch calls the generate
     // launches are skipped -- the buffers still hold the same rays when every computation is the same (bench.py), so

@@ -380,6 +380,8 @@ struct GatherGenParams {
     float light_length;
     uint32_t seed_hash;      // WangHash(seed)
     int32_t first_tri, tri_count, samples;
+    uint32_t seed;           // the raw seed: the stratified rule hashes it again for the triangle's rotation
+    int32_t mode;            // UVRT_GATHER_INDEPENDENT / UVRT_GATHER_STRATIFIED: which instantiation is launched
 };
 void launch_gather_generate(const GatherGenParams& p, hipStream_t s);
 void launch_gather_reduce(const float4* gtris, const double* w, const uint8_t* occluded, double* expected, int32_t first_tri,

@@ -180,16 +180,27 @@ __device__ __forceinline__ double tri_normal(const float4 e1, const float4 e2, d
     return sqrt(nx * nx + ny * ny + nz * nz);
 }
 
+// MODE: the context's gather sampling (include/uvrt.h uvrt_set_gather_sampling).  0 is the independent rule; 1 puts sample s
+// into stratum s of the rod and the sweep coordinate on a golden-ratio Weyl sequence rotated per triangle and seed.  The four
+// draws are the same in both, so (a, b) are: only u_h and u_m differ.
+template <int MODE>
 __global__ __launch_bounds__(256) void k_gather_generate(GatherGenParams g)
 {
+    static_assert(MODE == 0 || MODE == 1, "gather sampling: independent or stratified");
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)g.tri_count * g.samples) return;
     const uint32_t lt = (uint32_t)(i / g.samples), s = (uint32_t)(i - (int64_t)lt * g.samples);
     const uint32_t t = (uint32_t)g.first_tri + lt;
     const uint32_t j = t * (uint32_t)g.samples + s;
     uint32_t rng = wang_hash(j ^ g.seed_hash);
-    const float u_h = random_float(rng);
-    const float u_m = random_float(rng);
+    float u_h = random_float(rng);
+    float u_m = random_float(rng);
+    if (MODE == 1) {
+        u_h = ((float)s + u_h) / (float)g.samples;                          // jittered stratum s: two roundings
+        const uint32_t h_t = wang_hash(t ^ wang_hash(g.seed ^ 0x9E3779B9u));    // once per thread: the triangle's rotation
+        const uint32_t k = s * 0x9E3779B9u + h_t;                          // wraps
+        u_m = (float)(k >> 8) * 5.9604644775390625e-8f;                     // 24 bits x 2^-24: exact
+    }
     float a = random_float(rng);
     float b = random_float(rng);
     if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
@@ -227,7 +238,9 @@ void launch_gather_generate(const GatherGenParams& p, hipStream_t s)
 {
     const int64_t n = (int64_t)p.tri_count * p.samples;
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_gather_generate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (p.mode == 1) hipLaunchKernelGGL((k_gather_generate<1>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((k_gather_generate<0>), grid, dim3(256), 0, s, p);
 }
 
 __global__ __launch_bounds__(256) void k_gather_reduce(const float4* __restrict__ gtris, const double* __restrict__ w,

@@ -67,6 +67,8 @@ SYMBOLS = [
                                  C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_gather", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp,
                                         C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_sampling", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                                 C.c_int, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -83,9 +85,9 @@ SYMBOLS = [
 _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIterations",
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
-           "photonMapSize", "viewMode", "driveSpeed", "gatherSamples"}
+           "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
-               "photonMapSize", "viewMode", "gatherSamples"}
+               "photonMapSize", "viewMode", "gatherSamples", "gatherSampling"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 
@@ -242,7 +244,7 @@ class RayTracer:
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
 
     def PlanDurations(self, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None,
-                      gather_samples=0):
+                      gather_samples=0, gather_sampling=0):
         """RayTracer::PlanDurations: one batched computation over the current positions from the current SEED with the
         exposure captured, then the least durations that bring every required triangle to min_dose (default: the
         route's minDosage).  They are written into the positions; returns (durations float32[P], report dict with
@@ -251,12 +253,15 @@ class RayTracer:
         report (capi.PlanBoundsReport) and "segment_durations" (float32[P - 1]).  gather_samples = S > 0 plans from the
         direct gather instead (PlanOptions::gatherSamples): the launches of a gatherSamples = S run, launch by launch, into
         an exposure matrix of f64 expected counts (ctx.plan_read_exposure_expected), so triangles no photon reaches are
-        planned for too; the plan is as good as the estimator."""
+        planned for too; the plan is as good as the estimator (DESIGN.md 12).  gather_sampling (PlanOptions::gatherSampling)
+        is those launches' sampling mode: 0 independent, 1 stratified; it needs gather_samples > 0."""
+        if gather_sampling and not gather_samples:
+            raise ValueError("gather_sampling needs gather_samples > 0")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
         if gather_samples:
-            self._L.uvrt_host_rt_plan_gather(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                             float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                             int(gather_samples), C.byref(rep), C.byref(seed))
+            self._L.uvrt_host_rt_plan_gather_sampling(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                                      float(margin), float(rel_gap), int(max_iterations), _addr(keep),
+                                                      int(gather_samples), int(gather_sampling), C.byref(rep), C.byref(seed))
             return _plan_result(self, rep, seed)
         self._L.uvrt_host_rt_plan(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons), float(margin),
                                   float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))

@@ -27,11 +27,12 @@ std::vector<LightPos> positions(const float* xyd, int n)
 std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>((RayTracer**)rs, (RayTracer**)rs + n); }
 
 RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                    const unsigned char* mask, int gather_samples)
+                                    const unsigned char* mask, int gather_samples, int gather_sampling = 0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
     o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
+    o.gatherSampling = gather_sampling;
     return o;
 }
 
@@ -149,6 +150,14 @@ void uvrt_host_rt_plan_gather(void* r, float min_dose, int min_photons, double m
 {
     *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples), seed);
 }
+// the same with PlanOptions::gatherSampling beside it (include/uvrt.h uvrt_set_gather_sampling)
+void uvrt_host_rt_plan_gather_sampling(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                                       const unsigned char* mask, int gather_samples, int gather_sampling, uvrt_plan_report* rep,
+                                       unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling), seed);
+}
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
@@ -178,6 +187,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(minPower, float) F(photonsPerLight, int) F(compTime, float) F(progress, float)
     F(finishedComputation, bool) F(thresholdView, bool) F(startedComputation, bool)
     F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
+    F(gatherSampling, int)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

@@ -186,16 +186,16 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, -1);
+    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1);
 }
 
 void RayTracer::ComputeSegments()
 {
     for (const RouteLaunch& l : Launches())
-        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, -1);
+        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1);
 }
 
-void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int captureColumn)
+void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
@@ -210,6 +210,7 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
         g.samples = samples;
         g.seed = gatherLaunches++;
         g.photons_equiv = photons;
+        check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
         check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
         if (captureColumn >= 0) check(uvrt_plan_capture_expected(ctx, captureColumn), "plan_capture_expected");
         check(uvrt_accumulate_expected(ctx, l.duration, triangleCount), "accumulate_expected");
@@ -230,12 +231,14 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
 void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount)
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
-    RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples, -1);
+    RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
+              gatherSampling, -1);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
-    RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples, -1);
+    RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
+              gatherSampling, -1);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -352,7 +355,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 }
 
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
-void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples)
+void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     check(uvrt_plan_begin_expected(ctx, (int)list.size()), "plan_begin_expected");
@@ -361,7 +364,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, l.column);
+        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column);
         Shade();
         ++currIterations;
     }
@@ -424,7 +427,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
-        r0->PlanCaptureGather(list, opt.gatherSamples);
+        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -577,6 +580,7 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
     o << "    <minimale_bestralingssterkte>" << float_str(minPower) << "</minimale_bestralingssterkte>\n";
     if (driveSpeed > 0.0f) o << "    <rijsnelheid>" << float_str(driveSpeed) << "</rijsnelheid>\n";   // (not in the reference's files)
     if (gatherSamples > 0) o << "    <gather_samples>" << gatherSamples << "</gather_samples>\n";                  // (likewise)
+    if (gatherSamples > 0 && gatherSampling > 0) o << "    <gather_sampling>" << gatherSampling << "</gather_sampling>\n";
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
     if (lightPositions.empty()) o << "    <route/>\n";
@@ -614,6 +618,8 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("rijsnelheid"))) to_float(trim(e->text), &driveSpeed);
     gatherSamples = 0;
     if ((e = root.child("gather_samples"))) to_int(trim(e->text), &gatherSamples);
+    gatherSampling = 0;
+    if ((e = root.child("gather_sampling"))) to_int(trim(e->text), &gatherSampling);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

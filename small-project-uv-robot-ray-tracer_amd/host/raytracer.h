@@ -119,6 +119,9 @@ public:
         // counts; columns, bounds and N = maxIterations x photonsPerLight as for a counts plan.  A group of more than one
         // instance, shardWorld > 1 and reduceOverComm are fatal.  0: photon counts (RayTracer::gatherSamples > 0 is fatal).
         int gatherSamples = 0;
+        // the gather sampling mode of those launches (uvrt_set_gather_sampling; read only with gatherSamples > 0).  Like S it
+        // is the plan's own: RayTracer::gatherSampling is not touched.
+        int gatherSampling = 0;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -165,19 +168,24 @@ public:
     // launch, on one context, and a counts plan's exposure matrix holds photon counts.  To plan from the gather leave this
     // at 0 and give PlanOptions::gatherSamples: the plan is then as good as the estimator.
     int gatherSamples = 0;
+    // How the gather places its samples on the lamp (include/uvrt.h uvrt_set_gather_sampling): 0 independent draws (default),
+    // 1 rod strata and a rotated sweep sequence.  Handed to the context before every gather launch; read by
+    // nothing else.  Saved as <gather_sampling> after <gather_samples> in route files when both are > 0.
+    int gatherSampling = 0;
     unsigned gatherLaunches = 0;                    // gather launches since ResetDosageMap: the next launch's seed
 private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
     // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with samples > 0 the direct
     // gather -> accumulate_expected, its plane first captured into column captureColumn of a plan when that is >= 0.
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
-    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int captureColumn);
+    // `sampling`: the gather sampling mode of a launch with samples > 0.
+    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn);
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
-    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples);
+    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

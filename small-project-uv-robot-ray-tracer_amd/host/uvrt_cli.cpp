@@ -48,6 +48,12 @@
 //                                           saves the planned route with <gather_samples>S.  The plan is as good as the
 //                                           estimator: raise S or the margin for a tighter one.  One context,
 //                                           launch by launch: refused with --gather, --batch, --gpus > 1 and --plan-holdout
+//            [--gather-sampling independent|stratified]
+//                                           how the gather places its S samples on the lamp (RayTracer::gatherSampling,
+//                                           PlanOptions::gatherSampling; default: the route's <gather_sampling>, independent):
+//                                           stratified puts sample s into stratum s of the rod and the sweep coordinate on a
+//                                           rotated golden-ratio sequence -- the same shadow rays, at a stop an estimate about as
+//                                           tight as four times the samples.  Needs --gather S or --plan-gather S
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -111,18 +117,21 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 }
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
-             const std::string& dump, const std::string& verifyDump, int planGather)
+             const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
     opt.minDose = minDose;
     opt.minPhotons = minPhotons;
     opt.gatherSamples = planGather;
+    opt.gatherSampling = planGather > 0 ? gatherSampling : 0;
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
     if (planGather > 0) {
         rt.gatherSamples = planGather;       // the planned route is a gather route: --plan-verify and --save-route
+        rt.gatherSampling = opt.gatherSampling;
         printf("plan: exposure from the direct gather, %d samples per triangle and launch\n", planGather);
+        if (opt.gatherSampling == UVRT_GATHER_STRATIFIED) printf("plan: stratified gather sampling\n");
     }
     const float m = minDose >= 0.0f ? minDose : rt.minDosage;
     printf("plan: %d positions, %d used, total duration %.9g (lower bound %.9g, gap %.3g), %s after %d iterations\n",
@@ -188,7 +197,7 @@ int main(int argc, char** argv)
     int iterations = -1, lamps = -1, device = 0, gpus = 1, batch = 0, flavour = 0;
     bool calibrate = false, plan = false, planVerify = false, planHoldout = false;
     float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f, planDrive = -1.0f;
-    int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1, planGather = 0;
+    int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1, planGather = 0, gatherSampling = -1;
     uint32_t holdoutSeed = 0;
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -227,6 +236,13 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--plan-drive")) { need(1); plan = true; planDrive = (float)atof(argv[++i]); if (!(planDrive >= 0.0f)) { fprintf(stderr, "--plan-drive must be >= 0\n"); return 2; } }
         else if (!strcmp(argv[i], "--gather")) { need(1); gather = atoi(argv[++i]); if (gather < 0 || gather > 4096) { fprintf(stderr, "--gather must be in [0, 4096]\n"); return 2; } }
         else if (!strcmp(argv[i], "--plan-gather")) { need(1); plan = true; planGather = atoi(argv[++i]); if (planGather < 1 || planGather > 4096) { fprintf(stderr, "--plan-gather must be in [1, 4096]\n"); return 2; } }
+        else if (!strcmp(argv[i], "--gather-sampling")) {
+            need(1);
+            const char* v = argv[++i];
+            if (!strcmp(v, "independent")) gatherSampling = UVRT_GATHER_INDEPENDENT;
+            else if (!strcmp(v, "stratified")) gatherSampling = UVRT_GATHER_STRATIFIED;
+            else { fprintf(stderr, "--gather-sampling independent|stratified (with --gather S or --plan-gather S)\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -234,6 +250,7 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
+    if (gatherSampling >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-sampling needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
@@ -266,6 +283,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (gather >= 0) rayTracer.gatherSamples = gather;
+    if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
         return 2;
@@ -287,7 +305,8 @@ int main(int argc, char** argv)
         }
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
-        const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather);
+        const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
+                                gatherSampling < 0 ? 0 : gatherSampling);
         save_route(rayTracer, saveRoute);
         return rc;
     }
