@@ -205,6 +205,29 @@ typedef struct {
 enum { UVRT_GATHER_INDEPENDENT = 0, UVRT_GATHER_STRATIFIED = 1 };
 int uvrt_set_gather_sampling(uvrt_ctx* ctx, int32_t mode);
 int uvrt_get_gather_sampling(uvrt_ctx* ctx, int32_t* mode);
+/* The variance plane: with uvrt_set_gather_variance(ctx, 1) uvrt_gather_direct also writes variance[first_tri .. first_tri +
+ * tri_count), f64[T], an estimate of the variance of expected[t] from the same shadow rays.  A property of the context like
+ * the sampling mode: default 0, survives uvrt_set_scene, needs no device work; a value other than 0 / 1 is UVRT_ERR_INVALID
+ * with the state unchanged.  With the state off uvrt_gather_direct is the call above bit for bit and never touches the plane.
+ * With it on, samples < 2 is UVRT_ERR_INVALID with nothing changed, expected[t] carries the same bits as with it off, and with
+ * x_s = occluded ? 0 : w_s, `sum` and nn as above, m = sum / (double)S, c = (double)photons_equiv * (0.5*nn),
+ * SS = (double)S * (double)(S-1):
+ *     UVRT_GATHER_INDEPENDENT:  q = sum_{s=0}^{S-1} (x_s - m)*(x_s - m),            v = q / SS          (sample variance of the mean)
+ *     UVRT_GATHER_STRATIFIED:   q = sum_{s=1}^{S-1} (x_s - x_{s-1})*(x_s - x_{s-1}),  v = q / (2.0 * SS)  (successive differences)
+ *     variance[t] = (nn == 0) ? 0 : (c*c) * v
+ * every operator one f64 rounding, the sums in sample order, no atomics: a pure function of the arguments like the expected
+ * plane.  The successive-difference form suits one sample per stratum: the sample variance would charge the estimate for the
+ * rod's own trend in height, which stratification has taken out; a single visibility edge of weight w contributes
+ * w^2 / (2 S (S-1)), at least the true <= w^2 / (4 S^2), so the form is conservative there.  The estimate is for S >= 16: at
+ * S = 4 about half of all bounds expected - 2 sqrt(variance) are 0.
+ * The plane is allocated (zeroed) on first use and zeroed by uvrt_set_scene; uvrt_accumulate_expected zeroes
+ * variance[0 .. tri_count) along with the expected plane when the plane exists, so a stale variance is never paired with a
+ * later estimate.  uvrt_read_variance / uvrt_write_variance are uvrt_read_expected / uvrt_write_expected for this plane (the
+ * write serves a caller who brings an estimate of their own). */
+int uvrt_set_gather_variance(uvrt_ctx* ctx, int32_t on);
+int uvrt_get_gather_variance(uvrt_ctx* ctx, int32_t* on);
+int uvrt_read_variance(uvrt_ctx* ctx, double* out, int32_t first, int32_t count);
+int uvrt_write_variance(uvrt_ctx* ctx, const double* in, int32_t first, int32_t count);
 /* writes expected[first_tri .. first_tri + tri_count) */
 int uvrt_gather_direct(uvrt_ctx* ctx, const uvrt_gather_params* params, int32_t first_tri, int32_t tri_count);
 /* cl/accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]: photonMap += expected * (double)timeStep,
@@ -402,6 +425,29 @@ int uvrt_plan_read_exposure_expected(uvrt_ctx* ctx, int32_t position, double* ou
 /* UVRT_ERR_INVALID with nothing changed: uvrt_plan_capture_batch / uvrt_plan_read_exposure on an expected plan,
  * uvrt_plan_capture_expected / uvrt_plan_read_exposure_expected on a counts plan or without a plan, a position outside
  * [0, P), a null pointer. */
+/* ---- planning for a lower confidence bound: an exposure matrix with its variance ----
+ * The solver guarantees the minimum dose for the ESTIMATED exposure; an estimate scatters round the truth, so about half the
+ * rows that bind a plan sit below the minimum in reality.  An expected plan may carry V[p][t], the variance of X[p][t]:
+ * uvrt_plan_begin_expected_variance is uvrt_plan_begin_expected with V as double[P][T], zeroed, beside X (the same limits;
+ * drops a plan of either kind).  On such a plan uvrt_plan_capture_expected also does V[position][t] += variance[t] (launches
+ * of different seeds are independent, so their variances add as their estimates do; a sum that is not finite or is negative
+ * raises the same flag); on a plan without V it is the call above.  Calling sequence: uvrt_set_gather_variance(1) ->
+ * uvrt_plan_begin_expected_variance -> per launch uvrt_gather_direct -> uvrt_plan_capture_expected ->
+ * uvrt_accumulate_expected -> ... -> uvrt_plan_lower_confidence(z) -> uvrt_plan_solve*.
+ * uvrt_plan_lower_confidence, once per plan after the captures: for every element, in place,
+ *     lo = X - z*sqrt(V);  X = lo > 0 ? lo : 0                      (one f64 rounding per operator)
+ * z finite and >= 0; z = 0 leaves every bit of X as it was.  Afterwards every solve, model-dose, class and required call works
+ * on the bound unchanged -- one solver -- and uvrt_plan_capture_expected on this plan and a second
+ * uvrt_plan_lower_confidence return UVRT_ERR_INVALID with nothing changed.
+ * Why the bound is taken per element: for durations d >= 0, sum_p z sigma_p d_p >= z * sqrt(sum_p sigma_p^2 d_p^2), so the
+ * row sum of the bounds is at least as cautious as the estimate minus z standard errors of the row's own dose, for every
+ * duration vector; and the problem stays the same LP (the row's own standard error would make it a second-order cone).
+ * uvrt_plan_read_exposure_variance: test hook, row `position` of V; synchronises.
+ * UVRT_ERR_INVALID with nothing changed: either call on a plan without V or without a plan, z negative or not finite, a
+ * position outside [0, P), a null pointer. */
+int uvrt_plan_begin_expected_variance(uvrt_ctx* ctx, int32_t positions);
+int uvrt_plan_read_exposure_variance(uvrt_ctx* ctx, int32_t position, double* out, int32_t first, int32_t count);
+int uvrt_plan_lower_confidence(uvrt_ctx* ctx, double z);
 /* the smallest float >= v that "%.8g" (SaveRoute) prints back to itself through strtof (LoadRoute): how the solver rounds
  * the durations it returns.  Host only, no GPU needed. */
 float uvrt_plan_round_trip_up(float v);
@@ -481,7 +527,7 @@ int uvrt_read_photon_map(uvrt_ctx* ctx, int32_t which_map, double* out, int32_t 
  * tensors handed to an RCCL collective).  which: 0 photonMap f64[T], 1 maxPhotonMap f64[T],
  * 2 tempPhotonMap i32[T], 3 dosageMap f32[T], 4 colour f32[9T], 5 the folded planes i32[launches][T] of the
  * traced batch (for a caller that brings its own collective; uvrt_reduce_batch is the native one), 6 the direct gather's
- * expected plane f64[T].
+ * expected plane f64[T], 7 its variance plane f64[T].
  * The call is also the ordering point for external work on these arrays: it orders the context's
  * stream after every outstanding launch (with launch pipelining some sit on the library's second
  * stream) and makes the library's next work on the arrays wait for whatever the caller enqueues on

@@ -105,6 +105,13 @@ SYMBOLS = [
     ("uvrt_plan_begin_expected", C.c_int, [_vp, _i32]),
     ("uvrt_plan_capture_expected", C.c_int, [_vp, _i32]),
     ("uvrt_plan_read_exposure_expected", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_set_gather_variance", C.c_int, [_vp, _i32]),
+    ("uvrt_get_gather_variance", C.c_int, [_vp, C.POINTER(_i32)]),
+    ("uvrt_read_variance", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_write_variance", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_plan_begin_expected_variance", C.c_int, [_vp, _i32]),
+    ("uvrt_plan_read_exposure_variance", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_plan_lower_confidence", C.c_int, [_vp, C.c_double]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -408,6 +415,18 @@ class Ctx:
         v = np.ascontiguousarray(values, dtype=np.float64)
         self._ck(self._L.uvrt_write_expected(self._h, _ptr(v), int(first), int(v.size)))
 
+    def read_variance(self, first=0, count=None):
+        """the variance plane beside the expected plane (set_gather_variance)"""
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float64)
+        self._ck(self._L.uvrt_read_variance(self._h, _ptr(out), int(first), int(count)))
+        return out
+
+    def write_variance(self, values, first=0):
+        """host values into variance[first, first + len(values))"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        self._ck(self._L.uvrt_write_variance(self._h, _ptr(v), int(first), int(v.size)))
+
     @property
     def seed(self):
         s = C.c_uint32()
@@ -472,6 +491,15 @@ class Ctx:
         m = _i32()
         self._ck(self._L.uvrt_get_gather_sampling(self._h, C.byref(m)))
         return int(m.value)
+
+    def set_gather_variance(self, on):
+        """1: gather_direct also writes the variance plane (include/uvrt.h); needs samples >= 2"""
+        self._ck(self._L.uvrt_set_gather_variance(self._h, int(on)))
+
+    def get_gather_variance(self):
+        v = _i32()
+        self._ck(self._L.uvrt_get_gather_variance(self._h, C.byref(v)))
+        return int(v.value)
 
     def set_sort_bits(self, bits):
         self._ck(self._L.uvrt_set_sort_bits(self._h, int(bits)))
@@ -547,6 +575,21 @@ class Ctx:
         out = np.empty(count, dtype=np.float64)
         self._ck(self._L.uvrt_plan_read_exposure_expected(self._h, int(position), _ptr(out), int(first), int(count)))
         return out
+
+    def plan_begin_expected_variance(self, positions):
+        """an expected plan with V, the variance of every element, beside X: plan_capture_expected adds the variance plane"""
+        self._ck(self._L.uvrt_plan_begin_expected_variance(self._h, int(positions)))
+        self._plan_p = int(positions)
+
+    def plan_read_exposure_variance(self, position, first=0, count=None):
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float64)
+        self._ck(self._L.uvrt_plan_read_exposure_variance(self._h, int(position), _ptr(out), int(first), int(count)))
+        return out
+
+    def plan_lower_confidence(self, z):
+        """X = max(0, X - z sqrt(V)) in place, once per plan after the captures: the solves then plan for that bound"""
+        self._ck(self._L.uvrt_plan_lower_confidence(self._h, float(z)))
 
     def plan_capture_batch(self, positions_of_launches):
         pos = np.ascontiguousarray(positions_of_launches, dtype=np.int32)

@@ -366,6 +366,7 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     c->g_tris.release();                              // the gather's triangles and its plane: per scene, back (zeroed) on next use
     c->g_tris_valid = false;
     c->expected.release();
+    c->variance.release();
     c->scene_force_exact = tiny_bound || huge_vertex;
     if ((rc = hot_reset(c, true))) return rc;         // statistics of the previous scene; the new scene's first slab
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -696,7 +697,11 @@ int uvrt_device_ptr(uvrt_ctx* c, int32_t which, void** ptr, int64_t* bytes)
             if (int rc = ensure_expected(c)) return rc;
             b = &c->expected; elem = 8;
             break;
-        default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..6");
+        case 7:
+            if (int rc = ensure_variance(c)) return rc;
+            b = &c->variance; elem = 8;
+            break;
+        default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..7");
     }
     *ptr = b->p;
     *bytes = (int64_t)((size_t)c->T * elem);

@@ -1,6 +1,7 @@
 // uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
-// uvrt_occluded, uvrt_set_gather_sampling, uvrt_get_gather_sampling, uvrt_gather_direct, uvrt_accumulate_expected,
-// uvrt_read_expected, uvrt_write_expected (uvrt_occlude.hip's kernels)
+// uvrt_occluded, uvrt_set_gather_sampling, uvrt_get_gather_sampling, uvrt_set_gather_variance, uvrt_get_gather_variance,
+// uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected, uvrt_write_expected, uvrt_read_variance,
+// uvrt_write_variance (uvrt_occlude.hip's kernels)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
@@ -11,6 +12,11 @@ namespace uvrt_impl {
 int ensure_expected(uvrt_ctx* c)
 {
     return c->expected.ensure((size_t)c->T * 8, true, c->stream);      // (nothing to do once it is there)
+}
+
+int ensure_variance(uvrt_ctx* c)
+{
+    return c->variance.ensure((size_t)c->T * 8, true, c->stream);
 }
 
 // Everything a shadow-ray launch works on, on the context's stream behind all outstanding work: lane 0's ray buffer, the
@@ -90,6 +96,21 @@ int uvrt_get_gather_sampling(uvrt_ctx* c, int32_t* mode)
     return UVRT_OK;
 }
 
+int uvrt_set_gather_variance(uvrt_ctx* c, int32_t on)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_set_gather_variance: null context");
+    if (on != 0 && on != 1) return fail(UVRT_ERR_INVALID, "uvrt_set_gather_variance: on must be 0 or 1, not %d", on);
+    c->gather_variance = on;
+    return UVRT_OK;
+}
+
+int uvrt_get_gather_variance(uvrt_ctx* c, int32_t* on)
+{
+    if (!c || !on) return fail(UVRT_ERR_INVALID, "uvrt_get_gather_variance: null argument");
+    *on = c->gather_variance;
+    return UVRT_OK;
+}
+
 int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first_tri, int32_t tri_count)
 {
     if (!c || !prm) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: null argument");
@@ -100,6 +121,9 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: triangles [%d, +%d) outside [0, %d]", first_tri, tri_count, c->T);
     const int32_t S = prm->samples;
     if (S < 1 || S > 4096) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: samples = %d must be in [1, 4096]", S);
+    const bool var = c->gather_variance != 0;
+    if (var && S < 2)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: the variance plane needs samples >= 2 (uvrt_set_gather_variance), not %d", S);
     if ((int64_t)S > c->capacity)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: samples = %d exceed the ray capacity %lld (uvrt_resize_rays)", S, (long long)c->capacity);
     if ((int64_t)c->T * S >= ((int64_t)1 << 31))
@@ -110,6 +134,8 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     const size_t cap = (size_t)c->capacity;
     if (int rc = c->g_w.ensure(cap * 8, false, c->stream)) return rc;
     if (int rc = ensure_expected(c)) return rc;
+    if (var)
+        if (int rc = ensure_variance(c)) return rc;
     if (!c->g_tris_valid) {
         if (int rc = c->g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
         launch_gather_tris(c->ltris.as<LeafTri>(), c->g_tris.as<float4>(), c->T, c->stream);
@@ -140,8 +166,12 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         launch_gather_generate(g, c->stream);
         HIP_TRY(hipGetLastError());
         if (int rc = trace_shadow_rays(c, (int64_t)cnt * S, "uvrt_gather_direct")) return rc;
-        launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->expected.as<double>(), g.first_tri, cnt, S,
-                             prm->photons_equiv, c->stream);
+        if (var)
+            launch_gather_reduce_var(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->expected.as<double>(), c->variance.as<double>(),
+                                     g.first_tri, cnt, S, prm->photons_equiv, g.mode, c->stream);
+        else
+            launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->expected.as<double>(), g.first_tri, cnt, S,
+                                 prm->photons_equiv, c->stream);
         HIP_TRY(hipGetLastError());
     }
     return UVRT_OK;
@@ -158,29 +188,42 @@ int uvrt_accumulate_expected(uvrt_ctx* c, float time_step, int32_t tri_count)
     launch_accumulate_expected(c->photon_map.as<double>(), c->max_map.as<double>(), c->expected.as<double>(), time_step,
                                tri_count, c->stream);
     HIP_TRY(hipGetLastError());
+    // the variance of the estimate that has just been consumed goes with it: a stale one is never paired with a later estimate
+    if (c->variance.p && tri_count > 0) HIP_TRY(hipMemsetAsync(c->variance.p, 0, (size_t)tri_count * 8, c->stream));
     return mark_map_fence(c);                    // later accumulate / Shade work on a side lane waits for it
 }
 
-// uvrt_read_expected / uvrt_write_expected: a range of the expected plane (made, zeroed, by whichever call comes first)
-static int expected_range(uvrt_ctx* c, const char* who, void* host, int32_t first, int32_t count, hipMemcpyKind kind)
+// uvrt_read_expected / uvrt_write_expected and their variance twins: a range of the expected or the variance plane (made,
+// zeroed, by whichever call comes first)
+static int plane_range(uvrt_ctx* c, const char* who, bool variance, void* host, int32_t first, int32_t count, hipMemcpyKind kind)
 {
     if (!c || !host) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
     if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
     if (!range_ok(host, first, count, c->T))
         return fail(UVRT_ERR_INVALID, "%s: range [%d,+%d) outside [0,%d)", who, first, count, c->T);
     if (int rc = set_device(c)) return rc;
-    if (int rc = ensure_expected(c)) return rc;
-    return range_copy(c, c->expected.p, 8, host, first, count, kind);
+    if (int rc = variance ? ensure_variance(c) : ensure_expected(c)) return rc;
+    return range_copy(c, variance ? c->variance.p : c->expected.p, 8, host, first, count, kind);
 }
 
 int uvrt_read_expected(uvrt_ctx* c, double* out, int32_t first, int32_t count)
 {
-    return expected_range(c, "uvrt_read_expected", out, first, count, hipMemcpyDeviceToHost);
+    return plane_range(c, "uvrt_read_expected", false, out, first, count, hipMemcpyDeviceToHost);
 }
 
 int uvrt_write_expected(uvrt_ctx* c, const double* in, int32_t first, int32_t count)
 {
-    return expected_range(c, "uvrt_write_expected", const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
+    return plane_range(c, "uvrt_write_expected", false, const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
+}
+
+int uvrt_read_variance(uvrt_ctx* c, double* out, int32_t first, int32_t count)
+{
+    return plane_range(c, "uvrt_read_variance", true, out, first, count, hipMemcpyDeviceToHost);
+}
+
+int uvrt_write_variance(uvrt_ctx* c, const double* in, int32_t first, int32_t count)
+{
+    return plane_range(c, "uvrt_write_variance", true, const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
 }
 
 }  // extern "C"

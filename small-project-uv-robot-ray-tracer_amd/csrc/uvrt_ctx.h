@@ -3,7 +3,8 @@
 //   uvrt_capi_launch.hip  the per-launch entry points (generate, extend, accumulate, shade) and the launch lanes
 //   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / uvrt_trace_batch_launches / fold / replay)
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
-//   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected)
+//   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
+//                         uvrt_set_gather_variance and the variance plane)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -136,9 +137,9 @@ struct uvrt_ctx {
     DevBuf free_recs;                          // the free-origin kernel's records, [npairs + T + 1] x 64 B: made on first use
     bool free_recs_valid = false;              // ... for the current scene
     // shadow rays and the direct gather (uvrt_capi_gather.hip): every ray's {orig.x, orig.z}, tmax and answer, the samples'
-    // weights, the triangles by original id and the expected plane f64[T]; all made on first use.  (The rays themselves
-    // go through lane 0's ray buffer, on the context's stream.)
-    DevBuf g_oxz, g_tmax, g_occ, g_w, g_tris, expected;
+    // weights, the triangles by original id, the expected plane f64[T] and the variance plane f64[T] beside it; all made on
+    // first use.  (The rays themselves go through lane 0's ray buffer, on the context's stream.)
+    DevBuf g_oxz, g_tmax, g_occ, g_w, g_tris, expected, variance;
     bool g_tris_valid = false;                 // g_tris holds the current scene
 
     // Launch lanes: consecutive launches (generate -> extend -> accumulate ->
@@ -222,6 +223,7 @@ struct uvrt_ctx {
     int32_t variant = 0;
     int32_t flavour = 0;
     int32_t gather_sampling = 0;   // uvrt_set_gather_sampling: read by uvrt_gather_direct alone
+    int32_t gather_variance = 0;   // uvrt_set_gather_variance: uvrt_gather_direct writes the variance plane as well
 #ifdef UVRT_DEV_VARIANTS
     // timing-only probe of the developer build (UVRT_PROBE_SKIP_GENERATE=n): after n uvrt_trace_batch calls the generate
     // launches are skipped -- the buffers still hold the same rays when every computation is the same (bench.py), so
@@ -536,6 +538,8 @@ int ensure_free_records(uvrt_ctx* c);
 int make_free_records(uvrt_ctx* c);
 // the expected plane of the direct gather, f64[T]: allocated and zeroed on first use (uvrt_capi_gather.hip)
 int ensure_expected(uvrt_ctx* c);
+// the variance plane beside it, f64[T]: likewise
+int ensure_variance(uvrt_ctx* c);
 // the next pair of the extend timing pool (uvrt_extend_time_ms) with its start recorded on `s`; *stop stays null
 // while timing is off
 inline int timing_start(uvrt_ctx* c, hipStream_t s, hipEvent_t* stop)

@@ -386,6 +386,11 @@ struct GatherGenParams {
 void launch_gather_generate(const GatherGenParams& p, hipStream_t s);
 void launch_gather_reduce(const float4* gtris, const double* w, const uint8_t* occluded, double* expected, int32_t first_tri,
                           int32_t tri_count, int32_t samples, int32_t photons_equiv, hipStream_t s);
+// the same reduction with variance[t], the estimate's variance, beside expected[t] (the same bits): `mode` picks the sample
+// variance of the mean (independent samples) or successive differences (stratified); samples >= 2
+void launch_gather_reduce_var(const float4* gtris, const double* w, const uint8_t* occluded, double* expected, double* variance,
+                              int32_t first_tri, int32_t tri_count, int32_t samples, int32_t photons_equiv, int32_t mode,
+                              hipStream_t s);
 // accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]; the plane is zeroed like tempPhotonMap
 void launch_accumulate_expected(double* photon_map, double* max_map, double* expected, float time_step, int32_t T, hipStream_t s);
 

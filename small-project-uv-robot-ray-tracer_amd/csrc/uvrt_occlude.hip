@@ -16,7 +16,9 @@
 // The gather: k_gather_generate makes, for every (triangle, sample), a point on the triangle, a point on the lamp's rod (or
 // on the rod swept along a segment), the ray between them and the sample's weight; k_occlude_free answers which samples see
 // the lamp; k_gather_reduce sums the visible weights per triangle in sample order.  No atomics: the plane is a pure function
-// of the arguments.  This file is built without contraction, every operator below is one rounding.
+// of the arguments.  With the context's variance state on (uvrt_set_gather_variance) k_gather_reduce_var<MODE> takes
+// k_gather_reduce's place: the same expected[t], and beside it the variance of that estimate from a second pass over the same
+// samples.  This file is built without contraction, every operator below is one rounding.
 #include "uvrt_traverse.h"
 
 namespace uvrt {
@@ -264,6 +266,61 @@ void launch_gather_reduce(const float4* gtris, const double* w, const uint8_t* o
     if (tri_count <= 0) return;
     hipLaunchKernelGGL(k_gather_reduce, dim3((unsigned)((tri_count + 255) / 256)), dim3(256), 0, s, gtris, w, occluded, expected,
                        first_tri, tri_count, samples, photons_equiv);
+}
+
+// k_gather_reduce with the variance of the estimate beside it (include/uvrt.h uvrt_set_gather_variance): x_s = occluded ? 0 : w_s,
+// `sum` and nn formed as above, so expected[t] carries the same bits; then a second pass over the samples in order.  MODE 0
+// (independent samples): the sample variance of the mean, q = sum (x_s - m)^2 over S (S - 1).  MODE 1 (one sample per
+// stratum of the rod): successive differences, q = sum (x_s - x_{s-1})^2 over 2 S (S - 1) -- the sample variance would charge
+// the estimate for the rod's own trend, which stratification has already taken out.  samples >= 2.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_gather_reduce_var(const float4* __restrict__ gtris, const double* __restrict__ w,
+                                                           const uint8_t* __restrict__ occluded, double* __restrict__ expected,
+                                                           double* __restrict__ variance, int32_t first_tri, int32_t tri_count,
+                                                           int32_t samples, int32_t photons_equiv)
+{
+    static_assert(MODE == 0 || MODE == 1, "gather sampling: independent or stratified");
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= tri_count) return;
+    const size_t t = (size_t)first_tri + (size_t)i;
+    double nx, ny, nz;
+    const double nn = tri_normal(gtris[t * 3 + 1], gtris[t * 3 + 2], nx, ny, nz);
+    double sum = 0.0;
+    const size_t at = (size_t)i * (size_t)samples;
+    for (int32_t s = 0; s < samples; ++s) sum = sum + (occluded[at + s] ? 0.0 : w[at + s]);
+    const double c = (double)photons_equiv * (0.5 * nn);
+    const double m = sum / (double)samples;
+    expected[t] = nn == 0.0 ? 0.0 : c * m;
+    double q = 0.0;
+    if (MODE == 0) {
+        for (int32_t s = 0; s < samples; ++s) {
+            const double d = (occluded[at + s] ? 0.0 : w[at + s]) - m;
+            q = q + d * d;
+        }
+    } else {
+        double prev = occluded[at] ? 0.0 : w[at];
+        for (int32_t s = 1; s < samples; ++s) {
+            const double x = occluded[at + s] ? 0.0 : w[at + s];
+            const double d = x - prev;
+            q = q + d * d;
+            prev = x;
+        }
+    }
+    const double SS = (double)samples * (double)(samples - 1);
+    const double v = MODE == 0 ? q / SS : q / (2.0 * SS);
+    variance[t] = nn == 0.0 ? 0.0 : (c * c) * v;
+}
+
+void launch_gather_reduce_var(const float4* gtris, const double* w, const uint8_t* occluded, double* expected, double* variance,
+                              int32_t first_tri, int32_t tri_count, int32_t samples, int32_t photons_equiv, int32_t mode,
+                              hipStream_t s)
+{
+    if (tri_count <= 0) return;
+    const dim3 grid((unsigned)((tri_count + 255) / 256));
+    if (mode == 1) hipLaunchKernelGGL((k_gather_reduce_var<1>), grid, dim3(256), 0, s, gtris, w, occluded, expected, variance,
+                                      first_tri, tri_count, samples, photons_equiv);
+    else hipLaunchKernelGGL((k_gather_reduce_var<0>), grid, dim3(256), 0, s, gtris, w, occluded, expected, variance, first_tri,
+                            tri_count, samples, photons_equiv);
 }
 
 __global__ __launch_bounds__(256) void k_accumulate_expected(double* __restrict__ photon_map, double* __restrict__ max_map,

@@ -20,6 +20,10 @@
 // expected counts of the direct gather (uvrt_plan_begin_expected, uvrt_plan_capture_expected).  The row kernels and the
 // host loop take the element type ET as a template argument and do the same arithmetic on (double)E[p][t]; only the row
 // sums that class a triangle differ: exact uint64 for counts, f64 in ascending p for expected values.
+//
+// An expected plan may carry V, the variance of every element of E (uvrt_plan_begin_expected_variance: the capture adds the
+// gather's variance plane beside its expected plane).  uvrt_plan_lower_confidence then replaces E by max(0, E - z sqrt(V)),
+// once, and everything above plans for that bound: one solver, no solver kernel knows about V.
 #include "uvrt_ctx.h"
 #include "uvrt_plan_lp.h"
 
@@ -67,6 +71,17 @@ __global__ __launch_bounds__(256) void k_plan_capture_expected(double* __restric
     const double sum = X[t] + expected[t];
     if (!(sum >= 0.0) || sum == std::numeric_limits<double>::infinity()) atomicOr(bad, 1u);
     X[t] = sum;
+}
+
+// uvrt_plan_lower_confidence: X = max(0, X - z * sqrt(V)) over all P x T elements, one rounding per operator (this file is
+// built without contraction).  z = 0 leaves X as it is: X - 0 * sqrt(V) = X for the finite, non-negative sums a plan holds.
+__global__ __launch_bounds__(256) void k_plan_lower_confidence(double* __restrict__ X, const double* __restrict__ V, int64_t n,
+                                                              double z)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double lo = X[i] - z * sqrt(V[i]);
+    X[i] = lo > 0.0 ? lo : 0.0;
 }
 
 // the type a row of E is summed in when k_plan_classify classes it
@@ -297,7 +312,10 @@ struct PlanState {
     int32_t P = 0;
     bool expected = false;               // E holds f64 expected counts (uvrt_plan_begin_expected), not uint32 photon counts
     DevBuf E;
-    std::vector<uint64_t> rays;          // rays of this context's launches captured per position (uint32 overflow guard)
+    bool with_variance = false;          // an expected plan with V, the variance of every element of E, beside it (uvrt_plan_begin_expected_variance)
+    DevBuf V;                            // f64[P][T]
+    bool lowered = false;                // uvrt_plan_lower_confidence has turned E into its lower confidence bound: no more captures
+    std::vector<uint64_t> rays;         // rays of this context's launches captured per position (uint32 overflow guard)
     int64_t captures = 0;
     bool solved = false;
     float s = 0, Nf = 0;                 // of the last solve (uvrt_plan_model_dose)
@@ -415,7 +433,7 @@ int plan_solve(uvrt_ctx* c, const char* who, const uvrt_plan_params* prm, const 
 }
 
 // uvrt_plan_begin (uint32 counts) and uvrt_plan_begin_expected (f64 expected counts)
-int plan_begin(uvrt_ctx* c, const char* who, int32_t positions, bool expected)
+int plan_begin(uvrt_ctx* c, const char* who, int32_t positions, bool expected, bool with_variance = false)
 {
     if (!c || !c->have_scene) return fail(UVRT_ERR_INVALID, "%s: null context or no scene", who);
     if (positions < 1 || positions > PLAN_MAX_P)
@@ -428,7 +446,10 @@ int plan_begin(uvrt_ctx* c, const char* who, int32_t positions, bool expected)
     c->plan->P = positions;
     c->plan->expected = expected;
     c->plan->rays.assign(positions, 0);
+    c->plan->with_variance = with_variance;
     if (int rc = c->plan->E.ensure((size_t)positions * (size_t)c->T * (expected ? 8 : 4), true, c->stream)) { plan_drop(c); return rc; }
+    if (with_variance)
+        if (int rc = c->plan->V.ensure((size_t)positions * (size_t)c->T * 8, true, c->stream)) { plan_drop(c); return rc; }
     if (int rc = c->plan->overflow.ensure(4, true, c->stream)) { plan_drop(c); return rc; }
     return UVRT_OK;
 }
@@ -453,6 +474,11 @@ float uvrt_plan_round_trip_up(float v)
 int uvrt_plan_begin(uvrt_ctx* c, int32_t positions) { return plan_begin(c, "uvrt_plan_begin", positions, false); }
 
 int uvrt_plan_begin_expected(uvrt_ctx* c, int32_t positions) { return plan_begin(c, "uvrt_plan_begin_expected", positions, true); }
+
+int uvrt_plan_begin_expected_variance(uvrt_ctx* c, int32_t positions)
+{
+    return plan_begin(c, "uvrt_plan_begin_expected_variance", positions, true, true);
+}
 
 int uvrt_plan_end(uvrt_ctx* c)
 {
@@ -502,13 +528,23 @@ int uvrt_plan_capture_expected(uvrt_ctx* c, int32_t position)
     PlanState& S = *c->plan;
     if (position < 0 || position >= S.P)
         return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_expected: position %d outside [0,%d)", position, S.P);
+    if (S.lowered)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_capture_expected: the plan holds its lower confidence bound (uvrt_plan_lower_confidence): no more captures");
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     if (int rc = ensure_expected(c)) return rc;
+    if (S.with_variance)
+        if (int rc = ensure_variance(c)) return rc;
     hipLaunchKernelGGL(k_plan_capture_expected, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream,
                        S.E.as<double>() + (size_t)position * c->T, (const double*)c->expected.as<double>(), c->T,
                        S.overflow.as<uint32_t>());
     HIP_TRY(hipGetLastError());
+    if (S.with_variance) {      // V[position][t] += variance[t]: the same sum, the same flag
+        hipLaunchKernelGGL(k_plan_capture_expected, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream,
+                           S.V.as<double>() + (size_t)position * c->T, (const double*)c->variance.as<double>(), c->T,
+                           S.overflow.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+    }
     ++S.captures;
     return UVRT_OK;
 }
@@ -568,6 +604,35 @@ int uvrt_plan_read_exposure_expected(uvrt_ctx* c, int32_t position, double* out,
         return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: position %d outside [0,%d)", position, c->plan->P);
     if (!range_ok(out, first, count, c->T)) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_expected: bad range");
     return range_copy(c, c->plan->E.as<double>() + (size_t)position * c->T, 8, out, first, count, hipMemcpyDeviceToHost);
+}
+
+int uvrt_plan_read_exposure_variance(uvrt_ctx* c, int32_t position, double* out, int32_t first, int32_t count)
+{
+    if (!c || !c->plan || !c->plan->with_variance)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_variance: no plan with a variance (uvrt_plan_begin_expected_variance)");
+    if (position < 0 || position >= c->plan->P)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_variance: position %d outside [0,%d)", position, c->plan->P);
+    if (!range_ok(out, first, count, c->T)) return fail(UVRT_ERR_INVALID, "uvrt_plan_read_exposure_variance: bad range");
+    return range_copy(c, c->plan->V.as<double>() + (size_t)position * c->T, 8, out, first, count, hipMemcpyDeviceToHost);
+}
+
+int uvrt_plan_lower_confidence(uvrt_ctx* c, double z)
+{
+    if (!c || !c->plan || !c->plan->with_variance)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_lower_confidence: no plan with a variance (uvrt_plan_begin_expected_variance)");
+    PlanState& S = *c->plan;
+    if (S.lowered) return fail(UVRT_ERR_INVALID, "uvrt_plan_lower_confidence: the plan already holds its lower confidence bound");
+    if (!std::isfinite(z) || !(z >= 0.0)) return fail(UVRT_ERR_INVALID, "uvrt_plan_lower_confidence: z must be finite and >= 0");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    const int64_t n = (int64_t)S.P * c->T;
+    if (z != 0.0) {             // (z = 0: X - 0 * sqrt(V) is X; not launched, so that every bit stays whatever X holds)
+        hipLaunchKernelGGL(k_plan_lower_confidence, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, S.E.as<double>(),
+                           (const double*)S.V.as<double>(), n, z);
+        HIP_TRY(hipGetLastError());
+    }
+    S.lowered = true;
+    return UVRT_OK;
 }
 
 // a range of the last solve's row classes

@@ -69,6 +69,8 @@ SYMBOLS = [
                                         C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_gather_sampling", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
                                                  C.c_int, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_confidence", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                                   C.c_int, C.c_double, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -244,7 +246,7 @@ class RayTracer:
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
 
     def PlanDurations(self, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None,
-                      gather_samples=0, gather_sampling=0):
+                      gather_samples=0, gather_sampling=0, gather_confidence=0.0):
         """RayTracer::PlanDurations: one batched computation over the current positions from the current SEED with the
         exposure captured, then the least durations that bring every required triangle to min_dose (default: the
         route's minDosage).  They are written into the positions; returns (durations float32[P], report dict with
@@ -254,10 +256,24 @@ class RayTracer:
         direct gather instead (PlanOptions::gatherSamples): the launches of a gatherSamples = S run, launch by launch, into
         an exposure matrix of f64 expected counts (ctx.plan_read_exposure_expected), so triangles no photon reaches are
         planned for too; the plan is as good as the estimator (DESIGN.md 12).  gather_sampling (PlanOptions::gatherSampling)
-        is those launches' sampling mode: 0 independent, 1 stratified; it needs gather_samples > 0."""
+        is those launches' sampling mode: 0 independent, 1 stratified; it needs gather_samples > 0.
+        gather_confidence = z > 0 (PlanOptions::gatherConfidence) plans for the estimate's lower confidence bound, expected -
+        z standard errors element by element; it needs gather_samples >= 2 and is meant for 16 and more.
+        0 is the plan without it, bit for bit."""
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
+        z = float(gather_confidence)
+        if not (z >= 0.0) or z == float("inf"):
+            raise ValueError("gather_confidence must be finite and >= 0")
+        if z > 0.0 and int(gather_samples) < 2:
+            raise ValueError("gather_confidence needs gather_samples >= 2")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if z > 0.0:
+            self._L.uvrt_host_rt_plan_gather_confidence(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                                        float(margin), float(rel_gap), int(max_iterations), _addr(keep),
+                                                        int(gather_samples), int(gather_sampling), z, C.byref(rep),
+                                                        C.byref(seed))
+            return _plan_result(self, rep, seed)
         if gather_samples:
             self._L.uvrt_host_rt_plan_gather_sampling(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
                                                       float(margin), float(rel_gap), int(max_iterations), _addr(keep),

@@ -27,12 +27,14 @@ std::vector<LightPos> positions(const float* xyd, int n)
 std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>((RayTracer**)rs, (RayTracer**)rs + n); }
 
 RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                    const unsigned char* mask, int gather_samples, int gather_sampling = 0)
+                                    const unsigned char* mask, int gather_samples, int gather_sampling = 0,
+                                    double gather_confidence = 0.0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
     o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
     o.gatherSampling = gather_sampling;
+    o.gatherConfidence = gather_confidence;
     return o;
 }
 
@@ -157,6 +159,14 @@ void uvrt_host_rt_plan_gather_sampling(void* r, float min_dose, int min_photons,
 {
     *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
                                                        gather_sampling), seed);
+}
+// the same with PlanOptions::gatherConfidence beside them (include/uvrt.h uvrt_plan_lower_confidence)
+void uvrt_host_rt_plan_gather_confidence(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                                         const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
+                                         uvrt_plan_report* rep, unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence), seed);
 }
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)

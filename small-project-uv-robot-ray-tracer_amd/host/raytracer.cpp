@@ -355,10 +355,19 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 }
 
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
-void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling)
+// confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
+void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
-    check(uvrt_plan_begin_expected(ctx, (int)list.size()), "plan_begin_expected");
+    const bool bound = confidence > 0.0;
+    int32_t variance0 = 0;
+    if (bound) {
+        check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
+        check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
+        check(uvrt_plan_begin_expected_variance(ctx, (int)list.size()), "plan_begin_expected_variance");
+    } else {
+        check(uvrt_plan_begin_expected(ctx, (int)list.size()), "plan_begin_expected");
+    }
     ClearBuffers(true);                                      // ResetDosageMap without the route save
     currIterations = 0;
     launchIndex = 0;
@@ -367,6 +376,10 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
         for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column);
         Shade();
         ++currIterations;
+    }
+    if (bound) {
+        check(uvrt_plan_lower_confidence(ctx, confidence), "plan_lower_confidence");
+        check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
     }
 }
 
@@ -423,11 +436,15 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     if ((int)list.size() > L && L > 128) fatal("PlanDurations: a driving plan takes at most 128 positions (2L - 1 <= 256 columns)");
     if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
         fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
+    if (opt.gatherConfidence != 0.0) {
+        if (!(opt.gatherConfidence > 0.0) || !std::isfinite(opt.gatherConfidence)) fatal("PlanDurations: gatherConfidence must be finite and >= 0");
+        if (opt.gatherSamples < 2) fatal("PlanDurations: gatherConfidence needs a plan from the direct gather with gatherSamples >= 2");
+    }
     uint32_t seed0 = 0;
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
-        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling);
+        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }

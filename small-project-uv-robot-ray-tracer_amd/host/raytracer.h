@@ -122,6 +122,13 @@ public:
         // the gather sampling mode of those launches (uvrt_set_gather_sampling; read only with gatherSamples > 0).  Like S it
         // is the plan's own: RayTracer::gatherSampling is not touched.
         int gatherSampling = 0;
+        // z > 0: plan for the lower confidence bound of the gather's estimate (include/uvrt.h "planning for a lower confidence
+        // bound"): the same launches with the variance plane on, an exposure matrix with its variance, and
+        // uvrt_plan_lower_confidence(z) before the solve -- every required triangle reaches the minimum for expected - z
+        // standard errors, element by element.  The context's variance state is put back afterwards; no public field is
+        // touched.  0 (default): the plan above, bit for bit.  Not 0 with gatherSamples < 2, negative or not finite: fatal.
+        // Meant for gatherSamples >= 16: at 4 samples about half the bounds are 0.
+        double gatherConfidence = 0.0;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -185,7 +192,7 @@ private:
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
-    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling);
+    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

@@ -54,6 +54,13 @@
 //                                           stratified puts sample s into stratum s of the rod and the sweep coordinate on a
 //                                           rotated golden-ratio sequence -- the same shadow rays, at a stop an estimate about as
 //                                           tight as four times the samples.  Needs --gather S or --plan-gather S
+//            [--plan-confidence Z]          with --plan-gather S, S >= 2: plan for the lower confidence bound of the gather's
+//                                           estimate, expected - Z standard errors element by element (PlanOptions::
+//                                           gatherConfidence): every required triangle reaches the minimum with
+//                                           that confidence in the estimator, not just for the estimate.  Z finite and >= 0
+//                                           (0: the plan without it); meant for S >= 16 -- at S = 4 about half the bounds are 0.
+//                                           --plan-verify recomputes with the plain gather of the same seeds, whose estimate is
+//                                           >= the bound element by element, so the plan holds there
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -117,7 +124,7 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 }
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
-             const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling)
+             const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -125,6 +132,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.minPhotons = minPhotons;
     opt.gatherSamples = planGather;
     opt.gatherSampling = planGather > 0 ? gatherSampling : 0;
+    opt.gatherConfidence = planGather > 0 ? planConfidence : 0.0;
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
     if (planGather > 0) {
@@ -132,6 +140,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
         rt.gatherSampling = opt.gatherSampling;
         printf("plan: exposure from the direct gather, %d samples per triangle and launch\n", planGather);
         if (opt.gatherSampling == UVRT_GATHER_STRATIFIED) printf("plan: stratified gather sampling\n");
+        if (opt.gatherConfidence > 0.0) printf("plan: lower confidence bound, z = %.9g\n", opt.gatherConfidence);
     }
     const float m = minDose >= 0.0f ? minDose : rt.minDosage;
     printf("plan: %d positions, %d used, total duration %.9g (lower bound %.9g, gap %.3g), %s after %d iterations\n",
@@ -199,6 +208,7 @@ int main(int argc, char** argv)
     float planMin = -1.0f, gridInset = 0.5f, driveSpeed = -1.0f, planDrive = -1.0f;
     int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1, planGather = 0, gatherSampling = -1;
     uint32_t holdoutSeed = 0;
+    double planConfidence = -1.0;           // < 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
     ViewMode view = dosage;
@@ -243,6 +253,16 @@ int main(int argc, char** argv)
             else if (!strcmp(v, "stratified")) gatherSampling = UVRT_GATHER_STRATIFIED;
             else { fprintf(stderr, "--gather-sampling independent|stratified (with --gather S or --plan-gather S)\n"); return 2; }
         }
+        else if (!strcmp(argv[i], "--plan-confidence")) {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            planConfidence = strtod(v, &end);
+            if (end == v || *end != 0 || !std::isfinite(planConfidence) || !(planConfidence >= 0.0)) {
+                fprintf(stderr, "--plan-confidence Z: Z must be a finite number >= 0 (with --plan-gather S, S >= 2)\n");
+                return 2;
+            }
+        }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -251,6 +271,7 @@ int main(int argc, char** argv)
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
     if (gatherSampling >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-sampling needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
+    if (planConfidence >= 0.0 && planGather < 2) { fprintf(stderr, "--plan-confidence needs --plan-gather S with S >= 2\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
@@ -306,7 +327,7 @@ int main(int argc, char** argv)
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
-                                gatherSampling < 0 ? 0 : gatherSampling);
+                                gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence);
         save_route(rayTracer, saveRoute);
         return rc;
     }

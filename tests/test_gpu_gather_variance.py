@@ -1,0 +1,481 @@
+"""GPU: the gather's variance plane (uvrt_set_gather_variance, k_gather_reduce_var<MODE> of csrc/uvrt_occlude.hip) and planning
+for a lower confidence bound (uvrt_plan_begin_expected_variance, uvrt_plan_lower_confidence, PlanOptions::gatherConfidence,
+uvrt_cli --plan-confidence) against their restatement (tests/gather_variance_restate.py): every bit of `variance` and
+`expected` in both sampling modes, whatever the capacity and the split into ranges; the state off left as it was; the plan's X
+and V as the f64 sums of the restated launches and the bound bit for bit; the refusals; a plan for the bound through host.py
+and through uvrt_cli."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import gather_restate as gr
+import gather_stratified_restate as gs
+import gather_variance_restate as gv
+from conftest import GLB, GOLDEN, ROOT, ROUTE
+
+pytestmark = pytest.mark.gpu
+
+CLI = os.path.join(ROOT, "small-project-uv-robot-ray-tracer_amd", "uvrt_cli")
+S = 4
+N = 1 << 20
+SEED = 7
+MODES = (("independent", gv.INDEPENDENT), ("stratified", gv.STRATIFIED))
+f32 = np.float32
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def same(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def new_ctx(pkg, oscene, cap, mode=0, variance=1):
+    c = pkg.capi.Ctx(0)
+    c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+    c.resize_rays(cap)
+    c.set_gather_sampling(mode)
+    c.set_gather_variance(variance)
+    return c
+
+
+@pytest.fixture(scope="module")
+def places(orc, oscene, oroute):
+    comp = orc.Computation(oscene, oroute["lamps"], N, oroute["lightHeight"], oroute["lightLength"], oroute["lightIntensity"])
+    return [comp.lamp_world_pos(l) for l in oroute["lamps"][:3]]
+
+
+@pytest.fixture(scope="module")
+def restated(orc, oscene, oroute, places):
+    """(tag, mode name) -> (from, to, flavour, mode, expected, variance) of the whole room at S = 4"""
+    out = {}
+    for tag, frm, to, fl in (("stop", places[0], places[0], 0), ("segment", places[0], places[1], 0), ("stop fl1", places[0], places[0], 1)):
+        for name, mode in MODES:
+            e, v, _ = gv.gather(orc, oscene, frm, to, oroute["lightLength"], S, SEED, N, mode, flavour=fl)
+            e.setflags(write=False)
+            v.setflags(write=False)
+            out[(tag, name)] = (frm, to, fl, mode, e, v)
+    return out
+
+
+# ---------------------------------------------------------------- variance bits
+def test_variance_equals_the_restatement(pkg, orc, oscene, oroute, restated):
+    """Every bit of `variance` and `expected` over the whole room at S = 4: stop and segment in flavour 0, the stop in flavour
+    1, both sampling modes; the same bits from a capacity that gives several chunks with a ragged last one, and from two
+    triangle ranges; `expected` is what the call writes with the state off."""
+    T, length = oscene.T, oroute["lightLength"]
+    for (tag, name), (frm, to, fl, mode, want_e, want_v) in restated.items():
+        what = "%s, %s" % (tag, name)
+        plain = (gs.gather if mode else gr.gather)(orc, oscene, frm, to, length, S, SEED, N, flavour=fl)[0]
+        assert same(plain, want_e), what
+        print("%s: %d triangles with an estimate, %d with a variance, median sigma / expected %.3f" % (
+            what, int((want_e > 0).sum()), int((want_v > 0).sum()), float(np.median(np.sqrt(want_v[want_e > 0]) / want_e[want_e > 0]))))
+        assert np.isfinite(want_v).all() and (want_v >= 0).all() and (want_v > 0).sum() > 0.2 * T
+        assert not (want_v[want_e == 0] > 0).any()
+        c = new_ctx(pkg, oscene, T * S, mode)
+        c.set_flavour(fl)
+        c.gather_direct(frm, to, length, S, SEED, N)
+        got_e, got_v = c.read_expected(), c.read_variance()
+        assert same(got_e, want_e), "%s: %d expected entries differ" % (what, int((got_e != want_e).sum()))
+        assert same(got_v, want_v), "%s: %d variance entries differ" % (what, int((got_v != want_v).sum()))
+        c.close()
+        # several chunks, the last one ragged
+        c = new_ctx(pkg, oscene, 1000 * S + 3, mode)
+        c.set_flavour(fl)
+        c.gather_direct(frm, to, length, S, SEED, N)
+        assert same(c.read_expected(), want_e) and same(c.read_variance(), want_v), what + ", capacity 1000 S + 3"
+        # two ranges (the second in chunks again); uvrt_set_scene zeroes both planes and keeps the state
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        assert not c.read_expected().any() and not c.read_variance().any() and c.get_gather_variance() == 1
+        c.gather_direct(frm, to, length, S, SEED, N, 0, 777)
+        part = c.read_variance()
+        assert same(part[:777], want_v[:777]) and not part[777:].any()
+        c.gather_direct(frm, to, length, S, SEED, N, 777, T - 777)
+        assert same(c.read_expected(), want_e) and same(c.read_variance(), want_v), what + ", two ranges"
+        c.sync()
+        c.close()
+    # the two rules differ, on samples that differ
+    assert not same(restated[("stop", "independent")][5], restated[("stop", "stratified")][5])
+
+
+@pytest.mark.parametrize("samples,first,count", [(2, 100, 2000), (3, 100, 2000), (5, 100, 2000), (16, 0, 1000)])
+def test_sample_counts(pkg, orc, oscene, oroute, places, samples, first, count):
+    """S = 2 (the fewest), 3 and 5 (no powers of two: m = sum / S and the division by S (S - 1) round) and 16 on a range of
+    triangles, at a stop and on a segment, both modes"""
+    length = oroute["lightLength"]
+    c = new_ctx(pkg, oscene, count * samples)
+    for tag, frm, to in (("stop", places[0], places[0]), ("segment", places[0], places[1])):
+        for name, mode in MODES:
+            want_e, want_v, _ = gv.gather(orc, oscene, frm, to, length, samples, SEED, N, mode, first=first, count=count)
+            assert (want_v > 0).sum() > 0.1 * count
+            c.set_gather_sampling(mode)
+            c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+            c.gather_direct(frm, to, length, samples, SEED, N, first, count)
+            got_e, got_v = c.read_expected(), c.read_variance()
+            assert same(got_e[first:first + count], want_e), (tag, name)
+            assert same(got_v[first:first + count], want_v), "%s %s: %d entries differ" % (
+                tag, name, int((got_v[first:first + count] != want_v).sum()))
+            assert not got_v[:first].any() and not got_v[first + count:].any()
+    c.close()
+
+
+def test_one_sample_is_refused(pkg, oscene, oroute, places):
+    """S = 1 with the state on: UVRT_ERR_INVALID, both planes as they were; with the state off the call is served"""
+    T, length = oscene.T, oroute["lightLength"]
+    c = new_ctx(pkg, oscene, T * S)
+    e0, v0 = np.linspace(1.0, 2.0, T), np.linspace(3.0, 4.0, T)
+    c.write_expected(e0)
+    c.write_variance(v0)
+    for mode in (gv.INDEPENDENT, gv.STRATIFIED):
+        c.set_gather_sampling(mode)
+        with pytest.raises(pkg.capi.UvrtError, match="error -1.*samples >= 2"):
+            c.gather_direct(places[0], places[0], length, 1, SEED, N)
+        assert same(c.read_expected(), e0) and same(c.read_variance(), v0)
+    c.set_gather_variance(0)
+    c.gather_direct(places[0], places[0], length, 1, SEED, N)
+    assert not same(c.read_expected(), e0) and same(c.read_variance(), v0)
+    c.close()
+
+
+# ---------------------------------------------------------------- state and neighbours
+def test_the_state_off_is_untouched(pkg, orc, oscene, oroute, places, restated):
+    """A context that never hears of the state, and one set to 1 and back to 0, gather what they always did and leave the
+    variance plane alone; the state is the context's: default 0, it survives uvrt_set_scene, another value is refused and
+    changes nothing; SEED and tempPhotonMap are not the gather's business with the variance on either."""
+    T, length = oscene.T, oroute["lightLength"]
+    for name, mode in MODES:
+        frm, to, _, _, want_e, want_v = restated[("stop", name)]
+        c = pkg.capi.Ctx(0)
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        c.resize_rays(T * S)
+        c.set_gather_sampling(mode)
+        assert c.get_gather_variance() == 0
+        c.gather_direct(frm, to, length, S, SEED, N)
+        assert same(c.read_expected(), want_e)
+        sentinel = np.linspace(5.0, 6.0, T)
+        c.write_variance(sentinel)
+        assert same(c.read_variance(), sentinel)
+        part = c.read_variance(10, 5)
+        assert same(part, sentinel[10:15])
+        c.set_gather_variance(1)
+        c.set_gather_variance(0)
+        c.write_expected(np.zeros(T))
+        c.gather_direct(frm, to, length, S, SEED, N)
+        assert same(c.read_expected(), want_e) and same(c.read_variance(), sentinel), name
+        # refusals: the state stays
+        c.set_gather_variance(1)
+        for bad in (2, -1, 1 << 20):
+            with pytest.raises(pkg.capi.UvrtError, match="uvrt_set_gather_variance"):
+                c.set_gather_variance(bad)
+            assert c.get_gather_variance() == 1
+        L = pkg.capi.lib()
+        assert L.uvrt_get_gather_variance(c._h, None) == -1
+        assert L.uvrt_read_variance(c._h, None, 0, 4) == -1 and L.uvrt_write_variance(c._h, None, 0, 4) == -1
+        buf = np.zeros(4)
+        for call in (lambda: c.read_variance(T - 1, 2), lambda: c.read_variance(-1, 2), lambda: c.write_variance(buf, T - 3)):
+            with pytest.raises(pkg.capi.UvrtError, match="error -1"):
+                call()
+        assert same(c.read_variance(), sentinel)
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        assert c.get_gather_variance() == 1 and not c.read_variance().any()
+        c.resize_rays(T * S)
+        # photons around a gather with the variance on: counts and SEED as without it
+        n = 1 << 16
+        rays, seed1 = orc.generate(0, n, places[2], length, 0)
+        counts = np.zeros(T, dtype=np.int32)
+        orc.extend(counts, oscene.tris, rays, oscene.nodes, oscene.triIdx)
+        c.reset(True)
+        c.seed = 0
+        c.generate(places[2], length, 0, n)
+        c.extend(n)
+        c.gather_direct(frm, to, length, S, SEED, N)
+        assert np.array_equal(c.read_counts(), counts) and c.seed == seed1
+        assert same(c.read_expected(), want_e) and same(c.read_variance(), want_v)
+        # uvrt_device_ptr(7): the plane
+        ptr, nbytes = c.device_ptr(7)
+        ptr6, _ = c.device_ptr(6)
+        assert ptr != 0 and ptr != ptr6 and nbytes == T * 8
+        c.copy_device(7, ptr6, 1)                  # expected -> variance on the device: the pointer is the plane's
+        assert same(c.read_variance(), want_e)
+        c.sync()
+        c.close()
+
+
+def test_accumulate_expected_zeroes_both_planes(pkg, orc, oscene, oroute, restated):
+    """uvrt_accumulate_expected with the variance on: both planes zeroed, the maps, the dose and the colours as without it"""
+    T, length = oscene.T, oroute["lightLength"]
+    scaled = f32(f32(oroute["lightIntensity"]) * f32(0.1))
+    for name, mode in MODES:
+        pm, mx = np.zeros(T), np.zeros(T)
+        c, plain = new_ctx(pkg, oscene, T * S, mode), new_ctx(pkg, oscene, T * S, mode, variance=0)
+        c.reset(True)
+        plain.reset(True)
+        for tag, step in (("stop", 60.0), ("segment", 7.25)):
+            frm, to, _, _, want_e, want_v = restated[(tag, name)]
+            for x in (c, plain):
+                x.gather_direct(frm, to, length, S, SEED, N)
+            assert same(c.read_variance(), want_v)
+            for x in (c, plain):
+                x.accumulate_expected(step)
+                x.shade(0, N, scaled, oroute["minDosage"], 0)
+            gr.accumulate_expected(pm, mx, want_e, step)
+            assert not c.read_expected().any() and not c.read_variance().any()
+            assert same(c.read_photon_map(0), pm) and same(c.read_photon_map(1), mx), (tag, name)
+            assert same(c.read_photon_map(0), plain.read_photon_map(0)) and same(c.read_photon_map(1), plain.read_photon_map(1))
+            assert same(c.read_dosage(), plain.read_dosage()) and same(c.read_color(), plain.read_color())
+            assert same(c.read_dosage(), orc.compute_dosage(pm, oscene.tris, N, scaled)), (tag, name)
+        # a caller's own variance goes the same way, over the accumulate's range only
+        c.write_variance(np.full(T, 9.0))
+        c.accumulate_expected(1.0, 100)
+        v = c.read_variance()
+        assert not v[:100].any() and np.all(v[100:] == 9.0)
+        c.close()
+        plain.close()
+
+
+# ---------------------------------------------------------------- the plan: X, V and the bound
+PPL = 1 << 18
+ITER = 2
+
+
+@pytest.fixture(scope="module")
+def launches(orc, oscene, oroute):
+    """mode name -> the 3 * ITER stops of a gatherSamples = S run over positions 0-2 (launch k: seed k, position k % 3) as
+    (expected, variance), and the world positions"""
+    comp = orc.Computation(oscene, oroute["lamps"][:3], 3 * PPL, oroute["lightHeight"], oroute["lightLength"], oroute["lightIntensity"])
+    assert comp.photonsPerLight == PPL
+    world = [comp.lamp_world_pos(l) for l in oroute["lamps"][:3]]
+    out = {"world": world}
+    for name, mode in MODES:
+        out[name] = [gv.gather(orc, oscene, world[k % 3], world[k % 3], comp.lightLength, S, k, PPL, mode)[:2] for k in range(3 * ITER)]
+    return out
+
+
+def _rows(launches, name, T):
+    """X and V of the plan: per position the f64 sums of the launches in launch order"""
+    X, V = np.zeros((3, T)), np.zeros((3, T))
+    for p in range(3):
+        for it in range(ITER):
+            e, v = launches[name][3 * it + p]
+            X[p] = X[p] + e
+            V[p] = V[p] + v
+    return X, V
+
+
+def _capture_all(c, launches, length, P=3):
+    c.plan_begin_expected_variance(P)
+    for k in range(3 * ITER):
+        w = launches["world"][k % 3]
+        c.gather_direct(w, w, length, S, k, PPL)
+        c.plan_capture_expected(k % 3)
+        c.accumulate_expected(1.0)
+
+
+def _read(c, P=3):
+    return (np.stack([c.plan_read_exposure_expected(p) for p in range(P)]), np.stack([c.plan_read_exposure_variance(p) for p in range(P)]))
+
+
+def _rt(iterations):
+    from uvrt_amd import host
+    rt = host.RayTracer(GLB, ROUTE, device=0)
+    rt.set_lamps(rt.lamps()[:3])
+    rt.photonCount = 3 * PPL
+    rt.maxIterations = iterations
+    rt.viewMode = host.VIEW_DOSAGE
+    return rt
+
+
+@pytest.mark.parametrize("name,mode", MODES)
+def test_the_plan_carries_the_variance_and_its_bound(pkg, oscene, oroute, launches, name, mode):
+    """Positions 0-2, S = 4, photons_equiv 2^18, 2 iterations: the rows of X and V are the f64 sums of the restated launches;
+    uvrt_plan_lower_confidence(0) leaves X as it is; z = 2 on a fresh plan is the restatement bit for bit, and so is the
+    matrix PlanDurations(gather_confidence = 2) leaves behind."""
+    T, length = oscene.T, oroute["lightLength"]
+    X, V = _rows(launches, name, T)
+    assert (V > 0).sum() > 0.2 * V.size
+    c = new_ctx(pkg, oscene, T * S, mode)
+    try:
+        c.reset(True)
+        _capture_all(c, launches, length)
+        gx, gv_ = _read(c)
+        assert same(gx, X), "X: %d entries differ" % int((gx != X).sum())
+        assert same(gv_, V), "V: %d entries differ" % int((gv_ != V).sum())
+        c.plan_lower_confidence(0.0)
+        gx, gv_ = _read(c)
+        assert same(gx, X) and same(gv_, V)
+        with pytest.raises(pkg.capi.UvrtError, match="error -1.*uvrt_plan_lower_confidence"):
+            c.plan_lower_confidence(2.0)
+        _capture_all(c, launches, length)                      # a fresh plan: the earlier one is dropped
+        c.plan_lower_confidence(2.0)
+        want = gv.lower_confidence(X, V, 2.0)
+        gx, gv_ = _read(c)
+        assert same(gx, want), "bound: %d entries differ" % int((gx != want).sum())
+        assert same(gv_, V) and (want == 0).sum() > (X == 0).sum() and np.all(want <= X)
+        s = f32(f32(oroute["lightIntensity"]) * f32(0.1))
+        d, rep = c.plan_solve(50.0, s, ITER * PPL, positions=3)
+        assert rep["min_dose_ratio"] >= 1.0 and d.sum() > 0
+    finally:
+        c.close()
+    rt = _rt(ITER)
+    try:
+        d2, rep2 = rt.PlanDurations(min_dose=50.0, gather_samples=S, gather_sampling=mode, gather_confidence=2.0)
+        assert rt.gatherSamples == 0 and rt.gatherSampling == 0 and rt.ctx.get_gather_variance() == 0
+        gx, gv_ = _read(rt.ctx)
+        assert same(gx, want) and same(gv_, V)
+        assert np.array_equal(bits(d2), bits(d)) and rep2["required"] == rep["required"]
+    finally:
+        rt.close()
+
+
+def test_refusals_leave_the_matrices_alone(pkg, oscene):
+    Err = pkg.capi.UvrtError
+    T = oscene.T
+    c = pkg.capi.Ctx(0)
+    L = c._L
+    try:
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        c.resize_rays(4096)
+        c.reset(True)
+        good, var = np.linspace(0.0, 50.0, T), np.linspace(4.0, 0.0, T)
+        c.plan_begin_expected_variance(2)
+        c.write_expected(good)
+        c.write_variance(var)
+        c.plan_capture_expected(0)
+        c.plan_capture_expected(0)
+        c.write_expected(good[::-1])
+        c.plan_capture_expected(1)
+        X = np.stack([good + good, good[::-1]])
+        V = np.stack([var + var, var])
+        gx, gvv = _read(c, 2)
+        assert same(gx, X) and same(gvv, V)
+        assert same(c.read_expected(), good[::-1]) and same(c.read_variance(), var), "capture leaves the planes as they are"
+        # z negative, NaN, inf; positions and ranges; null pointers
+        for z in (-1.0, -0.0 - 1e-300, float("nan"), float("inf"), -float("inf")):
+            with pytest.raises(Err, match="error -1.*uvrt_plan_lower_confidence"):
+                c.plan_lower_confidence(z)
+        for call in (lambda: c.plan_read_exposure_variance(2), lambda: c.plan_read_exposure_variance(-1),
+                     lambda: c.plan_read_exposure_variance(0, T - 1, 2)):
+            with pytest.raises(Err, match="error -1"):
+                call()
+        assert L.uvrt_plan_read_exposure_variance(c._h, 0, None, 0, 4) == -1
+        gx, gvv = _read(c, 2)
+        assert same(gx, X) and same(gvv, V)
+        # the bound, then: no capture, no second bound
+        c.plan_lower_confidence(1.0)
+        want = gv.lower_confidence(X, V, 1.0)
+        for call in (lambda: c.plan_capture_expected(0), lambda: c.plan_lower_confidence(1.0), lambda: c.plan_lower_confidence(0.0)):
+            with pytest.raises(Err, match="error -1"):
+                call()
+        gx, gvv = _read(c, 2)
+        assert same(gx, want) and same(gvv, V) and not same(want, X)
+        d, rep = c.plan_solve(100.0, 45.0, 4096, min_photons=1, positions=2)
+        assert rep["min_dose_ratio"] >= 1.0 and d.sum() > 0
+        model = c.plan_model_dose(d)
+        assert c.plan_read_classes().size == T and c.plan_read_required().sum() == rep["required"] and np.isfinite(model).all()
+        # the wrong kind of plan, and none
+        c.plan_begin_expected(2)
+        c.write_expected(good)
+        c.plan_capture_expected(0)                              # the parent's call: V is not there to add to
+        for call in (lambda: c.plan_lower_confidence(1.0), lambda: c.plan_read_exposure_variance(0)):
+            with pytest.raises(Err, match="error -1.*uvrt_plan_begin_expected_variance"):
+                call()
+        assert same(c.plan_read_exposure_expected(0), good) and same(c.read_variance(), var)
+        c.plan_begin(2)
+        for call in (lambda: c.plan_lower_confidence(1.0), lambda: c.plan_read_exposure_variance(0)):
+            with pytest.raises(Err, match="error -1"):
+                call()
+        c.plan_end()
+        for call in (lambda: c.plan_lower_confidence(1.0), lambda: c.plan_read_exposure_variance(0)):
+            with pytest.raises(Err, match="error -1"):
+                call()
+        for p in (0, 257):
+            with pytest.raises(Err, match="error -1"):
+                c.plan_begin_expected_variance(p)
+        # a variance that is not a number raises the captures' flag: the solve refuses
+        for bad in (float("nan"), float("inf"), -1.0):
+            c.plan_begin_expected_variance(2)
+            v = var.copy()
+            v[T // 3] = bad
+            c.write_expected(good)
+            c.write_variance(v)
+            c.plan_capture_expected(1)
+            c.plan_lower_confidence(1.0)
+            with pytest.raises(Err, match="error -1.*not finite or is negative"):
+                c.plan_solve(100.0, 45.0, 4096, min_photons=1, positions=2)
+        # uvrt_set_scene drops the plan
+        c.plan_begin_expected_variance(2)
+        c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
+        with pytest.raises(Err, match="error -1"):
+            c.plan_read_exposure_variance(0)
+    finally:
+        c.close()
+
+
+# ---------------------------------------------------------------- end to end
+SE = 16
+
+
+def _plan_through_the_new_entry(rt, min_dose, samples, sampling, z):
+    """uvrt_host_rt_plan_gather_confidence itself (host.py takes the earlier entry points at z = 0)"""
+    from uvrt_amd import host
+    rep, seed = host.capi.PlanReport(), C.c_uint()
+    rt._L.uvrt_host_rt_plan_gather_confidence(rt._h, float(min_dose), 16, 1e-6, 1e-3, 200, None, int(samples), int(sampling),
+                                              float(z), C.byref(rep), C.byref(seed))
+    return host._plan_result(rt, rep, seed)
+
+
+def test_a_plan_for_the_bound_through_host_and_cli(pkg, tmp_path):
+    """S = 16 stratified, z = 2, minimum 50: host.py and uvrt_cli plan the same durations; the plan holds for the bound
+    (min_dose_ratio >= 1) and in the CLI's recompute with the plain gather of the same seeds; it is no shorter than the plan
+    at z = 0; and z = 0 through the new entry point is the plan without it, durations and every field of the report."""
+    from uvrt_amd import host
+    rt = _rt(ITER)
+    try:
+        d0, rep0 = rt.PlanDurations(min_dose=50.0, gather_samples=SE, gather_sampling=gs.STRATIFIED)
+        X0 = np.stack([rt.ctx.plan_read_exposure_expected(p) for p in range(3)])
+    finally:
+        rt.close()
+    rt = _rt(ITER)
+    try:
+        dz, repz = _plan_through_the_new_entry(rt, 50.0, SE, gs.STRATIFIED, 0.0)
+        Xz = np.stack([rt.ctx.plan_read_exposure_expected(p) for p in range(3)])
+        with pytest.raises(pkg.capi.UvrtError, match="error -1"):
+            rt.ctx.plan_read_exposure_variance(0)               # z = 0 begins the plan without V
+    finally:
+        rt.close()
+    assert np.array_equal(bits(dz), bits(d0)) and same(Xz, X0)
+    assert set(repz) == set(rep0)
+    for k in rep0:
+        assert repz[k] == rep0[k], (k, repz[k], rep0[k])
+    rt = _rt(ITER)
+    try:
+        d2, rep2 = rt.PlanDurations(min_dose=50.0, gather_samples=SE, gather_sampling=gs.STRATIFIED, gather_confidence=2.0)
+        X2 = np.stack([rt.ctx.plan_read_exposure_expected(p) for p in range(3)])
+        V2 = np.stack([rt.ctx.plan_read_exposure_variance(p) for p in range(3)])
+        assert rt.gatherSamples == 0 and rt.gatherSampling == 0 and rt.ctx.get_gather_variance() == 0
+    finally:
+        rt.close()
+    print("z = 0: total %.6g s, required %d, unresolved %d; z = 2: total %.6g s, required %d, unresolved %d" % (
+        rep0["total_duration"], rep0["required"], rep0["unresolved"], rep2["total_duration"], rep2["required"], rep2["unresolved"]))
+    assert same(X2, gv.lower_confidence(X0, V2, 2.0))
+    assert rep2["min_dose_ratio"] >= 1.0 and rep2["converged"]
+    assert rep2["total_duration"] >= rep0["total_duration"] and d2.sum() > 0
+    shutil.copy(os.path.join(GOLDEN, "lange_route.xml"), tmp_path / "lange_route.xml")
+    out = subprocess.run([CLI, "--room", GLB, "--route-dir", str(tmp_path), "--route", "lange_route", "--lamps", "3", "--photons",
+                          str(3 * PPL), "--iterations", str(ITER), "--plan-gather", str(SE), "--gather-sampling", "stratified",
+                          "--plan-confidence", "2", "--plan", "50", "--plan-verify", "--save-route", "planned"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "plan: lower confidence bound, z = 2\n" in out.stdout and "plan-verify: 0 below minimum" in out.stdout
+    saved = host.RayTracer(init=False)
+    saved.set_route_dir(str(tmp_path) + os.sep)
+    saved.LoadRoute("planned")
+    cli_d = np.array([l[2] for l in saved.lamps()], dtype=np.float32)
+    assert saved.gatherSamples == SE and saved.gatherSampling == gs.STRATIFIED
+    saved.close()
+    assert np.array_equal(bits(cli_d), bits(d2))
