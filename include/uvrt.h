@@ -288,6 +288,29 @@ int uvrt_fold_batch(uvrt_ctx* ctx);
 /* test hook: tempPhotonMap of launch `launch` of the traced batch (folds; after a reduce: the global counts) */
 int uvrt_read_batch_counts(uvrt_ctx* ctx, int32_t launch, int32_t* out, int32_t first, int32_t count);
 
+/* ---- batched tracing: every distinct photon of a lamp is traced once ----
+ * generate.cl:13 seeds work-item gid from an f32 sum, 17 gid + 1 + 13 lx + 7 ly + 11 lz + (SEED >> 15), that takes even values
+ * only above 2^24 and moves by less than 131 072 from launch to launch, so the launches of ONE lamp position draw mostly the
+ * same hash inputs at shifted gids: about half of the photons of 8 launches x 2 M are copies of another one (same ray, same
+ * hit).  A batch therefore traces the stops of a lamp column as dedupe groups -- up to 31 launches with one bit-identical lamp,
+ * in logical order: each distinct ray is traced once and its hit deposited in the plane of every launch that holds it.  The
+ * planes, and everything made of them, are bit for bit what tracing every launch's rays gives.  Traced as they are: a column
+ * of one launch, lamps that differ in y, sweeps, a range that ends past global id 126 322 567, a lamp coordinate of 1e7 and
+ * more, and everything outside a batch (uvrt_extend).  Duplicates are looked for within the call's own global-id range, so
+ * the ranks of a sharded job each dedupe their own range.
+ * uvrt_set_dedupe(ctx, 0) switches it off for later batches; the default is on, or what the environment variable
+ * UVRT_DEDUPE (0 / 1) says when the context is created. */
+int uvrt_set_dedupe(uvrt_ctx* ctx, int32_t on);
+/* test hook: the rays the traversal kernel was given for the stops of the last traced batch (waits for the batch) */
+int uvrt_batch_traced_rays(uvrt_ctx* ctx, int64_t* out);
+/* test hooks, host only.  uvrt_seed_input: what work-item gid of a launch hands to the hash (generate.cl:13; the rules of
+ * uvrt_set_seed_mode).  uvrt_dedupe_plan: the masks of a dedupe group of `count` launches from `lamp` over the global ids
+ * [first_gid, first_gid + n), masks[k * n + i] for launch k, gid first_gid + i: 0 = another occurrence traces this ray, else
+ * bit j = its hit goes to launch j's plane.  UVRT_ERR_INVALID when the launches cannot form a group (above). */
+uint32_t uvrt_seed_input(int64_t gid, const float lamp[3], uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode);
+int uvrt_dedupe_plan(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                     int32_t seed_mode, int64_t first_gid, int64_t n, uint32_t* masks);
+
 /* ---- the one collective of a sharded computation (RCCL over xGMI; librccl is opened on first use) ----
  * One process per GPU: rank 0 calls uvrt_comm_unique_id and hands the 128 bytes to every rank (any
  * out-of-band channel), every rank calls uvrt_comm_init_rank; then per batch uvrt_trace_batch (its own

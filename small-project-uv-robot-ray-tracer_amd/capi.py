@@ -50,6 +50,10 @@ SYMBOLS = [
     ("uvrt_replay_batch", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_fold_batch", C.c_int, [_vp]),
     ("uvrt_read_batch_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_set_dedupe", C.c_int, [_vp, _i32]),
+    ("uvrt_batch_traced_rays", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("uvrt_seed_input", _u32, [_i64, _fp, _u32, _u32, _i32]),
+    ("uvrt_dedupe_plan", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
     ("uvrt_comm_available", C.c_int, []),
     ("uvrt_comm_info", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_comm_unique_id", C.c_int, [_vp]),
@@ -226,6 +230,25 @@ def _ptr(a):
 def seed_next(light_pos, light_length, seed_prev, seed_mode=0):
     return int(lib().uvrt_seed_next_mode(_f3(light_pos), float(np.float32(light_length)), int(seed_prev),
                                          int(seed_mode)))
+
+
+def seed_input(gid, lamp, seed_prev, seed_next_, seed_mode=0):
+    """what work-item `gid` of a launch hands to the hash (generate.cl:13; host only)"""
+    return int(lib().uvrt_seed_input(int(gid), _f3(lamp), int(seed_prev), int(seed_next_), int(seed_mode)))
+
+
+def dedupe_plan(lamp, seed_prev, seed_next_, seed_mode, first_gid, n):
+    """The masks of a dedupe group (include/uvrt.h uvrt_dedupe_plan; host only): uint32[launches][n], 0 = another occurrence
+    traces this ray, else bit j = the hit goes to launch j's plane.  seed_prev / seed_next_: the launches' places in the SEED
+    chain."""
+    sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
+    sn = np.ascontiguousarray(seed_next_, dtype=np.uint32)
+    assert sp.size == sn.size
+    out = np.empty((sp.size, int(n)), dtype=np.uint32)
+    rc = lib().uvrt_dedupe_plan(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n), _ptr(out))
+    if rc != 0:
+        raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
+    return out
 
 
 def seed_next_sweep(frm, light_length, seed_prev):
@@ -461,6 +484,16 @@ class Ctx:
         out = np.empty(count, dtype=np.int32)
         self._ck(self._L.uvrt_read_batch_counts(self._h, int(launch), _ptr(out), first, count))
         return out
+
+    def set_dedupe(self, on):
+        """trace every distinct photon of a lamp once per batch (default on; include/uvrt.h uvrt_set_dedupe)"""
+        self._ck(self._L.uvrt_set_dedupe(self._h, 1 if on else 0))
+
+    def batch_traced_rays(self):
+        """rays the traversal kernel was given for the stops of the last traced batch"""
+        out = _i64()
+        self._ck(self._L.uvrt_batch_traced_rays(self._h, C.byref(out)))
+        return int(out.value)
 
     def comm_init_rank(self, id128, rank, world):
         assert len(id128) == 128

@@ -107,12 +107,13 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     HIP_TRY(hipEventCreateWithFlags(&c->ev_mapfence, hipEventDisableTiming));
     if (const char* e = getenv("UVRT_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL) c->nlanes = v; }
     if (const char* e = getenv("UVRT_PIPELINE")) c->pipeline = atoi(e) != 0;   // developer knob
-    if (const char* e = getenv("UVRT_BATCH_CHUNK_MB")) { const long v = atol(e); if (v > 0) c->batch_chunk_bytes = (size_t)v << 20; }
+    if (const char* e = getenv("UVRT_BATCH_CHUNK_MB")) { const long v = atol(e); if (v > 0) c->batch_chunk_bytes = c->dedupe_chunk_bytes = (size_t)v << 20; }
 #ifdef UVRT_DEV_VARIANTS
     if (const char* e = getenv("UVRT_PROBE_SKIP_GENERATE")) c->probe_skip_generate = atoi(e);
     if (const char* e = getenv("UVRT_NEARFAR_MINMAX")) c->nearfar_minmax = atoi(e) != 0;   // the checker / A-B partner of the sign-ordered block
 #endif
     if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
+    if (const char* e = getenv("UVRT_DEDUPE")) c->dedupe = atoi(e) != 0;                 // uvrt_set_dedupe's default
     if (const char* e = getenv("UVRT_BATCH_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL - 1) c->batch_lanes = v; }
     if (const char* e = getenv("UVRT_COMM_RESERVE_CUS")) { const int v = atoi(e); if (v >= 0 && v <= 64 && v % 8 == 0) c->comm_reserve_knob = v; }
     if (const char* e = getenv("UVRT_HOT_SAMPLE")) { const int v = atoi(e); if (v >= 256 && v <= (1 << 20)) c->hot_sample = v; }
@@ -577,6 +578,13 @@ int uvrt_set_hot_records(uvrt_ctx* c, int32_t mode)
     if (int rc = join_all(c)) return rc;
     c->hot_mode = mode;
     for (Lane& L : c->lanes) { L.recs_tag.valid = false; L.perm = nullptr; }
+    return UVRT_OK;
+}
+
+int uvrt_set_dedupe(uvrt_ctx* c, int32_t on)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "null context");
+    c->dedupe = on != 0;
     return UVRT_OK;
 }
 

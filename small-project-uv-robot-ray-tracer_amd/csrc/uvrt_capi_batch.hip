@@ -89,6 +89,51 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         }
         seed_after = seed;              // committed with the batch: a failed call leaves the SEED chain where it was
     }
+    // The columns in PIECES: a dedupe group each (uvrt_dedupe.h: 2..31 launches of one bit-identical lamp, every distinct ray
+    // traced once), or launches traced as they are -- a column of one, lamps that differ in y, a range or a lamp outside
+    // dedupe_group_ok, uvrt_set_dedupe(0), a kernel variant other than the default's code (the deduped kernel exists for leaf
+    // period 2 with the LDS cache only), the developer build's skip-generate probe.  A longer column is split evenly (33
+    // launches: 17 + 16).
+    struct Piece { int g, k0, kc; bool dd; int64_t chunk_gids; DedupeGroup G; };
+    std::vector<Piece> pieces;
+    size_t dd_chunks = 0, dd_tmp_bytes = 0, dd_block_bytes = 0;
+    bool may_dedupe = c->dedupe && variant_code6(c->variant) == 1;
+#ifdef UVRT_DEV_VARIANTS
+    may_dedupe = may_dedupe && c->probe_skip_generate <= 0;
+#endif
+    for (int g = 0; g < ngroups; ++g) {
+        bool same_lamp = may_dedupe && gsize[g] >= 2;
+        for (int j = 1; same_lamp && j < gsize[g]; ++j) same_lamp = memcmp(&gp.ly[gfirst[g]], &gp.ly[gfirst[g] + j], 4) == 0;
+        const int npieces = same_lamp ? (gsize[g] + DEDUPE_MAX - 1) / DEDUPE_MAX : 1;
+        const int per_piece = (gsize[g] + npieces - 1) / npieces;
+        for (int k0 = 0; k0 < gsize[g]; k0 += per_piece) {
+            Piece pc;
+            memset(&pc, 0, sizeof pc);
+            pc.g = g; pc.k0 = k0; pc.kc = std::min(per_piece, gsize[g] - k0);
+            const int ph0 = gfirst[g] + k0;
+            if (same_lamp && pc.kc >= 2) {
+                DedupeGroup& G = pc.G;
+                G.lx = gp.lx[ph0]; G.ly = gp.ly[ph0]; G.lz = gp.lz[ph0];
+                G.seed_mode = c->seed_mode;
+                G.count = pc.kc;
+                G.first_gid = first_gid; G.n = n;
+                for (int j = 0; j < pc.kc; ++j) { G.seed_prev[j] = gp.seed_prev[ph0 + j]; G.seed_next[j] = gp.seed_next[ph0 + j]; }
+                pc.dd = dedupe_group_ok(G);
+            }
+            if (pc.dd) {
+                // a chunk: a gid range across all the piece's launches, sized by its upper bound (no duplicates)
+                pc.chunk_gids = std::max<int64_t>(64, (int64_t)(c->dedupe_chunk_bytes / ((size_t)pc.kc * 16)) / 64 * 64);
+                // ... and the range dealt evenly over that many chunks (a short last chunk leaves one lane idle at the end)
+                const int64_t nch = (n + pc.chunk_gids - 1) / pc.chunk_gids;
+                pc.chunk_gids = ((n + nch - 1) / nch + 63) / 64 * 64;
+                const int64_t gn = std::min(pc.chunk_gids, n);
+                dd_chunks += (size_t)((n + pc.chunk_gids - 1) / pc.chunk_gids);
+                dd_tmp_bytes = std::max(dd_tmp_bytes, (size_t)pc.kc * (size_t)gn * 4);
+                dd_block_bytes = std::max(dd_block_bytes, (size_t)pc.kc * (size_t)((gn + 255) / 256) * 4);
+            }
+            pieces.push_back(pc);
+        }
+    }
     // The batch goes into the buffer set the previous batch did NOT use: its lanes start at once -- in the drain of
     // the previous batch, while that one is still being folded / reduced / replayed on the context's stream -- and
     // only wait for the set's last replay (free_ev), which is two batches back.  Anything that has to touch memory
@@ -101,9 +146,14 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     const size_t plane_alloc = (size_t)c->replicas * (size_t)c->T;
     // growing a buffer needs the device idle (hipFree / hipMalloc); new per-launch records only need the context's stream
     // ordered after the lanes' earlier work -- no host synchronisation, so a new lamp position costs its kernels only
+    bool dd_scratch_short = false;      // (every lane a chunk may run on: 0 without pipelining, else 1..batch_lanes)
+    for (int l = 0; l <= c->batch_lanes; ++l)
+        dd_scratch_short = dd_scratch_short || c->lanes[l].dd_tmp.bytes < dd_tmp_bytes || c->lanes[l].dd_blocks.bytes < dd_block_bytes;
     const bool need_alloc = S.rays.bytes < (size_t)count * (size_t)n_pad * 16 || S.planes.bytes < (size_t)count * plane_alloc * 4 ||
                             S.folded.bytes < (size_t)count * (size_t)c->T * 4 || (int)c->b_recs.size() < ngroups || !S.free_ev ||
-                            S.oxz.bytes < (size_t)nsweeps * (size_t)n_pad * 8 || (nsweeps > 0 && !c->free_recs_valid);
+                            S.oxz.bytes < (size_t)nsweeps * (size_t)n_pad * 8 || (nsweeps > 0 && !c->free_recs_valid) ||
+                            (dd_chunks > 0 && (S.masks.bytes < (size_t)count * (size_t)n_pad * 4 || S.dd_counts.bytes < dd_chunks * 4 ||
+                                               dd_scratch_short));
     bool recs_stale = false;
     const uint32_t* gperm[MAX_BATCH] = {};
     uint64_t ggen[MAX_BATCH] = {};
@@ -154,6 +204,15 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         c->b_recs_key.resize(c->b_recs.size());
         for (int l = 1; l <= c->batch_lanes; ++l)
             if ((rc = c->lanes[l].ovf.ensure(side_ovf_bytes(c), false, c->stream))) return rc;
+        if (dd_chunks > 0) {      // the deduped chunks' masks and counts, and every lane's scratch between the generate passes
+            if ((rc = S.masks.ensure((size_t)count * (size_t)n_pad * 4, false, c->stream))) return rc;
+            // (not zeroed: a chunk's generate runs on its lane BEFORE the lane waits for this stream, and writes its count)
+            if ((rc = S.dd_counts.ensure(dd_chunks * 4, false, c->stream))) return rc;
+            for (int l = 0; l <= c->batch_lanes; ++l) {
+                if ((rc = c->lanes[l].dd_tmp.ensure(dd_tmp_bytes, false, c->stream))) return rc;
+                if ((rc = c->lanes[l].dd_blocks.ensure(dd_block_bytes, false, c->stream))) return rc;
+            }
+        }
     }
     if (need_alloc || recs_stale) {
         // per-launch records of the lamp columns whose array holds something else
@@ -174,7 +233,9 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     // that writes them and the extend that reads them (a refill that has to go to HBM stalls its wave for
     // microseconds), and the next chunk's generate and first waves run in the drain of the previous one.
     bool lane_waited[uvrt_ctx::MAXL] = {};
-    const int per_chunk = (int)std::max<size_t>(1, c->batch_chunk_bytes / ((size_t)n_pad * 16));
+    // (a plane's offset shares its register with the exact-step flag, PLANE_OFF6: a chunk's planes stay below 2^31 counters)
+    const size_t planes_31 = std::max<size_t>(1, (((size_t)1 << 31) - 1) / plane_ints);
+    const int per_chunk = (int)std::min(planes_31, std::max<size_t>(1, c->batch_chunk_bytes / ((size_t)n_pad * 16)));
     // every error return below leaves the launch-lane rotation as it found it
     struct LaneGuard {
         uvrt_ctx* c; int lane; uint64_t chunks; bool armed;
@@ -205,9 +266,53 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         p.plane_stride = (uint32_t)plane_ints;
     };
     const int per_cu = variant_per_cu(c->variant, c->pipeline ? 7 : 8);
-    for (int g = 0; g < ngroups; ++g) {
-        for (int k0 = 0; k0 < gsize[g]; k0 += per_chunk) {
-            const int kc = std::min(per_chunk, gsize[g] - k0), ph0 = gfirst[g] + k0;
+    int64_t traced = 0;                  // rays handed to k_extend6 with their count known here; the deduped chunks' counts stay on the device
+    size_t dd_used = 0;
+    for (const Piece& pc : pieces) {
+        const int g = pc.g;
+        if (pc.dd) {
+            // a dedupe group: chunks are gid ranges across all its launches; whether an occurrence is an owner is decided over
+            // the whole call's range, a chunk only says where the owner's ray is generated
+            for (int64_t g0 = 0; g0 < n; g0 += pc.chunk_gids) {
+                const int64_t gn = std::min(pc.chunk_gids, n - g0);
+                const int ph0 = gfirst[g] + pc.k0;
+                hipStream_t ls;
+                if (int rcl = next_chunk_lane(&ls)) return rcl;
+                const size_t at = (size_t)ph0 * (size_t)n_pad + (size_t)pc.kc * (size_t)g0;
+                GenDedupeParams dq;
+                memset(&dq, 0, sizeof dq);
+                dq.g = pc.G;
+                dq.rays = S.rays.as<float4>() + at;
+                dq.masks = S.masks.as<uint32_t>() + at;
+                dq.total = S.dd_counts.as<uint32_t>() + dd_used++;
+                dq.tmp = cur_lane(c).dd_tmp.as<uint32_t>();
+                dq.block_counts = cur_lane(c).dd_blocks.as<uint32_t>();
+                dq.g0 = first_gid + g0;
+                dq.gn = gn;
+                dq.light_length = light_length;
+                launch_generate_dedupe(dq, ls);
+                if (int rcl = lane_stream(c, &ls)) return rcl;      // extend: after the fence
+                ExtendParams p;
+                fill_launch(c, p, gx[g], gz[g]);
+                p.rays = dq.rays;
+                p.masks = dq.masks;
+                p.n_dev = dq.total;
+                p.counts = S.planes.as<int32_t>() + (size_t)ph0 * plane_ints;
+                p.count_replicas = R;
+                p.count_stride = c->T;
+                p.n = (int64_t)pc.kc * gn;
+                p.plane_stride = (uint32_t)plane_ints;
+                p.recs = c->b_recs[g].p;
+                p.perm = gperm[g];
+                p.recs_prepared = 1;
+                if (int rct = timed_launch(c, ls, who, "the stops' launch", [&] { return launch_extend6_dedupe(p, variant_code6(c->variant), per_cu, ls); }))
+                    return rct;
+            }
+            continue;
+        }
+        for (int k0 = pc.k0; k0 < pc.k0 + pc.kc; k0 += per_chunk) {
+            const int kc = std::min(per_chunk, pc.k0 + pc.kc - k0), ph0 = gfirst[g] + k0;
+            traced += (int64_t)kc * n;
             hipStream_t ls;
             if (int rcl = next_chunk_lane(&ls)) return rcl;
             GenBatchParams gq;
@@ -241,7 +346,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     }
     // The sweeps: one further group (the free records are the scene's, whatever the segment), in chunks of as many bytes --
     // 16 B of ray plus 8 B of origin per photon -- over the same lanes in the same rotation.
-    const int per_sweep_chunk = (int)std::max<size_t>(1, c->batch_chunk_bytes / ((size_t)n_pad * 24));
+    const int per_sweep_chunk = (int)std::min(planes_31, std::max<size_t>(1, c->batch_chunk_bytes / ((size_t)n_pad * 24)));
     for (int k0 = 0; k0 < nsweeps; k0 += per_sweep_chunk) {
         const int kc = std::min(per_sweep_chunk, nsweeps - k0), ph0 = nstops + k0;
         hipStream_t ls;
@@ -288,6 +393,8 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     c->b_n = n;
     c->b_npad = n_pad;
     c->b_is_folded = false;
+    c->b_traced_known = traced;
+    c->b_traced_chunks = (int32_t)dd_used;
     memcpy(c->b_phys, phys, sizeof(int32_t) * (size_t)count);
     return UVRT_OK;
 }
@@ -312,6 +419,43 @@ int uvrt_trace_batch_launches(uvrt_ctx* c, const uvrt_launch* launches, float li
                               int64_t n)
 {
     return trace_launches(c, launches, light_length, count, first_gid, n, "uvrt_trace_batch_launches");
+}
+
+int uvrt_batch_traced_rays(uvrt_ctx* c, int64_t* out)
+{
+    if (!c || !out) return fail(UVRT_ERR_INVALID, "uvrt_batch_traced_rays: null argument");
+    if (c->b_traced_known < 0) return fail(UVRT_ERR_INVALID, "uvrt_batch_traced_rays: no batch has been traced");
+    int64_t total = c->b_traced_known;
+    if (c->b_traced_chunks > 0) {
+        std::vector<uint32_t> counts((size_t)c->b_traced_chunks);
+        if (int rc = range_copy(c, c->bs[c->b_set].dd_counts.p, 4, counts.data(), 0, c->b_traced_chunks, hipMemcpyDeviceToHost)) return rc;
+        for (uint32_t v : counts) total += v;
+    }
+    *out = total;
+    return UVRT_OK;
+}
+
+uint32_t uvrt_seed_input(int64_t gid, const float lamp[3], uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode)
+{
+    return seed_input(gid, lamp[0], lamp[1], lamp[2], seed_prev, seed_next, seed_mode);
+}
+
+int uvrt_dedupe_plan(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next, int32_t seed_mode,
+                     int64_t first_gid, int64_t n, uint32_t* masks)
+{
+    if (!lamp || !seed_prev || !seed_next || !masks || count < 2 || count > DEDUPE_MAX)
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan: null argument, or count outside [2,%d]", DEDUPE_MAX);
+    DedupeGroup G;
+    memset(&G, 0, sizeof G);
+    G.lx = lamp[0]; G.ly = lamp[1]; G.lz = lamp[2];
+    G.seed_mode = seed_mode;
+    G.count = count;
+    G.first_gid = first_gid; G.n = n;
+    for (int j = 0; j < count; ++j) { G.seed_prev[j] = seed_prev[j]; G.seed_next[j] = seed_next[j]; }
+    if (!dedupe_group_ok(G)) return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan: these launches cannot form a dedupe group");
+    for (int k = 0; k < count; ++k)
+        for (int64_t i = 0; i < n; ++i) masks[(size_t)k * (size_t)n + (size_t)i] = dedupe_mask(G, k, first_gid + i);
+    return UVRT_OK;
 }
 
 int uvrt_fold_batch(uvrt_ctx* c)

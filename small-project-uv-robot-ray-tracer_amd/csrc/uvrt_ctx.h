@@ -92,6 +92,7 @@ struct Lane {
     DevBuf hot_hist, hot_list;       // scratch of the hot-record set-up kernels (uvrt_hotset.hip)
     const uint32_t* perm = nullptr;  // renumbering of the lane's current launch (set by uvrt_generate)
     DevBuf oxz;                      // {orig.x, orig.z} of free rays, [capacity]; allocated by the lane's first free launch
+    DevBuf dd_tmp, dd_blocks;        // a deduped chunk's scratch between the passes of its generate (GenDedupeParams tmp, block_counts)
     ~Lane() { if (ev_tail) (void)hipEventDestroy(ev_tail); if (side) (void)hipStreamDestroy(side); }
 };
 
@@ -188,7 +189,8 @@ struct uvrt_ctx {
     // two buffer sets: batch k + 1 is traced (on the launch lanes) into one while batch k is folded, reduced and
     // replayed (on the context's stream) out of the other
     // (oxz: the {orig.x, orig.z} of the batch's sweeps, [sweep][n_pad]; allocated by the first batch that holds one)
-    struct BatchSet { DevBuf rays, planes, folded, oxz; hipEvent_t free_ev = nullptr; ~BatchSet() { if (free_ev) (void)hipEventDestroy(free_ev); } };
+    // (masks: the planes of every ray of a deduped chunk, indexed like rays; dd_counts: the rays each such chunk holds, uint32 each)
+    struct BatchSet { DevBuf rays, planes, folded, oxz, masks, dd_counts; hipEvent_t free_ev = nullptr; ~BatchSet() { if (free_ev) (void)hipEventDestroy(free_ev); } };
     BatchSet bs[2];
     int b_set = 0;                        // the set of the traced batch (b_count > 0) / of the last one
     uint64_t b_chunks = 0;                // chunks traced so far: consecutive chunks alternate over the launch lanes
@@ -205,6 +207,9 @@ struct uvrt_ctx {
     int32_t b_count = 0;                  // launches of the batch that has not been replayed (0: none)
     int64_t b_n = 0, b_npad = 0;
     int32_t b_phys[uvrt::MAX_BATCH] = {};       // logical launch -> physical plane (launches are grouped by lamp)
+    bool dedupe = true;                   // uvrt_set_dedupe / UVRT_DEDUPE: a lamp's distinct rays are traced once per batch (uvrt_dedupe.h)
+    int64_t b_traced_known = -1;          // uvrt_batch_traced_rays: the last traced batch's rays in chunks traced as they are ...
+    int32_t b_traced_chunks = 0;          // ... and its deduped chunks, whose counts are bs[b_set].dd_counts[0, b_traced_chunks)
     bool b_is_folded = false;             // b_folded holds the batch (fold / all-reduce done), the replicas are zero
     void* comm = nullptr;                 // ncclComm_t of a ray-range-sharded job (uvrt_comm_init_rank)
     // CUs the launch lanes leave to the context's stream while a communicator is set (uvrt_capi_comm.hip
@@ -232,6 +237,9 @@ struct uvrt_ctx {
     int probe_skip_generate = 0;
     int probe_batches = 0;
 #endif
+    // (a dedupe group's chunks -- gid ranges across its launches, sized by their upper bound of which about half is traced --
+    //  pay up to twice the size: profiles/r08/r08_chunk_sweep.txt; the knob sets both)
+    size_t dedupe_chunk_bytes = (size_t)192 << 20;
     size_t batch_chunk_bytes = (size_t)96 << 20;   // rays per fused launch of a batch (developer knob UVRT_BATCH_CHUNK_MB,
                                                    // read once in uvrt_create): a chunk's rays stay in the Infinity Cache
 

@@ -1,0 +1,170 @@
+// uvrt_dedupe.h -- which photons of a lamp column are the same photon (host and device).
+//
+// generate.cl:13 seeds work-item gid of a launch from an f32 sum, 17 gid + 1 + 13 lx + 7 ly + 11 lz + (SEED >> 15), converted
+// to uint32 and hashed.  Above 2^24 the sum takes even values only, and SEED >> 15 moves it by less than 131 072 from launch
+// to launch: launches from ONE lamp position draw mostly the same hash inputs at shifted gids.  wang_hash is a bijection, so
+// equal inputs under an equal lamp are the same 16-byte ray with the same hit, and different inputs are different RNG states.
+// A batch traces each distinct ray of a lamp once and deposits its hit in the plane of every launch that holds it.
+//
+// A dedupe group: up to DEDUPE_MAX stop launches with one bit-identical lamp, in logical order, all over the call's global-id
+// range [first_gid, first_gid + n).  For occurrence (k, g) with hash input h, m_j = the number of g' in the range whose input in
+// launch j is h:
+//   * some m_j >= 2 (sums from 2^27 on, or seed mode 1's negative sums that all convert to 0): traced alone, mask = bit k;
+//   * else some j < k has m_j = 1: absorbed (mask 0) -- launch j's occurrence, or an earlier one, traces it;
+//   * else the owner: mask = { j : m_j = 1 }.
+// Every occurrence of one h sees the same m, so the decisions agree and every (launch, gid) is deposited exactly once.
+//
+// The search works on the sum as an integer (`dedupe_key`): for g' >= 1 it never decreases with g' (the f32 adds and the
+// conversion are monotone), so the matches of a launch are one run near (h - offset) / 17: estimate, look at the keys
+// around it, walk if they do not settle it.  gid 0 reads the other SEED and is looked at on its own.  dedupe_group_ok() says when keys and hash inputs
+// are the same thing: 17 gid + 1 stays an int32 and so does every key of the call.
+// A launch may hold a key twice long before the ulp reaches 17: in [2^27, 2^28) the ulp is 16 and an add whose exact result
+// is a tie rounds two neighbouring gids to one value (SEED >> 15 = 8 mod 16 does it).  So the multiplicities are always
+// counted, never assumed.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define UVRT_HD __host__ __device__ __forceinline__
+#else
+#define UVRT_HD inline
+#endif
+
+namespace uvrt {
+
+constexpr int DEDUPE_MAX = 31;             // launches per group: bit 31 of a ray's mask is the exact-step flag
+constexpr int64_t DEDUPE_GID_END = 126322567;   // 17 gid + 1 fits an int32 below this
+
+// generate.cl:13 -- the f32 adds in source order (int threadID; work-item 0 and seed mode 1 read SEED_{k-1})
+UVRT_HD float seed_sum_of(int threadID, uint32_t SEED, float lx, float ly, float lz)
+{
+    float acc = (float)(int)((uint32_t)threadID * 17u + 1u);      // (int arithmetic: wraps like the device's)
+    acc = acc + lx * 13.0f;
+    acc = acc + ly * 7.0f;
+    acc = acc + lz * 11.0f;
+    acc = acc + (float)(SEED >> 15);
+    return acc;
+}
+UVRT_HD float seed_sum(int64_t gid, float lx, float ly, float lz, uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode)
+{
+    // generate.cl:11 (int threadID)
+    return seed_sum_of((int)gid, (gid == 0 || seed_mode == 1) ? seed_prev : seed_next, lx, ly, lz);
+}
+
+// what work-item gid hands to wang_hash: float -> uint through int64; seed mode 1 converts a negative sum to 0
+UVRT_HD uint32_t seed_input(int64_t gid, float lx, float ly, float lz, uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode)
+{
+    const float acc = seed_sum(gid, lx, ly, lz, seed_prev, seed_next, seed_mode);
+    return (seed_mode == 1 && acc < 0.0f) ? 0u : (uint32_t)(int64_t)acc;
+}
+
+struct DedupeGroup {
+    float lx, ly, lz;                      // the group's lamp
+    int32_t seed_mode;
+    int32_t count;                         // launches, 2..DEDUPE_MAX
+    int64_t first_gid, n;                  // the call's range: where duplicates are looked for
+    uint32_t seed_prev[DEDUPE_MAX], seed_next[DEDUPE_MAX];
+    // filled by dedupe_group_ok:
+    int32_t offset[DEDUPE_MAX];            // key of launch j ~ 17 gid + offset[j]
+    int32_t key0[DEDUPE_MAX];              // key of launch j's gid 0 (first_gid == 0)
+};
+
+// the sum as an integer (an int32 within a group that dedupe_group_ok accepts); equal keys <=> equal hash inputs there
+UVRT_HD int32_t dedupe_key(const DedupeGroup& G, int j, int64_t gid)
+{
+    const int32_t s = (int32_t)seed_sum(gid, G.lx, G.ly, G.lz, G.seed_prev[j], G.seed_next[j], G.seed_mode);
+    return (G.seed_mode == 1 && s < 0) ? 0 : s;
+}
+
+// the same for a gid >= 1 (no work-item 0 among them)
+UVRT_HD int32_t dedupe_key1(const DedupeGroup& G, int j, int32_t gid)
+{
+    const int32_t s = (int32_t)seed_sum_of(gid, G.seed_mode == 1 ? G.seed_prev[j] : G.seed_next[j], G.lx, G.ly, G.lz);
+    return (G.seed_mode == 1 && s < 0) ? 0 : s;
+}
+
+// Where key t sits among launch j's gids >= 1 of the call's range [lo, last]: walk from the estimate g (the keys never
+// decrease).  Returns the key found there (== t: a match at g).  (gids as int32: the range ends below DEDUPE_GID_END.)
+UVRT_HD int32_t dedupe_find(const DedupeGroup& G, int j, int32_t t, int32_t lo, int32_t last, int32_t& g)
+{
+    g = g < lo ? lo : (g > last ? last : g);
+    int32_t v = dedupe_key1(G, j, g);
+    while (v > t && g > lo) v = dedupe_key1(G, j, --g);
+    while (v < t && g < last) v = dedupe_key1(G, j, ++g);
+    return v;
+}
+// the estimate from the key alone: key ~ 17 gid + offset[j]
+UVRT_HD int32_t dedupe_estimate(const DedupeGroup& G, int j, int32_t t)
+{
+    return (int32_t)((float)((int64_t)t - (int64_t)G.offset[j]) * (1.0f / 17.0f));
+}
+
+// Occurrences of key t in launch j over the call's range: 0, 1, or 2 for "two or more"; g = where the key is expected.
+// The keys at g and its two neighbours settle nearly every case without a loop -- a match with both its neighbours known, or
+// t strictly between two of the three -- one more key settles a match at the edge of the three, the walk takes the rest.
+// Nothing is assumed about how often a launch holds a key (a sum that ties in an add holds it twice well below 2^28).
+UVRT_HD int dedupe_multiplicity(const DedupeGroup& G, int j, int32_t t, int32_t g)
+{
+    int m = 0;
+    int32_t lo = (int32_t)G.first_gid;
+    const int32_t last = (int32_t)(G.first_gid + G.n - 1);
+    if (lo == 0) { m += G.key0[j] == t; lo = 1; }
+    if (lo > last) return m;
+    g = g < lo ? lo : (g > last ? last : g);
+    const int32_t gm = g > lo ? g - 1 : g, gp = g < last ? g + 1 : g;
+    const int32_t a = dedupe_key1(G, j, gm), b = dedupe_key1(G, j, g), c = dedupe_key1(G, j, gp);
+    if (b == t) m += 1 + ((gm < g) & (a == t)) + ((gp > g) & (c == t));
+    else if (a == t) m += 1 + (gm > lo && dedupe_key1(G, j, gm - 1) == t);          // (b != t: the run ends at gm)
+    else if (c == t) m += 1 + (gp < last && dedupe_key1(G, j, gp + 1) == t);
+    else if (!(((a < t) | (gm == lo)) & ((t < c) | (gp == last)))) {                 // t is not between the three: walk
+        if (dedupe_find(G, j, t, lo, last, g) == t)
+            m += 1 + ((g > lo && dedupe_key1(G, j, g - 1) == t) || (g < last && dedupe_key1(G, j, g + 1) == t));
+    }
+    return m > 2 ? 2 : m;
+}
+
+// the mask of occurrence (k, gid): 0 = absorbed, else the launches whose plane its hit goes to
+UVRT_HD uint32_t dedupe_mask(const DedupeGroup& G, int k, int64_t gid)
+{
+    const int32_t t = dedupe_key(G, k, gid);
+    // the copy in launch j sits (offset[k] - offset[j]) / 17 gids from this one (work-item 0 reads the other SEED: from its key)
+    const int32_t here = gid == 0 ? dedupe_estimate(G, k, t) : (int32_t)gid;
+    uint32_t ones = 0;
+    bool many = false;
+    for (int j = 0; j < G.count; ++j) {
+        const int m = dedupe_multiplicity(G, j, t, here + (int32_t)((float)(G.offset[k] - G.offset[j]) * (1.0f / 17.0f)));
+        many = many || m >= 2;
+        if (m == 1) ones |= 1u << j;
+    }
+    if (many) return 1u << k;
+    if ((ones & ((1u << k) - 1u)) != 0) return 0u;
+    return ones;
+}
+
+// Host: may these launches form a group?  Fills G.offset and G.key0.  No: a lamp that is not finite, a range past
+// DEDUPE_GID_END, or a sum that leaves the int32 range.
+inline bool dedupe_group_ok(DedupeGroup& G)
+{
+    if (G.count < 2 || G.count > DEDUPE_MAX || G.n <= 0 || G.first_gid < 0 || G.first_gid + G.n > DEDUPE_GID_END) return false;
+    const float big = 1e7f;
+    if (!(G.lx > -big && G.lx < big) || !(G.ly > -big && G.ly < big) || !(G.lz > -big && G.lz < big)) return false;
+    const int64_t last = G.first_gid + G.n - 1, lo1 = G.first_gid > 1 ? G.first_gid : 1, at = lo1 <= last ? lo1 : last;
+    const auto sum64 = [&](int j, int64_t gid) {
+        return (int64_t)seed_sum(gid, G.lx, G.ly, G.lz, G.seed_prev[j], G.seed_next[j], G.seed_mode);
+    };
+    // the sums of a launch never decrease from gid 1 on: its extremes are at the ends of the range (and at gid 0)
+    int64_t smin = INT64_MAX, smax = INT64_MIN;
+    for (int j = 0; j < G.count; ++j) {
+        const int64_t ends[3] = {sum64(j, G.first_gid), sum64(j, at), sum64(j, last)};
+        for (int64_t e : ends) { smin = e < smin ? e : smin; smax = e > smax ? e : smax; }
+    }
+    if (smin <= (int64_t)INT32_MIN + 1 || smax >= (int64_t)INT32_MAX - 1) return false;
+    for (int j = 0; j < G.count; ++j) {
+        // (from the sum itself: seed mode 1's zero for a negative sum says nothing about where the positive ones lie)
+        G.offset[j] = (int32_t)(sum64(j, at) - 17 * at);
+        G.key0[j] = dedupe_key(G, j, 0);
+    }
+    return true;
+}
+
+}  // namespace uvrt

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "uvrt_dedupe.h"
 
 namespace uvrt {
 
@@ -115,16 +116,7 @@ __device__ __forceinline__ float4 generate_ray_rng(float lx, float ly, float lz,
                                                    uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode,
                                                    float& r0, double& x, double& y, uint32_t& seed)
 {
-    const int threadID = (int)gid;                       // generate.cl:11 (int threadID)
-    const uint32_t SEED = (gid == 0 || seed_mode == 1) ? seed_prev : seed_next;
-
-    // generate.cl:13 -- f32 adds in source order, then float -> uint through int64
-    float acc = (float)(threadID * 17 + 1);
-    acc = acc + lx * 13.0f;
-    acc = acc + ly * 7.0f;
-    acc = acc + lz * 11.0f;
-    acc = acc + (float)(SEED >> 15);
-    seed = wang_hash((seed_mode == 1 && acc < 0.0f) ? 0u : (uint32_t)(int64_t)acc);
+    seed = wang_hash(seed_input(gid, lx, ly, lz, seed_prev, seed_next, seed_mode));      // generate.cl:11-13 (uvrt_dedupe.h)
 
     r0 = random_float(seed);
     const float origy = ly + r0 * light_length;          // :16
@@ -164,6 +156,24 @@ struct GenBatchParams {
     float lx[MAX_BATCH], ly[MAX_BATCH], lz[MAX_BATCH];       // lamp of physical plane p
     uint32_t seed_prev[MAX_BATCH], seed_next[MAX_BATCH];     // its place in the SEED chain
 };
+
+// The distinct rays of a dedupe group (uvrt_dedupe.h) over the gids [g0, g0 + gn) of all its launches, compacted: the owners'
+// rays in (launch, gid) order with their masks beside them.  Three kernels: mark (the owner test, a count per workgroup), scan,
+// write (the f64 direction code, for owners only).  The order is a function of the group alone; the count stays on the device.
+struct GenDedupeParams {
+    DedupeGroup g;
+    float4* rays;                      // out: [*total] <= count * gn
+    uint32_t* masks;                   // out: parallel to rays
+    uint32_t* total;                   // out: rays written
+    uint32_t* tmp;                     // scratch [count][gn]: every occurrence's mask between the passes
+    uint32_t* block_counts;            // scratch [count * ceil(gn / 2048)] (sized for ceil(gn / 256) by the caller)
+    int64_t g0, gn;
+    float light_length;
+};
+void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s);
+// k_extend6 over such a list (p.masks, p.n_dev, p.n = the upper bound, p.plane_stride = ints between planes)
+struct ExtendParams;
+bool launch_extend6_dedupe(const ExtendParams& p, int code, int grid_per_cu, hipStream_t s);
 
 // one entry of uvrt_replay_batch, in LOGICAL launch order
 struct ReplayOp {
@@ -250,6 +260,10 @@ struct ExtendParams {
     int32_t nquads;
     uint32_t top_quads;      // nodes [0, top_quads) are served from LDS
     uint32_t root_ref4;      // REF_DONE / a leaf reference (re-based) / 0
+    // a deduped chunk of a batch (launch_extend6_dedupe; uvrt_dedupe.h): `rays` is a compacted list of *n_dev distinct rays
+    // (n is its upper bound: the grid is sized from it), masks[i] = the planes ray i deposits in, bit k = plane k of `counts`
+    const uint32_t* masks;
+    const uint32_t* n_dev;
 };
 
 // launch wrappers (uvrt_kernels.hip)

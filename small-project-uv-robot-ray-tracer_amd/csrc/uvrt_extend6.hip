@@ -375,12 +375,12 @@ __device__ __forceinline__ int run7(Lane6& L, const ExtendParams& p, uint32_t st
 constexpr uint32_t MERGE6_AT = UVRT_MERGE6_AT, MERGE6_FIELDS = 14;
 static_assert(4 * MERGE6_AT <= 64, "the rays of four waves must fit one");
 constexpr uint32_t TOP6_KEEP = TOP6_MAX + 1 - (MERGE6_FIELDS * 64 * 4 + TOP6_STRIDE - 1) / TOP6_STRIDE;      // 120 records stay cached
-template <bool RECORD>
+template <bool RECORD, bool DD = false>
 __device__ __forceinline__ bool merge6(Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t& plane_off, uint32_t& stack_base,
                                        uint32_t& slot, bool& live, uint32_t* row0, uint32_t* xch)
 {
     // (few scalars at a time: the kernel's long-lived ones leave little room, and what does not fit is spilled for the whole loop)
-    if (L.cur == REF_DONE) retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);   // rays finished since the last refill
+    if (L.cur == REF_DONE) retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live);   // rays finished since the last refill
     // the wave's number in its workgroup comes from the lane's own stack rows (not yet anybody else's; threadIdx.x is not kept)
     {
         const uint32_t cnt = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(L.cur != REF_DONE));
@@ -439,7 +439,9 @@ struct TripClock {
 };
 #endif
 
-template <int LEAFP, bool RECORD, bool TOP, int FL>
+// DD: a deduped chunk of a batch (uvrt_dedupe.h; launch_extend6_dedupe) -- the ray count is read from device memory here and
+// every wave's share computed from it, a refill loads the ray's mask beside the ray, a finished ray deposits once per mask bit
+template <int LEAFP, bool RECORD, bool TOP, int FL, bool DD = false>
 __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
 {
     __shared__ __attribute__((aligned(1024))) uint32_t s_stack[PS6 + 1][256];   // 9 KB: row 0 always holds REF_DONE ("entry -1"), the stack proper follows
@@ -476,7 +478,20 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     const uint32_t wave = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t W = gridDim.x * 4u;
     uint32_t cursor = 0;
-    const uint32_t chunk_end = p.chunk;
+    // (DD: what size_persistent_grid does for p.n on the host, for the count the generate wrote)
+    const uint32_t dd_n = DD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)*p.n_dev) : 0u;
+    uint32_t dd_chunk = 0u;
+    if constexpr (DD) {
+        // ceil(dd_n / W) from the host's rounded 1 / W (p.plane_inv: launch_extend6_dedupe), exact after one correction step
+        // as the plane of a batch is in refill_lane (dd_n / W < 2^20: the rounded product is off by less than 1)
+        uint32_t q = (uint32_t)((float)dd_n * p.plane_inv);
+        int32_t r = (int32_t)(dd_n - q * W);
+        if (r < 0) { --q; r += (int32_t)W; }
+        else if ((uint32_t)r >= W) { ++q; r -= (int32_t)W; }
+        if (r > 0) ++q;
+        dd_chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((q + 63u) / 64u * 64u));
+    }
+    const uint32_t chunk_end = DD ? dd_chunk : p.chunk;
     uint32_t trip = 0;
     unsigned long long km = ~0ull;          // all ones in a trip that visits leaves (every LEAFP-th)
     unsigned long long full;                // exec of the loop: all 64 lanes (the launch uses full workgroups)
@@ -541,12 +556,12 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
                 const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
                 const int nidle = __popcll(idle_mask);
                 if (cursor < chunk_end) {
-                    if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
+                    if (L.cur == REF_DONE) refill_lane<RECORD, FL, PLANES_ASK, DD>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6, chunk_end, dd_n);
                     cursor += (uint32_t)nidle;
                     if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
                 } else if (TOP && cursor != MERGED6) {
                     cursor = MERGED6;
-                    const bool go_on = merge6<RECORD>(L, p, my_counts, plane_off, stack_base, slot, live, &s_stack[0][0],
+                    const bool go_on = merge6<RECORD, DD>(L, p, my_counts, plane_off, stack_base, slot, live, &s_stack[0][0],
                                                       (uint32_t*)&s_top[TOP ? TOP6_KEEP * (TOP6_STRIDE / 16u) : 0u]);
                     if (!go_on) break;
                     top_pairs = top_pairs < TOP6_KEEP ? top_pairs : TOP6_KEEP;
@@ -572,7 +587,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
         const int nidle = __popcll(idle_mask);
         if (TOP && cursor >= chunk_end && cursor != MERGED6 && 64 - nidle <= (int)MERGE6_AT) {
             cursor = MERGED6;
-            const bool go_on = merge6<RECORD>(L, p, my_counts, plane_off, stack_base, slot, live, &s_stack[0][0],
+            const bool go_on = merge6<RECORD, DD>(L, p, my_counts, plane_off, stack_base, slot, live, &s_stack[0][0],
                                               (uint32_t*)&s_top[TOP ? TOP6_KEEP * (TOP6_STRIDE / 16u) : 0u]);
             if (!go_on) break;
             top_pairs = top_pairs < TOP6_KEEP ? top_pairs : TOP6_KEEP;
@@ -583,7 +598,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
             unsigned long long tclk = __builtin_readcyclecounter();
 #endif
             if (cursor < chunk_end) {
-                if (L.cur == REF_DONE) refill_lane<RECORD, FL>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6);
+                if (L.cur == REF_DONE) refill_lane<RECORD, FL, PLANES_ASK, DD>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6, chunk_end, dd_n);
                 cursor += (uint32_t)nidle;
                 if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
 #ifdef UVRT_TRIP_STATS
@@ -660,7 +675,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     }
 #endif
     // the wave's sequence is exhausted and every lane is idle: deposit what is still pending
-    retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);
+    retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live);
 }
 
 // Per-launch node-pair records recs[0, P): the lamp's x and z subtracted from the x / z bounds (the
@@ -704,6 +719,27 @@ void launch_prepare_leaves6(const LeafTri* ltris, void* recs, int32_t npairs, in
     if (T <= 0) return;
     hipLaunchKernelGGL(k_prepare_leaves6, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, ltris,
                        (float4*)recs, npairs, T);
+}
+
+// The default kernel (leaf visits every second trip, LDS cache) over the compacted rays of a deduped chunk: the grid is sized
+// for the upper bound p.n, the kernel reads the count itself.  No hit records.
+bool launch_extend6_dedupe(const ExtendParams& p0, int code, int grid_per_cu, hipStream_t s)
+{
+    if (p0.n <= 0) return true;
+    if ((code & 7) != 1 || p0.hits || !p0.masks || !p0.n_dev || !p0.recs_prepared || p0.plane_stride == 0) return false;
+    ExtendParams p = p0;
+    p.plane_batches = (uint32_t)((p.n + 63) / 64);      // (one list: no plane is looked up in it)
+    p.plane_n = (uint32_t)p.n;
+    const unsigned grid = size_persistent_grid(p, grid_per_cu);
+    if (grid == 0) return false;
+    p.plane_inv = 1.0f / (float)(grid * 4u);            // (no planes in the list: the kernel divides the count by its waves with it)
+    p.root_ref6 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
+                      ? p.scene.root_ref + (uint32_t)p.npairs : p.scene.root_ref;
+    if (p.perm) p.top_pairs = (uint32_t)p.npairs;
+    if (p.flavour == 2) hipLaunchKernelGGL((k_extend6<2, false, true, 2, true>), dim3(grid), dim3(256), 0, s, p);
+    else if (p.flavour) hipLaunchKernelGGL((k_extend6<2, false, true, 1, true>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((k_extend6<2, false, true, 0, true>), dim3(grid), dim3(256), 0, s, p);
+    return true;
 }
 
 // code: bits 0-1 leaf period - 1 (0..3), bit 2 = WITHOUT the top-of-tree cache (codes other than 1: developer build only)

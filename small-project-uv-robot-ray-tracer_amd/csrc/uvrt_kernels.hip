@@ -77,6 +77,91 @@ __global__ __launch_bounds__(256) void k_generate_batch(GenBatchParams p)
                                                     p.seed_prev[k], p.seed_next[k], p.seed_mode, r0, x, y);
 }
 
+// The distinct rays of a dedupe group (GenDedupeParams): blockIdx.y = launch of the group, blockIdx.x = DD_SLOTS gids of the
+// chunk, DD_ROUNDS per thread (few workgroup counts for the one-workgroup scan between the passes).
+constexpr int DD_ROUNDS = 8, DD_SLOTS = 256 * DD_ROUNDS;
+// mark: every occurrence's mask (uvrt_dedupe.h: 0 = another occurrence traces this ray) and the owners per workgroup
+__global__ __launch_bounds__(256) void k_dedupe_mark(GenDedupeParams p)
+{
+    __shared__ uint32_t s_owners;
+    if (threadIdx.x == 0) s_owners = 0u;
+    __syncthreads();
+    const int k = blockIdx.y;
+    uint32_t owners = 0;               // of this wave
+    for (int r = 0; r < DD_ROUNDS; ++r) {
+        const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
+        uint32_t mask = 0;
+        if (i < p.gn) {
+            mask = dedupe_mask(p.g, k, p.g0 + i);
+            p.tmp[(int64_t)k * p.gn + i] = mask;
+        }
+        owners += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u));
+    }
+    if ((threadIdx.x & 63u) == 0u) atomicAdd(&s_owners, owners);
+    __syncthreads();
+    if (threadIdx.x == 0) p.block_counts[(size_t)k * gridDim.x + blockIdx.x] = s_owners;
+}
+
+// scan: the workgroups' counts -> their first slot in the compacted list, in (launch, gid) order; the total.  One workgroup
+// of 256 threads: it must find room on a CU beside the persistent traversal grid of the other lane, as every kernel here.
+__global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uint32_t* total, uint32_t nblocks)
+{
+    __shared__ uint32_t s_part[256];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (nblocks + 255u) / 256u;
+    const uint32_t lo = min(tid * per, nblocks), hi = min(lo + per, nblocks);
+    uint32_t sum = 0;
+    for (uint32_t b = lo; b < hi; ++b) sum += block_counts[b];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 256u; off <<= 1) {
+        const uint32_t v = tid >= off ? s_part[tid - off] : 0u;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = s_part[tid] - sum;
+    for (uint32_t b = lo; b < hi; ++b) {
+        const uint32_t c = block_counts[b];
+        block_counts[b] = run;
+        run += c;
+    }
+    if (tid == 255u) *total = s_part[255];
+}
+
+// write: the owners' rays (generate.cl:11-37) and masks at their slots, in (launch, gid) order
+__global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
+{
+    __shared__ uint32_t s_cnt[DD_ROUNDS][4];
+    const int k = blockIdx.y;
+    const uint32_t wv = threadIdx.x >> 6;
+    uint32_t mask[DD_ROUNDS], rank[DD_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < DD_ROUNDS; ++r) {
+        const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
+        mask[r] = i < p.gn ? p.tmp[(int64_t)k * p.gn + i] : 0u;
+        const unsigned long long owners = __builtin_amdgcn_ballot_w64(mask[r] != 0u);
+        rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(owners >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)owners, 0u));
+        if ((threadIdx.x & 63u) == 0u) s_cnt[r][wv] = (uint32_t)__popcll(owners);
+    }
+    __syncthreads();
+    uint32_t pos = p.block_counts[(size_t)k * gridDim.x + blockIdx.x];      // (after the scan: the workgroup's first slot)
+#pragma unroll
+    for (int r = 0; r < DD_ROUNDS; ++r) {
+        for (uint32_t w = 0; w < 4u; ++w) {
+            if (w == wv && mask[r] != 0u) {
+                const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
+                float r0;
+                double x, y;
+                p.rays[pos + rank[r]] = generate_ray(p.g.lx, p.g.ly, p.g.lz, p.light_length, p.g0 + i, p.g.seed_prev[k],
+                                                     p.g.seed_next[k], p.g.seed_mode, r0, x, y);
+                p.masks[pos + rank[r]] = mask[r];
+            }
+            pos += s_cnt[r][w];
+        }
+    }
+}
+
 // Exclusive prefix sum over the key histogram (one 1024-thread workgroup; nbins <= 2^20), and
 // re-zero the histogram for the next launch.
 __global__ __launch_bounds__(1024) void k_scan_bins(uint32_t* hist, uint32_t* bin_start,
@@ -464,6 +549,15 @@ void launch_generate_batch(const GenBatchParams& p, hipStream_t s)
 {
     if (p.n <= 0 || p.count <= 0) return;
     hipLaunchKernelGGL(k_generate_batch, dim3(blocks_for(p.n, 256), (unsigned)p.count), dim3(256), 0, s, p);
+}
+
+void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s)
+{
+    if (p.gn <= 0 || p.g.count <= 0) return;
+    const dim3 grid(blocks_for(p.gn, DD_SLOTS), (unsigned)p.g.count);
+    hipLaunchKernelGGL(k_dedupe_mark, grid, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_dedupe_scan, dim3(1), dim3(256), 0, s, p.block_counts, p.total, grid.x * grid.y);
+    hipLaunchKernelGGL(k_dedupe_write, grid, dim3(256), 0, s, p);
 }
 
 void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32_t replicas, int32_t T, hipStream_t s)

@@ -269,7 +269,9 @@ __device__ __forceinline__ bool origin_outside_window(float o)
 
 // The results of the ray a lane has finished (extend.cl:94-98): its hit record when one is pending (`live`), and its deposit
 // unless it hit nothing (dist == 1e30f).
-template <bool RECORD>
+// DD: the ray of a deduped chunk (uvrt_dedupe.h) -- the register holds the MASK of its planes instead of one plane's offset,
+// and the hit is deposited once per set bit, at bit * plane_stride + triID (uint32: a batch has fewer than 2^32 counters).
+template <bool RECORD, bool DD = false>
 __device__ __forceinline__ void retire_ray(const Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t plane_off,
                                            uint32_t slot, bool live)
 {
@@ -277,6 +279,11 @@ __device__ __forceinline__ void retire_ray(const Lane6& L, const ExtendParams& p
         const uint32_t li = p.order ? p.order[slot] : slot;
         p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
     }
+    if constexpr (DD) {
+        if (L.po.y != 1e30f)
+            for (uint32_t m = plane_off & PLANE_OFF6; m != 0u; m &= m - 1u)
+                atomicAdd(&my_counts[(uint32_t)__builtin_ctz(m) * p.plane_stride + L.triID], 1);
+    } else
     if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
 }
 
@@ -288,18 +295,39 @@ enum PlaneMode { PLANES_ASK, PLANES_NONE, PLANES_ALL };
 // the idle lanes) of the wave's sequence of 64-ray batches wave, wave + W, wave + 2W, ...  A slot beyond the wave's share, the
 // launch or its plane leaves the lane idle.  `root`: the kernel's root reference; `oxz`: the rays' {origin x, origin z}, read for
 // a lane that carries them (LaneF).
-template <bool RECORD, int FL, PlaneMode PM = PLANES_ASK, class LaneT>
+// DD: a deduped chunk (uvrt_dedupe.h) -- one compacted list of dd_n rays (read from device memory by the kernel's prologue, as is
+// the wave's share dd_chunk), no planes in it: the ray's mask is loaded beside the ray, behind the same wait, and takes the
+// place of the plane offset (bit 31 is the exact-step flag either way).
+template <bool RECORD, int FL, PlaneMode PM = PLANES_ASK, bool DD = false, class LaneT>
 __device__ __forceinline__ void refill_lane(LaneT& L, const ExtendParams& p, const float2* oxz, int32_t* my_counts,
                                             uint32_t& plane_off, uint32_t& slot, bool& live, unsigned long long idle_mask,
-                                            uint32_t cursor, uint32_t wave, uint32_t W, uint32_t root)
+                                            uint32_t cursor, uint32_t wave, uint32_t W, uint32_t root,
+                                            uint32_t dd_chunk = 0u, uint32_t dd_n = 0u)
 {
-    retire_ray<RECORD>(L, p, my_counts, plane_off, slot, live);
+    retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live);
     live = false;
     L.po.y = 1e30f;
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
     const uint32_t v = cursor + rank;
     const uint32_t gb = (v >> 6) * W + wave;                 // global 64-slot batch
     const uint32_t my = gb * 64u + (v & 63u);
+    if constexpr (DD) {
+        static_assert(!LaneT::OWN_XZ && !RECORD, "deduped chunks are k_extend6's, and a batch records no hits");
+        if (v < dd_chunk && my < dd_n) {
+            const float4 rec = p.rays[my];
+            const uint32_t mask = p.masks[my];
+            set_in_place(L.px, rec.x, FL == 2 ? rcp_raw(rec.x) : rcp_exact(rec.x));
+            set_in_place(L.py, rec.y, FL == 2 ? rcp_raw(rec.y) : rcp_exact(rec.y));
+            set_in_place(L.pz, rec.z, FL == 2 ? rcp_raw(rec.z) : rcp_exact(rec.z));
+            set_in_place(L.po, rec.w, 1e30f);       // generate.cl:34-35
+            set_in_place(L.triID, 0u);
+            set_in_place(L.sp, 0);
+            set_in_place(L.cur, root);
+            const bool spec = FL != 2 && (outside_proof_conditions(rec) || p.force_exact != 0);
+            set_in_place(plane_off, mask | (spec ? SPECIAL6 : 0u));
+        }
+        return;
+    }
     // plane (= launch of a batched trace) of the batch: gb / plane_batches, exact after one
     // correction step (gb < 2^24 is exact in f32, the rounded reciprocal is off by < 1)
     uint32_t pl = 0;
