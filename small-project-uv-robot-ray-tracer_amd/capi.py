@@ -54,6 +54,8 @@ SYMBOLS = [
     ("uvrt_batch_traced_rays", C.c_int, [_vp, C.POINTER(_i64)]),
     ("uvrt_seed_input", _u32, [_i64, _fp, _u32, _u32, _i32]),
     ("uvrt_dedupe_plan", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
+    ("uvrt_dedupe_plan_tiled", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i64, _i64, _vp]),
+    ("uvrt_dedupe_mark_device", C.c_int, [_vp, _fp, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
     ("uvrt_comm_available", C.c_int, []),
     ("uvrt_comm_info", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_comm_unique_id", C.c_int, [_vp]),
@@ -246,6 +248,27 @@ def dedupe_plan(lamp, seed_prev, seed_next_, seed_mode, first_gid, n):
     assert sp.size == sn.size
     out = np.empty((sp.size, int(n)), dtype=np.uint32)
     rc = lib().uvrt_dedupe_plan(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n), _ptr(out))
+    if rc != 0:
+        raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
+    return out
+
+
+DEDUPE_TILE_KEYS = 3840      # the device's tile (csrc/uvrt_dedupe.h)
+DEDUPE_BLOCK_GIDS = 2048     # gids per owner count of a chunk (csrc/uvrt_device.h DD_SLOTS)
+
+
+def dedupe_plan_tiled(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, tile_keys=DEDUPE_TILE_KEYS, chunk_first=None,
+                      chunk_n=None):
+    """dedupe_plan's masks for the chunk [chunk_first, chunk_first + chunk_n) of the range (default: all of it), computed tile
+    by tile on the host (include/uvrt.h uvrt_dedupe_plan_tiled): uint32[launches][chunk_n]"""
+    sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
+    sn = np.ascontiguousarray(seed_next_, dtype=np.uint32)
+    assert sp.size == sn.size
+    chunk_first = first_gid if chunk_first is None else chunk_first
+    chunk_n = n if chunk_n is None else chunk_n
+    out = np.empty((sp.size, int(chunk_n)), dtype=np.uint32)
+    rc = lib().uvrt_dedupe_plan_tiled(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n),
+                                      int(tile_keys), int(chunk_first), int(chunk_n), _ptr(out))
     if rc != 0:
         raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
     return out
@@ -494,6 +517,21 @@ class Ctx:
         out = _i64()
         self._ck(self._L.uvrt_batch_traced_rays(self._h, C.byref(out)))
         return int(out.value)
+
+    def dedupe_mark_device(self, lamp, seed_prev, seed_next_, seed_mode, first_gid, n, chunk_first=None, chunk_n=None):
+        """k_dedupe_mark alone for a group and a chunk of its range (include/uvrt.h uvrt_dedupe_mark_device):
+        (masks uint32[launches][chunk_n], owners uint32[launches][ceil(chunk_n / DEDUPE_BLOCK_GIDS)])"""
+        sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
+        sn = np.ascontiguousarray(seed_next_, dtype=np.uint32)
+        assert sp.size == sn.size
+        chunk_first = first_gid if chunk_first is None else chunk_first
+        chunk_n = n if chunk_n is None else chunk_n
+        masks = np.empty((sp.size, int(chunk_n)), dtype=np.uint32)
+        owners = np.empty((sp.size, (int(chunk_n) + DEDUPE_BLOCK_GIDS - 1) // DEDUPE_BLOCK_GIDS), dtype=np.uint32)
+        self._ck(self._L.uvrt_dedupe_mark_device(self._h, _f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode),
+                                                 int(first_gid), int(n), int(chunk_first), int(chunk_n), _ptr(masks),
+                                                 _ptr(owners)))
+        return masks, owners
 
     def comm_init_rank(self, id128, rank, world):
         assert len(id128) == 128

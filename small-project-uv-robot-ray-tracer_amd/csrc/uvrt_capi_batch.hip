@@ -208,10 +208,13 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             if ((rc = S.masks.ensure((size_t)count * (size_t)n_pad * 4, false, c->stream))) return rc;
             // (not zeroed: a chunk's generate runs on its lane BEFORE the lane waits for this stream, and writes its count)
             if ((rc = S.dd_counts.ensure(dd_chunks * 4, false, c->stream))) return rc;
+            // (dd_blocks zeroed: k_dedupe_mark adds its owners to it and k_dedupe_write leaves it zero again.  A chunk's generate
+            //  does not wait for this stream, so the zero fill is waited for here, where a buffer has grown)
             for (int l = 0; l <= c->batch_lanes; ++l) {
                 if ((rc = c->lanes[l].dd_tmp.ensure(dd_tmp_bytes, false, c->stream))) return rc;
-                if ((rc = c->lanes[l].dd_blocks.ensure(dd_block_bytes, false, c->stream))) return rc;
+                if ((rc = c->lanes[l].dd_blocks.ensure(dd_block_bytes, true, c->stream))) return rc;
             }
+            HIP_TRY(hipStreamSynchronize(c->stream));
         }
     }
     if (need_alloc || recs_stale) {
@@ -289,6 +292,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
                 dq.block_counts = cur_lane(c).dd_blocks.as<uint32_t>();
                 dq.g0 = first_gid + g0;
                 dq.gn = gn;
+                dedupe_tile_range(dq.g, dq.g0, dq.gn, DEDUPE_TILE_KEYS, dq.key_lo, dq.tiles);
                 dq.light_length = light_length;
                 launch_generate_dedupe(dq, ls);
                 if (int rcl = lane_stream(c, &ls)) return rcl;      // extend: after the fence
@@ -455,6 +459,71 @@ int uvrt_dedupe_plan(const float lamp[3], int32_t count, const uint32_t* seed_pr
     if (!dedupe_group_ok(G)) return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan: these launches cannot form a dedupe group");
     for (int k = 0; k < count; ++k)
         for (int64_t i = 0; i < n; ++i) masks[(size_t)k * (size_t)n + (size_t)i] = dedupe_mask(G, k, first_gid + i);
+    return UVRT_OK;
+}
+
+// a dedupe group from a test hook's arguments (who: the hook's name for the error text)
+static int hook_group(DedupeGroup& G, const char* who, const float lamp[3], int32_t count, const uint32_t* seed_prev,
+                      const uint32_t* seed_next, int32_t seed_mode, int64_t first_gid, int64_t n)
+{
+    if (!lamp || !seed_prev || !seed_next || count < 2 || count > DEDUPE_MAX)
+        return fail(UVRT_ERR_INVALID, "%s: null argument, or count outside [2,%d]", who, DEDUPE_MAX);
+    memset(&G, 0, sizeof G);
+    G.lx = lamp[0]; G.ly = lamp[1]; G.lz = lamp[2];
+    G.seed_mode = seed_mode;
+    G.count = count;
+    G.first_gid = first_gid; G.n = n;
+    for (int j = 0; j < count; ++j) { G.seed_prev[j] = seed_prev[j]; G.seed_next[j] = seed_next[j]; }
+    if (!dedupe_group_ok(G)) return fail(UVRT_ERR_INVALID, "%s: these launches cannot form a dedupe group", who);
+    return UVRT_OK;
+}
+static bool chunk_ok(const DedupeGroup& G, int64_t chunk_first, int64_t chunk_n)
+{
+    return chunk_n > 0 && chunk_first >= G.first_gid && chunk_first + chunk_n <= G.first_gid + G.n;
+}
+
+int uvrt_dedupe_plan_tiled(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                           int32_t seed_mode, int64_t first_gid, int64_t n, int32_t tile_keys, int64_t chunk_first,
+                           int64_t chunk_n, uint32_t* masks)
+{
+    DedupeGroup G;
+    if (int rc = hook_group(G, "uvrt_dedupe_plan_tiled", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
+    if (!masks || tile_keys <= 0 || !chunk_ok(G, chunk_first, chunk_n))
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan_tiled: null masks, no tile width, or a chunk outside the range");
+    std::vector<uint32_t> table((size_t)tile_keys);
+    dedupe_plan_tiled(G, tile_keys, chunk_first, chunk_n, table.data(), masks);
+    return UVRT_OK;
+}
+
+int uvrt_dedupe_mark_device(uvrt_ctx* c, const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                            int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first, int64_t chunk_n,
+                            uint32_t* masks, uint32_t* block_owner_counts)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_dedupe_mark_device: null context");
+    GenDedupeParams dq;
+    memset(&dq, 0, sizeof dq);
+    if (int rc = hook_group(dq.g, "uvrt_dedupe_mark_device", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
+    if (!masks || !block_owner_counts || !chunk_ok(dq.g, chunk_first, chunk_n))
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_mark_device: null output, or a chunk outside the range");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    // lane 0's scratch, on the context's stream (what a chunk without pipelining uses); growing it needs the stream idle
+    Lane& L = c->lanes[0];
+    const size_t nblocks = (size_t)count * (size_t)((chunk_n + DD_SLOTS - 1) / DD_SLOTS);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = L.dd_tmp.ensure((size_t)count * (size_t)chunk_n * 4, false, c->stream)) return rc;
+    if (int rc = L.dd_blocks.ensure((size_t)count * (size_t)((chunk_n + 255) / 256) * 4, true, c->stream)) return rc;
+    dq.tmp = L.dd_tmp.as<uint32_t>();
+    dq.block_counts = L.dd_blocks.as<uint32_t>();
+    dq.g0 = chunk_first;
+    dq.gn = chunk_n;
+    dedupe_tile_range(dq.g, dq.g0, dq.gn, DEDUPE_TILE_KEYS, dq.key_lo, dq.tiles);
+    launch_dedupe_mark(dq, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(masks, dq.tmp, (size_t)count * (size_t)chunk_n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(block_owner_counts, dq.block_counts, nblocks * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(dq.block_counts, 0, nblocks * 4, c->stream));      // as k_dedupe_write would leave it
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return UVRT_OK;
 }
 

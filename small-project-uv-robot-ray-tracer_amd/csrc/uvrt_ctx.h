@@ -92,7 +92,8 @@ struct Lane {
     DevBuf hot_hist, hot_list;       // scratch of the hot-record set-up kernels (uvrt_hotset.hip)
     const uint32_t* perm = nullptr;  // renumbering of the lane's current launch (set by uvrt_generate)
     DevBuf oxz;                      // {orig.x, orig.z} of free rays, [capacity]; allocated by the lane's first free launch
-    DevBuf dd_tmp, dd_blocks;        // a deduped chunk's scratch between the passes of its generate (GenDedupeParams tmp, block_counts)
+    DevBuf dd_tmp, dd_blocks;        // a deduped chunk's scratch between the passes of its generate (GenDedupeParams tmp, block_counts;
+                                     // dd_blocks is allocated zeroed and every chunk leaves it zero)
     ~Lane() { if (ev_tail) (void)hipEventDestroy(ev_tail); if (side) (void)hipStreamDestroy(side); }
 };
 

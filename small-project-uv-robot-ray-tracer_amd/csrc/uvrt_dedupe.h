@@ -141,6 +141,120 @@ UVRT_HD uint32_t dedupe_mask(const DedupeGroup& G, int k, int64_t gid)
     return ones;
 }
 
+// ---- The same masks from one pass per key TILE (k_dedupe_mark; uvrt_dedupe_plan_tiled runs these functions on the host) ----
+// The multiplicities are a property of the key, not of the occurrence, and from gid 1 on a launch's keys never decrease: the
+// occurrences of a key interval [t0, t0 + W) are ONE gid run per launch.  A tile takes a table of W entries, one per key value
+// (below 2^24 every integer is a key), inserts the runs of all launches over the call's WHOLE range -- bit j = launch j holds
+// the key, DEDUPE_MANY = some launch holds it twice and more -- and then reads the mask of every occurrence whose gid lies in
+// the chunk from its key's entry: dedupe_mask()'s rule with m_j read from the table, K keys per gid instead of 3 K^2.
+// gid 0 reads the other SEED and is outside the monotone run: it belongs to the tile that holds key0[j].
+constexpr uint32_t DEDUPE_MANY = 1u << 31;     // (DEDUPE_MAX = 31 leaves the bit free)
+// the product's tile: the table, the run bounds and the owner counters stay within 16 KB of LDS (about 226 gids per launch)
+constexpr int32_t DEDUPE_TILE_KEYS = 3840;
+
+// The first gid of [lo, hi) whose key in launch j is >= t, or hi; lo >= 1.  From the estimate in doubling steps to a bracket,
+// then by halves: a few keys where the estimate is good, and no long walk where it is not (seed mode 1's run of key 0).
+UVRT_HD int32_t dedupe_lower_bound(const DedupeGroup& G, int j, int64_t t, int32_t lo, int32_t hi)
+{
+    if (lo >= hi) return hi;
+    int32_t g = (int32_t)((float)(t - (int64_t)G.offset[j]) * (1.0f / 17.0f));
+    g = g < lo ? lo : (g > hi - 1 ? hi - 1 : g);
+    int32_t a, b;                              // key(a) < t or a == lo - 1; key(b) >= t or b == hi
+    if ((int64_t)dedupe_key1(G, j, g) >= t) {
+        a = lo - 1; b = g;
+        for (int32_t step = 1; b > lo; step += step) {
+            const int32_t q = b - lo > step ? b - step : lo;
+            if ((int64_t)dedupe_key1(G, j, q) >= t) b = q; else { a = q; break; }
+        }
+    } else {
+        a = g; b = hi;
+        for (int32_t step = 1; a < hi - 1; step += step) {
+            const int32_t q = hi - 1 - a > step ? a + step : hi - 1;
+            if ((int64_t)dedupe_key1(G, j, q) < t) a = q; else { b = q; break; }
+        }
+    }
+    while (b - a > 1) {
+        const int32_t m = a + (b - a) / 2;
+        if ((int64_t)dedupe_key1(G, j, m) >= t) b = m; else a = m;
+    }
+    return b;
+}
+
+// launch j's gids >= 1 of the call's range with a key in [t0, t0 + W): the run [g_lo, g_hi)
+UVRT_HD void dedupe_tile_run(const DedupeGroup& G, int j, int64_t t0, int32_t W, int32_t& g_lo, int32_t& g_hi)
+{
+    const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
+    g_lo = dedupe_lower_bound(G, j, t0, lo, hi);
+    g_hi = dedupe_lower_bound(G, j, t0 + W, g_lo, hi);
+}
+// does the call's range hold launch j's gid 0, with its key in [t0, t0 + W)?
+UVRT_HD bool dedupe_tile_holds_gid0(const DedupeGroup& G, int j, int64_t t0, int32_t W)
+{
+    return G.first_gid == 0 && (int64_t)G.key0[j] >= t0 && (int64_t)G.key0[j] < t0 + W;
+}
+// the table entry of a key of the tile (t0 is a key of the group: it fits an int32), or W and more for a key outside it
+UVRT_HD uint32_t dedupe_tile_slot(int32_t key, int64_t t0) { return (uint32_t)key - (uint32_t)(int32_t)t0; }
+
+// one occurrence of launch j at `slot` (the device's table is in LDS, its workgroup inserts at once)
+UVRT_HD void dedupe_tile_insert(uint32_t* table, uint32_t slot, int j)
+{
+    const uint32_t bit = 1u << j;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (atomicOr(&table[slot], bit) & bit) atomicOr(&table[slot], DEDUPE_MANY);
+#else
+    if (table[slot] & bit) table[slot] |= DEDUPE_MANY;
+    table[slot] |= bit;
+#endif
+}
+// the mask of an occurrence of launch k from its key's entry, after every insert
+UVRT_HD uint32_t dedupe_tile_resolve(uint32_t entry, int k)
+{
+    if (entry & DEDUPE_MANY) return 1u << k;
+    if ((entry & ((1u << k) - 1u)) != 0) return 0u;
+    return entry;
+}
+
+// The tiles of the chunk [c0, c0 + cn) of the call's range: they partition the keys from the smallest to the largest of any
+// launch's gids in the chunk -- at the ends of the chunk (the keys never decrease from gid 1 on) and at gid 0.
+UVRT_HD void dedupe_tile_range(const DedupeGroup& G, int64_t c0, int64_t cn, int32_t W, int64_t& key_lo, int64_t& tiles)
+{
+    int64_t kmin = INT64_MAX, kmax = INT64_MIN;
+    const int64_t last = c0 + cn - 1, lo1 = c0 > 1 ? c0 : 1;
+    for (int j = 0; j < G.count; ++j) {
+        int64_t e[3];
+        int ne = 0;
+        if (c0 == 0) e[ne++] = G.key0[j];
+        if (lo1 <= last) { e[ne++] = dedupe_key1(G, j, (int32_t)lo1); e[ne++] = dedupe_key1(G, j, (int32_t)last); }
+        for (int i = 0; i < ne; ++i) { kmin = e[i] < kmin ? e[i] : kmin; kmax = e[i] > kmax ? e[i] : kmax; }
+    }
+    key_lo = kmin;
+    tiles = cn > 0 ? (kmax - kmin) / W + 1 : 0;
+}
+
+// Host: the masks of the chunk [c0, c0 + cn) of a group's range, masks[k * cn + i], tile by tile with a table of W entries
+inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int64_t c0, int64_t cn, uint32_t* table, uint32_t* masks)
+{
+    int64_t key_lo, tiles;
+    dedupe_tile_range(G, c0, cn, W, key_lo, tiles);
+    for (int64_t tile = 0; tile < tiles; ++tile) {
+        const int64_t t0 = key_lo + tile * W;
+        int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
+        for (int32_t i = 0; i < W; ++i) table[i] = 0u;
+        for (int j = 0; j < G.count; ++j) {
+            dedupe_tile_run(G, j, t0, W, g_lo[j], g_hi[j]);
+            for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) dedupe_tile_insert(table, dedupe_tile_slot(dedupe_key1(G, j, g), t0), j);
+            if (dedupe_tile_holds_gid0(G, j, t0, W)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
+        }
+        for (int k = 0; k < G.count; ++k) {
+            const int64_t a = g_lo[k] > c0 ? g_lo[k] : c0, b = g_hi[k] < c0 + cn ? g_hi[k] : c0 + cn;
+            for (int64_t g = a; g < b; ++g)
+                masks[(int64_t)k * cn + (g - c0)] = dedupe_tile_resolve(table[dedupe_tile_slot(dedupe_key1(G, k, (int32_t)g), t0)], k);
+            if (c0 == 0 && dedupe_tile_holds_gid0(G, k, t0, W))
+                masks[(int64_t)k * cn] = dedupe_tile_resolve(table[dedupe_tile_slot(G.key0[k], t0)], k);
+        }
+    }
+}
+
 // Host: may these launches form a group?  Fills G.offset and G.key0.  No: a lamp that is not finite, a range past
 // DEDUPE_GID_END, or a sum that leaves the int32 range.
 inline bool dedupe_group_ok(DedupeGroup& G)

@@ -158,19 +158,25 @@ struct GenBatchParams {
 };
 
 // The distinct rays of a dedupe group (uvrt_dedupe.h) over the gids [g0, g0 + gn) of all its launches, compacted: the owners'
-// rays in (launch, gid) order with their masks beside them.  Three kernels: mark (the owner test, a count per workgroup), scan,
-// write (the f64 direction code, for owners only).  The order is a function of the group alone; the count stays on the device.
+// rays in (launch, gid) order with their masks beside them.  Three kernels: mark (the owner test over key tiles, a count per
+// launch and block of DD_SLOTS gids), scan, write (the f64 direction code, for owners only).  The order is a function of the
+// group alone; the count stays on the device.
+constexpr int DD_ROUNDS = 8, DD_SLOTS = 256 * DD_ROUNDS;      // gids per workgroup of the write pass and per owner count
 struct GenDedupeParams {
     DedupeGroup g;
     float4* rays;                      // out: [*total] <= count * gn
     uint32_t* masks;                   // out: parallel to rays
     uint32_t* total;                   // out: rays written
     uint32_t* tmp;                     // scratch [count][gn]: every occurrence's mask between the passes
-    uint32_t* block_counts;            // scratch [count * ceil(gn / 2048)] (sized for ceil(gn / 256) by the caller)
+    uint32_t* block_counts;            // scratch [count * ceil(gn / 2048)] (sized for ceil(gn / 256) by the caller): ZERO before
+                                       // mark, which adds the owners; offsets after the scan; write leaves it zero again
     int64_t g0, gn;
+    int64_t key_lo, tiles;             // the chunk's key tiles (dedupe_tile_range with DEDUPE_TILE_KEYS)
     float light_length;
 };
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s);
+// its first kernel alone: tmp and the owners per block added to block_counts (a test hook runs it by itself)
+void launch_dedupe_mark(const GenDedupeParams& p, hipStream_t s);
 // k_extend6 over such a list (p.masks, p.n_dev, p.n = the upper bound, p.plane_stride = ints between planes)
 struct ExtendParams;
 bool launch_extend6_dedupe(const ExtendParams& p, int code, int grid_per_cu, hipStream_t s);

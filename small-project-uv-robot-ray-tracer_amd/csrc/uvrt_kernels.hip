@@ -77,29 +77,75 @@ __global__ __launch_bounds__(256) void k_generate_batch(GenBatchParams p)
                                                     p.seed_prev[k], p.seed_next[k], p.seed_mode, r0, x, y);
 }
 
-// The distinct rays of a dedupe group (GenDedupeParams): blockIdx.y = launch of the group, blockIdx.x = DD_SLOTS gids of the
-// chunk, DD_ROUNDS per thread (few workgroup counts for the one-workgroup scan between the passes).
-constexpr int DD_ROUNDS = 8, DD_SLOTS = 256 * DD_ROUNDS;
-// mark: every occurrence's mask (uvrt_dedupe.h: 0 = another occurrence traces this ray) and the owners per workgroup
+// The distinct rays of a dedupe group (GenDedupeParams).  Scan and write: blockIdx.y = launch of the group, blockIdx.x =
+// DD_SLOTS gids of the chunk, DD_ROUNDS per thread (few workgroup counts for the one-workgroup scan between the passes).
+//
+// mark: every occurrence's mask (uvrt_dedupe.h: 0 = another occurrence traces this ray) and the owners per launch and block
+// of DD_SLOTS gids, one workgroup per key tile (uvrt_dedupe.h, "one pass per key tile").  Every launch's gid run of the tile
+// goes into a table in LDS, a barrier, then every occurrence of the chunk reads its mask from its key's entry.  The owners
+// are counted with integer adds -- per wave, in LDS for the two blocks a run usually touches, one global add per block -- so
+// the counts and the compaction order stay a function of the group alone.  block_counts is zero on entry (k_dedupe_write
+// leaves it so).  16 KB of LDS: the kernel finds room on a CU beside the other lane's persistent traversal grid.
 __global__ __launch_bounds__(256) void k_dedupe_mark(GenDedupeParams p)
 {
-    __shared__ uint32_t s_owners;
-    if (threadIdx.x == 0) s_owners = 0u;
-    __syncthreads();
-    const int k = blockIdx.y;
-    uint32_t owners = 0;               // of this wave
-    for (int r = 0; r < DD_ROUNDS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
-        uint32_t mask = 0;
-        if (i < p.gn) {
-            mask = dedupe_mask(p.g, k, p.g0 + i);
-            p.tmp[(int64_t)k * p.gn + i] = mask;
-        }
-        owners += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u));
+    constexpr int32_t W = DEDUPE_TILE_KEYS;
+    __shared__ uint32_t s_table[W];
+    __shared__ int32_t s_run[DEDUPE_MAX][2];
+    __shared__ uint32_t s_cnt[DEDUPE_MAX * 2];
+    const int tid = threadIdx.x, K = p.g.count;
+    const int64_t t0 = p.key_lo + (int64_t)blockIdx.x * W;
+    const uint32_t nb = (uint32_t)((p.gn + DD_SLOTS - 1) / DD_SLOTS);
+    for (int i = tid; i < W; i += 256) s_table[i] = 0u;
+    if (tid < 2 * K) s_cnt[tid] = 0u;
+    if (tid < K) {      // the run bounds are uniform work: a lane per launch finds them
+        int32_t g_lo, g_hi;
+        dedupe_tile_run(p.g, tid, t0, W, g_lo, g_hi);
+        s_run[tid][0] = g_lo;
+        s_run[tid][1] = g_hi;
     }
-    if ((threadIdx.x & 63u) == 0u) atomicAdd(&s_owners, owners);
     __syncthreads();
-    if (threadIdx.x == 0) p.block_counts[(size_t)k * gridDim.x + blockIdx.x] = s_owners;
+    for (int j = 0; j < K; ++j) {
+        const int32_t hi = s_run[j][1];
+        for (int32_t g = s_run[j][0] + tid; g < hi; g += 256) {
+            const uint32_t slot = dedupe_tile_slot(dedupe_key1(p.g, j, g), t0);
+            if (slot < (uint32_t)W) dedupe_tile_insert(s_table, slot, j);
+        }
+    }
+    if (tid < K && dedupe_tile_holds_gid0(p.g, tid, t0, W)) dedupe_tile_insert(s_table, dedupe_tile_slot(p.g.key0[tid], t0), tid);
+    __syncthreads();
+    const int32_t c0 = (int32_t)p.g0, c1 = (int32_t)(p.g0 + p.gn);      // (gids as int32: the range ends below DEDUPE_GID_END)
+    for (int j = 0; j < K; ++j) {
+        const int32_t a = max(s_run[j][0], c0), b = min(s_run[j][1], c1);
+        const uint32_t b0 = (uint32_t)(a - c0) / (uint32_t)DD_SLOTS;      // (read only where a < b)
+        for (int32_t base = a; base < b; base += 256) {                   // (uniform trips: every lane takes part in the ballots)
+            const int32_t g = base + tid;
+            uint32_t mask = 0u, rel = 0u;
+            if (g < b) {
+                const uint32_t slot = dedupe_tile_slot(dedupe_key1(p.g, j, g), t0);
+                mask = dedupe_tile_resolve(slot < (uint32_t)W ? s_table[slot] : DEDUPE_MANY, j);
+                p.tmp[(int64_t)j * p.gn + (g - c0)] = mask;
+                rel = (uint32_t)(g - c0) / (uint32_t)DD_SLOTS - b0;
+            }
+            const uint32_t n0 = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u && rel == 0u));
+            const uint32_t n1 = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u && rel == 1u));
+            if ((tid & 63) == 0) {
+                if (n0) atomicAdd(&s_cnt[2 * j], n0);
+                if (n1) atomicAdd(&s_cnt[2 * j + 1], n1);
+            }
+            if (mask != 0u && rel >= 2u) atomicAdd(&p.block_counts[(size_t)j * nb + b0 + rel], 1u);      // (a long run: key 0 of seed mode 1)
+        }
+    }
+    if (c0 == 0 && tid < K && dedupe_tile_holds_gid0(p.g, tid, t0, W)) {      // work-item 0 of launch `tid`
+        const uint32_t mask = dedupe_tile_resolve(s_table[dedupe_tile_slot(p.g.key0[tid], t0)], tid);
+        p.tmp[(int64_t)tid * p.gn] = mask;
+        if (mask != 0u) atomicAdd(&p.block_counts[(size_t)tid * nb], 1u);
+    }
+    __syncthreads();
+    if (tid < 2 * K && s_cnt[tid] != 0u) {
+        const int j = tid >> 1;
+        const uint32_t b0 = (uint32_t)(max(s_run[j][0], c0) - c0) / (uint32_t)DD_SLOTS;
+        atomicAdd(&p.block_counts[(size_t)j * nb + b0 + (uint32_t)(tid & 1)], s_cnt[tid]);
+    }
 }
 
 // scan: the workgroups' counts -> their first slot in the compacted list, in (launch, gid) order; the total.  One workgroup
@@ -136,6 +182,7 @@ __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
     const int k = blockIdx.y;
     const uint32_t wv = threadIdx.x >> 6;
     uint32_t mask[DD_ROUNDS], rank[DD_ROUNDS];
+    uint32_t pos = p.block_counts[(size_t)k * gridDim.x + blockIdx.x];      // (after the scan: the workgroup's first slot)
 #pragma unroll
     for (int r = 0; r < DD_ROUNDS; ++r) {
         const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
@@ -145,7 +192,8 @@ __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
         if ((threadIdx.x & 63u) == 0u) s_cnt[r][wv] = (uint32_t)__popcll(owners);
     }
     __syncthreads();
-    uint32_t pos = p.block_counts[(size_t)k * gridDim.x + blockIdx.x];      // (after the scan: the workgroup's first slot)
+    // every thread has read the entry: zero again for the next chunk's mark, which adds its owners to it
+    if (threadIdx.x == 0) p.block_counts[(size_t)k * gridDim.x + blockIdx.x] = 0u;
 #pragma unroll
     for (int r = 0; r < DD_ROUNDS; ++r) {
         for (uint32_t w = 0; w < 4u; ++w) {
@@ -551,11 +599,17 @@ void launch_generate_batch(const GenBatchParams& p, hipStream_t s)
     hipLaunchKernelGGL(k_generate_batch, dim3(blocks_for(p.n, 256), (unsigned)p.count), dim3(256), 0, s, p);
 }
 
+void launch_dedupe_mark(const GenDedupeParams& p, hipStream_t s)
+{
+    if (p.gn <= 0 || p.g.count <= 0 || p.tiles <= 0) return;
+    hipLaunchKernelGGL(k_dedupe_mark, dim3((unsigned)p.tiles), dim3(256), 0, s, p);
+}
+
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s)
 {
     if (p.gn <= 0 || p.g.count <= 0) return;
     const dim3 grid(blocks_for(p.gn, DD_SLOTS), (unsigned)p.g.count);
-    hipLaunchKernelGGL(k_dedupe_mark, grid, dim3(256), 0, s, p);
+    launch_dedupe_mark(p, s);
     hipLaunchKernelGGL(k_dedupe_scan, dim3(1), dim3(256), 0, s, p.block_counts, p.total, grid.x * grid.y);
     hipLaunchKernelGGL(k_dedupe_write, grid, dim3(256), 0, s, p);
 }
