@@ -301,6 +301,15 @@ int uvrt_read_batch_counts(uvrt_ctx* ctx, int32_t launch, int32_t* out, int32_t 
  * uvrt_set_dedupe(ctx, 0) switches it off for later batches; the default is on, or what the environment variable
  * UVRT_DEDUPE (0 / 1) says when the context is created. */
 int uvrt_set_dedupe(uvrt_ctx* ctx, int32_t on);
+/* Developer knob: the instruction-issue priority (s_setprio level, 0..3) of the short kernels that run beside another launch
+ * lane's persistent traversal grid -- generate, the dedupe passes, fold, replay, accumulate, Shade, reset, the per-launch
+ * records.  Such a kernel's waves are the youngest on their SIMD and at level 0 issue only in the slots the traversal's waves
+ * leave; a level above 0 lets them issue when they are ready.  It changes when instructions issue, never what they compute:
+ * every result is bit for bit the same at every level.  The traversal kernels take no level.  Takes effect with the next
+ * launch; the default is 1, or what the environment variable UVRT_HELPER_PRIO (0..3) says when the context is created.
+ * A value outside 0..3: UVRT_ERR_INVALID, the level unchanged. */
+int uvrt_set_helper_priority(uvrt_ctx* ctx, int32_t prio);
+int uvrt_get_helper_priority(uvrt_ctx* ctx, int32_t* prio);
 /* test hook: the rays the traversal kernel was given for the stops of the last traced batch (waits for the batch) */
 int uvrt_batch_traced_rays(uvrt_ctx* ctx, int64_t* out);
 /* test hooks, host only.  uvrt_seed_input: what work-item gid of a launch hands to the hash (generate.cl:13; the rules of

@@ -51,6 +51,8 @@ SYMBOLS = [
     ("uvrt_fold_batch", C.c_int, [_vp]),
     ("uvrt_read_batch_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_set_dedupe", C.c_int, [_vp, _i32]),
+    ("uvrt_set_helper_priority", C.c_int, [_vp, _i32]),
+    ("uvrt_get_helper_priority", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_batch_traced_rays", C.c_int, [_vp, C.POINTER(_i64)]),
     ("uvrt_seed_input", _u32, [_i64, _fp, _u32, _u32, _i32]),
     ("uvrt_dedupe_plan", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
@@ -511,6 +513,16 @@ class Ctx:
     def set_dedupe(self, on):
         """trace every distinct photon of a lamp once per batch (default on; include/uvrt.h uvrt_set_dedupe)"""
         self._ck(self._L.uvrt_set_dedupe(self._h, 1 if on else 0))
+
+    def set_helper_priority(self, prio):
+        """issue priority (0..3) of the short kernels that run beside a traversal grid, from the next launch on
+        (include/uvrt.h uvrt_set_helper_priority; results are the same bits at every level)"""
+        self._ck(self._L.uvrt_set_helper_priority(self._h, int(prio)))
+
+    def get_helper_priority(self):
+        m = _i32()
+        self._ck(self._L.uvrt_get_helper_priority(self._h, C.byref(m)))
+        return int(m.value)
 
     def batch_traced_rays(self):
         """rays the traversal kernel was given for the stops of the last traced batch"""

@@ -114,6 +114,7 @@ int uvrt_create(int device_id, uvrt_ctx** out)
 #endif
     if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
     if (const char* e = getenv("UVRT_DEDUPE")) c->dedupe = atoi(e) != 0;                 // uvrt_set_dedupe's default
+    if (const char* e = getenv("UVRT_HELPER_PRIO")) { const int v = atoi(e); if (v >= 0 && v <= 3) c->helper_prio = v; }   // uvrt_set_helper_priority's default
     if (const char* e = getenv("UVRT_BATCH_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL - 1) c->batch_lanes = v; }
     if (const char* e = getenv("UVRT_COMM_RESERVE_CUS")) { const int v = atoi(e); if (v >= 0 && v <= 64 && v % 8 == 0) c->comm_reserve_knob = v; }
     if (const char* e = getenv("UVRT_HOT_SAMPLE")) { const int v = atoi(e); if (v >= 256 && v <= (1 << 20)) c->hot_sample = v; }
@@ -409,7 +410,7 @@ int uvrt_reset(uvrt_ctx* c, int32_t reset_color)
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     launch_reset(c->photon_map.as<double>(), c->max_map.as<double>(), c->lanes[0].counts.as<int32_t>(),
-                 c->replicas, c->T, c->color.as<float>(), reset_color, c->T, c->stream);
+                 c->replicas, c->T, c->color.as<float>(), reset_color, c->T, c->helper_prio, c->stream);
     HIP_TRY(hipGetLastError());
     // side-lane count buffers are zero unless an extend was never accumulated; only then must later
     // generate / extend work on the side streams wait for this reset (lane 0's: k_reset)
@@ -585,6 +586,20 @@ int uvrt_set_dedupe(uvrt_ctx* c, int32_t on)
 {
     if (!c) return fail(UVRT_ERR_INVALID, "null context");
     c->dedupe = on != 0;
+    return UVRT_OK;
+}
+
+int uvrt_set_helper_priority(uvrt_ctx* c, int32_t prio)
+{
+    if (!c || prio < 0 || prio > 3) return fail(UVRT_ERR_INVALID, "uvrt_set_helper_priority: the level must be 0..3");
+    c->helper_prio = prio;
+    return UVRT_OK;
+}
+
+int uvrt_get_helper_priority(uvrt_ctx* c, int32_t* prio)
+{
+    if (!c || !prio) return fail(UVRT_ERR_INVALID, "uvrt_get_helper_priority: null argument");
+    *prio = c->helper_prio;
     return UVRT_OK;
 }
 

@@ -222,7 +222,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         for (int g = 0; g < ngroups; ++g) {
             uvrt_ctx::RecsKey& key = c->b_recs_key[g];
             if (key.holds(gx[g], gz[g], gperm[g], ggen[g])) continue;
-            launch_prepare_launch6(c->pairs.as<PairRec>(), c->b_recs[g].p, gx[g], gz[g], c->npairs, gperm[g], c->stream);
+            launch_prepare_launch6(c->pairs.as<PairRec>(), c->b_recs[g].p, gx[g], gz[g], c->npairs, gperm[g], c->helper_prio, c->stream);
             key = {{true, gx[g], gz[g]}, gperm[g], ggen[g]};
         }
         // the scene's free records, on first use (the lanes are joined above, the fence below covers them)
@@ -294,6 +294,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
                 dq.gn = gn;
                 dedupe_tile_range(dq.g, dq.g0, dq.gn, DEDUPE_TILE_KEYS, dq.key_lo, dq.tiles);
                 dq.light_length = light_length;
+                dq.prio = c->helper_prio;
                 launch_generate_dedupe(dq, ls);
                 if (int rcl = lane_stream(c, &ls)) return rcl;      // extend: after the fence
                 ExtendParams p;
@@ -328,6 +329,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             gq.light_length = light_length;
             gq.seed_mode = c->seed_mode;
             gq.count = kc;
+            gq.prio = c->helper_prio;
             for (int j = 0; j < kc; ++j) {
                 gq.lx[j] = gp.lx[ph0 + j]; gq.ly[j] = gp.ly[ph0 + j]; gq.lz[j] = gp.lz[ph0 + j];
                 gq.seed_prev[j] = gp.seed_prev[ph0 + j]; gq.seed_next[j] = gp.seed_next[ph0 + j];
@@ -344,7 +346,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             p.recs = c->b_recs[g].p;
             p.perm = gperm[g];
             p.recs_prepared = 1;
-            if (int rct = timed_launch(c, ls, who, "the stops' launch", [&] { return launch_extend6(p, variant_code6(c->variant), per_cu, ls); }))
+            if (int rct = timed_launch(c, ls, who, "the stops' launch", [&] { return launch_extend6(p, variant_code6(c->variant), per_cu, c->helper_prio, ls); }))
                 return rct;
         }
     }
@@ -364,6 +366,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         sq.n = n;
         sq.light_length = light_length;
         sq.count = kc;
+        sq.prio = c->helper_prio;
         for (int j = 0; j < kc; ++j) {
             sq.fx[j] = sp.fx[k0 + j]; sq.fy[j] = sp.fy[k0 + j]; sq.fz[j] = sp.fz[k0 + j];
             sq.tx[j] = sp.tx[k0 + j]; sq.ty[j] = sp.ty[k0 + j]; sq.tz[j] = sp.tz[k0 + j];
@@ -518,6 +521,7 @@ int uvrt_dedupe_mark_device(uvrt_ctx* c, const float lamp[3], int32_t count, con
     dq.g0 = chunk_first;
     dq.gn = chunk_n;
     dedupe_tile_range(dq.g, dq.g0, dq.gn, DEDUPE_TILE_KEYS, dq.key_lo, dq.tiles);
+    dq.prio = c->helper_prio;
     launch_dedupe_mark(dq, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(masks, dq.tmp, (size_t)count * (size_t)chunk_n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -533,7 +537,7 @@ int uvrt_fold_batch(uvrt_ctx* c)
     if (c->b_is_folded) return UVRT_OK;
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
-    launch_fold_planes(c->bs[c->b_set].planes.as<int32_t>(), c->bs[c->b_set].folded.as<int32_t>(), c->b_count, c->b_repl, c->T, c->stream);
+    launch_fold_planes(c->bs[c->b_set].planes.as<int32_t>(), c->bs[c->b_set].folded.as<int32_t>(), c->b_count, c->b_repl, c->T, c->helper_prio, c->stream);
     HIP_TRY(hipGetLastError());
     c->b_is_folded = true;
     return UVRT_OK;          // on the context's stream like everything else that touches the set until its replay
@@ -560,6 +564,7 @@ int uvrt_replay_batch(uvrt_ctx* c, const uvrt_replay_op* ops, int32_t count, int
     p.T = tri_count;
     p.count = count;
     p.is_folded = c->b_is_folded ? 1 : 0;
+    p.prio = c->helper_prio;
     for (int k = 0; k < count; ++k) {
         if (ops[k].which_map != UVRT_MAP_SUM && ops[k].which_map != UVRT_MAP_MAX)
             return fail(UVRT_ERR_INVALID, "uvrt_replay_batch: which_map must be 0 or 1");

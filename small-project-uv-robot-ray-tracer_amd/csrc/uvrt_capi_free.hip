@@ -131,6 +131,7 @@ int uvrt_generate_sweep(uvrt_ctx* c, const float from[3], const float to[3], flo
     p.n = n;
     p.seed_prev = seed_prev;
     p.seed_next = seed_next;
+    p.prio = c->helper_prio;
     launch_generate_sweep(p, ls);
     HIP_TRY(hipGetLastError());
     c->seed = seed_next;

@@ -207,6 +207,7 @@ int uvrt_generate(uvrt_ctx* c, const float lp[3], float light_length, int64_t fi
         p.prep_perm = pm;
         p.prep_npairs = c->npairs;
     }
+    p.prio = c->helper_prio;
     launch_generate(p, ls);
     HIP_TRY(hipGetLastError());
     L.recs_tag = {p.prep_recs != nullptr, lp[0], lp[2]};
@@ -277,7 +278,7 @@ int uvrt_extend(uvrt_ctx* c, int64_t n)
         // (profiles/r02/r02_experiments.txt); with four launch lanes 4 per CU
         const int per_cu_default = (c->cur_pipelined && c->nlanes >= 4) ? 4 : c->cur_pipelined ? 7 : 8;
         if (int rc = timed_launch(c, ls, "uvrt_extend", "the launch", [&] {
-                return launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, per_cu_default), ls);
+                return launch_extend6(p, variant_code6(c->variant), variant_per_cu(c->variant, per_cu_default), c->helper_prio, ls);
             }))
             return rc;
     }
@@ -306,7 +307,7 @@ int uvrt_accumulate(uvrt_ctx* c, float time_step, int32_t tri_count)
         return UVRT_OK;
     }
     launch_accumulate(c->photon_map.as<double>(), c->max_map.as<double>(), cur_lane(c).counts.as<int32_t>(),
-                      c->replicas, c->T, time_step, tri_count, ls);
+                      c->replicas, c->T, time_step, tri_count, c->helper_prio, ls);
     HIP_TRY(hipGetLastError());
     return UVRT_OK;
 }
@@ -357,7 +358,7 @@ int uvrt_shade(uvrt_ctx* c, int32_t which, int32_t photons_per_light, float scal
         launch_accumulate_shade(c->photon_map.as<double>(), c->max_map.as<double>(), cur_lane(c).counts.as<int32_t>(), c->replicas,
                                 c->T, c->pend.time_step, c->dosage.as<float>(), c->area.as<float>(), c->color.as<float>(),
                                 which == UVRT_MAP_SUM ? 0 : 1, photons_per_light, scaled_power, min_value, threshold_view,
-                                tri_count, fs);
+                                tri_count, c->helper_prio, fs);
         HIP_TRY(hipGetLastError());
         return UVRT_OK;
     }
@@ -366,7 +367,7 @@ int uvrt_shade(uvrt_ctx* c, int32_t which, int32_t photons_per_light, float scal
     hipStream_t ls;
     if (int rc = lane_stream(c, &ls, true)) return rc;
     launch_shade(map, c->dosage.as<float>(), c->area.as<float>(), c->color.as<float>(), photons_per_light,
-                 scaled_power, min_value, threshold_view, tri_count, ls);
+                 scaled_power, min_value, threshold_view, tri_count, c->helper_prio, ls);
     HIP_TRY(hipGetLastError());
     return UVRT_OK;
 }

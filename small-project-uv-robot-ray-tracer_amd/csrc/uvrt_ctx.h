@@ -208,6 +208,8 @@ struct uvrt_ctx {
     int32_t b_count = 0;                  // launches of the batch that has not been replayed (0: none)
     int64_t b_n = 0, b_npad = 0;
     int32_t b_phys[uvrt::MAX_BATCH] = {};       // logical launch -> physical plane (launches are grouped by lamp)
+    int helper_prio = 1;                  // uvrt_set_helper_priority / UVRT_HELPER_PRIO: s_setprio level (0..3) of the short kernels that run
+                                          // beside a traversal grid (uvrt_device.h helper_priority); read at every launch
     bool dedupe = true;                   // uvrt_set_dedupe / UVRT_DEDUPE: a lamp's distinct rays are traced once per batch (uvrt_dedupe.h)
     int64_t b_traced_known = -1;          // uvrt_batch_traced_rays: the last traced batch's rays in chunks traced as they are ...
     int32_t b_traced_chunks = 0;          // ... and its deduped chunks, whose counts are bs[b_set].dd_counts[0, b_traced_chunks)
@@ -288,7 +290,7 @@ inline int flush_pending(uvrt_ctx* c)
     c->pend.valid = false;
     const int l = c->pend.lane;
     launch_accumulate(c->photon_map.as<double>(), c->max_map.as<double>(), c->lanes[l].counts.as<int32_t>(),
-                      c->replicas, c->T, c->pend.time_step, c->T, stream_of(c, l));
+                      c->replicas, c->T, c->pend.time_step, c->T, c->helper_prio, stream_of(c, l));
     HIP_TRY(hipGetLastError());
     return UVRT_OK;
 }

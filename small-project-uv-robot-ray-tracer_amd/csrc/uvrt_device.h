@@ -88,6 +88,21 @@ __device__ __forceinline__ void prepare_record6(const PairRec* __restrict__ pair
     recs[i * 4 + 3] = make_float4(__uint_as_float(r0), __uint_as_float(r1), 0.f, 0.f);
 }
 
+// ---- instruction-issue priority of the short kernels (include/uvrt.h uvrt_set_helper_priority) ----
+// Issue on a SIMD is arbitrated by priority, then age.  A short kernel that runs beside the other lane's persistent traversal
+// grid is the youngest wave on its SIMD, next to seven issue-bound traversal waves at priority 0, and gets the slots they
+// leave.  Called first in such a kernel with the context's setting (a kernel argument, so wave-uniform: s_setprio ignores
+// EXEC and must sit behind a scalar branch), it lets the wave issue when it is ready.  0 leaves the wave as it starts.
+__device__ __forceinline__ void helper_priority(int prio)
+{
+    switch (prio) {
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        case 3: __builtin_amdgcn_s_setprio(3); break;
+        default: break;
+    }
+}
+
 // ------------------------------------------------------------------ RNG, cl/tools.cl:2-4
 
 __device__ __forceinline__ uint32_t wang_hash(uint32_t s)
@@ -155,6 +170,7 @@ struct GenBatchParams {
     int32_t count;
     float lx[MAX_BATCH], ly[MAX_BATCH], lz[MAX_BATCH];       // lamp of physical plane p
     uint32_t seed_prev[MAX_BATCH], seed_next[MAX_BATCH];     // its place in the SEED chain
+    int32_t prio;                      // helper_priority
 };
 
 // The distinct rays of a dedupe group (uvrt_dedupe.h) over the gids [g0, g0 + gn) of all its launches, compacted: the owners'
@@ -173,6 +189,7 @@ struct GenDedupeParams {
     int64_t g0, gn;
     int64_t key_lo, tiles;             // the chunk's key tiles (dedupe_tile_range with DEDUPE_TILE_KEYS)
     float light_length;
+    int32_t prio;                      // helper_priority of the three kernels
 };
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s);
 // its first kernel alone: tmp and the owners per block added to block_counts (a test hook runs it by itself)
@@ -202,6 +219,7 @@ struct ReplayParams {
     const float* area;
     int64_t plane_stride;              // ints between planes of `planes` (= replicas * T)
     int32_t replicas, T, count, is_folded;
+    int32_t prio;                      // helper_priority
     ReplayOp ops[MAX_BATCH];
 };
 
@@ -224,6 +242,7 @@ struct GenParams {
     const uint32_t* prep_perm;
     int32_t prep_npairs;
     uint32_t ray_blocks;   // workgroups [0, ray_blocks) generate rays, the rest prepare records
+    int32_t prio;          // helper_priority
 };
 
 struct ExtendParams {
@@ -272,21 +291,23 @@ struct ExtendParams {
     const uint32_t* n_dev;
 };
 
-// launch wrappers (uvrt_kernels.hip)
+// launch wrappers (uvrt_kernels.hip).  `prio` (a params struct's field, or the argument before the stream) is the
+// helper_priority of the kernels that can run beside a traversal grid: the caller passes the context's helper_prio.
 void launch_generate(const GenParams& p, hipStream_t s);
 void launch_generate_batch(const GenBatchParams& p, hipStream_t s);
 // folded[p][i] = sum over the replicas of plane p, replicas zeroed (the all-reduce payload)
-void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32_t replicas, int32_t T, hipStream_t s);
+void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32_t replicas, int32_t T, int prio, hipStream_t s);
 void launch_replay_batch(const ReplayParams& p, hipStream_t s);
 void launch_add_counts(int32_t* dst, const int32_t* src, int64_t n, hipStream_t s);     // dst[i] += src[i]
 void launch_prepare_launch6(const PairRec* pairs, void* recs, float ox, float oz, int32_t npairs, const uint32_t* perm,
-                            hipStream_t s);
+                            int prio, hipStream_t s);
 void launch_scan_bins(uint32_t* hist, uint32_t* bin_start, int32_t nbins, hipStream_t s);
 void launch_scatter(const float4* rays, const uint2* keyrank, const uint32_t* bin_start,
                     float4* sorted, uint32_t* order, int64_t n, hipStream_t s);
 // extend (uvrt_extend6.hip): code bits 0-1 = leaf period - 1, bit 2 = no LDS top cache; returns false
-// (nothing launched) when the grid would not fit the overflow-stack buffer
-bool launch_extend6(const ExtendParams& p, int code, int grid_per_cu, hipStream_t s);
+// (nothing launched) when the grid would not fit the overflow-stack buffer.  prep_prio: the helper_priority of the
+// k_prepare_launch6 it runs first where the records are not prepared (the traversal itself takes none)
+bool launch_extend6(const ExtendParams& p, int code, int grid_per_cu, int prep_prio, hipStream_t s);
 // the opt-in 4-wide traversal (uvrt_extend4.hip)
 bool launch_extend4(const ExtendParams& p, int grid_per_cu, hipStream_t s);
 void launch_prepare_launch4(const QuadRec* quads, void* recs4, float ox, float oz, int32_t nquads, hipStream_t s);
@@ -313,19 +334,19 @@ void launch_hot_setup(const HotSetupParams& p, hipStream_t s);
 void launch_prepare_leaves6(const LeafTri* ltris, void* recs, int32_t npairs, int32_t T, hipStream_t s);
 constexpr uint64_t OVF_MAX_ENTRIES = (uint64_t)256 * 16 * 256 * 24;   // largest grid x deepest overflow
 void launch_accumulate(double* photon_map, double* max_map, int32_t* counts, int32_t replicas,
-                       int64_t stride, float time_step, int32_t T, hipStream_t s);
+                       int64_t stride, float time_step, int32_t T, int prio, hipStream_t s);
 void launch_reset(double* photon_map, double* max_map, int32_t* counts, int32_t replicas,
-                  int64_t stride, float* color, int32_t reset_color, int32_t T, hipStream_t s);
+                  int64_t stride, float* color, int32_t reset_color, int32_t T, int prio, hipStream_t s);
 void launch_fold_counts(int32_t* counts, int32_t replicas, int64_t stride, int32_t T, hipStream_t s);
 void launch_compute_dosage(const double* map, float* dosage, const float* area,
                            int32_t photons_per_light, float scaled_power, int32_t T,
                            hipStream_t s);
 void launch_shade(const double* map, float* dosage, const float* area, float* color, int32_t photons_per_light,
-                  float scaled_power, float min_value, int32_t threshold_view, int32_t T, hipStream_t s);
+                  float scaled_power, float min_value, int32_t threshold_view, int32_t T, int prio, hipStream_t s);
 void launch_accumulate_shade(double* photon_map, double* max_map, int32_t* counts, int32_t replicas, int64_t stride,
                              float time_step, float* dosage, const float* area, float* color, int32_t which_map,
                              int32_t photons_per_light, float scaled_power, float min_value, int32_t threshold_view,
-                             int32_t T, hipStream_t s);
+                             int32_t T, int prio, hipStream_t s);
 void launch_dosage_to_color(const float* dosage, float* color, float min_value,
                             int32_t threshold_view, int32_t T, hipStream_t s);
 void launch_prepare_scene(const float4* tris64, const uint32_t* tri_idx, LeafTri* ltris,
@@ -349,6 +370,7 @@ struct SweepParams {
     float light_length;
     int64_t first_gid, n;
     uint32_t seed_prev, seed_next;
+    int32_t prio;            // helper_priority
 };
 // The scene's free records, made once per scene: pair record i in the layout of prepare_record6 with the RAW bounds (a
 // ray subtracts its own origin) in breadth-first order, leaf references re-based; the leaf records follow at [npairs, npairs + T).
@@ -369,6 +391,7 @@ struct SweepBatchParams {
     float fx[MAX_BATCH], fy[MAX_BATCH], fz[MAX_BATCH];       // `from` of physical plane p
     float tx[MAX_BATCH], ty[MAX_BATCH], tz[MAX_BATCH];       // `to`
     uint32_t seed_prev[MAX_BATCH], seed_next[MAX_BATCH];     // its place in the SEED chain
+    int32_t prio;                      // helper_priority
 };
 void launch_generate_sweep_batch(const SweepBatchParams& p, hipStream_t s);
 // the free-origin traversal over the planes of a batch: e.plane_batches / plane_n / plane_stride as launch_extend6 takes

@@ -685,8 +685,9 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
 //   w2 = {c0 miny, c0 maxy, c1 miny, c1 maxy} (raw), w3 = {ref0, ref1, 0, 0}
 __global__ __launch_bounds__(256) void k_prepare_launch6(const PairRec* __restrict__ pairs,
                                                          float4* __restrict__ recs, float ox, float oz,
-                                                         int32_t npairs, const uint32_t* __restrict__ perm)
+                                                         int32_t npairs, const uint32_t* __restrict__ perm, int prio)
 {
+    helper_priority(prio);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= npairs) return;
     prepare_record6(pairs, recs, ox, oz, npairs, i, perm);
@@ -707,11 +708,11 @@ __global__ __launch_bounds__(256) void k_prepare_leaves6(const LeafTri* __restri
 }
 
 void launch_prepare_launch6(const PairRec* pairs, void* recs, float ox, float oz, int32_t npairs, const uint32_t* perm,
-                            hipStream_t s)
+                            int prio, hipStream_t s)
 {
     if (npairs <= 0) return;
     hipLaunchKernelGGL(k_prepare_launch6, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, s, pairs, (float4*)recs,
-                       ox, oz, npairs, perm);
+                       ox, oz, npairs, perm, prio);
 }
 
 void launch_prepare_leaves6(const LeafTri* ltris, void* recs, int32_t npairs, int32_t T, hipStream_t s)
@@ -743,7 +744,7 @@ bool launch_extend6_dedupe(const ExtendParams& p0, int code, int grid_per_cu, hi
 }
 
 // code: bits 0-1 leaf period - 1 (0..3), bit 2 = WITHOUT the top-of-tree cache (codes other than 1: developer build only)
-bool launch_extend6(const ExtendParams& p0, int code, int grid_per_cu, hipStream_t s)
+bool launch_extend6(const ExtendParams& p0, int code, int grid_per_cu, int prep_prio, hipStream_t s)
 {
     if (p0.n <= 0) return true;
     ExtendParams p = p0;
@@ -755,7 +756,7 @@ bool launch_extend6(const ExtendParams& p0, int code, int grid_per_cu, hipStream
     if (p.perm) p.top_pairs = (uint32_t)p.npairs;   // the hot prefix: as many records as the cache holds
     if (p.npairs > 0 && !p.recs_prepared)
         hipLaunchKernelGGL(k_prepare_launch6, dim3((unsigned)((p.npairs + 255) / 256)), dim3(256), 0, s,
-                           p.scene.pairs, (float4*)p.recs, p.ox, p.oz, p.npairs, p.perm);
+                           p.scene.pairs, (float4*)p.recs, p.ox, p.oz, p.npairs, p.perm, prep_prio);
 #define UVRT_L6K(LP, REC, TOP, FL) hipLaunchKernelGGL((k_extend6<LP, REC, TOP, FL>), dim3(grid), dim3(256), 0, s, p)
 #define UVRT_L6(LP, TOP)                                                                             \
     do {                                                                                             \

@@ -170,6 +170,7 @@ bool launch_extend_free_planes(const FreeParams& p0, int grid_per_cu, hipStream_
 // orig = generate's origin + u (to - from), each component fl(a + fl(u * fl(b - a))) (this file is built without contraction)
 __global__ __launch_bounds__(256) void k_generate_sweep(SweepParams p)
 {
+    helper_priority(p.prio);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= p.n) return;
     float r0;
@@ -192,6 +193,7 @@ void launch_generate_sweep(const SweepParams& p, hipStream_t s)
 // k_generate_sweep for the sweeps of a batch: blockIdx.y is the plane, the arithmetic is the same
 __global__ __launch_bounds__(256) void k_generate_sweep_batch(SweepBatchParams p)
 {
+    helper_priority(p.prio);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= p.n) return;
     const int k = blockIdx.y;

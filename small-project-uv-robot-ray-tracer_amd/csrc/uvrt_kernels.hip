@@ -34,6 +34,7 @@ __device__ __forceinline__ uint32_t coherence_key(uint32_t qphi, uint32_t qy, ui
 
 __global__ __launch_bounds__(256) void k_generate(GenParams p)
 {
+    helper_priority(p.prio);
     if (blockIdx.x >= p.ray_blocks) {   // extra workgroups: extend v6's per-launch node-pair records
         const int j = (int)(blockIdx.x - p.ray_blocks) * 256 + threadIdx.x;
         if (j < p.prep_npairs) prepare_record6(p.prep_pairs, p.prep_recs, p.lx, p.lz, p.prep_npairs, j, p.prep_perm);
@@ -68,6 +69,7 @@ __global__ __launch_bounds__(256) void k_generate(GenParams p)
 // generates the same global-id range under its own lamp and place in the SEED chain.
 __global__ __launch_bounds__(256) void k_generate_batch(GenBatchParams p)
 {
+    helper_priority(p.prio);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= p.n) return;
     const int k = blockIdx.y;
@@ -88,6 +90,7 @@ __global__ __launch_bounds__(256) void k_generate_batch(GenBatchParams p)
 // leaves it so).  16 KB of LDS: the kernel finds room on a CU beside the other lane's persistent traversal grid.
 __global__ __launch_bounds__(256) void k_dedupe_mark(GenDedupeParams p)
 {
+    helper_priority(p.prio);
     constexpr int32_t W = DEDUPE_TILE_KEYS;
     __shared__ uint32_t s_table[W];
     __shared__ int32_t s_run[DEDUPE_MAX][2];
@@ -150,8 +153,9 @@ __global__ __launch_bounds__(256) void k_dedupe_mark(GenDedupeParams p)
 
 // scan: the workgroups' counts -> their first slot in the compacted list, in (launch, gid) order; the total.  One workgroup
 // of 256 threads: it must find room on a CU beside the persistent traversal grid of the other lane, as every kernel here.
-__global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uint32_t* total, uint32_t nblocks)
+__global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uint32_t* total, uint32_t nblocks, int prio)
 {
+    helper_priority(prio);
     __shared__ uint32_t s_part[256];
     const uint32_t tid = threadIdx.x;
     const uint32_t per = (nblocks + 255u) / 256u;
@@ -178,6 +182,7 @@ __global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uin
 // write: the owners' rays (generate.cl:11-37) and masks at their slots, in (launch, gid) order
 __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
 {
+    helper_priority(p.prio);
     __shared__ uint32_t s_cnt[DD_ROUNDS][4];
     const int k = blockIdx.y;
     const uint32_t wv = threadIdx.x >> 6;
@@ -261,8 +266,9 @@ __global__ __launch_bounds__(256) void k_scatter(const float4* __restrict__ rays
 __global__ __launch_bounds__(256) void k_accumulate(double* __restrict__ photon_map,
                                                     double* __restrict__ max_map,
                                                     int32_t* __restrict__ counts, int32_t replicas,
-                                                    int64_t stride, float time_step, int32_t T)
+                                                    int64_t stride, float time_step, int32_t T, int prio)
 {
+    helper_priority(prio);
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int i = g >> 2, part = g & 3;
     int32_t total = 0;
@@ -321,8 +327,9 @@ __device__ __forceinline__ void heatmap(float intensity, float& r, float& g, flo
 // Batched tracing: per plane the (exact, integer) sum of its deposit replicas -- the int32 payload of the one
 // all-reduce of a ray-range-sharded computation -- and the replicas zeroed for the next batch.
 __global__ __launch_bounds__(256) void k_fold_planes(int32_t* __restrict__ planes, int32_t* __restrict__ folded,
-                                                     int32_t replicas, int32_t T)
+                                                     int32_t replicas, int32_t T, int prio)
 {
+    helper_priority(prio);
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int i = g >> 2, part = g & 3;
     int32_t* pl = planes + (int64_t)blockIdx.y * replicas * T;
@@ -344,6 +351,7 @@ __global__ __launch_bounds__(256) void k_fold_planes(int32_t* __restrict__ plane
 // dosageToColor with that Shade's arguments.  The planes are left zeroed.
 __global__ __launch_bounds__(256) void k_replay_batch(ReplayParams p)
 {
+    helper_priority(p.prio);
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int i = g >> 2, part = g & 3;
     const bool in = i < p.T;
@@ -403,8 +411,9 @@ __global__ __launch_bounds__(256) void k_reset(double* __restrict__ photon_map,
                                                double* __restrict__ max_map,
                                                int32_t* __restrict__ counts, int32_t replicas,
                                                int64_t stride, float* __restrict__ color,
-                                               int32_t reset_color, int32_t T)
+                                               int32_t reset_color, int32_t T, int prio)
 {
+    helper_priority(prio);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= T) return;
     photon_map[i] = 0;
@@ -504,8 +513,9 @@ __device__ __forceinline__ void shade_one(int i, double map_value, float* __rest
 __global__ __launch_bounds__(256) void k_shade(const double* __restrict__ map, float* __restrict__ dosage,
                                                const float* __restrict__ area, float* __restrict__ color,
                                                int32_t photons_per_light, float scaled_power,
-                                               float min_value, int32_t threshold_view, int32_t T)
+                                               float min_value, int32_t threshold_view, int32_t T, int prio)
 {
+    helper_priority(prio);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= T) return;
     shade_one(i, map[i], dosage, area, color, photons_per_light, scaled_power, min_value, threshold_view);
@@ -519,8 +529,9 @@ __global__ __launch_bounds__(256) void k_accumulate_shade(double* __restrict__ p
                                                           float time_step, float* __restrict__ dosage,
                                                           const float* __restrict__ area, float* __restrict__ color,
                                                           int32_t which_map, int32_t photons_per_light, float scaled_power,
-                                                          float min_value, int32_t threshold_view, int32_t T)
+                                                          float min_value, int32_t threshold_view, int32_t T, int prio)
 {
+    helper_priority(prio);
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int i = g >> 2, part = g & 3;
     int32_t total = 0;
@@ -610,15 +621,15 @@ void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s)
     if (p.gn <= 0 || p.g.count <= 0) return;
     const dim3 grid(blocks_for(p.gn, DD_SLOTS), (unsigned)p.g.count);
     launch_dedupe_mark(p, s);
-    hipLaunchKernelGGL(k_dedupe_scan, dim3(1), dim3(256), 0, s, p.block_counts, p.total, grid.x * grid.y);
+    hipLaunchKernelGGL(k_dedupe_scan, dim3(1), dim3(256), 0, s, p.block_counts, p.total, grid.x * grid.y, (int)p.prio);
     hipLaunchKernelGGL(k_dedupe_write, grid, dim3(256), 0, s, p);
 }
 
-void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32_t replicas, int32_t T, hipStream_t s)
+void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32_t replicas, int32_t T, int prio, hipStream_t s)
 {
     if (nplanes <= 0 || T <= 0) return;
     hipLaunchKernelGGL(k_fold_planes, dim3(blocks_for((int64_t)T * 4, 256), (unsigned)nplanes), dim3(256), 0, s, planes,
-                       folded, replicas, T);
+                       folded, replicas, T, prio);
 }
 
 void launch_replay_batch(const ReplayParams& p, hipStream_t s)
@@ -647,11 +658,11 @@ void launch_scatter(const float4* rays, const uint2* keyrank, const uint32_t* bi
 }
 
 void launch_accumulate(double* photon_map, double* max_map, int32_t* counts, int32_t replicas,
-                       int64_t stride, float time_step, int32_t T, hipStream_t s)
+                       int64_t stride, float time_step, int32_t T, int prio, hipStream_t s)
 {
     if (T <= 0) return;
     hipLaunchKernelGGL(k_accumulate, dim3(blocks_for((int64_t)T * 4, 256)), dim3(256), 0, s, photon_map,
-                       max_map, counts, replicas, stride, time_step, T);
+                       max_map, counts, replicas, stride, time_step, T, prio);
 }
 
 void launch_fold_counts(int32_t* counts, int32_t replicas, int64_t stride, int32_t T, hipStream_t s)
@@ -662,11 +673,11 @@ void launch_fold_counts(int32_t* counts, int32_t replicas, int64_t stride, int32
 }
 
 void launch_reset(double* photon_map, double* max_map, int32_t* counts, int32_t replicas,
-                  int64_t stride, float* color, int32_t reset_color, int32_t T, hipStream_t s)
+                  int64_t stride, float* color, int32_t reset_color, int32_t T, int prio, hipStream_t s)
 {
     if (T <= 0) return;
     hipLaunchKernelGGL(k_reset, dim3(blocks_for(T, 256)), dim3(256), 0, s, photon_map, max_map,
-                       counts, replicas, stride, color, reset_color, T);
+                       counts, replicas, stride, color, reset_color, T, prio);
 }
 
 void launch_compute_dosage(const double* map, float* dosage, const float* area,
@@ -679,22 +690,22 @@ void launch_compute_dosage(const double* map, float* dosage, const float* area,
 }
 
 void launch_shade(const double* map, float* dosage, const float* area, float* color, int32_t photons_per_light,
-                  float scaled_power, float min_value, int32_t threshold_view, int32_t T, hipStream_t s)
+                  float scaled_power, float min_value, int32_t threshold_view, int32_t T, int prio, hipStream_t s)
 {
     if (T <= 0) return;
     hipLaunchKernelGGL(k_shade, dim3(blocks_for(T, 256)), dim3(256), 0, s, map, dosage, area, color,
-                       photons_per_light, scaled_power, min_value, threshold_view, T);
+                       photons_per_light, scaled_power, min_value, threshold_view, T, prio);
 }
 
 void launch_accumulate_shade(double* photon_map, double* max_map, int32_t* counts, int32_t replicas, int64_t stride,
                              float time_step, float* dosage, const float* area, float* color, int32_t which_map,
                              int32_t photons_per_light, float scaled_power, float min_value, int32_t threshold_view,
-                             int32_t T, hipStream_t s)
+                             int32_t T, int prio, hipStream_t s)
 {
     if (T <= 0) return;
     hipLaunchKernelGGL(k_accumulate_shade, dim3(blocks_for((int64_t)T * 4, 256)), dim3(256), 0, s, photon_map, max_map, counts,
                        replicas, stride, time_step, dosage, area, color, which_map, photons_per_light, scaled_power, min_value,
-                       threshold_view, T);
+                       threshold_view, T, prio);
 }
 
 void launch_dosage_to_color(const float* dosage, float* color, float min_value,
