@@ -301,6 +301,29 @@ int uvrt_read_batch_counts(uvrt_ctx* ctx, int32_t launch, int32_t* out, int32_t 
  * uvrt_set_dedupe(ctx, 0) switches it off for later batches; the default is on, or what the environment variable
  * UVRT_DEDUPE (0 / 1) says when the context is created. */
 int uvrt_set_dedupe(uvrt_ctx* ctx, int32_t on);
+/* Mask classes: one deposit per traced ray.  A traced ray of a dedupe group deposits its hit once per launch that holds it,
+ * and a group's rays hold few distinct sets of launches.  With classes each of the group's most frequent sets of two and more
+ * launches gets a count plane of its own behind the launch planes of the batch: a ray of that set deposits there once, and
+ * the fold / replay adds a class plane into every launch of its set.  The per-launch totals are the same integers, so planes,
+ * maps, dose and colours do not change by a bit.  The class list is found on the host from a fixed sample of the call's range
+ * (a function of the lamp, the SEEDs, the range and the seed mode alone); a ray whose set has no class deposits per launch as
+ * before.  Groups of 31 launches take no classes.
+ * uvrt_set_dedupe_classes(ctx, max_classes): classes per group at most, 0..32; 0 deposits per launch throughout.  Takes effect
+ * with the next batch; the default is uvrt_dedupe_classes_default(), or what the environment variable UVRT_DEDUPE_CLASSES says
+ * when the context is created.  A value outside 0..32: UVRT_ERR_INVALID, the setting unchanged. */
+int uvrt_set_dedupe_classes(uvrt_ctx* ctx, int32_t max_classes);
+int uvrt_get_dedupe_classes(uvrt_ctx* ctx, int32_t* max_classes);
+int32_t uvrt_dedupe_classes_default(void);
+/* test hook: the atomic adds the traced rays of the last batch's dedupe groups issue if each of them hits -- one for a ray
+ * that deposits in one plane (its launch's own or a class plane), one per launch for any other (waits for the batch) */
+int uvrt_batch_deposits(uvrt_ctx* ctx, int64_t* out);
+/* test hook, host only: the class list a batch gives the dedupe group of uvrt_dedupe_plan's arguments when it may take up to
+ * max_classes classes and shares its class planes with no other group -- class_masks[0, *class_count), most frequent first,
+ * room for 32 -- and, where `deposits` is not null, the group's uvrt_batch_deposits figure with that list (max_classes 0 or a
+ * group of 31 launches: no classes, one deposit per occurrence). */
+int uvrt_dedupe_classes(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                        int32_t seed_mode, int64_t first_gid, int64_t n, int32_t max_classes, uint32_t* class_masks,
+                        int32_t* class_count, int64_t* deposits);
 /* Developer knob: the instruction-issue priority (s_setprio level, 0..3) of the short kernels that run beside another launch
  * lane's persistent traversal grid -- generate, the dedupe passes, fold, replay, accumulate, Shade, reset, the per-launch
  * records.  Such a kernel's waves are the youngest on their SIMD and at level 0 issue only in the slots the traversal's waves

@@ -54,6 +54,11 @@ SYMBOLS = [
     ("uvrt_set_helper_priority", C.c_int, [_vp, _i32]),
     ("uvrt_get_helper_priority", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_batch_traced_rays", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("uvrt_set_dedupe_classes", C.c_int, [_vp, _i32]),
+    ("uvrt_get_dedupe_classes", C.c_int, [_vp, C.POINTER(_i32)]),
+    ("uvrt_dedupe_classes_default", _i32, []),
+    ("uvrt_batch_deposits", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("uvrt_dedupe_classes", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _vp, C.POINTER(_i32), C.POINTER(_i64)]),
     ("uvrt_seed_input", _u32, [_i64, _fp, _u32, _u32, _i32]),
     ("uvrt_dedupe_plan", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
     ("uvrt_dedupe_plan_tiled", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i64, _i64, _vp]),
@@ -255,6 +260,29 @@ def dedupe_plan(lamp, seed_prev, seed_next_, seed_mode, first_gid, n):
     return out
 
 
+def dedupe_classes_default():
+    """the class maximum a new context starts with (include/uvrt.h uvrt_set_dedupe_classes; host only)"""
+    return int(lib().uvrt_dedupe_classes_default())
+
+
+def dedupe_classes(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, max_classes=None):
+    """The mask classes a batch gives the dedupe group of dedupe_plan's arguments (include/uvrt.h uvrt_dedupe_classes; host
+    only): (uint32 class masks, most frequent first; the group's uvrt_batch_deposits figure with them)."""
+    sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
+    sn = np.ascontiguousarray(seed_next_, dtype=np.uint32)
+    assert sp.size == sn.size
+    max_classes = dedupe_classes_default() if max_classes is None else max_classes
+    out = np.zeros(DEDUPE_CLASS_MAX, dtype=np.uint32)
+    nc, dep = _i32(), _i64()
+    rc = lib().uvrt_dedupe_classes(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n),
+                                   int(max_classes), _ptr(out), C.byref(nc), C.byref(dep))
+    if rc != 0:
+        raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
+    return out[:int(nc.value)].copy(), int(dep.value)
+
+
+DEDUPE_CLASS_MAX = 32        # classes per dedupe group at most (csrc/uvrt_dedupe.h)
+DEDUPE_CLASS_LAUNCHES = 30   # launches of a group that may take classes
 DEDUPE_TILE_KEYS = 3840      # the device's tile (csrc/uvrt_dedupe.h)
 DEDUPE_BLOCK_GIDS = 2048     # gids per owner count of a chunk (csrc/uvrt_device.h DD_SLOTS)
 
@@ -523,6 +551,21 @@ class Ctx:
         m = _i32()
         self._ck(self._L.uvrt_get_helper_priority(self._h, C.byref(m)))
         return int(m.value)
+
+    def set_dedupe_classes(self, max_classes):
+        """mask classes per dedupe group at most, 0 = one deposit per launch (include/uvrt.h uvrt_set_dedupe_classes)"""
+        self._ck(self._L.uvrt_set_dedupe_classes(self._h, int(max_classes)))
+
+    def get_dedupe_classes(self):
+        m = _i32()
+        self._ck(self._L.uvrt_get_dedupe_classes(self._h, C.byref(m)))
+        return int(m.value)
+
+    def batch_deposits(self):
+        """atomic adds the traced rays of the last batch's dedupe groups issue when each of them hits"""
+        out = _i64()
+        self._ck(self._L.uvrt_batch_deposits(self._h, C.byref(out)))
+        return int(out.value)
 
     def batch_traced_rays(self):
         """rays the traversal kernel was given for the stops of the last traced batch"""

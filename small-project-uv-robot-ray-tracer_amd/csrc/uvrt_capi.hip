@@ -114,6 +114,9 @@ int uvrt_create(int device_id, uvrt_ctx** out)
 #endif
     if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
     if (const char* e = getenv("UVRT_DEDUPE")) c->dedupe = atoi(e) != 0;                 // uvrt_set_dedupe's default
+    if (const char* e = getenv("UVRT_DEDUPE_CLASSES")) { const int v = atoi(e); if (v >= 0 && v <= DEDUPE_CLASS_MAX) c->dedupe_classes = v; }   // uvrt_set_dedupe_classes' default
+    if (const char* e = getenv("UVRT_DEDUPE_CLASS_REPLICAS")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->dedupe_class_replicas = v; }
+    if (const char* e = getenv("UVRT_DEDUPE_CLASS_MB")) { const long v = atol(e); if (v > 0 && v <= 4096) c->dedupe_class_bytes = (size_t)v << 20; }
     if (const char* e = getenv("UVRT_HELPER_PRIO")) { const int v = atoi(e); if (v >= 0 && v <= 3) c->helper_prio = v; }   // uvrt_set_helper_priority's default
     if (const char* e = getenv("UVRT_BATCH_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL - 1) c->batch_lanes = v; }
     if (const char* e = getenv("UVRT_COMM_RESERVE_CUS")) { const int v = atoi(e); if (v >= 0 && v <= 64 && v % 8 == 0) c->comm_reserve_knob = v; }
@@ -586,6 +589,21 @@ int uvrt_set_dedupe(uvrt_ctx* c, int32_t on)
 {
     if (!c) return fail(UVRT_ERR_INVALID, "null context");
     c->dedupe = on != 0;
+    return UVRT_OK;
+}
+
+int uvrt_set_dedupe_classes(uvrt_ctx* c, int32_t max_classes)
+{
+    if (!c || max_classes < 0 || max_classes > DEDUPE_CLASS_MAX)
+        return fail(UVRT_ERR_INVALID, "uvrt_set_dedupe_classes: the maximum must be 0..%d", DEDUPE_CLASS_MAX);
+    c->dedupe_classes = max_classes;
+    return UVRT_OK;
+}
+
+int uvrt_get_dedupe_classes(uvrt_ctx* c, int32_t* max_classes)
+{
+    if (!c || !max_classes) return fail(UVRT_ERR_INVALID, "uvrt_get_dedupe_classes: null argument");
+    *max_classes = c->dedupe_classes;
     return UVRT_OK;
 }
 

@@ -94,7 +94,11 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     // dedupe_group_ok, uvrt_set_dedupe(0), a kernel variant other than the default's code (the deduped kernel exists for leaf
     // period 2 with the LDS cache only), the developer build's skip-generate probe.  A longer column is split evenly (33
     // launches: 17 + 16).
-    struct Piece { int g, k0, kc; bool dd; int64_t chunk_gids; DedupeGroup G; };
+    struct Piece {
+        int g, k0, kc; bool dd; int64_t chunk_gids; DedupeGroup G;
+        DedupeTally cand[DEDUPE_CLASS_MAX]; int ncand; double keys;       // its owners' multi-bit masks by sampled frequency
+        int ncls, cls_base; DedupeClasses cls;                            // the classes it gets, from class plane cls_base on
+    };
     std::vector<Piece> pieces;
     size_t dd_chunks = 0, dd_tmp_bytes = 0, dd_block_bytes = 0;
     bool may_dedupe = c->dedupe && variant_code6(c->variant) == 1;
@@ -144,15 +148,53 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     const size_t plane_ints = (size_t)R * (size_t)c->T;
     // full planes are allocated for the context's replica count: R only shrinks the part of it that is used
     const size_t plane_alloc = (size_t)c->replicas * (size_t)c->T;
+    // The mask classes of the dedupe groups (uvrt_dedupe.h "mask classes"): every group's candidates from a sample of its key
+    // tiles -- a function of the group alone, found here on the host with no word from the device -- and the class planes of
+    // the set dealt to the groups by sampled frequency, most frequent first.  The planes sit behind the launch planes, at
+    // most class_cap of them: the set's byte budget, one bit each in ReplayParams::class_of, every offset below 2^32.
+    const bool classes_on = c->dedupe_classes > 0 && dd_chunks > 0;
+    int class_cap = 0, total_cls = 0;
+    const int cls_repl = std::max(1, std::min(c->dedupe_class_replicas, R));
+    if (classes_on) {
+        const uint64_t room = (((uint64_t)1 << 32) - 1) / (uint64_t)plane_ints;
+        class_cap = (int)std::min<uint64_t>({(uint64_t)MAX_CLASS_PLANES, (uint64_t)(c->dedupe_class_bytes / (plane_ints * 4)),
+                                             room > (uint64_t)count ? room - (uint64_t)count : 0});
+        std::vector<uint32_t> table((size_t)DEDUPE_TILE_KEYS);
+        for (Piece& pc : pieces)
+            if (pc.dd && pc.kc <= DEDUPE_CLASS_LAUNCHES)
+                pc.ncand = dedupe_class_tally(pc.G, table.data(), pc.cand, c->dedupe_classes, &pc.keys);
+        while (total_cls < class_cap) {
+            Piece* best = nullptr;
+            double best_f = 0.0;
+            for (Piece& pc : pieces) {
+                if (pc.ncls >= pc.ncand) continue;
+                const double f = pc.cand[pc.ncls].n / pc.keys;
+                if (f > best_f) { best_f = f; best = &pc; }
+            }
+            if (!best) break;
+            ++best->ncls;
+            ++total_cls;
+        }
+        int base = 0;
+        for (Piece& pc : pieces) {
+            uint32_t masks[DEDUPE_CLASS_MAX];
+            for (int i = 0; i < pc.ncls; ++i) masks[i] = pc.cand[i].mask;
+            pc.cls_base = base;
+            // (a class plane's index counts from the group's first launch plane, as a launch's does)
+            dedupe_classes_fill(pc.cls, masks, pc.ncls, (uint32_t)(count - (gfirst[pc.g] + pc.k0) + base));
+            base += pc.ncls;
+        }
+    }
+    const size_t planes_bytes = (size_t)count * plane_alloc * 4 + (size_t)class_cap * plane_ints * 4;
     // growing a buffer needs the device idle (hipFree / hipMalloc); new per-launch records only need the context's stream
     // ordered after the lanes' earlier work -- no host synchronisation, so a new lamp position costs its kernels only
     bool dd_scratch_short = false;      // (every lane a chunk may run on: 0 without pipelining, else 1..batch_lanes)
     for (int l = 0; l <= c->batch_lanes; ++l)
         dd_scratch_short = dd_scratch_short || c->lanes[l].dd_tmp.bytes < dd_tmp_bytes || c->lanes[l].dd_blocks.bytes < dd_block_bytes;
-    const bool need_alloc = S.rays.bytes < (size_t)count * (size_t)n_pad * 16 || S.planes.bytes < (size_t)count * plane_alloc * 4 ||
+    const bool need_alloc = S.rays.bytes < (size_t)count * (size_t)n_pad * 16 || S.planes.bytes < planes_bytes ||
                             S.folded.bytes < (size_t)count * (size_t)c->T * 4 || (int)c->b_recs.size() < ngroups || !S.free_ev ||
                             S.oxz.bytes < (size_t)nsweeps * (size_t)n_pad * 8 || (nsweeps > 0 && !c->free_recs_valid) ||
-                            (dd_chunks > 0 && (S.masks.bytes < (size_t)count * (size_t)n_pad * 4 || S.dd_counts.bytes < dd_chunks * 4 ||
+                            (dd_chunks > 0 && (S.masks.bytes < (size_t)count * (size_t)n_pad * 4 || S.dd_counts.bytes < dd_chunks * 8 ||
                                                dd_scratch_short));
     bool recs_stale = false;
     const uint32_t* gperm[MAX_BATCH] = {};
@@ -189,9 +231,9 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     if (need_alloc) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (!S.free_ev) HIP_TRY(hipEventCreateWithFlags(&S.free_ev, hipEventDisableTiming));
-        const bool grown = S.planes.bytes < (size_t)count * plane_alloc * 4 || S.folded.bytes < (size_t)count * (size_t)c->T * 4;
+        const bool grown = S.planes.bytes < planes_bytes || S.folded.bytes < (size_t)count * (size_t)c->T * 4;
         if ((rc = S.rays.ensure((size_t)count * (size_t)n_pad * 16, false, c->stream))) return rc;
-        if ((rc = S.planes.ensure((size_t)count * plane_alloc * 4, true, c->stream))) return rc;
+        if ((rc = S.planes.ensure(planes_bytes, true, c->stream))) return rc;
         if ((rc = S.folded.ensure((size_t)count * (size_t)c->T * 4, true, c->stream))) return rc;
         if ((rc = S.oxz.ensure((size_t)nsweeps * (size_t)n_pad * 8, false, c->stream))) return rc;      // (8 B of origin per photon of a sweep)
         if (grown) HIP_TRY(hipEventRecord(S.free_ev, c->stream));      // the zero fill is the set's "last replay"
@@ -206,8 +248,9 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             if ((rc = c->lanes[l].ovf.ensure(side_ovf_bytes(c), false, c->stream))) return rc;
         if (dd_chunks > 0) {      // the deduped chunks' masks and counts, and every lane's scratch between the generate passes
             if ((rc = S.masks.ensure((size_t)count * (size_t)n_pad * 4, false, c->stream))) return rc;
-            // (not zeroed: a chunk's generate runs on its lane BEFORE the lane waits for this stream, and writes its count)
-            if ((rc = S.dd_counts.ensure(dd_chunks * 4, false, c->stream))) return rc;
+            // (not zeroed: a chunk's generate runs on its lane BEFORE the lane waits for this stream, and writes its count;
+            //  the chunks' ray counts first, their deposit counts behind them)
+            if ((rc = S.dd_counts.ensure(dd_chunks * 8, false, c->stream))) return rc;
             // (dd_blocks zeroed: k_dedupe_mark adds its owners to it and k_dedupe_write leaves it zero again.  A chunk's generate
             //  does not wait for this stream, so the zero fill is waited for here, where a buffer has grown)
             for (int l = 0; l <= c->batch_lanes; ++l) {
@@ -287,7 +330,9 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
                 dq.g = pc.G;
                 dq.rays = S.rays.as<float4>() + at;
                 dq.masks = S.masks.as<uint32_t>() + at;
-                dq.total = S.dd_counts.as<uint32_t>() + dd_used++;
+                dq.total = S.dd_counts.as<uint32_t>() + dd_used;
+                dq.deposits = S.dd_counts.as<uint32_t>() + dd_chunks + dd_used++;
+                dq.cls = pc.cls;
                 dq.tmp = cur_lane(c).dd_tmp.as<uint32_t>();
                 dq.block_counts = cur_lane(c).dd_blocks.as<uint32_t>();
                 dq.g0 = first_gid + g0;
@@ -307,6 +352,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
                 p.count_stride = c->T;
                 p.n = (int64_t)pc.kc * gn;
                 p.plane_stride = (uint32_t)plane_ints;
+                p.cls_replicas = pc.cls.count > 0 ? cls_repl : 0;      // (0: the chunk's words are its masks)
                 p.recs = c->b_recs[g].p;
                 p.perm = gperm[g];
                 p.recs_prepared = 1;
@@ -402,6 +448,10 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
     c->b_is_folded = false;
     c->b_traced_known = traced;
     c->b_traced_chunks = (int32_t)dd_used;
+    c->b_ncls = total_cls;
+    c->b_cls_repl = cls_repl;
+    for (const Piece& pc : pieces)
+        for (int i = 0; i < pc.ncls; ++i) c->b_cls_launches[pc.cls_base + i] = (uint64_t)pc.cls.mask[i] << (gfirst[pc.g] + pc.k0);
     memcpy(c->b_phys, phys, sizeof(int32_t) * (size_t)count);
     return UVRT_OK;
 }
@@ -437,6 +487,20 @@ int uvrt_batch_traced_rays(uvrt_ctx* c, int64_t* out)
         std::vector<uint32_t> counts((size_t)c->b_traced_chunks);
         if (int rc = range_copy(c, c->bs[c->b_set].dd_counts.p, 4, counts.data(), 0, c->b_traced_chunks, hipMemcpyDeviceToHost)) return rc;
         for (uint32_t v : counts) total += v;
+    }
+    *out = total;
+    return UVRT_OK;
+}
+
+int uvrt_batch_deposits(uvrt_ctx* c, int64_t* out)
+{
+    if (!c || !out) return fail(UVRT_ERR_INVALID, "uvrt_batch_deposits: null argument");
+    if (c->b_traced_known < 0) return fail(UVRT_ERR_INVALID, "uvrt_batch_deposits: no batch has been traced");
+    int64_t total = 0;
+    if (c->b_traced_chunks > 0) {      // (the deposit counts follow the ray counts)
+        std::vector<uint32_t> counts(2 * (size_t)c->b_traced_chunks);
+        if (int rc = range_copy(c, c->bs[c->b_set].dd_counts.p, 4, counts.data(), 0, 2 * c->b_traced_chunks, hipMemcpyDeviceToHost)) return rc;
+        for (int32_t i = 0; i < c->b_traced_chunks; ++i) total += counts[(size_t)c->b_traced_chunks + (size_t)i];
     }
     *out = total;
     return UVRT_OK;
@@ -498,6 +562,31 @@ int uvrt_dedupe_plan_tiled(const float lamp[3], int32_t count, const uint32_t* s
     return UVRT_OK;
 }
 
+int32_t uvrt_dedupe_classes_default(void) { return DEDUPE_CLASSES_DEFAULT; }
+
+int uvrt_dedupe_classes(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next, int32_t seed_mode,
+                        int64_t first_gid, int64_t n, int32_t max_classes, uint32_t* class_masks, int32_t* class_count,
+                        int64_t* deposits)
+{
+    DedupeGroup G;
+    if (int rc = hook_group(G, "uvrt_dedupe_classes", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
+    if (!class_masks || !class_count || max_classes < 0 || max_classes > DEDUPE_CLASS_MAX)
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_classes: null output, or a maximum outside [0,%d]", DEDUPE_CLASS_MAX);
+    std::vector<uint32_t> table((size_t)DEDUPE_TILE_KEYS);
+    DedupeTally cand[DEDUPE_CLASS_MAX];
+    int nc = 0;
+    if (max_classes > 0 && count <= DEDUPE_CLASS_LAUNCHES)
+        nc = dedupe_class_tally(G, table.data(), cand, max_classes, nullptr);
+    for (int i = 0; i < nc; ++i) class_masks[i] = cand[i].mask;
+    *class_count = nc;
+    if (deposits) {
+        DedupeClasses C;
+        dedupe_classes_fill(C, class_masks, nc, (uint32_t)count);
+        *deposits = dedupe_class_deposits(G, DEDUPE_TILE_KEYS, C, table.data());
+    }
+    return UVRT_OK;
+}
+
 int uvrt_dedupe_mark_device(uvrt_ctx* c, const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
                             int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first, int64_t chunk_n,
                             uint32_t* masks, uint32_t* block_owner_counts)
@@ -538,6 +627,20 @@ int uvrt_fold_batch(uvrt_ctx* c)
     if (int rc = set_device(c)) return rc;
     if (int rc = join_all(c)) return rc;
     launch_fold_planes(c->bs[c->b_set].planes.as<int32_t>(), c->bs[c->b_set].folded.as<int32_t>(), c->b_count, c->b_repl, c->T, c->helper_prio, c->stream);
+    if (c->b_ncls > 0) {      // a launch's total = its own plane + the class planes of the masks that hold it
+        FoldClassParams q;
+        memset(&q, 0, sizeof q);
+        q.planes = c->bs[c->b_set].planes.as<int32_t>();
+        q.folded = c->bs[c->b_set].folded.as<int32_t>();
+        q.plane_stride = (int64_t)c->b_repl * c->T;
+        q.nplanes = c->b_count;
+        q.ncls = c->b_ncls;
+        q.cls_replicas = c->b_cls_repl;
+        q.T = c->T;
+        q.prio = c->helper_prio;
+        memcpy(q.launches, c->b_cls_launches, sizeof(uint64_t) * (size_t)c->b_ncls);
+        launch_fold_classes(q, c->stream);
+    }
     HIP_TRY(hipGetLastError());
     c->b_is_folded = true;
     return UVRT_OK;          // on the context's stream like everything else that touches the set until its replay
@@ -565,6 +668,12 @@ int uvrt_replay_batch(uvrt_ctx* c, const uvrt_replay_op* ops, int32_t count, int
     p.count = count;
     p.is_folded = c->b_is_folded ? 1 : 0;
     p.prio = c->helper_prio;
+    p.nplanes = c->b_count;
+    p.ncls = c->b_ncls;
+    p.cls_replicas = c->b_cls_repl;
+    for (int k = 0; k < count; ++k)
+        for (int cl = 0; cl < c->b_ncls; ++cl)
+            if ((c->b_cls_launches[cl] >> c->b_phys[k]) & 1ull) p.class_of[k] |= 1ull << cl;
     for (int k = 0; k < count; ++k) {
         if (ops[k].which_map != UVRT_MAP_SUM && ops[k].which_map != UVRT_MAP_MAX)
             return fail(UVRT_ERR_INVALID, "uvrt_replay_batch: which_map must be 0 or 1");

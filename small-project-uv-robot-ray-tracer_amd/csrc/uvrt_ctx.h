@@ -213,6 +213,13 @@ struct uvrt_ctx {
     bool dedupe = true;                   // uvrt_set_dedupe / UVRT_DEDUPE: a lamp's distinct rays are traced once per batch (uvrt_dedupe.h)
     int64_t b_traced_known = -1;          // uvrt_batch_traced_rays: the last traced batch's rays in chunks traced as they are ...
     int32_t b_traced_chunks = 0;          // ... and its deduped chunks, whose counts are bs[b_set].dd_counts[0, b_traced_chunks)
+    // mask classes of a batch's dedupe groups (uvrt_dedupe.h "mask classes")
+    int32_t dedupe_classes = uvrt::DEDUPE_CLASSES_DEFAULT;     // uvrt_set_dedupe_classes / UVRT_DEDUPE_CLASSES: classes per group at most, 0 = none
+    int32_t dedupe_class_replicas = 4;    // replicas of a class plane that take deposits (developer knob UVRT_DEDUPE_CLASS_REPLICAS)
+    size_t dedupe_class_bytes = (size_t)96 << 20;         // class planes of one buffer set (developer knob UVRT_DEDUPE_CLASS_MB)
+    int32_t b_ncls = 0, b_cls_repl = 1;   // the traced batch's class planes (behind its b_count launch planes) and their replicas in use
+    uint64_t b_cls_launches[uvrt::MAX_CLASS_PLANES] = {};        // the physical planes each of them is added to
+    // (the deduped chunks' deposit counts follow their ray counts in dd_counts: uvrt_batch_deposits)
     bool b_is_folded = false;             // b_folded holds the batch (fold / all-reduce done), the replicas are zero
     void* comm = nullptr;                 // ncclComm_t of a ray-range-sharded job (uvrt_comm_init_rank)
     // CUs the launch lanes leave to the context's stream while a communicator is set (uvrt_capi_comm.hip

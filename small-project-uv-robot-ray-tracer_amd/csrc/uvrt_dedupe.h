@@ -255,6 +255,182 @@ inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int64_t c0, int64
     }
 }
 
+// ---- Mask classes: one deposit per traced ray ("mask classes") ----
+// An owner deposits once per set bit of its mask, and a group's owners hold few distinct masks (71 in the headline, 32 of them
+// cover 0.9995 of its owners).  Each frequent multi-bit mask gets a count plane of its own behind the launch planes of the
+// batch, a ray of that mask deposits there ONCE, and the fold adds a class plane into every launch of its mask: the per-launch
+// totals stay the same exact integers.  The class list is a function of the group alone -- the host tallies the owners' masks
+// over a fixed sample of narrow key tiles of the call's range (dedupe_class_tally) -- and never decides correctness: a mask
+// without a class keeps the per-bit deposits.
+// The word a compacted ray carries instead of its mask (k_dedupe_write -> ExtendParams::masks -> retire_ray):
+//   DEDUPE_PLANE_FORM | index                       a single-bit mask: the launch's own plane, index = the bit
+//   DEDUPE_PLANE_FORM | DEDUPE_CLASS_FORM | index   a classed mask: its class plane, index counted from the group's first plane
+//   the mask itself (bits 0..29)                    any other mask: one deposit per set bit
+// Bit 31 stays the exact-step flag of the traversal's register, so a group of 31 launches (bit 30 is a launch there) takes no
+// classes and keeps the masks altogether, as does every group when classes are off.
+constexpr int DEDUPE_CLASS_MAX = 32;            // classes per group
+constexpr int DEDUPE_CLASSES_DEFAULT = 32;      // uvrt_set_dedupe_classes' default (DESIGN.md section 15 has the measurement)
+constexpr int DEDUPE_CLASS_SLOTS = 64;          // the lookup table: open addressing, at most half full
+constexpr int DEDUPE_CLASS_LAUNCHES = 30;       // launches of a group that may take classes
+constexpr uint32_t DEDUPE_PLANE_FORM = 1u << 30, DEDUPE_CLASS_FORM = 1u << 29, DEDUPE_PLANE_INDEX = 0xFFFFu;
+
+struct DedupeClasses {
+    int32_t count;                              // 0: every ray keeps its mask
+    uint32_t mask[DEDUPE_CLASS_MAX];            // most frequent first
+    uint32_t slot_mask[DEDUPE_CLASS_SLOTS];     // the table: a class's mask (0 = empty) ...
+    uint32_t slot_word[DEDUPE_CLASS_SLOTS];     // ... and the word of its rays
+};
+
+UVRT_HD uint32_t dedupe_class_slot(uint32_t mask) { return (mask * 0x9E3779B1u) >> 26; }
+UVRT_HD bool dedupe_single_bit(uint32_t mask) { return (mask & (mask - 1u)) == 0u; }
+UVRT_HD int dedupe_popcount(uint32_t v) { return __builtin_popcount(v); }
+
+// the word of an owner with `mask` (not 0) from the table (the device's copy is in LDS); on = the group takes classes
+UVRT_HD uint32_t dedupe_deposit_word(bool on, const uint32_t* slot_mask, const uint32_t* slot_word, uint32_t mask)
+{
+    if (!on) return mask;
+    if (dedupe_single_bit(mask)) return DEDUPE_PLANE_FORM | (uint32_t)__builtin_ctz(mask);
+    for (uint32_t s = dedupe_class_slot(mask);; s = (s + 1u) & (uint32_t)(DEDUPE_CLASS_SLOTS - 1)) {
+        const uint32_t m = slot_mask[s];
+        if (m == mask) return slot_word[s];
+        if (m == 0u) return mask;
+    }
+}
+// atomics a ray with this word issues when it hits (on: as above -- without classes bit 30 is a launch like any other)
+UVRT_HD int dedupe_word_deposits(bool on, uint32_t word) { return (on && (word & DEDUPE_PLANE_FORM)) ? 1 : dedupe_popcount(word); }
+
+// Host: the table of a class list; class i's plane is `first_plane + i` planes from the group's first launch plane
+inline void dedupe_classes_fill(DedupeClasses& C, const uint32_t* masks, int count, uint32_t first_plane)
+{
+    C = DedupeClasses{};
+    C.count = count;
+    for (int i = 0; i < count; ++i) {
+        C.mask[i] = masks[i];
+        uint32_t s = dedupe_class_slot(masks[i]);
+        while (C.slot_mask[s] != 0u) s = (s + 1u) & (uint32_t)(DEDUPE_CLASS_SLOTS - 1);
+        C.slot_mask[s] = masks[i];
+        C.slot_word[s] = DEDUPE_PLANE_FORM | DEDUPE_CLASS_FORM | (first_plane + (uint32_t)i);
+    }
+}
+
+// Host: one tile's table, as dedupe_plan_tiled fills it (every launch's run over the call's whole range, and gid 0)
+inline void dedupe_tile_fill(const DedupeGroup& G, int32_t W, int64_t t0, uint32_t* table, int32_t* g_lo, int32_t* g_hi)
+{
+    for (int32_t i = 0; i < W; ++i) table[i] = 0u;
+    for (int j = 0; j < G.count; ++j) {
+        dedupe_tile_run(G, j, t0, W, g_lo[j], g_hi[j]);
+        for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) dedupe_tile_insert(table, dedupe_tile_slot(dedupe_key1(G, j, g), t0), j);
+        if (dedupe_tile_holds_gid0(G, j, t0, W)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
+    }
+}
+
+// Host: the multi-bit masks of a group's owners by frequency, from a thin sample: one narrow key tile per STRATUM of the keys.
+// Which launches hold a key is periodic in the key wherever nothing about the sums changes: the keys advance by 17 per gid and
+// round to a multiple of the ulp, so the pattern repeats every 17 ulp keys (34 ulp with the ties' round-to-even).  What changes
+// it: a launch's first and last key of the call's range (a copy beyond them is outside the range), and a binade boundary 2^b,
+// b >= 24 -- crossed by the final sum at key 2^b in every launch and by launch j's sum before its last add, the SEED term
+// s_j = SEED >> 15, at key 2^b + s_j.  Between two neighbours of these 2 K + (K + 1) per-binade points the masks' shares are those of any
+// two periods, so a tile of 68 ulp keys from the middle of each stratum, weighted by the stratum's length, stands for it.  (The
+// lamp's terms move a boundary by a few keys and work-item 0 reads the other SEED: neither is looked for, the list decides
+// no result.)  A key that no launch holds twice has ONE owner and its table entry is that owner's mask, so the tally reads
+// the table and generates nothing.  Returns the distinct multi-bit masks found, most frequent first (ties: the smaller
+// mask), at most `cap`; *keys = the weighted keys with an owner.  `table`: DEDUPE_TILE_KEYS entries.
+struct DedupeTally { uint32_t mask; double n; };
+inline int dedupe_class_tally(const DedupeGroup& G, uint32_t* table, DedupeTally* out, int cap, double* keys)
+{
+    constexpr uint32_t H = 512;                 // (a group of 30 launches could hold more masks: the rarest are not counted then)
+    DedupeTally h[H] = {};
+    uint32_t used = 0;
+    double seen = 0.0;
+    // the strata's bounds
+    int64_t cut[2 * DEDUPE_MAX + 7 * (DEDUPE_MAX + 1) + 2];
+    int ncut = 0;
+    const int64_t last = G.first_gid + G.n - 1, lo1 = G.first_gid > 1 ? G.first_gid : 1;
+    if (lo1 > last) { if (keys) *keys = 0.0; return 0; }
+    int64_t klo = INT64_MAX, khi = INT64_MIN;
+    for (int j = 0; j < G.count; ++j) {
+        const int64_t a = dedupe_key1(G, j, (int32_t)lo1), b = (int64_t)dedupe_key1(G, j, (int32_t)last) + 1;
+        cut[ncut++] = a;
+        cut[ncut++] = b;
+        klo = a < klo ? a : klo;
+        khi = b > khi ? b : khi;
+    }
+    for (int b = 24; b <= 30; ++b) {
+        const int64_t B = (int64_t)1 << b;
+        if (B + 131072 <= klo || B >= khi) continue;
+        cut[ncut++] = B;
+        for (int j = 0; j < G.count; ++j) cut[ncut++] = B + (int64_t)((G.seed_mode == 1 ? G.seed_prev[j] : G.seed_next[j]) >> 15);
+    }
+    for (int i = 1; i < ncut; ++i) {            // (insertion sort: a few dozen points)
+        const int64_t v = cut[i];
+        int at = i;
+        for (; at > 0 && cut[at - 1] > v; --at) cut[at] = cut[at - 1];
+        cut[at] = v;
+    }
+    int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
+    for (int i = 0; i + 1 < ncut; ++i) {
+        const int64_t a = cut[i] < klo ? klo : cut[i], b = cut[i + 1] > khi ? khi : cut[i + 1];
+        if (b <= a) continue;
+        int64_t ulp = 1;
+        while (((int64_t)1 << 24) * ulp < b) ulp += ulp;
+        int64_t W = 68 * ulp < 272 ? 272 : 68 * ulp;
+        W = W > DEDUPE_TILE_KEYS ? DEDUPE_TILE_KEYS : W;
+        W = W > b - a ? b - a : W;
+        const double weight = (double)(b - a) / (double)W;
+        dedupe_tile_fill(G, (int32_t)W, a + (b - a - W) / 2, table, g_lo, g_hi);
+        for (int32_t k = 0; k < (int32_t)W; ++k) {
+            const uint32_t e = table[k];
+            if (e == 0u || (e & DEDUPE_MANY)) continue;
+            seen += weight;
+            if (dedupe_single_bit(e)) continue;
+            uint32_t at = (e * 0x9E3779B1u) >> 23;
+            while (h[at].mask != 0u && h[at].mask != e) at = (at + 1u) & (H - 1u);
+            if (h[at].mask == 0u) {
+                if (used >= H / 2u) continue;
+                ++used;
+                h[at].mask = e;
+            }
+            h[at].n += weight;
+        }
+    }
+    if (keys) *keys = seen;
+    int n = 0;
+    for (uint32_t i = 0; i < H; ++i) {          // compact, then an insertion sort: the lists are short
+        if (h[i].mask != 0u) h[n++] = h[i];
+    }
+    for (int i = 1; i < n; ++i) {
+        const DedupeTally v = h[i];
+        int at = i;
+        for (; at > 0 && (h[at - 1].n < v.n || (h[at - 1].n == v.n && h[at - 1].mask > v.mask)); --at) h[at] = h[at - 1];
+        h[at] = v;
+    }
+    n = n < cap ? n : cap;
+    for (int i = 0; i < n; ++i) out[i] = h[i];
+    return n;
+}
+
+// Host: the atomics the owners of a group issue with this class list (count 0: classes off, one per occurrence), every tile
+inline int64_t dedupe_class_deposits(const DedupeGroup& G, int32_t W, const DedupeClasses& C, uint32_t* table)
+{
+    int64_t key_lo, tiles, total = 0;
+    dedupe_tile_range(G, G.first_gid, G.n, W, key_lo, tiles);
+    int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
+    for (int64_t tile = 0; tile < tiles; ++tile) {
+        const int64_t t0 = key_lo + tile * W;
+        dedupe_tile_fill(G, W, t0, table, g_lo, g_hi);
+        for (int32_t i = 0; i < W; ++i) {
+            const uint32_t e = table[i];
+            if (e != 0u && !(e & DEDUPE_MANY)) total += dedupe_word_deposits(C.count > 0, dedupe_deposit_word(C.count > 0, C.slot_mask, C.slot_word, e));
+        }
+        // a key that some launch holds twice: every occurrence is its own owner with its own bit
+        for (int j = 0; j < G.count; ++j) {
+            for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) total += (table[dedupe_tile_slot(dedupe_key1(G, j, g), t0)] & DEDUPE_MANY) != 0u;
+            if (dedupe_tile_holds_gid0(G, j, t0, W)) total += (table[dedupe_tile_slot(G.key0[j], t0)] & DEDUPE_MANY) != 0u;
+        }
+    }
+    return total;
+}
+
 // Host: may these launches form a group?  Fills G.offset and G.key0.  No: a lamp that is not finite, a range past
 // DEDUPE_GID_END, or a sum that leaves the int32 range.
 inline bool dedupe_group_ok(DedupeGroup& G)

@@ -181,7 +181,7 @@ constexpr int DD_ROUNDS = 8, DD_SLOTS = 256 * DD_ROUNDS;      // gids per workgr
 struct GenDedupeParams {
     DedupeGroup g;
     float4* rays;                      // out: [*total] <= count * gn
-    uint32_t* masks;                   // out: parallel to rays
+    uint32_t* masks;                   // out: parallel to rays, each ray's deposit word (uvrt_dedupe.h "mask classes")
     uint32_t* total;                   // out: rays written
     uint32_t* tmp;                     // scratch [count][gn]: every occurrence's mask between the passes
     uint32_t* block_counts;            // scratch [count * ceil(gn / 2048)] (sized for ceil(gn / 256) by the caller): ZERO before
@@ -190,6 +190,8 @@ struct GenDedupeParams {
     int64_t key_lo, tiles;             // the chunk's key tiles (dedupe_tile_range with DEDUPE_TILE_KEYS)
     float light_length;
     int32_t prio;                      // helper_priority of the three kernels
+    uint32_t* deposits;                // out: the atomics these rays issue when each of them hits (dedupe_word_deposits summed)
+    DedupeClasses cls;                 // the group's mask classes (count 0: masks[] holds the masks themselves)
 };
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s);
 // its first kernel alone: tmp and the owners per block added to block_counts (a test hook runs it by itself)
@@ -220,8 +222,23 @@ struct ReplayParams {
     int64_t plane_stride;              // ints between planes of `planes` (= replicas * T)
     int32_t replicas, T, count, is_folded;
     int32_t prio;                      // helper_priority
+    // the mask classes of the batch's dedupe groups (uvrt_dedupe.h): class plane c is plane `nplanes + c` of `planes`, with
+    // cls_replicas replicas in use; class_of[k] = the class planes whose mask holds logical launch k
+    int32_t nplanes, ncls, cls_replicas;
+    uint64_t class_of[MAX_BATCH];
     ReplayOp ops[MAX_BATCH];
 };
+constexpr int MAX_CLASS_PLANES = 64;   // class planes of one batch, all its dedupe groups together (one bit each in class_of)
+
+// the class planes of a batch added into the folded planes of the launches their masks hold, and zeroed
+struct FoldClassParams {
+    int32_t* planes;                   // the batch set's planes: class plane c at planes + (nplanes + c) * plane_stride
+    int32_t* folded;                   // [nplanes][T], after launch_fold_planes
+    int64_t plane_stride;
+    int32_t nplanes, ncls, cls_replicas, T, prio;
+    uint64_t launches[MAX_CLASS_PLANES];     // physical planes class c is added to
+};
+void launch_fold_classes(const FoldClassParams& p, hipStream_t s);
 
 struct GenParams {
     float4* rays;          // [n] gid order: dir.xyz, orig.y
@@ -249,6 +266,10 @@ struct ExtendParams {
     SceneDev scene;
     const float4* rays;      // [n] in trace order
     uint32_t chunk;          // persistent kernel: trace slots owned by each wavefront
+    int32_t cls_replicas;    // a deduped chunk whose `masks` (below) are deposit words (uvrt_dedupe.h "mask classes"; 0: they are the masks themselves): a class plane takes
+                             // deposits in its first cls_replicas replicas only -- a class holds a fraction of a launch's rays, and
+                             // the replay reads every replica in use.  (It sits in the padding before the next pointer: no other
+                             // field moves, and the kernels that do not read it keep their code.)
     uint32_t* ovf_stack;     // persistent kernels: [grid threads][MAX_STACK - LDS entries] stack overflow
     uint64_t ovf_capacity;   // entries (uint32) available in ovf_stack; launches that need more are refused
     int32_t num_cus;         // compute units of the device (persistent grids are sized from it)
@@ -287,6 +308,7 @@ struct ExtendParams {
     uint32_t root_ref4;      // REF_DONE / a leaf reference (re-based) / 0
     // a deduped chunk of a batch (launch_extend6_dedupe; uvrt_dedupe.h): `rays` is a compacted list of *n_dev distinct rays
     // (n is its upper bound: the grid is sized from it), masks[i] = the planes ray i deposits in, bit k = plane k of `counts`
+    // -- or, where cls_replicas != 0, its deposit word (uvrt_dedupe.h "mask classes")
     const uint32_t* masks;
     const uint32_t* n_dev;
 };

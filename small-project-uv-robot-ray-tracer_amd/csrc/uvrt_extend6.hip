@@ -377,10 +377,10 @@ static_assert(4 * MERGE6_AT <= 64, "the rays of four waves must fit one");
 constexpr uint32_t TOP6_KEEP = TOP6_MAX + 1 - (MERGE6_FIELDS * 64 * 4 + TOP6_STRIDE - 1) / TOP6_STRIDE;      // 120 records stay cached
 template <bool RECORD, bool DD = false>
 __device__ __forceinline__ bool merge6(Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t& plane_off, uint32_t& stack_base,
-                                       uint32_t& slot, bool& live, uint32_t* row0, uint32_t* xch)
+                                       uint32_t& slot, bool& live, uint32_t* row0, uint32_t* xch, uint32_t cls_delta = 0u)
 {
     // (few scalars at a time: the kernel's long-lived ones leave little room, and what does not fit is spilled for the whole loop)
-    if (L.cur == REF_DONE) retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live);   // rays finished since the last refill
+    if (L.cur == REF_DONE) retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live, cls_delta);   // rays finished since the last refill
     // the wave's number in its workgroup comes from the lane's own stack rows (not yet anybody else's; threadIdx.x is not kept)
     {
         const uint32_t cnt = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(L.cur != REF_DONE));
@@ -440,7 +440,8 @@ struct TripClock {
 #endif
 
 // DD: a deduped chunk of a batch (uvrt_dedupe.h; launch_extend6_dedupe) -- the ray count is read from device memory here and
-// every wave's share computed from it, a refill loads the ray's mask beside the ray, a finished ray deposits once per mask bit
+// every wave's share computed from it, a refill loads the ray's deposit word (its mask, or the one plane it deposits in: uvrt_dedupe.h
+// "mask classes") beside the ray, a finished ray deposits once, or once per mask bit
 template <int LEAFP, bool RECORD, bool TOP, int FL, bool DD = false>
 __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
 {
@@ -492,6 +493,10 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
         dd_chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)((q + 63u) / 64u * 64u));
     }
     const uint32_t chunk_end = DD ? dd_chunk : p.chunk;
+    // (DD: ints from this workgroup's replica of a launch plane to its replica of a class plane -- a class plane takes deposits
+    //  in its first cls_replicas replicas only; uint32 arithmetic, as the deposit's offset)
+    const uint32_t cls_delta = DD && p.cls_replicas > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x % (unsigned)p.cls_replicas -
+                                        blockIdx.x % (unsigned)p.count_replicas) * (uint32_t)p.count_stride)) : 0u;
     uint32_t trip = 0;
     unsigned long long km = ~0ull;          // all ones in a trip that visits leaves (every LEAFP-th)
     unsigned long long full;                // exec of the loop: all 64 lanes (the launch uses full workgroups)
@@ -556,13 +561,13 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
                 const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
                 const int nidle = __popcll(idle_mask);
                 if (cursor < chunk_end) {
-                    if (L.cur == REF_DONE) refill_lane<RECORD, FL, PLANES_ASK, DD>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6, chunk_end, dd_n);
+                    if (L.cur == REF_DONE) refill_lane<RECORD, FL, PLANES_ASK, DD>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6, chunk_end, dd_n, cls_delta);
                     cursor += (uint32_t)nidle;
                     if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
                 } else if (TOP && cursor != MERGED6) {
                     cursor = MERGED6;
                     const bool go_on = merge6<RECORD, DD>(L, p, my_counts, plane_off, stack_base, slot, live, &s_stack[0][0],
-                                                      (uint32_t*)&s_top[TOP ? TOP6_KEEP * (TOP6_STRIDE / 16u) : 0u]);
+                                                      (uint32_t*)&s_top[TOP ? TOP6_KEEP * (TOP6_STRIDE / 16u) : 0u], cls_delta);
                     if (!go_on) break;
                     top_pairs = top_pairs < TOP6_KEEP ? top_pairs : TOP6_KEEP;
                     continue;
@@ -588,7 +593,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
         if (TOP && cursor >= chunk_end && cursor != MERGED6 && 64 - nidle <= (int)MERGE6_AT) {
             cursor = MERGED6;
             const bool go_on = merge6<RECORD, DD>(L, p, my_counts, plane_off, stack_base, slot, live, &s_stack[0][0],
-                                              (uint32_t*)&s_top[TOP ? TOP6_KEEP * (TOP6_STRIDE / 16u) : 0u]);
+                                              (uint32_t*)&s_top[TOP ? TOP6_KEEP * (TOP6_STRIDE / 16u) : 0u], cls_delta);
             if (!go_on) break;
             top_pairs = top_pairs < TOP6_KEEP ? top_pairs : TOP6_KEEP;
             continue;
@@ -598,7 +603,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
             unsigned long long tclk = __builtin_readcyclecounter();
 #endif
             if (cursor < chunk_end) {
-                if (L.cur == REF_DONE) refill_lane<RECORD, FL, PLANES_ASK, DD>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6, chunk_end, dd_n);
+                if (L.cur == REF_DONE) refill_lane<RECORD, FL, PLANES_ASK, DD>(L, p, nullptr, my_counts, plane_off, slot, live, idle_mask, cursor, wave, W, root6, chunk_end, dd_n, cls_delta);
                 cursor += (uint32_t)nidle;
                 if (cursor >= chunk_end) { refill_at = 64; if (!TOP || p.drain_merge == 0) cursor = MERGED6; }
 #ifdef UVRT_TRIP_STATS
@@ -675,7 +680,7 @@ __global__ __launch_bounds__(256, 8) void k_extend6(ExtendParams p)
     }
 #endif
     // the wave's sequence is exhausted and every lane is idle: deposit what is still pending
-    retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live);
+    retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live, cls_delta);
 }
 
 // Per-launch node-pair records recs[0, P): the lamp's x and z subtracted from the x / z bounds (the
@@ -729,6 +734,7 @@ bool launch_extend6_dedupe(const ExtendParams& p0, int code, int grid_per_cu, hi
     if (p0.n <= 0) return true;
     if ((code & 7) != 1 || p0.hits || !p0.masks || !p0.n_dev || !p0.recs_prepared || p0.plane_stride == 0) return false;
     ExtendParams p = p0;
+    if (p.cls_replicas < 0 || p.cls_replicas > p.count_replicas) p.cls_replicas = p.count_replicas;      // (0: the words are masks)
     p.plane_batches = (uint32_t)((p.n + 63) / 64);      // (one list: no plane is looked up in it)
     p.plane_n = (uint32_t)p.n;
     const unsigned grid = size_persistent_grid(p, grid_per_cu);

@@ -153,11 +153,12 @@ __global__ __launch_bounds__(256) void k_dedupe_mark(GenDedupeParams p)
 
 // scan: the workgroups' counts -> their first slot in the compacted list, in (launch, gid) order; the total.  One workgroup
 // of 256 threads: it must find room on a CU beside the persistent traversal grid of the other lane, as every kernel here.
-__global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uint32_t* total, uint32_t nblocks, int prio)
+__global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uint32_t* total, uint32_t* deposits, uint32_t nblocks, int prio)
 {
     helper_priority(prio);
     __shared__ uint32_t s_part[256];
     const uint32_t tid = threadIdx.x;
+    if (tid == 0u) *deposits = 0u;      // (the write pass adds to it, one add per workgroup)
     const uint32_t per = (nblocks + 255u) / 256u;
     const uint32_t lo = min(tid * per, nblocks), hi = min(lo + per, nblocks);
     uint32_t sum = 0;
@@ -179,11 +180,21 @@ __global__ __launch_bounds__(256) void k_dedupe_scan(uint32_t* block_counts, uin
     if (tid == 255u) *total = s_part[255];
 }
 
-// write: the owners' rays (generate.cl:11-37) and masks at their slots, in (launch, gid) order
+// write: the owners' rays (generate.cl:11-37) and deposit words at their slots, in (launch, gid) order.  The word is the mask
+// translated through the group's class table (uvrt_dedupe.h "mask classes"; the table comes with the parameters and is
+// looked up in LDS); the atomics the words stand for are counted, one add per workgroup.
 __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
 {
     helper_priority(p.prio);
     __shared__ uint32_t s_cnt[DD_ROUNDS][4];
+    __shared__ uint32_t s_slot_mask[DEDUPE_CLASS_SLOTS], s_slot_word[DEDUPE_CLASS_SLOTS], s_dep;
+    if (threadIdx.x < (unsigned)DEDUPE_CLASS_SLOTS) {
+        s_slot_mask[threadIdx.x] = p.cls.slot_mask[threadIdx.x];
+        s_slot_word[threadIdx.x] = p.cls.slot_word[threadIdx.x];
+    }
+    if (threadIdx.x == 0) s_dep = 0u;
+    const bool classes = p.cls.count > 0;
+    uint32_t dep = 0u;
     const int k = blockIdx.y;
     const uint32_t wv = threadIdx.x >> 6;
     uint32_t mask[DD_ROUNDS], rank[DD_ROUNDS];
@@ -208,11 +219,16 @@ __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
                 double x, y;
                 p.rays[pos + rank[r]] = generate_ray(p.g.lx, p.g.ly, p.g.lz, p.light_length, p.g0 + i, p.g.seed_prev[k],
                                                      p.g.seed_next[k], p.g.seed_mode, r0, x, y);
-                p.masks[pos + rank[r]] = mask[r];
+                const uint32_t word = dedupe_deposit_word(classes, s_slot_mask, s_slot_word, mask[r]);
+                p.masks[pos + rank[r]] = word;
+                dep += (uint32_t)dedupe_word_deposits(classes, word);
             }
             pos += s_cnt[r][w];
         }
     }
+    if (dep != 0u) atomicAdd(&s_dep, dep);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_dep != 0u) atomicAdd(p.deposits, s_dep);
 }
 
 // Exclusive prefix sum over the key histogram (one 1024-thread workgroup; nbins <= 2^20), and
@@ -345,6 +361,36 @@ __global__ __launch_bounds__(256) void k_fold_planes(int32_t* __restrict__ plane
     if (i < T && part == 0) folded[(int64_t)blockIdx.y * T + i] = total;
 }
 
+// The sum of a class plane's replicas in use for triangle i, the replicas zeroed: a quad of lanes shares the triangle as above
+__device__ __forceinline__ int32_t take_class_plane(int32_t* pl, int32_t replicas, int64_t replica_stride, int i, int part, bool in)
+{
+    int32_t total = 0;
+    if (in) {
+        for (int r = part; r < replicas; r += 4) {
+            total += pl[(int64_t)r * replica_stride + i];
+            pl[(int64_t)r * replica_stride + i] = 0;
+        }
+    }
+    total += __builtin_amdgcn_mov_dpp(total, 0xb1, 0xf, 0xf, true);
+    total += __builtin_amdgcn_mov_dpp(total, 0x4e, 0xf, 0xf, true);
+    return total;
+}
+
+// After k_fold_planes: every class plane of the batch (uvrt_dedupe.h "mask classes") read once per triangle and added to the
+// folded plane of each launch its mask holds -- a launch's total is its own plane plus the classes it is a member of.
+__global__ __launch_bounds__(256) void k_fold_classes(FoldClassParams p)
+{
+    helper_priority(p.prio);
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int i = g >> 2, part = g & 3;
+    const bool in = i < p.T;
+    for (int c = 0; c < p.ncls; ++c) {
+        const int32_t total = take_class_plane(p.planes + (int64_t)(p.nplanes + c) * p.plane_stride, p.cls_replicas, p.T, i, part, in);
+        if (!in || part != 0 || total == 0) continue;
+        for (uint64_t m = p.launches[c]; m != 0ull; m &= m - 1ull) p.folded[(int64_t)__builtin_ctzll(m) * p.T + i] += total;
+    }
+}
+
 // Replay of a batch in LOGICAL launch order, one quad of lanes per triangle: for every launch the
 // reference's accumulate (cl/accumulate.cl:4-14: same f64 additions in the same order, max over the
 // per-launch totals) and, where the host loop has a Shade behind it (raytracer.cpp:93-120), computeDosage +
@@ -357,6 +403,14 @@ __global__ __launch_bounds__(256) void k_replay_batch(ReplayParams p)
     const bool in = i < p.T;
     double pm = 0, mm = 0;
     if (in && part == 0) { pm = p.photon_map[i]; mm = p.max_map[i]; }
+    // the batch's class planes (uvrt_dedupe.h "mask classes"), each read ONCE per triangle: the quad's first lane keeps the
+    // totals in LDS and adds to a launch those of the classes it is a member of (a folded batch has them in its planes)
+    extern __shared__ int32_t s_cls[];          // [ncls][64 triangles of the workgroup]
+    const int ncls = p.is_folded ? 0 : p.ncls;
+    for (int c = 0; c < ncls; ++c) {
+        const int32_t total = take_class_plane(p.planes + (int64_t)(p.nplanes + c) * p.plane_stride, p.cls_replicas, p.T, i, part, in);
+        if (part == 0) s_cls[c * 64 + (threadIdx.x >> 2)] = total;
+    }
     for (int k = 0; k < p.count; ++k) {
         const ReplayOp op = p.ops[k];
         int32_t total = 0;
@@ -378,6 +432,8 @@ __global__ __launch_bounds__(256) void k_replay_batch(ReplayParams p)
             total += __builtin_amdgcn_mov_dpp(total, 0x4e, 0xf, 0xf, true);
         }
         if (!in || part != 0) continue;
+        if (ncls > 0)
+            for (uint64_t m = p.class_of[k]; m != 0ull; m &= m - 1ull) total += s_cls[__builtin_ctzll(m) * 64 + (threadIdx.x >> 2)];
         const double c = (double)total;                                   // accumulate.cl:9-13
         pm = pm + c * (double)op.duration;
         mm = mm < c ? c : mm;
@@ -621,7 +677,7 @@ void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s)
     if (p.gn <= 0 || p.g.count <= 0) return;
     const dim3 grid(blocks_for(p.gn, DD_SLOTS), (unsigned)p.g.count);
     launch_dedupe_mark(p, s);
-    hipLaunchKernelGGL(k_dedupe_scan, dim3(1), dim3(256), 0, s, p.block_counts, p.total, grid.x * grid.y, (int)p.prio);
+    hipLaunchKernelGGL(k_dedupe_scan, dim3(1), dim3(256), 0, s, p.block_counts, p.total, p.deposits, grid.x * grid.y, (int)p.prio);
     hipLaunchKernelGGL(k_dedupe_write, grid, dim3(256), 0, s, p);
 }
 
@@ -635,7 +691,14 @@ void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32
 void launch_replay_batch(const ReplayParams& p, hipStream_t s)
 {
     if (p.count <= 0 || p.T <= 0) return;
-    hipLaunchKernelGGL(k_replay_batch, dim3(blocks_for((int64_t)p.T * 4, 256)), dim3(256), 0, s, p);
+    const size_t lds = p.is_folded ? 0 : (size_t)p.ncls * 64 * sizeof(int32_t);      // (the class totals of the workgroup's triangles)
+    hipLaunchKernelGGL(k_replay_batch, dim3(blocks_for((int64_t)p.T * 4, 256)), dim3(256), lds, s, p);
+}
+
+void launch_fold_classes(const FoldClassParams& p, hipStream_t s)
+{
+    if (p.ncls <= 0 || p.T <= 0) return;
+    hipLaunchKernelGGL(k_fold_classes, dim3(blocks_for((int64_t)p.T * 4, 256)), dim3(256), 0, s, p);
 }
 
 void launch_add_counts(int32_t* dst, const int32_t* src, int64_t n, hipStream_t s)

@@ -269,20 +269,27 @@ __device__ __forceinline__ bool origin_outside_window(float o)
 
 // The results of the ray a lane has finished (extend.cl:94-98): its hit record when one is pending (`live`), and its deposit
 // unless it hit nothing (dist == 1e30f).
-// DD: the ray of a deduped chunk (uvrt_dedupe.h) -- the register holds the MASK of its planes instead of one plane's offset,
-// and the hit is deposited once per set bit, at bit * plane_stride + triID (uint32: a batch has fewer than 2^32 counters).
+// DD: the ray of a deduped chunk (uvrt_dedupe.h) -- the register holds the ray's deposit word instead of one plane's offset:
+// a plane index (the launch's own plane, or the class plane of its mask: one deposit at index * plane_stride + triID), or the
+// MASK of its planes, deposited once per set bit at bit * plane_stride + triID (uint32: a batch has fewer than 2^32 counters).
 template <bool RECORD, bool DD = false>
 __device__ __forceinline__ void retire_ray(const Lane6& L, const ExtendParams& p, int32_t* my_counts, uint32_t plane_off,
-                                           uint32_t slot, bool live)
+                                           uint32_t slot, bool live, uint32_t cls_delta = 0u)
 {
     if (RECORD && live && p.hits) {
         const uint32_t li = p.order ? p.order[slot] : slot;
         p.hits[li] = make_uint2(__float_as_uint(L.po.y), L.triID);
     }
     if constexpr (DD) {
-        if (L.po.y != 1e30f)
-            for (uint32_t m = plane_off & PLANE_OFF6; m != 0u; m &= m - 1u)
-                atomicAdd(&my_counts[(uint32_t)__builtin_ctz(m) * p.plane_stride + L.triID], 1);
+        if (L.po.y != 1e30f) {
+            const uint32_t w = plane_off & PLANE_OFF6;
+            // (a chunk without classes holds masks only, and bit 30 may be a launch there: p.cls_replicas == 0)
+            if (w & (p.cls_replicas != 0 ? uvrt::DEDUPE_PLANE_FORM : 0u))      // one plane: the launch's own, or the class plane of the ray's mask
+                atomicAdd(&my_counts[(w & uvrt::DEDUPE_PLANE_INDEX) * p.plane_stride + L.triID + ((w & uvrt::DEDUPE_CLASS_FORM) ? cls_delta : 0u)], 1);
+            else
+                for (uint32_t m = w; m != 0u; m &= m - 1u)
+                    atomicAdd(&my_counts[(uint32_t)__builtin_ctz(m) * p.plane_stride + L.triID], 1);
+        }
     } else
     if (L.po.y != 1e30f) atomicAdd(&my_counts[(plane_off & PLANE_OFF6) + L.triID], 1);
 }
@@ -302,9 +309,9 @@ template <bool RECORD, int FL, PlaneMode PM = PLANES_ASK, bool DD = false, class
 __device__ __forceinline__ void refill_lane(LaneT& L, const ExtendParams& p, const float2* oxz, int32_t* my_counts,
                                             uint32_t& plane_off, uint32_t& slot, bool& live, unsigned long long idle_mask,
                                             uint32_t cursor, uint32_t wave, uint32_t W, uint32_t root,
-                                            uint32_t dd_chunk = 0u, uint32_t dd_n = 0u)
+                                            uint32_t dd_chunk = 0u, uint32_t dd_n = 0u, uint32_t cls_delta = 0u)
 {
-    retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live);
+    retire_ray<RECORD, DD>(L, p, my_counts, plane_off, slot, live, cls_delta);
     live = false;
     L.po.y = 1e30f;
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
