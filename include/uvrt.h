@@ -281,7 +281,11 @@ typedef struct {
 } uvrt_launch;
 int uvrt_trace_batch_launches(uvrt_ctx* ctx, const uvrt_launch* launches, float light_length,
                               int32_t count, int64_t first_gid, int64_t n);
-/* per launch (logical order): accumulate.cl, then Shade where ops[k].shade is set; ends the batch */
+/* per launch (logical order): accumulate.cl, then Shade where ops[k].shade is set; ends the batch.
+ * tri_count in [0, T]: triangles [0, tri_count) are replayed from their launches' totals exactly as a full replay would replay
+ * them (folded or not, with or without dedupe and mask classes); both maps, the dose and the colours stay untouched from
+ * tri_count on.  Whatever tri_count is, the batch ends and its planes are cleared entirely: the counts of the triangles from
+ * tri_count on are dropped, as accumulate.cl leaves them out. */
 int uvrt_replay_batch(uvrt_ctx* ctx, const uvrt_replay_op* ops, int32_t count, int32_t tri_count);
 /* sum the deposit replicas of every plane into the int32[count][T] array the reduction works on */
 int uvrt_fold_batch(uvrt_ctx* ctx);
@@ -317,6 +321,11 @@ int32_t uvrt_dedupe_classes_default(void);
 /* test hook: the atomic adds the traced rays of the last batch's dedupe groups issue if each of them hits -- one for a ray
  * that deposits in one plane (its launch's own or a class plane), one per launch for any other (waits for the batch) */
 int uvrt_batch_deposits(uvrt_ctx* ctx, int64_t* out);
+/* test hook: the number of non-zero int32 values in the whole allocation of the count planes of both buffer sets of the
+ * context -- launch planes and class planes, used by the last batches or not.  Between batches it is 0: whatever a batch
+ * deposited, its fold or replay read back and zeroed (nothing else clears a set).  UVRT_ERR_INVALID while a traced batch has
+ * not been replayed.  Waits for everything the context has outstanding and copies the planes to the host. */
+int uvrt_batch_residue(uvrt_ctx* ctx, int64_t* nonzero);
 /* test hook, host only: the class list a batch gives the dedupe group of uvrt_dedupe_plan's arguments when it may take up to
  * max_classes classes and shares its class planes with no other group -- class_masks[0, *class_count), most frequent first,
  * room for 32 -- and, where `deposits` is not null, the group's uvrt_batch_deposits figure with that list (max_classes 0 or a

@@ -58,6 +58,7 @@ SYMBOLS = [
     ("uvrt_get_dedupe_classes", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_dedupe_classes_default", _i32, []),
     ("uvrt_batch_deposits", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("uvrt_batch_residue", C.c_int, [_vp, C.POINTER(_i64)]),
     ("uvrt_dedupe_classes", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _vp, C.POINTER(_i32), C.POINTER(_i64)]),
     ("uvrt_seed_input", _u32, [_i64, _fp, _u32, _u32, _i32]),
     ("uvrt_dedupe_plan", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
@@ -565,6 +566,12 @@ class Ctx:
         """atomic adds the traced rays of the last batch's dedupe groups issue when each of them hits"""
         out = _i64()
         self._ck(self._L.uvrt_batch_deposits(self._h, C.byref(out)))
+        return int(out.value)
+
+    def batch_residue(self):
+        """non-zero counters in the count planes of both buffer sets (include/uvrt.h uvrt_batch_residue): 0 between batches"""
+        out = _i64()
+        self._ck(self._L.uvrt_batch_residue(self._h, C.byref(out)))
         return int(out.value)
 
     def batch_traced_rays(self):

@@ -506,6 +506,31 @@ int uvrt_batch_deposits(uvrt_ctx* c, int64_t* out)
     return UVRT_OK;
 }
 
+int uvrt_batch_residue(uvrt_ctx* c, int64_t* nonzero)
+{
+    if (!c || !nonzero) return fail(UVRT_ERR_INVALID, "uvrt_batch_residue: null argument");
+    if (c->b_count > 0) return fail(UVRT_ERR_INVALID, "uvrt_batch_residue: the traced batch has not been replayed (uvrt_replay_batch)");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // the whole allocation of both sets' planes -- launch planes at any R and the class planes behind them -- piece by piece
+    // through one host buffer
+    const size_t piece = (size_t)16 << 20;      // ints
+    std::vector<int32_t> host;
+    int64_t total = 0;
+    for (const uvrt_ctx::BatchSet& S : c->bs) {
+        const size_t ints = S.planes.p ? S.planes.bytes / 4 : 0;
+        for (size_t at = 0; at < ints; at += piece) {
+            const size_t m = std::min(piece, ints - at);
+            host.resize(std::max(host.size(), m));
+            if (int rc = copy_sync(c, host.data(), (const int32_t*)S.planes.p + at, m * 4, hipMemcpyDeviceToHost)) return rc;
+            for (size_t i = 0; i < m; ++i) total += host[i] != 0;
+        }
+    }
+    *nonzero = total;
+    return UVRT_OK;
+}
+
 uint32_t uvrt_seed_input(int64_t gid, const float lamp[3], uint32_t seed_prev, uint32_t seed_next, int32_t seed_mode)
 {
     return seed_input(gid, lamp[0], lamp[1], lamp[2], seed_prev, seed_next, seed_mode);
@@ -664,7 +689,8 @@ int uvrt_replay_batch(uvrt_ctx* c, const uvrt_replay_op* ops, int32_t count, int
     p.area = c->area.as<float>();
     p.plane_stride = (int64_t)c->b_repl * c->T;
     p.replicas = c->b_repl;
-    p.T = tri_count;
+    p.T = c->T;
+    p.bound = tri_count;
     p.count = count;
     p.is_folded = c->b_is_folded ? 1 : 0;
     p.prio = c->helper_prio;

@@ -220,8 +220,9 @@ struct ReplayParams {
     float* color;
     const float* area;
     int64_t plane_stride;              // ints between planes of `planes` (= replicas * T)
-    int32_t replicas, T, count, is_folded;
+    int32_t replicas, T, count, is_folded;      // T: the scene's triangles, the stride of a replica and of a folded plane
     int32_t prio;                      // helper_priority
+    int32_t bound;                     // triangles [0, bound) are replayed (uvrt_replay_batch's tri_count <= T)
     // the mask classes of the batch's dedupe groups (uvrt_dedupe.h): class plane c is plane `nplanes + c` of `planes`, with
     // cls_replicas replicas in use; class_of[k] = the class planes whose mask holds logical launch k
     int32_t nplanes, ncls, cls_replicas;

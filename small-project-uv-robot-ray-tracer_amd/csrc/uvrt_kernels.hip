@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256) void k_replay_batch(ReplayParams p)
     helper_priority(p.prio);
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int i = g >> 2, part = g & 3;
-    const bool in = i < p.T;
+    const bool in = i < p.bound;
     double pm = 0, mm = 0;
     if (in && part == 0) { pm = p.photon_map[i]; mm = p.max_map[i]; }
     // the batch's class planes (uvrt_dedupe.h "mask classes"), each read ONCE per triangle: the quad's first lane keeps the
@@ -690,9 +690,9 @@ void launch_fold_planes(int32_t* planes, int32_t* folded, int32_t nplanes, int32
 
 void launch_replay_batch(const ReplayParams& p, hipStream_t s)
 {
-    if (p.count <= 0 || p.T <= 0) return;
+    if (p.count <= 0 || p.bound <= 0) return;
     const size_t lds = p.is_folded ? 0 : (size_t)p.ncls * 64 * sizeof(int32_t);      // (the class totals of the workgroup's triangles)
-    hipLaunchKernelGGL(k_replay_batch, dim3(blocks_for((int64_t)p.T * 4, 256)), dim3(256), lds, s, p);
+    hipLaunchKernelGGL(k_replay_batch, dim3(blocks_for((int64_t)p.bound * 4, 256)), dim3(256), lds, s, p);
 }
 
 void launch_fold_classes(const FoldClassParams& p, hipStream_t s)
