@@ -353,14 +353,20 @@ int uvrt_dedupe_plan(const float lamp[3], int32_t count, const uint32_t* seed_pr
                      int32_t seed_mode, int64_t first_gid, int64_t n, uint32_t* masks);
 /* test hooks for the form of the rule the device runs: one pass per key tile instead of a search per occurrence.
  * uvrt_dedupe_plan_tiled (host only): the same group, the masks of the chunk [chunk_first, chunk_first + chunk_n) inside the
- * range, masks[k * chunk_n + i], computed tile by tile with tiles of `tile_keys` keys -- the functions the kernel runs, on the
- * CPU.  They equal uvrt_dedupe_plan's for every tile width and chunk.
+ * range, masks[k * chunk_n + i], computed tile by tile with tiles of `tile_keys` keys, in strips of tiles with carried run
+ * bounds -- the functions the kernel runs, on the CPU.  They equal uvrt_dedupe_plan's for every tile width and chunk.
  * uvrt_dedupe_mark_device: the first kernel of a deduped chunk's generate alone, for that group and chunk on the context's
  * stream (waited for): every occurrence's mask as above, and the owners (non-zero masks) per launch and block of 2 048 gids
- * of the chunk, block_owner_counts[k * ceil(chunk_n / 2048) + b], as the scan pass will read them. */
+ * of the chunk, block_owner_counts[k * ceil(chunk_n / 2048) + b], as the scan pass reads them in a traced chunk (the hook
+ * zeroes lane 0's counts again behind its copy, as the write pass of a traced chunk leaves them). */
 int uvrt_dedupe_plan_tiled(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
                            int32_t seed_mode, int64_t first_gid, int64_t n, int32_t tile_keys, int64_t chunk_first,
                            int64_t chunk_n, uint32_t* masks);
+/* the same with strips of `strip_tiles` tiles (uvrt_dedupe_plan_tiled walks the device's shortest, 4): only a strip's first
+ * tile searches its run bounds, the others carry them.  The masks do not depend on the strip length either. */
+int uvrt_dedupe_plan_strips(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                            int32_t seed_mode, int64_t first_gid, int64_t n, int32_t tile_keys, int32_t strip_tiles,
+                            int64_t chunk_first, int64_t chunk_n, uint32_t* masks);
 int uvrt_dedupe_mark_device(uvrt_ctx* ctx, const float lamp[3], int32_t count, const uint32_t* seed_prev,
                             const uint32_t* seed_next, int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first,
                             int64_t chunk_n, uint32_t* masks, uint32_t* block_owner_counts);

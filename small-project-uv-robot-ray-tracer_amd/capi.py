@@ -63,6 +63,7 @@ SYMBOLS = [
     ("uvrt_seed_input", _u32, [_i64, _fp, _u32, _u32, _i32]),
     ("uvrt_dedupe_plan", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
     ("uvrt_dedupe_plan_tiled", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i64, _i64, _vp]),
+    ("uvrt_dedupe_plan_strips", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64, _vp]),
     ("uvrt_dedupe_mark_device", C.c_int, [_vp, _fp, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
     ("uvrt_comm_available", C.c_int, []),
     ("uvrt_comm_info", C.c_int, [_vp, C.POINTER(_i32)]),
@@ -284,12 +285,14 @@ def dedupe_classes(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, max_cla
 
 DEDUPE_CLASS_MAX = 32        # classes per dedupe group at most (csrc/uvrt_dedupe.h)
 DEDUPE_CLASS_LAUNCHES = 30   # launches of a group that may take classes
-DEDUPE_TILE_KEYS = 3840      # the device's tile (csrc/uvrt_dedupe.h)
+DEDUPE_TILE_KEYS = 3840      # the host's tile: class tally, deposit count (csrc/uvrt_dedupe.h)
+DEDUPE_MARK_KEYS = 960       # the tile of the device's mark pass, one wave each ...
+DEDUPE_STRIP_TILES = 4       # ... which walks strips of this many tiles with carried run bounds
 DEDUPE_BLOCK_GIDS = 2048     # gids per owner count of a chunk (csrc/uvrt_device.h DD_SLOTS)
 
 
 def dedupe_plan_tiled(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, tile_keys=DEDUPE_TILE_KEYS, chunk_first=None,
-                      chunk_n=None):
+                      chunk_n=None, strip_tiles=None):
     """dedupe_plan's masks for the chunk [chunk_first, chunk_first + chunk_n) of the range (default: all of it), computed tile
     by tile on the host (include/uvrt.h uvrt_dedupe_plan_tiled): uint32[launches][chunk_n]"""
     sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
@@ -298,8 +301,12 @@ def dedupe_plan_tiled(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, tile
     chunk_first = first_gid if chunk_first is None else chunk_first
     chunk_n = n if chunk_n is None else chunk_n
     out = np.empty((sp.size, int(chunk_n)), dtype=np.uint32)
-    rc = lib().uvrt_dedupe_plan_tiled(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n),
-                                      int(tile_keys), int(chunk_first), int(chunk_n), _ptr(out))
+    if strip_tiles is None:
+        rc = lib().uvrt_dedupe_plan_tiled(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n),
+                                          int(tile_keys), int(chunk_first), int(chunk_n), _ptr(out))
+    else:          # strips of that many tiles (include/uvrt.h uvrt_dedupe_plan_strips)
+        rc = lib().uvrt_dedupe_plan_strips(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n),
+                                           int(tile_keys), int(strip_tiles), int(chunk_first), int(chunk_n), _ptr(out))
     if rc != 0:
         raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
     return out

@@ -115,6 +115,7 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
     if (const char* e = getenv("UVRT_DEDUPE")) c->dedupe = atoi(e) != 0;                 // uvrt_set_dedupe's default
     if (const char* e = getenv("UVRT_DEDUPE_CLASSES")) { const int v = atoi(e); if (v >= 0 && v <= DEDUPE_CLASS_MAX) c->dedupe_classes = v; }   // uvrt_set_dedupe_classes' default
+    if (const char* e = getenv("UVRT_DEDUPE_STRIP")) { const int v = atoi(e); if (v >= 1 && v <= 1024) c->dedupe_strip = v; }   // developer knob: tiles per wave of the mark pass
     if (const char* e = getenv("UVRT_DEDUPE_CLASS_REPLICAS")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->dedupe_class_replicas = v; }
     if (const char* e = getenv("UVRT_DEDUPE_CLASS_MB")) { const long v = atol(e); if (v > 0 && v <= 4096) c->dedupe_class_bytes = (size_t)v << 20; }
     if (const char* e = getenv("UVRT_HELPER_PRIO")) { const int v = atoi(e); if (v >= 0 && v <= 3) c->helper_prio = v; }   // uvrt_set_helper_priority's default

@@ -7,6 +7,16 @@ using namespace uvrt_impl;
 
 namespace uvrt_impl {
 
+// The chunk's key tiles and the strip of them a wave of the mark pass walks: DEDUPE_STRIP_TILES, and up to twice that where
+// the chunk still keeps 4 096 waves busy -- a longer strip spreads its one search over more tiles, a shorter one leaves a
+// small chunk more waves to cover each other's waits (DESIGN.md section 15 has the sweep).
+static void mark_tiles(const uvrt_ctx* c, GenDedupeParams& q)
+{
+    dedupe_tile_range(q.g, q.g0, q.gn, DEDUPE_MARK_KEYS, q.key_lo, q.tiles);
+    const int64_t fit = std::min<int64_t>(2 * DEDUPE_STRIP_TILES, std::max<int64_t>(DEDUPE_STRIP_TILES, q.tiles / 4096));
+    q.strip_tiles = c->dedupe_strip > 0 ? c->dedupe_strip : (int32_t)fit;
+}
+
 // uvrt_trace_batch and uvrt_trace_batch_launches (`who` names the caller in the error texts): generate + extend for `count`
 // launches, stops grouped by lamp column and traced by k_extend6, sweeps as one further group traced by the plane-aware
 // k_extend_free.  Physical planes: the stops' groups first, then the sweeps in logical order.
@@ -334,10 +344,10 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
                 dq.deposits = S.dd_counts.as<uint32_t>() + dd_chunks + dd_used++;
                 dq.cls = pc.cls;
                 dq.tmp = cur_lane(c).dd_tmp.as<uint32_t>();
-                dq.block_counts = cur_lane(c).dd_blocks.as<uint32_t>();
                 dq.g0 = first_gid + g0;
                 dq.gn = gn;
-                dedupe_tile_range(dq.g, dq.g0, dq.gn, DEDUPE_TILE_KEYS, dq.key_lo, dq.tiles);
+                dq.block_counts = cur_lane(c).dd_blocks.as<uint32_t>();
+                mark_tiles(c, dq);
                 dq.light_length = light_length;
                 dq.prio = c->helper_prio;
                 launch_generate_dedupe(dq, ls);
@@ -574,17 +584,25 @@ static bool chunk_ok(const DedupeGroup& G, int64_t chunk_first, int64_t chunk_n)
     return chunk_n > 0 && chunk_first >= G.first_gid && chunk_first + chunk_n <= G.first_gid + G.n;
 }
 
+int uvrt_dedupe_plan_strips(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                            int32_t seed_mode, int64_t first_gid, int64_t n, int32_t tile_keys, int32_t strip_tiles,
+                            int64_t chunk_first, int64_t chunk_n, uint32_t* masks)
+{
+    DedupeGroup G;
+    if (int rc = hook_group(G, "uvrt_dedupe_plan_tiled", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
+    if (!masks || tile_keys <= 0 || strip_tiles <= 0 || !chunk_ok(G, chunk_first, chunk_n))
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan_tiled: null masks, no tile width, no strip length, or a chunk outside the range");
+    std::vector<uint32_t> table((size_t)tile_keys);
+    dedupe_plan_tiled(G, tile_keys, strip_tiles, chunk_first, chunk_n, table.data(), masks);
+    return UVRT_OK;
+}
+
 int uvrt_dedupe_plan_tiled(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
                            int32_t seed_mode, int64_t first_gid, int64_t n, int32_t tile_keys, int64_t chunk_first,
                            int64_t chunk_n, uint32_t* masks)
 {
-    DedupeGroup G;
-    if (int rc = hook_group(G, "uvrt_dedupe_plan_tiled", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
-    if (!masks || tile_keys <= 0 || !chunk_ok(G, chunk_first, chunk_n))
-        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan_tiled: null masks, no tile width, or a chunk outside the range");
-    std::vector<uint32_t> table((size_t)tile_keys);
-    dedupe_plan_tiled(G, tile_keys, chunk_first, chunk_n, table.data(), masks);
-    return UVRT_OK;
+    return uvrt_dedupe_plan_strips(lamp, count, seed_prev, seed_next, seed_mode, first_gid, n, tile_keys, DEDUPE_STRIP_TILES, chunk_first,
+                                   chunk_n, masks);
 }
 
 int32_t uvrt_dedupe_classes_default(void) { return DEDUPE_CLASSES_DEFAULT; }
@@ -631,10 +649,10 @@ int uvrt_dedupe_mark_device(uvrt_ctx* c, const float lamp[3], int32_t count, con
     if (int rc = L.dd_tmp.ensure((size_t)count * (size_t)chunk_n * 4, false, c->stream)) return rc;
     if (int rc = L.dd_blocks.ensure((size_t)count * (size_t)((chunk_n + 255) / 256) * 4, true, c->stream)) return rc;
     dq.tmp = L.dd_tmp.as<uint32_t>();
-    dq.block_counts = L.dd_blocks.as<uint32_t>();
     dq.g0 = chunk_first;
     dq.gn = chunk_n;
-    dedupe_tile_range(dq.g, dq.g0, dq.gn, DEDUPE_TILE_KEYS, dq.key_lo, dq.tiles);
+    dq.block_counts = L.dd_blocks.as<uint32_t>();
+    mark_tiles(c, dq);
     dq.prio = c->helper_prio;
     launch_dedupe_mark(dq, c->stream);
     HIP_TRY(hipGetLastError());

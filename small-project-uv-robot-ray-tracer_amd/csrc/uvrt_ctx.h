@@ -212,6 +212,7 @@ struct uvrt_ctx {
                                           // beside a traversal grid (uvrt_device.h helper_priority); read at every launch
     bool dedupe = true;                   // uvrt_set_dedupe / UVRT_DEDUPE: a lamp's distinct rays are traced once per batch (uvrt_dedupe.h)
     int64_t b_traced_known = -1;          // uvrt_batch_traced_rays: the last traced batch's rays in chunks traced as they are ...
+    int32_t dedupe_strip = 0;             // tiles per wave of the mark pass (developer knob UVRT_DEDUPE_STRIP; 0: uvrt_capi_batch.hip mark_tiles)
     int32_t b_traced_chunks = 0;          // ... and its deduped chunks, whose counts are bs[b_set].dd_counts[0, b_traced_chunks)
     // mask classes of a batch's dedupe groups (uvrt_dedupe.h "mask classes")
     int32_t dedupe_classes = uvrt::DEDUPE_CLASSES_DEFAULT;     // uvrt_set_dedupe_classes / UVRT_DEDUPE_CLASSES: classes per group at most, 0 = none

@@ -76,12 +76,15 @@ UVRT_HD int32_t dedupe_key(const DedupeGroup& G, int j, int64_t gid)
     return (G.seed_mode == 1 && s < 0) ? 0 : s;
 }
 
-// the same for a gid >= 1 (no work-item 0 among them)
-UVRT_HD int32_t dedupe_key1(const DedupeGroup& G, int j, int32_t gid)
+// the same for a gid >= 1 (no work-item 0 among them): they all read one SEED of launch j, dedupe_seed1 (a kernel that walks
+// the launches keeps it in a register)
+UVRT_HD uint32_t dedupe_seed1(const DedupeGroup& G, int j) { return G.seed_mode == 1 ? G.seed_prev[j] : G.seed_next[j]; }
+UVRT_HD int32_t dedupe_key1_of(const DedupeGroup& G, uint32_t seed1, int32_t gid)
 {
-    const int32_t s = (int32_t)seed_sum_of(gid, G.seed_mode == 1 ? G.seed_prev[j] : G.seed_next[j], G.lx, G.ly, G.lz);
+    const int32_t s = (int32_t)seed_sum_of(gid, seed1, G.lx, G.ly, G.lz);
     return (G.seed_mode == 1 && s < 0) ? 0 : s;
 }
+UVRT_HD int32_t dedupe_key1(const DedupeGroup& G, int j, int32_t gid) { return dedupe_key1_of(G, dedupe_seed1(G, j), gid); }
 
 // Where key t sits among launch j's gids >= 1 of the call's range [lo, last]: walk from the estimate g (the keys never
 // decrease).  Returns the key found there (== t: a match at g).  (gids as int32: the range ends below DEDUPE_GID_END.)
@@ -149,7 +152,8 @@ UVRT_HD uint32_t dedupe_mask(const DedupeGroup& G, int k, int64_t gid)
 // the chunk from its key's entry: dedupe_mask()'s rule with m_j read from the table, K keys per gid instead of 3 K^2.
 // gid 0 reads the other SEED and is outside the monotone run: it belongs to the tile that holds key0[j].
 constexpr uint32_t DEDUPE_MANY = 1u << 31;     // (DEDUPE_MAX = 31 leaves the bit free)
-// the product's tile: the table, the run bounds and the owner counters stay within 16 KB of LDS (about 226 gids per launch)
+// the host's tile (the class tally and the deposit count below); the mark pass walks narrower ones, DEDUPE_MARK_KEYS -- the
+// masks do not depend on the width
 constexpr int32_t DEDUPE_TILE_KEYS = 3840;
 
 // The first gid of [lo, hi) whose key in launch j is >= t, or hi; lo >= 1.  From the estimate in doubling steps to a bracket,
@@ -188,10 +192,11 @@ UVRT_HD void dedupe_tile_run(const DedupeGroup& G, int j, int64_t t0, int32_t W,
     g_hi = dedupe_lower_bound(G, j, t0 + W, g_lo, hi);
 }
 // does the call's range hold launch j's gid 0, with its key in [t0, t0 + W)?
-UVRT_HD bool dedupe_tile_holds_gid0(const DedupeGroup& G, int j, int64_t t0, int32_t W)
+UVRT_HD bool dedupe_tile_holds_key0(const DedupeGroup& G, int32_t key0, int64_t t0, int32_t W)
 {
-    return G.first_gid == 0 && (int64_t)G.key0[j] >= t0 && (int64_t)G.key0[j] < t0 + W;
+    return G.first_gid == 0 && (int64_t)key0 >= t0 && (int64_t)key0 < t0 + W;
 }
+UVRT_HD bool dedupe_tile_holds_gid0(const DedupeGroup& G, int j, int64_t t0, int32_t W) { return dedupe_tile_holds_key0(G, G.key0[j], t0, W); }
 // the table entry of a key of the tile (t0 is a key of the group: it fits an int32), or W and more for a key outside it
 UVRT_HD uint32_t dedupe_tile_slot(int32_t key, int64_t t0) { return (uint32_t)key - (uint32_t)(int32_t)t0; }
 
@@ -231,20 +236,70 @@ UVRT_HD void dedupe_tile_range(const DedupeGroup& G, int64_t c0, int64_t cn, int
     tiles = cn > 0 ? (kmax - kmin) / W + 1 : 0;
 }
 
-// Host: the masks of the chunk [c0, c0 + cn) of a group's range, masks[k * cn + i], tile by tile with a table of W entries
-inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int64_t c0, int64_t cn, uint32_t* table, uint32_t* masks)
+// ---- Strips of narrow tiles (k_dedupe_mark: a wave owns a strip; dedupe_plan_tiled walks strips of a given length on the host) ----
+// The unit that owns a tile is one wave: a table of DEDUPE_MARK_KEYS entries (about 56 gids per launch, one round of a wave)
+// in 3 840 B of LDS, so four single-wave workgroups find room on a CU beside the other lane's traversal grid and none of them
+// meets another at a barrier.  A unit walks a STRIP of DEDUPE_STRIP_TILES consecutive tiles and carries the run bounds: a
+// tile's g_hi per launch is the next tile's g_lo, and g_hi is where the run's keys leave the tile -- found by the insert pass
+// itself, which looks at the keys from g_lo on anyway (dedupe_in_tile; the keys never decrease).  Only a strip's first tile
+// searches (one dedupe_lower_bound per launch).
+// The insert needs no answer from the table: a launch holds a key twice exactly where two NEIGHBOURING gids of its run hold it
+// (the keys never decrease from gid 1 on), so an occurrence knows from the keys at g - 1 and g + 1 whether to set
+// DEDUPE_MANY (dedupe_run_twice, dedupe_tile_insert_run: one OR, nothing read back, no wait between the launches' inserts).
+// gid 0 is outside the monotone run: it goes in last, with dedupe_tile_insert, which reads the entry.
+constexpr int32_t DEDUPE_MARK_KEYS = 960;
+constexpr int32_t DEDUPE_STRIP_TILES = 4;
+
+// is `key`, the key of a gid >= g_lo of a launch whose run starts at g_lo, still in the tile?  (key >= t0 there)
+UVRT_HD bool dedupe_in_tile(int32_t key, int64_t t0, int32_t W) { return dedupe_tile_slot(key, t0) < (uint32_t)W; }
+// does the launch with dedupe_seed1 `seed1` hold `key`, the key of its gid g, at a neighbour of g among the gids [lo, hi)
+// too?  lo >= 1
+UVRT_HD bool dedupe_run_twice(const DedupeGroup& G, uint32_t seed1, int32_t g, int32_t key, int32_t lo, int32_t hi)
+{
+    const int before = (g > lo) & (dedupe_key1_of(G, seed1, g - 1) == key), after = (g + 1 < hi) & (dedupe_key1_of(G, seed1, g + 1) == key);
+    return (before | after) != 0;
+}
+// one occurrence of launch j's run at `slot`; twice: dedupe_run_twice
+UVRT_HD void dedupe_tile_insert_run(uint32_t* table, uint32_t slot, int j, bool twice)
+{
+    const uint32_t v = (1u << j) | (twice ? DEDUPE_MANY : 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicOr(&table[slot], v);
+#else
+    table[slot] |= v;
+#endif
+}
+// the first gid (>= 1) of the call's range whose key in launch j is >= t0: launch j's g_lo in the tile at t0
+UVRT_HD int32_t dedupe_strip_first(const DedupeGroup& G, int j, int64_t t0)
+{
+    return dedupe_lower_bound(G, j, t0, (int32_t)(G.first_gid > 1 ? G.first_gid : 1), (int32_t)(G.first_gid + G.n));
+}
+
+// Host: the masks of the chunk [c0, c0 + cn) of a group's range, masks[k * cn + i], tile by tile with a table of W entries,
+// in strips of `strip` tiles with carried bounds as the device walks them (the device's strip length is its launcher's choice,
+// DEDUPE_STRIP_TILES and more; the masks depend on it as little as on W)
+inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int32_t strip, int64_t c0, int64_t cn, uint32_t* table, uint32_t* masks)
 {
     int64_t key_lo, tiles;
     dedupe_tile_range(G, c0, cn, W, key_lo, tiles);
+    const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
+    int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
     for (int64_t tile = 0; tile < tiles; ++tile) {
         const int64_t t0 = key_lo + tile * W;
-        int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
         for (int32_t i = 0; i < W; ++i) table[i] = 0u;
         for (int j = 0; j < G.count; ++j) {
-            dedupe_tile_run(G, j, t0, W, g_lo[j], g_hi[j]);
-            for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) dedupe_tile_insert(table, dedupe_tile_slot(dedupe_key1(G, j, g), t0), j);
-            if (dedupe_tile_holds_gid0(G, j, t0, W)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
+            g_lo[j] = tile % strip == 0 ? dedupe_strip_first(G, j, t0) : g_hi[j];
+            const uint32_t seed1 = dedupe_seed1(G, j);
+            int32_t g = g_lo[j];
+            for (; g < hi; ++g) {
+                const int32_t key = dedupe_key1_of(G, seed1, g);
+                if (!dedupe_in_tile(key, t0, W)) break;
+                dedupe_tile_insert_run(table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(G, seed1, g, key, lo, hi));
+            }
+            g_hi[j] = g;
         }
+        for (int j = 0; j < G.count; ++j)
+            if (dedupe_tile_holds_gid0(G, j, t0, W)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
         for (int k = 0; k < G.count; ++k) {
             const int64_t a = g_lo[k] > c0 ? g_lo[k] : c0, b = g_hi[k] < c0 + cn ? g_hi[k] : c0 + cn;
             for (int64_t g = a; g < b; ++g)

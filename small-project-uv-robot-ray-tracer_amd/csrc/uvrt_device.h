@@ -174,7 +174,7 @@ struct GenBatchParams {
 };
 
 // The distinct rays of a dedupe group (uvrt_dedupe.h) over the gids [g0, g0 + gn) of all its launches, compacted: the owners'
-// rays in (launch, gid) order with their masks beside them.  Three kernels: mark (the owner test over key tiles, a count per
+// rays in (launch, gid) order with their masks beside them.  Three kernels: mark (the owner test over strips of key tiles, a count per
 // launch and block of DD_SLOTS gids), scan, write (the f64 direction code, for owners only).  The order is a function of the
 // group alone; the count stays on the device.
 constexpr int DD_ROUNDS = 8, DD_SLOTS = 256 * DD_ROUNDS;      // gids per workgroup of the write pass and per owner count
@@ -187,7 +187,8 @@ struct GenDedupeParams {
     uint32_t* block_counts;            // scratch [count * ceil(gn / 2048)] (sized for ceil(gn / 256) by the caller): ZERO before
                                        // mark, which adds the owners; offsets after the scan; write leaves it zero again
     int64_t g0, gn;
-    int64_t key_lo, tiles;             // the chunk's key tiles (dedupe_tile_range with DEDUPE_TILE_KEYS)
+    int64_t key_lo, tiles;             // the chunk's key tiles (dedupe_tile_range with DEDUPE_MARK_KEYS)
+    int32_t strip_tiles;               // consecutive tiles a wave of the mark pass walks (at least 1)
     float light_length;
     int32_t prio;                      // helper_priority of the three kernels
     uint32_t* deposits;                // out: the atomics these rays issue when each of them hits (dedupe_word_deposits summed)

@@ -83,72 +83,108 @@ __global__ __launch_bounds__(256) void k_generate_batch(GenBatchParams p)
 // DD_SLOTS gids of the chunk, DD_ROUNDS per thread (few workgroup counts for the one-workgroup scan between the passes).
 //
 // mark: every occurrence's mask (uvrt_dedupe.h: 0 = another occurrence traces this ray) and the owners per launch and block
-// of DD_SLOTS gids, one workgroup per key tile (uvrt_dedupe.h, "one pass per key tile").  Every launch's gid run of the tile
-// goes into a table in LDS, a barrier, then every occurrence of the chunk reads its mask from its key's entry.  The owners
-// are counted with integer adds -- per wave, in LDS for the two blocks a run usually touches, one global add per block -- so
-// the counts and the compaction order stay a function of the group alone.  block_counts is zero on entry (k_dedupe_write
-// leaves it so).  16 KB of LDS: the kernel finds room on a CU beside the other lane's persistent traversal grid.
-__global__ __launch_bounds__(256) void k_dedupe_mark(GenDedupeParams p)
+// of DD_SLOTS gids.  One WAVE per strip of key tiles (uvrt_dedupe.h, "strips of narrow tiles"), a workgroup of its own: beside
+// the other lane's persistent traversal grid a CU has four wave slots and 20 KB of LDS left, and four such workgroups of
+// 3 840 B take them and cover each other's waits; none waits for another.  Per tile every launch's gid run goes into a table
+// in LDS with one OR each and nothing read back -- the run's end is where its keys leave the tile, and that is the next
+// tile's start -- then every occurrence of the chunk reads its mask from its key's entry.  The owners are counted with
+// integer adds: a ballot per round, kept by lane j for launch j while the strip stays in one block, one global add per block
+// and strip -- so the counts and the compaction order stay a function of the group alone.  block_counts is zero on entry
+// (k_dedupe_write leaves it so).
+__global__ __launch_bounds__(64) void k_dedupe_mark(GenDedupeParams p)
 {
     helper_priority(p.prio);
-    constexpr int32_t W = DEDUPE_TILE_KEYS;
+    constexpr int32_t W = DEDUPE_MARK_KEYS;
     __shared__ uint32_t s_table[W];
-    __shared__ int32_t s_run[DEDUPE_MAX][2];
-    __shared__ uint32_t s_cnt[DEDUPE_MAX * 2];
-    const int tid = threadIdx.x, K = p.g.count;
-    const int64_t t0 = p.key_lo + (int64_t)blockIdx.x * W;
+    const int lane = threadIdx.x, K = p.g.count;
     const uint32_t nb = (uint32_t)((p.gn + DD_SLOTS - 1) / DD_SLOTS);
-    for (int i = tid; i < W; i += 256) s_table[i] = 0u;
-    if (tid < 2 * K) s_cnt[tid] = 0u;
-    if (tid < K) {      // the run bounds are uniform work: a lane per launch finds them
-        int32_t g_lo, g_hi;
-        dedupe_tile_run(p.g, tid, t0, W, g_lo, g_hi);
-        s_run[tid][0] = g_lo;
-        s_run[tid][1] = g_hi;
+    // (gids as int32: the range ends below DEDUPE_GID_END)
+    const int32_t lo = (int32_t)(p.g.first_gid > 1 ? p.g.first_gid : 1), hi = (int32_t)(p.g.first_gid + p.g.n);
+    const int32_t c0 = (int32_t)p.g0, c1 = (int32_t)(p.g0 + p.gn);
+    const int64_t tile0 = (int64_t)blockIdx.x * p.strip_tiles;
+    const int64_t tile1 = tile0 + p.strip_tiles < p.tiles ? tile0 + p.strip_tiles : p.tiles;
+    // lane j keeps what is uniform per launch j: its run [run_lo, run_hi) in the current tile, and the owners of its current
+    // block that no global add has taken yet; its SEED and the key of its gid 0, so that no loop below waits for a load
+    int32_t run_lo = hi, run_hi = hi, key0 = 0;
+    uint32_t seed1 = 0u;
+    if (lane < K) {
+        run_lo = dedupe_strip_first(p.g, lane, p.key_lo + tile0 * W);      // the strip's one search per launch
+        seed1 = dedupe_seed1(p.g, lane);
+        key0 = p.g.key0[lane];
     }
-    __syncthreads();
-    for (int j = 0; j < K; ++j) {
-        const int32_t hi = s_run[j][1];
-        for (int32_t g = s_run[j][0] + tid; g < hi; g += 256) {
-            const uint32_t slot = dedupe_tile_slot(dedupe_key1(p.g, j, g), t0);
-            if (slot < (uint32_t)W) dedupe_tile_insert(s_table, slot, j);
-        }
-    }
-    if (tid < K && dedupe_tile_holds_gid0(p.g, tid, t0, W)) dedupe_tile_insert(s_table, dedupe_tile_slot(p.g.key0[tid], t0), tid);
-    __syncthreads();
-    const int32_t c0 = (int32_t)p.g0, c1 = (int32_t)(p.g0 + p.gn);      // (gids as int32: the range ends below DEDUPE_GID_END)
-    for (int j = 0; j < K; ++j) {
-        const int32_t a = max(s_run[j][0], c0), b = min(s_run[j][1], c1);
-        const uint32_t b0 = (uint32_t)(a - c0) / (uint32_t)DD_SLOTS;      // (read only where a < b)
-        for (int32_t base = a; base < b; base += 256) {                   // (uniform trips: every lane takes part in the ballots)
-            const int32_t g = base + tid;
-            uint32_t mask = 0u, rel = 0u;
-            if (g < b) {
-                const uint32_t slot = dedupe_tile_slot(dedupe_key1(p.g, j, g), t0);
-                mask = dedupe_tile_resolve(slot < (uint32_t)W ? s_table[slot] : DEDUPE_MANY, j);
-                p.tmp[(int64_t)j * p.gn + (g - c0)] = mask;
-                rel = (uint32_t)(g - c0) / (uint32_t)DD_SLOTS - b0;
+    uint32_t cnt_block = 0u, cnt = 0u;
+    const auto add_owners = [&](int j, uint32_t block, uint32_t owners) { atomicAdd(&p.block_counts[(size_t)j * nb + block], owners); };
+    const auto count_owners = [&](int j, uint32_t block, uint32_t owners) {        // (uniform arguments)
+        if (lane == j && owners != 0u) {
+            if (block != cnt_block) {
+                if (cnt != 0u) add_owners(j, cnt_block, cnt);
+                cnt_block = block;
+                cnt = 0u;
             }
-            const uint32_t n0 = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u && rel == 0u));
-            const uint32_t n1 = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u && rel == 1u));
-            if ((tid & 63) == 0) {
-                if (n0) atomicAdd(&s_cnt[2 * j], n0);
-                if (n1) atomicAdd(&s_cnt[2 * j + 1], n1);
-            }
-            if (mask != 0u && rel >= 2u) atomicAdd(&p.block_counts[(size_t)j * nb + b0 + rel], 1u);      // (a long run: key 0 of seed mode 1)
+            cnt += owners;
         }
+    };
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const int64_t t0 = p.key_lo + tile * W;
+        static_assert(W % 64 == 0, "the wave zeroes the table in whole rounds");
+#pragma unroll
+        for (int i = 0; i < W; i += 64) s_table[i + lane] = 0u;
+        __syncthreads();      // (a workgroup of one wave: no s_barrier, the wave's LDS accesses stay in order)
+        // insert: launch j's run from its g_lo on, 64 gids a round, until its keys leave the tile -- that is its g_hi
+        for (int j = 0; j < K; ++j) {
+            int32_t base = __builtin_amdgcn_readlane(run_lo, j);
+            const uint32_t seed = (uint32_t)__builtin_amdgcn_readlane((int)seed1, j);
+            for (;;) {
+                const int32_t g = base + lane;
+                bool in = false;
+                if (g < hi) {
+                    const int32_t key = dedupe_key1_of(p.g, seed, g);
+                    in = dedupe_in_tile(key, t0, W);
+                    if (in) dedupe_tile_insert_run(s_table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(p.g, seed, g, key, lo, hi));
+                }
+                const int32_t n_in = (int32_t)__popcll(__builtin_amdgcn_ballot_w64(in));      // (a prefix of the lanes: the keys never decrease)
+                base += n_in;
+                if (n_in < 64) break;
+            }
+            if (lane == j) run_hi = base;
+        }
+        const bool holds0 = lane < K && dedupe_tile_holds_key0(p.g, key0, t0, W);      // gid 0 of launch `lane`: last, reading the entry
+        if (holds0) dedupe_tile_insert(s_table, dedupe_tile_slot(key0, t0), lane);
+        __syncthreads();
+        // resolve: every occurrence of the chunk reads its mask from its key's entry; the owners per block of DD_SLOTS gids
+        for (int j = 0; j < K; ++j) {
+            const int32_t a = max(__builtin_amdgcn_readlane(run_lo, j), c0), b = min(__builtin_amdgcn_readlane(run_hi, j), c1);
+            const uint32_t seed = (uint32_t)__builtin_amdgcn_readlane((int)seed1, j);
+            for (int32_t base = a; base < b; base += 64) {                    // (uniform trips: every lane takes part in the ballots)
+                const int32_t g = base + lane;
+                const uint32_t fb = (uint32_t)(base - c0) / (uint32_t)DD_SLOTS;      // the round's first block; 64 gids touch two at most
+                uint32_t mask = 0u, blk = fb;
+                if (g < b) {
+                    const uint32_t slot = dedupe_tile_slot(dedupe_key1_of(p.g, seed, g), t0);
+                    mask = dedupe_tile_resolve(slot < (uint32_t)W ? s_table[slot] : DEDUPE_MANY, j);
+                    p.tmp[(int64_t)j * p.gn + (g - c0)] = mask;
+                    blk = (uint32_t)(g - c0) / (uint32_t)DD_SLOTS;
+                }
+                const int32_t last = min(base + 63, b - 1);
+                if ((uint32_t)(last - c0) / (uint32_t)DD_SLOTS == fb) {      // (uniform; one round in 32 meets a block's end)
+                    count_owners(j, fb, (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u)));
+                } else {
+                    const uint32_t n0 = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u && blk == fb));
+                    const uint32_t n1 = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(mask != 0u && blk != fb));
+                    count_owners(j, fb, n0);
+                    count_owners(j, fb + 1u, n1);
+                }
+            }
+        }
+        if (c0 == 0 && holds0) {      // work-item 0 of launch `lane`
+            const uint32_t mask = dedupe_tile_resolve(s_table[dedupe_tile_slot(key0, t0)], lane);
+            p.tmp[(int64_t)lane * p.gn] = mask;
+            if (mask != 0u) add_owners(lane, 0u, 1u);
+        }
+        run_lo = run_hi;      // carried: where a launch's keys left this tile they enter the next
+        __syncthreads();      // (the table is zeroed again behind the reads)
     }
-    if (c0 == 0 && tid < K && dedupe_tile_holds_gid0(p.g, tid, t0, W)) {      // work-item 0 of launch `tid`
-        const uint32_t mask = dedupe_tile_resolve(s_table[dedupe_tile_slot(p.g.key0[tid], t0)], tid);
-        p.tmp[(int64_t)tid * p.gn] = mask;
-        if (mask != 0u) atomicAdd(&p.block_counts[(size_t)tid * nb], 1u);
-    }
-    __syncthreads();
-    if (tid < 2 * K && s_cnt[tid] != 0u) {
-        const int j = tid >> 1;
-        const uint32_t b0 = (uint32_t)(max(s_run[j][0], c0) - c0) / (uint32_t)DD_SLOTS;
-        atomicAdd(&p.block_counts[(size_t)j * nb + b0 + (uint32_t)(tid & 1)], s_cnt[tid]);
-    }
+    if (lane < K && cnt != 0u) add_owners(lane, cnt_block, cnt);
 }
 
 // scan: the workgroups' counts -> their first slot in the compacted list, in (launch, gid) order; the total.  One workgroup
@@ -668,8 +704,8 @@ void launch_generate_batch(const GenBatchParams& p, hipStream_t s)
 
 void launch_dedupe_mark(const GenDedupeParams& p, hipStream_t s)
 {
-    if (p.gn <= 0 || p.g.count <= 0 || p.tiles <= 0) return;
-    hipLaunchKernelGGL(k_dedupe_mark, dim3((unsigned)p.tiles), dim3(256), 0, s, p);
+    if (p.gn <= 0 || p.g.count <= 0 || p.tiles <= 0 || p.strip_tiles <= 0) return;
+    hipLaunchKernelGGL(k_dedupe_mark, dim3((unsigned)((p.tiles + p.strip_tiles - 1) / p.strip_tiles)), dim3(64), 0, s, p);
 }
 
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s)
