@@ -241,6 +241,53 @@ int uvrt_read_expected(uvrt_ctx* ctx, double* out, int32_t first, int32_t count)
  * writes is one irradiance estimate; a caller may capture an estimate of their own (uvrt_plan_capture_expected). */
 int uvrt_write_expected(uvrt_ctx* ctx, const double* in, int32_t first, int32_t count);
 
+/* ---- adaptive gather: extra shadow rays for the triangles whose estimate is the least certain ----
+ * uvrt_gather_direct spends the same S samples on every triangle; its variance plane says where they were too few.
+ * uvrt_gather_refine draws n_t further samples for triangle t, chosen from (expected[t], variance[t]), and merges them into
+ * both planes.
+ *
+ * What it works on: the context remembers the last successful uvrt_gather_direct that ran with the variance plane on -- its
+ * range, S0 = samples, seed, sampling mode, from, to, light_length and photons_equiv.  Host state only: no device work, no
+ * existing result changes.  The refined range lies inside the remembered one; geometry, photons_equiv, S0 and the mode are the
+ * remembered call's (not the context's current sampling mode).  The remembered gather is forgotten by a successful refine (one
+ * refine per gather), uvrt_gather_direct with the variance off, uvrt_accumulate_expected, uvrt_write_expected /
+ * uvrt_write_variance and uvrt_set_scene; uvrt_plan_capture_expected, uvrt_occluded and the read calls leave it.
+ *
+ * The count rule, for t in the range, X0 = expected[t], V0 = variance[t], nn as above; f64, one rounding per operator:
+ *     if (nn == 0 || !(X0 > 0) || !(V0 > 0) || X0 < min_expected)  n_t = 0
+ *     else  r = rel_error * X0;  want = ceil((double)S0 * (V0 / (r * r) - 1.0))
+ *           !(want >= 1): n_t = 0 (NaN included);  want >= max_extra: n_t = max_extra;
+ *           otherwise n_t = the smallest power of two >= max(want, 2)
+ * (S0 samples gave V0, so S0 + n samples of the same scatter give about V0 S0 / (S0 + n): `want` is the n that brings
+ * sqrt(variance) / expected to rel_error.)  A triangle whose first pass saw no scatter (V0 = 0: every sample occluded, or all
+ * equal) is never refined.
+ * The extra samples of a triangle with n_t > 0 are, bit for bit, the samples uvrt_gather_direct would draw for triangle t with
+ * samples = n_t, seed = params->seed and the remembered mode and lamp: j = t * n_t + s, and the stratified mode has n_t strata.
+ * With x_s = occluded ? 0 : w_s, X1 and V1 are expected[t] and variance[t] as that call would write them, and in place
+ *     a = (double)S0, b = (double)n_t, tot = a + b
+ *     expected[t] = (a * X0 + b * X1) / tot
+ *     variance[t] = ((a * a) * V0 + (b * b) * V1) / (tot * tot)
+ * A triangle with n_t = 0 keeps every bit of both planes.  The result is a pure function of the planes and the arguments,
+ * whatever the capacity (rays go in chunks of whole triangles, at most `capacity` each) or the cut of the range into calls.
+ * Device path: count, an exclusive prefix sum, ONE read-back of the offsets (the call synchronises there), then per chunk
+ * generate -> the shadow-ray kernel -> reduce; nothing is launched after the scan when no triangle wants a sample.
+ * Like uvrt_gather_direct the call drops "the last generate" and leaves SEED and tempPhotonMap untouched.
+ * UVRT_ERR_INVALID with nothing changed: no remembered gather, a range outside it, seed equal to the gather's, flavour 2, a
+ * limit of the struct, a null context or params. */
+typedef struct {
+    double  rel_error;     /* tau: target sqrt(variance)/expected; finite, > 0 */
+    double  min_expected;  /* triangles with expected < this are left alone; finite, >= 0 (0: none) */
+    int32_t max_extra;     /* power of two in [2, 4096]; <= capacity; T * max_extra < 2^31 */
+    uint32_t seed;         /* seed of the extra samples; must differ from the refined gather's seed */
+    int32_t reserved[2];   /* 0 */
+} uvrt_refine_params;
+typedef struct { int64_t extra_rays; int32_t refined; int32_t reserved; } uvrt_refine_report;   /* sum of n_t; triangles with n_t > 0 */
+int uvrt_gather_refine(uvrt_ctx* ctx, const uvrt_refine_params* params, int32_t first_tri, int32_t tri_count,
+                       uvrt_refine_report* report /* may be NULL */);
+/* test hook: n_t of the last uvrt_gather_refine, int32[T]; 0 outside its range (and before the first refine of a scene);
+ * synchronises */
+int uvrt_read_gather_extra(uvrt_ctx* ctx, int32_t* out, int32_t first, int32_t count);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).

@@ -127,6 +127,8 @@ SYMBOLS = [
     ("uvrt_plan_begin_expected_variance", C.c_int, [_vp, _i32]),
     ("uvrt_plan_read_exposure_variance", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_plan_lower_confidence", C.c_int, [_vp, C.c_double]),
+    ("uvrt_gather_refine", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    ("uvrt_read_gather_extra", C.c_int, [_vp, _vp, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -136,6 +138,17 @@ class GatherParams(C.Structure):
     """uvrt_gather_params (include/uvrt.h)"""
     _fields_ = [("from_", C.c_float * 3), ("to", C.c_float * 3), ("light_length", C.c_float), ("samples", C.c_int32),
                 ("seed", C.c_uint32), ("photons_equiv", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class RefineParams(C.Structure):
+    """uvrt_refine_params (include/uvrt.h)"""
+    _fields_ = [("rel_error", C.c_double), ("min_expected", C.c_double), ("max_extra", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class RefineReport(C.Structure):
+    """uvrt_refine_report (include/uvrt.h)"""
+    _fields_ = [("extra_rays", C.c_int64), ("refined", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PlanParams(C.Structure):
@@ -510,6 +523,26 @@ class Ctx:
         """host values into variance[first, first + len(values))"""
         v = np.ascontiguousarray(values, dtype=np.float64)
         self._ck(self._L.uvrt_write_variance(self._h, _ptr(v), int(first), int(v.size)))
+
+    def gather_refine(self, rel_error, max_extra, seed, min_expected=0.0, first_tri=0, tri_count=None):
+        """extra shadow rays for the triangles of the remembered gather whose sqrt(variance) / expected exceeds rel_error,
+        merged into both planes (include/uvrt.h "adaptive gather"); returns (extra rays, refined triangles)"""
+        prm = RefineParams()
+        prm.rel_error = float(rel_error)
+        prm.min_expected = float(min_expected)
+        prm.max_extra = int(max_extra)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        rep = RefineReport()
+        self._ck(self._L.uvrt_gather_refine(self._h, C.byref(prm), int(first_tri),
+                                            self.T - int(first_tri) if tri_count is None else int(tri_count), C.byref(rep)))
+        return int(rep.extra_rays), int(rep.refined)
+
+    def read_gather_extra(self, first=0, count=None):
+        """n_t of the last gather_refine, int32; 0 outside its range"""
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.int32)
+        self._ck(self._L.uvrt_read_gather_extra(self._h, _ptr(out), int(first), int(count)))
+        return out
 
     @property
     def seed(self):

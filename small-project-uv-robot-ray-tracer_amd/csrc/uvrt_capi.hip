@@ -373,6 +373,8 @@ int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes
     c->g_tris_valid = false;
     c->expected.release();
     c->variance.release();
+    c->g_extra.release();
+    c->gather_memo = {};                              // a refine works on one scene's planes
     c->scene_force_exact = tiny_bound || huge_vertex;
     if ((rc = hot_reset(c, true))) return rc;         // statistics of the previous scene; the new scene's first slab
     HIP_TRY(hipStreamSynchronize(c->stream));

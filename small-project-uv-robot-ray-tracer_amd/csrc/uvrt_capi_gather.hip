@@ -1,7 +1,7 @@
 // uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
 // uvrt_occluded, uvrt_set_gather_sampling, uvrt_get_gather_sampling, uvrt_set_gather_variance, uvrt_get_gather_variance,
 // uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected, uvrt_write_expected, uvrt_read_variance,
-// uvrt_write_variance (uvrt_occlude.hip's kernels)
+// uvrt_write_variance (uvrt_occlude.hip's kernels); uvrt_gather_refine, uvrt_read_gather_extra (uvrt_refine.hip's)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
@@ -130,6 +130,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: %d triangles x %d samples do not fit 2^31 sample numbers", c->T, S);
     if (prm->photons_equiv <= 0) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: photons_equiv must be > 0");
     if (int rc = set_device(c)) return rc;
+    c->gather_memo = {};                    // remembered again below, when this call has written both planes
     if (int rc = begin_shadow_launch(c)) return rc;
     const size_t cap = (size_t)c->capacity;
     if (int rc = c->g_w.ensure(cap * 8, false, c->stream)) return rc;
@@ -174,6 +175,16 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
                                  prm->photons_equiv, c->stream);
         HIP_TRY(hipGetLastError());
     }
+    if (var) {
+        uvrt_ctx::GatherMemo m;
+        m.valid = true;
+        m.first = first_tri; m.count = tri_count; m.samples = S; m.mode = g.mode; m.photons_equiv = prm->photons_equiv;
+        m.seed = prm->seed;
+        memcpy(m.from, prm->from, 12);
+        memcpy(m.to, prm->to, 12);
+        m.light_length = prm->light_length;
+        c->gather_memo = m;
+    }
     return UVRT_OK;
 }
 
@@ -184,6 +195,7 @@ int uvrt_accumulate_expected(uvrt_ctx* c, float time_step, int32_t tri_count)
     if (int rc = set_device(c)) return rc;       // (an accumulate that uvrt_accumulate has deferred goes first: launch order)
     if (int rc = join_all(c)) return rc;
     if (int rc = ensure_expected(c)) return rc;
+    c->gather_memo = {};                         // the estimate is consumed: nothing left to refine
     c->ext_touch_maps = false;                   // (on the context's stream, behind the caller's work: the fence below covers it)
     launch_accumulate_expected(c->photon_map.as<double>(), c->max_map.as<double>(), c->expected.as<double>(), time_step,
                                tri_count, c->stream);
@@ -203,6 +215,7 @@ static int plane_range(uvrt_ctx* c, const char* who, bool variance, void* host, 
         return fail(UVRT_ERR_INVALID, "%s: range [%d,+%d) outside [0,%d)", who, first, count, c->T);
     if (int rc = set_device(c)) return rc;
     if (int rc = variance ? ensure_variance(c) : ensure_expected(c)) return rc;
+    if (kind == hipMemcpyHostToDevice) c->gather_memo = {};     // the planes are the caller's now, not the remembered gather's
     return range_copy(c, variance ? c->variance.p : c->expected.p, 8, host, first, count, kind);
 }
 
@@ -224,6 +237,100 @@ int uvrt_read_variance(uvrt_ctx* c, double* out, int32_t first, int32_t count)
 int uvrt_write_variance(uvrt_ctx* c, const double* in, int32_t first, int32_t count)
 {
     return plane_range(c, "uvrt_write_variance", true, const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
+}
+
+int uvrt_gather_refine(uvrt_ctx* c, const uvrt_refine_params* prm, int32_t first_tri, int32_t tri_count, uvrt_refine_report* report)
+{
+    if (!c || !prm) return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: no scene");
+    if (c->flavour != 0 && c->flavour != 1)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: shadow rays are traced in flavours 0 and 1 only (uvrt_set_flavour %d)", c->flavour);
+    const uvrt_ctx::GatherMemo m = c->gather_memo;
+    if (!m.valid)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: no remembered gather (uvrt_gather_direct with uvrt_set_gather_variance(1), not yet refined or consumed)");
+    if (first_tri < m.first || tri_count < 0 || (int64_t)first_tri + tri_count > (int64_t)m.first + m.count)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: triangles [%d, +%d) outside the remembered gather's [%d, +%d)", first_tri,
+                    tri_count, m.first, m.count);
+    if (!(prm->rel_error > 0.0) || !std::isfinite(prm->rel_error))
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: rel_error must be finite and > 0");
+    if (!(prm->min_expected >= 0.0) || !std::isfinite(prm->min_expected))
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: min_expected must be finite and >= 0");
+    const int32_t M = prm->max_extra;
+    if (M < 2 || M > 4096 || (M & (M - 1)) != 0)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: max_extra = %d must be a power of two in [2, 4096]", M);
+    if ((int64_t)M > c->capacity)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: max_extra = %d exceeds the ray capacity %lld (uvrt_resize_rays)", M, (long long)c->capacity);
+    if ((int64_t)c->T * M >= ((int64_t)1 << 31))
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: %d triangles x %d samples do not fit 2^31 sample numbers", c->T, M);
+    if (prm->seed == m.seed)
+        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: seed %u is the refined gather's: the extra samples would repeat its own", prm->seed);
+    if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: reserved fields must be 0");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = begin_shadow_launch(c)) return rc;
+    const size_t cap = (size_t)c->capacity;
+    if (int rc = c->g_w.ensure(cap * 8, false, c->stream)) return rc;
+    if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
+    if (int rc = c->g_offs.ensure(((size_t)c->T + 1) * 4, false, c->stream)) return rc;
+    if (int rc = c->g_scan.ensure(((size_t)c->T / 1024 + 1) * 4, false, c->stream)) return rc;
+    if (report) *report = {};
+    // (the remembered gather made g_tris and both planes, and whatever releases them -- uvrt_set_scene -- forgets it)
+    const float4* gtris = c->g_tris.as<float4>();
+    int32_t* offs = c->g_offs.as<int32_t>();
+    launch_refine_count(gtris, c->expected.as<double>(), c->variance.as<double>(), c->g_extra.as<int32_t>(), c->T, first_tri,
+                        tri_count, m.samples, prm->rel_error, prm->min_expected, M, c->stream);
+    launch_refine_scan(c->g_extra.as<int32_t>(), offs, c->g_scan.as<int32_t>(), first_tri, tri_count, c->stream);
+    HIP_TRY(hipGetLastError());
+    // the call's one round trip: the offsets, to cut the range into chunks of at most `capacity` rays
+    std::vector<int32_t> h((size_t)tri_count + 1);
+    if (int rc = copy_sync(c, h.data(), offs, h.size() * 4, hipMemcpyDeviceToHost)) return rc;
+    c->gather_memo = {};                    // one refine per gather
+    Lane& L = c->lanes[0];
+    GatherGenParams g;
+    memset(&g, 0, sizeof g);
+    g.gtris = gtris;
+    g.rays = L.rays.as<float4>();
+    g.oxz = c->g_oxz.as<float2>();
+    g.tmax = c->g_tmax.as<float>();
+    g.w = c->g_w.as<double>();
+    g.fx = m.from[0]; g.fy = m.from[1]; g.fz = m.from[2];
+    g.tx = m.to[0]; g.ty = m.to[1]; g.tz = m.to[2];
+    g.light_length = m.light_length;
+    g.seed_hash = host_wang_hash(prm->seed);
+    g.first_tri = first_tri;
+    g.tri_count = tri_count;
+    g.seed = prm->seed;
+    g.mode = m.mode;
+    // chunks, greedily from consecutive triangles: a triangle's samples never straddle two of them (n_t <= max_extra <=
+    // capacity, so every chunk takes at least one triangle), and the chunking shows in no bit
+    int32_t refined = 0;
+    for (int32_t lo = 0; lo < tri_count;) {
+        int32_t hi = lo + 1;
+        while (hi < tri_count && (int64_t)h[hi + 1] - h[lo] <= c->capacity) ++hi;
+        const int32_t rays = h[hi] - h[lo];
+        for (int32_t i = lo; i < hi; ++i) refined += h[i + 1] > h[i];
+        if (rays > 0) {
+            launch_refine_generate(g, offs, lo, hi, rays, c->stream);
+            HIP_TRY(hipGetLastError());
+            if (int rc = trace_shadow_rays(c, rays, "uvrt_gather_refine")) return rc;
+            launch_refine_reduce(gtris, g.w, c->g_occ.as<uint8_t>(), offs, c->expected.as<double>(), c->variance.as<double>(),
+                                 first_tri, lo, hi, m.samples, m.photons_equiv, m.mode, c->stream);
+            HIP_TRY(hipGetLastError());
+        }
+        lo = hi;
+    }
+    if (report) { report->extra_rays = h[tri_count]; report->refined = refined; }
+    return UVRT_OK;
+}
+
+int uvrt_read_gather_extra(uvrt_ctx* c, int32_t* out, int32_t first, int32_t count)
+{
+    if (!c || !out) return fail(UVRT_ERR_INVALID, "uvrt_read_gather_extra: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_read_gather_extra: no scene");
+    if (!range_ok(out, first, count, c->T))
+        return fail(UVRT_ERR_INVALID, "uvrt_read_gather_extra: range [%d,+%d) outside [0,%d)", first, count, c->T);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
+    return range_copy(c, c->g_extra.p, 4, out, first, count, hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 //   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / uvrt_trace_batch_launches / fold / replay)
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
-//                         uvrt_set_gather_variance and the variance plane)
+//                         uvrt_set_gather_variance and the variance plane, uvrt_gather_refine)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -142,6 +142,17 @@ struct uvrt_ctx {
     // weights, the triangles by original id, the expected plane f64[T] and the variance plane f64[T] beside it; all made on
     // first use.  (The rays themselves go through lane 0's ray buffer, on the context's stream.)
     DevBuf g_oxz, g_tmax, g_occ, g_w, g_tris, expected, variance;
+    // uvrt_gather_refine (include/uvrt.h "adaptive gather"): n_t of the last refine, int32[T] (made zeroed on first use, per
+    // scene); the exclusive prefix sums of a refined range, int32[T + 1], and the scan's per-block totals
+    DevBuf g_extra, g_offs, g_scan;
+    // the last successful uvrt_gather_direct with the variance plane on: what uvrt_gather_refine refines.  Host state only.
+    // Assigned whole; `valid` false: forgotten.
+    struct GatherMemo {
+        bool valid = false;
+        int32_t first = 0, count = 0, samples = 0, mode = 0, photons_equiv = 0;
+        uint32_t seed = 0;
+        float from[3] = {0, 0, 0}, to[3] = {0, 0, 0}, light_length = 0;
+    } gather_memo;
     bool g_tris_valid = false;                 // g_tris holds the current scene
 
     // Launch lanes: consecutive launches (generate -> extend -> accumulate ->

@@ -461,4 +461,21 @@ void launch_gather_reduce_var(const float4* gtris, const double* w, const uint8_
 // accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]; the plane is zeroed like tempPhotonMap
 void launch_accumulate_expected(double* photon_map, double* max_map, double* expected, float time_step, int32_t T, hipStream_t s);
 
+// ---- the adaptive gather (uvrt_refine.hip; include/uvrt.h "adaptive gather") ----
+// extra[t] = n_t of the count rule for t in [first_tri, first_tri + tri_count), 0 for every other t < T
+void launch_refine_count(const float4* gtris, const double* expected, const double* variance, int32_t* extra, int32_t T,
+                         int32_t first_tri, int32_t tri_count, int32_t samples0, double rel_error, double min_expected,
+                         int32_t max_extra, hipStream_t s);
+// offs[i] = extra[first_tri] + ... + extra[first_tri + i - 1] for i in [0, tri_count]; block_sums: (tri_count + 1023) / 1024
+// int32 of scratch
+void launch_refine_scan(const int32_t* extra, int32_t* offs, int32_t* block_sums, int32_t first_tri, int32_t tri_count,
+                        hipStream_t s);
+// A chunk of a refined range: the triangles first_tri + [lo, hi) and their offs[hi] - offs[lo] rays, ray r of the chunk being
+// sample r + offs[lo] - offs[i] of the triangle i whose offsets enclose it.  g.samples is not read: S is the triangle's n_t.
+void launch_refine_generate(const GatherGenParams& g, const int32_t* offs, int32_t lo, int32_t hi, int32_t rays, hipStream_t s);
+// X1, V1 of every triangle of the chunk with n_t > 0 as k_gather_reduce_var<mode> forms them at S = n_t, merged in place
+void launch_refine_reduce(const float4* gtris, const double* w, const uint8_t* occluded, const int32_t* offs, double* expected,
+                          double* variance, int32_t first_tri, int32_t lo, int32_t hi, int32_t samples0, int32_t photons_equiv,
+                          int32_t mode, hipStream_t s);
+
 }  // namespace uvrt

@@ -71,6 +71,9 @@ SYMBOLS = [
                                                  C.c_int, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_gather_confidence", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
                                                    C.c_int, C.c_double, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_refine", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                               C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_set_gather_refine", None, [_vp, C.c_double, C.c_int]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -87,9 +90,10 @@ SYMBOLS = [
 _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIterations",
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
-           "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling"}
+           "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling", "gatherRelError",
+           "gatherMaxExtra"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
-               "photonMapSize", "viewMode", "gatherSamples", "gatherSampling"}
+               "photonMapSize", "viewMode", "gatherSamples", "gatherSampling", "gatherMaxExtra"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 
@@ -245,6 +249,10 @@ class RayTracer:
     def SetRayRange(self, rank, world): self._L.uvrt_host_rt_set_ray_range(self._h, int(rank), int(world))
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
 
+    def set_gather_refine(self, rel_error, max_extra=64):
+        """gatherRelError and gatherMaxExtra in one call: every gather launch is refined (0: off)"""
+        self._L.uvrt_host_rt_set_gather_refine(self._h, float(rel_error), int(max_extra))
+
     def PlanDurations(self, min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None,
                       gather_samples=0, gather_sampling=0, gather_confidence=0.0):
         """RayTracer::PlanDurations: one batched computation over the current positions from the current SEED with the
@@ -259,7 +267,24 @@ class RayTracer:
         is those launches' sampling mode: 0 independent, 1 stratified; it needs gather_samples > 0.
         gather_confidence = z > 0 (PlanOptions::gatherConfidence) plans for the estimate's lower confidence bound, expected -
         z standard errors element by element; it needs gather_samples >= 2 and is meant for 16 and more.
-        0 is the plan without it, bit for bit."""
+        0 is the plan without it, bit for bit.  (PlanDurationsRefined is this call with the adaptive gather.)"""
+        return self._plan_durations(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
+                                    gather_confidence, 0.0, 64)
+
+    def PlanDurationsRefined(self, gather_rel_error, gather_max_extra=64, **plan):
+        """PlanDurations(**plan) with PlanOptions::gatherRelError = gather_rel_error and gatherMaxExtra = gather_max_extra:
+        every gather launch of the plan is refined before its capture.  tau > 0 needs gather_samples >= 2 and
+        works with and without gather_confidence; 0 is PlanDurations, bit for bit."""
+        args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
+                    gather_sampling=0, gather_confidence=0.0)
+        unknown = set(plan) - set(args)
+        if unknown:
+            raise TypeError("PlanDurationsRefined: unknown arguments %s" % sorted(unknown))
+        args.update(plan)
+        return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, **args)
+
+    def _plan_durations(self, min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
+                        gather_confidence, gather_rel_error, gather_max_extra):
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
         z = float(gather_confidence)
@@ -267,7 +292,20 @@ class RayTracer:
             raise ValueError("gather_confidence must be finite and >= 0")
         if z > 0.0 and int(gather_samples) < 2:
             raise ValueError("gather_confidence needs gather_samples >= 2")
+        tau, extra = float(gather_rel_error), int(gather_max_extra)
+        if not (tau >= 0.0) or tau == float("inf"):
+            raise ValueError("gather_rel_error must be finite and >= 0")
+        if tau > 0.0 and int(gather_samples) < 2:
+            raise ValueError("gather_rel_error needs gather_samples >= 2")
+        if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
+            raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if tau > 0.0:
+            self._L.uvrt_host_rt_plan_gather_refine(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                                    float(margin), float(rel_gap), int(max_iterations), _addr(keep),
+                                                    int(gather_samples), int(gather_sampling), z, tau, extra, C.byref(rep),
+                                                    C.byref(seed))
+            return _plan_result(self, rep, seed)
         if z > 0.0:
             self._L.uvrt_host_rt_plan_gather_confidence(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
                                                         float(margin), float(rel_gap), int(max_iterations), _addr(keep),

@@ -28,13 +28,15 @@ std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>
 
 RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
                                     const unsigned char* mask, int gather_samples, int gather_sampling = 0,
-                                    double gather_confidence = 0.0)
+                                    double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
     o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
     o.gatherSampling = gather_sampling;
     o.gatherConfidence = gather_confidence;
+    o.gatherRelError = gather_rel_error;
+    o.gatherMaxExtra = gather_max_extra;
     return o;
 }
 
@@ -110,6 +112,13 @@ void uvrt_host_rt_set_shard(void* r, int rank, int world)
     ((RayTracer*)r)->launchIndex = 0;
 }
 
+// RayTracer::gatherRelError and gatherMaxExtra (the adaptive gather of every gather launch; rel_error 0: off)
+void uvrt_host_rt_set_gather_refine(void* r, double rel_error, int max_extra)
+{
+    ((RayTracer*)r)->gatherRelError = rel_error;
+    ((RayTracer*)r)->gatherMaxExtra = max_extra;
+}
+
 void uvrt_host_rt_compute_batched(void* r, int iterations) { ((RayTracer*)r)->ComputeIterationsBatched(iterations); }
 void uvrt_host_rt_compute_batched_group(void** rs, int n, int iterations)
 {
@@ -168,6 +177,14 @@ void uvrt_host_rt_plan_gather_confidence(void* r, float min_dose, int min_photon
     *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
                                                        gather_sampling, gather_confidence), seed);
 }
+// the same with PlanOptions::gatherRelError / gatherMaxExtra beside them (include/uvrt.h uvrt_gather_refine)
+void uvrt_host_rt_plan_gather_refine(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                                     const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
+                                     double gather_rel_error, int gather_max_extra, uvrt_plan_report* rep, unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra), seed);
+}
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
@@ -197,7 +214,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(minPower, float) F(photonsPerLight, int) F(compTime, float) F(progress, float)
     F(finishedComputation, bool) F(thresholdView, bool) F(startedComputation, bool)
     F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
-    F(gatherSampling, int)
+    F(gatherSampling, int) F(gatherRelError, double) F(gatherMaxExtra, int)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

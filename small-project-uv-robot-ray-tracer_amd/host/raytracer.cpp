@@ -186,19 +186,21 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1);
+    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra);
 }
 
 void RayTracer::ComputeSegments()
 {
     for (const RouteLaunch& l : Launches())
-        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1);
+        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra);
 }
 
-void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn)
+void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
+                          double relError, int maxExtra)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
+    if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
     if (samples > 0) {
         // the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
         if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
@@ -211,7 +213,23 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
         g.seed = gatherLaunches++;
         g.photons_equiv = photons;
         check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
-        check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+        if (relError != 0.0) {
+            // the adaptive gather (raytracer.h gatherRelError): the variance plane on for this launch, then the refine
+            if (!(relError > 0.0) || !std::isfinite(relError)) fatal("gatherRelError must be finite and >= 0");
+            int32_t variance0 = 0;
+            check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
+            check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
+            check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+            check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
+            uvrt_refine_params rp;
+            memset(&rp, 0, sizeof rp);
+            rp.rel_error = relError;
+            rp.max_extra = maxExtra;
+            rp.seed = ~g.seed;
+            check(uvrt_gather_refine(ctx, &rp, 0, triangleCount, nullptr), "gather_refine");
+        } else {
+            check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+        }
         if (captureColumn >= 0) check(uvrt_plan_capture_expected(ctx, captureColumn), "plan_capture_expected");
         check(uvrt_accumulate_expected(ctx, l.duration, triangleCount), "accumulate_expected");
     } else if (shardWorld <= 1 || (launchIndex % shardWorld) == shardRank) {
@@ -232,13 +250,13 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
     RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
     RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -356,7 +374,8 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
-void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence)
+void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
+                                  int maxExtra)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -373,7 +392,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column);
+        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column, relError, maxExtra);
         Shade();
         ++currIterations;
     }
@@ -440,11 +459,15 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (!(opt.gatherConfidence > 0.0) || !std::isfinite(opt.gatherConfidence)) fatal("PlanDurations: gatherConfidence must be finite and >= 0");
         if (opt.gatherSamples < 2) fatal("PlanDurations: gatherConfidence needs a plan from the direct gather with gatherSamples >= 2");
     }
+    if (opt.gatherRelError != 0.0) {
+        if (!(opt.gatherRelError > 0.0) || !std::isfinite(opt.gatherRelError)) fatal("PlanDurations: gatherRelError must be finite and >= 0");
+        if (opt.gatherSamples < 2) fatal("PlanDurations: gatherRelError needs a plan from the direct gather with gatherSamples >= 2");
+    }
     uint32_t seed0 = 0;
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
-        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence);
+        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }

@@ -129,6 +129,11 @@ public:
         // touched.  0 (default): the plan above, bit for bit.  Not 0 with gatherSamples < 2, negative or not finite: fatal.
         // Meant for gatherSamples >= 16: at 4 samples about half the bounds are 0.
         double gatherConfidence = 0.0;
+        // tau > 0: every gather launch of the plan is refined before its capture (RayTracer::gatherRelError below, with
+        // gatherMaxExtra beside it), with and without gatherConfidence.  The plan's own, like S: the RayTracer members are not
+        // touched.  0 (default): the plan above, bit for bit.  Not 0 with gatherSamples < 2, negative or not finite: fatal.
+        double gatherRelError = 0.0;
+        int gatherMaxExtra = 64;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -179,20 +184,29 @@ public:
     // 1 rod strata and a rotated sweep sequence.  Handed to the context before every gather launch; read by
     // nothing else.  Saved as <gather_sampling> after <gather_samples> in route files when both are > 0.
     int gatherSampling = 0;
-    unsigned gatherLaunches = 0;                    // gather launches since ResetDosageMap: the next launch's seed
+    // The adaptive gather (include/uvrt.h "adaptive gather").  gatherRelError = tau > 0 with gatherSamples >= 2:
+    // every gather launch runs with the variance plane on (the context's state is put back after the launch) and is followed
+    // by uvrt_gather_refine(rel_error = tau, min_expected = 0, max_extra = gatherMaxExtra, seed = ~the launch's seed) before
+    // its plane is captured or accumulated.  0 (default): the gather above, bit for bit.  tau not 0 with gatherSamples < 2
+    // (photon launches included), tau negative or not finite: fatal.  Not saved in route files.
+    double gatherRelError = 0.0;
+    int gatherMaxExtra = 64;
+    unsigned gatherLaunches = 0;                   // gather launches since ResetDosageMap: the next launch's seed
 private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
     // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with samples > 0 the direct
     // gather -> accumulate_expected, its plane first captured into column captureColumn of a plan when that is >= 0.
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
-    // `sampling`: the gather sampling mode of a launch with samples > 0.
-    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn);
+    // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError).
+    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
+                   double relError, int maxExtra);
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
-    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence);
+    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
+                           int maxExtra);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

@@ -61,6 +61,12 @@
 //                                           (0: the plan without it); meant for S >= 16 -- at S = 4 about half the bounds are 0.
 //                                           --plan-verify recomputes with the plain gather of the same seeds, whose estimate is
 //                                           >= the bound element by element, so the plan holds there
+//            [--gather-refine TAU[,MAX]]    with --gather S or --plan-gather S, S >= 2: the adaptive gather (RayTracer::
+//                                           gatherRelError / gatherMaxExtra, PlanOptions::gatherRelError / gatherMaxExtra, DESIGN.md
+//                                           16): after every gather launch the triangles whose standard error exceeds TAU times
+//                                           their estimate get up to MAX extra shadow rays (a power of two in [2, 4096], default
+//                                           64).  TAU finite and > 0.  With --plan-gather, --plan-verify recomputes with the same
+//                                           refine, so it sees the plan's own estimates; works with and without --plan-confidence
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -124,7 +130,8 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 }
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
-             const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence)
+             const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence,
+             double refineTau, int refineMax)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -133,6 +140,8 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.gatherSamples = planGather;
     opt.gatherSampling = planGather > 0 ? gatherSampling : 0;
     opt.gatherConfidence = planGather > 0 ? planConfidence : 0.0;
+    opt.gatherRelError = planGather > 0 ? refineTau : 0.0;
+    opt.gatherMaxExtra = refineMax;
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
     if (planGather > 0) {
@@ -141,6 +150,11 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
         printf("plan: exposure from the direct gather, %d samples per triangle and launch\n", planGather);
         if (opt.gatherSampling == UVRT_GATHER_STRATIFIED) printf("plan: stratified gather sampling\n");
         if (opt.gatherConfidence > 0.0) printf("plan: lower confidence bound, z = %.9g\n", opt.gatherConfidence);
+        if (opt.gatherRelError > 0.0) {
+            rt.gatherRelError = opt.gatherRelError;     // --plan-verify recomputes the plan's own estimates
+            rt.gatherMaxExtra = opt.gatherMaxExtra;
+            printf("plan: adaptive gather, relative error %.9g, at most %d extra samples\n", opt.gatherRelError, opt.gatherMaxExtra);
+        }
     }
     const float m = minDose >= 0.0f ? minDose : rt.minDosage;
     printf("plan: %d positions, %d used, total duration %.9g (lower bound %.9g, gap %.3g), %s after %d iterations\n",
@@ -209,6 +223,8 @@ int main(int argc, char** argv)
     int minPhotons = 16, gridX = 0, gridZ = 0, gather = -1, planGather = 0, gatherSampling = -1;
     uint32_t holdoutSeed = 0;
     double planConfidence = -1.0;           // < 0: not given
+    double refineTau = 0.0;                 // 0: not given
+    int refineMax = 64;
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
     ViewMode view = dosage;
@@ -263,6 +279,25 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (!strcmp(argv[i], "--gather-refine")) {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            refineTau = strtod(v, &end);
+            bool ok = end != v && std::isfinite(refineTau) && refineTau > 0.0;
+            if (ok && *end == ',') {
+                const char* m = end + 1;
+                const long extra = strtol(m, &end, 10);
+                ok = end != m && *end == 0 && extra >= 2 && extra <= 4096 && (extra & (extra - 1)) == 0;
+                refineMax = (int)extra;
+            } else if (ok) {
+                ok = *end == 0;
+            }
+            if (!ok) {
+                fprintf(stderr, "--gather-refine TAU[,MAX]: TAU must be a finite number > 0, MAX a power of two in [2, 4096] (with --gather S or --plan-gather S, S >= 2)\n");
+                return 2;
+            }
+        }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -272,6 +307,7 @@ int main(int argc, char** argv)
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
     if (gatherSampling >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-sampling needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planConfidence >= 0.0 && planGather < 2) { fprintf(stderr, "--plan-confidence needs --plan-gather S with S >= 2\n"); return 2; }
+    if (refineTau > 0.0 && gather < 2 && planGather < 2) { fprintf(stderr, "--gather-refine needs --gather S or --plan-gather S with S >= 2\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
@@ -305,6 +341,7 @@ int main(int argc, char** argv)
     }
     if (gather >= 0) rayTracer.gatherSamples = gather;
     if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
+    if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
         return 2;
@@ -327,7 +364,7 @@ int main(int argc, char** argv)
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
-                                gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence);
+                                gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax);
         save_route(rayTracer, saveRoute);
         return rc;
     }
