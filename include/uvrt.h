@@ -287,6 +287,19 @@ int uvrt_gather_refine(uvrt_ctx* ctx, const uvrt_refine_params* params, int32_t 
 /* test hook: n_t of the last uvrt_gather_refine, int32[T]; 0 outside its range (and before the first refine of a scene);
  * synchronises */
 int uvrt_read_gather_extra(uvrt_ctx* ctx, int32_t* out, int32_t first, int32_t count);
+/* test hook: the count rule and the prefix sum of uvrt_gather_refine alone, on the planes as they are.  uvrt_write_expected and
+ * uvrt_write_variance forget the remembered gather, so a refine only ever counts on planes a gather left; this call runs the
+ * same two device steps (the count, the three-pass scan) on whatever expected[] and variance[] hold, with S0 = samples0 in
+ * [2, 4096] from the caller, over triangles [first_tri, first_tri + tri_count) of [0, T].  offsets_out[0 .. tri_count] receives
+ * the exclusive prefix sum of n_t over the range (offsets_out[tri_count] is the total); n_t itself is what
+ * uvrt_read_gather_extra then reads, 0 outside the range.  Synchronises.
+ * It traces nothing and leaves both planes, the remembered gather, "the last generate", SEED and the maps as they are; planes
+ * and per-triangle records that no call has made yet are made (the planes zeroed) as their read calls would.  params is checked
+ * as uvrt_gather_refine checks it, but for the seed (no ray is drawn) and max_extra <= capacity (no ray is stored); there need
+ * be no remembered gather.  UVRT_ERR_INVALID with nothing changed, the n_t plane included: those limits, samples0, a range
+ * outside [0, T], flavour 2, no scene, a null argument. */
+int uvrt_refine_counts(uvrt_ctx* ctx, int32_t samples0, const uvrt_refine_params* params, int32_t first_tri, int32_t tri_count,
+                       int32_t* offsets_out /* tri_count + 1 */);
 
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *

@@ -129,6 +129,7 @@ SYMBOLS = [
     ("uvrt_plan_lower_confidence", C.c_int, [_vp, C.c_double]),
     ("uvrt_gather_refine", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("uvrt_read_gather_extra", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_refine_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -542,6 +543,19 @@ class Ctx:
         count = self.T - first if count is None else count
         out = np.empty(count, dtype=np.int32)
         self._ck(self._L.uvrt_read_gather_extra(self._h, _ptr(out), int(first), int(count)))
+        return out
+
+    def refine_counts(self, samples0, rel_error, max_extra, min_expected=0.0, first_tri=0, tri_count=None, seed=0):
+        """test hook (include/uvrt.h uvrt_refine_counts): the refine's count rule and prefix sum on the planes as they are,
+        nothing traced; returns the tri_count + 1 offsets, int32, and leaves n_t to read_gather_extra"""
+        prm = RefineParams()
+        prm.rel_error = float(rel_error)
+        prm.min_expected = float(min_expected)
+        prm.max_extra = int(max_extra)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        tri_count = self.T - int(first_tri) if tri_count is None else int(tri_count)
+        out = np.full(max(tri_count, 0) + 1, -1, dtype=np.int32)
+        self._ck(self._L.uvrt_refine_counts(self._h, int(samples0), C.byref(prm), int(first_tri), tri_count, _ptr(out)))
         return out
 
     @property

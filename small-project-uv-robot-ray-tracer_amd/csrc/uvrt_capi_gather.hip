@@ -1,7 +1,7 @@
 // uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
 // uvrt_occluded, uvrt_set_gather_sampling, uvrt_get_gather_sampling, uvrt_set_gather_variance, uvrt_get_gather_variance,
 // uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected, uvrt_write_expected, uvrt_read_variance,
-// uvrt_write_variance (uvrt_occlude.hip's kernels); uvrt_gather_refine, uvrt_read_gather_extra (uvrt_refine.hip's)
+// uvrt_write_variance (uvrt_occlude.hip's kernels); uvrt_gather_refine, uvrt_read_gather_extra, uvrt_refine_counts (uvrt_refine.hip's)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
@@ -17,6 +17,41 @@ int ensure_expected(uvrt_ctx* c)
 int ensure_variance(uvrt_ctx* c)
 {
     return c->variance.ensure((size_t)c->T * 8, true, c->stream);
+}
+
+// the gather's per-triangle records {v0, e1, e2} in tris64 order, made from the scene's leaf triangles on first use
+static int ensure_gather_tris(uvrt_ctx* c)
+{
+    if (c->g_tris_valid) return UVRT_OK;
+    if (int rc = c->g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
+    launch_gather_tris(c->ltris.as<LeafTri>(), c->g_tris.as<float4>(), c->T, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->g_tris_valid = true;
+    return UVRT_OK;
+}
+
+// the arguments uvrt_gather_refine and uvrt_refine_counts share; `who` names the call in the message
+static int check_refine_params(uvrt_ctx* c, const uvrt_refine_params* prm, const char* who)
+{
+    if (!(prm->rel_error > 0.0) || !std::isfinite(prm->rel_error))
+        return fail(UVRT_ERR_INVALID, "%s: rel_error must be finite and > 0", who);
+    if (!(prm->min_expected >= 0.0) || !std::isfinite(prm->min_expected))
+        return fail(UVRT_ERR_INVALID, "%s: min_expected must be finite and >= 0", who);
+    const int32_t M = prm->max_extra;
+    if (M < 2 || M > 4096 || (M & (M - 1)) != 0)
+        return fail(UVRT_ERR_INVALID, "%s: max_extra = %d must be a power of two in [2, 4096]", who, M);
+    if ((int64_t)c->T * M >= ((int64_t)1 << 31))
+        return fail(UVRT_ERR_INVALID, "%s: %d triangles x %d samples do not fit 2^31 sample numbers", who, c->T, M);
+    if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return fail(UVRT_ERR_INVALID, "%s: reserved fields must be 0", who);
+    return UVRT_OK;
+}
+
+// the refine's n_t plane, offsets and block sums, sized for the scene
+static int ensure_refine_buffers(uvrt_ctx* c)
+{
+    if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
+    if (int rc = c->g_offs.ensure(((size_t)c->T + 1) * 4, false, c->stream)) return rc;
+    return c->g_scan.ensure(((size_t)c->T / 1024 + 1) * 4, false, c->stream);
 }
 
 // Everything a shadow-ray launch works on, on the context's stream behind all outstanding work: lane 0's ray buffer, the
@@ -137,12 +172,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     if (int rc = ensure_expected(c)) return rc;
     if (var)
         if (int rc = ensure_variance(c)) return rc;
-    if (!c->g_tris_valid) {
-        if (int rc = c->g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
-        launch_gather_tris(c->ltris.as<LeafTri>(), c->g_tris.as<float4>(), c->T, c->stream);
-        HIP_TRY(hipGetLastError());
-        c->g_tris_valid = true;
-    }
+    if (int rc = ensure_gather_tris(c)) return rc;
     Lane& L = c->lanes[0];
     GatherGenParams g;
     memset(&g, 0, sizeof g);
@@ -251,27 +281,17 @@ int uvrt_gather_refine(uvrt_ctx* c, const uvrt_refine_params* prm, int32_t first
     if (first_tri < m.first || tri_count < 0 || (int64_t)first_tri + tri_count > (int64_t)m.first + m.count)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: triangles [%d, +%d) outside the remembered gather's [%d, +%d)", first_tri,
                     tri_count, m.first, m.count);
-    if (!(prm->rel_error > 0.0) || !std::isfinite(prm->rel_error))
-        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: rel_error must be finite and > 0");
-    if (!(prm->min_expected >= 0.0) || !std::isfinite(prm->min_expected))
-        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: min_expected must be finite and >= 0");
+    if (int rc = check_refine_params(c, prm, "uvrt_gather_refine")) return rc;
     const int32_t M = prm->max_extra;
-    if (M < 2 || M > 4096 || (M & (M - 1)) != 0)
-        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: max_extra = %d must be a power of two in [2, 4096]", M);
     if ((int64_t)M > c->capacity)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: max_extra = %d exceeds the ray capacity %lld (uvrt_resize_rays)", M, (long long)c->capacity);
-    if ((int64_t)c->T * M >= ((int64_t)1 << 31))
-        return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: %d triangles x %d samples do not fit 2^31 sample numbers", c->T, M);
     if (prm->seed == m.seed)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: seed %u is the refined gather's: the extra samples would repeat its own", prm->seed);
-    if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: reserved fields must be 0");
     if (int rc = set_device(c)) return rc;
     if (int rc = begin_shadow_launch(c)) return rc;
     const size_t cap = (size_t)c->capacity;
     if (int rc = c->g_w.ensure(cap * 8, false, c->stream)) return rc;
-    if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
-    if (int rc = c->g_offs.ensure(((size_t)c->T + 1) * 4, false, c->stream)) return rc;
-    if (int rc = c->g_scan.ensure(((size_t)c->T / 1024 + 1) * 4, false, c->stream)) return rc;
+    if (int rc = ensure_refine_buffers(c)) return rc;
     if (report) *report = {};
     // (the remembered gather made g_tris and both planes, and whatever releases them -- uvrt_set_scene -- forgets it)
     const float4* gtris = c->g_tris.as<float4>();
@@ -331,6 +351,32 @@ int uvrt_read_gather_extra(uvrt_ctx* c, int32_t* out, int32_t first, int32_t cou
     if (int rc = set_device(c)) return rc;
     if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
     return range_copy(c, c->g_extra.p, 4, out, first, count, hipMemcpyDeviceToHost);
+}
+
+int uvrt_refine_counts(uvrt_ctx* c, int32_t samples0, const uvrt_refine_params* prm, int32_t first_tri, int32_t tri_count,
+                       int32_t* offsets_out)
+{
+    if (!c || !prm || !offsets_out) return fail(UVRT_ERR_INVALID, "uvrt_refine_counts: null argument");
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_refine_counts: no scene");
+    if (c->flavour != 0 && c->flavour != 1)
+        return fail(UVRT_ERR_INVALID, "uvrt_refine_counts: shadow rays are traced in flavours 0 and 1 only (uvrt_set_flavour %d)", c->flavour);
+    if (first_tri < 0 || tri_count < 0 || (int64_t)first_tri + tri_count > c->T)
+        return fail(UVRT_ERR_INVALID, "uvrt_refine_counts: triangles [%d, +%d) outside [0, %d]", first_tri, tri_count, c->T);
+    if (samples0 < 2 || samples0 > 4096)
+        return fail(UVRT_ERR_INVALID, "uvrt_refine_counts: samples0 = %d must be in [2, 4096], a gather's with the variance on", samples0);
+    if (int rc = check_refine_params(c, prm, "uvrt_refine_counts")) return rc;
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;        // behind all outstanding work; "the last generate" and the remembered gather stay
+    if (int rc = ensure_expected(c)) return rc;
+    if (int rc = ensure_variance(c)) return rc;
+    if (int rc = ensure_gather_tris(c)) return rc;
+    if (int rc = ensure_refine_buffers(c)) return rc;
+    // the two launches of uvrt_gather_refine, on the planes as they are
+    launch_refine_count(c->g_tris.as<float4>(), c->expected.as<double>(), c->variance.as<double>(), c->g_extra.as<int32_t>(), c->T,
+                        first_tri, tri_count, samples0, prm->rel_error, prm->min_expected, prm->max_extra, c->stream);
+    launch_refine_scan(c->g_extra.as<int32_t>(), c->g_offs.as<int32_t>(), c->g_scan.as<int32_t>(), first_tri, tri_count, c->stream);
+    HIP_TRY(hipGetLastError());
+    return copy_sync(c, offsets_out, c->g_offs.p, ((size_t)tri_count + 1) * 4, hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

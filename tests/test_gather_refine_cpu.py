@@ -15,13 +15,14 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import gather_edge_scene as ge
 import gather_refine_restate as gf
 import gather_restate as gr
 import gather_stratified_restate as gs
 import gather_variance_restate as gv
 from conftest import GLB, GOLDEN, ROOT
 
-NEW = ("uvrt_gather_refine", "uvrt_read_gather_extra")
+NEW = ("uvrt_gather_refine", "uvrt_read_gather_extra", "uvrt_refine_counts")
 f32 = np.float32
 
 
@@ -35,7 +36,8 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
             assert getattr(pkg.capi.lib(dev), n).restype is C.c_int
     by_name = {n: a for n, _, a in pkg.capi.SYMBOLS}
     assert len(by_name["uvrt_gather_refine"]) == 5 and len(by_name["uvrt_read_gather_extra"]) == 4
-    for m in ("gather_refine", "read_gather_extra"):
+    assert len(by_name["uvrt_refine_counts"]) == 6 and by_name["uvrt_refine_counts"][1] is C.c_int32
+    for m in ("gather_refine", "read_gather_extra", "refine_counts"):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
     hosts = {n: a for n, _, a in host.SYMBOLS}
@@ -80,7 +82,9 @@ def test_null_arguments_are_refused_without_a_gpu(pkg):
         L = pkg.capi.lib(dev)
         calls = (("uvrt_gather_refine", lambda: L.uvrt_gather_refine(None, C.byref(prm), 0, 4, C.byref(rep))),
                  ("uvrt_gather_refine", lambda: L.uvrt_gather_refine(None, None, 0, 4, None)),
-                 ("uvrt_read_gather_extra", lambda: L.uvrt_read_gather_extra(None, buf.ctypes.data, 0, 4)))
+                 ("uvrt_read_gather_extra", lambda: L.uvrt_read_gather_extra(None, buf.ctypes.data, 0, 4)),
+                 ("uvrt_refine_counts", lambda: L.uvrt_refine_counts(None, 4, C.byref(prm), 0, 3, buf.ctypes.data)),
+                 ("uvrt_refine_counts", lambda: L.uvrt_refine_counts(None, 4, None, 0, 3, None)))
         for name, call in calls:
             assert call() == -1 and name.encode() in L.uvrt_last_error(), name          # UVRT_ERR_INVALID
     assert np.all(buf == 7) and (rep.extra_rays, rep.refined, rep.reserved) == (7, 7, 7)
@@ -180,6 +184,54 @@ def test_the_count_rule_at_its_edges():
     assert _n(4.0, 100.0, min_expected=4.0) == 64 and _n(4.0, 100.0, min_expected=4.000001) == 0
     n = gf.count_rule([4.0, 4.0, 0.0], [1.5, 100.0, 1.0], [1.0, 1.0, 1.0], 16, 0.25, 0.0, 64)
     assert n.dtype == np.int32 and n.tolist() == [8, 64, 0]
+
+
+def test_crafted_rows_pin_the_count_rule():
+    """gather_edge_scene.count_rule_rows, the planes tests/test_gpu_refine_gather_edges.py writes: where a row pins `want`, the restated
+    f64 `want`, the exact one and the rule's n_t agree with it; the rows of zeros, subnormals, inf, NaN and negatives give what
+    the header's rule says by hand"""
+    for S0 in (2, 3, 16):
+        for cap in (2, 64, 4096):
+            X, V, pinned = ge.count_rule_rows(S0, cap)
+            w = ge.restated_want(X, V, S0)
+            n = gf.count_rule(X, V, np.ones(X.size), S0, ge.ROW_TAU, 0.0, cap)
+            assert sorted({p for p in pinned if p is not None}) == sorted(set(ge.ROW_WANTS[:-1]) | {cap - 1, cap, cap + 1})
+            for k, p in enumerate(pinned):
+                if p is None:
+                    continue
+                exact = Fraction(S0) * (Fraction(V[k]) - 1)
+                assert w[k] == p == -(-exact.numerator // exact.denominator), (S0, cap, k, V[k])
+                want_n = 0 if p < 1 else cap if p >= cap else 1 << (max(p, 2) - 1).bit_length()
+                assert n[k] == want_n == _want(X[k], V[k], S0, ge.ROW_TAU, cap), (S0, cap, k, p)
+            big = np.flatnonzero((w > 1e299) & np.isfinite(w))  # want = 1e300, both forms
+            assert big.size == 2 and n[big].tolist() == [cap, cap]
+            tail = n[-20:].tolist()
+            assert tail[:8] == [0, 0, cap, cap, 0, 0, 0, 0], tail         # X0: +0, -0, subnormal, 1e-200, inf, NaN, negative, 1e200
+            assert tail[8:14] == [0, 0, 0, 0, cap, 0], tail               # V0: +0, -0, subnormal, negative, inf, NaN
+            assert tail[14:17] == [0, 0, cap] and np.isnan(w[-6:-4]).all() and np.isposinf(w[-4]), tail
+            assert all(v > 0 for v in tail[17:]), tail                    # X0 about min_expected, none set
+            assert gf.count_rule(X[-3:], V[-3:], np.ones(3), S0, ge.ROW_TAU, ge.ROW_X0, cap).tolist() == [0] + tail[18:]
+            assert gf.count_rule(X, V, np.zeros(X.size), S0, ge.ROW_TAU, 0.0, cap).tolist() == [0] * X.size
+
+
+def test_the_edge_scene_reaches_what_the_room_does_not(orc):
+    """gather_edge_scene.edge_scene on the restatements: the triangles without area are the named ones, a stop without length
+    leaves rays without a direction by underflow and by overflow, weights are NaN and no plane entry is; the refined sub-range
+    holds every n_t from 2 to 4096 in both modes with fewer than 300 000 extra rays"""
+    sc = ge.edge_scene(orc)
+    _, _, _, nn = gr.tri_normals(sc.tris)
+    assert np.array_equal(np.flatnonzero(nn == 0.0), sc.no_area) and sc.no_area.size == 5 and sc.T == ge.EDGE_SOUP + len(ge.HAND)
+    assert sc.sub_range[0] in sc.hand.values() and sum(sc.sub_range) - 1 in sc.hand.values() and sum(sc.sub_range) == sc.T
+    rays, w = gs.samples(orc, sc.tris, ge.LAMP, ge.LAMP, 0.0, 4, 3, 0, None, gs.INDEPENDENT)
+    untraced = (rays["dist"] == 0).reshape(sc.T, 4).sum(axis=1)
+    assert untraced[sc.hand["tiny at the foot"]] == 4 and nn[sc.hand["tiny at the foot"]] > 0        # underflow: r = 0, R > 0
+    assert untraced[sc.hand["far and huge"]] == 4 and np.isfinite(nn[sc.hand["far and huge"]])       # overflow: r = inf
+    assert np.isnan(w).sum() >= 4
+    first, count = sc.sub_range
+    for mode, tau in ((gv.STRATIFIED, 0.05), (gv.INDEPENDENT, 0.02)):
+        e, v, n, _, _ = gf.gather_and_refine(orc, sc, ge.LAMP, ge.LAMP, 1.0, 4, 3, 1 << 20, mode, tau, 4096, first=first, count=count)
+        assert sorted(set(n.tolist())) == [0] + [2 << k for k in range(12)] and n.sum() < 300000, (mode, int(n.sum()))
+        assert np.isfinite(e).all() and np.isfinite(v).all() and not n[sc.no_area - first].any()
 
 
 def test_the_merge_against_fractions():
