@@ -430,6 +430,28 @@ int uvrt_dedupe_plan_strips(const float lamp[3], int32_t count, const uint32_t* 
 int uvrt_dedupe_mark_device(uvrt_ctx* ctx, const float lamp[3], int32_t count, const uint32_t* seed_prev,
                             const uint32_t* seed_next, int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first,
                             int64_t chunk_n, uint32_t* masks, uint32_t* block_owner_counts);
+/* The period table: away from a few events -- the ends of the range, a sum that crosses a power of two, work-item 0 -- the
+ * mask of an occurrence is an exact periodic function of its gid with a period of 2 to 16 gids (csrc/uvrt_dedupe.h "period
+ * table").  With the table on, the host builds per interior of the group's key strata a table of launches x period deposit
+ * words, the mark pass walks only the keys outside the interiors, and the write pass and the owner counts read the table for
+ * the rest.  Rays, deposit words, their order and every count are bit for bit those of the general path, which still takes
+ * gid 0, groups of 31 launches, short or unproven interiors and whatever 12 interiors of 384 words in all do not hold.
+ * uvrt_set_dedupe_periodic(ctx, on): takes effect with the next batch; the default is on (DESIGN.md section 15 has the
+ * measurement), or what the environment variable UVRT_DEDUPE_PERIODIC (0 / 1) says when the context is created. */
+int uvrt_set_dedupe_periodic(uvrt_ctx* ctx, int32_t on);
+int uvrt_get_dedupe_periodic(uvrt_ctx* ctx, int32_t* on);
+/* test hook, host only: uvrt_dedupe_plan_tiled's chunk through the period table -- the functions the batch and its kernels
+ * run, on the CPU: masks[k * chunk_n + i], the owners per launch and block of 2 048 gids as uvrt_dedupe_mark_device lays them
+ * out (the interiors' in closed form from the table), and *from_table = the occurrences whose mask came from the table. */
+int uvrt_dedupe_plan_periodic(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                              int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first, int64_t chunk_n,
+                              uint32_t* masks, uint32_t* block_owner_counts, int64_t* from_table);
+/* test hook: the three generate kernels of a deduped chunk alone, for that group and chunk with the context's settings (mask
+ * classes, period table), on the context's stream (waited for): the compacted rays (16 bytes each) and deposit words in
+ * (launch, gid) order, room for count x chunk_n of each; *total = rays written, *deposits = the atomics they stand for. */
+int uvrt_dedupe_generate_device(uvrt_ctx* ctx, const float lamp[3], float light_length, int32_t count, const uint32_t* seed_prev,
+                                const uint32_t* seed_next, int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first,
+                                int64_t chunk_n, float* rays, uint32_t* words, uint32_t* total, uint32_t* deposits);
 
 /* ---- the one collective of a sharded computation (RCCL over xGMI; librccl is opened on first use) ----
  * One process per GPU: rank 0 calls uvrt_comm_unique_id and hands the 128 bytes to every rank (any

@@ -65,6 +65,11 @@ SYMBOLS = [
     ("uvrt_dedupe_plan_tiled", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i64, _i64, _vp]),
     ("uvrt_dedupe_plan_strips", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i64, _i64, _vp]),
     ("uvrt_dedupe_mark_device", C.c_int, [_vp, _fp, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp]),
+    ("uvrt_set_dedupe_periodic", C.c_int, [_vp, _i32]),
+    ("uvrt_get_dedupe_periodic", C.c_int, [_vp, C.POINTER(_i32)]),
+    ("uvrt_dedupe_plan_periodic", C.c_int, [_fp, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, C.POINTER(_i64)]),
+    ("uvrt_dedupe_generate_device", C.c_int, [_vp, _fp, C.c_float, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp,
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("uvrt_comm_available", C.c_int, []),
     ("uvrt_comm_info", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_comm_unique_id", C.c_int, [_vp]),
@@ -324,6 +329,25 @@ def dedupe_plan_tiled(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, tile
     if rc != 0:
         raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
     return out
+
+
+def dedupe_plan_periodic(lamp, seed_prev, seed_next_, seed_mode, first_gid, n, chunk_first=None, chunk_n=None):
+    """dedupe_plan_tiled's chunk through the period table on the host (include/uvrt.h uvrt_dedupe_plan_periodic):
+    (masks uint32[launches][chunk_n], owners uint32[launches][ceil(chunk_n / DEDUPE_BLOCK_GIDS)], occurrences whose mask came
+    from the table)"""
+    sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
+    sn = np.ascontiguousarray(seed_next_, dtype=np.uint32)
+    assert sp.size == sn.size
+    chunk_first = first_gid if chunk_first is None else chunk_first
+    chunk_n = n if chunk_n is None else chunk_n
+    masks = np.empty((sp.size, int(chunk_n)), dtype=np.uint32)
+    owners = np.empty((sp.size, (int(chunk_n) + DEDUPE_BLOCK_GIDS - 1) // DEDUPE_BLOCK_GIDS), dtype=np.uint32)
+    from_table = _i64()
+    rc = lib().uvrt_dedupe_plan_periodic(_f3(lamp), int(sp.size), _ptr(sp), _ptr(sn), int(seed_mode), int(first_gid), int(n),
+                                         int(chunk_first), int(chunk_n), _ptr(masks), _ptr(owners), C.byref(from_table))
+    if rc != 0:
+        raise UvrtError("uvrt error %d: %s" % (rc, lib().uvrt_last_error().decode()))
+    return masks, owners, int(from_table.value)
 
 
 def seed_next_sweep(frm, light_length, seed_prev):
@@ -615,6 +639,32 @@ class Ctx:
         m = _i32()
         self._ck(self._L.uvrt_get_dedupe_classes(self._h, C.byref(m)))
         return int(m.value)
+
+    def set_dedupe_periodic(self, on):
+        """interior masks of a dedupe group from its period table (include/uvrt.h uvrt_set_dedupe_periodic)"""
+        self._ck(self._L.uvrt_set_dedupe_periodic(self._h, 1 if on else 0))
+
+    def get_dedupe_periodic(self):
+        on = _i32()
+        self._ck(self._L.uvrt_get_dedupe_periodic(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def dedupe_generate_device(self, lamp, light_length, seed_prev, seed_next_, seed_mode, first_gid, n, chunk_first=None,
+                               chunk_n=None):
+        """the generate kernels of a deduped chunk alone (include/uvrt.h uvrt_dedupe_generate_device):
+        (rays float32[total][4], deposit words uint32[total], the deposits they stand for)"""
+        sp = np.ascontiguousarray(seed_prev, dtype=np.uint32)
+        sn = np.ascontiguousarray(seed_next_, dtype=np.uint32)
+        assert sp.size == sn.size
+        chunk_first = first_gid if chunk_first is None else chunk_first
+        chunk_n = n if chunk_n is None else chunk_n
+        rays = np.zeros((sp.size * int(chunk_n), 4), dtype=np.float32)
+        words = np.zeros(sp.size * int(chunk_n), dtype=np.uint32)
+        total, deposits = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.uvrt_dedupe_generate_device(self._h, _f3(lamp), float(np.float32(light_length)), int(sp.size), _ptr(sp),
+                                                     _ptr(sn), int(seed_mode), int(first_gid), int(n), int(chunk_first),
+                                                     int(chunk_n), _ptr(rays), _ptr(words), C.byref(total), C.byref(deposits)))
+        return rays[:total.value].copy(), words[:total.value].copy(), int(deposits.value)
 
     def batch_deposits(self):
         """atomic adds the traced rays of the last batch's dedupe groups issue when each of them hits"""

@@ -115,6 +115,7 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
     if (const char* e = getenv("UVRT_DEDUPE")) c->dedupe = atoi(e) != 0;                 // uvrt_set_dedupe's default
     if (const char* e = getenv("UVRT_DEDUPE_CLASSES")) { const int v = atoi(e); if (v >= 0 && v <= DEDUPE_CLASS_MAX) c->dedupe_classes = v; }   // uvrt_set_dedupe_classes' default
+    if (const char* e = getenv("UVRT_DEDUPE_PERIODIC")) c->dedupe_periodic = atoi(e) != 0;   // uvrt_set_dedupe_periodic's default
     if (const char* e = getenv("UVRT_DEDUPE_STRIP")) { const int v = atoi(e); if (v >= 1 && v <= 1024) c->dedupe_strip = v; }   // developer knob: tiles per wave of the mark pass
     if (const char* e = getenv("UVRT_DEDUPE_CLASS_REPLICAS")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->dedupe_class_replicas = v; }
     if (const char* e = getenv("UVRT_DEDUPE_CLASS_MB")) { const long v = atol(e); if (v > 0 && v <= 4096) c->dedupe_class_bytes = (size_t)v << 20; }
@@ -607,6 +608,20 @@ int uvrt_get_dedupe_classes(uvrt_ctx* c, int32_t* max_classes)
 {
     if (!c || !max_classes) return fail(UVRT_ERR_INVALID, "uvrt_get_dedupe_classes: null argument");
     *max_classes = c->dedupe_classes;
+    return UVRT_OK;
+}
+
+int uvrt_set_dedupe_periodic(uvrt_ctx* c, int32_t on)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_set_dedupe_periodic: null context");
+    c->dedupe_periodic = on != 0;
+    return UVRT_OK;
+}
+
+int uvrt_get_dedupe_periodic(uvrt_ctx* c, int32_t* on)
+{
+    if (!c || !on) return fail(UVRT_ERR_INVALID, "uvrt_get_dedupe_periodic: null argument");
+    *on = c->dedupe_periodic ? 1 : 0;
     return UVRT_OK;
 }
 

@@ -13,8 +13,14 @@ namespace uvrt_impl {
 static void mark_tiles(const uvrt_ctx* c, GenDedupeParams& q)
 {
     dedupe_tile_range(q.g, q.g0, q.gn, DEDUPE_MARK_KEYS, q.key_lo, q.tiles);
-    const int64_t fit = std::min<int64_t>(2 * DEDUPE_STRIP_TILES, std::max<int64_t>(DEDUPE_STRIP_TILES, q.tiles / 4096));
+    // ... of the key intervals that the group's period table (q.per; count 0: none) leaves to the mark pass: the tiles it
+    // walks (strips of one), then the strips
+    q.gaps = dedupe_periodic_gaps(q.per, q.key_lo, q.tiles * DEDUPE_MARK_KEYS, DEDUPE_MARK_KEYS, 1, q.gap_key, q.gap_keys, q.gap_strip0);
+    const int64_t walked = q.gap_strip0[q.gaps];
+    // (with a table few tiles are left and a wave's walk is all the pass takes: strips down to one tile)
+    const int64_t fit = std::min<int64_t>(2 * DEDUPE_STRIP_TILES, std::max<int64_t>(q.per.count > 0 ? 1 : DEDUPE_STRIP_TILES, walked / 4096));
     q.strip_tiles = c->dedupe_strip > 0 ? c->dedupe_strip : (int32_t)fit;
+    q.gaps = dedupe_periodic_gaps(q.per, q.key_lo, q.tiles * DEDUPE_MARK_KEYS, DEDUPE_MARK_KEYS, q.strip_tiles, q.gap_key, q.gap_keys, q.gap_strip0);
 }
 
 // uvrt_trace_batch and uvrt_trace_batch_launches (`who` names the caller in the error texts): generate + extend for `count`
@@ -108,6 +114,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
         int g, k0, kc; bool dd; int64_t chunk_gids; DedupeGroup G;
         DedupeTally cand[DEDUPE_CLASS_MAX]; int ncand; double keys;       // its owners' multi-bit masks by sampled frequency
         int ncls, cls_base; DedupeClasses cls;                            // the classes it gets, from class plane cls_base on
+        DedupePeriodic per;                                               // its period table (count 0: none)
     };
     std::vector<Piece> pieces;
     size_t dd_chunks = 0, dd_tmp_bytes = 0, dd_block_bytes = 0;
@@ -194,6 +201,13 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
             dedupe_classes_fill(pc.cls, masks, pc.ncls, (uint32_t)(count - (gfirst[pc.g] + pc.k0) + base));
             base += pc.ncls;
         }
+    }
+    // The period tables of the dedupe groups (uvrt_dedupe.h "period table"), words through the classes just dealt: a function
+    // of the group alone, built here at every call with no word from the device; they travel in the kernels' arguments.
+    if (c->dedupe_periodic && dd_chunks > 0) {
+        std::vector<uint32_t> table((size_t)DEDUPE_TILE_KEYS);
+        for (Piece& pc : pieces)
+            if (pc.dd) dedupe_periodic_build(pc.G, pc.cls, table.data(), pc.per);
     }
     const size_t planes_bytes = (size_t)count * plane_alloc * 4 + (size_t)class_cap * plane_ints * 4;
     // growing a buffer needs the device idle (hipFree / hipMalloc); new per-launch records only need the context's stream
@@ -343,6 +357,7 @@ static int trace_launches(uvrt_ctx* c, const uvrt_launch* launches, float light_
                 dq.total = S.dd_counts.as<uint32_t>() + dd_used;
                 dq.deposits = S.dd_counts.as<uint32_t>() + dd_chunks + dd_used++;
                 dq.cls = pc.cls;
+                dq.per = pc.per;
                 dq.tmp = cur_lane(c).dd_tmp.as<uint32_t>();
                 dq.g0 = first_gid + g0;
                 dq.gn = gn;
@@ -660,6 +675,82 @@ int uvrt_dedupe_mark_device(uvrt_ctx* c, const float lamp[3], int32_t count, con
     HIP_TRY(hipMemcpyAsync(block_owner_counts, dq.block_counts, nblocks * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(dq.block_counts, 0, nblocks * 4, c->stream));      // as k_dedupe_write would leave it
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return UVRT_OK;
+}
+
+int uvrt_dedupe_plan_periodic(const float lamp[3], int32_t count, const uint32_t* seed_prev, const uint32_t* seed_next,
+                              int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first, int64_t chunk_n,
+                              uint32_t* masks, uint32_t* block_owner_counts, int64_t* from_table)
+{
+    DedupeGroup G;
+    if (int rc = hook_group(G, "uvrt_dedupe_plan_periodic", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
+    if (!masks || !block_owner_counts || !from_table || !chunk_ok(G, chunk_first, chunk_n))
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_plan_periodic: null output, or a chunk outside the range");
+    std::vector<uint32_t> table((size_t)DEDUPE_TILE_KEYS);
+    DedupeClasses none = {};
+    DedupePeriodic T;
+    dedupe_periodic_build(G, none, table.data(), T);
+    *from_table = dedupe_plan_periodic(G, T, DEDUPE_MARK_KEYS, DEDUPE_STRIP_TILES, DD_SLOTS, chunk_first, chunk_n, table.data(), masks,
+                                       block_owner_counts);
+    return UVRT_OK;
+}
+
+int uvrt_dedupe_generate_device(uvrt_ctx* c, const float lamp[3], float light_length, int32_t count, const uint32_t* seed_prev,
+                                const uint32_t* seed_next, int32_t seed_mode, int64_t first_gid, int64_t n, int64_t chunk_first,
+                                int64_t chunk_n, float* rays, uint32_t* words, uint32_t* total, uint32_t* deposits)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_dedupe_generate_device: null context");
+    GenDedupeParams dq;
+    memset(&dq, 0, sizeof dq);
+    if (int rc = hook_group(dq.g, "uvrt_dedupe_generate_device", lamp, count, seed_prev, seed_next, seed_mode, first_gid, n)) return rc;
+    if (!rays || !words || !total || !deposits || !chunk_ok(dq.g, chunk_first, chunk_n))
+        return fail(UVRT_ERR_INVALID, "uvrt_dedupe_generate_device: null output, or a chunk outside the range");
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    // the group's classes as a batch of this group alone deals them, then its period table
+    std::vector<uint32_t> table((size_t)DEDUPE_TILE_KEYS);
+    if (c->dedupe_classes > 0 && count <= DEDUPE_CLASS_LAUNCHES) {
+        DedupeTally cand[DEDUPE_CLASS_MAX];
+        uint32_t class_masks[DEDUPE_CLASS_MAX];
+        const int nc = dedupe_class_tally(dq.g, table.data(), cand, c->dedupe_classes, nullptr);
+        for (int i = 0; i < nc; ++i) class_masks[i] = cand[i].mask;
+        dedupe_classes_fill(dq.cls, class_masks, nc, (uint32_t)count);
+    }
+    if (c->dedupe_periodic) dedupe_periodic_build(dq.g, dq.cls, table.data(), dq.per);
+    // lane 0's scratch, on the context's stream; growing it needs the stream idle
+    Lane& L = c->lanes[0];
+    const size_t slots = (size_t)count * (size_t)chunk_n;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = L.dd_tmp.ensure(slots * 4, false, c->stream)) return rc;
+    if (int rc = L.dd_blocks.ensure((size_t)count * (size_t)((chunk_n + 255) / 256) * 4, true, c->stream)) return rc;
+    DevBuf out_rays, out_words, out_counts;
+    if (int rc = out_rays.ensure(slots * 16, false, c->stream)) return rc;
+    if (int rc = out_words.ensure(slots * 4, false, c->stream)) return rc;
+    if (int rc = out_counts.ensure(8, true, c->stream)) return rc;
+    dq.rays = out_rays.as<float4>();
+    dq.masks = out_words.as<uint32_t>();
+    dq.total = out_counts.as<uint32_t>();
+    dq.deposits = out_counts.as<uint32_t>() + 1;
+    dq.tmp = L.dd_tmp.as<uint32_t>();
+    dq.g0 = chunk_first;
+    dq.gn = chunk_n;
+    dq.block_counts = L.dd_blocks.as<uint32_t>();
+    mark_tiles(c, dq);
+    dq.light_length = light_length;
+    dq.prio = c->helper_prio;
+    launch_generate_dedupe(dq, c->stream);
+    HIP_TRY(hipGetLastError());
+    uint32_t counts[2] = {0u, 0u};
+    HIP_TRY(hipMemcpyAsync(counts, dq.total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((size_t)counts[0] > slots) return fail(UVRT_ERR_INVALID, "uvrt_dedupe_generate_device: more rays than occurrences");
+    if (counts[0] > 0u) {
+        HIP_TRY(hipMemcpyAsync(rays, dq.rays, (size_t)counts[0] * 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(words, dq.masks, (size_t)counts[0] * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    *total = counts[0];
+    *deposits = counts[1];
     return UVRT_OK;
 }
 

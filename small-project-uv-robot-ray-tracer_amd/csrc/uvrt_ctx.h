@@ -227,6 +227,7 @@ struct uvrt_ctx {
     int32_t b_traced_chunks = 0;          // ... and its deduped chunks, whose counts are bs[b_set].dd_counts[0, b_traced_chunks)
     // mask classes of a batch's dedupe groups (uvrt_dedupe.h "mask classes")
     int32_t dedupe_classes = uvrt::DEDUPE_CLASSES_DEFAULT;     // uvrt_set_dedupe_classes / UVRT_DEDUPE_CLASSES: classes per group at most, 0 = none
+    bool dedupe_periodic = uvrt::DEDUPE_PERIODIC_DEFAULT;      // uvrt_set_dedupe_periodic / UVRT_DEDUPE_PERIODIC: interior masks from the period table (uvrt_dedupe.h)
     int32_t dedupe_class_replicas = 4;    // replicas of a class plane that take deposits (developer knob UVRT_DEDUPE_CLASS_REPLICAS)
     size_t dedupe_class_bytes = (size_t)96 << 20;         // class planes of one buffer set (developer knob UVRT_DEDUPE_CLASS_MB)
     int32_t b_ncls = 0, b_cls_repl = 1;   // the traced batch's class planes (behind its b_count launch planes) and their replicas in use

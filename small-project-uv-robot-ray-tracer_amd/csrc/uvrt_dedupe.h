@@ -23,6 +23,7 @@
 // counted, never assumed.
 #pragma once
 #include <stdint.h>
+#include <algorithm>
 
 #if defined(__HIPCC__)
 #define UVRT_HD __host__ __device__ __forceinline__
@@ -278,14 +279,17 @@ UVRT_HD int32_t dedupe_strip_first(const DedupeGroup& G, int j, int64_t t0)
 // Host: the masks of the chunk [c0, c0 + cn) of a group's range, masks[k * cn + i], tile by tile with a table of W entries,
 // in strips of `strip` tiles with carried bounds as the device walks them (the device's strip length is its launcher's choice,
 // DEDUPE_STRIP_TILES and more; the masks depend on it as little as on W)
-inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int32_t strip, int64_t c0, int64_t cn, uint32_t* table, uint32_t* masks)
+// the tiles of one key interval [key_lo, key_lo + keys): the last one is cut at the interval's end (its width w), so that the
+// mark pass may walk the parts of a chunk's keys that the period table below leaves to it and nothing beyond them
+inline void dedupe_plan_tiled_keys(const DedupeGroup& G, int32_t W, int32_t strip, int64_t c0, int64_t cn, int64_t key_lo, int64_t keys,
+                                   uint32_t* table, uint32_t* masks)
 {
-    int64_t key_lo, tiles;
-    dedupe_tile_range(G, c0, cn, W, key_lo, tiles);
+    const int64_t tiles = (keys + W - 1) / W;
     const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
     int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
     for (int64_t tile = 0; tile < tiles; ++tile) {
         const int64_t t0 = key_lo + tile * W;
+        const int32_t w = (int32_t)(keys - tile * W < W ? keys - tile * W : W);
         for (int32_t i = 0; i < W; ++i) table[i] = 0u;
         for (int j = 0; j < G.count; ++j) {
             g_lo[j] = tile % strip == 0 ? dedupe_strip_first(G, j, t0) : g_hi[j];
@@ -293,21 +297,27 @@ inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int32_t strip, in
             int32_t g = g_lo[j];
             for (; g < hi; ++g) {
                 const int32_t key = dedupe_key1_of(G, seed1, g);
-                if (!dedupe_in_tile(key, t0, W)) break;
+                if (!dedupe_in_tile(key, t0, w)) break;
                 dedupe_tile_insert_run(table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(G, seed1, g, key, lo, hi));
             }
             g_hi[j] = g;
         }
         for (int j = 0; j < G.count; ++j)
-            if (dedupe_tile_holds_gid0(G, j, t0, W)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
+            if (dedupe_tile_holds_gid0(G, j, t0, w)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
         for (int k = 0; k < G.count; ++k) {
             const int64_t a = g_lo[k] > c0 ? g_lo[k] : c0, b = g_hi[k] < c0 + cn ? g_hi[k] : c0 + cn;
             for (int64_t g = a; g < b; ++g)
                 masks[(int64_t)k * cn + (g - c0)] = dedupe_tile_resolve(table[dedupe_tile_slot(dedupe_key1(G, k, (int32_t)g), t0)], k);
-            if (c0 == 0 && dedupe_tile_holds_gid0(G, k, t0, W))
+            if (c0 == 0 && dedupe_tile_holds_gid0(G, k, t0, w))
                 masks[(int64_t)k * cn] = dedupe_tile_resolve(table[dedupe_tile_slot(G.key0[k], t0)], k);
         }
     }
+}
+inline void dedupe_plan_tiled(const DedupeGroup& G, int32_t W, int32_t strip, int64_t c0, int64_t cn, uint32_t* table, uint32_t* masks)
+{
+    int64_t key_lo, tiles;
+    dedupe_tile_range(G, c0, cn, W, key_lo, tiles);
+    dedupe_plan_tiled_keys(G, W, strip, c0, cn, key_lo, tiles * W, table, masks);
 }
 
 // ---- Mask classes: one deposit per traced ray ("mask classes") ----
@@ -510,6 +520,259 @@ inline bool dedupe_group_ok(DedupeGroup& G)
         G.key0[j] = dedupe_key(G, j, 0);
     }
     return true;
+}
+
+// ---- Interior masks from a per-stratum period table ("period table") ----
+// Which launches hold a key is an exact periodic function of the key away from a few events, and so is the mask of an
+// occurrence as a function of its gid: mask(k, g) = words[stratum][k][g mod P].  The host finds the strata and builds the
+// tables (dedupe_periodic_build), the mark pass walks only the keys outside them (dedupe_periodic_gaps), the write pass reads
+// an interior occurrence's word from the table (dedupe_periodic_word) and the owners per block of gids come from it in closed
+// form (dedupe_periodic_owners).  dedupe_mask() stays the definition; uvrt_dedupe_plan_periodic runs these functions on the
+// CPU.
+//
+// The sums.  For gid g >= 1 of launch j: a0 = fl(17 g + 1), a1 = fl(a0 + c1), a2 = fl(a1 + c2), a3 = fl(a2 + c3),
+// a4 = fl(a3 + s_j), key = trunc(a4), with the lamp's terms c and s_j = SEED_j >> 15 (an integer below 2^17).
+// Let REGION be a set of gids of launch j over which each of a0..a4 stays positive and inside ONE binade of its own, with ulps
+// u0..u4 <= u, and P a multiple of 2 max(u, 1).  Then for g and g + P in the region every a_i(g + P) = a_i(g) + 17 P: the
+// exact argument of each rounding moves by 17 P, a multiple of 2 u_i, so its place on the binade's grid AND the parity that
+// decides a tie stay the same (this is why P takes 2 u, not u), and the truncation moves by the integer 17 P.  So over a key
+// interval whose holders in EVERY launch lie in such regions, launch j holds key t exactly when it holds t + 17 P, as often,
+// and the mask of (k, g) equals that of (k, g + P).
+// The events that end a region, as keys: a_i of launch j leaves a binade at 2^b where key - a_i = s_j + (the lamp terms
+// still to come) + rounding, that is within L + E of 2^b + s_j, and a4 within 1 of 2^b, with L = ceil(13|lx| + 7|ly| + 11|lz|)
+// and E = 32 >= five roundings of at most half an ulp of 8 (keys below 2^27) plus the truncation; a launch's first and last key
+// of the call's range (beyond them it holds nothing); and the key of work-item 0, which reads the other SEED.  Below
+// FLOOR = max s_j + L + E + 1 a sum may not be positive, and from 2^27 on a launch may hold a key twice: no interiors there.
+// These are dedupe_class_tally's cuts, taken for EVERY binade (a fractional lamp term rounds differently in each binade below
+// 2^24, which a tally may ignore and a table may not) plus work-item 0's key.
+// The margin.  An occurrence with key t looks at key t in every launch, never at another key, so nothing of the offsets
+// between launches enters: an interior is a stratum shrunk at both ends by M = L + E + 34 DEDUPE_PERIOD_MAX keys -- L + E
+// for where an event really lies, and two periods of 17 P keys so that g - P and g + P of every holder stay inside.
+// The proof is never trusted alone: the table is built from one tile at each end of the interior with the tile functions of
+// the mark pass, every gid of both tiles must agree with its residue's entry, and a stratum that fails, or that shows a key
+// held twice, goes back to the general path.  So do gid 0, groups of more than DEDUPE_PERIODIC_LAUNCHES launches, interiors
+// shorter than four of the widest build tiles, and whatever does not fit the caps: the DEDUPE_PERIODIC_STRATA longest interiors are taken
+// while their K P words fit DEDUPE_PERIODIC_WORDS (the headline's group: 12 interiors and 256 words hold 0.975 of its
+// occurrences, the nine long ones 0.97; a route's group of 5 launches takes fewer words).
+constexpr int DEDUPE_PERIODIC_STRATA = 12;
+constexpr int DEDUPE_PERIODIC_WORDS = 384;
+constexpr int DEDUPE_PERIOD_MAX = 16;           // gids: 2 ulp with ulp <= 8 below 2^27
+constexpr int DEDUPE_PERIODIC_LAUNCHES = 30;
+constexpr bool DEDUPE_PERIODIC_DEFAULT = true;  // uvrt_set_dedupe_periodic's default (DESIGN.md section 15 has the measurement)
+constexpr int32_t DEDUPE_PERIODIC_TILE = 68 * DEDUPE_PERIOD_MAX;   // keys of the widest build tile: 68 P, four periods of every launch's gids
+
+struct DedupePeriodic {
+    int32_t count;                                  // interiors, ascending in the key; 0: everything takes the general path
+    int32_t key_lo[DEDUPE_PERIODIC_STRATA];         // interior s holds the keys [key_lo, key_lo + keys)
+    uint32_t keys[DEDUPE_PERIODIC_STRATA];
+    int32_t period[DEDUPE_PERIODIC_STRATA];         // gids, a power of two
+    int32_t word_off[DEDUPE_PERIODIC_STRATA];       // words[word_off + k * period + (gid & (period - 1))]
+    // the deposit word of the occurrence (dedupe_deposit_word), 0 = absorbed; room behind the last word for a reader that
+    // takes DEDUPE_PERIOD_MAX words wherever a launch's P words start
+    uint32_t words[DEDUPE_PERIODIC_WORDS + DEDUPE_PERIOD_MAX];
+};
+
+// the interior that holds `key`, or -1
+UVRT_HD int dedupe_periodic_find(const DedupePeriodic& T, int32_t key)
+{
+    for (int s = 0; s < T.count; ++s)
+        if ((uint32_t)key - (uint32_t)T.key_lo[s] < T.keys[s]) return s;
+    return -1;
+}
+UVRT_HD int32_t dedupe_periodic_index(const DedupePeriodic& T, int s, int k, int32_t gid)
+{
+    return T.word_off[s] + k * T.period[s] + (gid & (T.period[s] - 1));
+}
+// the owners among launch k's gids [x0, x1) (x0 >= 1, inside the call's range) that lie in an interior; `words`: T.words or a copy
+UVRT_HD uint32_t dedupe_periodic_owners(const DedupeGroup& G, const DedupePeriodic& T, const uint32_t* words, int k, int32_t x0, int32_t x1)
+{
+    if (x0 >= x1) return 0u;
+    const uint32_t seed1 = dedupe_seed1(G, k);
+    const int32_t ka = dedupe_key1_of(G, seed1, x0), kb = dedupe_key1_of(G, seed1, x1 - 1);
+    uint32_t total = 0u;
+    for (int s = 0; s < T.count; ++s) {
+        const int64_t A = T.key_lo[s], B = A + (int64_t)T.keys[s];
+        if ((int64_t)kb < A || (int64_t)ka >= B) continue;
+        const int32_t a = (int64_t)ka >= A ? x0 : dedupe_lower_bound(G, k, A, x0, x1);
+        const int32_t b = (int64_t)kb < B ? x1 : dedupe_lower_bound(G, k, B, a, x1);
+        // residue (a + r) mod P comes q times among [a, b), and once more for r below the rest
+        const int32_t P = T.period[s], n = b - a, q = n / P, rest = n & (P - 1);
+        for (int32_t r = 0; r < P; ++r)
+            if (words[dedupe_periodic_index(T, s, k, a + r)] != 0u) total += (uint32_t)(q + (r < rest));
+    }
+    return total;
+}
+
+// What the mark pass walks of a chunk's keys [key_lo, key_lo + keys): the intervals between the interiors, each in strips of
+// `strip` tiles of W keys.  gap_key / gap_keys: room for DEDUPE_PERIODIC_STRATA + 1; strip0: one more, the running strip
+// count (strip0[gaps] = the strips of all).  Returns the gaps.
+inline int dedupe_periodic_gaps(const DedupePeriodic& T, int64_t key_lo, int64_t keys, int32_t W, int32_t strip, int32_t* gap_key,
+                                uint32_t* gap_keys, int32_t* strip0)
+{
+    int n = 0;
+    int64_t cur = key_lo, strips = 0;
+    const int64_t end = key_lo + keys;
+    const auto gap = [&](int64_t a, int64_t b) {
+        gap_key[n] = (int32_t)a;
+        gap_keys[n] = (uint32_t)(b - a);
+        strip0[n++] = (int32_t)strips;
+        strips += ((b - a + W - 1) / W + strip - 1) / strip;
+    };
+    for (int s = 0; s < T.count && cur < end; ++s) {
+        const int64_t A = T.key_lo[s], B = A + (int64_t)T.keys[s];
+        if (B <= cur || A >= end) continue;
+        if (A > cur) gap(cur, A);
+        cur = B;
+    }
+    if (cur < end) gap(cur, end);
+    strip0[n] = (int32_t)strips;
+    return n;
+}
+
+// Host: one build tile of an interior with period P, the keys [t0, t0 + 68 P): the mask of every residue of every launch
+// into out[k * P + r].  false: a key held twice, a residue without a gid, or two gids of one residue that differ.
+inline bool dedupe_periodic_tile(const DedupeGroup& G, int64_t t0, int32_t P, uint32_t* table, uint32_t* out)
+{
+    const int32_t W = 68 * P;
+    const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
+    int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
+    for (int32_t i = 0; i < W; ++i) table[i] = 0u;
+    for (int j = 0; j < G.count; ++j) {
+        dedupe_tile_run(G, j, t0, W, g_lo[j], g_hi[j]);
+        const uint32_t seed1 = dedupe_seed1(G, j);
+        for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) {
+            const int32_t key = dedupe_key1_of(G, seed1, g);
+            dedupe_tile_insert_run(table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(G, seed1, g, key, lo, hi));
+        }
+        if (dedupe_tile_holds_gid0(G, j, t0, W)) return false;
+    }
+    for (int32_t i = 0; i < W; ++i)
+        if (table[i] & DEDUPE_MANY) return false;
+    for (int k = 0; k < G.count; ++k) {
+        if (g_hi[k] - g_lo[k] < P) return false;
+        for (int32_t g = g_lo[k]; g < g_hi[k]; ++g) {
+            const uint32_t mask = dedupe_tile_resolve(table[dedupe_tile_slot(dedupe_key1(G, k, g), t0)], k);
+            uint32_t& e = out[k * P + (g & (P - 1))];
+            if (g - g_lo[k] < P) e = mask;
+            else if (e != mask) return false;
+        }
+    }
+    return true;
+}
+
+// Host: the group's interiors and their tables (the words through the group's class table C, as k_dedupe_write translates a
+// mask; C.count 0: the masks themselves).  `table`: DEDUPE_TILE_KEYS entries.  A function of the group and C alone.
+inline void dedupe_periodic_build(const DedupeGroup& G, const DedupeClasses& C, uint32_t* table, DedupePeriodic& T)
+{
+    static_assert(DEDUPE_PERIODIC_TILE <= DEDUPE_TILE_KEYS, "the build tile fits the host's table");
+    T = DedupePeriodic{};
+    const int K = G.count;
+    const int64_t last = G.first_gid + G.n - 1, lo1 = G.first_gid > 1 ? G.first_gid : 1;
+    if (K > DEDUPE_PERIODIC_LAUNCHES || lo1 > last) return;
+    const double lamp = 13.0 * (double)(G.lx < 0 ? -G.lx : G.lx) + 7.0 * (double)(G.ly < 0 ? -G.ly : G.ly) + 11.0 * (double)(G.lz < 0 ? -G.lz : G.lz);
+    if (!(lamp < 1e6)) return;
+    const int64_t L = (int64_t)lamp + 1, E = 32, M = L + E + 34 * DEDUPE_PERIOD_MAX;
+    constexpr int BINADES = 27;                   // 2^0 .. 2^26; the keys from 2^27 on are left out below
+    int64_t cut[3 * DEDUPE_MAX + BINADES * (DEDUPE_MAX + 1) + 2];
+    int ncut = 0;
+    int64_t klo = INT64_MAX, khi = INT64_MIN, smax = 0;
+    for (int j = 0; j < K; ++j) {
+        const int64_t a = dedupe_key1(G, j, (int32_t)lo1), b = (int64_t)dedupe_key1(G, j, (int32_t)last) + 1;
+        cut[ncut++] = a;
+        cut[ncut++] = b;
+        if (G.first_gid == 0) cut[ncut++] = G.key0[j];
+        klo = a < klo ? a : klo;
+        khi = b > khi ? b : khi;
+        const int64_t s = (int64_t)(dedupe_seed1(G, j) >> 15);
+        smax = s > smax ? s : smax;
+    }
+    const int64_t floor_key = smax + L + E + 1;
+    klo = klo < floor_key ? floor_key : klo;
+    khi = khi > ((int64_t)1 << 27) ? ((int64_t)1 << 27) : khi;
+    if (khi - klo < 2 * M) return;
+    cut[ncut++] = klo;
+    cut[ncut++] = khi;
+    for (int b = 0; b < BINADES; ++b) {
+        const int64_t B = (int64_t)1 << b;
+        cut[ncut++] = B;
+        for (int j = 0; j < K; ++j) cut[ncut++] = B + (int64_t)(dedupe_seed1(G, j) >> 15);
+    }
+    std::sort(cut, cut + ncut);
+    // the candidates: every stratum's interior that is long enough, then the longest that fit the caps
+    struct Cand { int64_t a, b; int32_t P; };
+    Cand cand[DEDUPE_PERIODIC_STRATA + 1];
+    int nc = 0, words = 0;
+    for (int i = 0; i + 1 < ncut; ++i) {
+        const int64_t a = (cut[i] < klo ? klo : cut[i]) + M, b = (cut[i + 1] > khi ? khi : cut[i + 1]) - M;
+        if (b - a < 4 * (int64_t)DEDUPE_PERIODIC_TILE) continue;
+        int64_t ulp = 1;
+        while (((int64_t)1 << 24) * ulp < b + M) ulp += ulp;      // (b + M: the stratum's last key; no power of two inside it)
+        const Cand v = {a, b, (int32_t)(2 * ulp)};
+        if (v.P > DEDUPE_PERIOD_MAX) continue;
+        int at = nc;                              // by length, longest first; the list keeps one more than the cap and drops the last
+        for (; at > 0 && cand[at - 1].b - cand[at - 1].a < b - a; --at) cand[at] = cand[at - 1];
+        cand[at] = v;
+        if (nc < DEDUPE_PERIODIC_STRATA) ++nc;
+    }
+    int take = 0;
+    for (; take < nc && words + K * cand[take].P <= DEDUPE_PERIODIC_WORDS; ++take) words += K * cand[take].P;
+    for (int i = 1; i < take; ++i) {              // back into key order
+        const Cand v = cand[i];
+        int at = i;
+        for (; at > 0 && cand[at - 1].a > v.a; --at) cand[at] = cand[at - 1];
+        cand[at] = v;
+    }
+    uint32_t first[DEDUPE_PERIODIC_LAUNCHES * DEDUPE_PERIOD_MAX], second[DEDUPE_PERIODIC_LAUNCHES * DEDUPE_PERIOD_MAX];
+    int32_t off = 0;
+    for (int i = 0; i < take; ++i) {
+        const Cand& v = cand[i];
+        const int32_t P = v.P;
+        // a tile at each end (a residue is the gid's own, gid mod P: the two tiles compare like with like)
+        if (!dedupe_periodic_tile(G, v.a, P, table, first) || !dedupe_periodic_tile(G, v.b - 68 * P, P, table, second)) continue;
+        bool same = true;
+        for (int e = 0; e < K * P; ++e) same = same && first[e] == second[e];
+        if (!same) continue;
+        const int s = T.count++;
+        T.key_lo[s] = (int32_t)v.a;
+        T.keys[s] = (uint32_t)(v.b - v.a);
+        T.period[s] = P;
+        T.word_off[s] = off;
+        for (int e = 0; e < K * P; ++e)
+            T.words[off + e] = first[e] == 0u ? 0u : dedupe_deposit_word(C.count > 0, C.slot_mask, C.slot_word, first[e]);
+        off += K * P;
+    }
+}
+
+// Host: the masks of the chunk [c0, c0 + cn) as a chunk's generate finds them with the table T (built WITHOUT classes: its
+// words are the masks) -- the gaps tile by tile, the interiors from the table -- and the owners per launch and block of
+// `block` gids, counts[k * ceil(cn / block) + b], the interiors' in closed form.  Returns the occurrences taken from the table.
+inline int64_t dedupe_plan_periodic(const DedupeGroup& G, const DedupePeriodic& T, int32_t W, int32_t strip, int32_t block, int64_t c0,
+                                    int64_t cn, uint32_t* table, uint32_t* masks, uint32_t* counts)
+{
+    const int64_t nb = (cn + block - 1) / block;
+    for (int64_t i = 0; i < (int64_t)G.count * cn; ++i) masks[i] = 0u;
+    int64_t key_lo, tiles;
+    dedupe_tile_range(G, c0, cn, W, key_lo, tiles);
+    int32_t gap_key[DEDUPE_PERIODIC_STRATA + 1], strip0[DEDUPE_PERIODIC_STRATA + 2];
+    uint32_t gap_keys[DEDUPE_PERIODIC_STRATA + 1];
+    const int gaps = dedupe_periodic_gaps(T, key_lo, tiles * W, W, strip, gap_key, gap_keys, strip0);
+    for (int i = 0; i < gaps; ++i) dedupe_plan_tiled_keys(G, W, strip, c0, cn, gap_key[i], gap_keys[i], table, masks);
+    int64_t from_table = 0;
+    for (int k = 0; k < G.count; ++k) {
+        for (int64_t b = 0; b < nb; ++b) {
+            const int64_t x0 = c0 + b * block, x1 = x0 + block < c0 + cn ? x0 + block : c0 + cn;
+            uint32_t owners = 0u;
+            for (int64_t g = x0; g < x1; ++g) owners += masks[(int64_t)k * cn + (g - c0)] != 0u;      // (the gaps' only, so far)
+            counts[(int64_t)k * nb + b] = owners + dedupe_periodic_owners(G, T, T.words, k, (int32_t)(x0 > 1 ? x0 : 1), (int32_t)x1);
+        }
+        for (int64_t g = c0 > 1 ? c0 : 1; g < c0 + cn; ++g) {
+            const int s = dedupe_periodic_find(T, dedupe_key1(G, k, (int32_t)g));
+            if (s < 0) continue;
+            masks[(int64_t)k * cn + (g - c0)] = T.words[dedupe_periodic_index(T, s, k, (int32_t)g)];
+            ++from_table;
+        }
+    }
+    return from_table;
 }
 
 }  // namespace uvrt

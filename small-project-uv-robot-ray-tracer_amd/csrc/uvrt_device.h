@@ -193,7 +193,15 @@ struct GenDedupeParams {
     int32_t prio;                      // helper_priority of the three kernels
     uint32_t* deposits;                // out: the atomics these rays issue when each of them hits (dedupe_word_deposits summed)
     DedupeClasses cls;                 // the group's mask classes (count 0: masks[] holds the masks themselves)
+    // the period table (uvrt_dedupe.h "period table"): mark walks the key intervals between the interiors (gaps >= 1; without a
+    // table one gap, the chunk's key tiles) and counts the interiors' owners from the table, write reads their words from it
+    DedupePeriodic per;
+    int32_t gaps;
+    int32_t gap_key[DEDUPE_PERIODIC_STRATA + 1];
+    uint32_t gap_keys[DEDUPE_PERIODIC_STRATA + 1];
+    int32_t gap_strip0[DEDUPE_PERIODIC_STRATA + 2];      // gap i: the workgroups [gap_strip0[i], gap_strip0[i + 1]) of the mark pass
 };
+static_assert(sizeof(GenDedupeParams) <= 3584, "kernel arguments: 4 KB with the hidden ones");
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s);
 // its first kernel alone: tmp and the owners per block added to block_counts (a test hook runs it by itself)
 void launch_dedupe_mark(const GenDedupeParams& p, hipStream_t s);

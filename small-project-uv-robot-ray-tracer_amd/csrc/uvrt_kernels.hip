@@ -101,14 +101,37 @@ __global__ __launch_bounds__(64) void k_dedupe_mark(GenDedupeParams p)
     // (gids as int32: the range ends below DEDUPE_GID_END)
     const int32_t lo = (int32_t)(p.g.first_gid > 1 ? p.g.first_gid : 1), hi = (int32_t)(p.g.first_gid + p.g.n);
     const int32_t c0 = (int32_t)p.g0, c1 = (int32_t)(p.g0 + p.gn);
-    const int64_t tile0 = (int64_t)blockIdx.x * p.strip_tiles;
-    const int64_t tile1 = tile0 + p.strip_tiles < p.tiles ? tile0 + p.strip_tiles : p.tiles;
+    if ((int32_t)blockIdx.x >= p.gap_strip0[p.gaps]) {
+        // extra workgroups: the owners of the interiors of the period table, a thread per launch and block of DD_SLOTS gids, in
+        // closed form from the table (neither tmp nor the key table see those occurrences)
+        // (the words once into LDS: the arguments are quick to read for scalar loads only)
+        static_assert(DEDUPE_PERIODIC_WORDS % 64 == 0 && DEDUPE_PERIODIC_WORDS <= W, "the words fit the key table's LDS in whole rounds");
+#pragma unroll
+        for (int i = 0; i < DEDUPE_PERIODIC_WORDS; i += 64) s_table[i + lane] = p.per.words[i + lane];
+        __syncthreads();
+        const uint32_t t = (blockIdx.x - (uint32_t)p.gap_strip0[p.gaps]) * 64u + (uint32_t)lane;
+        if (t < (uint32_t)K * nb) {
+            const uint32_t k = t / nb, b = t - k * nb;
+            const int32_t x0 = c0 + (int32_t)(b * (uint32_t)DD_SLOTS), x1 = min(x0 + DD_SLOTS, c1);
+            const uint32_t owners = dedupe_periodic_owners(p.g, p.per, s_table, (int)k, max(x0, 1), x1);
+            if (owners != 0u) atomicAdd(&p.block_counts[t], owners);
+        }
+        return;
+    }
+    // the workgroup's strip: of the key interval `gap` (uniform: scalar loads and compares)
+    int gap = 0;
+    while (gap + 1 < p.gaps && (int32_t)blockIdx.x >= p.gap_strip0[gap + 1]) ++gap;
+    const int64_t gap_lo = p.gap_key[gap];
+    const uint32_t gap_keys = p.gap_keys[gap];
+    const int64_t gap_tiles = (int64_t)((gap_keys + (uint32_t)W - 1u) / (uint32_t)W);
+    const int64_t tile0 = (int64_t)((int32_t)blockIdx.x - p.gap_strip0[gap]) * p.strip_tiles;
+    const int64_t tile1 = tile0 + p.strip_tiles < gap_tiles ? tile0 + p.strip_tiles : gap_tiles;
     // lane j keeps what is uniform per launch j: its run [run_lo, run_hi) in the current tile, and the owners of its current
     // block that no global add has taken yet; its SEED and the key of its gid 0, so that no loop below waits for a load
     int32_t run_lo = hi, run_hi = hi, key0 = 0;
     uint32_t seed1 = 0u;
     if (lane < K) {
-        run_lo = dedupe_strip_first(p.g, lane, p.key_lo + tile0 * W);      // the strip's one search per launch
+        run_lo = dedupe_strip_first(p.g, lane, gap_lo + tile0 * W);      // the strip's one search per launch
         seed1 = dedupe_seed1(p.g, lane);
         key0 = p.g.key0[lane];
     }
@@ -125,7 +148,8 @@ __global__ __launch_bounds__(64) void k_dedupe_mark(GenDedupeParams p)
         }
     };
     for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t t0 = p.key_lo + tile * W;
+        const int64_t t0 = gap_lo + tile * W;
+        const int32_t w = (int32_t)min((uint32_t)W, gap_keys - (uint32_t)(tile * W));      // (the interval's last tile ends with it)
         static_assert(W % 64 == 0, "the wave zeroes the table in whole rounds");
 #pragma unroll
         for (int i = 0; i < W; i += 64) s_table[i + lane] = 0u;
@@ -139,7 +163,7 @@ __global__ __launch_bounds__(64) void k_dedupe_mark(GenDedupeParams p)
                 bool in = false;
                 if (g < hi) {
                     const int32_t key = dedupe_key1_of(p.g, seed, g);
-                    in = dedupe_in_tile(key, t0, W);
+                    in = dedupe_in_tile(key, t0, w);
                     if (in) dedupe_tile_insert_run(s_table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(p.g, seed, g, key, lo, hi));
                 }
                 const int32_t n_in = (int32_t)__popcll(__builtin_amdgcn_ballot_w64(in));      // (a prefix of the lanes: the keys never decrease)
@@ -148,7 +172,7 @@ __global__ __launch_bounds__(64) void k_dedupe_mark(GenDedupeParams p)
             }
             if (lane == j) run_hi = base;
         }
-        const bool holds0 = lane < K && dedupe_tile_holds_key0(p.g, key0, t0, W);      // gid 0 of launch `lane`: last, reading the entry
+        const bool holds0 = lane < K && dedupe_tile_holds_key0(p.g, key0, t0, w);      // gid 0 of launch `lane`: last, reading the entry
         if (holds0) dedupe_tile_insert(s_table, dedupe_tile_slot(key0, t0), lane);
         __syncthreads();
         // resolve: every occurrence of the chunk reads its mask from its key's entry; the owners per block of DD_SLOTS gids
@@ -161,7 +185,7 @@ __global__ __launch_bounds__(64) void k_dedupe_mark(GenDedupeParams p)
                 uint32_t mask = 0u, blk = fb;
                 if (g < b) {
                     const uint32_t slot = dedupe_tile_slot(dedupe_key1_of(p.g, seed, g), t0);
-                    mask = dedupe_tile_resolve(slot < (uint32_t)W ? s_table[slot] : DEDUPE_MANY, j);
+                    mask = dedupe_tile_resolve(slot < (uint32_t)w ? s_table[slot] : DEDUPE_MANY, j);
                     p.tmp[(int64_t)j * p.gn + (g - c0)] = mask;
                     blk = (uint32_t)(g - c0) / (uint32_t)DD_SLOTS;
                 }
@@ -233,12 +257,62 @@ __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
     uint32_t dep = 0u;
     const int k = blockIdx.y;
     const uint32_t wv = threadIdx.x >> 6;
+    // The period table (uvrt_dedupe.h): which interiors hold keys of this workgroup's gids, from the keys at its ends -- uniform,
+    // every interior's bounds in one round of scalar loads; `inside`: one interior holds them all, so a gid needs no key.  An
+    // occurrence of an interior takes its WORD from the table (mark wrote nothing for it), every other one its mask from tmp;
+    // `worded` says which, a bit per round.  The table travels in the kernel's arguments, which only scalar loads read
+    // quickly: a period divides 256, so a thread's gids of all rounds share one residue, and its word of an interior is
+    // picked from the interior's DEDUPE_PERIOD_MAX scalar words once per workgroup -- no vector load, no LDS, no barrier (a
+    // workgroup beside a traversal is alone on its CU and lives by its waits).
+    static_assert(256 % DEDUPE_PERIOD_MAX == 0, "a thread's rounds share their residue");
+    uint32_t near = 0u, worded = 0u;
+    bool inside = false;
+    const uint32_t seed1 = dedupe_seed1(p.g, k);
+    const int32_t gid0 = (int32_t)(p.g0 + (int64_t)blockIdx.x * DD_SLOTS) + (int32_t)threadIdx.x;      // the thread's gid of round 0
+    if (p.per.count > 0) {
+        const int32_t x0 = max((int32_t)(p.g0 + (int64_t)blockIdx.x * DD_SLOTS), 1);
+        const int32_t x1 = (int32_t)min(p.g0 + ((int64_t)blockIdx.x + 1) * DD_SLOTS, p.g0 + p.gn);
+        const int32_t ka = __builtin_amdgcn_readfirstlane(dedupe_key1_of(p.g, seed1, x0));
+        const int32_t kb = __builtin_amdgcn_readfirstlane(dedupe_key1_of(p.g, seed1, x1 - 1));
+#pragma unroll
+        for (int s = 0; s < DEDUPE_PERIODIC_STRATA; ++s) {      // (keys below 2^27: the bounds are int32)
+            const int32_t A = p.per.key_lo[s], B = A + (int32_t)p.per.keys[s];
+            if (s < p.per.count && kb >= A && ka < B) {
+                near |= 1u << s;
+                inside = ka >= A && kb < B;
+            }
+        }
+    }
     uint32_t mask[DD_ROUNDS], rank[DD_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < DD_ROUNDS; ++r) mask[r] = 0u;
+    for (uint32_t left = near; left != 0u; left &= left - 1u) {      // (uniform: one interior, two or three at a cluster of events)
+        const int s = __builtin_ctz(left);
+        const int32_t A = p.per.key_lo[s], P = p.per.period[s];
+        const uint32_t len = p.per.keys[s];
+        const uint32_t* w = &p.per.words[p.per.word_off[s] + k * P];
+        const int32_t res = gid0 & (P - 1);
+        uint32_t word = 0u;
+#pragma unroll
+        for (int q = 0; q < DEDUPE_PERIOD_MAX; ++q) {          // (words[] has room for the reads past the launch's P words)
+            const uint32_t wq = w[q];
+            if (res == q) word = wq;
+        }
+#pragma unroll
+        for (int r = 0; r < DD_ROUNDS; ++r) {
+            const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
+            const int32_t g = gid0 + r * 256;
+            if (i < p.gn && g >= 1 && (inside || (uint32_t)dedupe_key1_of(p.g, seed1, g) - (uint32_t)A < len)) {
+                mask[r] = word;
+                worded |= 1u << r;
+            }
+        }
+    }
     uint32_t pos = p.block_counts[(size_t)k * gridDim.x + blockIdx.x];      // (after the scan: the workgroup's first slot)
 #pragma unroll
     for (int r = 0; r < DD_ROUNDS; ++r) {
         const int64_t i = (int64_t)blockIdx.x * DD_SLOTS + r * 256 + threadIdx.x;
-        mask[r] = i < p.gn ? p.tmp[(int64_t)k * p.gn + i] : 0u;
+        if (!((worded >> r) & 1u) && i < p.gn) mask[r] = p.tmp[(int64_t)k * p.gn + i];
         const unsigned long long owners = __builtin_amdgcn_ballot_w64(mask[r] != 0u);
         rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(owners >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)owners, 0u));
         if ((threadIdx.x & 63u) == 0u) s_cnt[r][wv] = (uint32_t)__popcll(owners);
@@ -255,7 +329,7 @@ __global__ __launch_bounds__(256) void k_dedupe_write(GenDedupeParams p)
                 double x, y;
                 p.rays[pos + rank[r]] = generate_ray(p.g.lx, p.g.ly, p.g.lz, p.light_length, p.g0 + i, p.g.seed_prev[k],
                                                      p.g.seed_next[k], p.g.seed_mode, r0, x, y);
-                const uint32_t word = dedupe_deposit_word(classes, s_slot_mask, s_slot_word, mask[r]);
+                const uint32_t word = ((worded >> r) & 1u) ? mask[r] : dedupe_deposit_word(classes, s_slot_mask, s_slot_word, mask[r]);
                 p.masks[pos + rank[r]] = word;
                 dep += (uint32_t)dedupe_word_deposits(classes, word);
             }
@@ -704,8 +778,10 @@ void launch_generate_batch(const GenBatchParams& p, hipStream_t s)
 
 void launch_dedupe_mark(const GenDedupeParams& p, hipStream_t s)
 {
-    if (p.gn <= 0 || p.g.count <= 0 || p.tiles <= 0 || p.strip_tiles <= 0) return;
-    hipLaunchKernelGGL(k_dedupe_mark, dim3((unsigned)((p.tiles + p.strip_tiles - 1) / p.strip_tiles)), dim3(64), 0, s, p);
+    if (p.gn <= 0 || p.g.count <= 0 || (p.gaps <= 0 && p.per.count <= 0) || p.strip_tiles <= 0) return;
+    // the strips of the gaps, and with a period table a thread per launch and block of DD_SLOTS gids for the interiors' owners
+    const unsigned count_groups = p.per.count > 0 ? blocks_for((int64_t)p.g.count * blocks_for(p.gn, DD_SLOTS), 64) : 0u;
+    hipLaunchKernelGGL(k_dedupe_mark, dim3((unsigned)p.gap_strip0[p.gaps] + count_groups), dim3(64), 0, s, p);
 }
 
 void launch_generate_dedupe(const GenDedupeParams& p, hipStream_t s)
