@@ -531,6 +531,12 @@ int uvrt_plan_model_dose(uvrt_ctx* ctx, const float* durations, float* out, int3
  * met by the bounds); both synchronise */
 int uvrt_plan_read_exposure(uvrt_ctx* ctx, int32_t position, uint32_t* out, int32_t first, int32_t count);
 int uvrt_plan_read_required(uvrt_ctx* ctx, uint8_t* out, int32_t first, int32_t count);
+/* test hook: host values into E[position][first .. first + count) of a COUNTS plan, so that a test can plan on a matrix no
+ * trace gives (row sums past 2^32, competing classes, ties).  It counts as a capture (a solve does not refuse with "nothing
+ * captured") and leaves the per-position ray bookkeeping of uvrt_plan_capture_batch and the overflow flag as they are;
+ * synchronises.  UVRT_ERR_INVALID with nothing changed: an expected plan (uvrt_write_expected + uvrt_plan_capture_expected
+ * carry hand-written planes there), no plan, a position outside [0, P), a range outside [0, T), a null pointer. */
+int uvrt_plan_write_exposure(uvrt_ctx* ctx, int32_t position, const uint32_t* in, int32_t first, int32_t count);
 int uvrt_plan_end(uvrt_ctx* ctx);
 /* ---- bounded solve: columns with a value given in advance (a route that radiates while it drives) ----
  * d_p >= lower[p] on every column, and a FIXED column is no variable at all: d_p = lower[p].  With x = lower + e the

@@ -132,6 +132,7 @@ SYMBOLS = [
     ("uvrt_plan_begin_expected_variance", C.c_int, [_vp, _i32]),
     ("uvrt_plan_read_exposure_variance", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_plan_lower_confidence", C.c_int, [_vp, C.c_double]),
+    ("uvrt_plan_write_exposure", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_gather_refine", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("uvrt_read_gather_extra", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_refine_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
@@ -894,6 +895,11 @@ class Ctx:
         out = np.empty(count, dtype=np.uint32)
         self._ck(self._L.uvrt_plan_read_exposure(self._h, int(position), _ptr(out), int(first), int(count)))
         return out
+
+    def plan_write_exposure(self, position, values, first=0):
+        """test hook: uint32 values into E[position][first ...] of a counts plan; counts as a capture"""
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        self._ck(self._L.uvrt_plan_write_exposure(self._h, int(position), _ptr(v), int(first), int(v.size)))
 
     def plan_read_required(self, first=0, count=None):
         count = self.T - first if count is None else count

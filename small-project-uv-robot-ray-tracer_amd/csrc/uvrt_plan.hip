@@ -596,6 +596,22 @@ int uvrt_plan_read_exposure(uvrt_ctx* c, int32_t position, uint32_t* out, int32_
     return range_copy(c, c->plan->E.as<uint32_t>() + (size_t)position * c->T, 4, out, first, count, hipMemcpyDeviceToHost);
 }
 
+// test hook: host values into E[position][first .. first + count) of a counts plan.  It counts as a capture; the rays per
+// position and the overflow flag stay as they are (they describe traced batches, and a test writes what no trace gives).
+int uvrt_plan_write_exposure(uvrt_ctx* c, int32_t position, const uint32_t* in, int32_t first, int32_t count)
+{
+    if (!c || !c->plan) return fail(UVRT_ERR_INVALID, "uvrt_plan_write_exposure: no plan");
+    if (c->plan->expected) return fail(UVRT_ERR_INVALID, "uvrt_plan_write_exposure: the plan holds expected values (uvrt_write_expected, uvrt_plan_capture_expected)");
+    if (position < 0 || position >= c->plan->P)
+        return fail(UVRT_ERR_INVALID, "uvrt_plan_write_exposure: position %d outside [0,%d)", position, c->plan->P);
+    if (!range_ok(in, first, count, c->T)) return fail(UVRT_ERR_INVALID, "uvrt_plan_write_exposure: bad range");
+    if (int rc = range_copy(c, c->plan->E.as<uint32_t>() + (size_t)position * c->T, 4, const_cast<uint32_t*>(in), first, count,
+                            hipMemcpyHostToDevice))
+        return rc;
+    ++c->plan->captures;
+    return UVRT_OK;
+}
+
 int uvrt_plan_read_exposure_expected(uvrt_ctx* c, int32_t position, double* out, int32_t first, int32_t count)
 {
     if (!c || !c->plan || !c->plan->expected)

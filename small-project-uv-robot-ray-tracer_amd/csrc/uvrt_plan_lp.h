@@ -11,6 +11,10 @@
 //     covering LP's massive degeneracy (many rows tie at the optimum) does not stall the pivots.  The perturbation
 //     does not weaken anything: y stays a valid certificate (the caller divides sum y by max_p (A^T y)_p) and d = the
 //     shadow prices covers every row of W (A_W d >= 1 holds for the dual of any right-hand side).
+//   * a pivot candidate must exceed 1e-12 x the largest |entry| of the ENTERING COLUMN.  The floor is relative to that
+//     column alone, not to the largest entry of the whole matrix: the rows are scaled by r_t (and, bounded, by 1 / rho_t
+//     with rho_t down to 1e-9), so entries of different rows may lie more than 1e12 apart, and a floor taken from the
+//     largest of them would hide the only positive entry of a small row's column and call a covering LP unbounded.
 // d_p is the objective row's entry under slack p: exactly 0 for a position whose constraint is slack.
 #pragma once
 #include <algorithm>
@@ -22,7 +26,7 @@ namespace uvrt_plan_lp {
 
 class RestrictedLP {
 public:
-    explicit RestrictedLP(int P) : P_(P), cap_(0), n_(0), rhs_((size_t)P + 1, 0.0), basis_(P)
+    explicit RestrictedLP(int P) : P_(P), cap_(0), n_(0), rhs_((size_t)P + 1, 0.0), basis_(P), col_((size_t)P, 0.0)
     {
         grow(std::max(64, 2 * P));
         for (int p = 0; p < P; ++p) {
@@ -50,7 +54,6 @@ public:
             double rc = -1.0;                        // reduced cost -1 + d . a_j
             for (int p = 0; p < P_; ++p) rc += at(P_, p) * aj[p];
             at(P_, col) = rc;
-            for (int p = 0; p < P_; ++p) scale_ = std::max(scale_, std::fabs(aj[p]));
         }
         n_ += k;
     }
@@ -59,7 +62,6 @@ public:
     bool solve(int64_t max_pivots, int64_t* pivots)
     {
         const int64_t cols = P_ + n_;
-        const double eps = 1e-12 * std::max(scale_, 1.0);
         for (int64_t it = 0;; ++it) {
             int64_t e = -1;
             double best = -1e-12;
@@ -68,10 +70,16 @@ public:
                 if (obj[k] < best) { best = obj[k]; e = k; }
             if (e < 0) { if (pivots) *pivots += it; return true; }
             if (it >= max_pivots) { if (pivots) *pivots += it; return false; }
+            double amax = 0.0;                       // the pivot floor is relative to the entering column (above);
+            for (int q = 0; q < P_; ++q) {           // one strided walk down the tableau: the column is kept for the ratio test
+                col_[q] = at(q, e);
+                amax = std::max(amax, std::fabs(col_[q]));
+            }
+            const double eps = 1e-12 * amax;
             int r = -1;
             double rbest = 0, pbest = 0;
             for (int q = 0; q < P_; ++q) {
-                const double a = at(q, e);
+                const double a = col_[q];
                 if (a <= eps) continue;
                 const double ratio = rhs_[q] / a;
                 if (r < 0 || ratio < rbest || (ratio == rbest && a > pbest)) { r = q; rbest = ratio; pbest = a; }
@@ -94,10 +102,10 @@ public:
 private:
     int P_;
     int64_t cap_, n_;
-    double scale_ = 0.0;
     std::vector<double> tab_;           // (P + 1) rows x cap_ columns: [slacks | y columns], row P = objective
     std::vector<double> rhs_;           // P + 1
     std::vector<int64_t> basis_;
+    std::vector<double> col_;           // P: the entering column of the pivot at hand
     double& at(int64_t q, int64_t k) { return tab_[(size_t)q * cap_ + k]; }
     double at(int64_t q, int64_t k) const { return tab_[(size_t)q * cap_ + k]; }
 

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import plan_restate as pr
 from conftest import GLB, GOLDEN, ROOT, ROUTE
 
 pytestmark = pytest.mark.gpu
@@ -30,17 +31,6 @@ def _rt(positions=None, iterations=2, ppl=PPL):
     return rt
 
 
-def _areas(rt):
-    """k_prepare_scene's f32 triangle areas"""
-    t = rt.mesh.tris()
-    v0, v1, v2 = t[:, 0:3], t[:, 4:7], t[:, 8:11]
-    a, b = v0 - v1, v0 - v2
-    cx = a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]
-    cy = a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]
-    cz = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
-    return np.sqrt(cx * cx + cy * cy + cz * cz) / np.float32(2.0)
-
-
 def _lp(rt):
     """(E[P][T] float64, required mask, b_t of the required rows) of the last solve"""
     P = len(rt.lamps())
@@ -51,7 +41,7 @@ def _lp(rt):
 
 def _rhs(rt, m, margin=1e-6):
     N = rt.maxIterations * rt.photonsPerLight
-    den = (_areas(rt) * np.float32(N)).astype(np.float64)
+    den = (pr.areas(rt.mesh.tris()) * np.float32(N)).astype(np.float64)
     s = float(np.float32(np.float32(rt.lightIntensity) * np.float32(0.1)))
     return m * (1.0 + margin) * den / s
 
@@ -165,6 +155,13 @@ def test_plan_holds_in_the_pipeline_and_is_optimal(pkg, positions):
         m = float(np.float32(rt.minDosage))
         d, rep = rt.PlanDurations()
         assert rep["required"] > 0 and rep["min_dose_ratio"] >= 1.0
+        # the solver's word, restated: min over the required rows of D_t(d) / m in f64, bit for bit
+        E = np.stack([rt.ctx.plan_read_exposure(p) for p in range(d.size)])
+        s = np.float32(rt.lightIntensity) * np.float32(0.1)
+        cl = pr.classify(E, pr.areas(rt.mesh.tris()), s, rt.maxIterations * rt.photonsPerLight, m, 1e-6, 16)
+        assert np.array_equal(rt.ctx.plan_read_classes(), cl["cls"])
+        ratio = pr.min_dose_ratio(E, cl, d)
+        assert np.float64(rep["min_dose_ratio"]).view(np.uint64) == np.float64(ratio).view(np.uint64), (rep["min_dose_ratio"], ratio)
         assert np.array_equal(np.array([l[2] for l in rt.lamps()], dtype=np.float32), d)
         _check_optimality(rt, d, rep, m)
         req = rt.ctx.plan_read_required()
@@ -247,7 +244,7 @@ def test_edges(pkg, tmp_path):
         assert not rt.ctx.plan_read_exposure(2).any() and d[2] == 0.0 and d[:2].sum() > 0
         # unreachable: no photon from any position (or no area), with its f32 areas summed
         E, req = _lp(rt)
-        area = _areas(rt).astype(np.float64)
+        area = pr.areas(rt.mesh.tris()).astype(np.float64)
         unreach = (E.sum(axis=0) == 0) | ~(area > 0)
         assert rep["unreachable"] == int(unreach.sum()) > 0
         assert abs(rep["area_unreachable"] - float(area[unreach].sum())) <= 1e-9 * max(1.0, float(area.sum()))

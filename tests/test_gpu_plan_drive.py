@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import plan_restate as pr
 from conftest import GLB, GOLDEN, ROOT, ROUTE
 from sweep_restate import segment_duration, sweep
 
@@ -23,17 +24,6 @@ f32 = np.float32
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _areas_of(tris):
-    """k_prepare_scene's f32 triangle areas (as tests/test_gpu_plan.py forms them)"""
-    t = np.ascontiguousarray(tris).view(np.float32).reshape(-1, 16)
-    v0, v1, v2 = t[:, 0:3], t[:, 4:7], t[:, 8:11]
-    a, b = v0 - v1, v0 - v2
-    cx = a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]
-    cy = a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]
-    cz = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
-    return np.sqrt(cx * cx + cy * cy + cz * cz) / np.float32(2.0)
 
 
 def _world(orc, oscene, oroute, lamps):
@@ -122,7 +112,7 @@ class Captured:
         c.plan_capture_batch(list(range(5)) * ITER)
         c.replay_batch(np.zeros(5 * ITER, dtype=pkg.capi.REPLAY_OP_DT))
         self.E = np.stack([c.plan_read_exposure(p) for p in range(5)])
-        self.area = _areas_of(oscene.tris)
+        self.area = pr.areas(oscene.tris)
         self.cache = {}
 
     def bounds(self, variant):
@@ -245,6 +235,11 @@ def test_classes_and_optimum_against_numpy_and_highs(cap, variant):
     _check_columns(lower, fixed, out)
     _check_against_highs(cap.E, req, den, mprime, cap.s, lower, fixed, out, rep, brep)
     assert rep["min_dose_ratio"] >= 1.0
+    # the solver's word, restated: the x-space minimum over classes 0 and 4 in f64, bit for bit
+    cl = pr.classify(cap.E, cap.area, cap.s, cap.N, M, MARGIN, minph, lower=lower, fixed=fixed)
+    assert np.array_equal(cl["cls"], want)
+    ratio = pr.min_dose_ratio(cap.E, cl, out)
+    assert np.float64(rep["min_dose_ratio"]).view(np.uint64) == np.float64(ratio).view(np.uint64), (rep["min_dose_ratio"], ratio)
 
 
 def test_segment_times_as_lower_bounds_cost_no_more_than_fixed_segments(cap):
@@ -379,7 +374,7 @@ def test_largest_driving_route(pkg):
         fixed = np.concatenate([np.zeros(128, dtype=np.uint8), np.ones(127, dtype=np.uint8)])
         s = f32(f32(rt.lightIntensity) * f32(0.1))
         N = rt.maxIterations * rt.photonsPerLight
-        want, den, mprime = _restate_classes(E, _areas_of(rt.mesh.tris()), lower, fixed, s, N, m, MARGIN, 16)
+        want, den, mprime = _restate_classes(E, pr.areas(rt.mesh.tris()), lower, fixed, s, N, m, MARGIN, 16)
         assert np.array_equal(rt.ctx.plan_read_classes(), want)
         out = np.concatenate([d, seg])
         brep = {"lower_total": rep["lower_total"]}

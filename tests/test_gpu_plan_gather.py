@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gather_restate as gr
+import plan_restate as pr
 from conftest import GLB, GOLDEN, ROOT, ROUTE
 from sweep_restate import segment_duration
 
@@ -31,17 +32,6 @@ def bits(a):
 
 def bits64(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _areas_of(tris):
-    """k_prepare_scene's f32 triangle areas (as tests/test_gpu_plan.py forms them)"""
-    t = np.ascontiguousarray(tris).view(np.float32).reshape(-1, 16)
-    v0, v1, v2 = t[:, 0:3], t[:, 4:7], t[:, 8:11]
-    a, b = v0 - v1, v0 - v2
-    cx = a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1]
-    cy = a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2]
-    cz = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
-    return np.sqrt(cx * cx + cy * cy + cz * cz) / np.float32(2.0)
 
 
 def _comp(orc, oscene, oroute):
@@ -245,7 +235,7 @@ def test_the_gather_feeds_the_plan(pkg, oscene, oroute, restated, mode):
         seg = np.array([segment_duration(lamps[k][:2], lamps[k + 1][:2], SPEED) for k in range(2)], dtype=np.float32)
         lower = np.concatenate([np.zeros(3, dtype=np.float32), seg]) if drive else np.zeros(3, dtype=np.float32)
         fixed = np.array([0, 0, 0, 1, 1][:P], dtype=bool)
-        area = _areas_of(oscene.tris)
+        area = pr.areas(oscene.tris)
         cls, den, mprime, r, rho = _restate_classes(X, area, lower, fixed, s, N, m, 16, drive)
         got_cls = rt.ctx.plan_read_classes()
         n = [int((cls == k).sum()) for k in range(6)]

@@ -214,6 +214,9 @@ def test_reference_generate_kernel_is_the_oracle_under_one_of_two_seeds(ref, pkg
         c.close()
 
 
+RACE_ATTEMPTS = 8       # whole chains tried before the test gives the reference's SEED race up (each is well under a second)
+
+
 def test_whole_reference_kernel_chain_on_this_gpu_against_the_product(ref, pkg, orc, oscene, oroute):
     """No oracle in between: generate.cl -> extend.cl -> accumulate.cl -> shade.cl:computeDosage of the
     reference, all compiled unmodified and run live on this GPU (fresh module: SEED = 0), for lamps
@@ -225,8 +228,6 @@ def test_whole_reference_kernel_chain_on_this_gpu_against_the_product(ref, pkg, 
     length = oroute["lightLength"]
     comp = orc.Computation(oscene, lamps, 3 * n, oroute["lightHeight"], length, oroute["lightIntensity"])
     T = oscene.T
-    r_pm, r_mm = np.zeros(T), np.zeros(T)
-    orc.refgpu_reload()
     c = pkg.capi.Ctx(0)
     try:
         c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
@@ -234,23 +235,39 @@ def test_whole_reference_kernel_chain_on_this_gpu_against_the_product(ref, pkg, 
         c.set_flavour(1)
         c.set_seed_mode(1)
         c.set_record_hits(True)
-        c.reset(True)
-        size = 0
-        for it in range(2):
-            for lamp in lamps:
-                lp = comp.lamp_world_pos(lamp)
-                r_rays, _ = orc.refgpu_generate(n, lp, length)
-                c.generate(lp, length, 0, n)
-                if not np.array_equal(_ray_rows(c.read_rays(0, n)), _ray_rows(r_rays)):
-                    pytest.skip("the reference's SEED race resolved differently in this run (late readers)")
-                r_counts, _ = orc.refgpu_extend(r_rays, oscene.tris, oscene.nodes, oscene.triIdx)
-                c.extend(n)
-                got = c.read_rays(0, n)
-                assert np.array_equal(bits(got["dist"]), bits(r_rays["dist"])) and np.array_equal(got["triID"], r_rays["triID"])
-                assert np.array_equal(c.read_counts(), r_counts) and r_counts.sum() > 0.8 * n
-                c.accumulate(lamp[2])
-                orc.refgpu_accumulate(r_pm, r_mm, r_counts, lamp[2])
-                size += n
+        # The reference's generate.cl races on SEED.  When a launch resolves it with late readers (about one fresh process
+        # in four, docs/HISTORY.md) its rays are none the product can make, and the chain starts over on a fresh module
+        # (SEED = 0) and fresh maps on both sides; every comparison below is made on a chain that ran from SEED = 0 to
+        # its end.  The test skips itself only if the race goes the other way RACE_ATTEMPTS times in a row.
+        for attempt in range(RACE_ATTEMPTS):
+            r_pm, r_mm = np.zeros(T), np.zeros(T)
+            orc.refgpu_reload()
+            c.reset(True)
+            c.seed = 0
+            size, late = 0, False
+            for it in range(2):
+                for lamp in lamps:
+                    lp = comp.lamp_world_pos(lamp)
+                    r_rays, _ = orc.refgpu_generate(n, lp, length)
+                    c.generate(lp, length, 0, n)
+                    if not np.array_equal(_ray_rows(c.read_rays(0, n)), _ray_rows(r_rays)):
+                        late = True
+                        break
+                    r_counts, _ = orc.refgpu_extend(r_rays, oscene.tris, oscene.nodes, oscene.triIdx)
+                    c.extend(n)
+                    got = c.read_rays(0, n)
+                    assert np.array_equal(bits(got["dist"]), bits(r_rays["dist"])) and np.array_equal(got["triID"], r_rays["triID"])
+                    assert np.array_equal(c.read_counts(), r_counts) and r_counts.sum() > 0.8 * n
+                    c.accumulate(lamp[2])
+                    orc.refgpu_accumulate(r_pm, r_mm, r_counts, lamp[2])
+                    size += n
+                if late:
+                    break
+            if not late:
+                break
+            print("attempt %d: the reference's SEED race resolved with late readers after %d launches" % (attempt, size // n))
+        if late:
+            pytest.skip("the reference's SEED race resolved differently %d times in a row (late readers)" % RACE_ATTEMPTS)
         ppl = size // len(lamps)
         power = float(np.float32(oroute["lightIntensity"]) * np.float32(0.1))
         c.compute_dosage(0, ppl, power)
