@@ -1,7 +1,9 @@
 // uvrt_ctx.h -- the context behind the C ABI of include/uvrt.h, shared by the translation units that implement it:
 //   uvrt_capi.hip         context, scene, buffers, knobs, read-backs and test hooks
 //   uvrt_capi_launch.hip  the per-launch entry points (generate, extend, accumulate, shade) and the launch lanes
-//   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / uvrt_trace_batch_launches / fold / replay)
+//   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / uvrt_trace_batch_launches / fold / replay): provisioning, the
+//                         chunk emitters and the commit, over the plan of
+//   uvrt_batch_plan.h     the host-only plan of a batch (plan_batch, deal_classes, mark_tiles): no HIP, testable alone
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
 //                         uvrt_set_gather_variance and the variance plane, uvrt_gather_refine)
@@ -22,6 +24,7 @@
 #pragma once
 #include "../../include/uvrt.h"
 #include "uvrt_device.h"
+#include "uvrt_batch_plan.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -223,7 +226,7 @@ struct uvrt_ctx {
                                           // beside a traversal grid (uvrt_device.h helper_priority); read at every launch
     bool dedupe = true;                   // uvrt_set_dedupe / UVRT_DEDUPE: a lamp's distinct rays are traced once per batch (uvrt_dedupe.h)
     int64_t b_traced_known = -1;          // uvrt_batch_traced_rays: the last traced batch's rays in chunks traced as they are ...
-    int32_t dedupe_strip = 0;             // tiles per wave of the mark pass (developer knob UVRT_DEDUPE_STRIP; 0: uvrt_capi_batch.hip mark_tiles)
+    int32_t dedupe_strip = 0;             // tiles per wave of the mark pass (developer knob UVRT_DEDUPE_STRIP; 0: uvrt_batch_plan.h mark_tiles)
     int32_t b_traced_chunks = 0;          // ... and its deduped chunks, whose counts are bs[b_set].dd_counts[0, b_traced_chunks)
     // mask classes of a batch's dedupe groups (uvrt_dedupe.h "mask classes")
     int32_t dedupe_classes = uvrt::DEDUPE_CLASSES_DEFAULT;     // uvrt_set_dedupe_classes / UVRT_DEDUPE_CLASSES: classes per group at most, 0 = none

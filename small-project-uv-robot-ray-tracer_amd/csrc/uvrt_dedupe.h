@@ -33,6 +33,10 @@
 
 namespace uvrt {
 
+// (the batch's own limits, here for the host-only plan of a batch, uvrt_batch_plan.h, and the device structs alike)
+constexpr int MAX_BATCH = 64;              // launches per uvrt_trace_batch / uvrt_replay_batch call
+constexpr int MAX_CLASS_PLANES = 64;       // class planes of one batch, all its dedupe groups together (one bit each in ReplayParams::class_of)
+
 constexpr int DEDUPE_MAX = 31;             // launches per group: bit 31 of a ray's mask is the exact-step flag
 constexpr int64_t DEDUPE_GID_END = 126322567;   // 17 gid + 1 fits an int32 below this
 
@@ -276,6 +280,31 @@ UVRT_HD int32_t dedupe_strip_first(const DedupeGroup& G, int j, int64_t t0)
     return dedupe_lower_bound(G, j, t0, (int32_t)(G.first_gid > 1 ? G.first_gid : 1), (int32_t)(G.first_gid + G.n));
 }
 
+// Host: one tile's table over the keys [t0, t0 + W), as the mark pass fills it: every launch's run over the call's WHOLE range
+// with dedupe_tile_insert_run, then gid 0 with dedupe_tile_insert.  A run starts at start[j] (the g_hi a strip carries from its
+// previous tile; start may be g_hi itself) or, without `start`, where a search finds it, and ends where its keys leave the tile:
+// g_lo / g_hi.  Returns whether some launch's gid 0 fell in the tile.
+inline bool dedupe_tile_fill(const DedupeGroup& G, int64_t t0, int32_t W, const int32_t* start, uint32_t* table, int32_t* g_lo, int32_t* g_hi)
+{
+    const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
+    for (int32_t i = 0; i < W; ++i) table[i] = 0u;
+    for (int j = 0; j < G.count; ++j) {
+        g_lo[j] = start ? start[j] : dedupe_strip_first(G, j, t0);
+        const uint32_t seed1 = dedupe_seed1(G, j);
+        int32_t g = g_lo[j];
+        for (; g < hi; ++g) {
+            const int32_t key = dedupe_key1_of(G, seed1, g);
+            if (!dedupe_in_tile(key, t0, W)) break;
+            dedupe_tile_insert_run(table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(G, seed1, g, key, lo, hi));
+        }
+        g_hi[j] = g;
+    }
+    bool gid0 = false;
+    for (int j = 0; j < G.count; ++j)
+        if (dedupe_tile_holds_gid0(G, j, t0, W)) { dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j); gid0 = true; }
+    return gid0;
+}
+
 // Host: the masks of the chunk [c0, c0 + cn) of a group's range, masks[k * cn + i], tile by tile with a table of W entries,
 // in strips of `strip` tiles with carried bounds as the device walks them (the device's strip length is its launcher's choice,
 // DEDUPE_STRIP_TILES and more; the masks depend on it as little as on W)
@@ -285,25 +314,11 @@ inline void dedupe_plan_tiled_keys(const DedupeGroup& G, int32_t W, int32_t stri
                                    uint32_t* table, uint32_t* masks)
 {
     const int64_t tiles = (keys + W - 1) / W;
-    const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
     int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
     for (int64_t tile = 0; tile < tiles; ++tile) {
         const int64_t t0 = key_lo + tile * W;
         const int32_t w = (int32_t)(keys - tile * W < W ? keys - tile * W : W);
-        for (int32_t i = 0; i < W; ++i) table[i] = 0u;
-        for (int j = 0; j < G.count; ++j) {
-            g_lo[j] = tile % strip == 0 ? dedupe_strip_first(G, j, t0) : g_hi[j];
-            const uint32_t seed1 = dedupe_seed1(G, j);
-            int32_t g = g_lo[j];
-            for (; g < hi; ++g) {
-                const int32_t key = dedupe_key1_of(G, seed1, g);
-                if (!dedupe_in_tile(key, t0, w)) break;
-                dedupe_tile_insert_run(table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(G, seed1, g, key, lo, hi));
-            }
-            g_hi[j] = g;
-        }
-        for (int j = 0; j < G.count; ++j)
-            if (dedupe_tile_holds_gid0(G, j, t0, w)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
+        dedupe_tile_fill(G, t0, w, tile % strip == 0 ? nullptr : g_hi, table, g_lo, g_hi);
         for (int k = 0; k < G.count; ++k) {
             const int64_t a = g_lo[k] > c0 ? g_lo[k] : c0, b = g_hi[k] < c0 + cn ? g_hi[k] : c0 + cn;
             for (int64_t g = a; g < b; ++g)
@@ -378,15 +393,39 @@ inline void dedupe_classes_fill(DedupeClasses& C, const uint32_t* masks, int cou
     }
 }
 
-// Host: one tile's table, as dedupe_plan_tiled fills it (every launch's run over the call's whole range, and gid 0)
-inline void dedupe_tile_fill(const DedupeGroup& G, int32_t W, int64_t t0, uint32_t* table, int32_t* g_lo, int32_t* g_hi)
+// Host: the ends of a group's keys over the gids >= 1 of the call's range, [lo1, last]: the smallest first key of a launch and
+// one past the largest last key
+inline void dedupe_key_span(const DedupeGroup& G, int64_t lo1, int64_t last, int64_t& klo, int64_t& khi)
 {
-    for (int32_t i = 0; i < W; ++i) table[i] = 0u;
+    klo = INT64_MAX;
+    khi = INT64_MIN;
     for (int j = 0; j < G.count; ++j) {
-        dedupe_tile_run(G, j, t0, W, g_lo[j], g_hi[j]);
-        for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) dedupe_tile_insert(table, dedupe_tile_slot(dedupe_key1(G, j, g), t0), j);
-        if (dedupe_tile_holds_gid0(G, j, t0, W)) dedupe_tile_insert(table, dedupe_tile_slot(G.key0[j], t0), j);
+        const int64_t a = dedupe_key1(G, j, (int32_t)lo1), b = (int64_t)dedupe_key1(G, j, (int32_t)last) + 1;
+        klo = a < klo ? a : klo;
+        khi = b > khi ? b : khi;
     }
+}
+// Host: the sorted cut points between a group's strata (the tally below and the period table have the reasons): every launch's
+// first key of [lo1, last] and one past its last, and for the binades b_first .. b_last the boundary 2^b and 2^b + s_j of
+// every launch.  `ends`: work-item 0's keys (a range from gid 0) and the range ends klo / khi, as the caller has clamped them,
+// are cuts too.  `cut`: room for 3 K + (b_last - b_first + 1) (K + 1) + 2.  Returns their number.
+inline int dedupe_cuts(const DedupeGroup& G, int64_t lo1, int64_t last, int b_first, int b_last, bool ends, int64_t klo, int64_t khi,
+                       int64_t* cut)
+{
+    int ncut = 0;
+    for (int j = 0; j < G.count; ++j) {
+        cut[ncut++] = dedupe_key1(G, j, (int32_t)lo1);
+        cut[ncut++] = (int64_t)dedupe_key1(G, j, (int32_t)last) + 1;
+        if (ends && G.first_gid == 0) cut[ncut++] = G.key0[j];
+    }
+    if (ends) { cut[ncut++] = klo; cut[ncut++] = khi; }
+    for (int b = b_first; b <= b_last; ++b) {
+        const int64_t B = (int64_t)1 << b;
+        cut[ncut++] = B;
+        for (int j = 0; j < G.count; ++j) cut[ncut++] = B + (int64_t)(dedupe_seed1(G, j) >> 15);
+    }
+    std::sort(cut, cut + ncut);
+    return ncut;
 }
 
 // Host: the multi-bit masks of a group's owners by frequency, from a thin sample: one narrow key tile per STRATUM of the keys.
@@ -408,30 +447,16 @@ inline int dedupe_class_tally(const DedupeGroup& G, uint32_t* table, DedupeTally
     uint32_t used = 0;
     double seen = 0.0;
     // the strata's bounds
-    int64_t cut[2 * DEDUPE_MAX + 7 * (DEDUPE_MAX + 1) + 2];
-    int ncut = 0;
+    int64_t cut[3 * DEDUPE_MAX + 7 * (DEDUPE_MAX + 1) + 2];
     const int64_t last = G.first_gid + G.n - 1, lo1 = G.first_gid > 1 ? G.first_gid : 1;
     if (lo1 > last) { if (keys) *keys = 0.0; return 0; }
-    int64_t klo = INT64_MAX, khi = INT64_MIN;
-    for (int j = 0; j < G.count; ++j) {
-        const int64_t a = dedupe_key1(G, j, (int32_t)lo1), b = (int64_t)dedupe_key1(G, j, (int32_t)last) + 1;
-        cut[ncut++] = a;
-        cut[ncut++] = b;
-        klo = a < klo ? a : klo;
-        khi = b > khi ? b : khi;
-    }
-    for (int b = 24; b <= 30; ++b) {
-        const int64_t B = (int64_t)1 << b;
-        if (B + 131072 <= klo || B >= khi) continue;
-        cut[ncut++] = B;
-        for (int j = 0; j < G.count; ++j) cut[ncut++] = B + (int64_t)((G.seed_mode == 1 ? G.seed_prev[j] : G.seed_next[j]) >> 15);
-    }
-    for (int i = 1; i < ncut; ++i) {            // (insertion sort: a few dozen points)
-        const int64_t v = cut[i];
-        int at = i;
-        for (; at > 0 && cut[at - 1] > v; --at) cut[at] = cut[at - 1];
-        cut[at] = v;
-    }
+    int64_t klo, khi;
+    dedupe_key_span(G, lo1, last, klo, khi);
+    // (only the binades whose points can lie among the keys: B + 131072 <= klo holds up to some binade, B >= khi from one on)
+    int b_first = 24, b_last = 30;
+    while (b_first <= b_last && ((int64_t)1 << b_first) + 131072 <= klo) ++b_first;
+    while (b_last >= b_first && ((int64_t)1 << b_last) >= khi) --b_last;
+    const int ncut = dedupe_cuts(G, lo1, last, b_first, b_last, false, klo, khi, cut);
     int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
     for (int i = 0; i + 1 < ncut; ++i) {
         const int64_t a = cut[i] < klo ? klo : cut[i], b = cut[i + 1] > khi ? khi : cut[i + 1];
@@ -442,7 +467,7 @@ inline int dedupe_class_tally(const DedupeGroup& G, uint32_t* table, DedupeTally
         W = W > DEDUPE_TILE_KEYS ? DEDUPE_TILE_KEYS : W;
         W = W > b - a ? b - a : W;
         const double weight = (double)(b - a) / (double)W;
-        dedupe_tile_fill(G, (int32_t)W, a + (b - a - W) / 2, table, g_lo, g_hi);
+        dedupe_tile_fill(G, a + (b - a - W) / 2, (int32_t)W, nullptr, table, g_lo, g_hi);
         for (int32_t k = 0; k < (int32_t)W; ++k) {
             const uint32_t e = table[k];
             if (e == 0u || (e & DEDUPE_MANY)) continue;
@@ -482,7 +507,7 @@ inline int64_t dedupe_class_deposits(const DedupeGroup& G, int32_t W, const Dedu
     int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
     for (int64_t tile = 0; tile < tiles; ++tile) {
         const int64_t t0 = key_lo + tile * W;
-        dedupe_tile_fill(G, W, t0, table, g_lo, g_hi);
+        dedupe_tile_fill(G, t0, W, nullptr, table, g_lo, g_hi);
         for (int32_t i = 0; i < W; ++i) {
             const uint32_t e = table[i];
             if (e != 0u && !(e & DEDUPE_MANY)) total += dedupe_word_deposits(C.count > 0, dedupe_deposit_word(C.count > 0, C.slot_mask, C.slot_word, e));
@@ -634,18 +659,8 @@ inline int dedupe_periodic_gaps(const DedupePeriodic& T, int64_t key_lo, int64_t
 inline bool dedupe_periodic_tile(const DedupeGroup& G, int64_t t0, int32_t P, uint32_t* table, uint32_t* out)
 {
     const int32_t W = 68 * P;
-    const int32_t lo = (int32_t)(G.first_gid > 1 ? G.first_gid : 1), hi = (int32_t)(G.first_gid + G.n);
     int32_t g_lo[DEDUPE_MAX], g_hi[DEDUPE_MAX];
-    for (int32_t i = 0; i < W; ++i) table[i] = 0u;
-    for (int j = 0; j < G.count; ++j) {
-        dedupe_tile_run(G, j, t0, W, g_lo[j], g_hi[j]);
-        const uint32_t seed1 = dedupe_seed1(G, j);
-        for (int32_t g = g_lo[j]; g < g_hi[j]; ++g) {
-            const int32_t key = dedupe_key1_of(G, seed1, g);
-            dedupe_tile_insert_run(table, dedupe_tile_slot(key, t0), j, dedupe_run_twice(G, seed1, g, key, lo, hi));
-        }
-        if (dedupe_tile_holds_gid0(G, j, t0, W)) return false;
-    }
+    if (dedupe_tile_fill(G, t0, W, nullptr, table, g_lo, g_hi)) return false;
     for (int32_t i = 0; i < W; ++i)
         if (table[i] & DEDUPE_MANY) return false;
     for (int k = 0; k < G.count; ++k) {
@@ -674,30 +689,14 @@ inline void dedupe_periodic_build(const DedupeGroup& G, const DedupeClasses& C, 
     const int64_t L = (int64_t)lamp + 1, E = 32, M = L + E + 34 * DEDUPE_PERIOD_MAX;
     constexpr int BINADES = 27;                   // 2^0 .. 2^26; the keys from 2^27 on are left out below
     int64_t cut[3 * DEDUPE_MAX + BINADES * (DEDUPE_MAX + 1) + 2];
-    int ncut = 0;
-    int64_t klo = INT64_MAX, khi = INT64_MIN, smax = 0;
-    for (int j = 0; j < K; ++j) {
-        const int64_t a = dedupe_key1(G, j, (int32_t)lo1), b = (int64_t)dedupe_key1(G, j, (int32_t)last) + 1;
-        cut[ncut++] = a;
-        cut[ncut++] = b;
-        if (G.first_gid == 0) cut[ncut++] = G.key0[j];
-        klo = a < klo ? a : klo;
-        khi = b > khi ? b : khi;
-        const int64_t s = (int64_t)(dedupe_seed1(G, j) >> 15);
-        smax = s > smax ? s : smax;
-    }
+    int64_t klo, khi, smax = 0;
+    dedupe_key_span(G, lo1, last, klo, khi);
+    for (int j = 0; j < K; ++j) smax = std::max(smax, (int64_t)(dedupe_seed1(G, j) >> 15));
     const int64_t floor_key = smax + L + E + 1;
     klo = klo < floor_key ? floor_key : klo;
     khi = khi > ((int64_t)1 << 27) ? ((int64_t)1 << 27) : khi;
     if (khi - klo < 2 * M) return;
-    cut[ncut++] = klo;
-    cut[ncut++] = khi;
-    for (int b = 0; b < BINADES; ++b) {
-        const int64_t B = (int64_t)1 << b;
-        cut[ncut++] = B;
-        for (int j = 0; j < K; ++j) cut[ncut++] = B + (int64_t)(dedupe_seed1(G, j) >> 15);
-    }
-    std::sort(cut, cut + ncut);
+    const int ncut = dedupe_cuts(G, lo1, last, 0, BINADES - 1, true, klo, khi, cut);
     // the candidates: every stratum's interior that is long enough, then the longest that fit the caps
     struct Cand { int64_t a, b; int32_t P; };
     Cand cand[DEDUPE_PERIODIC_STRATA + 1];

@@ -159,8 +159,7 @@ __device__ __forceinline__ float4 generate_ray(float lx, float ly, float lz, flo
 constexpr uint32_t TOP6_MAX = 175;        // records cached in LDS: 176 x 64 B + 9 stack rows = 20 KB per workgroup, eight per CU
 
 // ---- batched tracing (include/uvrt.h uvrt_trace_batch): several launches' rays side by side ----
-constexpr int MAX_BATCH = 64;          // launches per uvrt_trace_batch / uvrt_replay_batch call
-
+// (MAX_BATCH, the launches per uvrt_trace_batch / uvrt_replay_batch call, and MAX_CLASS_PLANES: uvrt_dedupe.h)
 struct GenBatchParams {
     float4* rays;                      // [count][n_pad]: physical plane p at rays + p * n_pad
     int64_t n_pad;                     // rays per plane in the buffer (n rounded up to 64)
@@ -238,7 +237,6 @@ struct ReplayParams {
     uint64_t class_of[MAX_BATCH];
     ReplayOp ops[MAX_BATCH];
 };
-constexpr int MAX_CLASS_PLANES = 64;   // class planes of one batch, all its dedupe groups together (one bit each in class_of)
 
 // the class planes of a batch added into the folded planes of the launches their masks hold, and zeroed
 struct FoldClassParams {

@@ -163,8 +163,12 @@ def groups_of(step, pool):
         if len(ks) < 2 or len({pool[step["launches"][k][1]][1] for k in ks}) != 1:
             continue
         pieces = (len(ks) + DEDUPE_MAX - 1) // DEDUPE_MAX
-        per = (len(ks) + pieces - 1) // pieces
-        out += [ks[k0:k0 + per] for k0 in range(0, len(ks), per) if len(ks[k0:k0 + per]) >= 2]
+        k0 = 0
+        for i in range(pieces):           # sizes that differ by one at most, the larger pieces first (64: 22 + 21 + 21)
+            kc = len(ks) // pieces + (i < len(ks) % pieces)
+            if kc >= 2:
+                out.append(ks[k0:k0 + kc])
+            k0 += kc
     return out
 
 

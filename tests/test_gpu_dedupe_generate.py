@@ -85,7 +85,7 @@ def test_strip_seams(pkg, ctx, groups, name):
     """a chunk that begins inside the range, so that the chunk's first tile is not the range's.  check_mark compares every
     mask of the chunk; what this test adds is the proof that the chunk holds occurrences within a gid's step of a tile's
     first key, below it and at or above it, at tile seams and at strip seams.  (Strips of capi.DEDUPE_STRIP_TILES tiles:
-    what mark_tiles in csrc/uvrt_capi_batch.hip picks for chunks of fewer than 5 x 4 096 tiles, as these are; with longer
+    what mark_tiles in csrc/uvrt_batch_plan.h picks for chunks of fewer than 5 x 4 096 tiles, as these are; with longer
     strips every strip seam is still a tile seam.)"""
     capi, g = pkg.capi, groups[name]
     first, n = (g.first, g.n) if g.first == 0 else (g.first + 300, g.n - 600)
