@@ -1,6 +1,10 @@
 // uvrt_capi.hip -- context, scene, buffers, knobs, read-backs and test hooks
 // (the C ABI of include/uvrt.h over the HIP kernels; the context and its helpers are in uvrt_ctx.h)
 #include "uvrt_ctx.h"
+#include "uvrt_scene_layout.h"
+
+#include <climits>
+#include <cstddef>
 
 using namespace uvrt;
 using namespace uvrt_impl;
@@ -33,6 +37,133 @@ uvrt_ctx::~uvrt_ctx()
     if (probe_stream) (void)hipStreamDestroy(probe_stream);
     if (own_stream) (void)hipStreamDestroy(own_stream);
 }
+
+namespace {
+
+namespace sl = uvrt::scene_layout;
+using sl::SceneLayout;
+
+// the layout's records are uploaded as the device's, byte for byte, and its constants are the device's
+#define SAME_FIELD(A, B, f) (offsetof(A, f) == offsetof(B, f))
+static_assert(sizeof(sl::F4) == sizeof(float4) && SAME_FIELD(sl::F4, float4, x) && SAME_FIELD(sl::F4, float4, y) &&
+              SAME_FIELD(sl::F4, float4, z) && SAME_FIELD(sl::F4, float4, w), "F4 is float4's words");
+static_assert(sizeof(sl::PairWords) == sizeof(PairRec) && SAME_FIELD(sl::PairWords, PairRec, c0min_ref0) &&
+              SAME_FIELD(sl::PairWords, PairRec, c0max_ref1) && SAME_FIELD(sl::PairWords, PairRec, c1min) &&
+              SAME_FIELD(sl::PairWords, PairRec, c1max), "PairWords is PairRec");
+static_assert(sizeof(sl::QuadWords) == sizeof(QuadRec) && SAME_FIELD(sl::QuadWords, QuadRec, xz) && SAME_FIELD(sl::QuadWords, QuadRec, y01) &&
+              SAME_FIELD(sl::QuadWords, QuadRec, y23) && SAME_FIELD(sl::QuadWords, QuadRec, ref) && SAME_FIELD(sl::QuadWords, QuadRec, pad),
+              "QuadWords is QuadRec");
+#undef SAME_FIELD
+static_assert(sl::REF_LEAF_BIT == uvrt::REF_LEAF_BIT && sl::REF_DONE == uvrt::REF_DONE && sl::REF_COUNT_SHIFT == uvrt::REF_COUNT_SHIFT &&
+              sl::MAX_TRIS == uvrt::MAX_TRIS && sl::TOP6_MAX == uvrt::TOP6_MAX, "uvrt_scene_layout.h restates uvrt_device.h's constants");
+
+// An environment knob: the integer in `name`, where it is set and lies in [lo, hi], into `field`; true when it was taken.
+template <class I>
+bool env_int(const char* name, long lo, long hi, I& field)
+{
+    const char* e = getenv(name);
+    if (!e) return false;
+    const long v = atol(e);
+    if (v < lo || v > hi) return false;
+    field = (I)v;
+    return true;
+}
+// ... and an on / off knob: anything but 0 is on
+void env_bool(const char* name, bool& field)
+{
+    if (const char* e = getenv(name)) field = atoi(e) != 0;
+}
+
+// the scene's buffers and, where T changes, the per-triangle maps (the streams are joined and idle)
+int provision_scene(uvrt_ctx* c, const SceneLayout& L, int32_t T)
+{
+    const bool resized = (T != c->T);
+    int rc;
+    if ((rc = c->pairs.ensure(std::max<size_t>(L.pairs.size(), 1) * sizeof(PairRec), false, c->stream))) return rc;
+    for (int l = 0; l < c->nlanes; ++l)
+        if ((rc = c->lanes[l].recs.ensure((L.pairs.size() + (size_t)T + 1) * 64, true, c->stream))) return rc;
+    // + 16 bytes: the merged record fetch of the traversal reads 64 bytes at every leaf record
+    if ((rc = c->ltris.ensure((size_t)T * sizeof(LeafTri) + 16, true, c->stream))) return rc;
+    if ((rc = c->leaf_count.ensure((size_t)T * 4, false, c->stream))) return rc;
+    if ((rc = c->area.ensure((size_t)T * 4, false, c->stream))) return rc;
+    if (resized || !c->photon_map.p) {
+        // raytracer.cpp:32-37 (the reference leaves them uninitialised until reset; zero here)
+        // The colour buffer stands for the GL vertex buffer of the caller's mesh (raytracer.cpp:37): a scene swap
+        // does not touch it.  It only grows, so CalibratePower's detour over a 2-triangle scene
+        // (raytracer.cpp:166-224, ClearBuffers(false)) leaves the room's colours as they were.
+        for (DevBuf* b : {&c->photon_map, &c->max_map, &c->dosage}) b->release();
+        for (Lane& La : c->lanes) La.counts.release();
+        if ((rc = c->photon_map.ensure((size_t)T * 8, true, c->stream))) return rc;
+        if ((rc = c->max_map.ensure((size_t)T * 8, true, c->stream))) return rc;
+        // 16 deposit replicas (two per XCD: a workgroup deposits into replica blockIdx % 16), at most 64 MiB in
+        // total.  Fewer than 8 serialise on the hot triangles' counters; more than ~24 push the planes out of L2 and
+        // every wave then waits for its deposits' memory round trips (profiles/r02/r02_experiments.txt: 64 replicas cost
+        // the batched step 5 %)
+        int R = c->replicas_knob > 0 ? c->replicas_knob : 16;
+        while (R > 1 && (size_t)R * (size_t)T * 4 > ((size_t)64 << 20)) R >>= 1;
+        c->replicas = R;
+        for (int l = 0; l < c->nlanes; ++l)
+            if ((rc = c->lanes[l].counts.ensure((size_t)R * (size_t)T * 4, true, c->stream))) return rc;
+        if ((rc = c->dosage.ensure((size_t)T * 4, true, c->stream))) return rc;
+        if ((rc = c->color.ensure((size_t)T * 36, true, c->stream))) return rc;
+    }
+    return UVRT_OK;
+}
+
+// the layout and the caller's arrays to the device, the two preparation kernels, and the scene's scalars once they have run
+int upload_scene(uvrt_ctx* c, const SceneLayout& L, const void* tris64, int32_t T, const uint32_t* tri_idx)
+{
+    int rc;
+    if (!L.pairs.empty())
+        HIP_TRY(hipMemcpyAsync(c->pairs.p, L.pairs.data(), L.pairs.size() * sizeof(PairRec), hipMemcpyHostToDevice, c->stream));
+    if ((rc = c->quads.ensure(std::max<size_t>(L.quads.size(), 1) * sizeof(QuadRec), false, c->stream))) return rc;
+    if (!L.quads.empty())
+        HIP_TRY(hipMemcpyAsync(c->quads.p, L.quads.data(), L.quads.size() * sizeof(QuadRec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->leaf_count.p, L.leaf_count.data(), (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
+    // staging copies of the reference-layout arrays for the device-side preparation kernel
+    DevBuf d_tris, d_idx;
+    if ((rc = d_tris.ensure((size_t)T * 64, false, c->stream))) return rc;
+    if ((rc = d_idx.ensure((size_t)T * 4, false, c->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_tris.p, tris64, (size_t)T * 64, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_idx.p, tri_idx, (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
+    launch_prepare_scene(d_tris.as<float4>(), d_idx.as<uint32_t>(), c->ltris.as<LeafTri>(),
+                         c->area.as<float>(), T, c->stream);
+    for (int l = 0; l < c->nlanes; ++l)
+        launch_prepare_leaves6(c->ltris.as<LeafTri>(), c->lanes[l].recs.p, (int32_t)L.pairs.size(), T, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->T = T;
+    c->root_ref = L.root_ref;
+    c->top_pairs = L.top_pairs;
+    c->npairs = (int32_t)L.pairs.size();
+    c->nquads = (int32_t)L.quads.size();
+    c->top_quads = L.top_quads;
+    c->scene_force_exact = L.force_exact;
+    c->have_scene = true;
+    return UVRT_OK;
+}
+
+// Whatever an earlier scene left in the context is void.  What is made on first use goes whole (uvrt_ctx::SceneDerived:
+// nothing to list); each of the rest has a reason to be handled on its own.
+int void_scene_state(uvrt_ctx* c)
+{
+    for (Lane& La : c->lanes) { La.recs_tag.valid = false; La.recs4_tag.valid = false; }   // the buffers stay, their contents are stale
+    for (Lane& La : c->lanes) La.recs4.release();     // sized per scene; rebuilt on demand (uvrt_set_wide_bvh)
+    c->have_perm = false;                             // the caller's renumbering: `perm` is reused by the next one
+    c->derived = {};
+    if (int rc = hot_reset(c, true)) return rc;       // statistics of the previous scene; the new scene's first slab
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    plan_drop(c);                                     // E is per scene
+    // a batch of the previous scene is void; its buffers are sized per scene
+    c->b_count = 0;
+    c->b_is_folded = false;
+    c->b_recs.clear();
+    c->b_recs_key.clear();
+    for (auto& bset : c->bs) for (DevBuf* b : {&bset.planes, &bset.folded}) b->release();
+    return UVRT_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -92,10 +223,7 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     c->hot.reserve(uvrt_ctx::HOT_MAX);         // entries are referred to by pointer while their set-up is pending
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (c->num_cus > 256) c->num_cus = 256;   // the overflow-stack buffer is sized for 256 CUs x 16 workgroups
-    if (const char* e = getenv("UVRT_REPLICAS")) {   // developer knob: deposit replicas of tempPhotonMap
-        const int r = atoi(e);
-        if (r >= 1 && r <= 64) c->replicas_knob = r;
-    }
+    env_int("UVRT_REPLICAS", 1, 64, c->replicas_knob);   // developer knob: deposit replicas of tempPhotonMap
     HIP_TRY(hipSetDevice(device_id));
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
@@ -105,26 +233,26 @@ int uvrt_create(int device_id, uvrt_ctx** out)
     }
     HIP_TRY(hipEventCreateWithFlags(&c->ev_fence, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_mapfence, hipEventDisableTiming));
-    if (const char* e = getenv("UVRT_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL) c->nlanes = v; }
-    if (const char* e = getenv("UVRT_PIPELINE")) c->pipeline = atoi(e) != 0;   // developer knob
-    if (const char* e = getenv("UVRT_BATCH_CHUNK_MB")) { const long v = atol(e); if (v > 0) c->batch_chunk_bytes = c->dedupe_chunk_bytes = (size_t)v << 20; }
+    env_int("UVRT_LANES", 1, uvrt_ctx::MAXL, c->nlanes);
+    env_bool("UVRT_PIPELINE", c->pipeline);   // developer knob
+    if (long mb = 0; env_int("UVRT_BATCH_CHUNK_MB", 1, LONG_MAX, mb)) c->batch_chunk_bytes = c->dedupe_chunk_bytes = (size_t)mb << 20;
 #ifdef UVRT_DEV_VARIANTS
-    if (const char* e = getenv("UVRT_PROBE_SKIP_GENERATE")) c->probe_skip_generate = atoi(e);
-    if (const char* e = getenv("UVRT_NEARFAR_MINMAX")) c->nearfar_minmax = atoi(e) != 0;   // the checker / A-B partner of the sign-ordered block
+    env_int("UVRT_PROBE_SKIP_GENERATE", INT_MIN, INT_MAX, c->probe_skip_generate);
+    env_bool("UVRT_NEARFAR_MINMAX", c->nearfar_minmax);   // the checker / A-B partner of the sign-ordered block
 #endif
-    if (const char* e = getenv("UVRT_DRAIN_MERGE")) c->drain_merge = atoi(e) != 0;      // developer knob
-    if (const char* e = getenv("UVRT_DEDUPE")) c->dedupe = atoi(e) != 0;                 // uvrt_set_dedupe's default
-    if (const char* e = getenv("UVRT_DEDUPE_CLASSES")) { const int v = atoi(e); if (v >= 0 && v <= DEDUPE_CLASS_MAX) c->dedupe_classes = v; }   // uvrt_set_dedupe_classes' default
-    if (const char* e = getenv("UVRT_DEDUPE_PERIODIC")) c->dedupe_periodic = atoi(e) != 0;   // uvrt_set_dedupe_periodic's default
-    if (const char* e = getenv("UVRT_DEDUPE_STRIP")) { const int v = atoi(e); if (v >= 1 && v <= 1024) c->dedupe_strip = v; }   // developer knob: tiles per wave of the mark pass
-    if (const char* e = getenv("UVRT_DEDUPE_CLASS_REPLICAS")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->dedupe_class_replicas = v; }
-    if (const char* e = getenv("UVRT_DEDUPE_CLASS_MB")) { const long v = atol(e); if (v > 0 && v <= 4096) c->dedupe_class_bytes = (size_t)v << 20; }
-    if (const char* e = getenv("UVRT_HELPER_PRIO")) { const int v = atoi(e); if (v >= 0 && v <= 3) c->helper_prio = v; }   // uvrt_set_helper_priority's default
-    if (const char* e = getenv("UVRT_BATCH_LANES")) { const int v = atoi(e); if (v >= 1 && v <= uvrt_ctx::MAXL - 1) c->batch_lanes = v; }
-    if (const char* e = getenv("UVRT_COMM_RESERVE_CUS")) { const int v = atoi(e); if (v >= 0 && v <= 64 && v % 8 == 0) c->comm_reserve_knob = v; }
-    if (const char* e = getenv("UVRT_HOT_SAMPLE")) { const int v = atoi(e); if (v >= 256 && v <= (1 << 20)) c->hot_sample = v; }
-    if (const char* e = getenv("UVRT_HOT_DIRECT")) { const int v = atoi(e); if (v >= 0 && v <= 8192) c->hot_direct = v; }
-    if (const char* e = getenv("UVRT_HOT_TAIL")) { const int v = atoi(e); if (v >= 0 && v < 64) c->hot_tail = v; }
+    env_bool("UVRT_DRAIN_MERGE", c->drain_merge);      // developer knob
+    env_bool("UVRT_DEDUPE", c->dedupe);                 // uvrt_set_dedupe's default
+    env_int("UVRT_DEDUPE_CLASSES", 0, DEDUPE_CLASS_MAX, c->dedupe_classes);   // uvrt_set_dedupe_classes' default
+    env_bool("UVRT_DEDUPE_PERIODIC", c->dedupe_periodic);   // uvrt_set_dedupe_periodic's default
+    env_int("UVRT_DEDUPE_STRIP", 1, 1024, c->dedupe_strip);   // developer knob: tiles per wave of the mark pass
+    env_int("UVRT_DEDUPE_CLASS_REPLICAS", 1, 16, c->dedupe_class_replicas);
+    if (long mb = 0; env_int("UVRT_DEDUPE_CLASS_MB", 1, 4096, mb)) c->dedupe_class_bytes = (size_t)mb << 20;
+    env_int("UVRT_HELPER_PRIO", 0, 3, c->helper_prio);   // uvrt_set_helper_priority's default
+    env_int("UVRT_BATCH_LANES", 1, uvrt_ctx::MAXL - 1, c->batch_lanes);
+    if (int cus = 0; env_int("UVRT_COMM_RESERVE_CUS", 0, 64, cus) && cus % 8 == 0) c->comm_reserve_knob = cus;
+    env_int("UVRT_HOT_SAMPLE", 256, 1 << 20, c->hot_sample);
+    env_int("UVRT_HOT_DIRECT", 0, 8192, c->hot_direct);
+    env_int("UVRT_HOT_TAIL", 0, 63, c->hot_tail);
     if (int rc = c->error_flag.ensure(256, true, c->stream)) return rc;      // (a developer build keeps trip statistics behind the flag)
 #ifndef UVRT_TRIP_STATS
     // the stack-overflow flag lives in pinned host memory the kernels can write: uvrt_sync reads it after the stream sync
@@ -168,225 +296,17 @@ int uvrt_set_stream(uvrt_ctx* c, void* hip_stream)
 int uvrt_set_scene(uvrt_ctx* c, const void* tris64, int32_t T, const void* nodes32,
                    int32_t node_count, const uint32_t* tri_idx)
 {
-    if (!c || !tris64 || !nodes32 || !tri_idx) return fail(UVRT_ERR_INVALID, "uvrt_set_scene: null argument");
-    if (T <= 0 || T > MAX_TRIS || node_count <= 0)
-        return fail(UVRT_ERR_INVALID, "uvrt_set_scene: tri_count %d / node_count %d out of range", T, node_count);
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_set_scene: null argument");
+    SceneLayout L;
+    std::string why;
+    if (int rc = sl::build_scene_layout(tris64, T, nodes32, node_count, tri_idx, L, why)) return fail(rc, "%s", why.c_str());
     if (int rc = set_device(c)) return rc;
-
-    struct HostNode { float mn[3]; int32_t leftFirst; float mx[3]; int32_t triCount; };
-    static_assert(sizeof(HostNode) == 32, "BVHNode is 32 bytes (bvh.h:11-21)");
-    const HostNode* nodes = (const HostNode*)nodes32;
-
-    for (int32_t i = 0; i < T; ++i)
-        if (tri_idx[i] >= (uint32_t)T)
-            return fail(UVRT_ERR_BVH, "uvrt_set_scene: triIdx[%d] = %u >= tri_count %d", i, tri_idx[i], T);
-    // vertex coordinates beyond 1e9 (or non-finite): the shortcuts' range proofs do not cover them
-    bool huge_vertex = false;
-    {
-        const float* tv = (const float*)tris64;
-        for (int64_t i = 0; i < (int64_t)T && !huge_vertex; ++i)
-            for (int k = 0; k < 12; ++k)
-                if ((k & 3) != 3 && !(std::fabs(tv[i * 16 + k]) <= 1e9f)) { huge_vertex = true; break; }
-    }
-
-    // Re-layout: walk the tree breadth-first from node 0; every inner node becomes one pair
-    // record (numbered in visit order, so the top of the tree is contiguous at the front).
-    auto leaf_ref = [&](const HostNode& n, std::vector<uint32_t>& leaf_count, int& err) -> uint32_t {
-        int64_t first = n.leftFirst, cnt = n.triCount;
-        if (first < 0 || first + cnt > T) { err = 1; return REF_DONE; }
-        leaf_count[first] = (uint32_t)cnt;
-        uint32_t code = cnt >= 15 ? 15u : (uint32_t)cnt;
-        return REF_LEAF_BIT | (code << REF_COUNT_SHIFT) | (uint32_t)first;
-    };
-    std::vector<uint32_t> leaf_count(T, 0u);
-    std::vector<PairRec> pairs;
-    std::vector<int32_t> queue;   // inner nodes in BFS order; index in queue == pair index
-    std::vector<int32_t> depth;   // tree depth of queue[i]
-    uint32_t top_pairs = 0;
-    int err = 0;
-    bool tiny_bound = false;
-    uint32_t root_ref;
-    if (nodes[0].triCount > 0) {
-        root_ref = leaf_ref(nodes[0], leaf_count, err);
-    } else {
-        root_ref = 0;
-        queue.push_back(0);
-        depth.push_back(0);
-    }
-    for (size_t qi = 0; qi < queue.size() && !err; ++qi) {
-        const HostNode& n = nodes[queue[qi]];
-        const int64_t l = n.leftFirst;
-        if (l < 0 || l + 1 >= node_count) { err = 2; break; }
-        if (queue.size() > (size_t)node_count) { err = 3; break; }   // cycle
-        uint32_t ref[2];
-        for (int k = 0; k < 2; ++k) {
-            const HostNode& ch = nodes[l + k];
-            if (ch.triCount > 0) ref[k] = leaf_ref(ch, leaf_count, err);
-            else { ref[k] = (uint32_t)queue.size(); queue.push_back((int32_t)(l + k)); depth.push_back(depth[qi] + 1); }
-        }
-        const HostNode& a = nodes[l];
-        const HostNode& b = nodes[l + 1];
-        for (const HostNode* hn : {&a, &b})
-            for (int k = 0; k < 3; ++k)
-                for (float v : {hn->mn[k], hn->mx[k]})
-                    if ((v != 0.0f && std::fabs(v) < 8.6736174e-19f) || !(std::fabs(v) <= 1e9f))
-                        tiny_bound = true;   // below 2^-60, above 1e9, inf or NaN
-        PairRec pr;
-        pr.c0min_ref0 = make_float4(a.mn[0], a.mn[1], a.mn[2], 0.f);
-        pr.c0max_ref1 = make_float4(a.mx[0], a.mx[1], a.mx[2], 0.f);
-        memcpy(&pr.c0min_ref0.w, &ref[0], 4);
-        memcpy(&pr.c0max_ref1.w, &ref[1], 4);
-        pr.c1min = make_float4(b.mn[0], b.mn[1], b.mn[2], 0.f);
-        pr.c1max = make_float4(b.mx[0], b.mx[1], b.mx[2], 0.f);
-        pairs.push_back(pr);
-        if (depth[qi] < 8 && top_pairs < TOP6_MAX) top_pairs = (uint32_t)qi + 1;   // level order: a prefix
-    }
-    if (err) return fail(UVRT_ERR_BVH, "uvrt_set_scene: malformed BVH (code %d)", err);
-    // The 4-wide collapse (one level): a node takes the children of its inner children.  Numbered breadth-first
-    // like the pairs; a child reference is a 64-byte unit index (2 x node index) or the BVH2 leaf reference.
-    std::vector<QuadRec> quads;
-    uint32_t top_quads = 0;
-    if (!pairs.empty()) {
-        std::vector<int32_t> qpair{0};        // pair index (of the BVH2 inner node) of every 4-wide node
-        std::vector<int32_t> qdepth{0};
-        const float far_box = 1e30f;          // an empty slot: a box no ray reaches (entry distance >= 1e30)
-        for (size_t qi = 0; qi < qpair.size(); ++qi) {
-            struct Child { float mn[3], mx[3]; uint32_t ref; };
-            Child ch[4];
-            int nch = 0;
-            auto add = [&](const float4& mn, const float4& mx, uint32_t ref) {
-                Child& c4 = ch[nch++];
-                c4.mn[0] = mn.x; c4.mn[1] = mn.y; c4.mn[2] = mn.z;
-                c4.mx[0] = mx.x; c4.mx[1] = mx.y; c4.mx[2] = mx.z;
-                c4.ref = ref;
-            };
-            auto children_of = [&](const PairRec& pr, float4 mn[2], float4 mx[2], uint32_t ref[2]) {
-                mn[0] = pr.c0min_ref0; mx[0] = pr.c0max_ref1; mn[1] = pr.c1min; mx[1] = pr.c1max;
-                memcpy(&ref[0], &pr.c0min_ref0.w, 4);
-                memcpy(&ref[1], &pr.c0max_ref1.w, 4);
-            };
-            float4 mn[2], mx[2];
-            uint32_t ref[2];
-            children_of(pairs[qpair[qi]], mn, mx, ref);
-            for (int k = 0; k < 2; ++k) {
-                if (ref[k] >= REF_LEAF_BIT) { add(mn[k], mx[k], ref[k]); continue; }
-                float4 gmn[2], gmx[2];
-                uint32_t gref[2];
-                children_of(pairs[ref[k]], gmn, gmx, gref);
-                for (int j = 0; j < 2; ++j) add(gmn[j], gmx[j], gref[j]);
-            }
-            QuadRec q;
-            memset(&q, 0, sizeof q);
-            float y[4][2];
-            for (int k = 0; k < 4; ++k) {
-                if (k < nch) {
-                    uint32_t r = ch[k].ref;
-                    if (r < REF_LEAF_BIT) {           // inner: it becomes a 4-wide node of its own
-                        qpair.push_back((int32_t)r);
-                        qdepth.push_back(qdepth[qi] + 1);
-                        r = 2u * (uint32_t)(qpair.size() - 1);
-                    }
-                    q.xz[k] = make_float4(ch[k].mn[0], ch[k].mx[0], ch[k].mn[2], ch[k].mx[2]);
-                    y[k][0] = ch[k].mn[1]; y[k][1] = ch[k].mx[1];
-                    q.ref[k] = r;
-                } else {
-                    q.xz[k] = make_float4(far_box, far_box, far_box, far_box);
-                    y[k][0] = y[k][1] = far_box;
-                    q.ref[k] = REF_DONE;
-                }
-            }
-            q.y01 = make_float4(y[0][0], y[0][1], y[1][0], y[1][1]);
-            q.y23 = make_float4(y[2][0], y[2][1], y[3][0], y[3][1]);
-            quads.push_back(q);
-            if (qdepth[qi] < 4 && top_quads < 64) top_quads = (uint32_t)qi + 1;     // levels 0-3: up to 85 nodes, 64 cached
-        }
-    }
-    // a child reference is a record index with 32-bit byte offsets: inner-node records + leaf records < 2^26
-    if (pairs.size() + (size_t)T >= ((size_t)1 << 26))
-        return fail(UVRT_ERR_INVALID, "uvrt_set_scene: %zu inner nodes + %d triangles exceed 2^26 records", pairs.size(), T);
-
     if (int rcj = join_all(c)) return rcj;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->lane = 0;
-    const bool resized = (T != c->T);
-    int rc;
-    if ((rc = c->pairs.ensure(std::max<size_t>(pairs.size(), 1) * sizeof(PairRec), false, c->stream))) return rc;
-    for (int l = 0; l < c->nlanes; ++l)
-        if ((rc = c->lanes[l].recs.ensure((pairs.size() + (size_t)T + 1) * 64, true, c->stream))) return rc;
-    // + 16 bytes: the merged record fetch of the traversal reads 64 bytes at every leaf record
-    if ((rc = c->ltris.ensure((size_t)T * sizeof(LeafTri) + 16, true, c->stream))) return rc;
-    if ((rc = c->leaf_count.ensure((size_t)T * 4, false, c->stream))) return rc;
-    if ((rc = c->area.ensure((size_t)T * 4, false, c->stream))) return rc;
-    if (resized || !c->photon_map.p) {
-        // raytracer.cpp:32-37 (the reference leaves them uninitialised until reset; zero here)
-        // The colour buffer stands for the GL vertex buffer of the caller's mesh (raytracer.cpp:37): a scene swap
-        // does not touch it.  It only grows, so CalibratePower's detour over a 2-triangle scene
-        // (raytracer.cpp:166-224, ClearBuffers(false)) leaves the room's colours as they were.
-        for (DevBuf* b : {&c->photon_map, &c->max_map, &c->dosage}) b->release();
-        for (Lane& L : c->lanes) L.counts.release();
-        if ((rc = c->photon_map.ensure((size_t)T * 8, true, c->stream))) return rc;
-        if ((rc = c->max_map.ensure((size_t)T * 8, true, c->stream))) return rc;
-        // 16 deposit replicas (two per XCD: a workgroup deposits into replica blockIdx % 16), at most 64 MiB in
-        // total.  Fewer than 8 serialise on the hot triangles' counters; more than ~24 push the planes out of L2 and
-        // every wave then waits for its deposits' memory round trips (profiles/r02/r02_experiments.txt: 64 replicas cost
-        // the batched step 5 %)
-        int R = c->replicas_knob > 0 ? c->replicas_knob : 16;
-        while (R > 1 && (size_t)R * (size_t)T * 4 > ((size_t)64 << 20)) R >>= 1;
-        c->replicas = R;
-        for (int l = 0; l < c->nlanes; ++l)
-            if ((rc = c->lanes[l].counts.ensure((size_t)R * (size_t)T * 4, true, c->stream))) return rc;
-        if ((rc = c->dosage.ensure((size_t)T * 4, true, c->stream))) return rc;
-        if ((rc = c->color.ensure((size_t)T * 36, true, c->stream))) return rc;
-    }
-    if (!pairs.empty())
-        HIP_TRY(hipMemcpyAsync(c->pairs.p, pairs.data(), pairs.size() * sizeof(PairRec), hipMemcpyHostToDevice, c->stream));
-    if ((rc = c->quads.ensure(std::max<size_t>(quads.size(), 1) * sizeof(QuadRec), false, c->stream))) return rc;
-    if (!quads.empty())
-        HIP_TRY(hipMemcpyAsync(c->quads.p, quads.data(), quads.size() * sizeof(QuadRec), hipMemcpyHostToDevice, c->stream));
-    for (Lane& L : c->lanes) L.recs4.release();          // sized per scene; rebuilt on demand (uvrt_set_wide_bvh)
-    HIP_TRY(hipMemcpyAsync(c->leaf_count.p, leaf_count.data(), (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
-    // staging copies of the reference-layout arrays for the device-side preparation kernel
-    {
-        DevBuf d_tris, d_idx;
-        if ((rc = d_tris.ensure((size_t)T * 64, false, c->stream))) return rc;
-        if ((rc = d_idx.ensure((size_t)T * 4, false, c->stream))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_tris.p, tris64, (size_t)T * 64, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_idx.p, tri_idx, (size_t)T * 4, hipMemcpyHostToDevice, c->stream));
-        launch_prepare_scene(d_tris.as<float4>(), d_idx.as<uint32_t>(), c->ltris.as<LeafTri>(),
-                             c->area.as<float>(), T, c->stream);
-        for (int l = 0; l < c->nlanes; ++l)
-            launch_prepare_leaves6(c->ltris.as<LeafTri>(), c->lanes[l].recs.p, (int32_t)pairs.size(), T, c->stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    c->T = T;
-    c->root_ref = root_ref;
-    c->top_pairs = top_pairs;
-    c->npairs = (int32_t)pairs.size();
-    c->nquads = (int32_t)quads.size();
-    c->top_quads = top_quads;
-    for (Lane& L : c->lanes) { L.recs_tag.valid = false; L.recs4_tag.valid = false; }
-    c->have_perm = false;
-    c->have_scene = true;
-    c->free_recs.release();                           // sized per scene; rebuilt by the next free launch
-    c->free_recs_valid = false;
-    c->g_tris.release();                              // the gather's triangles and its plane: per scene, back (zeroed) on next use
-    c->g_tris_valid = false;
-    c->expected.release();
-    c->variance.release();
-    c->g_extra.release();
-    c->gather_memo = {};                              // a refine works on one scene's planes
-    c->scene_force_exact = tiny_bound || huge_vertex;
-    if ((rc = hot_reset(c, true))) return rc;         // statistics of the previous scene; the new scene's first slab
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    plan_drop(c);                                     // E is per scene
-    // a batch of the previous scene is void; its buffers are sized per scene
-    c->b_count = 0;
-    c->b_is_folded = false;
-    c->b_recs.clear();
-    c->b_recs_key.clear();
-    for (auto& bset : c->bs) for (DevBuf* b : {&bset.planes, &bset.folded}) b->release();
-    return UVRT_OK;
+    if (int rc = provision_scene(c, L, T)) return rc;
+    if (int rc = upload_scene(c, L, tris64, T, tri_idx)) return rc;
+    return void_scene_state(c);
 }
 
 int uvrt_resize_rays(uvrt_ctx* c, int64_t photon_count)
@@ -754,11 +674,11 @@ int uvrt_device_ptr(uvrt_ctx* c, int32_t which, void** ptr, int64_t* bytes)
             break;
         case 6:
             if (int rc = ensure_expected(c)) return rc;
-            b = &c->expected; elem = 8;
+            b = &c->derived.expected; elem = 8;
             break;
         case 7:
             if (int rc = ensure_variance(c)) return rc;
-            b = &c->variance; elem = 8;
+            b = &c->derived.variance; elem = 8;
             break;
         default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..7");
     }

@@ -95,7 +95,7 @@ static int provision_batch(BatchRun& r, int count)
         dd_scratch_short = dd_scratch_short || c->lanes[l].dd_tmp.bytes < P.dd_tmp_bytes || c->lanes[l].dd_blocks.bytes < P.dd_block_bytes;
     const bool need_alloc = S.rays.bytes < (size_t)count * (size_t)n_pad * 16 || S.planes.bytes < planes_bytes ||
                             S.folded.bytes < (size_t)count * (size_t)c->T * 4 || (int)c->b_recs.size() < P.ngroups || !S.free_ev ||
-                            S.oxz.bytes < (size_t)P.nsweeps * (size_t)n_pad * 8 || (P.nsweeps > 0 && !c->free_recs_valid) ||
+                            S.oxz.bytes < (size_t)P.nsweeps * (size_t)n_pad * 8 || (P.nsweeps > 0 && !c->derived.free_recs_valid) ||
                             (P.dd_chunks > 0 && (S.masks.bytes < (size_t)count * (size_t)n_pad * 4 || S.dd_counts.bytes < P.dd_chunks * 8 ||
                                                  dd_scratch_short));
     bool recs_stale = false;
@@ -144,7 +144,7 @@ static int provision_batch(BatchRun& r, int count)
             key = {{true, P.gx[g], P.gz[g]}, r.gperm[g], r.ggen[g]};
         }
         // the scene's free records, on first use (the lanes are joined above, the fence below covers them)
-        if (P.nsweeps > 0 && !c->free_recs_valid)
+        if (P.nsweeps > 0 && !c->derived.free_recs_valid)
             if ((rc = make_free_records(c))) return rc;
         HIP_TRY(hipGetLastError());
         if (int rcf = mark_fence(c)) return rcf;         // the lanes' next work waits for the records
@@ -313,7 +313,7 @@ static int enqueue_sweep_chunk(BatchRun& r, int k0, int kc)
     fp.e.rays = sq.rays;
     fp.oxz = sq.oxz;
     set_planes(r, fp.e, ph0, kc);
-    fp.e.recs = c->free_recs.p;
+    fp.e.recs = c->derived.free_recs.p;
     return timed_launch(c, ls, r.who, "the free-ray launch", [&] { return launch_extend_free_planes(fp, r.per_cu, ls); });
 }
 

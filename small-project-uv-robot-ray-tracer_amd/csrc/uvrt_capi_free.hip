@@ -11,15 +11,15 @@ namespace uvrt_impl {
 // callers that never trace such rays do not pay for them.
 int make_free_records(uvrt_ctx* c)
 {
-    if (int rc = c->free_recs.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream)) return rc;
-    launch_prepare_free_records(c->pairs.as<PairRec>(), c->ltris.as<LeafTri>(), c->free_recs.p, c->npairs, c->T, c->stream);
-    c->free_recs_valid = true;
+    if (int rc = c->derived.free_recs.ensure(((size_t)c->npairs + (size_t)c->T + 1) * 64, true, c->stream)) return rc;
+    launch_prepare_free_records(c->pairs.as<PairRec>(), c->ltris.as<LeafTri>(), c->derived.free_recs.p, c->npairs, c->T, c->stream);
+    c->derived.free_recs_valid = true;
     return UVRT_OK;
 }
 
 int ensure_free_records(uvrt_ctx* c)
 {
-    if (c->free_recs_valid) return UVRT_OK;
+    if (c->derived.free_recs_valid) return UVRT_OK;
     // on the context's stream, behind everything outstanding; the lanes' later work waits for it (mark_fence)
     if (int rc = join_all(c)) return rc;
     if (int rc = make_free_records(c)) return rc;
@@ -44,7 +44,7 @@ int extend_free(uvrt_ctx* c, int64_t n)
         if (int rc = c->hits.ensure((size_t)c->capacity * 8, false, c->stream)) return rc;
     }
     Lane& L = cur_lane(c);
-    if (!L.oxz.p || !c->free_recs_valid) return fail(UVRT_ERR_INVALID, "uvrt_extend: the free rays are gone (uvrt_set_scene / uvrt_resize_rays since)");
+    if (!L.oxz.p || !c->derived.free_recs_valid) return fail(UVRT_ERR_INVALID, "uvrt_extend: the free rays are gone (uvrt_set_scene / uvrt_resize_rays since)");
     FreeParams fp;
     fill_launch(c, fp.e, 0.0f, 0.0f);       // (force_exact: the scene's and the variant's conditions; the origins are per ray)
     hipStream_t ls;
@@ -56,7 +56,7 @@ int extend_free(uvrt_ctx* c, int64_t n)
     fp.e.count_replicas = c->replicas;
     fp.e.count_stride = c->T;
     fp.e.n = n;
-    fp.e.recs = c->free_recs.p;
+    fp.e.recs = c->derived.free_recs.p;
     // the grid knob of uvrt_set_variant applies; the leaf period / cache code does not (one kernel)
     const int per_cu_default = (c->cur_pipelined && c->nlanes >= 4) ? 4 : c->cur_pipelined ? 7 : 8;
     if (int rc = timed_launch(c, ls, "uvrt_extend", "the free-ray launch",

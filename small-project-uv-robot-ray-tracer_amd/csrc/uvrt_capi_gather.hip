@@ -11,22 +11,22 @@ namespace uvrt_impl {
 
 int ensure_expected(uvrt_ctx* c)
 {
-    return c->expected.ensure((size_t)c->T * 8, true, c->stream);      // (nothing to do once it is there)
+    return c->derived.expected.ensure((size_t)c->T * 8, true, c->stream);      // (nothing to do once it is there)
 }
 
 int ensure_variance(uvrt_ctx* c)
 {
-    return c->variance.ensure((size_t)c->T * 8, true, c->stream);
+    return c->derived.variance.ensure((size_t)c->T * 8, true, c->stream);
 }
 
 // the gather's per-triangle records {v0, e1, e2} in tris64 order, made from the scene's leaf triangles on first use
 static int ensure_gather_tris(uvrt_ctx* c)
 {
-    if (c->g_tris_valid) return UVRT_OK;
-    if (int rc = c->g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
-    launch_gather_tris(c->ltris.as<LeafTri>(), c->g_tris.as<float4>(), c->T, c->stream);
+    if (c->derived.g_tris_valid) return UVRT_OK;
+    if (int rc = c->derived.g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
+    launch_gather_tris(c->ltris.as<LeafTri>(), c->derived.g_tris.as<float4>(), c->T, c->stream);
     HIP_TRY(hipGetLastError());
-    c->g_tris_valid = true;
+    c->derived.g_tris_valid = true;
     return UVRT_OK;
 }
 
@@ -49,7 +49,7 @@ static int check_refine_params(uvrt_ctx* c, const uvrt_refine_params* prm, const
 // the refine's n_t plane, offsets and block sums, sized for the scene
 static int ensure_refine_buffers(uvrt_ctx* c)
 {
-    if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
+    if (int rc = c->derived.g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
     if (int rc = c->g_offs.ensure(((size_t)c->T + 1) * 4, false, c->stream)) return rc;
     return c->g_scan.ensure(((size_t)c->T / 1024 + 1) * 4, false, c->stream);
 }
@@ -84,7 +84,7 @@ static int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who)
     op.tmax = c->g_tmax.as<float>();
     op.occluded = c->g_occ.as<uint8_t>();
     op.e.n = n;
-    op.e.recs = c->free_recs.p;
+    op.e.recs = c->derived.free_recs.p;
     return timed_launch(c, c->stream, who, "the shadow-ray launch",
                         [&] { return launch_occlude_free(op, variant_per_cu(c->variant, 8), c->stream); });
 }
@@ -165,7 +165,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: %d triangles x %d samples do not fit 2^31 sample numbers", c->T, S);
     if (prm->photons_equiv <= 0) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: photons_equiv must be > 0");
     if (int rc = set_device(c)) return rc;
-    c->gather_memo = {};                    // remembered again below, when this call has written both planes
+    c->derived.gather_memo = {};                    // remembered again below, when this call has written both planes
     if (int rc = begin_shadow_launch(c)) return rc;
     const size_t cap = (size_t)c->capacity;
     if (int rc = c->g_w.ensure(cap * 8, false, c->stream)) return rc;
@@ -176,7 +176,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     Lane& L = c->lanes[0];
     GatherGenParams g;
     memset(&g, 0, sizeof g);
-    g.gtris = c->g_tris.as<float4>();
+    g.gtris = c->derived.g_tris.as<float4>();
     g.rays = L.rays.as<float4>();
     g.oxz = c->g_oxz.as<float2>();
     g.tmax = c->g_tmax.as<float>();
@@ -198,10 +198,10 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         HIP_TRY(hipGetLastError());
         if (int rc = trace_shadow_rays(c, (int64_t)cnt * S, "uvrt_gather_direct")) return rc;
         if (var)
-            launch_gather_reduce_var(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->expected.as<double>(), c->variance.as<double>(),
+            launch_gather_reduce_var(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->derived.expected.as<double>(), c->derived.variance.as<double>(),
                                      g.first_tri, cnt, S, prm->photons_equiv, g.mode, c->stream);
         else
-            launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->expected.as<double>(), g.first_tri, cnt, S,
+            launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->derived.expected.as<double>(), g.first_tri, cnt, S,
                                  prm->photons_equiv, c->stream);
         HIP_TRY(hipGetLastError());
     }
@@ -213,7 +213,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         memcpy(m.from, prm->from, 12);
         memcpy(m.to, prm->to, 12);
         m.light_length = prm->light_length;
-        c->gather_memo = m;
+        c->derived.gather_memo = m;
     }
     return UVRT_OK;
 }
@@ -225,13 +225,13 @@ int uvrt_accumulate_expected(uvrt_ctx* c, float time_step, int32_t tri_count)
     if (int rc = set_device(c)) return rc;       // (an accumulate that uvrt_accumulate has deferred goes first: launch order)
     if (int rc = join_all(c)) return rc;
     if (int rc = ensure_expected(c)) return rc;
-    c->gather_memo = {};                         // the estimate is consumed: nothing left to refine
+    c->derived.gather_memo = {};                         // the estimate is consumed: nothing left to refine
     c->ext_touch_maps = false;                   // (on the context's stream, behind the caller's work: the fence below covers it)
-    launch_accumulate_expected(c->photon_map.as<double>(), c->max_map.as<double>(), c->expected.as<double>(), time_step,
+    launch_accumulate_expected(c->photon_map.as<double>(), c->max_map.as<double>(), c->derived.expected.as<double>(), time_step,
                                tri_count, c->stream);
     HIP_TRY(hipGetLastError());
     // the variance of the estimate that has just been consumed goes with it: a stale one is never paired with a later estimate
-    if (c->variance.p && tri_count > 0) HIP_TRY(hipMemsetAsync(c->variance.p, 0, (size_t)tri_count * 8, c->stream));
+    if (c->derived.variance.p && tri_count > 0) HIP_TRY(hipMemsetAsync(c->derived.variance.p, 0, (size_t)tri_count * 8, c->stream));
     return mark_map_fence(c);                    // later accumulate / Shade work on a side lane waits for it
 }
 
@@ -245,8 +245,8 @@ static int plane_range(uvrt_ctx* c, const char* who, bool variance, void* host, 
         return fail(UVRT_ERR_INVALID, "%s: range [%d,+%d) outside [0,%d)", who, first, count, c->T);
     if (int rc = set_device(c)) return rc;
     if (int rc = variance ? ensure_variance(c) : ensure_expected(c)) return rc;
-    if (kind == hipMemcpyHostToDevice) c->gather_memo = {};     // the planes are the caller's now, not the remembered gather's
-    return range_copy(c, variance ? c->variance.p : c->expected.p, 8, host, first, count, kind);
+    if (kind == hipMemcpyHostToDevice) c->derived.gather_memo = {};     // the planes are the caller's now, not the remembered gather's
+    return range_copy(c, variance ? c->derived.variance.p : c->derived.expected.p, 8, host, first, count, kind);
 }
 
 int uvrt_read_expected(uvrt_ctx* c, double* out, int32_t first, int32_t count)
@@ -275,7 +275,7 @@ int uvrt_gather_refine(uvrt_ctx* c, const uvrt_refine_params* prm, int32_t first
     if (!c->have_scene) return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: no scene");
     if (c->flavour != 0 && c->flavour != 1)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: shadow rays are traced in flavours 0 and 1 only (uvrt_set_flavour %d)", c->flavour);
-    const uvrt_ctx::GatherMemo m = c->gather_memo;
+    const uvrt_ctx::GatherMemo m = c->derived.gather_memo;
     if (!m.valid)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_refine: no remembered gather (uvrt_gather_direct with uvrt_set_gather_variance(1), not yet refined or consumed)");
     if (first_tri < m.first || tri_count < 0 || (int64_t)first_tri + tri_count > (int64_t)m.first + m.count)
@@ -294,16 +294,16 @@ int uvrt_gather_refine(uvrt_ctx* c, const uvrt_refine_params* prm, int32_t first
     if (int rc = ensure_refine_buffers(c)) return rc;
     if (report) *report = {};
     // (the remembered gather made g_tris and both planes, and whatever releases them -- uvrt_set_scene -- forgets it)
-    const float4* gtris = c->g_tris.as<float4>();
+    const float4* gtris = c->derived.g_tris.as<float4>();
     int32_t* offs = c->g_offs.as<int32_t>();
-    launch_refine_count(gtris, c->expected.as<double>(), c->variance.as<double>(), c->g_extra.as<int32_t>(), c->T, first_tri,
+    launch_refine_count(gtris, c->derived.expected.as<double>(), c->derived.variance.as<double>(), c->derived.g_extra.as<int32_t>(), c->T, first_tri,
                         tri_count, m.samples, prm->rel_error, prm->min_expected, M, c->stream);
-    launch_refine_scan(c->g_extra.as<int32_t>(), offs, c->g_scan.as<int32_t>(), first_tri, tri_count, c->stream);
+    launch_refine_scan(c->derived.g_extra.as<int32_t>(), offs, c->g_scan.as<int32_t>(), first_tri, tri_count, c->stream);
     HIP_TRY(hipGetLastError());
     // the call's one round trip: the offsets, to cut the range into chunks of at most `capacity` rays
     std::vector<int32_t> h((size_t)tri_count + 1);
     if (int rc = copy_sync(c, h.data(), offs, h.size() * 4, hipMemcpyDeviceToHost)) return rc;
-    c->gather_memo = {};                    // one refine per gather
+    c->derived.gather_memo = {};                    // one refine per gather
     Lane& L = c->lanes[0];
     GatherGenParams g;
     memset(&g, 0, sizeof g);
@@ -332,7 +332,7 @@ int uvrt_gather_refine(uvrt_ctx* c, const uvrt_refine_params* prm, int32_t first
             launch_refine_generate(g, offs, lo, hi, rays, c->stream);
             HIP_TRY(hipGetLastError());
             if (int rc = trace_shadow_rays(c, rays, "uvrt_gather_refine")) return rc;
-            launch_refine_reduce(gtris, g.w, c->g_occ.as<uint8_t>(), offs, c->expected.as<double>(), c->variance.as<double>(),
+            launch_refine_reduce(gtris, g.w, c->g_occ.as<uint8_t>(), offs, c->derived.expected.as<double>(), c->derived.variance.as<double>(),
                                  first_tri, lo, hi, m.samples, m.photons_equiv, m.mode, c->stream);
             HIP_TRY(hipGetLastError());
         }
@@ -349,8 +349,8 @@ int uvrt_read_gather_extra(uvrt_ctx* c, int32_t* out, int32_t first, int32_t cou
     if (!range_ok(out, first, count, c->T))
         return fail(UVRT_ERR_INVALID, "uvrt_read_gather_extra: range [%d,+%d) outside [0,%d)", first, count, c->T);
     if (int rc = set_device(c)) return rc;
-    if (int rc = c->g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
-    return range_copy(c, c->g_extra.p, 4, out, first, count, hipMemcpyDeviceToHost);
+    if (int rc = c->derived.g_extra.ensure((size_t)c->T * 4, true, c->stream)) return rc;
+    return range_copy(c, c->derived.g_extra.p, 4, out, first, count, hipMemcpyDeviceToHost);
 }
 
 int uvrt_refine_counts(uvrt_ctx* c, int32_t samples0, const uvrt_refine_params* prm, int32_t first_tri, int32_t tri_count,
@@ -372,9 +372,9 @@ int uvrt_refine_counts(uvrt_ctx* c, int32_t samples0, const uvrt_refine_params* 
     if (int rc = ensure_gather_tris(c)) return rc;
     if (int rc = ensure_refine_buffers(c)) return rc;
     // the two launches of uvrt_gather_refine, on the planes as they are
-    launch_refine_count(c->g_tris.as<float4>(), c->expected.as<double>(), c->variance.as<double>(), c->g_extra.as<int32_t>(), c->T,
+    launch_refine_count(c->derived.g_tris.as<float4>(), c->derived.expected.as<double>(), c->derived.variance.as<double>(), c->derived.g_extra.as<int32_t>(), c->T,
                         first_tri, tri_count, samples0, prm->rel_error, prm->min_expected, prm->max_extra, c->stream);
-    launch_refine_scan(c->g_extra.as<int32_t>(), c->g_offs.as<int32_t>(), c->g_scan.as<int32_t>(), first_tri, tri_count, c->stream);
+    launch_refine_scan(c->derived.g_extra.as<int32_t>(), c->g_offs.as<int32_t>(), c->g_scan.as<int32_t>(), first_tri, tri_count, c->stream);
     HIP_TRY(hipGetLastError());
     return copy_sync(c, offsets_out, c->g_offs.p, ((size_t)tri_count + 1) * 4, hipMemcpyDeviceToHost);
 }

@@ -1,5 +1,6 @@
 // uvrt_ctx.h -- the context behind the C ABI of include/uvrt.h, shared by the translation units that implement it:
-//   uvrt_capi.hip         context, scene, buffers, knobs, read-backs and test hooks
+//   uvrt_capi.hip         context, scene, buffers, knobs, read-backs and test hooks; the scene is provisioned and uploaded from
+//   uvrt_scene_layout.h   the host-only re-layout of a scene (build_scene_layout): no HIP, testable alone
 //   uvrt_capi_launch.hip  the per-launch entry points (generate, extend, accumulate, shade) and the launch lanes
 //   uvrt_capi_batch.hip   batched tracing (uvrt_trace_batch / uvrt_trace_batch_launches / fold / replay): provisioning, the
 //                         chunk emitters and the commit, over the plan of
@@ -15,8 +16,11 @@
 //
 // Who owns what.  A DevBuf owns its allocation, a Lane its side stream and tail event, a BatchSet its free event, the
 // context the rest (~uvrt_ctx).  A member added to one of these structs is released with it: there is no list to extend.
-// Buffers are named for release only where a SUBSET is dropped on purpose: per scene (uvrt_set_scene, hot_reset), per
-// capacity (uvrt_resize_rays).
+// Buffers are named for release only where a SUBSET is dropped on purpose, per capacity (uvrt_resize_rays) or per scene.
+// Per scene (uvrt_capi.hip void_scene_state): what is derived from the scene and made on first use lives in
+// uvrt_ctx::SceneDerived and is dropped whole, so a member added there is voided with it; named beside it are only the few
+// that need handling of their own -- the lanes' record tags and recs4, the caller's renumbering, the hot entries
+// (hot_reset), the plan (plan_drop) and the traced batch.
 // Destruction order.  No destructor waits for a stream, so nothing may be deleted while a stream can still run work that
 // reads it: uvrt_destroy makes the device current, waits for the context's stream, the side streams and the probe's,
 // destroys the communicator (which puts the lanes' plain streams back) and only then deletes the context.  plan_drop waits
@@ -53,6 +57,11 @@ struct DevBuf {
     size_t bytes = 0;
     DevBuf() = default;
     DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
     ~DevBuf() { release(); }
     // Zeroing is enqueued on `s`, the stream every kernel of the context runs on (the
     // context's stream is non-blocking, so a null-stream hipMemset would not be ordered
@@ -120,7 +129,7 @@ struct uvrt_ctx {
     uint64_t perm_gen = 0;       // stamp of what `perm` holds
     int32_t npairs = 0;
     uint32_t root_ref = uvrt::REF_DONE;
-    uint32_t top_pairs = 0;      // inner nodes of the first 7 tree levels (breadth-first prefix of `pairs`)
+    uint32_t top_pairs = 0;      // inner nodes at tree depths 0..7, the first eight levels, TOP6_MAX at most (breadth-first prefix of `pairs`)
     bool have_scene = false;
     int32_t replicas = 1;        // deposit replicas of tempPhotonMap (uvrt_device.h ExtendParams)
     int32_t replicas_knob = -1;  // -1: choose from T
@@ -139,15 +148,12 @@ struct uvrt_ctx {
     // origins of their own, uvrt_capi_free.hip).  Assigned whole.
     struct LastRays { int64_t n = -1, first = 0; bool sorted = false, extended = false, free_rays = false; } last;
     float ox = 0, oz = 0;
-    DevBuf free_recs;                          // the free-origin kernel's records, [npairs + T + 1] x 64 B: made on first use
-    bool free_recs_valid = false;              // ... for the current scene
-    // shadow rays and the direct gather (uvrt_capi_gather.hip): every ray's {orig.x, orig.z}, tmax and answer, the samples'
-    // weights, the triangles by original id, the expected plane f64[T] and the variance plane f64[T] beside it; all made on
-    // first use.  (The rays themselves go through lane 0's ray buffer, on the context's stream.)
-    DevBuf g_oxz, g_tmax, g_occ, g_w, g_tris, expected, variance;
-    // uvrt_gather_refine (include/uvrt.h "adaptive gather"): n_t of the last refine, int32[T] (made zeroed on first use, per
-    // scene); the exclusive prefix sums of a refined range, int32[T + 1], and the scan's per-block totals
-    DevBuf g_extra, g_offs, g_scan;
+    // shadow rays and the direct gather (uvrt_capi_gather.hip): every ray's {orig.x, orig.z}, tmax and answer and the samples'
+    // weights, made on first use.  (The rays themselves go through lane 0's ray buffer, on the context's stream.)
+    DevBuf g_oxz, g_tmax, g_occ, g_w;
+    // uvrt_gather_refine (include/uvrt.h "adaptive gather"): the exclusive prefix sums of a refined range, int32[T + 1], and
+    // the scan's per-block totals
+    DevBuf g_offs, g_scan;
     // the last successful uvrt_gather_direct with the variance plane on: what uvrt_gather_refine refines.  Host state only.
     // Assigned whole; `valid` false: forgotten.
     struct GatherMemo {
@@ -155,8 +161,18 @@ struct uvrt_ctx {
         int32_t first = 0, count = 0, samples = 0, mode = 0, photons_equiv = 0;
         uint32_t seed = 0;
         float from[3] = {0, 0, 0}, to[3] = {0, 0, 0}, light_length = 0;
-    } gather_memo;
-    bool g_tris_valid = false;                 // g_tris holds the current scene
+    };
+    // What is derived from the scene and made on first use.  uvrt_set_scene drops the struct whole (void_scene_state,
+    // uvrt_capi.hip): a member added here is voided with it.
+    struct SceneDerived {
+        DevBuf free_recs;                      // the free-origin kernel's records, [npairs + T + 1] x 64 B
+        bool free_recs_valid = false;          // ... for the current scene
+        DevBuf g_tris;                         // the gather's triangles by original id
+        bool g_tris_valid = false;             // g_tris holds the current scene
+        DevBuf expected, variance;             // the gather's expected plane f64[T] and the variance plane f64[T] beside it
+        DevBuf g_extra;                        // n_t of the last refine, int32[T] (made zeroed)
+        GatherMemo gather_memo;                // a refine works on one scene's planes
+    } derived;
 
     // Launch lanes: consecutive launches (generate -> extend -> accumulate ->
     // shade) alternate between the context's stream and an internal side stream, each with its own

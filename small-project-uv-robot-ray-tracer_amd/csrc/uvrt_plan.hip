@@ -536,12 +536,12 @@ int uvrt_plan_capture_expected(uvrt_ctx* c, int32_t position)
     if (S.with_variance)
         if (int rc = ensure_variance(c)) return rc;
     hipLaunchKernelGGL(k_plan_capture_expected, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream,
-                       S.E.as<double>() + (size_t)position * c->T, (const double*)c->expected.as<double>(), c->T,
+                       S.E.as<double>() + (size_t)position * c->T, (const double*)c->derived.expected.as<double>(), c->T,
                        S.overflow.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     if (S.with_variance) {      // V[position][t] += variance[t]: the same sum, the same flag
         hipLaunchKernelGGL(k_plan_capture_expected, dim3(nblocks(c->T, 256)), dim3(256), 0, c->stream,
-                           S.V.as<double>() + (size_t)position * c->T, (const double*)c->variance.as<double>(), c->T,
+                           S.V.as<double>() + (size_t)position * c->T, (const double*)c->derived.variance.as<double>(), c->T,
                            S.overflow.as<uint32_t>());
         HIP_TRY(hipGetLastError());
     }

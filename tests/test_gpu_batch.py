@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import GLB, ROUTE
+from scene_layout_restate import pair_order
 
 pytestmark = pytest.mark.gpu
 
@@ -99,12 +100,7 @@ def test_a_new_record_renumbering_at_the_same_address_is_not_mistaken_for_the_ol
     c = pkg.capi.Ctx(0)
     try:
         c.set_scene(oscene.tris, oscene.nodes, oscene.triIdx)
-        nodes = oscene.nodes                                     # inner nodes reachable from the root
-        q, i = [0], 0
-        while i < len(q):
-            l = int(nodes[q[i]]["leftFirst"]); i += 1
-            q += [l + k for k in (0, 1) if nodes[l + k]["triCount"] == 0]
-        npairs = len(q)
+        npairs = pair_order(oscene.nodes).size                   # inner nodes reachable from the root
         expect = []
         seed = 0
         for _ in range(3):

@@ -5,23 +5,12 @@ counts of the ORACLE's traversal of the same sample rays."""
 import numpy as np
 import pytest
 
+from scene_layout_restate import pair_order
+
 pytestmark = pytest.mark.gpu
 
 KEEP = 175      # records the traversal kernel serves from LDS (uvrt_device.h TOP6_MAX)
 SAMPLE = 32768  # photons of the launch whose visits are counted (uvrt_ctx.h hot_sample)
-
-
-def pair_order(nodes):
-    """node index of every pair record: the inner nodes breadth-first from node 0, as uvrt_set_scene numbers them"""
-    order = [0]
-    qi = 0
-    while qi < len(order):
-        l = int(nodes["leftFirst"][order[qi]])
-        for ch in (l, l + 1):
-            if nodes["triCount"][ch] == 0:
-                order.append(ch)
-        qi += 1
-    return np.array(order, dtype=np.int64)
 
 
 def lamp_pos(orc, oscene, oroute, k):

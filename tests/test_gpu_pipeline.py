@@ -4,6 +4,8 @@ result must equal the one-stream behaviour and the oracle, bit for bit."""
 import numpy as np
 import pytest
 
+from scene_layout_restate import pair_order
+
 pytestmark = pytest.mark.gpu
 
 
@@ -128,13 +130,7 @@ def test_record_renumbering_does_not_change_results(ctx, orc, oscene, oroute):
     kernel; any permutation must give the same counts (here: a random one and the reversal)."""
     lps = positions(orc, oscene, oroute)
     n = 80000
-    nodes = oscene.nodes                                     # inner nodes reachable from the root
-    q = [0] if nodes[0]["triCount"] == 0 else []
-    i = 0
-    while i < len(q):
-        l = int(nodes[q[i]]["leftFirst"]); i += 1
-        q += [l + k for k in (0, 1) if nodes[l + k]["triCount"] == 0]
-    npairs = len(q)
+    npairs = pair_order(oscene.nodes).size                   # inner nodes reachable from the root
     ctx.set_pipeline(True)
     ctx.resize_rays(n)
     rays, _ = orc.generate(0, n, lps[0], oroute["lightLength"], 5)

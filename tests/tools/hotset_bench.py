@@ -5,6 +5,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as g
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from scene_layout_restate import pair_order
 
 pkg = g.load_package(); orc = g.load_oracle()
 glb = os.path.join(ROOT, "tests/golden/testroomopt.glb")
@@ -16,15 +18,8 @@ n = 2073600
 sample = int(os.environ.get("SAMPLE", 65536))
 rays, _ = orc.generate(0, sample, lp, route["lightLength"], 12345)     # a different seed than the timed launch
 hist = orc.extend_visit_hist(s.tris, rays, s.nodes, s.triIdx)
-nodes = s.nodes
-q = [0] if nodes[0]["triCount"] == 0 else []
-i = 0
-while i < len(q):
-    l = int(nodes[q[i]]["leftFirst"]); i += 1
-    for k in (0, 1):
-        if nodes[l + k]["triCount"] == 0:
-            q.append(l + k)
-visits = hist[np.array(q)].astype(np.int64)
+q = pair_order(s.nodes)                              # node of every pair record
+visits = hist[q].astype(np.int64)
 order = np.argsort(-visits, kind="stable")          # hottest first
 perm = np.empty(len(q), dtype=np.uint32)
 perm[order] = np.arange(len(q), dtype=np.uint32)

@@ -8,6 +8,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as g
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from scene_layout_restate import pair_order
 
 pkg = g.load_package(); orc = g.load_oracle()
 glb = os.path.join(ROOT, "tests/golden/testroomopt.glb")
@@ -20,17 +22,9 @@ sample = int(os.environ.get("SAMPLE", 262144))
 rays, _ = orc.generate(0, sample, lp, route["lightLength"], 12345)
 hist = orc.extend_visit_hist(s.tris, rays, s.nodes, s.triIdx)
 nodes = s.nodes
-q = [0] if nodes[0]["triCount"] == 0 else []
-pos = {0: 0}
-kids = []
-i = 0
-while i < len(q):
-    l = int(nodes[q[i]]["leftFirst"]); i += 1
-    ks = []
-    for k in (0, 1):
-        if nodes[l + k]["triCount"] == 0:
-            pos[l + k] = len(q); ks.append(len(q)); q.append(l + k)
-    kids.append(ks)
+q = [int(x) for x in pair_order(nodes)]              # node of every pair record
+pos = {node: i for i, node in enumerate(q)}
+kids = [[pos[ch] for ch in (int(nodes[x]["leftFirst"]), int(nodes[x]["leftFirst"]) + 1) if nodes[ch]["triCount"] == 0] for x in q]   # a pair's inner children
 P = len(q)
 visits = hist[np.array(q)].astype(np.int64)
 TOP = 127
