@@ -301,6 +301,69 @@ int uvrt_read_gather_extra(uvrt_ctx* ctx, int32_t* out, int32_t first, int32_t c
 int uvrt_refine_counts(uvrt_ctx* ctx, int32_t samples0, const uvrt_refine_params* params, int32_t first_tri, int32_t tri_count,
                        int32_t* offsets_out /* tri_count + 1 */);
 
+/* ---- one diffuse bounce: a closest-hit query and a final gather over a per-triangle source plane ----
+ * The direct gather sees the lamp alone; light that arrives by reflection it cannot see.  uvrt_gather_indirect adds one
+ * bounce as a final gather: from points on triangle t it shoots cosine-distributed rays, finds the closest hit and looks up
+ * what the hit triangle already receives in a third plane, `source`, f64[T].  The query is the free-origin
+ * traversal with dist preset to tmax that runs to the end of its stack and deposits nothing: what extend.cl leaves in
+ * ray->dist / ray->triID for that preset (flavours 0 and 1; flavour 2 is refused).  Like the shadow-ray calls, every tracing
+ * call below runs on the context's stream behind all outstanding launches, leaves SEED and tempPhotonMap untouched and drops
+ * "the last generate".
+ *
+ * The source plane holds, for ALL T triangles, the expected tempPhotonMap entry that acts as the emitter -- normally a
+ * snapshot of a finished direct gather (uvrt_indirect_source_from_expected).  It is allocated (zeroed) on first use, zeroed
+ * by uvrt_set_scene, and is uvrt_device_ptr(ctx, 8, ...).  uvrt_read_indirect_source / uvrt_write_indirect_source are
+ * uvrt_read_expected / uvrt_write_expected for this plane: the write serves a caller who wants further bounces or a
+ * reflectance per triangle (scale the plane).
+ *
+ * uvrt_gather_indirect reads source[0..T) and writes only expected[first_tri .. first_tri + tri_count).  For triangle t of the
+ * range and sample s < S2, j = t*S2 + s (uint32); f32 and f64 as marked, every operator one rounding:
+ *     rng = WangHash(j ^ WangHash(seed));  a, b = RandomFloat(&rng) x 2;  if (a + b > 1) { a = 1 - a; b = 1 - b; }      (f32)
+ *     p.c = (v0.c + a*e1.c) + b*e2.c                                                the gather's point
+ *     up to 8 rounds:  xf, yf = RandomFloat x 2;  x = (double)(xf*2.0f - 1.0f), y likewise;  accept when x*x + y*y <= 1.0
+ *                      after 8 rejected rounds: x = y = 0                           (generate.cl:25-28's disc, bounded)
+ *     n = cross(e1, e2), nn = |n|  (f64);  E = (double)e1;  l1 = sqrt((E.x*E.x + E.y*E.y) + E.z*E.z);  T = E / l1
+ *     B.x = (n.y*T.z - n.z*T.y) / nn,  B.y = (n.z*T.x - n.x*T.z) / nn,  B.z = (n.x*T.y - n.y*T.x) / nn
+ *     z = sqrt(1.0 - (x*x + y*y));  zz = ((s & 1) ? -z : z) / nn        odd samples leave the other face: the model is two-sided
+ *     D.c = ((x*T.c) + (y*B.c)) + (zz*n.c);  dir.c = (float)D.c
+ *     ray: orig = p, dir, tmax = 1e30f.  Not traced (dir = (0,1,0), tmax = 0): nn == 0, a dir component not finite, or all zero
+ *     h_s = the closest hit's triangle;  y_s = (hit && h_s != t && nn_h > 0) ? source[h_s] / (0.5*nn_h) : 0.0
+ *     ind[t] = (nn == 0) ? 0 : ((double)rho * (0.5*nn)) * ((2.0 * sum_s y_s) / (double)S2)      sum in sample order, no atomics
+ *     expected[t] = add ? expected[t] + ind[t] : ind[t]
+ * Directions (x, y, sqrt(1 - x^2 - y^2)) over a uniform disc are cosine-distributed, so the irradiance a Lambertian surround of
+ * radiosity rho*e' sends to p is rho x the mean of e' over a hemisphere's samples; S2/2 samples go to each face and the faces
+ * add, hence 2/S2.  The units are those of `expected`.  A pure function of the source plane, the range's own expected values
+ * (when add) and the arguments, whatever the capacity (triangles go in chunks of floor(capacity / S2)) or the cut of the range
+ * into calls.  Device path per chunk: generate -> the closest-hit kernel -> reduce.
+ * The call leaves `source` and the variance plane untouched and forgets the remembered gather of uvrt_gather_refine, as
+ * uvrt_write_expected does; uvrt_indirect_source_from_expected and the read calls leave it.
+ * Limits: one bounce; rho uniform; a single-sheet object lit on one face re-emits from both (at most a factor rho); the
+ * variance plane is the direct part's.
+ * UVRT_ERR_INVALID with nothing changed: a null argument, no scene, flavour 2, a range outside [0, T], odd or out-of-range
+ * samples, reflectance outside [0, 1] or not finite, add other than 0 / 1, non-zero reserved, the limits of the struct. */
+/* test / interop hook, the closest-hit twin of uvrt_occluded: n 32-byte Ray records with origins of their own, rec.dist = tmax
+ * (1e30f: none).  dist_out[i] / tri_out[i] = what extend.cl leaves in ray->dist / ray->triID for that preset, tri_out = -1 and
+ * dist_out = tmax (same bits) when nothing is accepted.  Flavours 0 and 1; n <= capacity; uploads, traces, reads back,
+ * synchronises; leaves SEED and tempPhotonMap untouched and drops "the last generate", like uvrt_occluded. */
+int uvrt_closest_hits(uvrt_ctx* ctx, const void* rays32, int64_t n, float* dist_out, int32_t* tri_out);
+
+typedef struct {
+    float    reflectance;   /* rho: finite, in [0, 1] */
+    int32_t  samples;       /* S2: EVEN, in [2, 4096]; <= capacity; T * S2 < 2^31 */
+    uint32_t seed;
+    int32_t  add;           /* 0: expected[t] = ind[t];  1: expected[t] = expected[t] + ind[t] */
+    int32_t  reserved[2];   /* 0 */
+} uvrt_indirect_params;
+/* source[0..T) = expected[0..T), on the stream; both planes made if absent */
+int uvrt_indirect_source_from_expected(uvrt_ctx* ctx);
+int uvrt_read_indirect_source(uvrt_ctx* ctx, double* out, int32_t first, int32_t count);
+int uvrt_write_indirect_source(uvrt_ctx* ctx, const double* in, int32_t first, int32_t count);
+int uvrt_gather_indirect(uvrt_ctx* ctx, const uvrt_indirect_params* params, int32_t first_tri, int32_t tri_count);
+/* test hook: the rays uvrt_gather_indirect would trace for the range (its generate kernel alone, chunked the same way),
+ * as 32-byte Ray records with dist = tmax; synchronises; changes no plane */
+int uvrt_gather_indirect_rays(uvrt_ctx* ctx, const uvrt_indirect_params* params, int32_t first_tri, int32_t tri_count,
+                              void* rays32_out);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).
@@ -698,7 +761,7 @@ int uvrt_read_photon_map(uvrt_ctx* ctx, int32_t which_map, double* out, int32_t 
  * tensors handed to an RCCL collective).  which: 0 photonMap f64[T], 1 maxPhotonMap f64[T],
  * 2 tempPhotonMap i32[T], 3 dosageMap f32[T], 4 colour f32[9T], 5 the folded planes i32[launches][T] of the
  * traced batch (for a caller that brings its own collective; uvrt_reduce_batch is the native one), 6 the direct gather's
- * expected plane f64[T], 7 its variance plane f64[T].
+ * expected plane f64[T], 7 its variance plane f64[T], 8 the one-bounce gather's source plane f64[T].
  * The call is also the ordering point for external work on these arrays: it orders the context's
  * stream after every outstanding launch (with launch pipelining some sit on the library's second
  * stream) and makes the library's next work on the arrays wait for whatever the caller enqueues on

@@ -136,6 +136,12 @@ SYMBOLS = [
     ("uvrt_gather_refine", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("uvrt_read_gather_extra", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_refine_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    ("uvrt_closest_hits", C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    ("uvrt_indirect_source_from_expected", C.c_int, [_vp]),
+    ("uvrt_read_indirect_source", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_write_indirect_source", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_gather_indirect", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_gather_indirect_rays", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -156,6 +162,12 @@ class RefineParams(C.Structure):
 class RefineReport(C.Structure):
     """uvrt_refine_report (include/uvrt.h)"""
     _fields_ = [("extra_rays", C.c_int64), ("refined", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IndirectParams(C.Structure):
+    """uvrt_indirect_params (include/uvrt.h)"""
+    _fields_ = [("reflectance", C.c_float), ("samples", C.c_int32), ("seed", C.c_uint32), ("add", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class PlanParams(C.Structure):
@@ -581,6 +593,52 @@ class Ctx:
         tri_count = self.T - int(first_tri) if tri_count is None else int(tri_count)
         out = np.full(max(tri_count, 0) + 1, -1, dtype=np.int32)
         self._ck(self._L.uvrt_refine_counts(self._h, int(samples0), C.byref(prm), int(first_tri), tri_count, _ptr(out)))
+        return out
+
+    # ---- closest hits and the one-bounce gather ----
+    def closest_hits(self, rays):
+        """(float32 dist[n], int32 tri[n]): what extend.cl leaves for rays whose dist is preset to rays["dist"] (the ray's
+        tmax); tri = -1 and dist = tmax (same bits) where nothing is accepted"""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DT)
+        dist = np.zeros(rays.size, dtype=np.float32)
+        tri = np.zeros(rays.size, dtype=np.int32)
+        self._ck(self._L.uvrt_closest_hits(self._h, _ptr(rays), rays.size, _ptr(dist), _ptr(tri)))
+        return dist, tri
+
+    def indirect_source_from_expected(self):
+        self._ck(self._L.uvrt_indirect_source_from_expected(self._h))
+
+    def read_indirect_source(self, first=0, count=None):
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float64)
+        self._ck(self._L.uvrt_read_indirect_source(self._h, _ptr(out), int(first), int(count)))
+        return out
+
+    def write_indirect_source(self, values, first=0):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        self._ck(self._L.uvrt_write_indirect_source(self._h, _ptr(v), int(first), int(v.size)))
+
+    @staticmethod
+    def _indirect_params(reflectance, samples, seed, add):
+        prm = IndirectParams()
+        prm.reflectance = float(np.float32(reflectance))
+        prm.samples = int(samples)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        prm.add = int(add)
+        return prm
+
+    def gather_indirect(self, reflectance, samples, seed, add=0, first_tri=0, tri_count=None):
+        """expected[first_tri, +tri_count) = (add ? expected : 0) + one diffuse bounce of the source plane"""
+        prm = self._indirect_params(reflectance, samples, seed, add)
+        self._ck(self._L.uvrt_gather_indirect(self._h, C.byref(prm), int(first_tri),
+                                              self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    def gather_indirect_rays(self, reflectance, samples, seed, first_tri=0, tri_count=None):
+        """test hook: the rays gather_indirect would trace for the range, RAY_DT with dist = tmax"""
+        prm = self._indirect_params(reflectance, samples, seed, 0)
+        tri_count = self.T - int(first_tri) if tri_count is None else int(tri_count)
+        out = np.zeros(max(tri_count, 0) * max(int(samples), 0), dtype=RAY_DT)
+        self._ck(self._L.uvrt_gather_indirect_rays(self._h, C.byref(prm), int(first_tri), tri_count, _ptr(out)))
         return out
 
     @property

@@ -680,7 +680,11 @@ int uvrt_device_ptr(uvrt_ctx* c, int32_t which, void** ptr, int64_t* bytes)
             if (int rc = ensure_variance(c)) return rc;
             b = &c->derived.variance; elem = 8;
             break;
-        default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..7");
+        case 8:
+            if (int rc = ensure_source(c)) return rc;
+            b = &c->derived.source; elem = 8;
+            break;
+        default: return fail(UVRT_ERR_INVALID, "uvrt_device_ptr: which must be 0..8");
     }
     *ptr = b->p;
     *bytes = (int64_t)((size_t)c->T * elem);

@@ -20,7 +20,7 @@ int ensure_variance(uvrt_ctx* c)
 }
 
 // the gather's per-triangle records {v0, e1, e2} in tris64 order, made from the scene's leaf triangles on first use
-static int ensure_gather_tris(uvrt_ctx* c)
+int ensure_gather_tris(uvrt_ctx* c)
 {
     if (c->derived.g_tris_valid) return UVRT_OK;
     if (int rc = c->derived.g_tris.ensure((size_t)c->T * 48, true, c->stream)) return rc;
@@ -58,7 +58,7 @@ static int ensure_refine_buffers(uvrt_ctx* c)
 // scene's free records, every ray's {orig.x, orig.z}, tmax and answer.  The rays of "the last generate" are gone after it; the
 // launch lane of the last generate stays the current one, so its deposits (tempPhotonMap) are still what uvrt_accumulate,
 // uvrt_read_counts and uvrt_device_ptr see.
-static int begin_shadow_launch(uvrt_ctx* c)
+int begin_shadow_launch(uvrt_ctx* c)
 {
     if (int rc = join_all(c)) return rc;
     c->last = {};                           // lane 0's rays are about to be overwritten

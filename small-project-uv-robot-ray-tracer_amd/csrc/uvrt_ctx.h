@@ -8,6 +8,7 @@
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
 //                         uvrt_set_gather_variance and the variance plane, uvrt_gather_refine)
+//   uvrt_capi_indirect.hip  closest hits and the one-bounce gather (uvrt_closest_hits, uvrt_gather_indirect, the source plane)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -151,6 +152,7 @@ struct uvrt_ctx {
     // shadow rays and the direct gather (uvrt_capi_gather.hip): every ray's {orig.x, orig.z}, tmax and answer and the samples'
     // weights, made on first use.  (The rays themselves go through lane 0's ray buffer, on the context's stream.)
     DevBuf g_oxz, g_tmax, g_occ, g_w;
+    DevBuf g_hit;                              // closest hits (uvrt_capi_indirect.hip): every ray's (dist bits, triID), uint2[capacity]
     // uvrt_gather_refine (include/uvrt.h "adaptive gather"): the exclusive prefix sums of a refined range, int32[T + 1], and
     // the scan's per-block totals
     DevBuf g_offs, g_scan;
@@ -171,6 +173,7 @@ struct uvrt_ctx {
         bool g_tris_valid = false;             // g_tris holds the current scene
         DevBuf expected, variance;             // the gather's expected plane f64[T] and the variance plane f64[T] beside it
         DevBuf g_extra;                        // n_t of the last refine, int32[T] (made zeroed)
+        DevBuf source;                         // the one-bounce gather's source plane f64[T] (made zeroed)
         GatherMemo gather_memo;                // a refine works on one scene's planes
     } derived;
 
@@ -590,6 +593,12 @@ int make_free_records(uvrt_ctx* c);
 int ensure_expected(uvrt_ctx* c);
 // the variance plane beside it, f64[T]: likewise
 int ensure_variance(uvrt_ctx* c);
+// the one-bounce gather's source plane, f64[T]: likewise (uvrt_capi_indirect.hip)
+int ensure_source(uvrt_ctx* c);
+// what the shadow-ray and closest-hit launches share (uvrt_capi_gather.hip): lane 0's ray buffer behind all outstanding work,
+// the scene's free records, every ray's {orig.x, orig.z}, tmax and answer byte; the gather's triangles by original id
+int begin_shadow_launch(uvrt_ctx* c);
+int ensure_gather_tris(uvrt_ctx* c);
 // the next pair of the extend timing pool (uvrt_extend_time_ms) with its start recorded on `s`; *stop stays null
 // while timing is off
 inline int timing_start(uvrt_ctx* c, hipStream_t s, hipEvent_t* stop)

@@ -484,4 +484,36 @@ void launch_refine_reduce(const float4* gtris, const double* w, const uint8_t* o
                           double* variance, int32_t first_tri, int32_t lo, int32_t hi, int32_t samples0, int32_t photons_equiv,
                           int32_t mode, hipStream_t s);
 
+// ---- closest hits and the one-bounce gather (uvrt_indirect.hip; include/uvrt.h "one diffuse bounce") ----
+// The closest-hit traversal's arguments: an OccludeParams with a hit record in place of the byte.  hit[i] = (dist bits, triID)
+// as extend.cl leaves them for a ray whose dist is preset to tmax[i]; (tmax bits, 0xFFFFFFFF) when nothing is accepted.
+struct ClosestParams {
+    ExtendParams e;
+    const float2* oxz;       // [n] orig.x, orig.z
+    const float* tmax;       // [n]
+    uint2* hit;              // [n]
+};
+bool launch_closest_free(const ClosestParams& p, int grid_per_cu, hipStream_t s);
+struct IndirectGenParams {
+    const float4* gtris;
+    float4* rays;            // [tri_count * samples] dir.xyz, orig.y
+    float2* oxz;             // orig.x, orig.z
+    float* tmax;             // 1e30f, or 0 for a sample that is not traced
+    uint32_t seed_hash;      // WangHash(seed)
+    int32_t first_tri, tri_count, samples;
+};
+void launch_indirect_generate(const IndirectGenParams& p, hipStream_t s);
+// expected[t] = (add ? expected[t] : 0) + ind[t] for t in [first_tri, first_tri + tri_count), from the chunk's hit records
+struct IndirectReduceParams {
+    const float4* gtris;
+    const double* source;    // [T]
+    const uint2* hit;        // [tri_count * samples]
+    double* expected;        // [T]
+    int32_t first_tri, tri_count, samples, T;
+    float reflectance;
+    int32_t add;
+};
+void launch_indirect_reduce(const IndirectReduceParams& p, hipStream_t s);
+void launch_export_closest_rays(const float4* rays, const float2* oxz, const float* tmax, void* out32, int64_t count, hipStream_t s);
+
 }  // namespace uvrt

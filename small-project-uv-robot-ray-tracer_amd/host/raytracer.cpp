@@ -186,21 +186,23 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra);
+    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
 }
 
 void RayTracer::ComputeSegments()
 {
     for (const RouteLaunch& l : Launches())
-        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra);
+        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
 }
 
 void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                          double relError, int maxExtra)
+                          double relError, int maxExtra, float reflect, int reflectS)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
     if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
+    if (reflect != 0.0f && samples < 1) fatal("reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)");
+    if (!(reflect >= 0.0f) || !(reflect <= 1.0f)) fatal("reflectance must be in [0, 1]");
     if (samples > 0) {
         // the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
         if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
@@ -230,6 +232,17 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
         } else {
             check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
         }
+        if (reflect > 0.0f) {
+            // one diffuse bounce (raytracer.h reflectance): the finished direct plane is the emitter, its bounce is added to it
+            uvrt_indirect_params ip;
+            memset(&ip, 0, sizeof ip);
+            ip.reflectance = reflect;
+            ip.samples = reflectS;
+            ip.seed = g.seed ^ 0x85EBCA6Bu;
+            ip.add = 1;
+            check(uvrt_indirect_source_from_expected(ctx), "indirect_source_from_expected");
+            check(uvrt_gather_indirect(ctx, &ip, 0, triangleCount), "gather_indirect");
+        }
         if (captureColumn >= 0) check(uvrt_plan_capture_expected(ctx, captureColumn), "plan_capture_expected");
         check(uvrt_accumulate_expected(ctx, l.duration, triangleCount), "accumulate_expected");
     } else if (shardWorld <= 1 || (launchIndex % shardWorld) == shardRank) {
@@ -250,13 +263,13 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
     RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
     RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -375,7 +388,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
 void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra)
+                                  int maxExtra, float reflect, int reflectS)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -392,7 +405,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column, relError, maxExtra);
+        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column, relError, maxExtra, reflect, reflectS);
         Shade();
         ++currIterations;
     }
@@ -463,11 +476,18 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (!(opt.gatherRelError > 0.0) || !std::isfinite(opt.gatherRelError)) fatal("PlanDurations: gatherRelError must be finite and >= 0");
         if (opt.gatherSamples < 2) fatal("PlanDurations: gatherRelError needs a plan from the direct gather with gatherSamples >= 2");
     }
+    if (opt.reflectance != 0.0f) {
+        if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
+        if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
+        if (opt.gatherConfidence != 0.0)
+            fatal("PlanDurations: reflectance is not supported with gatherConfidence (the variance plane knows nothing of the indirect part)");
+    }
     uint32_t seed0 = 0;
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
-        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra);
+        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
+                              opt.reflectance, opt.reflectSamples);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -621,6 +641,10 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
     if (driveSpeed > 0.0f) o << "    <rijsnelheid>" << float_str(driveSpeed) << "</rijsnelheid>\n";   // (not in the reference's files)
     if (gatherSamples > 0) o << "    <gather_samples>" << gatherSamples << "</gather_samples>\n";                  // (likewise)
     if (gatherSamples > 0 && gatherSampling > 0) o << "    <gather_sampling>" << gatherSampling << "</gather_sampling>\n";
+    if (reflectance > 0.0f) {
+        o << "    <reflectance>" << float_str(reflectance) << "</reflectance>\n";
+        o << "    <reflect_samples>" << reflectSamples << "</reflect_samples>\n";
+    }
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
     if (lightPositions.empty()) o << "    <route/>\n";
@@ -660,6 +684,10 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("gather_samples"))) to_int(trim(e->text), &gatherSamples);
     gatherSampling = 0;
     if ((e = root.child("gather_sampling"))) to_int(trim(e->text), &gatherSampling);
+    reflectance = 0.0f;
+    if ((e = root.child("reflectance"))) to_float(trim(e->text), &reflectance);
+    reflectSamples = 16;
+    if ((e = root.child("reflect_samples"))) to_int(trim(e->text), &reflectSamples);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

@@ -134,6 +134,12 @@ public:
         // touched.  0 (default): the plan above, bit for bit.  Not 0 with gatherSamples < 2, negative or not finite: fatal.
         double gatherRelError = 0.0;
         int gatherMaxExtra = 64;
+        // rho > 0: every gather launch of the plan gets one diffuse bounce before its capture (RayTracer::reflectance below,
+        // with reflectSamples beside it).  The plan's own, like S.  0 (default): the plan above, bit for bit.  Not 0 with
+        // gatherSamples = 0, outside [0, 1], or with gatherConfidence != 0: fatal -- the variance plane knows nothing of the
+        // indirect part, so the bound would promise more than it has.
+        float reflectance = 0.0f;
+        int reflectSamples = 16;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -191,22 +197,31 @@ public:
     // (photon launches included), tau negative or not finite: fatal.  Not saved in route files.
     double gatherRelError = 0.0;
     int gatherMaxExtra = 64;
+    // One diffuse bounce on top of the direct gather (include/uvrt.h "one diffuse bounce").  reflectance = rho
+    // in (0, 1] with gatherSamples > 0: after a launch's gather (and its refine, if any) and before its plane is captured or
+    // accumulated, uvrt_indirect_source_from_expected and uvrt_gather_indirect(rho, samples = reflectSamples, seed = the
+    // launch's gather seed ^ 0x85EBCA6B, add = 1) over all triangles.  0 (default): the gather above, bit for bit.  rho not 0
+    // with gatherSamples = 0, or outside [0, 1]: fatal.  One bounce, one rho for the whole scene; the variance plane stays the
+    // direct part's.  Saved as <reflectance> and <reflect_samples> after the gather tags in route files when rho > 0.
+    float reflectance = 0.0f;
+    int reflectSamples = 16;
     unsigned gatherLaunches = 0;                   // gather launches since ResetDosageMap: the next launch's seed
 private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
     // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with samples > 0 the direct
     // gather -> accumulate_expected, its plane first captured into column captureColumn of a plan when that is >= 0.
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
-    // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError).
+    // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError);
+    // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance).
     void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                   double relError, int maxExtra);
+                   double relError, int maxExtra, float reflect, int reflectS);
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
     void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra);
+                           int maxExtra, float reflect, int reflectS);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

@@ -67,6 +67,14 @@
 //                                           their estimate get up to MAX extra shadow rays (a power of two in [2, 4096], default
 //                                           64).  TAU finite and > 0.  With --plan-gather, --plan-verify recomputes with the same
 //                                           refine, so it sees the plan's own estimates; works with and without --plan-confidence
+//            [--reflect RHO[,S2]]           with --gather S or --plan-gather S (also under --drive-speed / --plan-drive): one diffuse
+//                                           bounce on top of every gather launch (RayTracer::reflectance / reflectSamples,
+//                                           PlanOptions::reflectance / reflectSamples): S2 cosine-distributed rays per
+//                                           triangle (even, in [2, 4096], default 16) look up what their closest hit receives
+//                                           directly; RHO in [0, 1] is the one reflectance of every surface.  The triangles behind
+//                                           furniture that see no lamp get an estimate.  One bounce; the variance plane stays the
+//                                           direct part's, so --plan-confidence refuses it.  --save-route writes <reflectance> and
+//                                           <reflect_samples>; --plan-verify recomputes with the same bounce
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -131,7 +139,7 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
              const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence,
-             double refineTau, int refineMax)
+             double refineTau, int refineMax, float reflect, int reflectS)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -142,6 +150,8 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.gatherConfidence = planGather > 0 ? planConfidence : 0.0;
     opt.gatherRelError = planGather > 0 ? refineTau : 0.0;
     opt.gatherMaxExtra = refineMax;
+    opt.reflectance = planGather > 0 ? reflect : 0.0f;
+    opt.reflectSamples = reflectS;
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
     if (planGather > 0) {
@@ -154,6 +164,11 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
             rt.gatherRelError = opt.gatherRelError;     // --plan-verify recomputes the plan's own estimates
             rt.gatherMaxExtra = opt.gatherMaxExtra;
             printf("plan: adaptive gather, relative error %.9g, at most %d extra samples\n", opt.gatherRelError, opt.gatherMaxExtra);
+        }
+        if (opt.reflectance > 0.0f) {
+            rt.reflectance = opt.reflectance;           // --plan-verify and --save-route: the plan's own bounce
+            rt.reflectSamples = opt.reflectSamples;
+            printf("plan: one diffuse bounce, reflectance %.8g, %d samples per triangle and launch\n", (double)opt.reflectance, opt.reflectSamples);
         }
     }
     const float m = minDose >= 0.0f ? minDose : rt.minDosage;
@@ -225,6 +240,8 @@ int main(int argc, char** argv)
     double planConfidence = -1.0;           // < 0: not given
     double refineTau = 0.0;                 // 0: not given
     int refineMax = 64;
+    float reflect = -1.0f;                  // < 0: not given
+    int reflectS = 16;
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
     ViewMode view = dosage;
@@ -298,6 +315,26 @@ int main(int argc, char** argv)
                 return 2;
             }
         }
+        else if (!strcmp(argv[i], "--reflect")) {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            const double rho = strtod(v, &end);
+            bool ok = end != v && std::isfinite(rho) && rho >= 0.0 && rho <= 1.0;
+            if (ok && *end == ',') {
+                const char* m = end + 1;
+                const long s2 = strtol(m, &end, 10);
+                ok = end != m && *end == 0 && s2 >= 2 && s2 <= 4096 && (s2 & 1) == 0;
+                reflectS = (int)s2;
+            } else if (ok) {
+                ok = *end == 0;
+            }
+            if (!ok) {
+                fprintf(stderr, "--reflect RHO[,S2]: RHO must be in [0, 1], S2 even and in [2, 4096] (with --gather S or --plan-gather S)\n");
+                return 2;
+            }
+            reflect = (float)rho;
+        }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -308,6 +345,8 @@ int main(int argc, char** argv)
     if (gatherSampling >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-sampling needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planConfidence >= 0.0 && planGather < 2) { fprintf(stderr, "--plan-confidence needs --plan-gather S with S >= 2\n"); return 2; }
     if (refineTau > 0.0 && gather < 2 && planGather < 2) { fprintf(stderr, "--gather-refine needs --gather S or --plan-gather S with S >= 2\n"); return 2; }
+    if (reflect >= 0.0f && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--reflect needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
+    if (reflect >= 0.0f && planConfidence >= 0.0) { fprintf(stderr, "--reflect cannot be combined with --plan-confidence (the variance plane knows nothing of the indirect part)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
@@ -342,6 +381,8 @@ int main(int argc, char** argv)
     if (gather >= 0) rayTracer.gatherSamples = gather;
     if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
     if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
+    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; }
+    if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectance = 0.0f;    // (the route file's own <reflectance>: a plan's bounce is --reflect's)
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
         return 2;
@@ -364,7 +405,8 @@ int main(int argc, char** argv)
         rayTracer.ResetDosageMap();
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
-                                gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax);
+                                gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax,
+                                reflect < 0.0f ? 0.0f : reflect, reflectS);
         save_route(rayTracer, saveRoute);
         return rc;
     }
