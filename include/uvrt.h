@@ -364,6 +364,57 @@ int uvrt_gather_indirect(uvrt_ctx* ctx, const uvrt_indirect_params* params, int3
 int uvrt_gather_indirect_rays(uvrt_ctx* ctx, const uvrt_indirect_params* params, int32_t first_tri, int32_t tri_count,
                               void* rays32_out);
 
+/* ---- recorded hit links: the bounce's rays traced once per scene, and gathers of several bounces over them ----
+ * The rays of uvrt_gather_indirect are a function of the scene, S2 and the seed alone; only the `source` values looked up at
+ * their hits change from launch to launch.  uvrt_indirect_links_build traces them once, for ALL T triangles, and records for
+ * every (triangle t, sample s) the hit link
+ *     link[t][s] = (hit && h_s != t && nn_h > 0) ? h_s : -1
+ * with h_s as above: the condition under which y_s can be non-zero is baked into the link.  It runs on the context's stream
+ * behind all outstanding launches, in chunks of floor(capacity / S2) triangles, each chunk generate -> the closest-hit kernel
+ * (as uvrt_gather_indirect, with the same sample numbers and WangHash(seed)) -> a store kernel.  Like uvrt_gather_indirect it
+ * drops "the last generate" and leaves SEED, tempPhotonMap and every plane untouched; it also leaves the remembered gather of
+ * uvrt_gather_refine.  A second build replaces the links, uvrt_set_scene drops them, uvrt_set_flavour leaves them:
+ * uvrt_indirect_links_info reports {samples (0: no links), seed, the flavour they were traced in, 0}.
+ * UVRT_ERR_INVALID with nothing changed and earlier links kept: a null argument, no scene, flavour 2, non-zero reserved, and
+ * what uvrt_gather_indirect refuses for `samples`.  A failed allocation: UVRT_ERR_HIP, earlier links kept.
+ * uvrt_read_indirect_links (test hook; synchronises): out[(t - first_tri) * S2 + s] = link[t][s], whatever the device layout
+ * (which is sample-major).
+ *
+ * uvrt_gather_indirect_linked reads source[0..T) and the links and writes only expected[first_tri .. first_tri + tri_count).
+ * K = bounces in [1, 16]; everything f64, every operator one rounding, nn_t = |cross(e1, e2)| as above:
+ *     e_0[h] = nn_h > 0 ? source[h] / (0.5*nn_h) : 0.0                                                       all h
+ *     for b = 1..K:
+ *       g_b[t] = nn_t == 0 ? 0.0 : ((double)rho * (0.5*nn_t)) * ((2.0 * sum_s (link[t][s] >= 0 ? e_{b-1}[link[t][s]] : 0.0)) / (double)S2)
+ *       e_b[t] = nn_t > 0 ? g_b[t] / (0.5*nn_t) : 0.0
+ *     total[t]    = (..((g_1[t] + g_2[t]) + g_3[t]) .. + g_K[t])             ascending b; K = 1: g_1[t]
+ *     expected[t] = add ? expected[t] + total[t] : total[t]
+ * The sum over s runs in sample order from +0.0, without atomics.  These are uvrt_gather_indirect's expressions: with K = 1
+ * and links built with (S2, seed) in flavour f the call gives `expected` bit for bit what uvrt_gather_indirect(rho, S2, seed,
+ * add) gives in flavour f.  Bounces before the last are evaluated for all T triangles (they are the next bounce's source), so
+ * a triangle's result depends neither on the range nor on its cut into calls.  The call traces nothing: it works in any
+ * flavour, runs on the context's stream behind all outstanding launches (one kernel launch per bounce), leaves "the last
+ * generate", SEED, tempPhotonMap, `source`, the variance plane and the links untouched and forgets the remembered gather of
+ * uvrt_gather_refine, as uvrt_write_expected does.
+ * What is traded: every launch sees the same directions, so the bounce's sampling error is common to all
+ * launches of a route and does not average out over them; S2 is paid once per scene and can be chosen much larger.
+ * UVRT_ERR_INVALID with nothing changed: a null argument, no scene, no links, bounces outside [1, 16], reflectance outside
+ * [0, 1] or not finite, add other than 0 / 1, non-zero reserved, a range outside [0, T]. */
+typedef struct {
+    int32_t  samples;       /* S2: as for uvrt_indirect_params */
+    uint32_t seed;
+    int32_t  reserved[2];   /* 0 */
+} uvrt_links_params;
+int uvrt_indirect_links_build(uvrt_ctx* ctx, const uvrt_links_params* params);
+int uvrt_indirect_links_info(uvrt_ctx* ctx, int32_t out4[4]);
+int uvrt_read_indirect_links(uvrt_ctx* ctx, int32_t* out, int32_t first_tri, int32_t tri_count);
+typedef struct {
+    float    reflectance;   /* rho: finite, in [0, 1] */
+    int32_t  bounces;       /* K: in [1, 16] */
+    int32_t  add;           /* 0: expected[t] = total[t];  1: expected[t] = expected[t] + total[t] */
+    int32_t  reserved[3];   /* 0 */
+} uvrt_linked_params;
+int uvrt_gather_indirect_linked(uvrt_ctx* ctx, const uvrt_linked_params* params, int32_t first_tri, int32_t tri_count);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).

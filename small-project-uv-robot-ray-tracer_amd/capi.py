@@ -142,6 +142,10 @@ SYMBOLS = [
     ("uvrt_write_indirect_source", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_gather_indirect", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_gather_indirect_rays", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    ("uvrt_indirect_links_build", C.c_int, [_vp, _vp]),
+    ("uvrt_indirect_links_info", C.c_int, [_vp, _vp]),
+    ("uvrt_read_indirect_links", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_gather_indirect_linked", C.c_int, [_vp, _vp, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -168,6 +172,16 @@ class IndirectParams(C.Structure):
     """uvrt_indirect_params (include/uvrt.h)"""
     _fields_ = [("reflectance", C.c_float), ("samples", C.c_int32), ("seed", C.c_uint32), ("add", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class LinksParams(C.Structure):
+    """uvrt_links_params (include/uvrt.h)"""
+    _fields_ = [("samples", C.c_int32), ("seed", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
+class LinkedParams(C.Structure):
+    """uvrt_linked_params (include/uvrt.h)"""
+    _fields_ = [("reflectance", C.c_float), ("bounces", C.c_int32), ("add", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class PlanParams(C.Structure):
@@ -640,6 +654,38 @@ class Ctx:
         out = np.zeros(max(tri_count, 0) * max(int(samples), 0), dtype=RAY_DT)
         self._ck(self._L.uvrt_gather_indirect_rays(self._h, C.byref(prm), int(first_tri), tri_count, _ptr(out)))
         return out
+
+    # ---- recorded hit links and the multi-bounce gather over them ----
+    def indirect_links_build(self, samples, seed):
+        """traces the bounce's rays of all triangles once and records what each sees (or -1)"""
+        prm = LinksParams()
+        prm.samples = int(samples)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        self._ck(self._L.uvrt_indirect_links_build(self._h, C.byref(prm)))
+
+    def indirect_links_info(self):
+        """(samples, seed, flavour): samples 0 = no links"""
+        out = np.zeros(4, dtype=np.int32)
+        self._ck(self._L.uvrt_indirect_links_info(self._h, _ptr(out)))
+        return int(out[0]), int(out[1]) & 0xFFFFFFFF, int(out[2])
+
+    def read_indirect_links(self, first_tri=0, tri_count=None):
+        """test hook: int32 [tri_count, samples], triangle-major whatever the device layout"""
+        tri_count = self.T - int(first_tri) if tri_count is None else int(tri_count)
+        s2 = self.indirect_links_info()[0]
+        n = max(tri_count, 0) * s2
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self._ck(self._L.uvrt_read_indirect_links(self._h, _ptr(out), int(first_tri), tri_count))
+        return out[:n].reshape(max(tri_count, 0), s2)
+
+    def gather_indirect_linked(self, reflectance, bounces, add=0, first_tri=0, tri_count=None):
+        """expected[first_tri, +tri_count) = (add ? expected : 0) + `bounces` diffuse bounces of the source plane over the links"""
+        prm = LinkedParams()
+        prm.reflectance = float(np.float32(reflectance))
+        prm.bounces = int(bounces)
+        prm.add = int(add)
+        self._ck(self._L.uvrt_gather_indirect_linked(self._h, C.byref(prm), int(first_tri),
+                                                     self.T - int(first_tri) if tri_count is None else int(tri_count)))
 
     @property
     def seed(self):

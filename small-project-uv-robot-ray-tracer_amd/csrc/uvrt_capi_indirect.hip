@@ -14,14 +14,14 @@ int ensure_source(uvrt_ctx* c)
 }
 
 // begin_shadow_launch plus the hit records
-static int begin_closest_launch(uvrt_ctx* c)
+int begin_closest_launch(uvrt_ctx* c)
 {
     if (int rc = begin_shadow_launch(c)) return rc;
     return c->g_hit.ensure((size_t)std::max<int64_t>(c->capacity, 1) * 8, false, c->stream);
 }
 
 // k_closest_free over the first n rays of lane 0 (rays, g_oxz, g_tmax -> g_hit) on the context's stream
-static int trace_closest_rays(uvrt_ctx* c, int64_t n, const char* who)
+int trace_closest_rays(uvrt_ctx* c, int64_t n, const char* who)
 {
     Lane& L = c->lanes[0];
     ClosestParams cp;
@@ -40,7 +40,7 @@ static int trace_closest_rays(uvrt_ctx* c, int64_t n, const char* who)
 }
 
 // the arguments uvrt_gather_indirect and uvrt_gather_indirect_rays share; `who` names the call in the message
-static int check_indirect(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t first_tri, int32_t tri_count, const char* who)
+int check_indirect(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t first_tri, int32_t tri_count, const char* who)
 {
     if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
     if (c->flavour != 0 && c->flavour != 1)
@@ -60,7 +60,7 @@ static int check_indirect(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t 
     return UVRT_OK;
 }
 
-static IndirectGenParams indirect_gen_params(uvrt_ctx* c, const uvrt_indirect_params* prm)
+IndirectGenParams indirect_gen_params(uvrt_ctx* c, const uvrt_indirect_params* prm)
 {
     IndirectGenParams g;
     memset(&g, 0, sizeof g);

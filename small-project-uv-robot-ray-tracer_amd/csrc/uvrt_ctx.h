@@ -9,6 +9,8 @@
 //   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
 //                         uvrt_set_gather_variance and the variance plane, uvrt_gather_refine)
 //   uvrt_capi_indirect.hip  closest hits and the one-bounce gather (uvrt_closest_hits, uvrt_gather_indirect, the source plane)
+//   uvrt_capi_links.hip   recorded hit links and the multi-bounce gather over them (uvrt_indirect_links_build,
+//                         uvrt_gather_indirect_linked)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -174,6 +176,11 @@ struct uvrt_ctx {
         DevBuf expected, variance;             // the gather's expected plane f64[T] and the variance plane f64[T] beside it
         DevBuf g_extra;                        // n_t of the last refine, int32[T] (made zeroed)
         DevBuf source;                         // the one-bounce gather's source plane f64[T] (made zeroed)
+        // recorded hit links (uvrt_capi_links.hip): int32[links_samples * T], sample-major (links[s * T + t]); links_samples 0:
+        // none.  Beside them the linked gather's two irradiance planes (ping-pong over the bounces) and its running total, f64[T]
+        DevBuf links, link_e[2], link_total;
+        int32_t links_samples = 0, links_flavour = 0;
+        uint32_t links_seed = 0;
         GatherMemo gather_memo;                // a refine works on one scene's planes
     } derived;
 
@@ -599,6 +606,13 @@ int ensure_source(uvrt_ctx* c);
 // the scene's free records, every ray's {orig.x, orig.z}, tmax and answer byte; the gather's triangles by original id
 int begin_shadow_launch(uvrt_ctx* c);
 int ensure_gather_tris(uvrt_ctx* c);
+// what the one-bounce gather and the link build share (uvrt_capi_indirect.hip): begin_shadow_launch plus the hit records;
+// the argument check (`who` names the call in the message); the generate kernel's arguments; k_closest_free over the first
+// n rays of lane 0 (rays, g_oxz, g_tmax -> g_hit) on the context's stream
+int begin_closest_launch(uvrt_ctx* c);
+int check_indirect(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t first_tri, int32_t tri_count, const char* who);
+IndirectGenParams indirect_gen_params(uvrt_ctx* c, const uvrt_indirect_params* prm);
+int trace_closest_rays(uvrt_ctx* c, int64_t n, const char* who);
 // the next pair of the extend timing pool (uvrt_extend_time_ms) with its start recorded on `s`; *stop stays null
 // while timing is off
 inline int timing_start(uvrt_ctx* c, hipStream_t s, hipEvent_t* stop)

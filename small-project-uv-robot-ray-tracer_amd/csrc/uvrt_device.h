@@ -516,4 +516,37 @@ struct IndirectReduceParams {
 void launch_indirect_reduce(const IndirectReduceParams& p, hipStream_t s);
 void launch_export_closest_rays(const float4* rays, const float2* oxz, const float* tmax, void* out32, int64_t count, hipStream_t s);
 
+// ---- recorded hit links and multi-bounce gathers (uvrt_links.hip; include/uvrt.h "recorded hit links") ----
+// The links are SAMPLE-major on the device: links[s * T + t], so that the 64 lanes of a wave (64 consecutive triangles) read
+// 256 contiguous bytes per sample.
+// links[s * T + t] = h_s or -1, for t in [first_tri, first_tri + tri_count), from a chunk's hit records (triangle-major)
+struct LinksStoreParams {
+    const float4* gtris;
+    const uint2* hit;        // [tri_count * samples]
+    int32_t* links;          // [samples * T]
+    int32_t first_tri, tri_count, samples, T;
+};
+void launch_links_store(const LinksStoreParams& p, hipStream_t s);
+// e[h] = nn_h > 0 ? source[h] / (0.5 * nn_h) : 0.0 for all h < T
+void launch_links_irradiance(const float4* gtris, const double* source, double* e, int32_t T, hipStream_t s);
+// One bounce b of uvrt_gather_indirect_linked for t in [first_tri, first_tri + tri_count): g = the lookup-and-sum over e_in.
+// e_out (not the last bounce): e_out[t] = g's irradiance.  total_in / total_out: the running sum g_1 + .. (null: none / not
+// kept).  expected (the last bounce): expected[t] = (add ? expected[t] : 0) + total.
+struct LinksApplyParams {
+    const float4* gtris;
+    const int32_t* links;    // [samples * T]
+    const double* e_in;      // [T]
+    double* e_out;           // [T] or null
+    const double* total_in;  // [T] or null (bounce 1)
+    double* total_out;       // [T] or null (the last bounce)
+    double* expected;        // [T] or null (every bounce but the last)
+    int32_t first_tri, tri_count, samples, T;
+    float reflectance;
+    int32_t add;
+};
+void launch_links_apply(const LinksApplyParams& p, hipStream_t s);
+// test hook: out[(t - first_tri) * samples + s] = links[s * T + t]
+void launch_links_export(const int32_t* links, int32_t* out, int32_t first_tri, int32_t tri_count, int32_t samples, int32_t T,
+                         hipStream_t s);
+
 }  // namespace uvrt

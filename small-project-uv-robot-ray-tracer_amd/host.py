@@ -77,6 +77,9 @@ SYMBOLS = [
     ("uvrt_host_rt_plan_gather_reflect", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
                                                 C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, _vp,
                                                 C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_reflect_linked", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
+                                                       _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -94,10 +97,10 @@ _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIt
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
            "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling", "gatherRelError",
-           "gatherMaxExtra", "reflectance", "reflectSamples"}
+           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
                "photonMapSize", "viewMode", "gatherSamples", "gatherSampling", "gatherMaxExtra",
-               "reflectSamples"}
+               "reflectSamples", "reflectBounces"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 
@@ -221,6 +224,8 @@ class RayTracer:
 
     def __setattr__(self, name, value):
         if name in _FIELDS:
+            if name == "reflectBounces" and not (0 <= int(value) <= 16 and int(value) == value):
+                raise ValueError("reflectBounces must be an integer in [0, 16]")
             self._L.uvrt_host_rt_set(self._h, name.encode(), float(value))
             if name == "photonCount":
                 self._L.uvrt_host_rt_update_photons_per_light(self._h)
@@ -287,10 +292,13 @@ class RayTracer:
         args.update(plan)
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, **args)
 
-    def PlanDurationsReflect(self, reflectance, reflect_samples=16, gather_rel_error=0.0, gather_max_extra=64, **plan):
+    def PlanDurationsReflect(self, reflectance, reflect_samples=16, gather_rel_error=0.0, gather_max_extra=64, reflect_bounces=0,
+                             **plan):
         """PlanDurations(**plan) with PlanOptions::reflectance = rho and reflectSamples: every gather launch of the plan gets one
         diffuse bounce before its capture.  rho > 0 needs gather_samples > 0 and refuses gather_confidence: the
-        variance plane knows nothing of the indirect part.  0 is PlanDurations / PlanDurationsRefined, bit for bit."""
+        variance plane knows nothing of the indirect part.  0 is PlanDurations / PlanDurationsRefined, bit for bit.
+        reflect_bounces = K in [1, 16] (PlanOptions::reflectBounces): K bounces over hit links recorded once per scene instead of
+        the bounce traced per launch; 0 is the traced bounce, bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
                     gather_sampling=0, gather_confidence=0.0)
         unknown = set(plan) - set(args)
@@ -298,6 +306,8 @@ class RayTracer:
             raise TypeError("PlanDurationsReflect: unknown arguments %s" % sorted(unknown))
         args.update(plan)
         rho, s2 = float(np.float32(reflectance)), int(reflect_samples)
+        if int(reflect_bounces) != reflect_bounces or not (0 <= int(reflect_bounces) <= 16):
+            raise ValueError("reflect_bounces must be an integer in [0, 16]")
         if not (0.0 <= rho <= 1.0):
             raise ValueError("reflectance must be in [0, 1]")
         if rho > 0.0 and not args["gather_samples"]:
@@ -307,10 +317,11 @@ class RayTracer:
         if rho > 0.0 and (s2 < 2 or s2 > 4096 or s2 & 1):
             raise ValueError("reflect_samples must be even and in [2, 4096]")
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, reflectance=rho,
-                                    reflect_samples=s2, **args)
+                                    reflect_samples=s2, reflect_bounces=int(reflect_bounces), **args)
 
     def _plan_durations(self, min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
-                        gather_confidence, gather_rel_error, gather_max_extra, reflectance=0.0, reflect_samples=16):
+                        gather_confidence, gather_rel_error, gather_max_extra, reflectance=0.0, reflect_samples=16,
+                        reflect_bounces=0):
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
         z = float(gather_confidence)
@@ -326,6 +337,13 @@ class RayTracer:
         if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
             raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if reflectance > 0.0 and reflect_bounces > 0:
+            self._L.uvrt_host_rt_plan_gather_reflect_linked(self._h, -1.0 if min_dose is None else float(min_dose),
+                                                            int(min_photons), float(margin), float(rel_gap), int(max_iterations),
+                                                            _addr(keep), int(gather_samples), int(gather_sampling), z, tau, extra,
+                                                            float(reflectance), int(reflect_samples), int(reflect_bounces),
+                                                            C.byref(rep), C.byref(seed))
+            return _plan_result(self, rep, seed)
         if reflectance > 0.0:
             self._L.uvrt_host_rt_plan_gather_reflect(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
                                                      float(margin), float(rel_gap), int(max_iterations), _addr(keep),

@@ -29,7 +29,7 @@ std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>
 RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
                                     const unsigned char* mask, int gather_samples, int gather_sampling = 0,
                                     double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64,
-                                    float reflectance = 0.0f, int reflect_samples = 16)
+                                    float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
@@ -40,6 +40,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
     o.gatherMaxExtra = gather_max_extra;
     o.reflectance = reflectance;
     o.reflectSamples = reflect_samples;
+    o.reflectBounces = reflect_bounces;
     return o;
 }
 
@@ -198,6 +199,17 @@ void uvrt_host_rt_plan_gather_reflect(void* r, float min_dose, int min_photons, 
                                                        gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
                                                        reflectance, reflect_samples), seed);
 }
+// the same with PlanOptions::reflectBounces: the bounces over recorded hit links (include/uvrt.h uvrt_gather_indirect_linked)
+void uvrt_host_rt_plan_gather_reflect_linked(void* r, float min_dose, int min_photons, double margin, double rel_gap,
+                                             int max_iterations, const unsigned char* mask, int gather_samples, int gather_sampling,
+                                             double gather_confidence, double gather_rel_error, int gather_max_extra,
+                                             float reflectance, int reflect_samples, int reflect_bounces, uvrt_plan_report* rep,
+                                             unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
+                                                       reflectance, reflect_samples, reflect_bounces), seed);
+}
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
@@ -228,7 +240,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(finishedComputation, bool) F(thresholdView, bool) F(startedComputation, bool)
     F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
     F(gatherSampling, int) F(gatherRelError, double) F(gatherMaxExtra, int)
-    F(reflectance, float) F(reflectSamples, int)
+    F(reflectance, float) F(reflectSamples, int) F(reflectBounces, int)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

@@ -186,19 +186,20 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
+    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
 }
 
 void RayTracer::ComputeSegments()
 {
     for (const RouteLaunch& l : Launches())
-        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
+        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
 }
 
 void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                          double relError, int maxExtra, float reflect, int reflectS)
+                          double relError, int maxExtra, float reflect, int reflectS, int reflectK)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
+    if (reflectK < 0 || reflectK > 16) fatal("reflectBounces must be in [0, 16]");
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
     if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
     if (reflect != 0.0f && samples < 1) fatal("reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)");
@@ -232,7 +233,26 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
         } else {
             check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
         }
-        if (reflect > 0.0f) {
+        if (reflect > 0.0f && reflectK > 0) {
+            // reflectK bounces over recorded hit links (raytracer.h reflectBounces): traced once per scene and reflectS
+            const uint32_t linkSeed = 0x85EBCA6Bu;
+            int32_t info[4];
+            check(uvrt_indirect_links_info(ctx, info), "indirect_links_info");
+            if (info[0] != reflectS || (uint32_t)info[1] != linkSeed) {
+                uvrt_links_params lp;
+                memset(&lp, 0, sizeof lp);
+                lp.samples = reflectS;
+                lp.seed = linkSeed;
+                check(uvrt_indirect_links_build(ctx, &lp), "indirect_links_build");
+            }
+            uvrt_linked_params kp;
+            memset(&kp, 0, sizeof kp);
+            kp.reflectance = reflect;
+            kp.bounces = reflectK;
+            kp.add = 1;
+            check(uvrt_indirect_source_from_expected(ctx), "indirect_source_from_expected");
+            check(uvrt_gather_indirect_linked(ctx, &kp, 0, triangleCount), "gather_indirect_linked");
+        } else if (reflect > 0.0f) {
             // one diffuse bounce (raytracer.h reflectance): the finished direct plane is the emitter, its bounce is added to it
             uvrt_indirect_params ip;
             memset(&ip, 0, sizeof ip);
@@ -263,13 +283,13 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
     RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
     RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -388,7 +408,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
 void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra, float reflect, int reflectS)
+                                  int maxExtra, float reflect, int reflectS, int reflectK)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -405,7 +425,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column, relError, maxExtra, reflect, reflectS);
+        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column, relError, maxExtra, reflect, reflectS, reflectK);
         Shade();
         ++currIterations;
     }
@@ -476,6 +496,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (!(opt.gatherRelError > 0.0) || !std::isfinite(opt.gatherRelError)) fatal("PlanDurations: gatherRelError must be finite and >= 0");
         if (opt.gatherSamples < 2) fatal("PlanDurations: gatherRelError needs a plan from the direct gather with gatherSamples >= 2");
     }
+    if (opt.reflectBounces < 0 || opt.reflectBounces > 16) fatal("PlanDurations: reflectBounces must be in [0, 16]");
     if (opt.reflectance != 0.0f) {
         if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
         if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
@@ -487,7 +508,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
         r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
-                              opt.reflectance, opt.reflectSamples);
+                              opt.reflectance, opt.reflectSamples, opt.reflectBounces);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -644,6 +665,7 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
     if (reflectance > 0.0f) {
         o << "    <reflectance>" << float_str(reflectance) << "</reflectance>\n";
         o << "    <reflect_samples>" << reflectSamples << "</reflect_samples>\n";
+        if (reflectBounces > 0) o << "    <reflect_bounces>" << reflectBounces << "</reflect_bounces>\n";
     }
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
@@ -688,6 +710,8 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("reflectance"))) to_float(trim(e->text), &reflectance);
     reflectSamples = 16;
     if ((e = root.child("reflect_samples"))) to_int(trim(e->text), &reflectSamples);
+    reflectBounces = 0;
+    if ((e = root.child("reflect_bounces"))) to_int(trim(e->text), &reflectBounces);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

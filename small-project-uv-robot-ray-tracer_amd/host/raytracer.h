@@ -140,6 +140,9 @@ public:
         // indirect part, so the bound would promise more than it has.
         float reflectance = 0.0f;
         int reflectSamples = 16;
+        // K in [1, 16] with reflectance > 0: the plan's launches take K bounces over recorded hit links instead of the traced
+        // one (RayTracer::reflectBounces below).  0 (default): the traced bounce, bit for bit.  Outside [0, 16]: fatal.
+        int reflectBounces = 0;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -205,23 +208,34 @@ public:
     // direct part's.  Saved as <reflectance> and <reflect_samples> after the gather tags in route files when rho > 0.
     float reflectance = 0.0f;
     int reflectSamples = 16;
-    unsigned gatherLaunches = 0;                   // gather launches since ResetDosageMap: the next launch's seed
+    // Bounces over recorded hit links (include/uvrt.h "recorded hit links").  0 (default): the traced bounce
+    // above, once per launch, bit for bit.  K in [1, 16] with reflectance > 0: the links are built once per scene
+    // (uvrt_indirect_links_build with samples = reflectSamples and the fixed seed 0x85EBCA6B; rebuilt when
+    // uvrt_indirect_links_info reports another scene's or another sample count's), and every gather launch does
+    // uvrt_indirect_source_from_expected and uvrt_gather_indirect_linked(rho, K, add = 1) over all triangles in place of the
+    // traced bounce: no ray is traced per launch, and bounces 2..K come with it.  Every launch then sees the same directions,
+    // so the bounce's sampling error no longer averages out over a route; reflectSamples is paid once and can be much larger.
+    // Outside [0, 16]: fatal.  Without effect at reflectance 0.  Saved as <reflect_bounces> after <reflect_samples> when both
+    // rho and K are > 0.
+    int reflectBounces = 0;
+    unsigned gatherLaunches = 0;                  // gather launches since ResetDosageMap: the next launch's seed
 private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
     // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with samples > 0 the direct
     // gather -> accumulate_expected, its plane first captured into column captureColumn of a plan when that is >= 0.
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
     // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError);
-    // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance).
+    // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance), or with reflectK > 0 that many
+    // bounces over recorded hit links (reflectBounces).
     void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                   double relError, int maxExtra, float reflect, int reflectS);
+                   double relError, int maxExtra, float reflect, int reflectS, int reflectK);
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
     void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra, float reflect, int reflectS);
+                           int maxExtra, float reflect, int reflectS, int reflectK);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

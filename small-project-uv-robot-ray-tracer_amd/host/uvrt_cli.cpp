@@ -75,6 +75,12 @@
 //                                           furniture that see no lamp get an estimate.  One bounce; the variance plane stays the
 //                                           direct part's, so --plan-confidence refuses it.  --save-route writes <reflectance> and
 //                                           <reflect_samples>; --plan-verify recomputes with the same bounce
+//            [--reflect-bounces K]          with --reflect: K bounces in [1, 16] over hit links recorded once per scene instead of
+//                                           the one bounce traced per launch (RayTracer::reflectBounces, PlanOptions::reflectBounces,
+//                                           DESIGN.md 18): the bounce's rays are traced once with S2 samples and a fixed seed, every
+//                                           launch then looks its sources up along them, and bounces 2..K come with it.  All launches
+//                                           see the same directions: the bounce's sampling error no longer averages out over a
+//                                           route, but S2 is paid once and can be much larger.  --save-route writes <reflect_bounces>
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -139,7 +145,7 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
              const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence,
-             double refineTau, int refineMax, float reflect, int reflectS)
+             double refineTau, int refineMax, float reflect, int reflectS, int reflectK)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -152,6 +158,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.gatherMaxExtra = refineMax;
     opt.reflectance = planGather > 0 ? reflect : 0.0f;
     opt.reflectSamples = reflectS;
+    opt.reflectBounces = planGather > 0 ? reflectK : 0;
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
     if (planGather > 0) {
@@ -168,7 +175,11 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
         if (opt.reflectance > 0.0f) {
             rt.reflectance = opt.reflectance;           // --plan-verify and --save-route: the plan's own bounce
             rt.reflectSamples = opt.reflectSamples;
-            printf("plan: one diffuse bounce, reflectance %.8g, %d samples per triangle and launch\n", (double)opt.reflectance, opt.reflectSamples);
+            rt.reflectBounces = opt.reflectBounces;
+            if (opt.reflectBounces > 0)
+                printf("plan: %d diffuse bounces over recorded hit links, reflectance %.8g, %d samples per triangle\n", opt.reflectBounces, (double)opt.reflectance, opt.reflectSamples);
+            else
+                printf("plan: one diffuse bounce, reflectance %.8g, %d samples per triangle and launch\n", (double)opt.reflectance, opt.reflectSamples);
         }
     }
     const float m = minDose >= 0.0f ? minDose : rt.minDosage;
@@ -242,6 +253,7 @@ int main(int argc, char** argv)
     int refineMax = 64;
     float reflect = -1.0f;                  // < 0: not given
     int reflectS = 16;
+    int reflectK = 0;                       // 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
     ViewMode view = dosage;
@@ -335,6 +347,17 @@ int main(int argc, char** argv)
             }
             reflect = (float)rho;
         }
+        else if (!strcmp(argv[i], "--reflect-bounces")) {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            const long k = strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 1 || k > 16) {
+                fprintf(stderr, "--reflect-bounces K: K must be an integer in [1, 16] (with --reflect RHO[,S2])\n");
+                return 2;
+            }
+            reflectK = (int)k;
+        }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -347,6 +370,7 @@ int main(int argc, char** argv)
     if (refineTau > 0.0 && gather < 2 && planGather < 2) { fprintf(stderr, "--gather-refine needs --gather S or --plan-gather S with S >= 2\n"); return 2; }
     if (reflect >= 0.0f && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--reflect needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (reflect >= 0.0f && planConfidence >= 0.0) { fprintf(stderr, "--reflect cannot be combined with --plan-confidence (the variance plane knows nothing of the indirect part)\n"); return 2; }
+    if (reflectK > 0 && !(reflect >= 0.0f)) { fprintf(stderr, "--reflect-bounces needs --reflect RHO[,S2] (with --gather S or --plan-gather S)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
@@ -381,7 +405,7 @@ int main(int argc, char** argv)
     if (gather >= 0) rayTracer.gatherSamples = gather;
     if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
     if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
-    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; }
+    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; }
     if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectance = 0.0f;    // (the route file's own <reflectance>: a plan's bounce is --reflect's)
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
@@ -406,7 +430,7 @@ int main(int argc, char** argv)
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
                                 gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax,
-                                reflect < 0.0f ? 0.0f : reflect, reflectS);
+                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK);
         save_route(rayTracer, saveRoute);
         return rc;
     }
