@@ -73,20 +73,22 @@ int begin_shadow_launch(uvrt_ctx* c)
 // k_occlude_free over the first n rays of lane 0 (rays, oxz, g_tmax -> g_occ) on the context's stream
 static int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who)
 {
-    Lane& L = c->lanes[0];
     OccludeParams op;
-    fill_launch(c, op.e, 0.0f, 0.0f);       // (force_exact: the scene's and the variant's conditions; the origins are per ray)
-    op.e.ovf_stack = L.ovf.as<uint32_t>();  // lane 0's, like its rays: this launch runs on the context's stream
-    op.e.ovf_capacity = L.ovf.bytes / sizeof(uint32_t);
-    op.e.num_cus = c->num_cus;
-    op.e.rays = L.rays.as<float4>();
-    op.oxz = c->g_oxz.as<float2>();
-    op.tmax = c->g_tmax.as<float>();
+    fill_query_launch(c, op, n);
     op.occluded = c->g_occ.as<uint8_t>();
-    op.e.n = n;
-    op.e.recs = c->derived.free_recs.p;
     return timed_launch(c, c->stream, who, "the shadow-ray launch",
                         [&] { return launch_occlude_free(op, variant_per_cu(c->variant, 8), c->stream); });
+}
+
+int upload_query_rays(uvrt_ctx* c, const void* rays32, int64_t n, int (*begin)(uvrt_ctx*))
+{
+    std::vector<float> packed, oxz, tmax;
+    unpack_rays((const HostRay*)rays32, n, packed, &oxz, &tmax);
+    if (int rc = begin(c)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->lanes[0].rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->g_oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->g_tmax.p, tmax.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    return UVRT_OK;
 }
 
 }  // namespace uvrt_impl
@@ -104,13 +106,7 @@ int uvrt_occluded(uvrt_ctx* c, const void* rays32, int64_t n, uint8_t* out)
                     (long long)c->capacity);
     if (n == 0) return UVRT_OK;
     if (int rc = set_device(c)) return rc;
-    std::vector<float> packed, oxz, tmax;
-    unpack_rays((const HostRay*)rays32, n, packed, &oxz, &tmax);
-    if (int rc = begin_shadow_launch(c)) return rc;
-    Lane& L = c->lanes[0];
-    HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->g_oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->g_tmax.p, tmax.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (int rc = upload_query_rays(c, rays32, n, begin_shadow_launch)) return rc;
     if (int rc = trace_shadow_rays(c, n, "uvrt_occluded")) return rc;
     return copy_sync(c, out, c->g_occ.p, (size_t)n, hipMemcpyDeviceToHost);
 }
@@ -188,10 +184,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     g.samples = S;
     g.seed = prm->seed;
     g.mode = c->gather_sampling;
-    // chunks of floor(capacity / S) triangles: a triangle's samples never straddle two of them, so the chunking shows in no bit
-    const int32_t per_chunk = (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX);
-    for (int32_t done = 0; done < tri_count; done += per_chunk) {
-        const int32_t cnt = std::min(per_chunk, tri_count - done);
+    const int rc = for_tri_chunks(c, S, tri_count, [&](int32_t done, int32_t cnt) -> int {
         g.first_tri = first_tri + done;
         g.tri_count = cnt;
         launch_gather_generate(g, c->stream);
@@ -204,7 +197,9 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
             launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->derived.expected.as<double>(), g.first_tri, cnt, S,
                                  prm->photons_equiv, c->stream);
         HIP_TRY(hipGetLastError());
-    }
+        return UVRT_OK;
+    });
+    if (rc) return rc;
     if (var) {
         uvrt_ctx::GatherMemo m;
         m.valid = true;

@@ -23,18 +23,9 @@ int begin_closest_launch(uvrt_ctx* c)
 // k_closest_free over the first n rays of lane 0 (rays, g_oxz, g_tmax -> g_hit) on the context's stream
 int trace_closest_rays(uvrt_ctx* c, int64_t n, const char* who)
 {
-    Lane& L = c->lanes[0];
     ClosestParams cp;
-    fill_launch(c, cp.e, 0.0f, 0.0f);       // (force_exact: the scene's and the variant's conditions; the origins are per ray)
-    cp.e.ovf_stack = L.ovf.as<uint32_t>();  // lane 0's, like its rays: this launch runs on the context's stream
-    cp.e.ovf_capacity = L.ovf.bytes / sizeof(uint32_t);
-    cp.e.num_cus = c->num_cus;
-    cp.e.rays = L.rays.as<float4>();
-    cp.oxz = c->g_oxz.as<float2>();
-    cp.tmax = c->g_tmax.as<float>();
+    fill_query_launch(c, cp, n);
     cp.hit = c->g_hit.as<uint2>();
-    cp.e.n = n;
-    cp.e.recs = c->derived.free_recs.p;
     return timed_launch(c, c->stream, who, "the closest-hit launch",
                         [&] { return launch_closest_free(cp, variant_per_cu(c->variant, 8), c->stream); });
 }
@@ -99,13 +90,7 @@ int uvrt_closest_hits(uvrt_ctx* c, const void* rays32, int64_t n, float* dist_ou
                     (long long)c->capacity);
     if (n == 0) return UVRT_OK;
     if (int rc = set_device(c)) return rc;
-    std::vector<float> packed, oxz, tmax;
-    unpack_rays((const HostRay*)rays32, n, packed, &oxz, &tmax);
-    if (int rc = begin_closest_launch(c)) return rc;
-    Lane& L = c->lanes[0];
-    HIP_TRY(hipMemcpyAsync(L.rays.p, packed.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->g_oxz.p, oxz.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->g_tmax.p, tmax.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (int rc = upload_query_rays(c, rays32, n, begin_closest_launch)) return rc;
     if (int rc = trace_closest_rays(c, n, "uvrt_closest_hits")) return rc;
     std::vector<uint32_t> h((size_t)n * 2);
     if (int rc = copy_sync(c, h.data(), c->g_hit.p, (size_t)n * 8, hipMemcpyDeviceToHost)) return rc;
@@ -161,10 +146,7 @@ int uvrt_gather_indirect(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t f
     r.T = c->T;
     r.reflectance = prm->reflectance;
     r.add = prm->add;
-    // chunks of floor(capacity / S) triangles: a triangle's samples never straddle two of them, so the chunking shows in no bit
-    const int32_t per_chunk = (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX);
-    for (int32_t done = 0; done < tri_count; done += per_chunk) {
-        const int32_t cnt = std::min(per_chunk, tri_count - done);
+    return for_tri_chunks(c, S, tri_count, [&](int32_t done, int32_t cnt) -> int {
         g.first_tri = r.first_tri = first_tri + done;
         g.tri_count = r.tri_count = cnt;
         launch_indirect_generate(g, c->stream);
@@ -172,8 +154,8 @@ int uvrt_gather_indirect(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t f
         if (int rc = trace_closest_rays(c, (int64_t)cnt * S, "uvrt_gather_indirect")) return rc;
         launch_indirect_reduce(r, c->stream);
         HIP_TRY(hipGetLastError());
-    }
-    return UVRT_OK;
+        return UVRT_OK;
+    });
 }
 
 int uvrt_gather_indirect_rays(uvrt_ctx* c, const uvrt_indirect_params* prm, int32_t first_tri, int32_t tri_count, void* rays32_out)
@@ -184,20 +166,20 @@ int uvrt_gather_indirect_rays(uvrt_ctx* c, const uvrt_indirect_params* prm, int3
     if (int rc = begin_closest_launch(c)) return rc;
     if (int rc = ensure_gather_tris(c)) return rc;
     const int32_t S = prm->samples;
-    const int32_t per_chunk = (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX);
+    const int32_t per_chunk = tris_per_chunk(c, S);
     DevBuf out;                                     // one chunk of 32-byte records
     if (int rc = out.ensure((size_t)std::min<int64_t>(per_chunk, std::max(tri_count, 1)) * S * 32, false, c->stream)) return rc;
     IndirectGenParams g = indirect_gen_params(c, prm);
-    for (int32_t done = 0; done < tri_count; done += per_chunk) {
-        const int32_t cnt = std::min(per_chunk, tri_count - done);
+    const int rc = for_tri_chunks(c, S, tri_count, [&](int32_t done, int32_t cnt) -> int {
         const int64_t n = (int64_t)cnt * S;
         g.first_tri = first_tri + done;
         g.tri_count = cnt;
         launch_indirect_generate(g, c->stream);
         launch_export_closest_rays(g.rays, g.oxz, g.tmax, out.p, n, c->stream);
         HIP_TRY(hipGetLastError());
-        if (int rc = copy_sync(c, (char*)rays32_out + (size_t)done * S * 32, out.p, (size_t)n * 32, hipMemcpyDeviceToHost)) return rc;
-    }
+        return copy_sync(c, (char*)rays32_out + (size_t)done * S * 32, out.p, (size_t)n * 32, hipMemcpyDeviceToHost);
+    });
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return UVRT_OK;
 }

@@ -32,10 +32,8 @@ int uvrt_indirect_links_build(uvrt_ctx* c, const uvrt_links_params* prm)
     st.links = fresh.as<int32_t>();
     st.samples = S;
     st.T = c->T;
-    // uvrt_gather_indirect's chunks: floor(capacity / S) triangles, generate -> the closest-hit kernel, then the store
-    const int32_t per_chunk = (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX);
-    for (int32_t done = 0; done < c->T; done += per_chunk) {
-        const int32_t cnt = std::min(per_chunk, c->T - done);
+    // uvrt_gather_indirect's chunks: generate -> the closest-hit kernel, then the store
+    const int rc = for_tri_chunks(c, S, c->T, [&](int32_t done, int32_t cnt) -> int {
         g.first_tri = st.first_tri = done;
         g.tri_count = st.tri_count = cnt;
         launch_indirect_generate(g, c->stream);
@@ -43,7 +41,9 @@ int uvrt_indirect_links_build(uvrt_ctx* c, const uvrt_links_params* prm)
         if (int rc = trace_closest_rays(c, (int64_t)cnt * S, who)) return rc;
         launch_links_store(st, c->stream);
         HIP_TRY(hipGetLastError());
-    }
+        return UVRT_OK;
+    });
+    if (rc) return rc;
     c->derived.links = std::move(fresh);            // (freeing the earlier ones waits for the device)
     c->derived.links_samples = S;
     c->derived.links_seed = prm->seed;

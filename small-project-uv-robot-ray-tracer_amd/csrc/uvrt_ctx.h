@@ -606,6 +606,37 @@ int ensure_source(uvrt_ctx* c);
 // the scene's free records, every ray's {orig.x, orig.z}, tmax and answer byte; the gather's triangles by original id
 int begin_shadow_launch(uvrt_ctx* c);
 int ensure_gather_tris(uvrt_ctx* c);
+// n rays of the ABI (dist = tmax) into lane 0's rays, g_oxz and g_tmax: unpacked, then `begin` (begin_shadow_launch or
+// begin_closest_launch), then the three uploads on the context's stream
+int upload_query_rays(uvrt_ctx* c, const void* rays32, int64_t n, int (*begin)(uvrt_ctx*));
+// The arguments of a query launch (an OccludeParams or a ClosestParams) over the first n rays of lane 0 (rays, g_oxz,
+// g_tmax) on the context's stream; the caller adds where the answers go
+template <class QueryParams>
+inline void fill_query_launch(uvrt_ctx* c, QueryParams& q, int64_t n)
+{
+    Lane& L = c->lanes[0];
+    fill_launch(c, q.e, 0.0f, 0.0f);        // (force_exact: the scene's and the variant's conditions; the origins are per ray)
+    q.e.ovf_stack = L.ovf.as<uint32_t>();   // lane 0's, like its rays: this launch runs on the context's stream
+    q.e.ovf_capacity = L.ovf.bytes / sizeof(uint32_t);
+    q.e.num_cus = c->num_cus;
+    q.e.rays = L.rays.as<float4>();
+    q.oxz = c->g_oxz.as<float2>();
+    q.tmax = c->g_tmax.as<float>();
+    q.e.n = n;
+    q.e.recs = c->derived.free_recs.p;
+}
+// A gather's triangles in chunks of floor(capacity / S): a triangle's S samples never straddle two of them, so the chunking
+// shows in no bit.  each(done, cnt) works on the cnt triangles behind the first `done` and returns a status; the first that
+// is not UVRT_OK ends the walk and is returned.
+inline int32_t tris_per_chunk(const uvrt_ctx* c, int32_t S) { return (int32_t)std::min<int64_t>(c->capacity / S, INT32_MAX); }
+template <class Each>
+inline int for_tri_chunks(const uvrt_ctx* c, int32_t S, int32_t tri_count, Each&& each)
+{
+    const int32_t per_chunk = tris_per_chunk(c, S);
+    for (int32_t done = 0; done < tri_count; done += per_chunk)
+        if (int rc = each(done, std::min(per_chunk, tri_count - done))) return rc;
+    return UVRT_OK;
+}
 // what the one-bounce gather and the link build share (uvrt_capi_indirect.hip): begin_shadow_launch plus the hit records;
 // the argument check (`who` names the call in the message); the generate kernel's arguments; k_closest_free over the first
 // n rays of lane 0 (rays, g_oxz, g_tmax -> g_hit) on the context's stream

@@ -440,6 +440,17 @@ struct OccludeParams {
     uint8_t* occluded;       // [n]
 };
 bool launch_occlude_free(const OccludeParams& p, int grid_per_cu, hipStream_t s);
+// n = cross(e1, e2) in f64 and its length: the one expression of the gather, refine, bounce and link kernels (each is built
+// without contraction, every operator is one rounding)
+__device__ __forceinline__ double tri_normal(const float4 e1, const float4 e2, double& nx, double& ny, double& nz)
+{
+    const double ax = (double)e1.x, ay = (double)e1.y, az = (double)e1.z;
+    const double bx = (double)e2.x, by = (double)e2.y, bz = (double)e2.z;
+    nx = ay * bz - az * by;
+    ny = az * bx - ax * bz;
+    nz = ax * by - ay * bx;
+    return sqrt(nx * nx + ny * ny + nz * nz);
+}
 // the triangles by ORIGINAL id, 3 x float4 each: v0, e1 = v1 - v0, e2 = v2 - v0 (the leaf records' own values, scattered by
 // their id; a triangle no leaf holds stays zero: no area, no estimate)
 void launch_gather_tris(const LeafTri* ltris, float4* gtris, int32_t T, hipStream_t s);

@@ -33,7 +33,7 @@
 // fails (a NaN or infinite origin component fails the range test too) takes the exact step, IEEE divisions as the reference
 // writes them.  The launch-uniform conditions stay what they were: scene_force_exact and variants 500-599 put every ray on
 // the exact step.
-#include "uvrt_traverse.h"
+#include "uvrt_query.h"
 
 namespace uvrt {
 
@@ -132,12 +132,8 @@ void launch_prepare_free_records(const PairRec* pairs, const LeafTri* ltris, voi
 static bool dispatch_extend_free(FreeParams& fp, bool planes, int grid_per_cu, hipStream_t s)
 {
     ExtendParams& p = fp.e;
-    if (p.flavour != 0 && p.flavour != 1) return false;
-    p.order = nullptr;                      // gid order
-    const unsigned grid = size_persistent_grid(p, grid_per_cu < FREE_GRID_PER_CU ? grid_per_cu : FREE_GRID_PER_CU);
+    const unsigned grid = prepare_free_launch(p, grid_per_cu);
     if (grid == 0) return false;
-    p.root_ref6 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
-                      ? p.scene.root_ref + (uint32_t)p.npairs : p.scene.root_ref;
 #define UVRT_LFK(REC, PL)                                                                                              \
     do {                                                                                                               \
         if (p.flavour == 1) hipLaunchKernelGGL((k_extend_free<REC, 1, PL>), dim3(grid), dim3(256), 0, s, fp);           \

@@ -16,15 +16,11 @@
 
 namespace uvrt {
 
-// |cross(e1, e2)| in f64: uvrt_indirect.hip's tri_normal2, the same expression
+// |cross(e1, e2)| in f64, where the normal itself is not asked for
 __device__ __forceinline__ double tri_normal_len(const float4 e1, const float4 e2)
 {
-    const double ax = (double)e1.x, ay = (double)e1.y, az = (double)e1.z;
-    const double bx = (double)e2.x, by = (double)e2.y, bz = (double)e2.z;
-    const double nx = ay * bz - az * by;
-    const double ny = az * bx - ax * bz;
-    const double nz = ax * by - ay * bx;
-    return sqrt(nx * nx + ny * ny + nz * nz);
+    double nx, ny, nz;
+    return tri_normal(e1, e2, nx, ny, nz);
 }
 
 // thread i = (sample s, local triangle lt), lt fastest: the stores are contiguous, the 8-byte reads S2 * 8 bytes apart

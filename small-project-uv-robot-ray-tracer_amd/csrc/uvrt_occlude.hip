@@ -1,17 +1,9 @@
 // uvrt_occlude.hip -- shadow rays (an occlusion query: a ray with a maximum distance that stops at its first hit) and the
 // per-triangle direct gather built on them (include/uvrt.h "shadow rays and the direct gather").
 //
-// k_occlude_free is k_extend_free's persistent-wave traversal (uvrt_extend_free.hip): the lane type LaneF, step6 / step7 of
-// uvrt_traverse.h called unchanged, the same LDS top cache, stack and overflow rows, the same rule for the exact step.  Three
-// things differ:
-//  (a) a refill starts a lane with dist = the ray's tmax (a third per-ray array; the lane keeps it in one register);
-//  (b) after every step a lane whose dist bits differ from its tmax bits is finished: some triangle was accepted, which is
-//      all the query asks.  Bit patterns, not floats: a NaN tmax never compares below anything, so it means "never occluded";
-//  (c) retiring writes one byte per ray slot, occluded[slot] = dist bits != tmax bits, and deposits nothing.
-// That is what extend.cl computes when ray->dist is preset to tmax (extend.cl:25 accepts t only below dist, :36-38 culls
-// boxes beyond it): stopping at the FIRST accepted hit cannot change the boolean, the visit order up to it is the same.
-// The refill is this kernel's own (refill_occluder): refill_lane of uvrt_traverse.h stays as it is for the kernels that
-// deposit, whose code must not move.
+// k_occlude_free is uvrt_query.h's traversal with FIRST_HIT -- after every step a lane whose dist bits differ from its tmax
+// bits is finished: some triangle was accepted, which is all the query asks -- and an answer of one byte per ray slot,
+// occluded[slot] = dist bits != tmax bits.
 //
 // The gather: k_gather_generate makes, for every (triangle, sample), a point on the triangle, a point on the lamp's rod (or
 // on the rod swept along a segment), the ray between them and the sample's weight; k_occlude_free answers which samples see
@@ -19,136 +11,28 @@
 // of the arguments.  With the context's variance state on (uvrt_set_gather_variance) k_gather_reduce_var<MODE> takes
 // k_gather_reduce's place: the same expected[t], and beside it the variance of that estimate from a second pass over the same
 // samples.  This file is built without contraction, every operator below is one rounding.
-#include "uvrt_traverse.h"
+#include "uvrt_query.h"
 
 namespace uvrt {
 
-constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
-
 // the answer of the ray a lane has finished
-__device__ __forceinline__ void retire_occluder(const LaneF& L, const OccludeParams& op, float tmax, uint32_t slot)
-{
-    if (slot != NO_SLOT) op.occluded[slot] = __float_as_uint(L.po.y) != __float_as_uint(tmax) ? 1 : 0;
-}
-
-// refill_lane (uvrt_traverse.h) for a launch without planes, hit records or deposits: the lane starts at dist = tmax
-template <int FL>
-__device__ __forceinline__ void refill_occluder(LaneF& L, const OccludeParams& op, float& tmax, uint32_t& special, uint32_t& slot,
-                                                unsigned long long idle_mask, uint32_t cursor, uint32_t wave, uint32_t W,
-                                                uint32_t root)
-{
-    const ExtendParams& p = op.e;
-    retire_occluder(L, op, tmax, slot);
-    slot = NO_SLOT;
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_mask, 0u));
-    const uint32_t v = cursor + rank;
-    const uint32_t gb = (v >> 6) * W + wave;                 // global 64-slot batch
-    const uint32_t my = gb * 64u + (v & 63u);
-    if (v < p.chunk && my < (uint32_t)p.n) {
-        const float4 rec = p.rays[my];
-        const float2 o = op.oxz[my];
-        const float tm = op.tmax[my];
-        set_in_place(L.px, rec.x, rcp_exact(rec.x));
-        set_in_place(L.py, rec.y, rcp_exact(rec.y));
-        set_in_place(L.pz, rec.z, rcp_exact(rec.z));
-        set_in_place(L.po, rec.w, tm);
-        set_in_place(L.oxz, o.x, o.y);
-        set_in_place(tmax, tm);
-        set_in_place(L.triID, 0u);
-        set_in_place(slot, my);
-        set_in_place(L.sp, 0);
-        set_in_place(L.cur, root);
-        const bool outside = outside_proof_conditions(rec) || origin_outside_window(o.x) || origin_outside_window(o.y);
-        set_in_place(special, (outside || p.force_exact != 0) ? SPECIAL6 : 0u);
+struct OccludedAnswer {
+    const OccludeParams& op;
+    __device__ __forceinline__ void operator()(const LaneF& L, float tmax, uint32_t slot) const
+    {
+        if (slot != NO_SLOT) op.occluded[slot] = __float_as_uint(L.po.y) != __float_as_uint(tmax) ? 1 : 0;
     }
-}
+};
 
 template <int FL>
 __global__ __launch_bounds__(256, FREE_GRID_PER_CU) void k_occlude_free(OccludeParams op)
 {
-    static_assert(FL == 0 || FL == 1, "shadow rays: flavours 0 and 1");
-    const ExtendParams& p = op.e;
-    __shared__ __attribute__((aligned(1024))) uint32_t s_stack[PS6 + 1][256];   // row 0 always holds REF_DONE ("entry -1")
-    __shared__ float4 s_top[(TOP6_MAX + 1) * (TOP6_STRIDE / 16)];
-    const uint32_t top_pairs = p.top_pairs < TOP6_MAX ? p.top_pairs : TOP6_MAX;
-    {
-        const float4* src = (const float4*)p.recs;
-        for (uint32_t i = threadIdx.x; i < top_pairs * 4u; i += 256u) s_top[i] = src[i];
-    }
-    s_stack[0][threadIdx.x] = REF_DONE;
-    __syncthreads();
-    const uint32_t stack_base = (uint32_t)(uintptr_t)&s_stack[0][threadIdx.x];
-    LaneF L;
-    L.px = L.py = L.pz = (v2f){1.f, 1.f};
-    L.po = (v2f){0.f, 1e30f};
-    L.oxz = (v2f){0.f, 0.f};
-    L.triID = 0;
-    L.cur = REF_DONE;
-    L.sp = 0;
-    float tmax = 1e30f;             // the bits of dist: a lane without a ray never looks finished by a hit
-    uint32_t slot = NO_SLOT;
-    uint32_t special = 0;           // bit 31: the lane's ray needs the exact step
-    const uint32_t wave = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t W = gridDim.x * 4u;
-    uint32_t cursor = 0;
-    const uint32_t chunk_end = p.chunk;
-    unsigned long long km = ~0ull;          // all ones in a trip that visits leaves (every second one)
-    unsigned long long full;
-    asm volatile("s_mov_b64 %0, exec" : "=s"(full));
-    const uint32_t top_base = (uint32_t)(uintptr_t)s_top;
-    int refill_at = p.refill_min;           // idle lanes that trigger a refill; 64 once the wave's share is handed out
-
-    for (;;) {
-        const unsigned long long special_mask = __builtin_amdgcn_ballot_w64((int32_t)special < 0);
-        const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(L.cur == REF_DONE);
-        const int nidle = __popcll(idle_mask);
-        if (nidle >= refill_at) {
-            if (cursor < chunk_end) {
-                if (L.cur == REF_DONE) refill_occluder<FL>(L, op, tmax, special, slot, idle_mask, cursor, wave, W, p.root_ref6);
-                cursor += (uint32_t)nidle;
-                if (cursor >= chunk_end) refill_at = 64;
-            }
-            if (__builtin_amdgcn_ballot_w64(L.cur != REF_DONE) == 0) {
-                if (cursor >= chunk_end) break;
-                continue;
-            }
-        }
-        const unsigned long long m_in = __builtin_amdgcn_ballot_w64((int32_t)L.cur >= 0);
-        const unsigned long long m_lf = __builtin_amdgcn_ballot_w64((int32_t)L.cur < -1);
-        const unsigned long long m_top = __builtin_amdgcn_ballot_w64(L.cur < top_pairs);
-        const unsigned long long m_deep = __builtin_amdgcn_ballot_w64(L.sp >= PS6);
-        // leaves are visited in every second trip, and in any trip that has no lane at an inner node
-        const unsigned long long kme = m_in == 0 ? ~0ull : km;
-        km = ~km;
-        if ((special_mask | m_deep) != 0)
-            step6<true, FL>(L, p, stack_base, s_top, top_pairs, kme != 0, (special_mask & (m_in | m_lf)) != 0, m_in | m_lf);
-        else
-            step7<true, FL>(L, p, stack_base, top_base, m_in, m_lf & kme, m_top, full);
-        // (b): an accepted hit ends the ray -- whatever is left on its stack cannot change the answer
-        if (__float_as_uint(L.po.y) != __float_as_uint(tmax)) {
-            L.cur = REF_DONE;
-            L.sp = 0;
-        }
-    }
-    retire_occluder(L, op, tmax, slot);
+    run_query_rays<FL, true>(op.e, op.oxz, op.tmax, OccludedAnswer{op});
 }
 
-bool launch_occlude_free(const OccludeParams& p0, int grid_per_cu, hipStream_t s)
+bool launch_occlude_free(const OccludeParams& p, int grid_per_cu, hipStream_t s)
 {
-    if (p0.e.n <= 0) return true;
-    OccludeParams op = p0;
-    ExtendParams& p = op.e;
-    if (p.flavour != 0 && p.flavour != 1) return false;
-    p.order = nullptr;
-    p.hits = nullptr;
-    p.plane_batches = 0;                    // one launch, one plane
-    const unsigned grid = size_persistent_grid(p, grid_per_cu < FREE_GRID_PER_CU ? grid_per_cu : FREE_GRID_PER_CU);
-    if (grid == 0) return false;
-    p.root_ref6 = (p.scene.root_ref >= REF_LEAF_BIT && p.scene.root_ref != REF_DONE)
-                      ? p.scene.root_ref + (uint32_t)p.npairs : p.scene.root_ref;
-    if (p.flavour == 1) hipLaunchKernelGGL((k_occlude_free<1>), dim3(grid), dim3(256), 0, s, op);
-    else hipLaunchKernelGGL((k_occlude_free<0>), dim3(grid), dim3(256), 0, s, op);
-    return true;
+    return launch_query_free(p, k_occlude_free<0>, k_occlude_free<1>, grid_per_cu, s);
 }
 
 // ---- the direct gather ----
@@ -169,17 +53,6 @@ void launch_gather_tris(const LeafTri* ltris, float4* gtris, int32_t T, hipStrea
 {
     if (T <= 0) return;
     hipLaunchKernelGGL(k_gather_tris, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, ltris, gtris, T);
-}
-
-// n = cross(e1, e2) in f64 and its length
-__device__ __forceinline__ double tri_normal(const float4 e1, const float4 e2, double& nx, double& ny, double& nz)
-{
-    const double ax = (double)e1.x, ay = (double)e1.y, az = (double)e1.z;
-    const double bx = (double)e2.x, by = (double)e2.y, bz = (double)e2.z;
-    nx = ay * bz - az * by;
-    ny = az * bx - ax * bz;
-    nz = ax * by - ay * bx;
-    return sqrt(nx * nx + ny * ny + nz * nz);
 }
 
 // MODE: the context's gather sampling (include/uvrt.h uvrt_set_gather_sampling).  0 is the independent rule; 1 puts sample s

@@ -6,29 +6,19 @@
 // (k_refine_block_sums, k_refine_scan_sums, k_refine_offsets) gives every triangle's first ray; the host reads the offsets
 // once and cuts the range into chunks of at most `capacity` rays.  Per chunk k_refine_generate<MODE> makes the rays -- one
 // thread per ray, its triangle found by a search in the offsets, then k_gather_generate's rule with S := n_t --,
-// k_occlude_free (uvrt_occlude.hip, as it is) answers them and k_refine_reduce<MODE> forms X1, V1 of every refined triangle as
+// k_occlude_free (uvrt_occlude.hip) answers them and k_refine_reduce<MODE> forms X1, V1 of every refined triangle as
 // k_gather_reduce_var<MODE> would at S = n_t and merges them into the planes.  No atomics and sums in sample order: the planes
 // are a pure function of what they held and the arguments.
 //
-// The generate and reduce rules are restated here, not shared with uvrt_occlude.hip: that file's kernels stay instruction for
-// instruction what they were.  This file is built without contraction, every operator below is one rounding.
+// The generate and reduce rules follow k_gather_generate and k_gather_reduce_var (uvrt_occlude.hip) with S := n_t and a merge at
+// the end; the triangle normal is the shared tri_normal (uvrt_device.h).  This file is built without contraction, every operator
+// below is one rounding.
 #include "uvrt_device.h"
 
 namespace uvrt {
 
 constexpr int SCAN_PER_THREAD = 4;
 constexpr int SCAN_PER_BLOCK = 256 * SCAN_PER_THREAD;
-
-// n = cross(e1, e2) in f64 and its length (uvrt_occlude.hip tri_normal)
-__device__ __forceinline__ double refine_normal(const float4 e1, const float4 e2, double& nx, double& ny, double& nz)
-{
-    const double ax = (double)e1.x, ay = (double)e1.y, az = (double)e1.z;
-    const double bx = (double)e2.x, by = (double)e2.y, bz = (double)e2.z;
-    nx = ay * bz - az * by;
-    ny = az * bx - ax * bz;
-    nz = ax * by - ay * bx;
-    return sqrt(nx * nx + ny * ny + nz * nz);
-}
 
 // The count rule (include/uvrt.h): how many extra samples bring sqrt(variance) / expected down to rel_error, if the extra
 // samples scatter like the first S0 did; a power of two in [2, max_extra], or 0.
@@ -42,7 +32,7 @@ __global__ __launch_bounds__(256) void k_refine_count(const float4* __restrict__
     int32_t n = 0;
     if (t >= first_tri && t - first_tri < tri_count) {
         double nx, ny, nz;
-        const double nn = refine_normal(gtris[(size_t)t * 3 + 1], gtris[(size_t)t * 3 + 2], nx, ny, nz);
+        const double nn = tri_normal(gtris[(size_t)t * 3 + 1], gtris[(size_t)t * 3 + 2], nx, ny, nz);
         const double X0 = expected[t], V0 = variance[t];
         if (!(nn == 0.0) && X0 > 0.0 && V0 > 0.0 && !(X0 < min_expected)) {
             const double r = rel_error * X0;
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(256) void k_refine_generate(GatherGenParams g, cons
     const float dx = px - ox, dy = py - oy, dz = pz - oz;
     const float r = sqrtf((dx * dx + dy * dy) + dz * dz);
     double nx, ny, nz;
-    const double nn = refine_normal(e1, e2, nx, ny, nz);
+    const double nn = tri_normal(e1, e2, nx, ny, nz);
     const double Dx = (double)dx, Dy = (double)dy, Dz = (double)dz;
     const double R2 = Dx * Dx + Dy * Dy + Dz * Dz;
     const double R = sqrt(R2);
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(256) void k_refine_reduce(const float4* __restrict_
     if (samples == 0) return;                                  // every bit of both planes stays
     const size_t t = (size_t)first_tri + (size_t)i;
     double nx, ny, nz;
-    const double nn = refine_normal(gtris[t * 3 + 1], gtris[t * 3 + 2], nx, ny, nz);
+    const double nn = tri_normal(gtris[t * 3 + 1], gtris[t * 3 + 2], nx, ny, nz);
     double sum = 0.0;
     const size_t at = (size_t)(offs[i] - offs[lo]);
     for (int32_t s = 0; s < samples; ++s) sum = sum + (occluded[at + s] ? 0.0 : w[at + s]);

@@ -60,13 +60,11 @@ def test_tmax_boundaries(pkg, orc, oscene, uniform):
         rays, hit = rays[:16384], hit[:16384]
         is_hit = hit != MISS
         assert 0.3 * hit.size < is_hit.sum() < hit.size
-        up = np.nextafter(hit, f32(np.inf)).astype(np.float32)
-        small = np.resize(np.array([1e-4, 0.0, -0.0, -1.0, 5e-5, 1e-38, -1e30], dtype=np.float32), hit.size)
-        nan = np.full(hit.size, np.nan, dtype=np.float32)
+        tm = sr.boundary_tmax(hit)
         none = lambda tm: (lambda d, t: np.all(t == -1) and np.array_equal(gr.bits(d), gr.bits(tm)))
         found = lambda d, t: np.array_equal(t >= 0, is_hit) and np.array_equal(gr.bits(d[is_hit]), gr.bits(hit[is_hit]))
-        cases = [("exact", hit, none(hit)), ("nextafter", up, found), ("small", small, none(small)), ("nan", nan, none(nan)),
-                 ("1e30", np.full(hit.size, MISS), found)]
+        cases = [("exact", tm["exact"], none(tm["exact"])), ("nextafter", tm["nextafter"], found),
+                 ("small", tm["small"], none(tm["small"])), ("nan", tm["nan"], none(tm["nan"])), ("1e30", tm["1e30"], found)]
         c = sr.new_ctx(pkg, oscene, hit.size)
         c.set_flavour(fl)
         for name, tmax, holds in cases:
@@ -76,6 +74,28 @@ def test_tmax_boundaries(pkg, orc, oscene, uniform):
             assert holds(*want), "oracle, flavour %d %s" % (fl, name)
             assert same(got, want), "flavour %d %s" % (fl, name)
         c.close()
+
+
+def test_occluded_is_a_closest_hit(pkg, oscene, uniform):
+    """k_occlude_free and k_closest_free are one traversal (csrc/uvrt_query.h): over 4096 uniform rays and the rays of
+    test_tmax_boundaries (tmax NaN, 0 and the exact hit distance among them), occluded[i] == (tri[i] != -1) for every ray,
+    GPU against GPU.  Exact: both answers come from testing the ray's final dist bits against its tmax bits.  The oracle's
+    answer for the uniform rays holds both outcomes, so the equality is not a row of zeros."""
+    for fl in (0, 1):
+        rays, hit, want, _ = uniform[fl]
+        accepted = want[1][:4096] >= 0
+        assert 0.1 * 4096 < accepted.sum() < 0.9 * 4096, "flavour %d: the oracle must see both outcomes" % fl
+        edge = [sr.with_tmax(rays[:16384], tm) for tm in sr.boundary_tmax(hit[:16384]).values()]
+        r = np.concatenate([rays[:4096]] + edge)
+        c = sr.new_ctx(pkg, oscene, r.size)
+        c.set_flavour(fl)
+        occ = c.occluded(r)
+        tri = c.closest_hits(r)[1]
+        c.sync()
+        c.close()
+        assert np.array_equal(occ[:4096] != 0, accepted), "flavour %d: the uniform rays against the oracle" % fl
+        bad = (occ != 0) != (tri != -1)
+        assert not bad.any(), "flavour %d: %d of %d rays, first %d" % (fl, int(bad.sum()), r.size, int(np.argmax(bad)))
 
 
 def test_adversarial_rays_equal_the_oracle(pkg, orc, oscene):

@@ -11,8 +11,9 @@ pytestmark = pytest.mark.gpu
 f32 = np.float32
 MISS = f32(1e30)
 # 98 299 rays: at 65 521 the unoccluded rays of seed 23 stop at 8 stack entries, the LDS rows; here they reach 10.  The
-# other counts are prefixes of the same rays.
-COUNTS = (98299, 65521, 1, 63, 64, 65, 4099)
+# other counts are prefixes of the same rays: a wave with one live lane, a full 64-ray batch less one, the batch, the batch
+# plus one lane, one ray in a second workgroup's share, and an odd count over many workgroups.
+COUNTS = (98299, 65521, 1, 63, 64, 65, 257, 4099)
 
 
 def unit_dirs(rng, n):
@@ -59,6 +60,15 @@ def scaled_tmax(hit, rng):
     """closest-hit distance x U(0.5, 1.5), 1e30f for a miss"""
     t = (hit * rng.uniform(0.5, 1.5, size=hit.size).astype(np.float32)).astype(np.float32)
     return np.where(hit == MISS, MISS, t).astype(np.float32)
+
+
+def boundary_tmax(hit):
+    """the tmax arrays of test_tmax_boundaries by name, for rays whose closest-hit distances are `hit`"""
+    return {"exact": hit,
+            "nextafter": np.nextafter(hit, f32(np.inf)).astype(np.float32),
+            "small": np.resize(np.array([1e-4, 0.0, -0.0, -1.0, 5e-5, 1e-38, -1e30], dtype=np.float32), hit.size),
+            "nan": np.full(hit.size, np.nan, dtype=np.float32),
+            "1e30": np.full(hit.size, MISS)}
 
 
 def uniform_shadow_rays(orc, oscene, n, seed, flavour):
@@ -169,13 +179,12 @@ def test_tmax_boundaries(pkg, orc, oscene, uniform):
         rays, hit = rays[:16384], hit[:16384]
         is_hit = hit != MISS
         assert 0.3 * hit.size < is_hit.sum() < hit.size
-        up = np.nextafter(hit, f32(np.inf)).astype(np.float32)
-        small = np.resize(np.array([1e-4, 0.0, -0.0, -1.0, 5e-5, 1e-38, -1e30], dtype=np.float32), hit.size)
-        cases = [("exact", hit, lambda g: not g.any()),
-                 ("nextafter", up, lambda g: g[is_hit].all() and not g[~is_hit].any()),
-                 ("small", small, lambda g: not g.any()),
-                 ("nan", np.full(hit.size, np.nan, dtype=np.float32), lambda g: not g.any()),
-                 ("1e30", np.full(hit.size, MISS), lambda g: np.array_equal(g != 0, is_hit))]
+        tm = boundary_tmax(hit)
+        cases = [("exact", tm["exact"], lambda g: not g.any()),
+                 ("nextafter", tm["nextafter"], lambda g: g[is_hit].all() and not g[~is_hit].any()),
+                 ("small", tm["small"], lambda g: not g.any()),
+                 ("nan", tm["nan"], lambda g: not g.any()),
+                 ("1e30", tm["1e30"], lambda g: np.array_equal(g != 0, is_hit))]
         c = new_ctx(pkg, oscene, hit.size)
         c.set_flavour(fl)
         for name, tmax, holds in cases:
