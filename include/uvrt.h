@@ -301,6 +301,44 @@ int uvrt_read_gather_extra(uvrt_ctx* ctx, int32_t* out, int32_t first, int32_t c
 int uvrt_refine_counts(uvrt_ctx* ctx, int32_t samples0, const uvrt_refine_params* params, int32_t first_tri, int32_t tri_count,
                        int32_t* offsets_out /* tri_count + 1 */);
 
+/* ---- batched direct gather: one shadow-ray pass for several launches ----
+ * A gather launch on a room of 45 k triangles is a launch tail, not a traversal: at S = 16 it holds little more than one ray
+ * per lane of the persistent query grid.  uvrt_gather_direct_batch traces `count` launches over one triangle range in one
+ * pass and keeps their planes; uvrt_gather_batch_select then puts launch k's where uvrt_gather_direct would
+ * have left them.  Every bit equals what the launch-by-launch calls give.
+ *
+ * uvrt_gather_direct_batch: count in [1, UVRT_GATHER_BATCH_MAX]; every launch is checked as uvrt_gather_direct checks it
+ * (flavour 0 / 1, a scene, the range, S in [1, 4096], S <= capacity, T*S < 2^31, photons_equiv > 0, S >= 2 with the variance
+ * state on), and all launches share one `samples`; from, to (stops and sweeps mix), light_length, seed and photons_equiv may
+ * differ.  A refusal is UVRT_ERR_INVALID with nothing changed: an earlier batch is kept.  A call that passes drops the earlier
+ * batch, records the context's sampling mode, variance state and flavour as they are now and makes E_b, f64[count][T] (and
+ * V_b, the same shape, when the variance state is on): E_b[k][t] is the plane uvrt_gather_direct(&launches[k], first_tri,
+ * tri_count) would leave in `expected`, V_b[k][t] in `variance`; entries outside the range are 0; tri_count = 0 is a valid empty
+ * batch.  The unit of work is the pair q = k * tri_count + lt, launch-major; pairs go in chunks of floor(capacity / S) through
+ * lane 0's ray buffers (a chunk may straddle a launch boundary), per chunk generate -> the shadow-ray kernel -> reduce, with the
+ * sample rule and the sample-order sums above and no atomics: a pure function of the arguments and the recorded state,
+ * whatever the capacity.  It runs on the context's stream behind all outstanding launches and, like every shadow-ray call,
+ * drops "the last generate"; it leaves SEED, tempPhotonMap, expected, variance, source, the links and the remembered gather of
+ * uvrt_gather_refine untouched.
+ *
+ * uvrt_gather_batch_select(k): expected[range] = E_b[k][range] -- and variance[range] = V_b[k][range] when the batch has a
+ * variance plane, else that plane is not touched --, device to device on the stream; entries outside the range keep their bits.
+ * The remembered gather becomes launch k's under the recorded mode when the batch has a variance plane, and is forgotten
+ * otherwise: the context is as uvrt_gather_direct(&launches[k], ..) would have left it under the recorded state, so refine, both
+ * bounces, uvrt_plan_capture_expected and uvrt_accumulate_expected follow unchanged.  Any k, in any order, repeatedly.
+ * UVRT_ERR_INVALID with nothing changed: no batch, k outside [0, count).
+ * A batch survives every call but uvrt_set_scene, the next successful uvrt_gather_direct_batch and uvrt_destroy (the refine and
+ * the bounces trace through lane 0's ray buffers, not the batch's planes). */
+enum { UVRT_GATHER_BATCH_MAX = 64 };
+/* E_b[k][t], k < count: the plane uvrt_gather_direct(&launches[k], first_tri, tri_count) would leave in `expected`
+ * (and V_b[k][t] its variance plane when uvrt_set_gather_variance is on), all traced in one pass */
+int uvrt_gather_direct_batch(uvrt_ctx* ctx, const uvrt_gather_params* launches, int32_t count,
+                             int32_t first_tri, int32_t tri_count);
+int uvrt_gather_batch_select(uvrt_ctx* ctx, int32_t k);
+int uvrt_gather_batch_info(uvrt_ctx* ctx, int32_t out4[4]);   /* {count (0: no batch), samples, first_tri, tri_count} */
+/* test hook: which = 0 expected, 1 variance (UVRT_ERR_INVALID for a batch without one); any range of [0, T); synchronises */
+int uvrt_read_gather_batch(uvrt_ctx* ctx, int32_t k, int32_t which, double* out, int32_t first, int32_t count);
+
 /* ---- one diffuse bounce: a closest-hit query and a final gather over a per-triangle source plane ----
  * The direct gather sees the lamp alone; light that arrives by reflection it cannot see.  uvrt_gather_indirect adds one
  * bounce as a final gather: from points on triangle t it shoots cosine-distributed rays, finds the closest hit and looks up

@@ -136,6 +136,10 @@ SYMBOLS = [
     ("uvrt_gather_refine", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     ("uvrt_read_gather_extra", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_refine_counts", C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    ("uvrt_gather_direct_batch", C.c_int, [_vp, _vp, _i32, _i32, _i32]),
+    ("uvrt_gather_batch_select", C.c_int, [_vp, _i32]),
+    ("uvrt_gather_batch_info", C.c_int, [_vp, _vp]),
+    ("uvrt_read_gather_batch", C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32]),
     ("uvrt_closest_hits", C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     ("uvrt_indirect_source_from_expected", C.c_int, [_vp]),
     ("uvrt_read_indirect_source", C.c_int, [_vp, _vp, _i32, _i32]),
@@ -607,6 +611,39 @@ class Ctx:
         tri_count = self.T - int(first_tri) if tri_count is None else int(tri_count)
         out = np.full(max(tri_count, 0) + 1, -1, dtype=np.int32)
         self._ck(self._L.uvrt_refine_counts(self._h, int(samples0), C.byref(prm), int(first_tri), tri_count, _ptr(out)))
+        return out
+
+    # ---- the batched direct gather ----
+    def gather_direct_batch(self, launches, first_tri=0, tri_count=None):
+        """one shadow-ray pass for several gather launches (include/uvrt.h "batched direct gather"): `launches` is a sequence of
+        dicts with gather_direct's frm, to, light_length, samples, seed and photons_equiv; plane k is what gather_direct of
+        launch k would leave in `expected` (and `variance`), read by read_gather_batch, put there by gather_batch_select"""
+        arr = (GatherParams * max(len(launches), 1))()
+        for prm, l in zip(arr, launches):
+            prm.from_ = _f3(l["frm"])
+            prm.to = _f3(l["to"])
+            prm.light_length = float(np.float32(l["light_length"]))
+            prm.samples = int(l["samples"])
+            prm.seed = int(l["seed"])
+            prm.photons_equiv = int(l["photons_equiv"])
+        self._ck(self._L.uvrt_gather_direct_batch(self._h, C.cast(arr, _vp), len(launches), int(first_tri),
+                                                  self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    def gather_batch_select(self, k):
+        """expected (and variance) of the batch's range := launch k's planes; the context as gather_direct of launch k leaves it"""
+        self._ck(self._L.uvrt_gather_batch_select(self._h, int(k)))
+
+    def gather_batch_info(self):
+        """(count, samples, first_tri, tri_count) of the context's batch; count 0: none"""
+        out = np.full(4, -1, dtype=np.int32)
+        self._ck(self._L.uvrt_gather_batch_info(self._h, _ptr(out)))
+        return tuple(int(v) for v in out)
+
+    def read_gather_batch(self, k, which=0, first=0, count=None):
+        """plane k of the batch, float64: which = 0 expected, 1 variance"""
+        count = self.T - first if count is None else count
+        out = np.empty(count, dtype=np.float64)
+        self._ck(self._L.uvrt_read_gather_batch(self._h, int(k), int(which), _ptr(out), int(first), int(count)))
         return out
 
     # ---- closest hits and the one-bounce gather ----

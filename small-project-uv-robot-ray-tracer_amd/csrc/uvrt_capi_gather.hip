@@ -71,7 +71,7 @@ int begin_shadow_launch(uvrt_ctx* c)
 }
 
 // k_occlude_free over the first n rays of lane 0 (rays, oxz, g_tmax -> g_occ) on the context's stream
-static int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who)
+int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who)
 {
     OccludeParams op;
     fill_query_launch(c, op, n);

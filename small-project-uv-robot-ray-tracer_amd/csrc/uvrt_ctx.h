@@ -8,6 +8,7 @@
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
 //                         uvrt_set_gather_variance and the variance plane, uvrt_gather_refine)
+//   uvrt_capi_gather_batch.hip  the batched direct gather (uvrt_gather_direct_batch, uvrt_gather_batch_select)
 //   uvrt_capi_indirect.hip  closest hits and the one-bounce gather (uvrt_closest_hits, uvrt_gather_indirect, the source plane)
 //   uvrt_capi_links.hip   recorded hit links and the multi-bounce gather over them (uvrt_indirect_links_build,
 //                         uvrt_gather_indirect_linked)
@@ -182,7 +183,19 @@ struct uvrt_ctx {
         int32_t links_samples = 0, links_flavour = 0;
         uint32_t links_seed = 0;
         GatherMemo gather_memo;                // a refine works on one scene's planes
+        // the batch of the last successful uvrt_gather_direct_batch (uvrt_capi_gather_batch.hip; count 0: none): its launches,
+        // range and sample count, the sampling mode, variance state and flavour it ran under, and its planes f64[count][T]
+        // (v: with the variance state on)
+        struct GatherBatch {
+            int32_t count = 0, samples = 0, first = 0, tri_count = 0, mode = 0, flavour = 0;
+            bool var = false;
+            std::vector<uvrt_gather_params> launches;
+            DevBuf e, v;
+        } gather_batch;
     } derived;
+    // uvrt_gather_direct_batch's launch table: the host copy the call fills and the device copy it uploads on the stream
+    std::vector<uvrt::GatherBatchLaunch> gb_host;
+    DevBuf gb_table;
 
     // Launch lanes: consecutive launches (generate -> extend -> accumulate ->
     // shade) alternate between the context's stream and an internal side stream, each with its own
@@ -606,6 +619,8 @@ int ensure_source(uvrt_ctx* c);
 // the scene's free records, every ray's {orig.x, orig.z}, tmax and answer byte; the gather's triangles by original id
 int begin_shadow_launch(uvrt_ctx* c);
 int ensure_gather_tris(uvrt_ctx* c);
+// k_occlude_free over the first n rays of lane 0 (rays, g_oxz, g_tmax -> g_occ) on the context's stream; `who` names the call
+int trace_shadow_rays(uvrt_ctx* c, int64_t n, const char* who);
 // n rays of the ABI (dist = tmax) into lane 0's rays, g_oxz and g_tmax: unpacked, then `begin` (begin_shadow_launch or
 // begin_closest_launch), then the three uploads on the context's stream
 int upload_query_rays(uvrt_ctx* c, const void* rays32, int64_t n, int (*begin)(uvrt_ctx*));

@@ -478,6 +478,37 @@ void launch_gather_reduce_var(const float4* gtris, const double* w, const uint8_
 // accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]; the plane is zeroed like tempPhotonMap
 void launch_accumulate_expected(double* photon_map, double* max_map, double* expected, float time_step, int32_t T, hipStream_t s);
 
+// ---- the batched direct gather (uvrt_gather_batch.hip; include/uvrt.h "batched direct gather") ----
+// One launch of a batch as the kernels read it from the device table: 48 bytes, so three 16-byte loads.
+struct alignas(16) GatherBatchLaunch {
+    float fx, fy, fz, tx, ty, tz;
+    float light_length;
+    uint32_t seed;           // the raw seed
+    uint32_t seed_hash;      // WangHash(seed)
+    int32_t photons_equiv;
+    int32_t pad[2];
+};
+// A chunk of a batch: pairs [first_pair, first_pair + pair_count) of the launch-major sequence q = k * tri_count + lt, given as
+// k0 = first_pair / tri_count and lt0 = first_pair % tri_count (host, int64).  Pair p of the chunk is launch
+// k0 + (lt0 + p) / tri_count, triangle first_tri + (lt0 + p) % tri_count; its samples are rays [p * samples, (p + 1) * samples)
+// of the chunk.  pair_count * samples <= capacity, and lt0 + p < 2^32.
+struct GatherBatchParams {
+    const float4* gtris;
+    const GatherBatchLaunch* table;    // [count]
+    float4* rays;            // [pair_count * samples] dir.xyz, orig.y
+    float2* oxz;
+    float* tmax;
+    double* w;
+    const uint8_t* occluded; // the reduce kernels: the chunk's answers
+    double* e_planes;        // f64[count][T]
+    double* v_planes;        // f64[count][T] (the variance reduce)
+    int32_t k0, lt0, pair_count;
+    int32_t first_tri, tri_count, samples, T;
+    int32_t mode;            // which instantiation is launched
+};
+void launch_gather_generate_batch(const GatherBatchParams& p, hipStream_t s);
+void launch_gather_reduce_batch(const GatherBatchParams& p, bool variance, hipStream_t s);
+
 // ---- the adaptive gather (uvrt_refine.hip; include/uvrt.h "adaptive gather") ----
 // extra[t] = n_t of the count rule for t in [first_tri, first_tri + tri_count), 0 for every other t < T
 void launch_refine_count(const float4* gtris, const double* expected, const double* variance, int32_t* extra, int32_t T,

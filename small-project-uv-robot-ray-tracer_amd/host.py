@@ -49,6 +49,7 @@ SYMBOLS = [
     ("uvrt_host_rt_compute_dosage_map", None, [_vp]),
     ("uvrt_host_rt_compute_single", None, [_vp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]),
     ("uvrt_host_rt_compute_segment", None, [_vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int]),
+    ("uvrt_host_rt_compute_segments", None, [_vp]),
     ("uvrt_host_rt_shade", None, [_vp]),
     ("uvrt_host_rt_add_lamp", None, [_vp]),
     ("uvrt_host_rt_calibrate", None, [_vp, C.c_float, C.c_float, C.c_float]),
@@ -80,6 +81,9 @@ SYMBOLS = [
     ("uvrt_host_rt_plan_gather_reflect_linked", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
                                                        C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
                                                        _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_batch", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                              C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                              _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -97,10 +101,10 @@ _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIt
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
            "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling", "gatherRelError",
-           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces"}
+           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces", "gatherBatch"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
                "photonMapSize", "viewMode", "gatherSamples", "gatherSampling", "gatherMaxExtra",
-               "reflectSamples", "reflectBounces"}
+               "reflectSamples", "reflectBounces", "gatherBatch"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 
@@ -226,6 +230,8 @@ class RayTracer:
         if name in _FIELDS:
             if name == "reflectBounces" and not (0 <= int(value) <= 16 and int(value) == value):
                 raise ValueError("reflectBounces must be an integer in [0, 16]")
+            if name == "gatherBatch":
+                _check_gather_batch(value)
             self._L.uvrt_host_rt_set(self._h, name.encode(), float(value))
             if name == "photonCount":
                 self._L.uvrt_host_rt_update_photons_per_light(self._h)
@@ -241,6 +247,9 @@ class RayTracer:
     def ComputeSegmentDosageMap(self, a, b, photonsPerLight, triangleCount):
         """the dose of the drive from position a to position b ((x, z) pairs) at driveSpeed"""
         self._L.uvrt_host_rt_compute_segment(self._h, a[0], a[1], b[0], b[1], int(photonsPerLight), int(triangleCount))
+    def ComputeSegments(self):
+        """the segments of one iteration, in order (nothing at driveSpeed 0)"""
+        self._L.uvrt_host_rt_compute_segments(self._h)
     def Shade(self): self._L.uvrt_host_rt_shade(self._h)
     def ResetDosageMap(self): self._L.uvrt_host_rt_reset_dosage_map(self._h)
     def ClearBuffers(self, resetColor): self._L.uvrt_host_rt_clear_buffers(self._h, int(bool(resetColor)))
@@ -257,6 +266,17 @@ class RayTracer:
     def ComputeIterationsBatched(self, iterations): self._L.uvrt_host_rt_compute_batched(self._h, int(iterations))
     def SetRayRange(self, rank, world): self._L.uvrt_host_rt_set_ray_range(self._h, int(rank), int(world))
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
+
+    @property
+    def gather_batch(self):
+        """RayTracer::gatherBatch = B: with gatherSamples > 0 the launches of ComputeDosageMap / ComputeSegments are traced in
+        groups of up to B (one uvrt_gather_direct_batch each).  0 (default) and 1: launch by launch.  B changes
+        no bit of any result."""
+        return self.gatherBatch
+
+    @gather_batch.setter
+    def gather_batch(self, value):
+        self.gatherBatch = value
 
     def set_gather_refine(self, rel_error, max_extra=64):
         """gatherRelError and gatherMaxExtra in one call: every gather launch is refined (0: off)"""
@@ -276,16 +296,30 @@ class RayTracer:
         is those launches' sampling mode: 0 independent, 1 stratified; it needs gather_samples > 0.
         gather_confidence = z > 0 (PlanOptions::gatherConfidence) plans for the estimate's lower confidence bound, expected -
         z standard errors element by element; it needs gather_samples >= 2 and is meant for 16 and more.
-        0 is the plan without it, bit for bit.  (PlanDurationsRefined is this call with the adaptive gather.)"""
+        0 is the plan without it, bit for bit.  (PlanDurationsRefined is this call with the adaptive gather, PlanDurationsBatched
+        with the plan's gather launches traced in groups.)"""
         return self._plan_durations(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
                                     gather_confidence, 0.0, 64)
+
+    def PlanDurationsBatched(self, gather_batch, **plan):
+        """PlanDurations(**plan) with PlanOptions::gatherBatch = B in [0, 64]: the plan's gather launches are traced in groups of
+        up to B, one shadow-ray pass each.  B > 0 needs gather_samples > 0; it changes no bit of the durations, the
+        report or the captured columns.  0 and 1 are PlanDurations.  (PlanDurationsRefined and PlanDurationsReflect take
+        gather_batch = B among their plan arguments.)"""
+        args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
+                    gather_sampling=0, gather_confidence=0.0)
+        unknown = set(plan) - set(args)
+        if unknown:
+            raise TypeError("PlanDurationsBatched: unknown arguments %s" % sorted(unknown))
+        args.update(plan)
+        return self._plan_durations(gather_rel_error=0.0, gather_max_extra=64, gather_batch=gather_batch, **args)
 
     def PlanDurationsRefined(self, gather_rel_error, gather_max_extra=64, **plan):
         """PlanDurations(**plan) with PlanOptions::gatherRelError = gather_rel_error and gatherMaxExtra = gather_max_extra:
         every gather launch of the plan is refined before its capture.  tau > 0 needs gather_samples >= 2 and
         works with and without gather_confidence; 0 is PlanDurations, bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0)
+                    gather_sampling=0, gather_confidence=0.0, gather_batch=0)
         unknown = set(plan) - set(args)
         if unknown:
             raise TypeError("PlanDurationsRefined: unknown arguments %s" % sorted(unknown))
@@ -300,7 +334,7 @@ class RayTracer:
         reflect_bounces = K in [1, 16] (PlanOptions::reflectBounces): K bounces over hit links recorded once per scene instead of
         the bounce traced per launch; 0 is the traced bounce, bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0)
+                    gather_sampling=0, gather_confidence=0.0, gather_batch=0)
         unknown = set(plan) - set(args)
         if unknown:
             raise TypeError("PlanDurationsReflect: unknown arguments %s" % sorted(unknown))
@@ -321,9 +355,12 @@ class RayTracer:
 
     def _plan_durations(self, min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
                         gather_confidence, gather_rel_error, gather_max_extra, reflectance=0.0, reflect_samples=16,
-                        reflect_bounces=0):
+                        reflect_bounces=0, gather_batch=0):
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
+        B = _check_gather_batch(gather_batch)
+        if B and not gather_samples:
+            raise ValueError("gather_batch needs gather_samples > 0")
         z = float(gather_confidence)
         if not (z >= 0.0) or z == float("inf"):
             raise ValueError("gather_confidence must be finite and >= 0")
@@ -337,6 +374,12 @@ class RayTracer:
         if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
             raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if B:
+            self._L.uvrt_host_rt_plan_gather_batch(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                                   float(margin), float(rel_gap), int(max_iterations), _addr(keep),
+                                                   int(gather_samples), int(gather_sampling), z, tau, extra, float(reflectance),
+                                                   int(reflect_samples), int(reflect_bounces), B, C.byref(rep), C.byref(seed))
+            return _plan_result(self, rep, seed)
         if reflectance > 0.0 and reflect_bounces > 0:
             self._L.uvrt_host_rt_plan_gather_reflect_linked(self._h, -1.0 if min_dose is None else float(min_dose),
                                                             int(min_photons), float(margin), float(rel_gap), int(max_iterations),
@@ -403,6 +446,12 @@ def compute_iterations_batched_group(rts, iterations):
     """RayTracer::ComputeIterationsBatched over instances that share every launch by ray range (one process)."""
     arr = (C.c_void_p * len(rts))(*[rt._h for rt in rts])
     lib().uvrt_host_rt_compute_batched_group(arr, len(rts), int(iterations))
+
+
+def _check_gather_batch(value):
+    if int(value) != value or not (0 <= int(value) <= 64):
+        raise ValueError("gather_batch must be an integer in [0, 64]")
+    return int(value)
 
 
 def _mask_arg(mask, T):

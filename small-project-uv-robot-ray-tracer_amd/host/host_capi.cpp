@@ -29,7 +29,7 @@ std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>
 RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
                                     const unsigned char* mask, int gather_samples, int gather_sampling = 0,
                                     double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64,
-                                    float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0)
+                                    float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0, int gather_batch = 0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
@@ -41,6 +41,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
     o.reflectance = reflectance;
     o.reflectSamples = reflect_samples;
     o.reflectBounces = reflect_bounces;
+    o.gatherBatch = gather_batch;
     return o;
 }
 
@@ -103,6 +104,7 @@ void uvrt_host_rt_compute_segment(void* r, float ax, float ay, float bx, float b
 {
     ((RayTracer*)r)->ComputeSegmentDosageMap({make_float2(ax, ay), 0.0f}, {make_float2(bx, by), 0.0f}, photons, tris);
 }
+void uvrt_host_rt_compute_segments(void* r) { ((RayTracer*)r)->ComputeSegments(); }
 void uvrt_host_rt_shade(void* r) { ((RayTracer*)r)->Shade(); }
 void uvrt_host_rt_add_lamp(void* r) { ((RayTracer*)r)->AddLamp(); }
 void uvrt_host_rt_calibrate(void* r, float p, float h, float d) { ((RayTracer*)r)->CalibratePower(p, h, d); }
@@ -210,6 +212,16 @@ void uvrt_host_rt_plan_gather_reflect_linked(void* r, float min_dose, int min_ph
                                                        gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
                                                        reflectance, reflect_samples, reflect_bounces), seed);
 }
+// the same with PlanOptions::gatherBatch: the plan's gather launches traced in groups (include/uvrt.h uvrt_gather_direct_batch)
+void uvrt_host_rt_plan_gather_batch(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                                    const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
+                                    double gather_rel_error, int gather_max_extra, float reflectance, int reflect_samples,
+                                    int reflect_bounces, int gather_batch, uvrt_plan_report* rep, unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
+                                                       reflectance, reflect_samples, reflect_bounces, gather_batch), seed);
+}
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
@@ -240,7 +252,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(finishedComputation, bool) F(thresholdView, bool) F(startedComputation, bool)
     F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
     F(gatherSampling, int) F(gatherRelError, double) F(gatherMaxExtra, int)
-    F(reflectance, float) F(reflectSamples, int) F(reflectBounces, int)
+    F(reflectance, float) F(reflectSamples, int) F(reflectBounces, int) F(gatherBatch, int)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

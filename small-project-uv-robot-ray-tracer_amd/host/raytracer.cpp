@@ -186,17 +186,75 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    for (const RouteLaunch& l : Launches()) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
+    RunLaunches(Launches(), photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
+                reflectance, reflectSamples, reflectBounces, gatherBatch);
 }
 
 void RayTracer::ComputeSegments()
 {
+    std::vector<RouteLaunch> sweeps;
     for (const RouteLaunch& l : Launches())
-        if (l.kind == UVRT_LAUNCH_SWEEP) RunLaunch(l, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
+        if (l.kind == UVRT_LAUNCH_SWEEP) sweeps.push_back(l);
+    RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
+                reflectance, reflectSamples, reflectBounces, gatherBatch);
+}
+
+// the uvrt_gather_params of a gather launch with seed `seed`
+static uvrt_gather_params gather_params(const RouteLaunch& l, float lightLength, int samples, unsigned seed, int photons)
+{
+    uvrt_gather_params g;
+    memset(&g, 0, sizeof g);
+    memcpy(g.from, l.from, 12);
+    memcpy(g.to, l.kind == UVRT_LAUNCH_SWEEP ? l.to : l.from, 12);       // from == to: a stop
+    g.light_length = lightLength;
+    g.samples = samples;
+    g.seed = seed;
+    g.photons_equiv = photons;
+    return g;
+}
+
+void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
+                            double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch)
+{
+    if (batch < 0 || batch > UVRT_GATHER_BATCH_MAX) fatal("gatherBatch must be in [0, 64]");
+    // (a refine that RunLaunch is about to refuse is left to it: its batch would be refused first, with another message)
+    const bool refineOk = relError == 0.0 || (samples >= 2 && relError > 0.0 && std::isfinite(relError));
+    if (batch < 2 || samples <= 0 || !refineOk) {
+        for (const RouteLaunch& l : list)
+            RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS, reflectK);
+        return;
+    }
+    // groups of up to `batch` consecutive launches: one shadow-ray pass each (include/uvrt.h uvrt_gather_direct_batch), then
+    // every launch as RunLaunch runs it, with uvrt_gather_batch_select where uvrt_gather_direct stood
+    const long long want = std::min<long long>((long long)std::min<size_t>((size_t)batch, list.size()) * triangleCount * samples, 1ll << 23);
+    if (want > rayCapacity) {                                // results never depend on the capacity: the cap is a memory choice
+        check(uvrt_resize_rays(ctx, want), "resize_rays");
+        rayCapacity = want;
+    }
+    std::vector<uvrt_gather_params> params;
+    for (size_t first = 0; first < list.size(); first += (size_t)batch) {
+        const size_t cnt = std::min((size_t)batch, list.size() - first);
+        params.clear();
+        for (size_t k = 0; k < cnt; ++k)                     // the seeds the launches take from gatherLaunches below
+            params.push_back(gather_params(list[first + k], lightLength, samples, gatherLaunches + (unsigned)k, photons));
+        check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
+        int32_t variance0 = 0;
+        if (relError != 0.0) {                               // the refine reads the variance plane (RunLaunch)
+            check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
+            check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
+        }
+        check(uvrt_gather_direct_batch(ctx, params.data(), (int32_t)cnt, 0, triangleCount), "gather_direct_batch");
+        if (relError != 0.0) check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
+        for (size_t k = 0; k < cnt; ++k) {
+            const RouteLaunch& l = list[first + k];
+            RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS,
+                      reflectK, (int)k);
+        }
+    }
 }
 
 void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                          double relError, int maxExtra, float reflect, int reflectS, int reflectK)
+                          double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (reflectK < 0 || reflectK > 16) fatal("reflectBounces must be in [0, 16]");
@@ -207,22 +265,20 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
     if (samples > 0) {
         // the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
         if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
-        uvrt_gather_params g;
-        memset(&g, 0, sizeof g);
-        memcpy(g.from, l.from, 12);
-        memcpy(g.to, sweep ? l.to : l.from, 12);             // from == to: a stop
-        g.light_length = lightLength;
-        g.samples = samples;
-        g.seed = gatherLaunches++;
-        g.photons_equiv = photons;
+        const uvrt_gather_params g = gather_params(l, lightLength, samples, gatherLaunches++, photons);
         check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
+        // the launch's planes: traced here, or taken from the batch that RunLaunches has traced (batchSlot >= 0)
+        auto gather = [&] {
+            if (batchSlot >= 0) check(uvrt_gather_batch_select(ctx, batchSlot), "gather_batch_select");
+            else check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+        };
         if (relError != 0.0) {
             // the adaptive gather (raytracer.h gatherRelError): the variance plane on for this launch, then the refine
             if (!(relError > 0.0) || !std::isfinite(relError)) fatal("gatherRelError must be finite and >= 0");
             int32_t variance0 = 0;
             check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
             check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
-            check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+            gather();
             check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
             uvrt_refine_params rp;
             memset(&rp, 0, sizeof rp);
@@ -231,7 +287,7 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
             rp.seed = ~g.seed;
             check(uvrt_gather_refine(ctx, &rp, 0, triangleCount, nullptr), "gather_refine");
         } else {
-            check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+            gather();
         }
         if (reflect > 0.0f && reflectK > 0) {
             // reflectK bounces over recorded hit links (raytracer.h reflectBounces): traced once per scene and reflectS
@@ -408,7 +464,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
 void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra, float reflect, int reflectS, int reflectK)
+                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -425,7 +481,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        for (const RouteLaunch& l : list) RunLaunch(l, photonsPerLight, mesh->triangleCount, samples, sampling, l.column, relError, maxExtra, reflect, reflectS, reflectK);
+        RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch);
         Shade();
         ++currIterations;
     }
@@ -497,6 +553,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (opt.gatherSamples < 2) fatal("PlanDurations: gatherRelError needs a plan from the direct gather with gatherSamples >= 2");
     }
     if (opt.reflectBounces < 0 || opt.reflectBounces > 16) fatal("PlanDurations: reflectBounces must be in [0, 16]");
+    if (opt.gatherBatch < 0 || opt.gatherBatch > UVRT_GATHER_BATCH_MAX) fatal("PlanDurations: gatherBatch must be in [0, 64]");
     if (opt.reflectance != 0.0f) {
         if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
         if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
@@ -508,7 +565,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
         r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
-                              opt.reflectance, opt.reflectSamples, opt.reflectBounces);
+                              opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -588,6 +645,7 @@ void RayTracer::ClearBuffers(bool resetColor)                // raytracer.cpp:13
 {
     photonMapSize = 0;
     check(uvrt_resize_rays(ctx, photonCount), "resize_rays");
+    rayCapacity = photonCount;
     check(uvrt_reset(ctx, resetColor), "reset");
 }
 

@@ -143,6 +143,10 @@ public:
         // K in [1, 16] with reflectance > 0: the plan's launches take K bounces over recorded hit links instead of the traced
         // one (RayTracer::reflectBounces below).  0 (default): the traced bounce, bit for bit.  Outside [0, 16]: fatal.
         int reflectBounces = 0;
+        // B in [2, 64]: the plan's gather launches are traced in groups of up to B (RayTracer::gatherBatch below).  The plan's
+        // own, like S.  0 (default) and 1: launch by launch.  Durations, report and every captured column are the same bits
+        // for every B.  Outside [0, 64]: fatal.
+        int gatherBatch = 0;
     };
     uvrt_plan_report PlanDurations(const PlanOptions& opt, unsigned* seedOut = nullptr);
     static uvrt_plan_report PlanDurations(const std::vector<RayTracer*>& group, const PlanOptions& opt, unsigned* seedOut = nullptr);
@@ -218,6 +222,15 @@ public:
     // Outside [0, 16]: fatal.  Without effect at reflectance 0.  Saved as <reflect_bounces> after <reflect_samples> when both
     // rho and K are > 0.
     int reflectBounces = 0;
+    // The batched direct gather (include/uvrt.h "batched direct gather").  gatherBatch = B in [2, 64] with
+    // gatherSamples > 0: ComputeDosageMap and ComputeSegments walk their launches in groups of up to B consecutive ones; a
+    // group's shadow rays are traced in one uvrt_gather_direct_batch (the seeds the launches would have taken, the variance
+    // state on around it when gatherRelError asks for it), and every launch then runs as before with
+    // uvrt_gather_batch_select(k) where uvrt_gather_direct stood -- refine, bounce, capture and accumulate after it, the
+    // seed counter advancing the same.  B changes no bit of any result, so it is not saved in route files.  Before the first
+    // group the ray capacity is raised to min(B, launches) x triangles x gatherSamples rays, 2^23 at most (ClearBuffers puts
+    // photonCount back).  0 (default) and 1: launch by launch.  Outside [0, 64]: fatal.
+    int gatherBatch = 0;
     unsigned gatherLaunches = 0;                  // gather launches since ResetDosageMap: the next launch's seed
 private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
@@ -227,15 +240,21 @@ private:
     // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError);
     // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance), or with reflectK > 0 that many
     // bounces over recorded hit links (reflectBounces).
+    // batchSlot >= 0: the launch's planes are those of launch batchSlot of the context's gather batch (RunLaunches).
     void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                   double relError, int maxExtra, float reflect, int reflectS, int reflectK);
+                   double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1);
+    // A list of launches through RunLaunch, in order (capture: every plane into its launch's column of a plan); with
+    // samples > 0 and batch >= 2 in groups of up to `batch` behind one uvrt_gather_direct_batch each (gatherBatch).
+    void RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
+                     double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch);
+    long long rayCapacity = 0;                      // what ClearBuffers / RunLaunches last gave uvrt_resize_rays
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
     void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra, float reflect, int reflectS, int reflectK);
+                           int maxExtra, float reflect, int reflectS, int reflectK, int batch);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

@@ -81,6 +81,10 @@
 //                                           launch then looks its sources up along them, and bounces 2..K come with it.  All launches
 //                                           see the same directions: the bounce's sampling error no longer averages out over a
 //                                           route, but S2 is paid once and can be much larger.  --save-route writes <reflect_bounces>
+//            [--gather-batch B]             with --gather S or --plan-gather S: trace the gather launches in groups of up to B in
+//                                           [0, 64] (RayTracer::gatherBatch, PlanOptions::gatherBatch): one shadow-ray
+//                                           pass per group instead of one per launch.  0 (default) and 1: launch by launch.  B
+//                                           changes no bit of the dose, the plan or its report, and is not saved in route files
 #include "raytracer.h"
 #include "../../include/uvrt.h"
 
@@ -159,6 +163,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.reflectance = planGather > 0 ? reflect : 0.0f;
     opt.reflectSamples = reflectS;
     opt.reflectBounces = planGather > 0 ? reflectK : 0;
+    opt.gatherBatch = planGather > 0 ? rt.gatherBatch : 0;   // (--gather-batch: --plan-verify recomputes in the same groups)
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
     if (planGather > 0) {
@@ -254,6 +259,7 @@ int main(int argc, char** argv)
     float reflect = -1.0f;                  // < 0: not given
     int reflectS = 16;
     int reflectK = 0;                       // 0: not given
+    int gatherBatch = -1;                   // < 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
     ViewMode view = dosage;
@@ -358,6 +364,17 @@ int main(int argc, char** argv)
             }
             reflectK = (int)k;
         }
+        else if (!strcmp(argv[i], "--gather-batch")) {
+            need(1);
+            char* end = nullptr;
+            const char* v = argv[++i];
+            const long b = strtol(v, &end, 10);
+            if (end == v || *end != 0 || b < 0 || b > UVRT_GATHER_BATCH_MAX) {
+                fprintf(stderr, "--gather-batch B: B must be an integer in [0, 64] (with --gather S or --plan-gather S)\n");
+                return 2;
+            }
+            gatherBatch = (int)b;
+        }
         else if (!strcmp(argv[i], "--min-photons")) { need(1); minPhotons = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
@@ -371,6 +388,7 @@ int main(int argc, char** argv)
     if (reflect >= 0.0f && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--reflect needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (reflect >= 0.0f && planConfidence >= 0.0) { fprintf(stderr, "--reflect cannot be combined with --plan-confidence (the variance plane knows nothing of the indirect part)\n"); return 2; }
     if (reflectK > 0 && !(reflect >= 0.0f)) { fprintf(stderr, "--reflect-bounces needs --reflect RHO[,S2] (with --gather S or --plan-gather S)\n"); return 2; }
+    if (gatherBatch >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-batch needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (planGather > 0 && gpus != 1) { fprintf(stderr, "--plan-gather runs on one context (--gpus 1)\n"); return 2; }
@@ -406,6 +424,7 @@ int main(int argc, char** argv)
     if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
     if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
     if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; }
+    if (gatherBatch >= 0) rayTracer.gatherBatch = gatherBatch;
     if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectance = 0.0f;    // (the route file's own <reflectance>: a plan's bounce is --reflect's)
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
