@@ -412,7 +412,8 @@ int uvrt_gather_indirect_rays(uvrt_ctx* ctx, const uvrt_indirect_params* params,
  * (as uvrt_gather_indirect, with the same sample numbers and WangHash(seed)) -> a store kernel.  Like uvrt_gather_indirect it
  * drops "the last generate" and leaves SEED, tempPhotonMap and every plane untouched; it also leaves the remembered gather of
  * uvrt_gather_refine.  A second build replaces the links, uvrt_set_scene drops them, uvrt_set_flavour leaves them:
- * uvrt_indirect_links_info reports {samples (0: no links), seed, the flavour they were traced in, 0}.
+ * uvrt_indirect_links_info reports {samples (0: no links), seed, the flavour they were traced in, the kind (0: these links; 1: sided ones,
+ * "face-resolved gather and bounces" below)}.
  * UVRT_ERR_INVALID with nothing changed and earlier links kept: a null argument, no scene, flavour 2, non-zero reserved, and
  * what uvrt_gather_indirect refuses for `samples`.  A failed allocation: UVRT_ERR_HIP, earlier links kept.
  * uvrt_read_indirect_links (test hook; synchronises): out[(t - first_tri) * S2 + s] = link[t][s], whatever the device layout
@@ -452,6 +453,67 @@ typedef struct {
     int32_t  reserved[3];   /* 0 */
 } uvrt_linked_params;
 int uvrt_gather_indirect_linked(uvrt_ctx* ctx, const uvrt_linked_params* params, int32_t first_tri, int32_t tri_count);
+
+/* ---- face-resolved gather and bounces: every triangle an opaque sheet whose two faces keep their own irradiance ----
+ * The bounces above are two-sided: a triangle gathers over both hemispheres and what arrives on either face is re-emitted
+ * from both, so the bounce operator can have a gain above 1 and the series g_1 + g_2 + .. need not converge.
+ * The calls below resolve the faces instead: light that arrives on a face is re-emitted from that face only, and a
+ * ray that leaves face f of triangle t and arrives on face a of triangle h looks up what face a of h receives.  No notion of
+ * "inside" is needed: the arrival face is the sign of n_h . dir.  Everything here is additive: `expected`, the photon path and
+ * every call above keep their bits.
+ *
+ * Face convention: face 0 of triangle t is the side n = cross(e1, e2) points to.  A ray travelling along v arrives on face 0
+ * iff n.v < 0, on face 1 otherwise.  Even samples of the bounce leave face 0 and odd samples face 1 (`zz` above).
+ *
+ * The direct gather's face planes.  uvrt_set_gather_faces is a property of the context like uvrt_set_gather_variance: default
+ * 0, survives uvrt_set_scene, needs no device work; a value other than 0 / 1 is UVRT_ERR_INVALID with the state unchanged.  With
+ * the state off uvrt_gather_direct launches what it launches without it and makes no buffer.  With it on the call also writes
+ * faces[f][t], f64[2][T], for t in the range; in the notation of uvrt_gather_direct, for sample s
+ *     c_s = (n.x*D.x + n.y*D.y) + n.z*D.z          the f64 value the weight takes fabs of
+ *     f_s = c_s < 0 ? 0 : 1,     x_s = occluded ? 0 : w_s
+ *     faces[f][t] = nn == 0 ? 0 : ((double)photons_equiv * (0.5*nn)) * ((sum_{s : f_s = f} x_s) / (double)S)
+ * the sum in sample order from +0.0, no atomics (every term is >= +0, so skipping the other face's samples and adding +0.0
+ * for them give the same bits).  expected[t] and variance[t] carry the bits they carry with the state off; when every visible
+ * sample of a triangle lies on one face, that face's entry equals expected[t] bit for bit and the other is +0.0.  The planes
+ * are allocated (zeroed) on first use and zeroed by uvrt_set_scene; uvrt_accumulate_expected zeroes faces[.][0 .. tri_count)
+ * when they exist, as it does for the variance.  uvrt_gather_refine, uvrt_gather_indirect*, uvrt_write_expected and
+ * uvrt_gather_batch_select leave them alone: after a refine the planes describe the first pass.  uvrt_gather_direct_batch with
+ * the state on is UVRT_ERR_INVALID with nothing changed and an earlier batch kept (a batch keeps no face planes).
+ * uvrt_read_gather_faces / uvrt_write_gather_faces: a range of plane `face` (0 / 1, else UVRT_ERR_INVALID) as
+ * uvrt_read_variance / uvrt_write_variance; they synchronise; the write serves tests and a caller with an emitter of their own
+ * and, touching neither plane a refine works on, leaves the remembered gather.  The planes are not a uvrt_device_ptr index. */
+int uvrt_set_gather_faces(uvrt_ctx* ctx, int32_t on);
+int uvrt_get_gather_faces(uvrt_ctx* ctx, int32_t* on);
+int uvrt_read_gather_faces(uvrt_ctx* ctx, int32_t face, double* out, int32_t first, int32_t count);
+int uvrt_write_gather_faces(uvrt_ctx* ctx, int32_t face, const double* in, int32_t first, int32_t count);
+/* Sided links.  uvrt_indirect_links_build_sided is uvrt_indirect_links_build in everything -- the same rays, chunks, refusals
+ * and lifecycle, built into a buffer of its own and swapped in at the end -- but for the stored value:
+ *     link[t][s] = keep ? (h_s << 1) | a_s : -1        keep: the filter of the plain link (hit && h_s != t && nn_h > 0)
+ *     a_s = c < 0 ? 0 : 1,   c = (n_h.x*(double)dir.x + n_h.y*(double)dir.y) + n_h.z*(double)dir.z
+ * with n_h = cross(e1, e2) of h_s in f64 and dir the f32 direction of the sample (uvrt_gather_indirect_rays).  For the same
+ * (S2, seed, flavour) link >> 1 is the plain link wherever it is >= 0, and -1 sits in the same places.  A context holds one
+ * link set: a plain build replaces sided links and the other way round; uvrt_indirect_links_info reports the kind in out4[3]
+ * (0 plain, 1 sided) and uvrt_read_indirect_links returns the stored values as they are.  uvrt_gather_indirect_linked on sided
+ * links and uvrt_gather_indirect_linked_sided on plain ones are UVRT_ERR_INVALID with nothing changed.
+ *
+ * uvrt_gather_indirect_linked_sided: the struct, the checks and K in [1, 16] of uvrt_gather_indirect_linked.  It reads
+ * faces[2][T] as the emitter (no snapshot; made zeroed when absent; never written) and the sided links, and writes only
+ * expected[first_tri .. first_tri + tri_count).  Everything f64, every operator one rounding, L = link[t][s]:
+ *     e_0[f][h] = nn_h > 0 ? faces[f][h] / (0.5*nn_h) : 0.0                                      f = 0, 1; all h
+ *     for b = 1..K, f = 0, 1:
+ *       g_b[f][t] = nn_t == 0 ? 0.0
+ *                 : ((double)rho * (0.5*nn_t)) * ((2.0 * sum_{s = f, f+2, .. < S2} (L >= 0 ? e_{b-1}[L & 1][L >> 1] : 0.0)) / (double)S2)
+ *       e_b[f][t] = nn_t > 0 ? g_b[f][t] / (0.5*nn_t) : 0.0
+ *     G_b[t]      = g_b[0][t] + g_b[1][t]
+ *     total[t]    = (..((G_1[t] + G_2[t]) + G_3[t]) .. + G_K[t])
+ *     expected[t] = add ? expected[t] + total[t] : total[t]
+ * Each face has S2/2 cosine samples over its own hemisphere, hence 2/S2 (S2 is even).  The sums run in ascending s from +0.0,
+ * without atomics.  Bounces before the last are evaluated for all T triangles, so the result depends neither on the range nor
+ * on its cut into calls.  max e_b <= rho * max e_{b-1} up to rounding, so the series converges for every rho <= 1.  The call
+ * traces nothing, works in any flavour (one plain kernel launch per bounce) and leaves and forgets exactly what
+ * uvrt_gather_indirect_linked leaves and forgets. */
+int uvrt_indirect_links_build_sided(uvrt_ctx* ctx, const uvrt_links_params* params);
+int uvrt_gather_indirect_linked_sided(uvrt_ctx* ctx, const uvrt_linked_params* params, int32_t first_tri, int32_t tri_count);
 
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *

@@ -150,6 +150,12 @@ SYMBOLS = [
     ("uvrt_indirect_links_info", C.c_int, [_vp, _vp]),
     ("uvrt_read_indirect_links", C.c_int, [_vp, _vp, _i32, _i32]),
     ("uvrt_gather_indirect_linked", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_set_gather_faces", C.c_int, [_vp, _i32]),
+    ("uvrt_get_gather_faces", C.c_int, [_vp, C.POINTER(_i32)]),
+    ("uvrt_read_gather_faces", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_write_gather_faces", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_indirect_links_build_sided", C.c_int, [_vp, _vp]),
+    ("uvrt_gather_indirect_linked_sided", C.c_int, [_vp, _vp, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -580,6 +586,18 @@ class Ctx:
         v = np.ascontiguousarray(values, dtype=np.float64)
         self._ck(self._L.uvrt_write_variance(self._h, _ptr(v), int(first), int(v.size)))
 
+    def read_gather_faces(self, face, first=0, count=None):
+        """plane `face` (0 / 1) of the direct gather's face planes (set_gather_faces)"""
+        count = self.T - first if count is None else count
+        out = np.empty(max(int(count), 0), dtype=np.float64)
+        self._ck(self._L.uvrt_read_gather_faces(self._h, int(face), _ptr(out), int(first), int(count)))
+        return out
+
+    def write_gather_faces(self, face, values, first=0):
+        """host values into faces[face][first, first + len(values))"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        self._ck(self._L.uvrt_write_gather_faces(self._h, int(face), _ptr(v), int(first), int(v.size)))
+
     def gather_refine(self, rel_error, max_extra, seed, min_expected=0.0, first_tri=0, tri_count=None):
         """extra shadow rays for the triangles of the remembered gather whose sqrt(variance) / expected exceeds rel_error,
         merged into both planes (include/uvrt.h "adaptive gather"); returns (extra rays, refined triangles)"""
@@ -723,6 +741,30 @@ class Ctx:
         prm.add = int(add)
         self._ck(self._L.uvrt_gather_indirect_linked(self._h, C.byref(prm), int(first_tri),
                                                      self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    # ---- face-resolved bounces: sided links and the gather over the direct gather's face planes ----
+    def indirect_links_build_sided(self, samples, seed):
+        """indirect_links_build that also records the face of the hit triangle each ray arrives on: (h << 1) | face, or -1"""
+        prm = LinksParams()
+        prm.samples = int(samples)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        self._ck(self._L.uvrt_indirect_links_build_sided(self._h, C.byref(prm)))
+
+    def indirect_links_kind(self):
+        """0: plain links (or none); 1: sided links"""
+        out = np.zeros(4, dtype=np.int32)
+        self._ck(self._L.uvrt_indirect_links_info(self._h, _ptr(out)))
+        return int(out[3])
+
+    def gather_indirect_linked_sided(self, reflectance, bounces, add=0, first_tri=0, tri_count=None):
+        """expected[first_tri, +tri_count) = (add ? expected : 0) + `bounces` face-resolved bounces of the face planes over the
+        sided links"""
+        prm = LinkedParams()
+        prm.reflectance = float(np.float32(reflectance))
+        prm.bounces = int(bounces)
+        prm.add = int(add)
+        self._ck(self._L.uvrt_gather_indirect_linked_sided(self._h, C.byref(prm), int(first_tri),
+                                                           self.T - int(first_tri) if tri_count is None else int(tri_count)))
 
     @property
     def seed(self):
@@ -874,6 +916,15 @@ class Ctx:
     def set_gather_variance(self, on):
         """1: gather_direct also writes the variance plane (include/uvrt.h); needs samples >= 2"""
         self._ck(self._L.uvrt_set_gather_variance(self._h, int(on)))
+
+    def set_gather_faces(self, on):
+        """1: gather_direct also writes the two face planes (include/uvrt.h "face-resolved gather and bounces")"""
+        self._ck(self._L.uvrt_set_gather_faces(self._h, int(on)))
+
+    def get_gather_faces(self):
+        v = C.c_int32()
+        self._ck(self._L.uvrt_get_gather_faces(self._h, C.byref(v)))
+        return int(v.value)
 
     def get_gather_variance(self):
         v = _i32()

@@ -1,7 +1,8 @@
 // uvrt_capi_gather.hip -- shadow rays and the per-triangle direct gather (include/uvrt.h "shadow rays and the direct gather"):
 // uvrt_occluded, uvrt_set_gather_sampling, uvrt_get_gather_sampling, uvrt_set_gather_variance, uvrt_get_gather_variance,
 // uvrt_gather_direct, uvrt_accumulate_expected, uvrt_read_expected, uvrt_write_expected, uvrt_read_variance,
-// uvrt_write_variance (uvrt_occlude.hip's kernels); uvrt_gather_refine, uvrt_read_gather_extra, uvrt_refine_counts (uvrt_refine.hip's)
+// uvrt_write_variance, uvrt_set_gather_faces, uvrt_get_gather_faces, uvrt_read_gather_faces, uvrt_write_gather_faces
+// (uvrt_occlude.hip's kernels); uvrt_gather_refine, uvrt_read_gather_extra, uvrt_refine_counts (uvrt_refine.hip's)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
@@ -17,6 +18,11 @@ int ensure_expected(uvrt_ctx* c)
 int ensure_variance(uvrt_ctx* c)
 {
     return c->derived.variance.ensure((size_t)c->T * 8, true, c->stream);
+}
+
+int ensure_faces(uvrt_ctx* c)
+{
+    return c->derived.faces.ensure((size_t)c->T * 16, true, c->stream);
 }
 
 // the gather's per-triangle records {v0, e1, e2} in tris64 order, made from the scene's leaf triangles on first use
@@ -142,6 +148,21 @@ int uvrt_get_gather_variance(uvrt_ctx* c, int32_t* on)
     return UVRT_OK;
 }
 
+int uvrt_set_gather_faces(uvrt_ctx* c, int32_t on)
+{
+    if (!c) return fail(UVRT_ERR_INVALID, "uvrt_set_gather_faces: null context");
+    if (on != 0 && on != 1) return fail(UVRT_ERR_INVALID, "uvrt_set_gather_faces: on must be 0 or 1, not %d", on);
+    c->gather_faces = on;
+    return UVRT_OK;
+}
+
+int uvrt_get_gather_faces(uvrt_ctx* c, int32_t* on)
+{
+    if (!c || !on) return fail(UVRT_ERR_INVALID, "uvrt_get_gather_faces: null argument");
+    *on = c->gather_faces;
+    return UVRT_OK;
+}
+
 int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first_tri, int32_t tri_count)
 {
     if (!c || !prm) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: null argument");
@@ -152,7 +173,7 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: triangles [%d, +%d) outside [0, %d]", first_tri, tri_count, c->T);
     const int32_t S = prm->samples;
     if (S < 1 || S > 4096) return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: samples = %d must be in [1, 4096]", S);
-    const bool var = c->gather_variance != 0;
+    const bool var = c->gather_variance != 0, sided = c->gather_faces != 0;
     if (var && S < 2)
         return fail(UVRT_ERR_INVALID, "uvrt_gather_direct: the variance plane needs samples >= 2 (uvrt_set_gather_variance), not %d", S);
     if ((int64_t)S > c->capacity)
@@ -168,6 +189,10 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     if (int rc = ensure_expected(c)) return rc;
     if (var)
         if (int rc = ensure_variance(c)) return rc;
+    if (sided) {
+        if (int rc = c->g_face.ensure(cap, false, c->stream)) return rc;
+        if (int rc = ensure_faces(c)) return rc;
+    }
     if (int rc = ensure_gather_tris(c)) return rc;
     Lane& L = c->lanes[0];
     GatherGenParams g;
@@ -187,7 +212,8 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
     const int rc = for_tri_chunks(c, S, tri_count, [&](int32_t done, int32_t cnt) -> int {
         g.first_tri = first_tri + done;
         g.tri_count = cnt;
-        launch_gather_generate(g, c->stream);
+        if (sided) launch_gather_generate_faces(g, c->g_face.as<uint8_t>(), c->stream);
+        else launch_gather_generate(g, c->stream);
         HIP_TRY(hipGetLastError());
         if (int rc = trace_shadow_rays(c, (int64_t)cnt * S, "uvrt_gather_direct")) return rc;
         if (var)
@@ -196,6 +222,9 @@ int uvrt_gather_direct(uvrt_ctx* c, const uvrt_gather_params* prm, int32_t first
         else
             launch_gather_reduce(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->derived.expected.as<double>(), g.first_tri, cnt, S,
                                  prm->photons_equiv, c->stream);
+        if (sided)
+            launch_gather_reduce_faces(g.gtris, g.w, c->g_occ.as<uint8_t>(), c->g_face.as<uint8_t>(), c->derived.faces.as<double>(),
+                                       g.first_tri, cnt, S, prm->photons_equiv, c->T, c->stream);
         HIP_TRY(hipGetLastError());
         return UVRT_OK;
     });
@@ -227,6 +256,9 @@ int uvrt_accumulate_expected(uvrt_ctx* c, float time_step, int32_t tri_count)
     HIP_TRY(hipGetLastError());
     // the variance of the estimate that has just been consumed goes with it: a stale one is never paired with a later estimate
     if (c->derived.variance.p && tri_count > 0) HIP_TRY(hipMemsetAsync(c->derived.variance.p, 0, (size_t)tri_count * 8, c->stream));
+    if (c->derived.faces.p && tri_count > 0)     // ... and so do its face planes
+        for (int f = 0; f < 2; ++f)
+            HIP_TRY(hipMemsetAsync(c->derived.faces.as<double>() + (size_t)f * (size_t)c->T, 0, (size_t)tri_count * 8, c->stream));
     return mark_map_fence(c);                    // later accumulate / Shade work on a side lane waits for it
 }
 
@@ -262,6 +294,30 @@ int uvrt_read_variance(uvrt_ctx* c, double* out, int32_t first, int32_t count)
 int uvrt_write_variance(uvrt_ctx* c, const double* in, int32_t first, int32_t count)
 {
     return plane_range(c, "uvrt_write_variance", true, const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
+}
+
+// a range of face plane `face`; unlike the write calls above, the write leaves the remembered gather: it touches neither plane
+// a refine works on
+static int faces_range(uvrt_ctx* c, const char* who, int32_t face, void* host, int32_t first, int32_t count, hipMemcpyKind kind)
+{
+    if (!c || !host) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
+    if (face != 0 && face != 1) return fail(UVRT_ERR_INVALID, "%s: face must be 0 or 1, not %d", who, face);
+    if (!range_ok(host, first, count, c->T))
+        return fail(UVRT_ERR_INVALID, "%s: range [%d,+%d) outside [0,%d)", who, first, count, c->T);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = ensure_faces(c)) return rc;
+    return range_copy(c, c->derived.faces.as<double>() + (size_t)face * (size_t)c->T, 8, host, first, count, kind);
+}
+
+int uvrt_read_gather_faces(uvrt_ctx* c, int32_t face, double* out, int32_t first, int32_t count)
+{
+    return faces_range(c, "uvrt_read_gather_faces", face, out, first, count, hipMemcpyDeviceToHost);
+}
+
+int uvrt_write_gather_faces(uvrt_ctx* c, int32_t face, const double* in, int32_t first, int32_t count)
+{
+    return faces_range(c, "uvrt_write_gather_faces", face, const_cast<double*>(in), first, count, hipMemcpyHostToDevice);
 }
 
 int uvrt_gather_refine(uvrt_ctx* c, const uvrt_refine_params* prm, int32_t first_tri, int32_t tri_count, uvrt_refine_report* report)

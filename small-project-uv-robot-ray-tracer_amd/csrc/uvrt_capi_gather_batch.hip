@@ -16,6 +16,8 @@ int uvrt_gather_direct_batch(uvrt_ctx* c, const uvrt_gather_params* launches, in
     if (!c || !launches) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
     if (count < 1 || count > UVRT_GATHER_BATCH_MAX)
         return fail(UVRT_ERR_INVALID, "%s: count = %d must be in [1, %d]", who, count, UVRT_GATHER_BATCH_MAX);
+    if (c->gather_faces != 0)
+        return fail(UVRT_ERR_INVALID, "%s: a batch keeps no face planes: switch uvrt_set_gather_faces off, or gather launch by launch", who);
     // every launch as uvrt_gather_direct checks it
     if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
     if (c->flavour != 0 && c->flavour != 1)

@@ -1,16 +1,15 @@
 // uvrt_capi_links.hip -- recorded hit links and the multi-bounce gather over them (include/uvrt.h "recorded hit links"):
-// uvrt_indirect_links_build, uvrt_indirect_links_info, uvrt_read_indirect_links, uvrt_gather_indirect_linked
+// uvrt_indirect_links_build, uvrt_indirect_links_info, uvrt_read_indirect_links, uvrt_gather_indirect_linked, and their sided
+// forms (include/uvrt.h "face-resolved gather and bounces"): uvrt_indirect_links_build_sided, uvrt_gather_indirect_linked_sided
 // (uvrt_links.hip's kernels; the build traces with uvrt_indirect.hip's, through uvrt_capi_indirect.hip's helpers)
 #include "uvrt_ctx.h"
 
 using namespace uvrt;
 using namespace uvrt_impl;
 
-extern "C" {
-
-int uvrt_indirect_links_build(uvrt_ctx* c, const uvrt_links_params* prm)
+// uvrt_indirect_links_build (kind 0) and uvrt_indirect_links_build_sided (kind 1): one build, two store kernels
+static int links_build(uvrt_ctx* c, const uvrt_links_params* prm, int32_t kind, const char* who)
 {
-    const char* who = "uvrt_indirect_links_build";
     if (!c || !prm) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
     if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return fail(UVRT_ERR_INVALID, "%s: reserved fields must be 0", who);
     uvrt_indirect_params ip;                        // the traced bounce these links stand for
@@ -39,7 +38,8 @@ int uvrt_indirect_links_build(uvrt_ctx* c, const uvrt_links_params* prm)
         launch_indirect_generate(g, c->stream);
         HIP_TRY(hipGetLastError());
         if (int rc = trace_closest_rays(c, (int64_t)cnt * S, who)) return rc;
-        launch_links_store(st, c->stream);
+        if (kind) launch_links_store_sided(st, g.rays, c->stream);
+        else launch_links_store(st, c->stream);
         HIP_TRY(hipGetLastError());
         return UVRT_OK;
     });
@@ -48,7 +48,83 @@ int uvrt_indirect_links_build(uvrt_ctx* c, const uvrt_links_params* prm)
     c->derived.links_samples = S;
     c->derived.links_seed = prm->seed;
     c->derived.links_flavour = c->flavour;
+    c->derived.links_kind = kind;
     return UVRT_OK;
+}
+
+// uvrt_gather_indirect_linked (kind 0: `source` and plain links) and uvrt_gather_indirect_linked_sided (kind 1: the face planes
+// and sided links, every irradiance plane interleaved e[2 * h + face]): the same checks, the same sequence of launches
+static int linked_gather(uvrt_ctx* c, const uvrt_linked_params* prm, int32_t first_tri, int32_t tri_count, int32_t kind, const char* who)
+{
+    if (!c || !prm) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
+    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
+    const int32_t S = c->derived.links_samples;
+    if (S <= 0)
+        return fail(UVRT_ERR_INVALID, "%s: no links (%s)", who, kind ? "uvrt_indirect_links_build_sided" : "uvrt_indirect_links_build");
+    if (c->derived.links_kind != kind)
+        return fail(UVRT_ERR_INVALID, kind ? "%s: the links are plain: this call reads sided ones (uvrt_indirect_links_build_sided)"
+                                           : "%s: the links are sided: this call reads plain ones (uvrt_indirect_links_build)", who);
+    const int32_t K = prm->bounces;
+    if (K < 1 || K > 16) return fail(UVRT_ERR_INVALID, "%s: bounces = %d must be in [1, 16]", who, K);
+    if (!std::isfinite(prm->reflectance) || !(prm->reflectance >= 0.0f) || !(prm->reflectance <= 1.0f))
+        return fail(UVRT_ERR_INVALID, "%s: reflectance must be finite and in [0, 1]", who);
+    if (prm->add != 0 && prm->add != 1) return fail(UVRT_ERR_INVALID, "%s: add must be 0 or 1, not %d", who, prm->add);
+    if (prm->reserved[0] != 0 || prm->reserved[1] != 0 || prm->reserved[2] != 0)
+        return fail(UVRT_ERR_INVALID, "%s: reserved fields must be 0", who);
+    if (first_tri < 0 || tri_count < 0 || (int64_t)first_tri + tri_count > c->T)
+        return fail(UVRT_ERR_INVALID, "%s: triangles [%d, +%d) outside [0, %d]", who, first_tri, tri_count, c->T);
+    if (int rc = set_device(c)) return rc;
+    if (int rc = join_all(c)) return rc;
+    uvrt_ctx::SceneDerived& d = c->derived;
+    if (int rc = ensure_expected(c)) return rc;
+    if (int rc = kind ? ensure_faces(c) : ensure_source(c)) return rc;
+    if (int rc = ensure_gather_tris(c)) return rc;
+    const size_t plane = (size_t)c->T * 8;
+    const size_t eplane = kind ? plane * 2 : plane;         // (ensure only ever grows a buffer: the two kinds share link_e)
+    if (int rc = d.link_e[0].ensure(eplane, false, c->stream)) return rc;
+    if (K > 1) {
+        if (int rc = d.link_e[1].ensure(eplane, false, c->stream)) return rc;
+        if (int rc = d.link_total.ensure(plane, false, c->stream)) return rc;
+    }
+    d.gather_memo = {};                             // the expected plane is no longer the remembered gather's
+    LinksApplyParams a;
+    memset(&a, 0, sizeof a);
+    a.gtris = d.g_tris.as<float4>();
+    a.links = d.links.as<int32_t>();
+    a.samples = S;
+    a.T = c->T;
+    a.reflectance = prm->reflectance;
+    a.add = prm->add;
+    if (kind) launch_links_irradiance_sided(a.gtris, d.faces.as<double>(), d.link_e[0].as<double>(), c->T, c->stream);
+    else launch_links_irradiance(a.gtris, d.source.as<double>(), d.link_e[0].as<double>(), c->T, c->stream);
+    HIP_TRY(hipGetLastError());
+    // one launch per bounce; the bounces before the last run over all T triangles: they are the next bounce's source
+    for (int32_t b = 1; b <= K; ++b) {
+        const bool last = b == K;
+        a.e_in = d.link_e[(b - 1) & 1].as<double>();
+        a.e_out = last ? nullptr : d.link_e[b & 1].as<double>();
+        a.total_in = b == 1 ? nullptr : d.link_total.as<double>();
+        a.total_out = last ? nullptr : d.link_total.as<double>();
+        a.expected = last ? d.expected.as<double>() : nullptr;
+        a.first_tri = last ? first_tri : 0;
+        a.tri_count = last ? tri_count : c->T;
+        if (kind) launch_links_apply_sided(a, c->stream);
+        else launch_links_apply(a, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return UVRT_OK;
+}
+
+extern "C" {
+
+int uvrt_indirect_links_build(uvrt_ctx* c, const uvrt_links_params* prm)
+{
+    return links_build(c, prm, 0, "uvrt_indirect_links_build");
+}
+
+int uvrt_indirect_links_build_sided(uvrt_ctx* c, const uvrt_links_params* prm)
+{
+    return links_build(c, prm, 1, "uvrt_indirect_links_build_sided");
 }
 
 int uvrt_indirect_links_info(uvrt_ctx* c, int32_t out4[4])
@@ -58,7 +134,7 @@ int uvrt_indirect_links_info(uvrt_ctx* c, int32_t out4[4])
     out4[0] = have ? c->derived.links_samples : 0;
     out4[1] = have ? (int32_t)c->derived.links_seed : 0;
     out4[2] = have ? c->derived.links_flavour : 0;
-    out4[3] = 0;
+    out4[3] = have ? c->derived.links_kind : 0;
     return UVRT_OK;
 }
 
@@ -84,57 +160,12 @@ int uvrt_read_indirect_links(uvrt_ctx* c, int32_t* out, int32_t first_tri, int32
 
 int uvrt_gather_indirect_linked(uvrt_ctx* c, const uvrt_linked_params* prm, int32_t first_tri, int32_t tri_count)
 {
-    const char* who = "uvrt_gather_indirect_linked";
-    if (!c || !prm) return fail(UVRT_ERR_INVALID, "%s: null argument", who);
-    if (!c->have_scene) return fail(UVRT_ERR_INVALID, "%s: no scene", who);
-    const int32_t S = c->derived.links_samples;
-    if (S <= 0) return fail(UVRT_ERR_INVALID, "%s: no links (uvrt_indirect_links_build)", who);
-    const int32_t K = prm->bounces;
-    if (K < 1 || K > 16) return fail(UVRT_ERR_INVALID, "%s: bounces = %d must be in [1, 16]", who, K);
-    if (!std::isfinite(prm->reflectance) || !(prm->reflectance >= 0.0f) || !(prm->reflectance <= 1.0f))
-        return fail(UVRT_ERR_INVALID, "%s: reflectance must be finite and in [0, 1]", who);
-    if (prm->add != 0 && prm->add != 1) return fail(UVRT_ERR_INVALID, "%s: add must be 0 or 1, not %d", who, prm->add);
-    if (prm->reserved[0] != 0 || prm->reserved[1] != 0 || prm->reserved[2] != 0)
-        return fail(UVRT_ERR_INVALID, "%s: reserved fields must be 0", who);
-    if (first_tri < 0 || tri_count < 0 || (int64_t)first_tri + tri_count > c->T)
-        return fail(UVRT_ERR_INVALID, "%s: triangles [%d, +%d) outside [0, %d]", who, first_tri, tri_count, c->T);
-    if (int rc = set_device(c)) return rc;
-    if (int rc = join_all(c)) return rc;
-    uvrt_ctx::SceneDerived& d = c->derived;
-    if (int rc = ensure_expected(c)) return rc;
-    if (int rc = ensure_source(c)) return rc;
-    if (int rc = ensure_gather_tris(c)) return rc;
-    const size_t plane = (size_t)c->T * 8;
-    if (int rc = d.link_e[0].ensure(plane, false, c->stream)) return rc;
-    if (K > 1) {
-        if (int rc = d.link_e[1].ensure(plane, false, c->stream)) return rc;
-        if (int rc = d.link_total.ensure(plane, false, c->stream)) return rc;
-    }
-    d.gather_memo = {};                             // the expected plane is no longer the remembered gather's
-    LinksApplyParams a;
-    memset(&a, 0, sizeof a);
-    a.gtris = d.g_tris.as<float4>();
-    a.links = d.links.as<int32_t>();
-    a.samples = S;
-    a.T = c->T;
-    a.reflectance = prm->reflectance;
-    a.add = prm->add;
-    launch_links_irradiance(a.gtris, d.source.as<double>(), d.link_e[0].as<double>(), c->T, c->stream);
-    HIP_TRY(hipGetLastError());
-    // one launch per bounce; the bounces before the last run over all T triangles: they are the next bounce's source
-    for (int32_t b = 1; b <= K; ++b) {
-        const bool last = b == K;
-        a.e_in = d.link_e[(b - 1) & 1].as<double>();
-        a.e_out = last ? nullptr : d.link_e[b & 1].as<double>();
-        a.total_in = b == 1 ? nullptr : d.link_total.as<double>();
-        a.total_out = last ? nullptr : d.link_total.as<double>();
-        a.expected = last ? d.expected.as<double>() : nullptr;
-        a.first_tri = last ? first_tri : 0;
-        a.tri_count = last ? tri_count : c->T;
-        launch_links_apply(a, c->stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return UVRT_OK;
+    return linked_gather(c, prm, first_tri, tri_count, 0, "uvrt_gather_indirect_linked");
+}
+
+int uvrt_gather_indirect_linked_sided(uvrt_ctx* c, const uvrt_linked_params* prm, int32_t first_tri, int32_t tri_count)
+{
+    return linked_gather(c, prm, first_tri, tri_count, 1, "uvrt_gather_indirect_linked_sided");
 }
 
 }  // extern "C"

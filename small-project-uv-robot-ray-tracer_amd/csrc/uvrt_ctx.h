@@ -7,11 +7,13 @@
 //   uvrt_batch_plan.h     the host-only plan of a batch (plan_batch, deal_classes, mark_tiles): no HIP, testable alone
 //   uvrt_capi_free.hip    rays with origins of their own (uvrt_write_free_rays, uvrt_generate_sweep)
 //   uvrt_capi_gather.hip  shadow rays and the direct gather (uvrt_occluded, uvrt_gather_direct, uvrt_accumulate_expected,
-//                         uvrt_set_gather_variance and the variance plane, uvrt_gather_refine)
+//                         uvrt_set_gather_variance and the variance plane, uvrt_set_gather_faces and the face planes,
+//                         uvrt_gather_refine)
 //   uvrt_capi_gather_batch.hip  the batched direct gather (uvrt_gather_direct_batch, uvrt_gather_batch_select)
 //   uvrt_capi_indirect.hip  closest hits and the one-bounce gather (uvrt_closest_hits, uvrt_gather_indirect, the source plane)
 //   uvrt_capi_links.hip   recorded hit links and the multi-bounce gather over them (uvrt_indirect_links_build,
-//                         uvrt_gather_indirect_linked)
+//                         uvrt_gather_indirect_linked) and their sided forms (uvrt_indirect_links_build_sided,
+//                         uvrt_gather_indirect_linked_sided)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -155,6 +157,7 @@ struct uvrt_ctx {
     // shadow rays and the direct gather (uvrt_capi_gather.hip): every ray's {orig.x, orig.z}, tmax and answer and the samples'
     // weights, made on first use.  (The rays themselves go through lane 0's ray buffer, on the context's stream.)
     DevBuf g_oxz, g_tmax, g_occ, g_w;
+    DevBuf g_face;                             // the face each sample arrives on, uint8[capacity] (uvrt_set_gather_faces)
     DevBuf g_hit;                              // closest hits (uvrt_capi_indirect.hip): every ray's (dist bits, triID), uint2[capacity]
     // uvrt_gather_refine (include/uvrt.h "adaptive gather"): the exclusive prefix sums of a refined range, int32[T + 1], and
     // the scan's per-block totals
@@ -175,12 +178,14 @@ struct uvrt_ctx {
         DevBuf g_tris;                         // the gather's triangles by original id
         bool g_tris_valid = false;             // g_tris holds the current scene
         DevBuf expected, variance;             // the gather's expected plane f64[T] and the variance plane f64[T] beside it
+        DevBuf faces;                          // the direct gather's face planes f64[2][T] (made zeroed; uvrt_set_gather_faces)
         DevBuf g_extra;                        // n_t of the last refine, int32[T] (made zeroed)
         DevBuf source;                         // the one-bounce gather's source plane f64[T] (made zeroed)
         // recorded hit links (uvrt_capi_links.hip): int32[links_samples * T], sample-major (links[s * T + t]); links_samples 0:
         // none.  Beside them the linked gather's two irradiance planes (ping-pong over the bounces) and its running total, f64[T]
         DevBuf links, link_e[2], link_total;
         int32_t links_samples = 0, links_flavour = 0;
+        int32_t links_kind = 0;                // 0: plain links (h or -1); 1: sided ((h << 1) | arrival face, or -1)
         uint32_t links_seed = 0;
         GatherMemo gather_memo;                // a refine works on one scene's planes
         // the batch of the last successful uvrt_gather_direct_batch (uvrt_capi_gather_batch.hip; count 0: none): its launches,
@@ -294,6 +299,7 @@ struct uvrt_ctx {
     int32_t flavour = 0;
     int32_t gather_sampling = 0;   // uvrt_set_gather_sampling: read by uvrt_gather_direct alone
     int32_t gather_variance = 0;   // uvrt_set_gather_variance: uvrt_gather_direct writes the variance plane as well
+    int32_t gather_faces = 0;      // uvrt_set_gather_faces: uvrt_gather_direct writes the two face planes as well
 #ifdef UVRT_DEV_VARIANTS
     // timing-only probe of the developer build (UVRT_PROBE_SKIP_GENERATE=n): after n uvrt_trace_batch calls the generate
     // launches are skipped -- the buffers still hold the same rays when every computation is the same (bench.py), so
@@ -613,6 +619,8 @@ int make_free_records(uvrt_ctx* c);
 int ensure_expected(uvrt_ctx* c);
 // the variance plane beside it, f64[T]: likewise
 int ensure_variance(uvrt_ctx* c);
+// the direct gather's face planes, f64[2][T]: likewise
+int ensure_faces(uvrt_ctx* c);
 // the one-bounce gather's source plane, f64[T]: likewise (uvrt_capi_indirect.hip)
 int ensure_source(uvrt_ctx* c);
 // what the shadow-ray and closest-hit launches share (uvrt_capi_gather.hip): lane 0's ray buffer behind all outstanding work,

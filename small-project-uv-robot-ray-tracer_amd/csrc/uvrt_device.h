@@ -475,6 +475,11 @@ void launch_gather_reduce(const float4* gtris, const double* w, const uint8_t* o
 void launch_gather_reduce_var(const float4* gtris, const double* w, const uint8_t* occluded, double* expected, double* variance,
                               int32_t first_tri, int32_t tri_count, int32_t samples, int32_t photons_equiv, int32_t mode,
                               hipStream_t s);
+// the face-resolved gather (include/uvrt.h "face-resolved gather and bounces"): launch_gather_generate that also writes
+// face[i], the face sample i arrives on, and the reduction of the chunk into faces[f * T + t], f64[2][T], beside the reduce above
+void launch_gather_generate_faces(const GatherGenParams& p, uint8_t* face, hipStream_t s);
+void launch_gather_reduce_faces(const float4* gtris, const double* w, const uint8_t* occluded, const uint8_t* face, double* faces,
+                                int32_t first_tri, int32_t tri_count, int32_t samples, int32_t photons_equiv, int32_t T, hipStream_t s);
 // accumulate.cl:4-14 with expected[t] in place of (double)tempPhotonMap[t]; the plane is zeroed like tempPhotonMap
 void launch_accumulate_expected(double* photon_map, double* max_map, double* expected, float time_step, int32_t T, hipStream_t s);
 
@@ -587,6 +592,14 @@ struct LinksApplyParams {
     int32_t add;
 };
 void launch_links_apply(const LinksApplyParams& p, hipStream_t s);
+// the sided forms (include/uvrt.h "face-resolved gather and bounces").  The store: links[s * T + t] =
+// (h_s << 1) | a_s or -1, a_s the face of h_s the chunk's ray (rays: lane 0's, dir.xyz as the generate kernel wrote them)
+// arrives on.  The irradiance: e[2 * h + f] = nn_h > 0 ? faces[f * T + h] / (0.5 * nn_h) : 0.0, interleaved so that a sided link
+// is the index of what it points at.  The apply: LinksApplyParams with e_in / e_out of 2 * T entries; sample s leaves face
+// s & 1 of t, g[f] sums the samples of face f and the total takes g[0] + g[1].
+void launch_links_store_sided(const LinksStoreParams& p, const float4* rays, hipStream_t s);
+void launch_links_irradiance_sided(const float4* gtris, const double* faces, double* e, int32_t T, hipStream_t s);
+void launch_links_apply_sided(const LinksApplyParams& p, hipStream_t s);
 // test hook: out[(t - first_tri) * samples + s] = links[s * T + t]
 void launch_links_export(const int32_t* links, int32_t* out, int32_t first_tri, int32_t tri_count, int32_t samples, int32_t T,
                          hipStream_t s);

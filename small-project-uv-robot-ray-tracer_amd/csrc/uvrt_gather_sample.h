@@ -21,6 +21,7 @@ struct GatherSample {
     float2 oxz;              // orig.x, orig.z
     float tmax;
     double w;                // the sample's weight (0 for a sample that is not traced)
+    double c;                // n.D, the value w takes fabs of: its sign is the face the sample arrives on (gather_face)
 };
 
 // Sample s of `samples` of triangle t.  MODE: the gather sampling (include/uvrt.h uvrt_set_gather_sampling).  0 is the
@@ -61,7 +62,8 @@ __device__ __forceinline__ GatherSample gather_sample(const float4* __restrict__
     const double R2 = Dx * Dx + Dy * Dy + Dz * Dz;
     const double R = sqrt(R2);
     GatherSample o;
-    o.w = fabs(nx * Dx + ny * Dy + nz * Dz) / (nn * (R2 * R) * 12.566370614359172);
+    o.c = nx * Dx + ny * Dy + nz * Dz;
+    o.w = fabs(o.c) / (nn * (R2 * R) * 12.566370614359172);
     o.ray = make_float4(dx / r, dy / r, dz / r, oy);
     o.tmax = r * 0.9990234375f;
     if (!(r > 0.0f) || !(r <= 3.4028234663852886e38f)) {      // no direction: not traced (tmax 0 accepts no hit), weighs 0
@@ -93,6 +95,29 @@ __device__ __forceinline__ double gather_sum(const double* __restrict__ w, const
 __device__ __forceinline__ double gather_expected(double nn, double sum, int32_t samples, int32_t photons_equiv)
 {
     return nn == 0.0 ? 0.0 : ((double)photons_equiv * (0.5 * nn)) * (sum / (double)samples);
+}
+
+// The face a sample arrives on (include/uvrt.h "face-resolved gather and bounces"): face 0 is the side n = cross(e1, e2) points
+// to, and light travelling along D reaches it iff n.D < 0.  c is GatherSample::c (a NaN, from a sample that weighs 0, counts
+// as face 1).
+__device__ __forceinline__ uint8_t gather_face(double c)
+{
+    return c < 0.0 ? (uint8_t)0 : (uint8_t)1;
+}
+
+// gather_sum split by the face of each sample: sum0 + sum1 visit the samples gather_sum visits, each in sample order from
+// +0.0 (a sample of the other face is skipped: every term is >= +0, so adding +0.0 for it would leave the same bits)
+__device__ __forceinline__ void gather_face_sums(const double* __restrict__ w, const uint8_t* __restrict__ occluded,
+                                                 const uint8_t* __restrict__ face, size_t at, int32_t samples, double& sum0,
+                                                 double& sum1)
+{
+    sum0 = 0.0;
+    sum1 = 0.0;
+    for (int32_t s = 0; s < samples; ++s) {
+        const double x = occluded[at + s] ? 0.0 : w[at + s];
+        if (face[at + s]) sum1 = sum1 + x;
+        else sum0 = sum0 + x;
+    }
 }
 
 // expected[t] (the bits of gather_expected) and the variance of that estimate from a second pass over the samples in order

@@ -12,6 +12,9 @@
 // One thread per triangle walks its S2 links in sample order: the contract fixes the order of the sum.  The loads of a
 // group of samples are issued together, only the adds are chained.  One plain launch per bounce; every loop is bounded by
 // S2.  No atomics.  Only + - * / sqrt: this file is built without contraction, every operator below is one rounding.
+// The sided forms at the end of the file (include/uvrt.h "face-resolved gather and bounces") keep the face
+// of the hit triangle a ray arrives on in bit 0 of the link and one irradiance per face, interleaved e[2 * h + face]: the same
+// layout, loads and launch structure, two sums per triangle.
 #include "uvrt_device.h"
 
 namespace uvrt {
@@ -105,6 +108,107 @@ void launch_links_apply(const LinksApplyParams& p, hipStream_t s)
 {
     if (p.tri_count <= 0) return;
     hipLaunchKernelGGL(k_links_apply, dim3((unsigned)((p.tri_count + LINKS_APPLY_BLOCK - 1) / LINKS_APPLY_BLOCK)),
+                       dim3(LINKS_APPLY_BLOCK), 0, s, p);
+}
+
+// ---- the sided forms: every triangle an opaque sheet whose two faces keep their own irradiance ----
+
+// k_links_store with the arrival face in bit 0: a = 0 when the ray meets the side n_h points to (n_h . dir < 0).  dir is the
+// f32 direction k_indirect_generate wrote into the chunk's rays; the closest-hit kernel reads them only.
+__global__ __launch_bounds__(256) void k_links_store_sided(LinksStoreParams p, const float4* __restrict__ rays)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)p.tri_count * p.samples) return;
+    const uint32_t s = (uint32_t)i / (uint32_t)p.tri_count, lt = (uint32_t)i - s * (uint32_t)p.tri_count;    // (T * S2 < 2^31)
+    const uint32_t t = (uint32_t)p.first_tri + lt;
+    const size_t r = (size_t)lt * (size_t)p.samples + s;
+    const uint32_t h = p.hit[r].y;
+    int32_t link = -1;
+    if (h < (uint32_t)p.T && h != t) {
+        double nx, ny, nz;
+        const double nh = tri_normal(p.gtris[(size_t)h * 3 + 1], p.gtris[(size_t)h * 3 + 2], nx, ny, nz);
+        const float4 d = rays[r];
+        const double c = (nx * (double)d.x + ny * (double)d.y) + nz * (double)d.z;
+        if (nh > 0.0) link = (int32_t)((h << 1) | (c < 0.0 ? 0u : 1u));          // (S2 >= 2: h < T < 2^30)
+    }
+    p.links[(size_t)s * (size_t)p.T + t] = link;
+}
+
+void launch_links_store_sided(const LinksStoreParams& p, const float4* rays, hipStream_t s)
+{
+    const int64_t n = (int64_t)p.tri_count * p.samples;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_links_store_sided, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, rays);
+}
+
+__global__ __launch_bounds__(256) void k_links_irradiance_sided(const float4* __restrict__ gtris, const double* __restrict__ faces,
+                                                                double* __restrict__ e, int32_t T)
+{
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= T) return;
+    const double nh = tri_normal_len(gtris[(size_t)h * 3 + 1], gtris[(size_t)h * 3 + 2]);
+    e[(size_t)h * 2 + 0] = nh > 0.0 ? faces[h] / (0.5 * nh) : 0.0;
+    e[(size_t)h * 2 + 1] = nh > 0.0 ? faces[(size_t)T + h] / (0.5 * nh) : 0.0;
+}
+
+void launch_links_irradiance_sided(const float4* gtris, const double* faces, double* e, int32_t T, hipStream_t s)
+{
+    if (T <= 0) return;
+    hipLaunchKernelGGL(k_links_irradiance_sided, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, gtris, faces, e, T);
+}
+
+// One thread per triangle, one accumulator per face: sample s leaves face s & 1, so the even slots of a group of the unroll
+// go to face 0 and the odd ones to face 1 (LINKS_UNROLL is even and s starts at 0).  The loads of a group are issued together
+// as in k_links_apply; the two chains of adds are independent, each half as long as k_links_apply's one.  A sided link is the
+// index into the interleaved plane, so linked_value is the plain kernel's load.
+__global__ __launch_bounds__(LINKS_APPLY_BLOCK) void k_links_apply_sided(LinksApplyParams p)
+{
+    static_assert(LINKS_UNROLL % 2 == 0, "a group of the unroll holds whole (face 0, face 1) pairs");
+    const int i = blockIdx.x * LINKS_APPLY_BLOCK + threadIdx.x;
+    if (i >= p.tri_count) return;
+    const size_t t = (size_t)p.first_tri + (size_t)i;
+    const size_t T = (size_t)p.T;
+    const double nn = tri_normal_len(p.gtris[t * 3 + 1], p.gtris[t * 3 + 2]);
+    const int32_t* __restrict__ lp = p.links + t;
+    const double* __restrict__ e = p.e_in;
+    double sum0 = 0.0, sum1 = 0.0;
+    int32_t s = 0;
+    for (; s + LINKS_UNROLL <= p.samples; s += LINKS_UNROLL) {
+        int32_t l[LINKS_UNROLL];
+        double v[LINKS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LINKS_UNROLL; ++u) l[u] = lp[(size_t)(s + u) * T];
+#pragma unroll
+        for (int u = 0; u < LINKS_UNROLL; ++u) v[u] = linked_value(e, l[u]);
+#pragma unroll
+        for (int u = 0; u < LINKS_UNROLL; u += 2) {
+            sum0 = sum0 + v[u];
+            sum1 = sum1 + v[u + 1];
+        }
+    }
+    for (; s + 2 <= p.samples; s += 2) {            // (samples is even)
+        const int32_t l0 = lp[(size_t)s * T], l1 = lp[(size_t)(s + 1) * T];
+        const double v0 = linked_value(e, l0), v1 = linked_value(e, l1);
+        sum0 = sum0 + v0;
+        sum1 = sum1 + v1;
+    }
+    const double k = (double)p.reflectance * (0.5 * nn);
+    const double g0 = nn == 0.0 ? 0.0 : k * ((2.0 * sum0) / (double)p.samples);
+    const double g1 = nn == 0.0 ? 0.0 : k * ((2.0 * sum1) / (double)p.samples);
+    if (p.e_out) {
+        p.e_out[t * 2 + 0] = nn > 0.0 ? g0 / (0.5 * nn) : 0.0;
+        p.e_out[t * 2 + 1] = nn > 0.0 ? g1 / (0.5 * nn) : 0.0;
+    }
+    const double g = g0 + g1;
+    const double total = p.total_in ? p.total_in[t] + g : g;
+    if (p.total_out) p.total_out[t] = total;
+    if (p.expected) p.expected[t] = p.add ? p.expected[t] + total : total;
+}
+
+void launch_links_apply_sided(const LinksApplyParams& p, hipStream_t s)
+{
+    if (p.tri_count <= 0) return;
+    hipLaunchKernelGGL(k_links_apply_sided, dim3((unsigned)((p.tri_count + LINKS_APPLY_BLOCK - 1) / LINKS_APPLY_BLOCK)),
                        dim3(LINKS_APPLY_BLOCK), 0, s, p);
 }
 

@@ -11,7 +11,10 @@
 // of the arguments.  With the context's variance state on (uvrt_set_gather_variance) k_gather_reduce_var<MODE> takes
 // k_gather_reduce's place: the same expected[t], and beside it the variance of that estimate from a second pass over the same
 // samples.  The sample rule and the sums are uvrt_gather_sample.h's, which the batched gather
-// (uvrt_gather_batch.hip) shares.  This file is built without contraction, every operator is one rounding.
+// (uvrt_gather_batch.hip) shares.  With the context's faces state on (uvrt_set_gather_faces) k_gather_generate_faces<MODE> takes
+// k_gather_generate's place -- the same arrays and a byte per sample, the face it arrives on -- and k_gather_reduce_faces runs
+// beside the reduce kernel of the state and writes the two face planes.
+// This file is built without contraction, every operator is one rounding.
 #include "uvrt_query.h"
 #include "uvrt_gather_sample.h"
 
@@ -81,6 +84,59 @@ void launch_gather_generate(const GatherGenParams& p, hipStream_t s)
     const dim3 grid((unsigned)((n + 255) / 256));
     if (p.mode == 1) hipLaunchKernelGGL((k_gather_generate<1>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((k_gather_generate<0>), grid, dim3(256), 0, s, p);
+}
+
+// k_gather_generate<MODE> that also keeps the face each sample arrives on (uvrt_gather_sample.h gather_face), a byte beside w:
+// launched in its place while the context's faces state is on (include/uvrt.h uvrt_set_gather_faces)
+template <int MODE>
+__global__ __launch_bounds__(256) void k_gather_generate_faces(GatherGenParams g, uint8_t* __restrict__ face)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)g.tri_count * g.samples) return;
+    const uint32_t lt = (uint32_t)(i / g.samples), s = (uint32_t)(i - (int64_t)lt * g.samples);
+    const uint32_t t = (uint32_t)g.first_tri + lt;
+    const GatherLamp l = {g.fx, g.fy, g.fz, g.tx, g.ty, g.tz, g.light_length, g.seed, g.seed_hash};
+    const GatherSample o = gather_sample<MODE>(g.gtris, l, t, s, g.samples);
+    g.rays[i] = o.ray;
+    g.oxz[i] = o.oxz;
+    g.tmax[i] = o.tmax;
+    g.w[i] = o.w;
+    face[i] = gather_face(o.c);
+}
+
+void launch_gather_generate_faces(const GatherGenParams& p, uint8_t* face, hipStream_t s)
+{
+    const int64_t n = (int64_t)p.tri_count * p.samples;
+    if (n <= 0) return;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (p.mode == 1) hipLaunchKernelGGL((k_gather_generate_faces<1>), grid, dim3(256), 0, s, p, face);
+    else hipLaunchKernelGGL((k_gather_generate_faces<0>), grid, dim3(256), 0, s, p, face);
+}
+
+// The face planes: faces[f * T + t] = what k_gather_reduce gives from the samples that arrive on face f alone.  It runs beside
+// the reduce kernel of the state (which writes expected[t], and variance[t], as ever), one thread per triangle, two sums in
+// sample order.
+__global__ __launch_bounds__(256) void k_gather_reduce_faces(const float4* __restrict__ gtris, const double* __restrict__ w,
+                                                             const uint8_t* __restrict__ occluded, const uint8_t* __restrict__ face,
+                                                             double* __restrict__ faces, int32_t first_tri, int32_t tri_count,
+                                                             int32_t samples, int32_t photons_equiv, int32_t T)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= tri_count) return;
+    const size_t t = (size_t)first_tri + (size_t)i;
+    const double nn = gather_tri_nn(gtris, t);
+    double sum0, sum1;
+    gather_face_sums(w, occluded, face, (size_t)i * (size_t)samples, samples, sum0, sum1);
+    faces[t] = gather_expected(nn, sum0, samples, photons_equiv);
+    faces[(size_t)T + t] = gather_expected(nn, sum1, samples, photons_equiv);
+}
+
+void launch_gather_reduce_faces(const float4* gtris, const double* w, const uint8_t* occluded, const uint8_t* face, double* faces,
+                                int32_t first_tri, int32_t tri_count, int32_t samples, int32_t photons_equiv, int32_t T, hipStream_t s)
+{
+    if (tri_count <= 0) return;
+    hipLaunchKernelGGL(k_gather_reduce_faces, dim3((unsigned)((tri_count + 255) / 256)), dim3(256), 0, s, gtris, w, occluded, face,
+                       faces, first_tri, tri_count, samples, photons_equiv, T);
 }
 
 __global__ __launch_bounds__(256) void k_gather_reduce(const float4* __restrict__ gtris, const double* __restrict__ w,

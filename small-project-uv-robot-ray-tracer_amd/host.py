@@ -84,6 +84,9 @@ SYMBOLS = [
     ("uvrt_host_rt_plan_gather_batch", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
                                               C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                               _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_reflect_sided", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                                      C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
+                                                      C.c_int, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -101,10 +104,10 @@ _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIt
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
            "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling", "gatherRelError",
-           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces", "gatherBatch"}
+           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
                "photonMapSize", "viewMode", "gatherSamples", "gatherSampling", "gatherMaxExtra",
-               "reflectSamples", "reflectBounces", "gatherBatch"}
+               "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 
@@ -230,6 +233,8 @@ class RayTracer:
         if name in _FIELDS:
             if name == "reflectBounces" and not (0 <= int(value) <= 16 and int(value) == value):
                 raise ValueError("reflectBounces must be an integer in [0, 16]")
+            if name == "reflectSided" and not (int(value) in (0, 1) and int(value) == value):
+                raise ValueError("reflectSided must be 0 or 1")
             if name == "gatherBatch":
                 _check_gather_batch(value)
             self._L.uvrt_host_rt_set(self._h, name.encode(), float(value))
@@ -327,12 +332,14 @@ class RayTracer:
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, **args)
 
     def PlanDurationsReflect(self, reflectance, reflect_samples=16, gather_rel_error=0.0, gather_max_extra=64, reflect_bounces=0,
-                             **plan):
+                             reflect_sided=0, **plan):
         """PlanDurations(**plan) with PlanOptions::reflectance = rho and reflectSamples: every gather launch of the plan gets one
         diffuse bounce before its capture.  rho > 0 needs gather_samples > 0 and refuses gather_confidence: the
         variance plane knows nothing of the indirect part.  0 is PlanDurations / PlanDurationsRefined, bit for bit.
         reflect_bounces = K in [1, 16] (PlanOptions::reflectBounces): K bounces over hit links recorded once per scene instead of
-        the bounce traced per launch; 0 is the traced bounce, bit for bit."""
+        the bounce traced per launch; 0 is the traced bounce, bit for bit.
+        reflect_sided = 1 (PlanOptions::reflectSided): those K bounces face-resolved (DESIGN.md 21); it needs rho > 0 and K >= 1 and
+        refuses gather_batch >= 2; 0 is the two-sided bounces, bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
                     gather_sampling=0, gather_confidence=0.0, gather_batch=0)
         unknown = set(plan) - set(args)
@@ -344,6 +351,14 @@ class RayTracer:
             raise ValueError("reflect_bounces must be an integer in [0, 16]")
         if not (0.0 <= rho <= 1.0):
             raise ValueError("reflectance must be in [0, 1]")
+        if reflect_sided not in (0, 1) or int(reflect_sided) != reflect_sided:
+            raise ValueError("reflect_sided must be 0 or 1")
+        if reflect_sided and not rho > 0.0:
+            raise ValueError("reflect_sided needs reflectance > 0: without a bounce there are no faces to resolve")
+        if reflect_sided and int(reflect_bounces) < 1:
+            raise ValueError("reflect_sided needs reflect_bounces >= 1: the traced single bounce has no face-resolved form")
+        if reflect_sided and _check_gather_batch(args["gather_batch"]):
+            raise ValueError("reflect_sided is not supported with gather_batch >= 2: a gather batch keeps no face planes")
         if rho > 0.0 and not args["gather_samples"]:
             raise ValueError("reflectance needs gather_samples > 0")
         if rho > 0.0 and float(args["gather_confidence"]) != 0.0:
@@ -351,11 +366,12 @@ class RayTracer:
         if rho > 0.0 and (s2 < 2 or s2 > 4096 or s2 & 1):
             raise ValueError("reflect_samples must be even and in [2, 4096]")
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, reflectance=rho,
-                                    reflect_samples=s2, reflect_bounces=int(reflect_bounces), **args)
+                                    reflect_samples=s2, reflect_bounces=int(reflect_bounces), reflect_sided=int(reflect_sided),
+                                    **args)
 
     def _plan_durations(self, min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
                         gather_confidence, gather_rel_error, gather_max_extra, reflectance=0.0, reflect_samples=16,
-                        reflect_bounces=0, gather_batch=0):
+                        reflect_bounces=0, gather_batch=0, reflect_sided=0):
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
         B = _check_gather_batch(gather_batch)
@@ -374,6 +390,13 @@ class RayTracer:
         if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
             raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if reflect_sided:
+            self._L.uvrt_host_rt_plan_gather_reflect_sided(self._h, -1.0 if min_dose is None else float(min_dose),
+                                                           int(min_photons), float(margin), float(rel_gap), int(max_iterations),
+                                                           _addr(keep), int(gather_samples), int(gather_sampling), z, tau, extra,
+                                                           float(reflectance), int(reflect_samples), int(reflect_bounces), 1,
+                                                           C.byref(rep), C.byref(seed))
+            return _plan_result(self, rep, seed)
         if B:
             self._L.uvrt_host_rt_plan_gather_batch(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
                                                    float(margin), float(rel_gap), int(max_iterations), _addr(keep),

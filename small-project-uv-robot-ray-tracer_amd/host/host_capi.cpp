@@ -29,7 +29,8 @@ std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>
 RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
                                     const unsigned char* mask, int gather_samples, int gather_sampling = 0,
                                     double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64,
-                                    float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0, int gather_batch = 0)
+                                    float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0, int gather_batch = 0,
+                                    int reflect_sided = 0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
@@ -42,6 +43,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
     o.reflectSamples = reflect_samples;
     o.reflectBounces = reflect_bounces;
     o.gatherBatch = gather_batch;
+    o.reflectSided = reflect_sided;
     return o;
 }
 
@@ -222,6 +224,17 @@ void uvrt_host_rt_plan_gather_batch(void* r, float min_dose, int min_photons, do
                                                        gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
                                                        reflectance, reflect_samples, reflect_bounces, gather_batch), seed);
 }
+// the same with PlanOptions::reflectSided: face-resolved bounces (include/uvrt.h uvrt_gather_indirect_linked_sided)
+void uvrt_host_rt_plan_gather_reflect_sided(void* r, float min_dose, int min_photons, double margin, double rel_gap,
+                                            int max_iterations, const unsigned char* mask, int gather_samples, int gather_sampling,
+                                            double gather_confidence, double gather_rel_error, int gather_max_extra,
+                                            float reflectance, int reflect_samples, int reflect_bounces, int reflect_sided,
+                                            uvrt_plan_report* rep, unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
+                                                       reflectance, reflect_samples, reflect_bounces, 0, reflect_sided), seed);
+}
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
 {
@@ -253,6 +266,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
     F(gatherSampling, int) F(gatherRelError, double) F(gatherMaxExtra, int)
     F(reflectance, float) F(reflectSamples, int) F(reflectBounces, int) F(gatherBatch, int)
+    F(reflectSided, int)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

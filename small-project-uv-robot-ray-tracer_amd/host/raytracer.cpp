@@ -187,7 +187,7 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
     RunLaunches(Launches(), photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch);
+                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided);
 }
 
 void RayTracer::ComputeSegments()
@@ -196,7 +196,7 @@ void RayTracer::ComputeSegments()
     for (const RouteLaunch& l : Launches())
         if (l.kind == UVRT_LAUNCH_SWEEP) sweeps.push_back(l);
     RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch);
+                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided);
 }
 
 // the uvrt_gather_params of a gather launch with seed `seed`
@@ -214,14 +214,16 @@ static uvrt_gather_params gather_params(const RouteLaunch& l, float lightLength,
 }
 
 void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
-                            double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch)
+                            double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided)
 {
     if (batch < 0 || batch > UVRT_GATHER_BATCH_MAX) fatal("gatherBatch must be in [0, 64]");
+    if (sided != 0 && batch >= 2) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
     // (a refine that RunLaunch is about to refuse is left to it: its batch would be refused first, with another message)
     const bool refineOk = relError == 0.0 || (samples >= 2 && relError > 0.0 && std::isfinite(relError));
     if (batch < 2 || samples <= 0 || !refineOk) {
         for (const RouteLaunch& l : list)
-            RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS, reflectK);
+            RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS, reflectK, -1,
+                      sided);
         return;
     }
     // groups of up to `batch` consecutive launches: one shadow-ray pass each (include/uvrt.h uvrt_gather_direct_batch), then
@@ -254,10 +256,16 @@ void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, i
 }
 
 void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                          double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot)
+                          double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot, int sided)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (reflectK < 0 || reflectK > 16) fatal("reflectBounces must be in [0, 16]");
+    if (sided != 0) {
+        if (sided != 1) fatal("reflectSided must be 0 or 1");
+        if (reflect == 0.0f) fatal("reflectSided needs reflectance > 0 (without a bounce there are no faces to resolve)");
+        if (reflectK < 1) fatal("reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)");
+        if (batchSlot >= 0) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
+    }
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
     if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
     if (reflect != 0.0f && samples < 1) fatal("reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)");
@@ -268,9 +276,16 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
         const uvrt_gather_params g = gather_params(l, lightLength, samples, gatherLaunches++, photons);
         check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
         // the launch's planes: traced here, or taken from the batch that RunLaunches has traced (batchSlot >= 0)
+        // (reflectSided: with the faces state on around it, as the variance state is for the refine; the context's is put back)
         auto gather = [&] {
-            if (batchSlot >= 0) check(uvrt_gather_batch_select(ctx, batchSlot), "gather_batch_select");
-            else check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+            if (batchSlot >= 0) { check(uvrt_gather_batch_select(ctx, batchSlot), "gather_batch_select"); return; }
+            int32_t faces0 = 0;
+            if (sided) {
+                check(uvrt_get_gather_faces(ctx, &faces0), "get_gather_faces");
+                check(uvrt_set_gather_faces(ctx, 1), "set_gather_faces");
+            }
+            check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
+            if (sided) check(uvrt_set_gather_faces(ctx, faces0), "set_gather_faces");
         };
         if (relError != 0.0) {
             // the adaptive gather (raytracer.h gatherRelError): the variance plane on for this launch, then the refine
@@ -294,20 +309,26 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
             const uint32_t linkSeed = 0x85EBCA6Bu;
             int32_t info[4];
             check(uvrt_indirect_links_info(ctx, info), "indirect_links_info");
-            if (info[0] != reflectS || (uint32_t)info[1] != linkSeed) {
+            if (info[0] != reflectS || (uint32_t)info[1] != linkSeed || info[3] != sided) {
                 uvrt_links_params lp;
                 memset(&lp, 0, sizeof lp);
                 lp.samples = reflectS;
                 lp.seed = linkSeed;
-                check(uvrt_indirect_links_build(ctx, &lp), "indirect_links_build");
+                if (sided) check(uvrt_indirect_links_build_sided(ctx, &lp), "indirect_links_build_sided");
+                else check(uvrt_indirect_links_build(ctx, &lp), "indirect_links_build");
             }
             uvrt_linked_params kp;
             memset(&kp, 0, sizeof kp);
             kp.reflectance = reflect;
             kp.bounces = reflectK;
             kp.add = 1;
-            check(uvrt_indirect_source_from_expected(ctx), "indirect_source_from_expected");
-            check(uvrt_gather_indirect_linked(ctx, &kp, 0, triangleCount), "gather_indirect_linked");
+            if (sided) {
+                // the face-resolved bounces (raytracer.h reflectSided): the gather's face planes are the emitter, no snapshot
+                check(uvrt_gather_indirect_linked_sided(ctx, &kp, 0, triangleCount), "gather_indirect_linked_sided");
+            } else {
+                check(uvrt_indirect_source_from_expected(ctx), "indirect_source_from_expected");
+                check(uvrt_gather_indirect_linked(ctx, &kp, 0, triangleCount), "gather_indirect_linked");
+            }
         } else if (reflect > 0.0f) {
             // one diffuse bounce (raytracer.h reflectance): the finished direct plane is the emitter, its bounce is added to it
             uvrt_indirect_params ip;
@@ -339,13 +360,13 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
     RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
     RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -464,7 +485,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
 void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch)
+                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -481,7 +502,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch);
+        RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch, sided);
         Shade();
         ++currIterations;
     }
@@ -554,6 +575,12 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     }
     if (opt.reflectBounces < 0 || opt.reflectBounces > 16) fatal("PlanDurations: reflectBounces must be in [0, 16]");
     if (opt.gatherBatch < 0 || opt.gatherBatch > UVRT_GATHER_BATCH_MAX) fatal("PlanDurations: gatherBatch must be in [0, 64]");
+    if (opt.reflectSided != 0) {
+        if (opt.reflectSided != 1) fatal("PlanDurations: reflectSided must be 0 or 1");
+        if (opt.reflectance == 0.0f) fatal("PlanDurations: reflectSided needs reflectance > 0 (without a bounce there are no faces to resolve)");
+        if (opt.reflectBounces < 1) fatal("PlanDurations: reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)");
+        if (opt.gatherBatch >= 2) fatal("PlanDurations: reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
+    }
     if (opt.reflectance != 0.0f) {
         if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
         if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
@@ -565,7 +592,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
         r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
-                              opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch);
+                              opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch, opt.reflectSided);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -724,6 +751,7 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
         o << "    <reflectance>" << float_str(reflectance) << "</reflectance>\n";
         o << "    <reflect_samples>" << reflectSamples << "</reflect_samples>\n";
         if (reflectBounces > 0) o << "    <reflect_bounces>" << reflectBounces << "</reflect_bounces>\n";
+        if (reflectBounces > 0 && reflectSided != 0) o << "    <reflect_sided>1</reflect_sided>\n";
     }
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
@@ -770,6 +798,8 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("reflect_samples"))) to_int(trim(e->text), &reflectSamples);
     reflectBounces = 0;
     if ((e = root.child("reflect_bounces"))) to_int(trim(e->text), &reflectBounces);
+    reflectSided = 0;
+    if ((e = root.child("reflect_sided"))) to_int(trim(e->text), &reflectSided);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

@@ -143,6 +143,9 @@ public:
         // K in [1, 16] with reflectance > 0: the plan's launches take K bounces over recorded hit links instead of the traced
         // one (RayTracer::reflectBounces below).  0 (default): the traced bounce, bit for bit.  Outside [0, 16]: fatal.
         int reflectBounces = 0;
+        // 1 with reflectance > 0 and reflectBounces >= 1: the plan's bounces are face-resolved (RayTracer::reflectSided below).
+        // 0 (default): the two-sided bounces, bit for bit.  1 with reflectance 0, reflectBounces 0 or gatherBatch >= 2: fatal.
+        int reflectSided = 0;
         // B in [2, 64]: the plan's gather launches are traced in groups of up to B (RayTracer::gatherBatch below).  The plan's
         // own, like S.  0 (default) and 1: launch by launch.  Durations, report and every captured column are the same bits
         // for every B.  Outside [0, 64]: fatal.
@@ -222,6 +225,16 @@ public:
     // Outside [0, 16]: fatal.  Without effect at reflectance 0.  Saved as <reflect_bounces> after <reflect_samples> when both
     // rho and K are > 0.
     int reflectBounces = 0;
+    // Face-resolved bounces (include/uvrt.h "face-resolved gather and bounces"): every triangle an opaque sheet
+    // whose two faces keep their own irradiance, so that the bounces conserve energy at every reflectance.  1 with reflectance
+    // > 0 and reflectBounces = K >= 1: every gather launch runs with the context's faces state on (put back after the launch; a
+    // refine may follow, the face planes then describe the first pass), the links are built with
+    // uvrt_indirect_links_build_sided (rebuilt when uvrt_indirect_links_info reports another sample count, seed or kind), and
+    // uvrt_gather_indirect_linked_sided(rho, K, add = 1) stands where the snapshot and the two-sided call stood.  0 (default):
+    // the bounces above, bit for bit.  1 is fatal with reflectance 0 (there is no bounce to resolve), with reflectBounces 0 (the
+    // traced single bounce has no face-resolved form) and with gatherBatch >= 2 (a gather batch keeps no face planes).  Saved
+    // as <reflect_sided>1</reflect_sided> after <reflect_bounces> when that tag is written and this is on.
+    int reflectSided = 0;
     // The batched direct gather (include/uvrt.h "batched direct gather").  gatherBatch = B in [2, 64] with
     // gatherSamples > 0: ComputeDosageMap and ComputeSegments walk their launches in groups of up to B consecutive ones; a
     // group's shadow rays are traced in one uvrt_gather_direct_batch (the seeds the launches would have taken, the variance
@@ -239,14 +252,14 @@ private:
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
     // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError);
     // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance), or with reflectK > 0 that many
-    // bounces over recorded hit links (reflectBounces).
+    // bounces over recorded hit links (reflectBounces), face-resolved with `sided` (reflectSided).
     // batchSlot >= 0: the launch's planes are those of launch batchSlot of the context's gather batch (RunLaunches).
     void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                   double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1);
+                   double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1, int sided = 0);
     // A list of launches through RunLaunch, in order (capture: every plane into its launch's column of a plan); with
     // samples > 0 and batch >= 2 in groups of up to `batch` behind one uvrt_gather_direct_batch each (gatherBatch).
     void RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
-                     double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch);
+                     double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0);
     long long rayCapacity = 0;                      // what ClearBuffers / RunLaunches last gave uvrt_resize_rays
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
@@ -254,7 +267,7 @@ private:
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
     void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra, float reflect, int reflectS, int reflectK, int batch);
+                           int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

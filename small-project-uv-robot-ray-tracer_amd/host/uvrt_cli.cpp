@@ -81,6 +81,11 @@
 //                                           launch then looks its sources up along them, and bounces 2..K come with it.  All launches
 //                                           see the same directions: the bounce's sampling error no longer averages out over a
 //                                           route, but S2 is paid once and can be much larger.  --save-route writes <reflect_bounces>
+//            [--reflect-sided]              with --reflect RHO > 0 and --reflect-bounces K: the K bounces are face-resolved
+//                                           (RayTracer::reflectSided, PlanOptions::reflectSided): every triangle is an
+//                                           opaque sheet whose two faces keep their own irradiance, so the bounces conserve energy
+//                                           at every RHO.  Refused without --reflect-bounces (the traced single bounce has no such
+//                                           form), with RHO = 0 and with --gather-batch B >= 2.  --save-route writes <reflect_sided>
 //            [--gather-batch B]             with --gather S or --plan-gather S: trace the gather launches in groups of up to B in
 //                                           [0, 64] (RayTracer::gatherBatch, PlanOptions::gatherBatch): one shadow-ray
 //                                           pass per group instead of one per launch.  0 (default) and 1: launch by launch.  B
@@ -149,7 +154,7 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
              const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence,
-             double refineTau, int refineMax, float reflect, int reflectS, int reflectK)
+             double refineTau, int refineMax, float reflect, int reflectS, int reflectK, int reflectSided)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -163,6 +168,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.reflectance = planGather > 0 ? reflect : 0.0f;
     opt.reflectSamples = reflectS;
     opt.reflectBounces = planGather > 0 ? reflectK : 0;
+    opt.reflectSided = planGather > 0 ? reflectSided : 0;
     opt.gatherBatch = planGather > 0 ? rt.gatherBatch : 0;   // (--gather-batch: --plan-verify recomputes in the same groups)
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
@@ -181,6 +187,8 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
             rt.reflectance = opt.reflectance;           // --plan-verify and --save-route: the plan's own bounce
             rt.reflectSamples = opt.reflectSamples;
             rt.reflectBounces = opt.reflectBounces;
+            rt.reflectSided = opt.reflectSided;
+            if (opt.reflectSided) printf("plan: face-resolved bounces\n");
             if (opt.reflectBounces > 0)
                 printf("plan: %d diffuse bounces over recorded hit links, reflectance %.8g, %d samples per triangle\n", opt.reflectBounces, (double)opt.reflectance, opt.reflectSamples);
             else
@@ -259,6 +267,7 @@ int main(int argc, char** argv)
     float reflect = -1.0f;                  // < 0: not given
     int reflectS = 16;
     int reflectK = 0;                       // 0: not given
+    int reflectSided = 0;                   // --reflect-sided
     int gatherBatch = -1;                   // < 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -364,6 +373,7 @@ int main(int argc, char** argv)
             }
             reflectK = (int)k;
         }
+        else if (!strcmp(argv[i], "--reflect-sided")) reflectSided = 1;
         else if (!strcmp(argv[i], "--gather-batch")) {
             need(1);
             char* end = nullptr;
@@ -388,6 +398,9 @@ int main(int argc, char** argv)
     if (reflect >= 0.0f && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--reflect needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (reflect >= 0.0f && planConfidence >= 0.0) { fprintf(stderr, "--reflect cannot be combined with --plan-confidence (the variance plane knows nothing of the indirect part)\n"); return 2; }
     if (reflectK > 0 && !(reflect >= 0.0f)) { fprintf(stderr, "--reflect-bounces needs --reflect RHO[,S2] (with --gather S or --plan-gather S)\n"); return 2; }
+    if (reflectSided && reflectK < 1) { fprintf(stderr, "--reflect-sided needs --reflect-bounces K (with --reflect RHO[,S2]): the traced single bounce has no face-resolved form\n"); return 2; }
+    if (reflectSided && !(reflect > 0.0f)) { fprintf(stderr, "--reflect-sided needs --reflect RHO with RHO > 0: without a bounce there are no faces to resolve\n"); return 2; }
+    if (reflectSided && gatherBatch >= 2) { fprintf(stderr, "--reflect-sided cannot be combined with --gather-batch B >= 2 (a gather batch keeps no face planes)\n"); return 2; }
     if (gatherBatch >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-batch needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
@@ -423,7 +436,7 @@ int main(int argc, char** argv)
     if (gather >= 0) rayTracer.gatherSamples = gather;
     if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
     if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
-    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; }
+    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; rayTracer.reflectSided = reflectSided; }
     if (gatherBatch >= 0) rayTracer.gatherBatch = gatherBatch;
     if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectance = 0.0f;    // (the route file's own <reflectance>: a plan's bounce is --reflect's)
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
@@ -449,7 +462,7 @@ int main(int argc, char** argv)
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
                                 gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax,
-                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK);
+                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK, reflectSided);
         save_route(rayTracer, saveRoute);
         return rc;
     }
