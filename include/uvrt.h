@@ -515,6 +515,55 @@ int uvrt_write_gather_faces(uvrt_ctx* ctx, int32_t face, const double* in, int32
 int uvrt_indirect_links_build_sided(uvrt_ctx* ctx, const uvrt_links_params* params);
 int uvrt_gather_indirect_linked_sided(uvrt_ctx* ctx, const uvrt_linked_params* params, int32_t first_tri, int32_t tri_count);
 
+/* ---- per-face reflectance: the face-resolved bounces with a reflectance map instead of one rho ----
+ * The reflectance planes.  rho[f][t], f32[2][T], plane-major like `faces`: the diffuse reflectance of face f of triangle t, in
+ * the face convention above (face 0 is the side cross(e1, e2) points to).  A scene has no planes until a call below makes them;
+ * uvrt_set_scene drops them and every other call above leaves them bit for bit.  They are not a uvrt_device_ptr index.
+ *   uvrt_fill_reflectance   makes the planes if absent and sets all 2*T entries to rho (on the stream, behind outstanding work).
+ *   uvrt_write_reflectance  makes the planes if absent -- zeroed, so an unlisted face absorbs everything and never overstates
+ *                           a dose -- then writes [first, first + count) of plane `face`; synchronises, like
+ *                           uvrt_write_gather_faces.
+ *   uvrt_read_reflectance   the same range back; UVRT_ERR_INVALID when there are no planes ("no map" is not "rho = 0").
+ *   uvrt_reflectance_info   *have = 1 when the scene has planes, else 0.
+ *   uvrt_drop_reflectance   frees them (nothing to do when there are none).
+ * Every value must be finite and in [0, 1]; the host checks the whole input before anything is uploaded.  A bad value, a face
+ * other than 0 / 1, a range outside [0, T), a null argument or no scene: UVRT_ERR_INVALID with nothing changed, and planes that
+ * did not exist are not made.
+ *
+ * uvrt_gather_indirect_linked_mapped reads faces[2][T] (made zeroed when absent, never written), the SIDED links and rho, and
+ * writes only expected[first_tri .. first_tri + tri_count).  Everything f64, every operator one rounding, L = link[t][s],
+ * nn_t = |cross(e1, e2)|:
+ *     e_0[f][h] = nn_h > 0 ? faces[f][h] / (0.5*nn_h) : 0.0                                      f = 0, 1; all h
+ *     r_b[f][h] = (double)rho[f][h] * e_b[f][h]                                                   what face f of h sends back
+ *     for b = 1..K, f = 0, 1:
+ *       g_b[f][t] = nn_t == 0 ? 0.0
+ *                 : (0.5*nn_t) * ((2.0 * sum_{s = f, f+2, .. < S2} (L >= 0 ? r_{b-1}[L & 1][L >> 1] : 0.0)) / (double)S2)
+ *       e_b[f][t] = nn_t > 0 ? g_b[f][t] / (0.5*nn_t) : 0.0
+ *     G_b[t]      = g_b[0][t] + g_b[1][t]
+ *     total[t]    = (..((G_1[t] + G_2[t]) + G_3[t]) .. + G_K[t])
+ *     expected[t] = add ? expected[t] + total[t] : total[t]
+ * The reflectance belongs to the face that EMITS -- the face the link arrives on -- not to the receiver: with one rho the two
+ * placements are the same number, with a map only this one is physics.  The sums run in ascending s from +0.0, without atomics;
+ * bounces before the last are evaluated for all T triangles, so the result depends neither on the range nor on its cut into
+ * calls; max e_b <= max rho * max e_{b-1} up to rounding.  With rho == 1.0f everywhere `total` is that of
+ * uvrt_gather_indirect_linked_sided(reflectance = 1) bit for bit (1.0*x is exact); with any other constant c the two differ by
+ * rounding alone: |mapped / sided - 1| <= K * (S2 + 16) * 2^-53 wherever the sided value is > 0, zeros in the same places.
+ * The call traces nothing, works in any flavour (one plain kernel launch per bounce), leaves and forgets exactly what
+ * uvrt_gather_indirect_linked_sided leaves and forgets, and leaves rho.
+ * UVRT_ERR_INVALID with nothing changed: a null argument, no scene, no links, plain links, no reflectance planes, bounces
+ * outside [1, 16], add other than 0 / 1, non-zero reserved, a range outside [0, T]. */
+int uvrt_fill_reflectance(uvrt_ctx* ctx, float rho);
+int uvrt_write_reflectance(uvrt_ctx* ctx, int32_t face, const float* in, int32_t first, int32_t count);
+int uvrt_read_reflectance(uvrt_ctx* ctx, int32_t face, float* out, int32_t first, int32_t count);
+int uvrt_reflectance_info(uvrt_ctx* ctx, int32_t* have);
+int uvrt_drop_reflectance(uvrt_ctx* ctx);
+typedef struct {
+    int32_t  bounces;       /* K: in [1, 16] */
+    int32_t  add;           /* 0: expected[t] = total[t];  1: expected[t] = expected[t] + total[t] */
+    int32_t  reserved[2];   /* 0 */
+} uvrt_mapped_params;
+int uvrt_gather_indirect_linked_mapped(uvrt_ctx* ctx, const uvrt_mapped_params* params, int32_t first_tri, int32_t tri_count);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).

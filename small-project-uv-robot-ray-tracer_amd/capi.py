@@ -156,6 +156,12 @@ SYMBOLS = [
     ("uvrt_write_gather_faces", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
     ("uvrt_indirect_links_build_sided", C.c_int, [_vp, _vp]),
     ("uvrt_gather_indirect_linked_sided", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_fill_reflectance", C.c_int, [_vp, _f32]),
+    ("uvrt_write_reflectance", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_read_reflectance", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_reflectance_info", C.c_int, [_vp, C.POINTER(_i32)]),
+    ("uvrt_drop_reflectance", C.c_int, [_vp]),
+    ("uvrt_gather_indirect_linked_mapped", C.c_int, [_vp, _vp, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -192,6 +198,11 @@ class LinksParams(C.Structure):
 class LinkedParams(C.Structure):
     """uvrt_linked_params (include/uvrt.h)"""
     _fields_ = [("reflectance", C.c_float), ("bounces", C.c_int32), ("add", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MappedParams(C.Structure):
+    """uvrt_mapped_params (include/uvrt.h)"""
+    _fields_ = [("bounces", C.c_int32), ("add", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class PlanParams(C.Structure):
@@ -765,6 +776,42 @@ class Ctx:
         prm.add = int(add)
         self._ck(self._L.uvrt_gather_indirect_linked_sided(self._h, C.byref(prm), int(first_tri),
                                                            self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    # ---- per-face reflectance: the planes rho[2][T] and the face-resolved bounces that read them ----
+    def fill_reflectance(self, rho):
+        """makes the reflectance planes if absent and sets all 2 * T entries to rho"""
+        self._ck(self._L.uvrt_fill_reflectance(self._h, float(np.float32(rho))))
+
+    def write_reflectance(self, face, values, first=0):
+        """host values into rho[face][first, first + len(values)); planes that did not exist are made zeroed"""
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        self._ck(self._L.uvrt_write_reflectance(self._h, int(face), _ptr(v), int(first), int(v.size)))
+
+    def read_reflectance(self, face, first=0, count=None):
+        """plane `face` (0 / 1) of the reflectance planes; an error when the scene has none"""
+        count = self.T - first if count is None else count
+        out = np.empty(max(int(count), 0), dtype=np.float32)
+        self._ck(self._L.uvrt_read_reflectance(self._h, int(face), _ptr(out), int(first), int(count)))
+        return out
+
+    def have_reflectance(self):
+        """True when the scene has reflectance planes"""
+        v = C.c_int32()
+        self._ck(self._L.uvrt_reflectance_info(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def drop_reflectance(self):
+        self._ck(self._L.uvrt_drop_reflectance(self._h))
+
+    def gather_indirect_linked_mapped(self, bounces, add=0, first_tri=0, tri_count=None, reserved=(0, 0)):
+        """expected[first_tri, +tri_count) = (add ? expected : 0) + `bounces` face-resolved bounces of the face planes over the
+        sided links, every emitting face with its own reflectance"""
+        prm = MappedParams()
+        prm.bounces = int(bounces)
+        prm.add = int(add)
+        prm.reserved[0], prm.reserved[1] = int(reserved[0]), int(reserved[1])
+        self._ck(self._L.uvrt_gather_indirect_linked_mapped(self._h, C.byref(prm), int(first_tri),
+                                                            self.T - int(first_tri) if tri_count is None else int(tri_count)))
 
     @property
     def seed(self):

@@ -187,6 +187,8 @@ struct uvrt_ctx {
         int32_t links_samples = 0, links_flavour = 0;
         int32_t links_kind = 0;                // 0: plain links (h or -1); 1: sided ((h << 1) | arrival face, or -1)
         uint32_t links_seed = 0;
+        DevBuf rho;                            // the reflectance planes f32[2][T] of uvrt_gather_indirect_linked_mapped
+        bool have_rho = false;                 // ... exist (a scene has none until a fill or a write makes them)
         GatherMemo gather_memo;                // a refine works on one scene's planes
         // the batch of the last successful uvrt_gather_direct_batch (uvrt_capi_gather_batch.hip; count 0: none): its launches,
         // range and sample count, the sampling mode, variance state and flavour it ran under, and its planes f64[count][T]

@@ -600,6 +600,24 @@ void launch_links_apply(const LinksApplyParams& p, hipStream_t s);
 void launch_links_store_sided(const LinksStoreParams& p, const float4* rays, hipStream_t s);
 void launch_links_irradiance_sided(const float4* gtris, const double* faces, double* e, int32_t T, hipStream_t s);
 void launch_links_apply_sided(const LinksApplyParams& p, hipStream_t s);
+// the mapped forms (include/uvrt.h "per-face reflectance"): rho[f * T + t], f32[2][T], the reflectance of
+// face f of t.  The radiosity: r[2 * h + f] = nn_h > 0 ? (double)rho[f * T + h] * (faces[f * T + h] / (0.5 * nn_h)) : 0.0, in
+// the sided irradiance's layout.  The apply: the sided apply without a reflectance on the receiver; r_out (not the last bounce)
+// takes rho of t's own faces times the irradiance they have just received, the next bounce's r_in.
+void launch_links_radiosity_sided(const float4* gtris, const double* faces, const float* rho, double* r, int32_t T, hipStream_t s);
+struct LinksMappedParams {
+    const float4* gtris;
+    const int32_t* links;    // [samples * T], sided
+    const float* rho;        // [2 * T]
+    const double* r_in;      // [2 * T]
+    double* r_out;           // [2 * T] or null (the last bounce)
+    const double* total_in;  // [T] or null (bounce 1)
+    double* total_out;       // [T] or null (the last bounce)
+    double* expected;        // [T] or null (every bounce but the last)
+    int32_t first_tri, tri_count, samples, T;
+    int32_t add;
+};
+void launch_links_apply_mapped(const LinksMappedParams& p, hipStream_t s);
 // test hook: out[(t - first_tri) * samples + s] = links[s * T + t]
 void launch_links_export(const int32_t* links, int32_t* out, int32_t first_tri, int32_t tri_count, int32_t samples, int32_t T,
                          hipStream_t s);

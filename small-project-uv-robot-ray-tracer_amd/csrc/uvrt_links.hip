@@ -15,6 +15,8 @@
 // The sided forms at the end of the file (include/uvrt.h "face-resolved gather and bounces") keep the face
 // of the hit triangle a ray arrives on in bit 0 of the link and one irradiance per face, interleaved e[2 * h + face]: the same
 // layout, loads and launch structure, two sums per triangle.
+// The mapped forms behind them (include/uvrt.h "per-face reflectance") give every face a reflectance of
+// its own: the planes of the bounces then hold radiosities rho[f][h] * e[f][h], multiplied in where a plane is written.
 #include "uvrt_device.h"
 
 namespace uvrt {
@@ -209,6 +211,81 @@ void launch_links_apply_sided(const LinksApplyParams& p, hipStream_t s)
 {
     if (p.tri_count <= 0) return;
     hipLaunchKernelGGL(k_links_apply_sided, dim3((unsigned)((p.tri_count + LINKS_APPLY_BLOCK - 1) / LINKS_APPLY_BLOCK)),
+                       dim3(LINKS_APPLY_BLOCK), 0, s, p);
+}
+
+// ---- the mapped forms: the sided bounce with a reflectance per face, rho[f * T + t] f32[2][T] ----
+// The reflectance belongs to the face that emits, so it is multiplied into the plane the links point at -- the radiosity
+// r[2 * h + f] = rho[f][h] * e[f][h] -- and the receiver's epilogue carries none.  The plane keeps the interleaved layout: a
+// sided link is still the index of what it points at and linked_value is still the load.
+
+__global__ __launch_bounds__(256) void k_links_radiosity_sided(const float4* __restrict__ gtris, const double* __restrict__ faces,
+                                                               const float* __restrict__ rho, double* __restrict__ r, int32_t T)
+{
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= T) return;
+    const double nh = tri_normal_len(gtris[(size_t)h * 3 + 1], gtris[(size_t)h * 3 + 2]);
+    r[(size_t)h * 2 + 0] = nh > 0.0 ? (double)rho[h] * (faces[h] / (0.5 * nh)) : 0.0;
+    r[(size_t)h * 2 + 1] = nh > 0.0 ? (double)rho[(size_t)T + h] * (faces[(size_t)T + h] / (0.5 * nh)) : 0.0;
+}
+
+void launch_links_radiosity_sided(const float4* gtris, const double* faces, const float* rho, double* r, int32_t T, hipStream_t s)
+{
+    if (T <= 0) return;
+    hipLaunchKernelGGL(k_links_radiosity_sided, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, gtris, faces, rho, r, T);
+}
+
+// k_links_apply_sided's loop, a copy of it (a shared helper would have to leave that kernel's code as it is, instruction for
+// instruction); the epilogue has no reflectance on the receiver and writes the next bounce's radiosity, rho of this triangle's
+// own faces times the irradiance they have just received: two coalesced f32 loads per thread, no second launch per bounce.
+__global__ __launch_bounds__(LINKS_APPLY_BLOCK) void k_links_apply_mapped(LinksMappedParams p)
+{
+    static_assert(LINKS_UNROLL % 2 == 0, "a group of the unroll holds whole (face 0, face 1) pairs");
+    const int i = blockIdx.x * LINKS_APPLY_BLOCK + threadIdx.x;
+    if (i >= p.tri_count) return;
+    const size_t t = (size_t)p.first_tri + (size_t)i;
+    const size_t T = (size_t)p.T;
+    const double nn = tri_normal_len(p.gtris[t * 3 + 1], p.gtris[t * 3 + 2]);
+    const int32_t* __restrict__ lp = p.links + t;
+    const double* __restrict__ r = p.r_in;
+    double sum0 = 0.0, sum1 = 0.0;
+    int32_t s = 0;
+    for (; s + LINKS_UNROLL <= p.samples; s += LINKS_UNROLL) {
+        int32_t l[LINKS_UNROLL];
+        double v[LINKS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LINKS_UNROLL; ++u) l[u] = lp[(size_t)(s + u) * T];
+#pragma unroll
+        for (int u = 0; u < LINKS_UNROLL; ++u) v[u] = linked_value(r, l[u]);
+#pragma unroll
+        for (int u = 0; u < LINKS_UNROLL; u += 2) {
+            sum0 = sum0 + v[u];
+            sum1 = sum1 + v[u + 1];
+        }
+    }
+    for (; s + 2 <= p.samples; s += 2) {            // (samples is even)
+        const int32_t l0 = lp[(size_t)s * T], l1 = lp[(size_t)(s + 1) * T];
+        const double v0 = linked_value(r, l0), v1 = linked_value(r, l1);
+        sum0 = sum0 + v0;
+        sum1 = sum1 + v1;
+    }
+    const double g0 = nn == 0.0 ? 0.0 : (0.5 * nn) * ((2.0 * sum0) / (double)p.samples);
+    const double g1 = nn == 0.0 ? 0.0 : (0.5 * nn) * ((2.0 * sum1) / (double)p.samples);
+    if (p.r_out) {
+        const double rho0 = (double)p.rho[t], rho1 = (double)p.rho[T + t];
+        p.r_out[t * 2 + 0] = nn > 0.0 ? rho0 * (g0 / (0.5 * nn)) : 0.0;
+        p.r_out[t * 2 + 1] = nn > 0.0 ? rho1 * (g1 / (0.5 * nn)) : 0.0;
+    }
+    const double g = g0 + g1;
+    const double total = p.total_in ? p.total_in[t] + g : g;
+    if (p.total_out) p.total_out[t] = total;
+    if (p.expected) p.expected[t] = p.add ? p.expected[t] + total : total;
+}
+
+void launch_links_apply_mapped(const LinksMappedParams& p, hipStream_t s)
+{
+    if (p.tri_count <= 0) return;
+    hipLaunchKernelGGL(k_links_apply_mapped, dim3((unsigned)((p.tri_count + LINKS_APPLY_BLOCK - 1) / LINKS_APPLY_BLOCK)),
                        dim3(LINKS_APPLY_BLOCK), 0, s, p);
 }
 

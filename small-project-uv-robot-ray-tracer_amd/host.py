@@ -87,6 +87,16 @@ SYMBOLS = [
     ("uvrt_host_rt_plan_gather_reflect_sided", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
                                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
                                                       C.c_int, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_gather_reflect_mapped", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
+                                                       C.c_int, C.c_int, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_set_reflect_map", None, [_vp, C.c_char_p]),
+    ("uvrt_host_rt_get_reflect_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_rt_set_reflectance_map", None, [_vp, _vp, C.c_int]),
+    ("uvrt_host_rt_reflectance_map", C.c_int, [_vp, _vp, C.c_int]),
+    ("uvrt_host_rt_has_reflect_map", C.c_int, [_vp]),
+    ("uvrt_host_rt_prepare_reflect_map", C.c_int, [_vp, C.c_float, C.c_char_p, C.c_int]),
+    ("uvrt_host_reflect_rules", C.c_int, [C.c_char_p, _vp, C.c_int, C.c_float, _vp, C.c_char_p, C.c_int]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -124,6 +134,19 @@ def lib():
             fn.argtypes = args
         _LIB = L
     return _LIB
+
+
+def parse_reflect_rules(path, tris, base):
+    """RayTracer::ParseReflectRules: the rules file `path` over the 64-byte Tri records `tris` (centroids filled, as a Mesh or
+    a BVH build leaves them) into rho float32[2][T], every entry starting at `base`.  Host only: no GPU is touched.  A line
+    that cannot be read raises ValueError("FILE:LINE: reason")."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    out = np.empty((2, t.shape[0]), dtype=np.float32)
+    err = C.create_string_buffer(1024)
+    if lib().uvrt_host_reflect_rules(os.fsencode(path), t.ctypes.data_as(_vp), t.shape[0], float(np.float32(base)),
+                                     out.ctypes.data_as(_vp), err, len(err)) != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    return out
 
 
 class Mesh:
@@ -243,17 +266,79 @@ class RayTracer:
         else:
             object.__setattr__(self, name, value)
 
+    # ---- RayTracer::reflectMap: a reflectance per face for the face-resolved bounces ----
+    @property
+    def reflectMap(self):
+        """the rules file of the reflectance map ("" for none); a relative name is resolved against the route directory.  Used
+        only with reflectSided = 1; every face starts at `reflectance`."""
+        buf = C.create_string_buffer(4096)
+        self._L.uvrt_host_rt_get_reflect_map(self._h, buf, len(buf))
+        return os.fsdecode(buf.value)
+
+    @reflectMap.setter
+    def reflectMap(self, path):
+        path = path or ""
+        if any(ch in path for ch in "<>&"):
+            raise ValueError("reflectMap: a file name with <, > or & cannot stand in a route file")
+        self._L.uvrt_host_rt_set_reflect_map(self._h, os.fsencode(path))
+
+    def SetReflectanceMap(self, planes):
+        """the planes themselves, float32[2][T] (face 0's, then face 1's), for a caller that brings them; None forgets them"""
+        if planes is None:
+            self._L.uvrt_host_rt_set_reflectance_map(self._h, None, 0)
+            return
+        v = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1)
+        if not (np.all(np.isfinite(v)) and np.all(v >= 0.0) and np.all(v <= 1.0)):
+            raise ValueError("every reflectance must be finite and in [0, 1]")
+        if self.mesh is not None and v.size != 2 * self.mesh.triangleCount:
+            raise ValueError("the reflectance map must hold 2 x triangleCount values")
+        self._L.uvrt_host_rt_set_reflectance_map(self._h, v.ctypes.data_as(_vp), v.size)
+
+    def reflectance_map(self):
+        """the planes a mapped launch would upload now: the file's when reflectMap names one (None until it has been read), else
+        SetReflectanceMap's; None without either"""
+        n = self._L.uvrt_host_rt_reflectance_map(self._h, None, 0)
+        if n == 0:
+            return None
+        out = np.empty(n, dtype=np.float32)
+        self._L.uvrt_host_rt_reflectance_map(self._h, out.ctypes.data_as(_vp), n)
+        return out.reshape(2, -1)
+
+    def _has_reflect_map(self):
+        return bool(self._L.uvrt_host_rt_has_reflect_map(self._h))
+
+    def _check_reflect_map(self, base=None, sided=None):
+        """what the host layer would end the process for: a map without reflectSided, a rules file with a line it cannot read (the
+        file is read here, once per name and base, into the cache the launches use), a map of the wrong size"""
+        if not self._has_reflect_map():
+            return
+        if not (self.reflectSided if sided is None else sided):
+            raise ValueError("reflectMap needs reflectSided = 1: only the face-resolved bounces know which face a reflectance belongs to")
+        if self.mesh is None:
+            raise ValueError("a reflectance map needs a mesh (this RayTracer was made with init=False)")
+        err = C.create_string_buffer(1024)
+        if self._L.uvrt_host_rt_prepare_reflect_map(self._h, float(np.float32(self.reflectance if base is None else base)), err,
+                                                    len(err)) != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+        if self._L.uvrt_host_rt_reflectance_map(self._h, None, 0) != 2 * self.mesh.triangleCount:
+            raise ValueError("the reflectance map must hold 2 x triangleCount values")
+
     # reference method names
     def UpdatePhotonsPerLight(self): self._L.uvrt_host_rt_update_photons_per_light(self._h)
-    def ComputeDosageMap(self): self._L.uvrt_host_rt_compute_dosage_map(self._h)
+    def ComputeDosageMap(self):
+        self._check_reflect_map()
+        self._L.uvrt_host_rt_compute_dosage_map(self._h)
     def ComputeSingleLightDosageMap(self, lamp, photonsPerLight, triangleCount):
+        self._check_reflect_map()
         self._L.uvrt_host_rt_compute_single(self._h, lamp[0], lamp[1], lamp[2], int(photonsPerLight),
                                             int(triangleCount))
     def ComputeSegmentDosageMap(self, a, b, photonsPerLight, triangleCount):
         """the dose of the drive from position a to position b ((x, z) pairs) at driveSpeed"""
+        self._check_reflect_map()
         self._L.uvrt_host_rt_compute_segment(self._h, a[0], a[1], b[0], b[1], int(photonsPerLight), int(triangleCount))
     def ComputeSegments(self):
         """the segments of one iteration, in order (nothing at driveSpeed 0)"""
+        self._check_reflect_map()
         self._L.uvrt_host_rt_compute_segments(self._h)
     def Shade(self): self._L.uvrt_host_rt_shade(self._h)
     def ResetDosageMap(self): self._L.uvrt_host_rt_reset_dosage_map(self._h)
@@ -332,14 +417,17 @@ class RayTracer:
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, **args)
 
     def PlanDurationsReflect(self, reflectance, reflect_samples=16, gather_rel_error=0.0, gather_max_extra=64, reflect_bounces=0,
-                             reflect_sided=0, **plan):
+                             reflect_sided=0, reflect_mapped=0, **plan):
         """PlanDurations(**plan) with PlanOptions::reflectance = rho and reflectSamples: every gather launch of the plan gets one
         diffuse bounce before its capture.  rho > 0 needs gather_samples > 0 and refuses gather_confidence: the
         variance plane knows nothing of the indirect part.  0 is PlanDurations / PlanDurationsRefined, bit for bit.
         reflect_bounces = K in [1, 16] (PlanOptions::reflectBounces): K bounces over hit links recorded once per scene instead of
         the bounce traced per launch; 0 is the traced bounce, bit for bit.
         reflect_sided = 1 (PlanOptions::reflectSided): those K bounces face-resolved (DESIGN.md 21); it needs rho > 0 and K >= 1 and
-        refuses gather_batch >= 2; 0 is the two-sided bounces, bit for bit."""
+        refuses gather_batch >= 2; 0 is the two-sided bounces, bit for bit.
+        reflect_mapped = 1 (PlanOptions::reflectMapped): those bounces take the ray tracer's reflectance map (reflectMap or
+        SetReflectanceMap) with rho as every face's start; it needs reflect_sided = 1 and a map; 0 is the one rho,
+        bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
                     gather_sampling=0, gather_confidence=0.0, gather_batch=0)
         unknown = set(plan) - set(args)
@@ -359,6 +447,14 @@ class RayTracer:
             raise ValueError("reflect_sided needs reflect_bounces >= 1: the traced single bounce has no face-resolved form")
         if reflect_sided and _check_gather_batch(args["gather_batch"]):
             raise ValueError("reflect_sided is not supported with gather_batch >= 2: a gather batch keeps no face planes")
+        if reflect_mapped not in (0, 1) or int(reflect_mapped) != reflect_mapped:
+            raise ValueError("reflect_mapped must be 0 or 1")
+        if reflect_mapped and not reflect_sided:
+            raise ValueError("reflect_mapped needs reflect_sided = 1: only the face-resolved bounces know which face a reflectance belongs to")
+        if reflect_mapped and not self._has_reflect_map():
+            raise ValueError("reflect_mapped needs a reflectance map (reflectMap or SetReflectanceMap)")
+        if reflect_mapped:
+            self._check_reflect_map(base=rho, sided=1)
         if rho > 0.0 and not args["gather_samples"]:
             raise ValueError("reflectance needs gather_samples > 0")
         if rho > 0.0 and float(args["gather_confidence"]) != 0.0:
@@ -367,11 +463,11 @@ class RayTracer:
             raise ValueError("reflect_samples must be even and in [2, 4096]")
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, reflectance=rho,
                                     reflect_samples=s2, reflect_bounces=int(reflect_bounces), reflect_sided=int(reflect_sided),
-                                    **args)
+                                    reflect_mapped=int(reflect_mapped), **args)
 
     def _plan_durations(self, min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
                         gather_confidence, gather_rel_error, gather_max_extra, reflectance=0.0, reflect_samples=16,
-                        reflect_bounces=0, gather_batch=0, reflect_sided=0):
+                        reflect_bounces=0, gather_batch=0, reflect_sided=0, reflect_mapped=0):
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
         B = _check_gather_batch(gather_batch)
@@ -390,6 +486,13 @@ class RayTracer:
         if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
             raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if reflect_mapped:
+            self._L.uvrt_host_rt_plan_gather_reflect_mapped(self._h, -1.0 if min_dose is None else float(min_dose),
+                                                            int(min_photons), float(margin), float(rel_gap), int(max_iterations),
+                                                            _addr(keep), int(gather_samples), int(gather_sampling), z, tau, extra,
+                                                            float(reflectance), int(reflect_samples), int(reflect_bounces), 1, 1,
+                                                            C.byref(rep), C.byref(seed))
+            return _plan_result(self, rep, seed)
         if reflect_sided:
             self._L.uvrt_host_rt_plan_gather_reflect_sided(self._h, -1.0 if min_dose is None else float(min_dose),
                                                            int(min_photons), float(margin), float(rel_gap), int(max_iterations),

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 using namespace Tmpl8;
@@ -30,7 +31,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
                                     const unsigned char* mask, int gather_samples, int gather_sampling = 0,
                                     double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64,
                                     float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0, int gather_batch = 0,
-                                    int reflect_sided = 0)
+                                    int reflect_sided = 0, int reflect_mapped = 0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
@@ -44,6 +45,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
     o.reflectBounces = reflect_bounces;
     o.gatherBatch = gather_batch;
     o.reflectSided = reflect_sided;
+    o.reflectMapped = reflect_mapped;
     return o;
 }
 
@@ -118,6 +120,38 @@ void uvrt_host_rt_set_shard(void* r, int rank, int world)
     ((RayTracer*)r)->shardRank = rank;
     ((RayTracer*)r)->shardWorld = world;
     ((RayTracer*)r)->launchIndex = 0;
+}
+
+// RayTracer::reflectMap (the rules file; "" for none) and the caller's planes (SetReflectanceMap; count 0 forgets them);
+// uvrt_host_rt_reflectance_map returns the size of the active map (ActiveReflectanceMap) and copies at most n values;
+// uvrt_host_rt_prepare_reflect_map is PrepareReflectMap: 0, or -1 and the message in err
+void uvrt_host_rt_set_reflect_map(void* r, const char* file) { ((RayTracer*)r)->reflectMap = file ? file : ""; }
+int uvrt_host_rt_get_reflect_map(void* r, char* out, int n)
+{
+    const std::string& f = ((RayTracer*)r)->reflectMap;
+    if (n > 0) { strncpy(out, f.c_str(), (size_t)n - 1); out[n - 1] = 0; }
+    return (int)f.size();
+}
+void uvrt_host_rt_set_reflectance_map(void* r, const float* rho2T, int count) { ((RayTracer*)r)->SetReflectanceMap(rho2T, count); }
+int uvrt_host_rt_reflectance_map(void* r, float* out, int n)
+{
+    const std::vector<float>& v = ((RayTracer*)r)->ActiveReflectanceMap();
+    for (int i = 0; i < n && i < (int)v.size(); ++i) out[i] = v[i];
+    return (int)v.size();
+}
+int uvrt_host_rt_has_reflect_map(void* r) { return ((RayTracer*)r)->HasReflectanceMap() ? 1 : 0; }
+int uvrt_host_rt_prepare_reflect_map(void* r, float base, char* err, int err_len)
+{
+    const std::string e = ((RayTracer*)r)->PrepareReflectMap(base);
+    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
+    return e.empty() ? 0 : -1;
+}
+// RayTracer::ParseReflectRules over `count` 64-byte Tri records: 0 and out[2 * count], or -1 and the message in err
+int uvrt_host_reflect_rules(const char* path, const void* tris64, int count, float base, float* out, char* err, int err_len)
+{
+    const std::string e = RayTracer::ParseReflectRules(path, (const Tri*)tris64, count, base, out);
+    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
+    return e.empty() ? 0 : -1;
 }
 
 // RayTracer::gatherRelError and gatherMaxExtra (the adaptive gather of every gather launch; rel_error 0: off)
@@ -234,6 +268,18 @@ void uvrt_host_rt_plan_gather_reflect_sided(void* r, float min_dose, int min_pho
     *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
                                                        gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
                                                        reflectance, reflect_samples, reflect_bounces, 0, reflect_sided), seed);
+}
+// the same with PlanOptions::reflectMapped: the ray tracer's reflectance map (include/uvrt.h uvrt_gather_indirect_linked_mapped)
+void uvrt_host_rt_plan_gather_reflect_mapped(void* r, float min_dose, int min_photons, double margin, double rel_gap,
+                                             int max_iterations, const unsigned char* mask, int gather_samples, int gather_sampling,
+                                             double gather_confidence, double gather_rel_error, int gather_max_extra,
+                                             float reflectance, int reflect_samples, int reflect_bounces, int reflect_sided,
+                                             int reflect_mapped, uvrt_plan_report* rep, unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
+                                                       reflectance, reflect_samples, reflect_bounces, 0, reflect_sided,
+                                                       reflect_mapped), seed);
 }
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)

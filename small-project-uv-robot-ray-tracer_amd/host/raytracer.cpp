@@ -187,7 +187,119 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
     RunLaunches(Launches(), photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided);
+                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap());
+}
+
+// ------------------------------------------------------------ the reflectance map (raytracer.h reflectMap)
+namespace {
+
+// a whole word as a number: a double, rounded once to f32
+bool rule_number(const std::string& w, float* out)
+{
+    if (w.empty()) return false;
+    char* end = nullptr;
+    const double v = strtod(w.c_str(), &end);
+    if (end != w.c_str() + w.size() || std::isnan(v)) return false;
+    *out = (float)v;
+    return true;
+}
+
+}  // namespace
+
+std::string RayTracer::ParseReflectRules(const char* path, const Tri* tris, int triangleCount, float base, float* out)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return std::string(path) + ": cannot be read";
+    const size_t T = (size_t)std::max(triangleCount, 0);
+    for (size_t i = 0; i < 2 * T; ++i) out[i] = base;
+    std::string line;
+    for (int no = 1; std::getline(f, line); ++no) {
+        auto bad = [&](const std::string& why) { return std::string(path) + ":" + std::to_string(no) + ": " + why; };
+        std::istringstream ss(line.substr(0, line.find('#')));
+        std::vector<std::string> w;
+        for (std::string word; ss >> word;) w.push_back(word);
+        if (w.empty()) continue;
+        if (w[0] != "box") return bad("unknown keyword '" + w[0] + "'");
+        const bool toward = w.size() == 12 && w[8] == "toward";
+        if (w.size() != 8 && !toward) return bad("box takes X0 Y0 Z0 X1 Y1 Z1 RHO [toward PX PY PZ]");
+        float v[7], p[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < 7; ++k)
+            if (!rule_number(w[1 + k], &v[k])) return bad("'" + w[1 + k] + "' is not a number");
+        for (int k = 0; toward && k < 3; ++k)
+            if (!rule_number(w[9 + k], &p[k]) || !std::isfinite(p[k])) return bad("'" + w[9 + k] + "' is not a finite number");
+        const float rho = v[6];
+        if (!std::isfinite(rho) || !(rho >= 0.0f) || !(rho <= 1.0f)) return bad("RHO must be finite and in [0, 1]");
+        if (v[0] > v[3] || v[1] > v[4] || v[2] > v[5]) return bad("a lower bound of the box lies above its upper bound");
+        for (size_t t = 0; t < T; ++t) {
+            const Tri& tr = tris[t];
+            const float3_strict& c = tr.centroid;
+            if (!(c.x >= v[0] && c.x <= v[3] && c.y >= v[1] && c.y <= v[4] && c.z >= v[2] && c.z <= v[5])) continue;
+            if (!toward) { out[t] = out[T + t] = rho; continue; }
+            // the device's normal: the f32 edges, their cross product in f64 (uvrt_device.h tri_normal)
+            const double ax = (double)(tr.vertex1.x - tr.vertex0.x), ay = (double)(tr.vertex1.y - tr.vertex0.y),
+                         az = (double)(tr.vertex1.z - tr.vertex0.z);
+            const double bx = (double)(tr.vertex2.x - tr.vertex0.x), by = (double)(tr.vertex2.y - tr.vertex0.y),
+                         bz = (double)(tr.vertex2.z - tr.vertex0.z);
+            const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+            if (sqrt((nx * nx + ny * ny) + nz * nz) == 0.0) continue;
+            const double dx = (double)p[0] - (double)tr.vertex0.x, dy = (double)p[1] - (double)tr.vertex0.y,
+                         dz = (double)p[2] - (double)tr.vertex0.z;
+            const double d = (nx * dx + ny * dy) + nz * dz;
+            out[(d > 0.0 ? 0 : T) + t] = rho;
+        }
+    }
+    return std::string();
+}
+
+void RayTracer::SetReflectanceMap(const float* rho2T, int count)
+{
+    if (count < 0 || (count > 0 && !rho2T)) fatal("SetReflectanceMap: no values");
+    reflectMapValues.assign(rho2T, rho2T + count);
+    reflectValuesStamp = reflectStampNext++;
+}
+
+std::string RayTracer::ReflectMapPath() const
+{
+    return reflectMap.empty() || reflectMap[0] == '/' ? reflectMap : routeDir + reflectMap;
+}
+
+std::string RayTracer::PrepareReflectMap(float base)
+{
+    if (reflectMap.empty()) return std::string();
+    if (!mesh) return "reflectMap: no mesh (Init comes first)";
+    const std::string path = ReflectMapPath();
+    const size_t n = 2 * (size_t)mesh->triangleCount;
+    if (reflectFileParsed == path && memcmp(&reflectFileBase, &base, 4) == 0 && reflectFileValues.size() == n) return std::string();
+    reflectFileParsed.clear();
+    reflectFileValues.assign(n, 0.0f);
+    const std::string err = ParseReflectRules(path.c_str(), mesh->triangles, mesh->triangleCount, base, reflectFileValues.data());
+    if (!err.empty()) { reflectFileValues.clear(); return err; }
+    reflectFileParsed = path;
+    reflectFileBase = base;
+    reflectFileStamp = reflectStampNext++;
+    return std::string();
+}
+
+const std::vector<float>& RayTracer::ActiveReflectanceMap() const
+{
+    static const std::vector<float> none;
+    if (reflectMap.empty()) return reflectMapValues;
+    return reflectFileParsed == ReflectMapPath() ? reflectFileValues : none;
+}
+
+void RayTracer::UploadReflectanceMap(int triangleCount, float base)
+{
+    const std::string err = PrepareReflectMap(base);
+    if (!err.empty()) fatal(("reflectMap: " + err).c_str());
+    const std::vector<float>& values = ActiveReflectanceMap();
+    const unsigned long long stamp = reflectMap.empty() ? reflectValuesStamp : reflectFileStamp;
+    if (values.size() != 2 * (size_t)triangleCount) fatal("the reflectance map must hold 2 x triangleCount values");
+    int32_t have = 0;
+    check(uvrt_reflectance_info(ctx, &have), "reflectance_info");
+    if (have && reflectUploaded == stamp) return;
+    for (int f = 0; f < 2; ++f)
+        check(uvrt_write_reflectance(ctx, f, values.data() + (size_t)f * (size_t)triangleCount, 0, triangleCount), "write_reflectance");
+    reflectUploaded = stamp;
 }
 
 void RayTracer::ComputeSegments()
@@ -196,7 +308,7 @@ void RayTracer::ComputeSegments()
     for (const RouteLaunch& l : Launches())
         if (l.kind == UVRT_LAUNCH_SWEEP) sweeps.push_back(l);
     RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided);
+                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap());
 }
 
 // the uvrt_gather_params of a gather launch with seed `seed`
@@ -214,7 +326,8 @@ static uvrt_gather_params gather_params(const RouteLaunch& l, float lightLength,
 }
 
 void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
-                            double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided)
+                            double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided,
+                            bool mapped)
 {
     if (batch < 0 || batch > UVRT_GATHER_BATCH_MAX) fatal("gatherBatch must be in [0, 64]");
     if (sided != 0 && batch >= 2) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
@@ -223,7 +336,7 @@ void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, i
     if (batch < 2 || samples <= 0 || !refineOk) {
         for (const RouteLaunch& l : list)
             RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS, reflectK, -1,
-                      sided);
+                      sided, mapped);
         return;
     }
     // groups of up to `batch` consecutive launches: one shadow-ray pass each (include/uvrt.h uvrt_gather_direct_batch), then
@@ -250,13 +363,14 @@ void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, i
         for (size_t k = 0; k < cnt; ++k) {
             const RouteLaunch& l = list[first + k];
             RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS,
-                      reflectK, (int)k);
+                      reflectK, (int)k, 0, mapped);
         }
     }
 }
 
 void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                          double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot, int sided)
+                          double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot, int sided,
+                          bool mapped)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (reflectK < 0 || reflectK > 16) fatal("reflectBounces must be in [0, 16]");
@@ -266,6 +380,7 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
         if (reflectK < 1) fatal("reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)");
         if (batchSlot >= 0) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
     }
+    if (mapped && sided == 0) fatal("reflectMap needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)");
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
     if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
     if (reflect != 0.0f && samples < 1) fatal("reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)");
@@ -322,7 +437,15 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
             kp.reflectance = reflect;
             kp.bounces = reflectK;
             kp.add = 1;
-            if (sided) {
+            if (mapped) {
+                // the face-resolved bounces with a reflectance per face (raytracer.h reflectMap): `reflect` is the map's base only
+                UploadReflectanceMap(triangleCount, reflect);
+                uvrt_mapped_params mp;
+                memset(&mp, 0, sizeof mp);
+                mp.bounces = reflectK;
+                mp.add = 1;
+                check(uvrt_gather_indirect_linked_mapped(ctx, &mp, 0, triangleCount), "gather_indirect_linked_mapped");
+            } else if (sided) {
                 // the face-resolved bounces (raytracer.h reflectSided): the gather's face planes are the emitter, no snapshot
                 check(uvrt_gather_indirect_linked_sided(ctx, &kp, 0, triangleCount), "gather_indirect_linked_sided");
             } else {
@@ -360,13 +483,15 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
     RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided,
+              HasReflectanceMap());
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
     RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided);
+              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided,
+              HasReflectanceMap());
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -485,7 +610,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
 void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided)
+                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided, bool mapped)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -502,7 +627,8 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch, sided);
+        RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch, sided,
+                    mapped);
         Shade();
         ++currIterations;
     }
@@ -581,6 +707,11 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (opt.reflectBounces < 1) fatal("PlanDurations: reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)");
         if (opt.gatherBatch >= 2) fatal("PlanDurations: reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
     }
+    if (opt.reflectMapped != 0) {
+        if (opt.reflectMapped != 1) fatal("PlanDurations: reflectMapped must be 0 or 1");
+        if (opt.reflectSided != 1) fatal("PlanDurations: reflectMapped needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)");
+        if (!r0->HasReflectanceMap()) fatal("PlanDurations: reflectMapped needs a reflectance map (RayTracer::reflectMap or SetReflectanceMap)");
+    }
     if (opt.reflectance != 0.0f) {
         if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
         if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
@@ -592,7 +723,8 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
         r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
-                              opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch, opt.reflectSided);
+                              opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch, opt.reflectSided,
+                              opt.reflectMapped != 0);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -752,6 +884,10 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
         o << "    <reflect_samples>" << reflectSamples << "</reflect_samples>\n";
         if (reflectBounces > 0) o << "    <reflect_bounces>" << reflectBounces << "</reflect_bounces>\n";
         if (reflectBounces > 0 && reflectSided != 0) o << "    <reflect_sided>1</reflect_sided>\n";
+        if (reflectBounces > 0 && reflectSided != 0 && !reflectMap.empty()) {
+            if (reflectMap.find_first_of("<>&") != std::string::npos) fatal("reflectMap: a file name with <, > or & cannot stand in a route file");
+            o << "    <reflect_map>" << reflectMap << "</reflect_map>\n";
+        }
     }
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
@@ -800,6 +936,10 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     if ((e = root.child("reflect_bounces"))) to_int(trim(e->text), &reflectBounces);
     reflectSided = 0;
     if ((e = root.child("reflect_sided"))) to_int(trim(e->text), &reflectSided);
+    reflectMap.clear();                                      // (the file's cache goes with the name it belongs to)
+    reflectFileValues.clear();
+    reflectFileParsed.clear();
+    if ((e = root.child("reflect_map"))) reflectMap = trim(e->text);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

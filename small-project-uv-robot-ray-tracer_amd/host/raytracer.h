@@ -146,6 +146,10 @@ public:
         // 1 with reflectance > 0 and reflectBounces >= 1: the plan's bounces are face-resolved (RayTracer::reflectSided below).
         // 0 (default): the two-sided bounces, bit for bit.  1 with reflectance 0, reflectBounces 0 or gatherBatch >= 2: fatal.
         int reflectSided = 0;
+        // 1 with reflectSided = 1: the plan's bounces take the ray tracer's reflectance map (RayTracer::reflectMap or
+        // SetReflectanceMap below) in place of the one rho.  0 (default): the plan above, bit for bit.  1 without reflectSided or
+        // without a map: fatal.
+        int reflectMapped = 0;
         // B in [2, 64]: the plan's gather launches are traced in groups of up to B (RayTracer::gatherBatch below).  The plan's
         // own, like S.  0 (default) and 1: launch by launch.  Durations, report and every captured column are the same bits
         // for every B.  Outside [0, 64]: fatal.
@@ -235,6 +239,38 @@ public:
     // traced single bounce has no face-resolved form) and with gatherBatch >= 2 (a gather batch keeps no face planes).  Saved
     // as <reflect_sided>1</reflect_sided> after <reflect_bounces> when that tag is written and this is on.
     int reflectSided = 0;
+    // A reflectance per face in place of the one rho of the face-resolved bounces (include/uvrt.h "per-face reflectance", DESIGN.md
+    // 22).  reflectMap names a rules file (empty: none; a relative name is resolved against routeDir):
+    //     box X0 Y0 Z0 X1 Y1 Z1 RHO                    both faces of every triangle whose Tri.centroid lies in the closed box
+    //     box X0 Y0 Z0 X1 Y1 Z1 RHO toward PX PY PZ    only the face that looks at P
+    // (ParseReflectRules below).  Every entry starts at `reflectance`; later lines override earlier ones.  The file is read by the
+    // first gather launch that needs it (or by PrepareReflectMap), once per file name and base, into a cache of its own.
+    // SetReflectanceMap hands over 2 x triangleCount values directly (face 0's plane, then face 1's) for a caller that brings
+    // planes: they are reflectMapValues, and an empty call (nullptr, 0) forgets them.  A file, when one is named, goes before the
+    // caller's planes; clearing the name (or loading a route without the tag) leaves no trace of the file: the caller's planes
+    // count again, or there is no map.  With a map and reflectSided = 1 every gather launch uploads the planes when
+    // uvrt_reflectance_info says the context has none (a scene swap drops them) or the map is not the one uploaded last, and
+    // calls uvrt_gather_indirect_linked_mapped(K, add = 1) where uvrt_gather_indirect_linked_sided stood; everything else about
+    // the launch stays.  A map without reflectSided and a map whose size is not 2 x triangleCount are fatal.  No map: every path
+    // bit for bit as before.  Saved as <reflect_map>FILE</reflect_map> after <reflect_sided> when that tag is written and a
+    // file is named; a name that holds <, > or & cannot stand in a route file and is fatal there.
+    std::string reflectMap;
+    std::vector<float> reflectMapValues;            // the caller's planes (SetReflectanceMap); never the file's
+    void SetReflectanceMap(const float* rho2T, int count);
+    bool HasReflectanceMap() const { return !reflectMap.empty() || !reflectMapValues.empty(); }
+    // Reads reflectMap's file with `base` as every entry's start unless that is what the cache holds; nothing to do without a
+    // file name.  Returns an empty string or ParseReflectRules' message: for a caller that wants to hear of a bad file before a
+    // launch ends the process over it.
+    std::string PrepareReflectMap(float base);
+    // the planes a mapped launch would upload now: the file's when a file is named (empty until it has been read), else the
+    // caller's
+    const std::vector<float>& ActiveReflectanceMap() const;
+    // The rules file above into out[2 * triangleCount] (plane-major), every entry starting at `base`.  Host only.  Returns an
+    // empty string, or what is wrong as "FILE:LINE: reason": an unknown keyword, a wrong count of numbers, an RHO that is not
+    // finite or not in [0, 1], a box with a lower bound above its upper bound (or "FILE: cannot be read").  In a box the
+    // centroid is compared in f32, bounds included; `toward P` takes face 0 iff n.(P - v0) > 0 with n = cross(e1, e2), all in
+    // f64 from the f32 values, and leaves a triangle with |n| == 0 as it is.
+    static std::string ParseReflectRules(const char* path, const Tri* tris, int triangleCount, float base, float* out);
     // The batched direct gather (include/uvrt.h "batched direct gather").  gatherBatch = B in [2, 64] with
     // gatherSamples > 0: ComputeDosageMap and ComputeSegments walk their launches in groups of up to B consecutive ones; a
     // group's shadow rays are traced in one uvrt_gather_direct_batch (the seeds the launches would have taken, the variance
@@ -252,14 +288,26 @@ private:
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
     // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError);
     // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance), or with reflectK > 0 that many
-    // bounces over recorded hit links (reflectBounces), face-resolved with `sided` (reflectSided).
+    // bounces over recorded hit links (reflectBounces), face-resolved with `sided` (reflectSided), with the reflectance map in
+    // place of `reflect` with `mapped` (reflectMap).
     // batchSlot >= 0: the launch's planes are those of launch batchSlot of the context's gather batch (RunLaunches).
     void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                   double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1, int sided = 0);
+                   double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1, int sided = 0,
+                   bool mapped = false);
     // A list of launches through RunLaunch, in order (capture: every plane into its launch's column of a plan); with
     // samples > 0 and batch >= 2 in groups of up to `batch` behind one uvrt_gather_direct_batch each (gatherBatch).
     void RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
-                     double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0);
+                     double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0,
+                     bool mapped = false);
+    // the active map (the file's, read with `base` as every entry's start, or the caller's) into the context's planes when the
+    // context has none or the map is not the one uploaded last (RunLaunch)
+    void UploadReflectanceMap(int triangleCount, float base);
+    std::string ReflectMapPath() const;             // reflectMap as it is opened: a relative name is routeDir's
+    std::vector<float> reflectFileValues;           // the cache of reflectMap's file ...
+    std::string reflectFileParsed;                  // ... the path it was read from (empty: nothing cached) ...
+    float reflectFileBase = 0.0f;                   // ... and the base it was read with
+    // every change of either source takes a new stamp; the context's planes hold the source with stamp reflectUploaded (0: none)
+    unsigned long long reflectStampNext = 1, reflectFileStamp = 0, reflectValuesStamp = 0, reflectUploaded = 0;
     long long rayCapacity = 0;                      // what ClearBuffers / RunLaunches last gave uvrt_resize_rays
     struct ShadeArguments { int which_map, photons_per_light; float scaled_power, min_value; };
     ShadeArguments ShadeArgs() const;               // what Shade passes on for viewMode (raytracer.cpp:96-116)
@@ -267,7 +315,7 @@ private:
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
     void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0);
+                           int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0, bool mapped = false);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

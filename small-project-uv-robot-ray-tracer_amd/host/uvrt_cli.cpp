@@ -86,6 +86,12 @@
 //                                           opaque sheet whose two faces keep their own irradiance, so the bounces conserve energy
 //                                           at every RHO.  Refused without --reflect-bounces (the traced single bounce has no such
 //                                           form), with RHO = 0 and with --gather-batch B >= 2.  --save-route writes <reflect_sided>
+//            [--reflect-map FILE]           with --reflect-sided: a reflectance per face in place of the one RHO (RayTracer::reflectMap,
+//                                           PlanOptions::reflectMapped).  FILE holds lines "box X0 Y0 Z0 X1 Y1 Z1 RHO"
+//                                           (both faces of every triangle whose centroid lies in the closed box) and "box .. RHO
+//                                           toward PX PY PZ" (only the face that looks at P); later lines override earlier ones, #
+//                                           starts a comment, every face starts at --reflect's RHO.  A relative FILE is resolved
+//                                           against --route-dir.  Refused without --reflect-sided.  --save-route writes <reflect_map>
 //            [--gather-batch B]             with --gather S or --plan-gather S: trace the gather launches in groups of up to B in
 //                                           [0, 64] (RayTracer::gatherBatch, PlanOptions::gatherBatch): one shadow-ray
 //                                           pass per group instead of one per launch.  0 (default) and 1: launch by launch.  B
@@ -154,7 +160,7 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
              const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence,
-             double refineTau, int refineMax, float reflect, int reflectS, int reflectK, int reflectSided)
+             double refineTau, int refineMax, float reflect, int reflectS, int reflectK, int reflectSided, int reflectMapped)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -169,6 +175,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.reflectSamples = reflectS;
     opt.reflectBounces = planGather > 0 ? reflectK : 0;
     opt.reflectSided = planGather > 0 ? reflectSided : 0;
+    opt.reflectMapped = planGather > 0 ? reflectMapped : 0;
     opt.gatherBatch = planGather > 0 ? rt.gatherBatch : 0;   // (--gather-batch: --plan-verify recomputes in the same groups)
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
@@ -189,6 +196,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
             rt.reflectBounces = opt.reflectBounces;
             rt.reflectSided = opt.reflectSided;
             if (opt.reflectSided) printf("plan: face-resolved bounces\n");
+            if (opt.reflectMapped) printf("plan: reflectance map %s over the base reflectance\n", rt.reflectMap.c_str());
             if (opt.reflectBounces > 0)
                 printf("plan: %d diffuse bounces over recorded hit links, reflectance %.8g, %d samples per triangle\n", opt.reflectBounces, (double)opt.reflectance, opt.reflectSamples);
             else
@@ -268,6 +276,7 @@ int main(int argc, char** argv)
     int reflectS = 16;
     int reflectK = 0;                       // 0: not given
     int reflectSided = 0;                   // --reflect-sided
+    std::string reflectMapFile;             // --reflect-map
     int gatherBatch = -1;                   // < 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -374,6 +383,7 @@ int main(int argc, char** argv)
             reflectK = (int)k;
         }
         else if (!strcmp(argv[i], "--reflect-sided")) reflectSided = 1;
+        else if (!strcmp(argv[i], "--reflect-map")) { need(1); reflectMapFile = argv[++i]; if (reflectMapFile.empty() || reflectMapFile.find_first_of("<>&") != std::string::npos) { fprintf(stderr, "--reflect-map FILE: a file name without <, > and & (it goes into route files as it is)\n"); return 2; } }
         else if (!strcmp(argv[i], "--gather-batch")) {
             need(1);
             char* end = nullptr;
@@ -401,6 +411,7 @@ int main(int argc, char** argv)
     if (reflectSided && reflectK < 1) { fprintf(stderr, "--reflect-sided needs --reflect-bounces K (with --reflect RHO[,S2]): the traced single bounce has no face-resolved form\n"); return 2; }
     if (reflectSided && !(reflect > 0.0f)) { fprintf(stderr, "--reflect-sided needs --reflect RHO with RHO > 0: without a bounce there are no faces to resolve\n"); return 2; }
     if (reflectSided && gatherBatch >= 2) { fprintf(stderr, "--reflect-sided cannot be combined with --gather-batch B >= 2 (a gather batch keeps no face planes)\n"); return 2; }
+    if (!reflectMapFile.empty() && !reflectSided) { fprintf(stderr, "--reflect-map needs --reflect-sided (with --reflect RHO[,S2] and --reflect-bounces K): only the face-resolved bounces know which face a reflectance belongs to\n"); return 2; }
     if (gatherBatch >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-batch needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
@@ -436,9 +447,10 @@ int main(int argc, char** argv)
     if (gather >= 0) rayTracer.gatherSamples = gather;
     if (gatherSampling >= 0 && gather > 0) rayTracer.gatherSampling = gatherSampling;
     if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
-    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; rayTracer.reflectSided = reflectSided; }
+    if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; rayTracer.reflectSided = reflectSided; rayTracer.reflectMap = reflectMapFile; }
     if (gatherBatch >= 0) rayTracer.gatherBatch = gatherBatch;
     if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectance = 0.0f;    // (the route file's own <reflectance>: a plan's bounce is --reflect's)
+    if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectMap = planGather > 0 ? reflectMapFile : std::string();   // (likewise its <reflect_map>)
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
         return 2;
@@ -462,7 +474,7 @@ int main(int argc, char** argv)
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
                                 gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax,
-                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK, reflectSided);
+                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK, reflectSided, reflectMapFile.empty() ? 0 : 1);
         save_route(rayTracer, saveRoute);
         return rc;
     }
