@@ -564,6 +564,66 @@ typedef struct {
 } uvrt_mapped_params;
 int uvrt_gather_indirect_linked_mapped(uvrt_ctx* ctx, const uvrt_mapped_params* params, int32_t first_tri, int32_t tri_count);
 
+/* ---- specular panels: the mirror-image gather of the lamp ----
+ * Everything above is diffuse.  A polished panel does not spread the lamp's light over the hemisphere: it shows every surface
+ * in front of it a second lamp behind the wall.  For a planar panel the path lamp -> panel -> surface has a closed form, the
+ * image method: the receiver sees the lamp point mirrored in the panel's plane, at the unfolded distance, provided the mirror
+ * point lies on the panel, the lamp sees the mirror point and the mirror point sees the receiver.  Everything here is
+ * additive: with no panels set every call above keeps its bits.
+ *
+ * Panels.  Panel k is an ideal plane (point q, normal m) with a specular reflectance rho_k in [0, 1]; it reflects on the side m
+ * points to.  panel_of_tri[t], uint8[T], is 0 (no mirror) or k + 1: the plane carries the optics, the member triangles say
+ * where the plane is a mirror (and occlude like every triangle).  uvrt_set_mirrors validates everything on the host before
+ * anything is uploaded -- count outside [1, UVRT_MIRROR_MAX], a non-finite value, |m| = 0, rho outside [0, 1], reserved != 0,
+ * an entry of panel_of_tri above count, no scene, a null argument: UVRT_ERR_INVALID with nothing changed -- forms
+ * mh = m / |m| in f64 (|m| = sqrt((m.x*m.x + m.y*m.y) + m.z*m.z) of the (double) components) and keeps it with (double)q.  A
+ * second call replaces the first.  The panels belong to the scene: uvrt_set_scene and uvrt_drop_mirrors drop them, every other
+ * call leaves them bit for bit; they are not a uvrt_device_ptr index.  uvrt_mirror_info: out4 = {count (0: none), member
+ * triangles, 0, 0}.  uvrt_read_mirrors: the records as they were set and panel_of_tri as the kernels read it; UVRT_ERR_INVALID
+ * when there are none.
+ *
+ * uvrt_gather_mirror, for panel k = 0 .. count-1 in order, triangle t of the range and sample s < S = params->samples, in the
+ * notation of uvrt_gather_direct and under the context's sampling mode (the draws, p and o are uvrt_gather_direct's, sample for
+ * sample; flavours 0 and 1):
+ *     d_o = (((double)o.x - q.x)*mh.x + ((double)o.y - q.y)*mh.y) + ((double)o.z - q.z)*mh.z,   d_p likewise from p      (f64)
+ *     unless d_o > 0 and d_p > 0 the sample weighs 0 and is not traced (ray (0,1,0), tmax 0)
+ *     o' = (float)((double)o - (2.0*d_o)*mh)                                    per component: the image of the lamp point
+ *     D' = p - o' (f32), r' = sqrtf((D'.x*D'.x + D'.y*D'.y) + D'.z*D'.z);  r' not finite or not > 0: weighs 0, not traced
+ *     c' = n.D',  w' = (double)rho_k * ( |c'| / (nn * (R2'*R') * 12.566370614359172) ),  face f_s = c' < 0 ? 0 : 1
+ * (c' and the bracket are uvrt_gather_direct's own expressions with o' in place of o: one copy serves both gathers).
+ *   Leg A, lamp to mirror point:  tau = d_o / (d_o + d_p),  P = (float)((double)o' + tau*(double)D'),  A = P - o (f32),
+ *     r_A = sqrtf((A.x*A.x + A.y*A.y) + A.z*A.z); r_A not finite or not > 0: weighs 0, not traced.  Ray: origin o, direction
+ *     A / r_A, tmax 1e30f; a closest-hit query (uvrt_closest_hits) answers (dist, h).  The sample is LOST unless h < T and
+ *     panel_of_tri[h] == k + 1.
+ *   Leg B, mirror point to receiver:  P_h = o + dist*(A / r_A),  B = p - P_h,  r_B = sqrtf((B.x*B.x + B.y*B.y) + B.z*B.z), all
+ *     f32; r_B not finite or not > 0: lost.  Ray: origin P_h + B*2^-10, direction B / r_B, tmax r_B * (1 - 2^-9): both ends are
+ *     pulled in by 2^-10 of the leg, as the direct gather pulls in its receiver end.  An occlusion query answers.
+ *   x_s = (lost or occluded) ? 0 : w'
+ *   m_k[t] = nn == 0 ? 0 : ((double)photons_equiv * (0.5*nn)) * ((sum_s x_s) / (double)S)             the sum in sample order
+ *   expected[t] = (add || k > 0) ? expected[t] + m_k[t] : m_k[t]
+ * With uvrt_set_gather_faces(1) the same sum, split by f_s as uvrt_gather_direct splits it, is added into faces[f][t] under the
+ * same rule, so the face-resolved bounces see the specular light as a source; with the state off `faces` is untouched.
+ * Every operator one rounding, no atomics: a pure function of the arguments, whatever the capacity or the cut of a range
+ * into calls.  In a room whose mirror wall is taken away, the direct gather of the mirrored lamp gives the same bits wherever
+ * no sample is lost or occluded and the mirroring is exact ("the virtual lamp").
+ * The call writes no variance; leaves SEED, tempPhotonMap, the source plane, links, rho and a gather batch alone; drops "the
+ * last generate" like every shadow-ray call; and forgets the remembered gather, so a uvrt_gather_refine behind it is refused
+ * and cannot merge into a plane that already holds specular light.  Entries outside the range are untouched.
+ * UVRT_ERR_INVALID with nothing changed: no panels, flavour 2, samples outside [1, 4096] or above the capacity, T*S >= 2^31,
+ * photons_equiv <= 0, add other than 0 / 1, a range outside [0, T], no scene, a null argument. */
+#define UVRT_MIRROR_MAX 8
+typedef struct {
+    float   point[3];        /* q: any point of the plane */
+    float   normal[3];       /* m: not zero; the panel reflects on the side it points to */
+    float   reflectance;     /* rho in [0, 1] */
+    int32_t reserved;        /* 0 */
+} uvrt_mirror;               /* 32 bytes */
+int uvrt_set_mirrors(uvrt_ctx* ctx, const uvrt_mirror* panels, int32_t count, const uint8_t* panel_of_tri);
+int uvrt_mirror_info(uvrt_ctx* ctx, int32_t out4[4]);
+int uvrt_read_mirrors(uvrt_ctx* ctx, uvrt_mirror* panels_out, uint8_t* panel_of_tri_out);
+int uvrt_drop_mirrors(uvrt_ctx* ctx);
+int uvrt_gather_mirror(uvrt_ctx* ctx, const uvrt_gather_params* launch, int32_t add, int32_t first_tri, int32_t tri_count);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).

@@ -162,6 +162,11 @@ SYMBOLS = [
     ("uvrt_reflectance_info", C.c_int, [_vp, C.POINTER(_i32)]),
     ("uvrt_drop_reflectance", C.c_int, [_vp]),
     ("uvrt_gather_indirect_linked_mapped", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_set_mirrors", C.c_int, [_vp, _vp, _i32, _vp]),
+    ("uvrt_mirror_info", C.c_int, [_vp, _vp]),
+    ("uvrt_read_mirrors", C.c_int, [_vp, _vp, _vp]),
+    ("uvrt_drop_mirrors", C.c_int, [_vp]),
+    ("uvrt_gather_mirror", C.c_int, [_vp, _vp, _i32, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -203,6 +208,16 @@ class LinkedParams(C.Structure):
 class MappedParams(C.Structure):
     """uvrt_mapped_params (include/uvrt.h)"""
     _fields_ = [("bounces", C.c_int32), ("add", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# uvrt_mirror (include/uvrt.h): a specular panel
+MIRROR_MAX = 8
+MIRROR_DT = np.dtype([("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("reflectance", "<f4"), ("reserved", "<i4")])
+
+
+def mirror(point, normal, reflectance, reserved=0):
+    """a uvrt_mirror record: the plane through `point` with `normal`, reflecting on the side the normal points to"""
+    return (tuple(point), tuple(normal), reflectance, reserved)
 
 
 class PlanParams(C.Structure):
@@ -812,6 +827,44 @@ class Ctx:
         prm.reserved[0], prm.reserved[1] = int(reserved[0]), int(reserved[1])
         self._ck(self._L.uvrt_gather_indirect_linked_mapped(self._h, C.byref(prm), int(first_tri),
                                                             self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    # ---- specular panels and the mirror gather ----
+    def set_mirrors(self, panels, panel_of_tri, count=None):
+        """panels: uvrt_mirror records (capi.mirror); panel_of_tri: uint8[T], 0 or k + 1"""
+        rec = np.ascontiguousarray(np.array(panels, dtype=MIRROR_DT).reshape(-1))
+        pot = np.ascontiguousarray(panel_of_tri, dtype=np.uint8)
+        if pot.size != self.T:
+            raise UvrtError("set_mirrors: panel_of_tri has %d entries, the scene %d triangles" % (pot.size, self.T))
+        self._ck(self._L.uvrt_set_mirrors(self._h, _ptr(rec) if rec.size else None, rec.size if count is None else int(count),
+                                          _ptr(pot)))
+
+    def mirror_info(self):
+        """(panels (0: none), member triangles)"""
+        out = np.zeros(4, dtype=np.int32)
+        self._ck(self._L.uvrt_mirror_info(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
+
+    def read_mirrors(self):
+        """(the panels as they were set, MIRROR_DT[count]; panel_of_tri uint8[T] as the kernels read it)"""
+        rec = np.zeros(MIRROR_MAX, dtype=MIRROR_DT)
+        pot = np.zeros(self.T, dtype=np.uint8)
+        self._ck(self._L.uvrt_read_mirrors(self._h, _ptr(rec), _ptr(pot)))
+        return rec[:self.mirror_info()[0]].copy(), pot
+
+    def drop_mirrors(self):
+        self._ck(self._L.uvrt_drop_mirrors(self._h))
+
+    def gather_mirror(self, frm, to, light_length, samples, seed, photons_equiv, add=0, first_tri=0, tri_count=None):
+        """expected[first_tri, +tri_count) = (add ? expected : 0) + the lamp's light by way of every panel, in panel order"""
+        prm = GatherParams()
+        prm.from_ = _f3(frm)
+        prm.to = _f3(to)
+        prm.light_length = float(np.float32(light_length))
+        prm.samples = int(samples)
+        prm.seed = int(seed)
+        prm.photons_equiv = int(photons_equiv)
+        self._ck(self._L.uvrt_gather_mirror(self._h, C.byref(prm), int(add), int(first_tri),
+                                            self.T - int(first_tri) if tri_count is None else int(tri_count)))
 
     @property
     def seed(self):

@@ -14,6 +14,7 @@
 //   uvrt_capi_links.hip   recorded hit links and the multi-bounce gather over them (uvrt_indirect_links_build,
 //                         uvrt_gather_indirect_linked) and their sided forms (uvrt_indirect_links_build_sided,
 //                         uvrt_gather_indirect_linked_sided)
+//   uvrt_capi_mirror.hip  specular panels and the mirror gather (uvrt_set_mirrors, uvrt_gather_mirror)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -159,6 +160,7 @@ struct uvrt_ctx {
     DevBuf g_oxz, g_tmax, g_occ, g_w;
     DevBuf g_face;                             // the face each sample arrives on, uint8[capacity] (uvrt_set_gather_faces)
     DevBuf g_hit;                              // closest hits (uvrt_capi_indirect.hip): every ray's (dist bits, triID), uint2[capacity]
+    DevBuf g_point;                            // the mirror gather's receiver points (uvrt_capi_mirror.hip), float4[capacity]
     // uvrt_gather_refine (include/uvrt.h "adaptive gather"): the exclusive prefix sums of a refined range, int32[T + 1], and
     // the scan's per-block totals
     DevBuf g_offs, g_scan;
@@ -189,6 +191,12 @@ struct uvrt_ctx {
         uint32_t links_seed = 0;
         DevBuf rho;                            // the reflectance planes f32[2][T] of uvrt_gather_indirect_linked_mapped
         bool have_rho = false;                 // ... exist (a scene has none until a fill or a write makes them)
+        // specular panels (uvrt_capi_mirror.hip): the caller's records as they came, the planes as the kernels read them
+        // (point and unit normal in f64) and panel_of_tri, uint8[T], on the device; mirror_count 0: none
+        int32_t mirror_count = 0, mirror_members = 0;
+        uvrt_mirror mirrors[UVRT_MIRROR_MAX] = {};
+        uvrt::MirrorPanel mirror_planes[UVRT_MIRROR_MAX] = {};
+        DevBuf panel_of_tri_dev;
         GatherMemo gather_memo;                // a refine works on one scene's planes
         // the batch of the last successful uvrt_gather_direct_batch (uvrt_capi_gather_batch.hip; count 0: none): its launches,
         // range and sample count, the sampling mode, variance state and flavour it ran under, and its planes f64[count][T]

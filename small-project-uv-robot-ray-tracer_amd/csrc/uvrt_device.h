@@ -622,4 +622,49 @@ void launch_links_apply_mapped(const LinksMappedParams& p, hipStream_t s);
 void launch_links_export(const int32_t* links, int32_t* out, int32_t first_tri, int32_t tri_count, int32_t samples, int32_t T,
                          hipStream_t s);
 
+// ---- specular panels and the mirror gather (uvrt_mirror.hip; include/uvrt.h "specular panels") ----
+// A panel as the kernels read it: the plane's point and unit normal in f64 (the host normalises), the reflectance, and the
+// value panel_of_tri holds for its member triangles.
+struct MirrorPanel {
+    double qx, qy, qz;
+    double mx, my, mz;
+    double rho;              // (double) of the f32 reflectance
+    int32_t member;          // k + 1
+    int32_t pad;
+};
+// leg A of every (triangle, sample) of a chunk: a GatherGenParams' arrays (w: rho * the image's weight), the face byte and
+// the receiver point of each sample
+struct MirrorGenParams {
+    GatherGenParams g;
+    MirrorPanel m;
+    uint8_t* face;           // [tri_count * samples]
+    float4* point;           // [tri_count * samples] p.xyz
+};
+void launch_mirror_generate(const MirrorGenParams& p, hipStream_t s);
+// leg B over leg A, from the chunk's hit records; w[i] = 0 for a sample whose leg A did not end on the panel
+struct MirrorFoldParams {
+    float4* rays;
+    float2* oxz;
+    float* tmax;
+    double* w;
+    const uint2* hit;
+    const float4* point;
+    const uint8_t* panel_of_tri;   // [T]
+    int64_t n;
+    int32_t member, T;
+};
+void launch_mirror_fold(const MirrorFoldParams& p, hipStream_t s);
+// expected[t] (and, with `faces`, faces[f * T + t]) = accumulate ? old + m : m for the chunk's triangles
+struct MirrorReduceParams {
+    const float4* gtris;
+    const double* w;
+    const uint8_t* occluded;
+    const uint8_t* face;
+    double* expected;        // [T]
+    double* faces;           // [2 * T], or null: the faces state is off
+    int32_t first_tri, tri_count, samples, photons_equiv, T;
+    int32_t accumulate;
+};
+void launch_mirror_reduce(const MirrorReduceParams& p, hipStream_t s);
+
 }  // namespace uvrt

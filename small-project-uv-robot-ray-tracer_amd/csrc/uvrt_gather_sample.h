@@ -22,13 +22,22 @@ struct GatherSample {
     float tmax;
     double w;                // the sample's weight (0 for a sample that is not traced)
     double c;                // n.D, the value w takes fabs of: its sign is the face the sample arrives on (gather_face)
+    float dx, dy, dz, r;     // D = p - source point in f32 and its f32 length, before the division
 };
 
-// Sample s of `samples` of triangle t.  MODE: the gather sampling (include/uvrt.h uvrt_set_gather_sampling).  0 is the
-// independent rule; 1 puts sample s into stratum s of the rod and the sweep coordinate on a golden-ratio Weyl sequence rotated
-// per triangle and seed.  The four draws are the same in both, so (a, b) are: only u_h and u_m differ.
+// The two points of a sample: p on the triangle, o on the lamp's rod (or on the rod swept along the segment), and the
+// triangle's edges for the normal.  What the direct gather and the mirror gather (uvrt_mirror_sample.h) both start from.
+struct GatherPoints {
+    float px, py, pz;
+    float ox, oy, oz;
+    float4 e1, e2;
+};
+
+// The points of sample s of `samples` of triangle t.  MODE: the gather sampling (include/uvrt.h uvrt_set_gather_sampling).  0 is
+// the independent rule; 1 puts sample s into stratum s of the rod and the sweep coordinate on a golden-ratio Weyl sequence
+// rotated per triangle and seed.  The four draws are the same in both, so (a, b) are: only u_h and u_m differ.
 template <int MODE>
-__device__ __forceinline__ GatherSample gather_sample(const float4* __restrict__ gtris, const GatherLamp& l, uint32_t t, uint32_t s,
+__device__ __forceinline__ GatherPoints gather_points(const float4* __restrict__ gtris, const GatherLamp& l, uint32_t t, uint32_t s,
                                                       int32_t samples)
 {
     static_assert(MODE == 0 || MODE == 1, "gather sampling: independent or stratified");
@@ -46,22 +55,33 @@ __device__ __forceinline__ GatherSample gather_sample(const float4* __restrict__
     float b = random_float(rng);
     if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
     const float4 v0 = gtris[(size_t)t * 3 + 0], e1 = gtris[(size_t)t * 3 + 1], e2 = gtris[(size_t)t * 3 + 2];
-    const float px = (v0.x + a * e1.x) + b * e2.x;
-    const float py = (v0.y + a * e1.y) + b * e2.y;
-    const float pz = (v0.z + a * e1.z) + b * e2.z;
+    GatherPoints g;
+    g.px = (v0.x + a * e1.x) + b * e2.x;
+    g.py = (v0.y + a * e1.y) + b * e2.y;
+    g.pz = (v0.z + a * e1.z) + b * e2.z;
     // k_generate_sweep's origin with r1 := u_h and u := u_m
     const float sx = l.tx - l.fx, sy = l.ty - l.fy, sz = l.tz - l.fz;
-    const float ox = l.fx + u_m * sx;
-    const float oy = (l.fy + u_h * l.light_length) + u_m * sy;
-    const float oz = l.fz + u_m * sz;
-    const float dx = px - ox, dy = py - oy, dz = pz - oz;
+    g.ox = l.fx + u_m * sx;
+    g.oy = (l.fy + u_h * l.light_length) + u_m * sy;
+    g.oz = l.fz + u_m * sz;
+    g.e1 = e1;
+    g.e2 = e2;
+    return g;
+}
+
+// The ray from the source point (ox, oy, oz) to the sample's point p, its weight and the n.D the weight takes fabs of.  The
+// direct gather's source point is the sample's own o; the mirror gather's is o's image behind a panel.
+__device__ __forceinline__ GatherSample gather_weigh(const GatherPoints& g, float ox, float oy, float oz)
+{
+    const float dx = g.px - ox, dy = g.py - oy, dz = g.pz - oz;
     const float r = sqrtf((dx * dx + dy * dy) + dz * dz);
     double nx, ny, nz;
-    const double nn = tri_normal(e1, e2, nx, ny, nz);
+    const double nn = tri_normal(g.e1, g.e2, nx, ny, nz);
     const double Dx = (double)dx, Dy = (double)dy, Dz = (double)dz;
     const double R2 = Dx * Dx + Dy * Dy + Dz * Dz;
     const double R = sqrt(R2);
     GatherSample o;
+    o.dx = dx; o.dy = dy; o.dz = dz; o.r = r;
     o.c = nx * Dx + ny * Dy + nz * Dz;
     o.w = fabs(o.c) / (nn * (R2 * R) * 12.566370614359172);
     o.ray = make_float4(dx / r, dy / r, dz / r, oy);
@@ -73,6 +93,15 @@ __device__ __forceinline__ GatherSample gather_sample(const float4* __restrict__
     }
     o.oxz = make_float2(ox, oz);
     return o;
+}
+
+// Sample s of `samples` of triangle t of the direct gather: the ray from its lamp point to its point on the triangle
+template <int MODE>
+__device__ __forceinline__ GatherSample gather_sample(const float4* __restrict__ gtris, const GatherLamp& l, uint32_t t, uint32_t s,
+                                                      int32_t samples)
+{
+    const GatherPoints g = gather_points<MODE>(gtris, l, t, s, samples);
+    return gather_weigh(g, g.ox, g.oy, g.oz);
 }
 
 // |cross(e1, e2)| of triangle t

@@ -97,6 +97,15 @@ SYMBOLS = [
     ("uvrt_host_rt_has_reflect_map", C.c_int, [_vp]),
     ("uvrt_host_rt_prepare_reflect_map", C.c_int, [_vp, C.c_float, C.c_char_p, C.c_int]),
     ("uvrt_host_reflect_rules", C.c_int, [C.c_char_p, _vp, C.c_int, C.c_float, _vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_rt_plan_gather_mirror", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
+                                               C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_set_mirror_map", None, [_vp, C.c_char_p]),
+    ("uvrt_host_rt_get_mirror_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_rt_set_mirrors", None, [_vp, _vp, C.c_int, _vp, C.c_int]),
+    ("uvrt_host_rt_has_mirrors", C.c_int, [_vp]),
+    ("uvrt_host_rt_prepare_mirror_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_mirror_rules", C.c_int, [C.c_char_p, _vp, C.c_int, _vp, C.POINTER(C.c_int), _vp, C.c_char_p, C.c_int]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
@@ -147,6 +156,21 @@ def parse_reflect_rules(path, tris, base):
                                      out.ctypes.data_as(_vp), err, len(err)) != 0:
         raise ValueError(err.value.decode(errors="replace"))
     return out
+
+
+def parse_mirror_rules(path, tris):
+    """RayTracer::ParseMirrorRules: the rules file `path` over the 64-byte Tri records `tris` (centroids filled) into (panels
+    capi.MIRROR_DT[count], panel_of_tri uint8[T]: 0 or k + 1).  Host only: no GPU is touched.  A line that cannot be read raises
+    ValueError("FILE:LINE: reason")."""
+    t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 16)
+    panels = np.zeros(capi.MIRROR_MAX, dtype=capi.MIRROR_DT)
+    members = np.zeros(t.shape[0], dtype=np.uint8)
+    count = C.c_int(0)
+    err = C.create_string_buffer(1024)
+    if lib().uvrt_host_mirror_rules(os.fsencode(path), t.ctypes.data_as(_vp), t.shape[0], panels.ctypes.data_as(_vp),
+                                    C.byref(count), members.ctypes.data_as(_vp), err, len(err)) != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    return panels[:count.value].copy(), members
 
 
 class Mesh:
@@ -323,22 +347,79 @@ class RayTracer:
         if self._L.uvrt_host_rt_reflectance_map(self._h, None, 0) != 2 * self.mesh.triangleCount:
             raise ValueError("the reflectance map must hold 2 x triangleCount values")
 
+    # ---- RayTracer::mirrorMap: specular panels and the mirror gather behind every gather launch ----
+    @property
+    def mirrorMap(self):
+        """the rules file of the specular panels ("" for none); a relative name is resolved against the route directory.  Used
+        only with gatherSamples > 0."""
+        buf = C.create_string_buffer(4096)
+        self._L.uvrt_host_rt_get_mirror_map(self._h, buf, len(buf))
+        return os.fsdecode(buf.value)
+
+    @mirrorMap.setter
+    def mirrorMap(self, path):
+        path = path or ""
+        if any(ch in path for ch in "<>&"):
+            raise ValueError("mirrorMap: a file name with <, > or & cannot stand in a route file")
+        self._L.uvrt_host_rt_set_mirror_map(self._h, os.fsencode(path))
+
+    def SetMirrors(self, panels, panel_of_tri=None):
+        """the panels themselves (capi.mirror records, 1 to 8) and panel_of_tri uint8[T] (0 or k + 1), for a caller that brings
+        them; SetMirrors(None) forgets them"""
+        if panels is None:
+            self._L.uvrt_host_rt_set_mirrors(self._h, None, 0, None, 0)
+            return
+        rec = np.ascontiguousarray(np.array(panels, dtype=capi.MIRROR_DT).reshape(-1))
+        members = np.ascontiguousarray(panel_of_tri, dtype=np.uint8).reshape(-1)
+        if not 1 <= rec.size <= capi.MIRROR_MAX:
+            raise ValueError("SetMirrors takes 1 to %d panels" % capi.MIRROR_MAX)
+        ok = np.isfinite(rec["point"]).all() and np.isfinite(rec["normal"]).all() and np.isfinite(rec["reflectance"]).all()
+        if not ok or (rec["reflectance"] < 0).any() or (rec["reflectance"] > 1).any() or (rec["reserved"] != 0).any():
+            raise ValueError("every panel needs finite values, a reflectance in [0, 1] and reserved = 0")
+        if (np.abs(rec["normal"]).max(axis=1) == 0).any():
+            raise ValueError("a panel's normal is zero")
+        if members.size and members.max() > rec.size:
+            raise ValueError("panel_of_tri names a panel that is not there")
+        if self.mesh is not None and members.size != self.mesh.triangleCount:
+            raise ValueError("panel_of_tri must hold triangleCount entries")
+        self._L.uvrt_host_rt_set_mirrors(self._h, rec.ctypes.data_as(_vp), rec.size, members.ctypes.data_as(_vp), members.size)
+
+    def _has_mirrors(self):
+        return bool(self._L.uvrt_host_rt_has_mirrors(self._h))
+
+    def _check_mirrors(self, samples=None):
+        """what the host layer would end the process for: panels without gatherSamples, a rules file with a line it cannot read
+        (the file is read here, once per name, into the cache the launches use)"""
+        if not self._has_mirrors():
+            return
+        if not (self.gatherSamples if samples is None else samples):
+            raise ValueError("mirrorMap needs gatherSamples > 0: the mirror gather adds to the direct gather's plane")
+        if self.mesh is None:
+            raise ValueError("specular panels need a mesh (this RayTracer was made with init=False)")
+        err = C.create_string_buffer(1024)
+        if self._L.uvrt_host_rt_prepare_mirror_map(self._h, err, len(err)) != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+
     # reference method names
     def UpdatePhotonsPerLight(self): self._L.uvrt_host_rt_update_photons_per_light(self._h)
     def ComputeDosageMap(self):
         self._check_reflect_map()
+        self._check_mirrors()
         self._L.uvrt_host_rt_compute_dosage_map(self._h)
     def ComputeSingleLightDosageMap(self, lamp, photonsPerLight, triangleCount):
         self._check_reflect_map()
+        self._check_mirrors()
         self._L.uvrt_host_rt_compute_single(self._h, lamp[0], lamp[1], lamp[2], int(photonsPerLight),
                                             int(triangleCount))
     def ComputeSegmentDosageMap(self, a, b, photonsPerLight, triangleCount):
         """the dose of the drive from position a to position b ((x, z) pairs) at driveSpeed"""
         self._check_reflect_map()
+        self._check_mirrors()
         self._L.uvrt_host_rt_compute_segment(self._h, a[0], a[1], b[0], b[1], int(photonsPerLight), int(triangleCount))
     def ComputeSegments(self):
         """the segments of one iteration, in order (nothing at driveSpeed 0)"""
         self._check_reflect_map()
+        self._check_mirrors()
         self._L.uvrt_host_rt_compute_segments(self._h)
     def Shade(self): self._L.uvrt_host_rt_shade(self._h)
     def ResetDosageMap(self): self._L.uvrt_host_rt_reset_dosage_map(self._h)
@@ -386,7 +467,10 @@ class RayTracer:
         is those launches' sampling mode: 0 independent, 1 stratified; it needs gather_samples > 0.
         gather_confidence = z > 0 (PlanOptions::gatherConfidence) plans for the estimate's lower confidence bound, expected -
         z standard errors element by element; it needs gather_samples >= 2 and is meant for 16 and more.
-        0 is the plan without it, bit for bit.  (PlanDurationsRefined is this call with the adaptive gather, PlanDurationsBatched
+        0 is the plan without it, bit for bit.  (PlanDurationsBatched, PlanDurationsRefined and PlanDurationsReflect also take
+        mirror_mapped = 1 (PlanOptions::mirrorMapped) among their plan arguments: the mirror gather over the ray tracer's specular
+        panels (mirrorMap or SetMirrors) follows every gather launch of the plan; it needs gather_samples > 0 and
+        panels and refuses gather_confidence.)  (PlanDurationsRefined is this call with the adaptive gather, PlanDurationsBatched
         with the plan's gather launches traced in groups.)"""
         return self._plan_durations(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
                                     gather_confidence, 0.0, 64)
@@ -397,7 +481,7 @@ class RayTracer:
         report or the captured columns.  0 and 1 are PlanDurations.  (PlanDurationsRefined and PlanDurationsReflect take
         gather_batch = B among their plan arguments.)"""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0)
+                    gather_sampling=0, gather_confidence=0.0, mirror_mapped=0)
         unknown = set(plan) - set(args)
         if unknown:
             raise TypeError("PlanDurationsBatched: unknown arguments %s" % sorted(unknown))
@@ -409,7 +493,7 @@ class RayTracer:
         every gather launch of the plan is refined before its capture.  tau > 0 needs gather_samples >= 2 and
         works with and without gather_confidence; 0 is PlanDurations, bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0, gather_batch=0)
+                    gather_sampling=0, gather_confidence=0.0, gather_batch=0, mirror_mapped=0)
         unknown = set(plan) - set(args)
         if unknown:
             raise TypeError("PlanDurationsRefined: unknown arguments %s" % sorted(unknown))
@@ -429,7 +513,7 @@ class RayTracer:
         SetReflectanceMap) with rho as every face's start; it needs reflect_sided = 1 and a map; 0 is the one rho,
         bit for bit."""
         args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0, gather_batch=0)
+                    gather_sampling=0, gather_confidence=0.0, gather_batch=0, mirror_mapped=0)
         unknown = set(plan) - set(args)
         if unknown:
             raise TypeError("PlanDurationsReflect: unknown arguments %s" % sorted(unknown))
@@ -467,7 +551,17 @@ class RayTracer:
 
     def _plan_durations(self, min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples, gather_sampling,
                         gather_confidence, gather_rel_error, gather_max_extra, reflectance=0.0, reflect_samples=16,
-                        reflect_bounces=0, gather_batch=0, reflect_sided=0, reflect_mapped=0):
+                        reflect_bounces=0, gather_batch=0, reflect_sided=0, reflect_mapped=0, mirror_mapped=0):
+        if mirror_mapped not in (0, 1) or int(mirror_mapped) != mirror_mapped:
+            raise ValueError("mirror_mapped must be 0 or 1")
+        if mirror_mapped and not gather_samples:
+            raise ValueError("mirror_mapped needs gather_samples > 0")
+        if mirror_mapped and float(gather_confidence) != 0.0:
+            raise ValueError("mirror_mapped is not supported with gather_confidence: the variance plane knows nothing of the specular part")
+        if mirror_mapped and not self._has_mirrors():
+            raise ValueError("mirror_mapped needs specular panels (mirrorMap or SetMirrors)")
+        if mirror_mapped:
+            self._check_mirrors(samples=gather_samples)
         if gather_sampling and not gather_samples:
             raise ValueError("gather_sampling needs gather_samples > 0")
         B = _check_gather_batch(gather_batch)
@@ -486,6 +580,13 @@ class RayTracer:
         if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
             raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
         rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
+        if mirror_mapped:
+            self._L.uvrt_host_rt_plan_gather_mirror(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
+                                                    float(margin), float(rel_gap), int(max_iterations), _addr(keep),
+                                                    int(gather_samples), int(gather_sampling), z, tau, extra, float(reflectance),
+                                                    int(reflect_samples), int(reflect_bounces), B, int(reflect_sided),
+                                                    int(reflect_mapped), 1, C.byref(rep), C.byref(seed))
+            return _plan_result(self, rep, seed)
         if reflect_mapped:
             self._L.uvrt_host_rt_plan_gather_reflect_mapped(self._h, -1.0 if min_dose is None else float(min_dose),
                                                             int(min_photons), float(margin), float(rel_gap), int(max_iterations),

@@ -31,7 +31,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
                                     const unsigned char* mask, int gather_samples, int gather_sampling = 0,
                                     double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64,
                                     float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0, int gather_batch = 0,
-                                    int reflect_sided = 0, int reflect_mapped = 0)
+                                    int reflect_sided = 0, int reflect_mapped = 0, int mirror_mapped = 0)
 {
     RayTracer::PlanOptions o;
     o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
@@ -46,6 +46,7 @@ RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double marg
     o.gatherBatch = gather_batch;
     o.reflectSided = reflect_sided;
     o.reflectMapped = reflect_mapped;
+    o.mirrorMapped = mirror_mapped;
     return o;
 }
 
@@ -150,6 +151,36 @@ int uvrt_host_rt_prepare_reflect_map(void* r, float base, char* err, int err_len
 int uvrt_host_reflect_rules(const char* path, const void* tris64, int count, float base, float* out, char* err, int err_len)
 {
     const std::string e = RayTracer::ParseReflectRules(path, (const Tri*)tris64, count, base, out);
+    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
+    return e.empty() ? 0 : -1;
+}
+
+// RayTracer::mirrorMap (the rules file; "" for none) and the caller's panels (SetMirrors; count 0 forgets them);
+// uvrt_host_rt_prepare_mirror_map is PrepareMirrorMap: 0, or -1 and the message in err
+void uvrt_host_rt_set_mirror_map(void* r, const char* file) { ((RayTracer*)r)->mirrorMap = file ? file : ""; }
+int uvrt_host_rt_get_mirror_map(void* r, char* out, int n)
+{
+    const std::string& f = ((RayTracer*)r)->mirrorMap;
+    if (n > 0) { strncpy(out, f.c_str(), (size_t)n - 1); out[n - 1] = 0; }
+    return (int)f.size();
+}
+void uvrt_host_rt_set_mirrors(void* r, const uvrt_mirror* panels, int count, const unsigned char* panel_of_tri, int n_tris)
+{
+    ((RayTracer*)r)->SetMirrors(panels, count, panel_of_tri, n_tris);
+}
+int uvrt_host_rt_has_mirrors(void* r) { return ((RayTracer*)r)->HasMirrors() ? 1 : 0; }
+int uvrt_host_rt_prepare_mirror_map(void* r, char* err, int err_len)
+{
+    const std::string e = ((RayTracer*)r)->PrepareMirrorMap();
+    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
+    return e.empty() ? 0 : -1;
+}
+// RayTracer::ParseMirrorRules over `count` 64-byte Tri records: 0, *panels_count, panels_out[8] and panel_of_tri_out[count], or
+// -1 and the message in err
+int uvrt_host_mirror_rules(const char* path, const void* tris64, int count, uvrt_mirror* panels_out, int* panels_count,
+                           unsigned char* panel_of_tri_out, char* err, int err_len)
+{
+    const std::string e = RayTracer::ParseMirrorRules(path, (const Tri*)tris64, count, panels_out, panels_count, panel_of_tri_out);
     if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
     return e.empty() ? 0 : -1;
 }
@@ -280,6 +311,18 @@ void uvrt_host_rt_plan_gather_reflect_mapped(void* r, float min_dose, int min_ph
                                                        gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
                                                        reflectance, reflect_samples, reflect_bounces, 0, reflect_sided,
                                                        reflect_mapped), seed);
+}
+// the same with PlanOptions::gatherBatch and mirrorMapped: the ray tracer's specular panels (include/uvrt.h uvrt_gather_mirror)
+void uvrt_host_rt_plan_gather_mirror(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
+                                     const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
+                                     double gather_rel_error, int gather_max_extra, float reflectance, int reflect_samples,
+                                     int reflect_bounces, int gather_batch, int reflect_sided, int reflect_mapped, int mirror_mapped,
+                                     uvrt_plan_report* rep, unsigned* seed)
+{
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
+                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
+                                                       reflectance, reflect_samples, reflect_bounces, gather_batch, reflect_sided,
+                                                       reflect_mapped, mirror_mapped), seed);
 }
 void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
                              int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)

@@ -187,7 +187,7 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
     RunLaunches(Launches(), photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap());
+                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap(), HasMirrors());
 }
 
 // ------------------------------------------------------------ the reflectance map (raytracer.h reflectMap)
@@ -302,13 +302,106 @@ void RayTracer::UploadReflectanceMap(int triangleCount, float base)
     reflectUploaded = stamp;
 }
 
+// ------------------------------------------------------------ specular panels (raytracer.h mirrorMap)
+std::string RayTracer::ParseMirrorRules(const char* path, const Tri* tris, int triangleCount, uvrt_mirror* panelsOut, int* countOut,
+                                        uint8_t* panelOfTriOut)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return std::string(path) + ": cannot be read";
+    const size_t T = (size_t)std::max(triangleCount, 0);
+    for (size_t t = 0; t < T; ++t) panelOfTriOut[t] = 0;
+    int count = 0;
+    *countOut = 0;
+    std::string line;
+    for (int no = 1; std::getline(f, line); ++no) {
+        auto bad = [&](const std::string& why) { return std::string(path) + ":" + std::to_string(no) + ": " + why; };
+        std::istringstream ss(line.substr(0, line.find('#')));
+        std::vector<std::string> w;
+        for (std::string word; ss >> word;) w.push_back(word);
+        if (w.empty()) continue;
+        if (w[0] != "mirror") return bad("unknown keyword '" + w[0] + "'");
+        if (w.size() != 15 || w[8] != "plane") return bad("mirror takes X0 Y0 Z0 X1 Y1 Z1 RHO plane QX QY QZ MX MY MZ");
+        float v[7], q[6];
+        for (int k = 0; k < 7; ++k)
+            if (!rule_number(w[1 + k], &v[k])) return bad("'" + w[1 + k] + "' is not a number");
+        for (int k = 0; k < 6; ++k)
+            if (!rule_number(w[9 + k], &q[k]) || !std::isfinite(q[k])) return bad("'" + w[9 + k] + "' is not a finite number");
+        const float rho = v[6];
+        if (!std::isfinite(rho) || !(rho >= 0.0f) || !(rho <= 1.0f)) return bad("RHO must be finite and in [0, 1]");
+        if (q[3] == 0.0f && q[4] == 0.0f && q[5] == 0.0f) return bad("the plane's normal is zero");
+        if (v[0] > v[3] || v[1] > v[4] || v[2] > v[5]) return bad("a lower bound of the box lies above its upper bound");
+        if (count == UVRT_MIRROR_MAX) return bad("a ninth panel (at most " + std::to_string(UVRT_MIRROR_MAX) + ")");
+        uvrt_mirror& m = panelsOut[count++];
+        memset(&m, 0, sizeof m);
+        for (int k = 0; k < 3; ++k) { m.point[k] = q[k]; m.normal[k] = q[3 + k]; }
+        m.reflectance = rho;
+        for (size_t t = 0; t < T; ++t) {
+            const float3_strict& c = tris[t].centroid;
+            if (c.x >= v[0] && c.x <= v[3] && c.y >= v[1] && c.y <= v[4] && c.z >= v[2] && c.z <= v[5]) panelOfTriOut[t] = (uint8_t)count;
+        }
+    }
+    *countOut = count;
+    return std::string();
+}
+
+void RayTracer::SetMirrors(const uvrt_mirror* panels, int count, const uint8_t* panelOfTri, int triangleCount)
+{
+    if (count < 0 || count > UVRT_MIRROR_MAX || triangleCount < 0 || (count > 0 && (!panels || !panelOfTri)))
+        fatal("SetMirrors: between 1 and 8 panels with a panel_of_tri, or nothing");
+    mirrorPanels.assign(panels, panels + count);
+    mirrorPanelOfTri.assign(panelOfTri, panelOfTri + (count > 0 ? triangleCount : 0));
+    mirrorValuesStamp = mirrorStampNext++;
+}
+
+std::string RayTracer::MirrorMapPath() const
+{
+    return mirrorMap.empty() || mirrorMap[0] == '/' ? mirrorMap : routeDir + mirrorMap;
+}
+
+std::string RayTracer::PrepareMirrorMap()
+{
+    if (mirrorMap.empty()) return std::string();
+    if (!mesh) return "mirrorMap: no mesh (Init comes first)";
+    const std::string path = MirrorMapPath();
+    if (mirrorFileParsed == path && mirrorFilePanelOfTri.size() == (size_t)mesh->triangleCount) return std::string();
+    mirrorFileParsed.clear();
+    mirrorFilePanels.assign(UVRT_MIRROR_MAX, uvrt_mirror{});
+    mirrorFilePanelOfTri.assign((size_t)mesh->triangleCount, 0);
+    int count = 0;
+    const std::string err = ParseMirrorRules(path.c_str(), mesh->triangles, mesh->triangleCount, mirrorFilePanels.data(), &count,
+                                             mirrorFilePanelOfTri.data());
+    if (!err.empty()) { mirrorFilePanels.clear(); mirrorFilePanelOfTri.clear(); return err; }
+    if (count == 0) { mirrorFilePanels.clear(); mirrorFilePanelOfTri.clear(); return path + ": no panel"; }
+    mirrorFilePanels.resize((size_t)count);
+    mirrorFileParsed = path;
+    mirrorFileStamp = mirrorStampNext++;
+    return std::string();
+}
+
+void RayTracer::UploadMirrors(int triangleCount)
+{
+    const std::string err = PrepareMirrorMap();
+    if (!err.empty()) fatal(("mirrorMap: " + err).c_str());
+    const bool file = !mirrorMap.empty();
+    const std::vector<uvrt_mirror>& panels = file ? mirrorFilePanels : mirrorPanels;
+    const std::vector<uint8_t>& members = file ? mirrorFilePanelOfTri : mirrorPanelOfTri;
+    const unsigned long long stamp = file ? mirrorFileStamp : mirrorValuesStamp;
+    if (panels.empty()) fatal("the mirror gather needs panels (mirrorMap or SetMirrors)");
+    if (members.size() != (size_t)triangleCount) fatal("the panels' panel_of_tri must hold triangleCount entries");
+    int32_t info[4];
+    check(uvrt_mirror_info(ctx, info), "mirror_info");
+    if (info[0] > 0 && mirrorUploaded == stamp) return;
+    check(uvrt_set_mirrors(ctx, panels.data(), (int32_t)panels.size(), members.data()), "set_mirrors");
+    mirrorUploaded = stamp;
+}
+
 void RayTracer::ComputeSegments()
 {
     std::vector<RouteLaunch> sweeps;
     for (const RouteLaunch& l : Launches())
         if (l.kind == UVRT_LAUNCH_SWEEP) sweeps.push_back(l);
     RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap());
+                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap(), HasMirrors());
 }
 
 // the uvrt_gather_params of a gather launch with seed `seed`
@@ -327,7 +420,7 @@ static uvrt_gather_params gather_params(const RouteLaunch& l, float lightLength,
 
 void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
                             double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided,
-                            bool mapped)
+                            bool mapped, bool mirrored)
 {
     if (batch < 0 || batch > UVRT_GATHER_BATCH_MAX) fatal("gatherBatch must be in [0, 64]");
     if (sided != 0 && batch >= 2) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
@@ -336,7 +429,7 @@ void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, i
     if (batch < 2 || samples <= 0 || !refineOk) {
         for (const RouteLaunch& l : list)
             RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS, reflectK, -1,
-                      sided, mapped);
+                      sided, mapped, mirrored);
         return;
     }
     // groups of up to `batch` consecutive launches: one shadow-ray pass each (include/uvrt.h uvrt_gather_direct_batch), then
@@ -363,14 +456,14 @@ void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, i
         for (size_t k = 0; k < cnt; ++k) {
             const RouteLaunch& l = list[first + k];
             RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS,
-                      reflectK, (int)k, 0, mapped);
+                      reflectK, (int)k, 0, mapped, mirrored);
         }
     }
 }
 
 void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
                           double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot, int sided,
-                          bool mapped)
+                          bool mapped, bool mirrored)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (reflectK < 0 || reflectK > 16) fatal("reflectBounces must be in [0, 16]");
@@ -385,6 +478,7 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
     if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
     if (reflect != 0.0f && samples < 1) fatal("reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)");
     if (!(reflect >= 0.0f) || !(reflect <= 1.0f)) fatal("reflectance must be in [0, 1]");
+    if (mirrored && samples < 1) fatal("mirrorMap needs gatherSamples > 0 (the mirror gather adds to the direct gather's plane)");
     if (samples > 0) {
         // the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
         if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
@@ -418,6 +512,18 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
             check(uvrt_gather_refine(ctx, &rp, 0, triangleCount, nullptr), "gather_refine");
         } else {
             gather();
+        }
+        if (mirrored) {
+            // the specular panels (raytracer.h mirrorMap): the lamp's light by way of every panel, added to the finished direct
+            // plane -- and, under reflectSided, to the face planes, so that the bounces below see it as a source
+            UploadMirrors(triangleCount);
+            int32_t faces0 = 0;
+            if (sided) {
+                check(uvrt_get_gather_faces(ctx, &faces0), "get_gather_faces");
+                check(uvrt_set_gather_faces(ctx, 1), "set_gather_faces");
+            }
+            check(uvrt_gather_mirror(ctx, &g, 1, 0, triangleCount), "gather_mirror");
+            if (sided) check(uvrt_set_gather_faces(ctx, faces0), "set_gather_faces");
         }
         if (reflect > 0.0f && reflectK > 0) {
             // reflectK bounces over recorded hit links (raytracer.h reflectBounces): traced once per scene and reflectS
@@ -484,14 +590,14 @@ void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLi
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
     RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
               gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided,
-              HasReflectanceMap());
+              HasReflectanceMap(), HasMirrors());
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
     RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
               gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided,
-              HasReflectanceMap());
+              HasReflectanceMap(), HasMirrors());
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -610,7 +716,7 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
 // capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
 void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided, bool mapped)
+                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided, bool mapped, bool mirrored)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
@@ -628,7 +734,7 @@ void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samp
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
         RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch, sided,
-                    mapped);
+                    mapped, mirrored);
         Shade();
         ++currIterations;
     }
@@ -712,6 +818,13 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (opt.reflectSided != 1) fatal("PlanDurations: reflectMapped needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)");
         if (!r0->HasReflectanceMap()) fatal("PlanDurations: reflectMapped needs a reflectance map (RayTracer::reflectMap or SetReflectanceMap)");
     }
+    if (opt.mirrorMapped != 0) {
+        if (opt.mirrorMapped != 1) fatal("PlanDurations: mirrorMapped must be 0 or 1");
+        if (opt.gatherSamples < 1) fatal("PlanDurations: mirrorMapped needs a plan from the direct gather (gatherSamples > 0)");
+        if (opt.gatherConfidence != 0.0)
+            fatal("PlanDurations: mirrorMapped is not supported with gatherConfidence (the variance plane knows nothing of the specular part)");
+        if (!r0->HasMirrors()) fatal("PlanDurations: mirrorMapped needs specular panels (RayTracer::mirrorMap or SetMirrors)");
+    }
     if (opt.reflectance != 0.0f) {
         if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
         if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
@@ -724,7 +837,7 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
         r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
                               opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch, opt.reflectSided,
-                              opt.reflectMapped != 0);
+                              opt.reflectMapped != 0, opt.mirrorMapped != 0);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }
@@ -889,6 +1002,10 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
             o << "    <reflect_map>" << reflectMap << "</reflect_map>\n";
         }
     }
+    if (!mirrorMap.empty()) {                                // the last gather tag
+        if (mirrorMap.find_first_of("<>&") != std::string::npos) fatal("mirrorMap: a file name with <, > or & cannot stand in a route file");
+        o << "    <mirror_map>" << mirrorMap << "</mirror_map>\n";
+    }
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
     if (lightPositions.empty()) o << "    <route/>\n";
@@ -940,6 +1057,11 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     reflectFileValues.clear();
     reflectFileParsed.clear();
     if ((e = root.child("reflect_map"))) reflectMap = trim(e->text);
+    mirrorMap.clear();                                       // (likewise)
+    mirrorFilePanels.clear();
+    mirrorFilePanelOfTri.clear();
+    mirrorFileParsed.clear();
+    if ((e = root.child("mirror_map"))) mirrorMap = trim(e->text);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

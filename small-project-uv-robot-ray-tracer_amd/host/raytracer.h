@@ -150,6 +150,10 @@ public:
         // SetReflectanceMap below) in place of the one rho.  0 (default): the plan above, bit for bit.  1 without reflectSided or
         // without a map: fatal.
         int reflectMapped = 0;
+        // 1 with gatherSamples > 0: every gather launch of the plan is followed by the mirror gather over the ray tracer's
+        // specular panels (RayTracer::mirrorMap or SetMirrors below).  0 (default): the plan above, bit for bit.  1 without
+        // panels, without gatherSamples or with gatherConfidence != 0 (the variance plane is the direct part's): fatal.
+        int mirrorMapped = 0;
         // B in [2, 64]: the plan's gather launches are traced in groups of up to B (RayTracer::gatherBatch below).  The plan's
         // own, like S.  0 (default) and 1: launch by launch.  Durations, report and every captured column are the same bits
         // for every B.  Outside [0, 64]: fatal.
@@ -271,6 +275,35 @@ public:
     // centroid is compared in f32, bounds included; `toward P` takes face 0 iff n.(P - v0) > 0 with n = cross(e1, e2), all in
     // f64 from the f32 values, and leaves a triangle with |n| == 0 as it is.
     static std::string ParseReflectRules(const char* path, const Tri* tris, int triangleCount, float base, float* out);
+    // Specular panels (include/uvrt.h "specular panels").  mirrorMap names a rules file (empty: none; a relative
+    // name is resolved against routeDir, as reflectMap's):
+    //     mirror X0 Y0 Z0 X1 Y1 Z1 RHO plane QX QY QZ MX MY MZ
+    // Every line makes the next panel: the plane through Q with normal M (it reflects on the side M points to), specular
+    // reflectance RHO, its members the triangles whose Tri.centroid lies in the closed box (ParseMirrorRules below; a later
+    // line takes a triangle over).  SetMirrors hands panels and panel_of_tri[triangleCount] over directly; an empty call
+    // (nullptr, 0, nullptr, 0) forgets them; a file, when one is named, goes before them.  With panels and gatherSamples > 0
+    // every gather launch -- after its direct gather (or uvrt_gather_batch_select) and its refine, before its bounces, its
+    // capture and its accumulate -- uploads the panels when uvrt_mirror_info says the context has none (a scene swap drops
+    // them) or the active panels are not the ones uploaded last, and calls uvrt_gather_mirror(the launch's gather parameters,
+    // add = 1) over all triangles, with the faces state on under reflectSided so that the bounces see the specular light.
+    // Panels with gatherSamples = 0 and a panel_of_tri whose size is not triangleCount are fatal.  No panels: every path bit
+    // for bit as before.  Saved as <mirror_map>FILE</mirror_map>, the last gather tag, when a file is named; a name that
+    // holds <, > or & cannot stand in a route file and is fatal there.
+    std::string mirrorMap;
+    std::vector<uvrt_mirror> mirrorPanels;          // the caller's panels (SetMirrors); never the file's
+    std::vector<uint8_t> mirrorPanelOfTri;
+    void SetMirrors(const uvrt_mirror* panels, int count, const uint8_t* panelOfTri, int triangleCount);
+    bool HasMirrors() const { return !mirrorMap.empty() || !mirrorPanels.empty(); }
+    // Reads mirrorMap's file unless that is what the cache holds; nothing to do without a file name.  Returns an empty string
+    // or ParseMirrorRules' message.
+    std::string PrepareMirrorMap();
+    // The rules file above into panelsOut[UVRT_MIRROR_MAX], *countOut and panelOfTriOut[triangleCount] (0 or k + 1).  Host
+    // only.  Returns an empty string, or what is wrong as "FILE:LINE: reason": an unknown keyword, a wrong count of numbers, a
+    // ninth panel, an RHO that is not finite or not in [0, 1], a zero normal, a value that is not finite where the context
+    // would refuse it, a box with a lower bound above its upper bound (or "FILE: cannot be read").  The centroid is compared
+    // in f32, bounds included.
+    static std::string ParseMirrorRules(const char* path, const Tri* tris, int triangleCount, uvrt_mirror* panelsOut, int* countOut,
+                                        uint8_t* panelOfTriOut);
     // The batched direct gather (include/uvrt.h "batched direct gather").  gatherBatch = B in [2, 64] with
     // gatherSamples > 0: ComputeDosageMap and ComputeSegments walk their launches in groups of up to B consecutive ones; a
     // group's shadow rays are traced in one uvrt_gather_direct_batch (the seeds the launches would have taken, the variance
@@ -290,18 +323,26 @@ private:
     // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance), or with reflectK > 0 that many
     // bounces over recorded hit links (reflectBounces), face-resolved with `sided` (reflectSided), with the reflectance map in
     // place of `reflect` with `mapped` (reflectMap).
+    // `mirrored`: the mirror gather over the specular panels follows the gather and its refine (mirrorMap).
     // batchSlot >= 0: the launch's planes are those of launch batchSlot of the context's gather batch (RunLaunches).
     void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
                    double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1, int sided = 0,
-                   bool mapped = false);
+                   bool mapped = false, bool mirrored = false);
     // A list of launches through RunLaunch, in order (capture: every plane into its launch's column of a plan); with
     // samples > 0 and batch >= 2 in groups of up to `batch` behind one uvrt_gather_direct_batch each (gatherBatch).
     void RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
                      double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0,
-                     bool mapped = false);
+                     bool mapped = false, bool mirrored = false);
     // the active map (the file's, read with `base` as every entry's start, or the caller's) into the context's planes when the
     // context has none or the map is not the one uploaded last (RunLaunch)
     void UploadReflectanceMap(int triangleCount, float base);
+    // the active panels (the file's or the caller's) into the context when it has none or they are not the ones uploaded last
+    void UploadMirrors(int triangleCount);
+    std::string MirrorMapPath() const;              // mirrorMap as it is opened: a relative name is routeDir's
+    std::vector<uvrt_mirror> mirrorFilePanels;      // the cache of mirrorMap's file ...
+    std::vector<uint8_t> mirrorFilePanelOfTri;
+    std::string mirrorFileParsed;                   // ... and the path it was read from (empty: nothing cached)
+    unsigned long long mirrorStampNext = 1, mirrorFileStamp = 0, mirrorValuesStamp = 0, mirrorUploaded = 0;
     std::string ReflectMapPath() const;             // reflectMap as it is opened: a relative name is routeDir's
     std::vector<float> reflectFileValues;           // the cache of reflectMap's file ...
     std::string reflectFileParsed;                  // ... the path it was read from (empty: nothing cached) ...
@@ -315,7 +356,8 @@ private:
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
     void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0, bool mapped = false);
+                           int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0, bool mapped = false,
+                           bool mirrored = false);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

@@ -92,6 +92,15 @@
 //                                           toward PX PY PZ" (only the face that looks at P); later lines override earlier ones, #
 //                                           starts a comment, every face starts at --reflect's RHO.  A relative FILE is resolved
 //                                           against --route-dir.  Refused without --reflect-sided.  --save-route writes <reflect_map>
+//            [--mirror-map FILE]            with --gather S or --plan-gather S: specular reflector panels (RayTracer::mirrorMap,
+//                                           PlanOptions::mirrorMapped).  FILE holds lines "mirror X0 Y0 Z0 X1 Y1 Z1 RHO
+//                                           plane QX QY QZ MX MY MZ": the next panel (8 at most) is the plane through Q with normal
+//                                           M, it reflects on the side M points to with the specular reflectance RHO, and the
+//                                           triangles whose centroid lies in the closed box are where it is a mirror; # starts a
+//                                           comment.  After every gather launch the lamp's mirror image in every panel is gathered
+//                                           into the launch's plane (two traced legs per sample), before the diffuse bounces.  A
+//                                           relative FILE is resolved against --route-dir.  Refused with --plan-confidence (the
+//                                           variance plane is the direct part's).  --save-route writes <mirror_map>
 //            [--gather-batch B]             with --gather S or --plan-gather S: trace the gather launches in groups of up to B in
 //                                           [0, 64] (RayTracer::gatherBatch, PlanOptions::gatherBatch): one shadow-ray
 //                                           pass per group instead of one per launch.  0 (default) and 1: launch by launch.  B
@@ -160,7 +169,8 @@ std::vector<float> recompute(RayTracer& rt, uint32_t seed, int batch)
 
 int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool holdout, uint32_t holdoutSeed, int batch,
              const std::string& dump, const std::string& verifyDump, int planGather, int gatherSampling, double planConfidence,
-             double refineTau, int refineMax, float reflect, int reflectS, int reflectK, int reflectSided, int reflectMapped)
+             double refineTau, int refineMax, float reflect, int reflectS, int reflectK, int reflectSided, int reflectMapped,
+             int mirrorMapped)
 {
     const int T = rt.mesh->triangleCount;
     RayTracer::PlanOptions opt;
@@ -176,6 +186,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
     opt.reflectBounces = planGather > 0 ? reflectK : 0;
     opt.reflectSided = planGather > 0 ? reflectSided : 0;
     opt.reflectMapped = planGather > 0 ? reflectMapped : 0;
+    opt.mirrorMapped = planGather > 0 ? mirrorMapped : 0;
     opt.gatherBatch = planGather > 0 ? rt.gatherBatch : 0;   // (--gather-batch: --plan-verify recomputes in the same groups)
     unsigned seed0 = 0;
     const uvrt_plan_report r = rt.PlanDurations(opt, &seed0);
@@ -185,6 +196,7 @@ int run_plan(RayTracer& rt, float minDose, int minPhotons, bool verify, bool hol
         printf("plan: exposure from the direct gather, %d samples per triangle and launch\n", planGather);
         if (opt.gatherSampling == UVRT_GATHER_STRATIFIED) printf("plan: stratified gather sampling\n");
         if (opt.gatherConfidence > 0.0) printf("plan: lower confidence bound, z = %.9g\n", opt.gatherConfidence);
+        if (opt.mirrorMapped) printf("plan: specular panels %s\n", rt.mirrorMap.c_str());
         if (opt.gatherRelError > 0.0) {
             rt.gatherRelError = opt.gatherRelError;     // --plan-verify recomputes the plan's own estimates
             rt.gatherMaxExtra = opt.gatherMaxExtra;
@@ -277,6 +289,7 @@ int main(int argc, char** argv)
     int reflectK = 0;                       // 0: not given
     int reflectSided = 0;                   // --reflect-sided
     std::string reflectMapFile;             // --reflect-map
+    std::string mirrorMapFile;              // --mirror-map
     int gatherBatch = -1;                   // < 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -384,6 +397,7 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(argv[i], "--reflect-sided")) reflectSided = 1;
         else if (!strcmp(argv[i], "--reflect-map")) { need(1); reflectMapFile = argv[++i]; if (reflectMapFile.empty() || reflectMapFile.find_first_of("<>&") != std::string::npos) { fprintf(stderr, "--reflect-map FILE: a file name without <, > and & (it goes into route files as it is)\n"); return 2; } }
+        else if (!strcmp(argv[i], "--mirror-map")) { need(1); mirrorMapFile = argv[++i]; if (mirrorMapFile.empty() || mirrorMapFile.find_first_of("<>&") != std::string::npos) { fprintf(stderr, "--mirror-map FILE: a file name without <, > and & (it goes into route files as it is)\n"); return 2; } }
         else if (!strcmp(argv[i], "--gather-batch")) {
             need(1);
             char* end = nullptr;
@@ -412,6 +426,8 @@ int main(int argc, char** argv)
     if (reflectSided && !(reflect > 0.0f)) { fprintf(stderr, "--reflect-sided needs --reflect RHO with RHO > 0: without a bounce there are no faces to resolve\n"); return 2; }
     if (reflectSided && gatherBatch >= 2) { fprintf(stderr, "--reflect-sided cannot be combined with --gather-batch B >= 2 (a gather batch keeps no face planes)\n"); return 2; }
     if (!reflectMapFile.empty() && !reflectSided) { fprintf(stderr, "--reflect-map needs --reflect-sided (with --reflect RHO[,S2] and --reflect-bounces K): only the face-resolved bounces know which face a reflectance belongs to\n"); return 2; }
+    if (!mirrorMapFile.empty() && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--mirror-map needs --gather S or --plan-gather S (S > 0): the mirror gather adds to the direct gather's plane\n"); return 2; }
+    if (!mirrorMapFile.empty() && planConfidence >= 0.0) { fprintf(stderr, "--mirror-map cannot be combined with --plan-confidence (the variance plane knows nothing of the specular part)\n"); return 2; }
     if (gatherBatch >= 0 && !(gather > 0) && !(planGather > 0)) { fprintf(stderr, "--gather-batch needs --gather S or --plan-gather S (S > 0)\n"); return 2; }
     if (planGather > 0 && gather > 0) { fprintf(stderr, "--plan-gather cannot be combined with --gather (it plans a route of stops and segments and gathers on its own)\n"); return 2; }
     if (planGather > 0 && batch > 0) { fprintf(stderr, "--plan-gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
@@ -449,6 +465,8 @@ int main(int argc, char** argv)
     if (refineTau > 0.0 && gather > 0) { rayTracer.gatherRelError = refineTau; rayTracer.gatherMaxExtra = refineMax; }
     if (reflect >= 0.0f && gather > 0) { rayTracer.reflectance = reflect; rayTracer.reflectSamples = reflectS; rayTracer.reflectBounces = reflectK; rayTracer.reflectSided = reflectSided; rayTracer.reflectMap = reflectMapFile; }
     if (gatherBatch >= 0) rayTracer.gatherBatch = gatherBatch;
+    if (!mirrorMapFile.empty()) rayTracer.mirrorMap = mirrorMapFile;
+    else if (rayTracer.gatherSamples == 0 || plan) rayTracer.mirrorMap.clear();    // (the route file's own <mirror_map>: a plan's panels are --mirror-map's)
     if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectance = 0.0f;    // (the route file's own <reflectance>: a plan's bounce is --reflect's)
     if (rayTracer.gatherSamples == 0 || plan) rayTracer.reflectMap = planGather > 0 ? reflectMapFile : std::string();   // (likewise its <reflect_map>)
     if (rayTracer.gatherSamples > 0 && (batch > 0 || gpus != 1 || plan)) {     // (the route file's own <gather_samples>)
@@ -474,7 +492,8 @@ int main(int argc, char** argv)
         rayTracer.viewMode = dosage;
         const int rc = run_plan(rayTracer, planMin, minPhotons, planVerify, planHoldout, holdoutSeed, batch, dump, verifyDump, planGather,
                                 gatherSampling < 0 ? 0 : gatherSampling, planConfidence < 0.0 ? 0.0 : planConfidence, refineTau, refineMax,
-                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK, reflectSided, reflectMapFile.empty() ? 0 : 1);
+                                reflect < 0.0f ? 0.0f : reflect, reflectS, reflectK, reflectSided, reflectMapFile.empty() ? 0 : 1,
+                                mirrorMapFile.empty() ? 0 : 1);
         save_route(rayTracer, saveRoute);
         return rc;
     }
