@@ -64,32 +64,10 @@ SYMBOLS = [
     ("uvrt_host_rt_lamp_count", C.c_int, [_vp]),
     ("uvrt_host_rt_get_lamp", None, [_vp, C.c_int, C.POINTER(C.c_float)]),
     ("uvrt_host_rt_set_lamps", None, [_vp, C.POINTER(C.c_float), C.c_int]),
-    ("uvrt_host_rt_plan", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, _vp,
-                                 C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int, _vp,
-                                        C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_sampling", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                                 C.c_int, _vp, C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_confidence", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                                   C.c_int, C.c_double, _vp, C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_refine", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                               C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_plan_options_init", None, [_vp]),
+    ("uvrt_host_plan_options_layout", C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    ("uvrt_host_rt_plan", None, [_vp, _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_set_gather_refine", None, [_vp, C.c_double, C.c_int]),
-    ("uvrt_host_rt_plan_gather_reflect", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                                C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, _vp,
-                                                C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_reflect_linked", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
-                                                       _vp, C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_batch", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                              C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
-                                              _vp, C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_reflect_sided", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                                      C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
-                                                      C.c_int, _vp, C.POINTER(C.c_uint)]),
-    ("uvrt_host_rt_plan_gather_reflect_mapped", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
-                                                       C.c_int, C.c_int, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_set_reflect_map", None, [_vp, C.c_char_p]),
     ("uvrt_host_rt_get_reflect_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
     ("uvrt_host_rt_set_reflectance_map", None, [_vp, _vp, C.c_int]),
@@ -97,17 +75,13 @@ SYMBOLS = [
     ("uvrt_host_rt_has_reflect_map", C.c_int, [_vp]),
     ("uvrt_host_rt_prepare_reflect_map", C.c_int, [_vp, C.c_float, C.c_char_p, C.c_int]),
     ("uvrt_host_reflect_rules", C.c_int, [C.c_char_p, _vp, C.c_int, C.c_float, _vp, C.c_char_p, C.c_int]),
-    ("uvrt_host_rt_plan_gather_mirror", None, [_vp, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_int,
-                                               C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, C.c_int, C.c_int,
-                                               C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_set_mirror_map", None, [_vp, C.c_char_p]),
     ("uvrt_host_rt_get_mirror_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
     ("uvrt_host_rt_set_mirrors", None, [_vp, _vp, C.c_int, _vp, C.c_int]),
     ("uvrt_host_rt_has_mirrors", C.c_int, [_vp]),
     ("uvrt_host_rt_prepare_mirror_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
     ("uvrt_host_mirror_rules", C.c_int, [C.c_char_p, _vp, C.c_int, _vp, C.POINTER(C.c_int), _vp, C.c_char_p, C.c_int]),
-    ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
-                                       _vp, _vp, C.POINTER(C.c_uint)]),
+    ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
     ("uvrt_host_rt_plan_segments", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     ("uvrt_host_rt_end_plan", None, [_vp]),
@@ -128,6 +102,24 @@ _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations
                "photonMapSize", "viewMode", "gatherSamples", "gatherSampling", "gatherMaxExtra",
                "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
+
+
+
+class PlanOptions(C.Structure):
+    """uvrt_host_plan_options (host/host_capi.cpp), the plain mirror of RayTracer::PlanOptions that uvrt_host_rt_plan and
+    uvrt_host_rt_plan_group take.  A new one holds the defaults of RayTracer::PlanOptions{} (uvrt_host_plan_options_init);
+    keyword arguments set fields."""
+    _fields_ = [("min_dose", C.c_float), ("min_photons", C.c_int), ("margin", C.c_double), ("rel_gap", C.c_double),
+                ("max_iterations", C.c_int), ("mask", _vp), ("gather_samples", C.c_int), ("gather_sampling", C.c_int),
+                ("gather_confidence", C.c_double), ("gather_rel_error", C.c_double), ("gather_max_extra", C.c_int),
+                ("reflectance", C.c_float), ("reflect_samples", C.c_int), ("reflect_bounces", C.c_int),
+                ("reflect_sided", C.c_int), ("reflect_mapped", C.c_int), ("mirror_mapped", C.c_int), ("gather_batch", C.c_int)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        lib().uvrt_host_plan_options_init(C.byref(self))
+        for name, value in fields.items():
+            setattr(self, name, value)
 
 
 def lib():
@@ -480,24 +472,14 @@ class RayTracer:
         up to B, one shadow-ray pass each.  B > 0 needs gather_samples > 0; it changes no bit of the durations, the
         report or the captured columns.  0 and 1 are PlanDurations.  (PlanDurationsRefined and PlanDurationsReflect take
         gather_batch = B among their plan arguments.)"""
-        args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0, mirror_mapped=0)
-        unknown = set(plan) - set(args)
-        if unknown:
-            raise TypeError("PlanDurationsBatched: unknown arguments %s" % sorted(unknown))
-        args.update(plan)
+        args = _plan_args("PlanDurationsBatched", plan, mirror_mapped=0)
         return self._plan_durations(gather_rel_error=0.0, gather_max_extra=64, gather_batch=gather_batch, **args)
 
     def PlanDurationsRefined(self, gather_rel_error, gather_max_extra=64, **plan):
         """PlanDurations(**plan) with PlanOptions::gatherRelError = gather_rel_error and gatherMaxExtra = gather_max_extra:
         every gather launch of the plan is refined before its capture.  tau > 0 needs gather_samples >= 2 and
         works with and without gather_confidence; 0 is PlanDurations, bit for bit."""
-        args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0, gather_batch=0, mirror_mapped=0)
-        unknown = set(plan) - set(args)
-        if unknown:
-            raise TypeError("PlanDurationsRefined: unknown arguments %s" % sorted(unknown))
-        args.update(plan)
+        args = _plan_args("PlanDurationsRefined", plan, gather_batch=0, mirror_mapped=0)
         return self._plan_durations(gather_rel_error=gather_rel_error, gather_max_extra=gather_max_extra, **args)
 
     def PlanDurationsReflect(self, reflectance, reflect_samples=16, gather_rel_error=0.0, gather_max_extra=64, reflect_bounces=0,
@@ -512,12 +494,7 @@ class RayTracer:
         reflect_mapped = 1 (PlanOptions::reflectMapped): those bounces take the ray tracer's reflectance map (reflectMap or
         SetReflectanceMap) with rho as every face's start; it needs reflect_sided = 1 and a map; 0 is the one rho,
         bit for bit."""
-        args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
-                    gather_sampling=0, gather_confidence=0.0, gather_batch=0, mirror_mapped=0)
-        unknown = set(plan) - set(args)
-        if unknown:
-            raise TypeError("PlanDurationsReflect: unknown arguments %s" % sorted(unknown))
-        args.update(plan)
+        args = _plan_args("PlanDurationsReflect", plan, gather_batch=0, mirror_mapped=0)
         rho, s2 = float(np.float32(reflectance)), int(reflect_samples)
         if int(reflect_bounces) != reflect_bounces or not (0 <= int(reflect_bounces) <= 16):
             raise ValueError("reflect_bounces must be an integer in [0, 16]")
@@ -579,66 +556,16 @@ class RayTracer:
             raise ValueError("gather_rel_error needs gather_samples >= 2")
         if tau > 0.0 and (extra < 2 or extra > 4096 or extra & (extra - 1)):
             raise ValueError("gather_max_extra must be a power of two in [2, 4096]")
-        rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, self.mesh.triangleCount)
-        if mirror_mapped:
-            self._L.uvrt_host_rt_plan_gather_mirror(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                                    float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                                    int(gather_samples), int(gather_sampling), z, tau, extra, float(reflectance),
-                                                    int(reflect_samples), int(reflect_bounces), B, int(reflect_sided),
-                                                    int(reflect_mapped), 1, C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if reflect_mapped:
-            self._L.uvrt_host_rt_plan_gather_reflect_mapped(self._h, -1.0 if min_dose is None else float(min_dose),
-                                                            int(min_photons), float(margin), float(rel_gap), int(max_iterations),
-                                                            _addr(keep), int(gather_samples), int(gather_sampling), z, tau, extra,
-                                                            float(reflectance), int(reflect_samples), int(reflect_bounces), 1, 1,
-                                                            C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if reflect_sided:
-            self._L.uvrt_host_rt_plan_gather_reflect_sided(self._h, -1.0 if min_dose is None else float(min_dose),
-                                                           int(min_photons), float(margin), float(rel_gap), int(max_iterations),
-                                                           _addr(keep), int(gather_samples), int(gather_sampling), z, tau, extra,
-                                                           float(reflectance), int(reflect_samples), int(reflect_bounces), 1,
-                                                           C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if B:
-            self._L.uvrt_host_rt_plan_gather_batch(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                                   float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                                   int(gather_samples), int(gather_sampling), z, tau, extra, float(reflectance),
-                                                   int(reflect_samples), int(reflect_bounces), B, C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if reflectance > 0.0 and reflect_bounces > 0:
-            self._L.uvrt_host_rt_plan_gather_reflect_linked(self._h, -1.0 if min_dose is None else float(min_dose),
-                                                            int(min_photons), float(margin), float(rel_gap), int(max_iterations),
-                                                            _addr(keep), int(gather_samples), int(gather_sampling), z, tau, extra,
-                                                            float(reflectance), int(reflect_samples), int(reflect_bounces),
-                                                            C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if reflectance > 0.0:
-            self._L.uvrt_host_rt_plan_gather_reflect(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                                     float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                                     int(gather_samples), int(gather_sampling), z, tau, extra,
-                                                     float(reflectance), int(reflect_samples), C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if tau > 0.0:
-            self._L.uvrt_host_rt_plan_gather_refine(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                                    float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                                    int(gather_samples), int(gather_sampling), z, tau, extra, C.byref(rep),
-                                                    C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if z > 0.0:
-            self._L.uvrt_host_rt_plan_gather_confidence(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                                        float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                                        int(gather_samples), int(gather_sampling), z, C.byref(rep),
-                                                        C.byref(seed))
-            return _plan_result(self, rep, seed)
-        if gather_samples:
-            self._L.uvrt_host_rt_plan_gather_sampling(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                                      float(margin), float(rel_gap), int(max_iterations), _addr(keep),
-                                                      int(gather_samples), int(gather_sampling), C.byref(rep), C.byref(seed))
-            return _plan_result(self, rep, seed)
-        self._L.uvrt_host_rt_plan(self._h, -1.0 if min_dose is None else float(min_dose), int(min_photons), float(margin),
-                                  float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))
+        keep = _mask_arg(mask, self.mesh.triangleCount)
+        opt = PlanOptions(min_dose=-1.0 if min_dose is None else float(min_dose), min_photons=int(min_photons), margin=float(margin),
+                          rel_gap=float(rel_gap), max_iterations=int(max_iterations), mask=_addr(keep),
+                          gather_samples=int(gather_samples), gather_sampling=int(gather_sampling), gather_confidence=z,
+                          gather_rel_error=tau, gather_max_extra=extra, reflectance=float(reflectance),
+                          reflect_samples=int(reflect_samples), reflect_bounces=int(reflect_bounces),
+                          reflect_sided=int(reflect_sided), reflect_mapped=int(reflect_mapped), mirror_mapped=int(mirror_mapped),
+                          gather_batch=B)
+        rep, seed = capi.PlanReport(), C.c_uint()
+        self._L.uvrt_host_rt_plan(self._h, C.byref(opt), C.byref(rep), C.byref(seed))
         return _plan_result(self, rep, seed)
 
     def EndPlan(self):
@@ -681,6 +608,17 @@ def _check_gather_batch(value):
     return int(value)
 
 
+def _plan_args(who, plan, **own):
+    """the **plan of the wrapper `who` over PlanDurations' arguments and the wrapper's `own`; a name that is neither is a TypeError"""
+    args = dict(min_dose=None, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, mask=None, gather_samples=0,
+                gather_sampling=0, gather_confidence=0.0, **own)
+    unknown = set(plan) - set(args)
+    if unknown:
+        raise TypeError("%s: unknown arguments %s" % (who, sorted(unknown)))
+    args.update(plan)
+    return args
+
+
 def _mask_arg(mask, T):
     if mask is None:
         return None
@@ -711,9 +649,11 @@ def plan_durations_group(rts, min_dose=None, min_photons=16, margin=1e-6, rel_ga
     """RayTracer::PlanDurations over instances that share every launch by ray range (one process): every context
     captures after the group reduce and solves on its own; the durations must agree."""
     arr = (C.c_void_p * len(rts))(*[rt._h for rt in rts])
-    rep, seed, keep = capi.PlanReport(), C.c_uint(), _mask_arg(mask, rts[0].mesh.triangleCount)
-    lib().uvrt_host_rt_plan_group(arr, len(rts), -1.0 if min_dose is None else float(min_dose), int(min_photons),
-                                  float(margin), float(rel_gap), int(max_iterations), _addr(keep), C.byref(rep), C.byref(seed))
+    keep = _mask_arg(mask, rts[0].mesh.triangleCount)
+    opt = PlanOptions(min_dose=-1.0 if min_dose is None else float(min_dose), min_photons=int(min_photons), margin=float(margin),
+                      rel_gap=float(rel_gap), max_iterations=int(max_iterations), mask=_addr(keep))
+    rep, seed = capi.PlanReport(), C.c_uint()
+    lib().uvrt_host_rt_plan_group(arr, len(rts), C.byref(opt), C.byref(rep), C.byref(seed))
     return _plan_result(rts[0], rep, seed)
 
 

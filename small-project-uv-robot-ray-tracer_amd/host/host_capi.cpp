@@ -3,6 +3,7 @@
 #include "raytracer.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -27,27 +28,11 @@ std::vector<LightPos> positions(const float* xyd, int n)
 
 std::vector<RayTracer*> group(void** rs, int n) { return std::vector<RayTracer*>((RayTracer**)rs, (RayTracer**)rs + n); }
 
-RayTracer::PlanOptions plan_options(float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                    const unsigned char* mask, int gather_samples, int gather_sampling = 0,
-                                    double gather_confidence = 0.0, double gather_rel_error = 0.0, int gather_max_extra = 64,
-                                    float reflectance = 0.0f, int reflect_samples = 16, int reflect_bounces = 0, int gather_batch = 0,
-                                    int reflect_sided = 0, int reflect_mapped = 0, int mirror_mapped = 0)
+// a message for a ctypes caller: copied into err (cut to fit), 0 when it is empty and -1 otherwise
+int report(const std::string& e, char* err, int err_len)
 {
-    RayTracer::PlanOptions o;
-    o.minDose = min_dose; o.minPhotons = min_photons; o.margin = margin; o.relGap = rel_gap;
-    o.maxIterations = max_iterations; o.mask = mask; o.gatherSamples = gather_samples;
-    o.gatherSampling = gather_sampling;
-    o.gatherConfidence = gather_confidence;
-    o.gatherRelError = gather_rel_error;
-    o.gatherMaxExtra = gather_max_extra;
-    o.reflectance = reflectance;
-    o.reflectSamples = reflect_samples;
-    o.reflectBounces = reflect_bounces;
-    o.gatherBatch = gather_batch;
-    o.reflectSided = reflect_sided;
-    o.reflectMapped = reflect_mapped;
-    o.mirrorMapped = mirror_mapped;
-    return o;
+    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
+    return e.empty() ? 0 : -1;
 }
 
 }  // namespace
@@ -143,16 +128,12 @@ int uvrt_host_rt_reflectance_map(void* r, float* out, int n)
 int uvrt_host_rt_has_reflect_map(void* r) { return ((RayTracer*)r)->HasReflectanceMap() ? 1 : 0; }
 int uvrt_host_rt_prepare_reflect_map(void* r, float base, char* err, int err_len)
 {
-    const std::string e = ((RayTracer*)r)->PrepareReflectMap(base);
-    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
-    return e.empty() ? 0 : -1;
+    return report(((RayTracer*)r)->PrepareReflectMap(base), err, err_len);
 }
 // RayTracer::ParseReflectRules over `count` 64-byte Tri records: 0 and out[2 * count], or -1 and the message in err
 int uvrt_host_reflect_rules(const char* path, const void* tris64, int count, float base, float* out, char* err, int err_len)
 {
-    const std::string e = RayTracer::ParseReflectRules(path, (const Tri*)tris64, count, base, out);
-    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
-    return e.empty() ? 0 : -1;
+    return report(RayTracer::ParseReflectRules(path, (const Tri*)tris64, count, base, out), err, err_len);
 }
 
 // RayTracer::mirrorMap (the rules file; "" for none) and the caller's panels (SetMirrors; count 0 forgets them);
@@ -171,18 +152,14 @@ void uvrt_host_rt_set_mirrors(void* r, const uvrt_mirror* panels, int count, con
 int uvrt_host_rt_has_mirrors(void* r) { return ((RayTracer*)r)->HasMirrors() ? 1 : 0; }
 int uvrt_host_rt_prepare_mirror_map(void* r, char* err, int err_len)
 {
-    const std::string e = ((RayTracer*)r)->PrepareMirrorMap();
-    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
-    return e.empty() ? 0 : -1;
+    return report(((RayTracer*)r)->PrepareMirrorMap(), err, err_len);
 }
 // RayTracer::ParseMirrorRules over `count` 64-byte Tri records: 0, *panels_count, panels_out[8] and panel_of_tri_out[count], or
 // -1 and the message in err
 int uvrt_host_mirror_rules(const char* path, const void* tris64, int count, uvrt_mirror* panels_out, int* panels_count,
                            unsigned char* panel_of_tri_out, char* err, int err_len)
 {
-    const std::string e = RayTracer::ParseMirrorRules(path, (const Tri*)tris64, count, panels_out, panels_count, panel_of_tri_out);
-    if (err && err_len > 0) { strncpy(err, e.c_str(), (size_t)err_len - 1); err[err_len - 1] = 0; }
-    return e.empty() ? 0 : -1;
+    return report(RayTracer::ParseMirrorRules(path, (const Tri*)tris64, count, panels_out, panels_count, panel_of_tri_out), err, err_len);
 }
 
 // RayTracer::gatherRelError and gatherMaxExtra (the adaptive gather of every gather launch; rel_error 0: off)
@@ -222,112 +199,56 @@ int uvrt_host_route_launches(const float* xzd, int L, float y, float drive_speed
     return (int)list.size();
 }
 
-// duration planning: durations -> lightPositions, report -> *rep, starting SEED -> *seed
-void uvrt_host_rt_plan(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                       const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
+// duration planning: RayTracer::PlanOptions as one plain struct (host.PlanOptions mirrors it field for field; a new option is
+// a line in X below and one there).  uvrt_host_plan_options_init writes the defaults of RayTracer::PlanOptions{};
+// uvrt_host_plan_options_layout writes every field's offset in declaration order, then the size, and returns how many numbers
+// that is (at most `max` are written): the mirror is held to it.
+#define UVRT_HOST_PLAN_OPTIONS(X) \
+    X(float, min_dose, minDose) X(int, min_photons, minPhotons) X(double, margin, margin) X(double, rel_gap, relGap) \
+    X(int, max_iterations, maxIterations) X(const unsigned char*, mask, mask) X(int, gather_samples, gatherSamples) \
+    X(int, gather_sampling, gatherSampling) X(double, gather_confidence, gatherConfidence) \
+    X(double, gather_rel_error, gatherRelError) X(int, gather_max_extra, gatherMaxExtra) X(float, reflectance, reflectance) \
+    X(int, reflect_samples, reflectSamples) X(int, reflect_bounces, reflectBounces) X(int, reflect_sided, reflectSided) \
+    X(int, reflect_mapped, reflectMapped) X(int, mirror_mapped, mirrorMapped) X(int, gather_batch, gatherBatch)
+struct uvrt_host_plan_options {
+#define X(type, name, member) type name;
+    UVRT_HOST_PLAN_OPTIONS(X)
+#undef X
+};
+static RayTracer::PlanOptions plan_options(const uvrt_host_plan_options* o)
 {
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, 0), seed);
+    RayTracer::PlanOptions p;
+#define X(type, name, member) p.member = o->name;
+    UVRT_HOST_PLAN_OPTIONS(X)
+#undef X
+    return p;
 }
-// the same with PlanOptions::gatherSamples: > 0 plans from the direct gather
-void uvrt_host_rt_plan_gather(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                              const unsigned char* mask, int gather_samples, uvrt_plan_report* rep, unsigned* seed)
+void uvrt_host_plan_options_init(uvrt_host_plan_options* o)
 {
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples), seed);
+    const RayTracer::PlanOptions p;
+#define X(type, name, member) o->name = p.member;
+    UVRT_HOST_PLAN_OPTIONS(X)
+#undef X
 }
-// the same with PlanOptions::gatherSampling beside it (include/uvrt.h uvrt_set_gather_sampling)
-void uvrt_host_rt_plan_gather_sampling(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                       const unsigned char* mask, int gather_samples, int gather_sampling, uvrt_plan_report* rep,
-                                       unsigned* seed)
+int uvrt_host_plan_options_layout(int* out, int max)
 {
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling), seed);
+    const int layout[] = {
+#define X(type, name, member) (int)offsetof(uvrt_host_plan_options, name),
+        UVRT_HOST_PLAN_OPTIONS(X)
+#undef X
+        (int)sizeof(uvrt_host_plan_options)};
+    const int n = (int)(sizeof layout / sizeof layout[0]);
+    for (int i = 0; i < n && i < max; ++i) out[i] = layout[i];
+    return n;
 }
-// the same with PlanOptions::gatherConfidence beside them (include/uvrt.h uvrt_plan_lower_confidence)
-void uvrt_host_rt_plan_gather_confidence(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                         const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
-                                         uvrt_plan_report* rep, unsigned* seed)
+// durations -> lightPositions, report -> *rep, starting SEED -> *seed
+void uvrt_host_rt_plan(void* r, const uvrt_host_plan_options* o, uvrt_plan_report* rep, unsigned* seed)
 {
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence), seed);
+    *rep = ((RayTracer*)r)->PlanDurations(plan_options(o), seed);
 }
-// the same with PlanOptions::gatherRelError / gatherMaxExtra beside them (include/uvrt.h uvrt_gather_refine)
-void uvrt_host_rt_plan_gather_refine(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                     const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
-                                     double gather_rel_error, int gather_max_extra, uvrt_plan_report* rep, unsigned* seed)
+void uvrt_host_rt_plan_group(void** rs, int n, const uvrt_host_plan_options* o, uvrt_plan_report* rep, unsigned* seed)
 {
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra), seed);
-}
-// the same with PlanOptions::reflectance / reflectSamples beside them (include/uvrt.h uvrt_gather_indirect)
-void uvrt_host_rt_plan_gather_reflect(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                      const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
-                                      double gather_rel_error, int gather_max_extra, float reflectance, int reflect_samples,
-                                      uvrt_plan_report* rep, unsigned* seed)
-{
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
-                                                       reflectance, reflect_samples), seed);
-}
-// the same with PlanOptions::reflectBounces: the bounces over recorded hit links (include/uvrt.h uvrt_gather_indirect_linked)
-void uvrt_host_rt_plan_gather_reflect_linked(void* r, float min_dose, int min_photons, double margin, double rel_gap,
-                                             int max_iterations, const unsigned char* mask, int gather_samples, int gather_sampling,
-                                             double gather_confidence, double gather_rel_error, int gather_max_extra,
-                                             float reflectance, int reflect_samples, int reflect_bounces, uvrt_plan_report* rep,
-                                             unsigned* seed)
-{
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
-                                                       reflectance, reflect_samples, reflect_bounces), seed);
-}
-// the same with PlanOptions::gatherBatch: the plan's gather launches traced in groups (include/uvrt.h uvrt_gather_direct_batch)
-void uvrt_host_rt_plan_gather_batch(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                    const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
-                                    double gather_rel_error, int gather_max_extra, float reflectance, int reflect_samples,
-                                    int reflect_bounces, int gather_batch, uvrt_plan_report* rep, unsigned* seed)
-{
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
-                                                       reflectance, reflect_samples, reflect_bounces, gather_batch), seed);
-}
-// the same with PlanOptions::reflectSided: face-resolved bounces (include/uvrt.h uvrt_gather_indirect_linked_sided)
-void uvrt_host_rt_plan_gather_reflect_sided(void* r, float min_dose, int min_photons, double margin, double rel_gap,
-                                            int max_iterations, const unsigned char* mask, int gather_samples, int gather_sampling,
-                                            double gather_confidence, double gather_rel_error, int gather_max_extra,
-                                            float reflectance, int reflect_samples, int reflect_bounces, int reflect_sided,
-                                            uvrt_plan_report* rep, unsigned* seed)
-{
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
-                                                       reflectance, reflect_samples, reflect_bounces, 0, reflect_sided), seed);
-}
-// the same with PlanOptions::reflectMapped: the ray tracer's reflectance map (include/uvrt.h uvrt_gather_indirect_linked_mapped)
-void uvrt_host_rt_plan_gather_reflect_mapped(void* r, float min_dose, int min_photons, double margin, double rel_gap,
-                                             int max_iterations, const unsigned char* mask, int gather_samples, int gather_sampling,
-                                             double gather_confidence, double gather_rel_error, int gather_max_extra,
-                                             float reflectance, int reflect_samples, int reflect_bounces, int reflect_sided,
-                                             int reflect_mapped, uvrt_plan_report* rep, unsigned* seed)
-{
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
-                                                       reflectance, reflect_samples, reflect_bounces, 0, reflect_sided,
-                                                       reflect_mapped), seed);
-}
-// the same with PlanOptions::gatherBatch and mirrorMapped: the ray tracer's specular panels (include/uvrt.h uvrt_gather_mirror)
-void uvrt_host_rt_plan_gather_mirror(void* r, float min_dose, int min_photons, double margin, double rel_gap, int max_iterations,
-                                     const unsigned char* mask, int gather_samples, int gather_sampling, double gather_confidence,
-                                     double gather_rel_error, int gather_max_extra, float reflectance, int reflect_samples,
-                                     int reflect_bounces, int gather_batch, int reflect_sided, int reflect_mapped, int mirror_mapped,
-                                     uvrt_plan_report* rep, unsigned* seed)
-{
-    *rep = ((RayTracer*)r)->PlanDurations(plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, gather_samples,
-                                                       gather_sampling, gather_confidence, gather_rel_error, gather_max_extra,
-                                                       reflectance, reflect_samples, reflect_bounces, gather_batch, reflect_sided,
-                                                       reflect_mapped, mirror_mapped), seed);
-}
-void uvrt_host_rt_plan_group(void** rs, int n, float min_dose, int min_photons, double margin, double rel_gap,
-                             int max_iterations, const unsigned char* mask, uvrt_plan_report* rep, unsigned* seed)
-{
-    *rep = RayTracer::PlanDurations(group(rs, n), plan_options(min_dose, min_photons, margin, rel_gap, max_iterations, mask, 0), seed);
+    *rep = RayTracer::PlanDurations(group(rs, n), plan_options(o), seed);
 }
 // of the last PlanDurations: the bounds report and the segment columns (returns their number; copies at most n)
 void uvrt_host_rt_plan_bounds(void* r, uvrt_plan_bounds_report* out) { *out = ((RayTracer*)r)->planBounds; }

@@ -127,6 +127,30 @@ bool to_float(const std::string& t, float* v) { return sscanf(t.c_str(), "%f", v
 // tinyxml2 XMLUtil::ToStr(float): "%.8g"
 std::string float_str(float v) { char b[64]; snprintf(b, sizeof b, "%.8g", (double)v); return b; }
 
+// A 0/1 state of the context that a launch needs on: read, set to 1, and put back when the scope ends (nothing when not armed)
+struct ContextState {
+    int (*get)(uvrt_ctx*, int32_t*);
+    int (*set)(uvrt_ctx*, int32_t);
+    const char *getName, *setName;
+};
+const ContextState kVariancePlane = {uvrt_get_gather_variance, uvrt_set_gather_variance, "get_gather_variance", "set_gather_variance"};
+const ContextState kFacePlanes = {uvrt_get_gather_faces, uvrt_set_gather_faces, "get_gather_faces", "set_gather_faces"};
+struct ScopedState {
+    ScopedState(uvrt_ctx* c, const ContextState& s, bool on) : ctx(c), state(s), armed(on)
+    {
+        if (!armed) return;
+        check(state.get(ctx, &before), state.getName);
+        check(state.set(ctx, 1), state.setName);
+    }
+    ~ScopedState() { if (armed) check(state.set(ctx, before), state.setName); }
+    ScopedState(const ScopedState&) = delete;
+    ScopedState& operator=(const ScopedState&) = delete;
+    uvrt_ctx* ctx;
+    const ContextState& state;
+    bool armed;
+    int32_t before = 0;
+};
+
 }  // namespace
 
 RayTracer::~RayTracer()
@@ -186,8 +210,62 @@ std::vector<RouteLaunch> RayTracer::Launches() const
 
 void RayTracer::ComputeDosageMap()                           // raytracer.cpp:66-72
 {
-    RunLaunches(Launches(), photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap(), HasMirrors());
+    RunLaunches(Launches(), photonsPerLight, mesh->triangleCount, OwnGather(), false);
+}
+
+// ------------------------------------------------------------ how a launch gathers (raytracer.h GatherOptions)
+RayTracer::GatherOptions RayTracer::OwnGather() const
+{
+    GatherOptions g;
+    g.samples = gatherSamples; g.sampling = gatherSampling;
+    g.relError = gatherRelError; g.maxExtra = gatherMaxExtra;
+    g.reflectance = reflectance; g.reflectSamples = reflectSamples; g.reflectBounces = reflectBounces;
+    g.sided = reflectSided; g.mapped = HasReflectanceMap(); g.mirrored = HasMirrors();
+    g.batch = gatherBatch;
+    return g;
+}
+
+RayTracer::GatherOptions RayTracer::PlanGather(const PlanOptions& opt)
+{
+    GatherOptions g;
+    g.samples = opt.gatherSamples; g.sampling = opt.gatherSampling;
+    g.relError = opt.gatherRelError; g.maxExtra = opt.gatherMaxExtra;
+    g.reflectance = opt.reflectance; g.reflectSamples = opt.reflectSamples; g.reflectBounces = opt.reflectBounces;
+    g.sided = opt.reflectSided; g.mapped = opt.reflectMapped != 0; g.mirrored = opt.mirrorMapped != 0;
+    g.batch = opt.gatherBatch;
+    return g;
+}
+
+const char* RayTracer::GatherRefusal(const GatherOptions& g, int checks, bool plan)
+{
+    if (checks & kBatchRefusals) {
+        if (g.batch < 0 || g.batch > UVRT_GATHER_BATCH_MAX) return "gatherBatch must be in [0, 64]";
+        if (g.sided != 0 && g.batch >= 2) return "reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)";
+    }
+    if (!(checks & kLaunchRefusals)) return nullptr;
+    if (g.reflectBounces < 0 || g.reflectBounces > 16) return "reflectBounces must be in [0, 16]";
+    if (g.sided != 0) {
+        if (g.sided != 1) return "reflectSided must be 0 or 1";
+        if (g.reflectance == 0.0f) return "reflectSided needs reflectance > 0 (without a bounce there are no faces to resolve)";
+        if (g.reflectBounces < 1) return "reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)";
+    }
+    if (g.mapped && g.sided == 0)
+        return plan ? "reflectMapped needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)"
+                    : "reflectMap needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)";
+    if (g.relError != 0.0) {
+        if (g.samples < 2)
+            return plan ? "gatherRelError needs a plan from the direct gather with gatherSamples >= 2"
+                        : "gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)";
+        if (!(g.relError > 0.0) || !std::isfinite(g.relError)) return "gatherRelError must be finite and >= 0";
+    }
+    if (g.reflectance != 0.0f && g.samples < 1)
+        return plan ? "reflectance needs a plan from the direct gather (gatherSamples > 0)"
+                    : "reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)";
+    if (!(g.reflectance >= 0.0f) || !(g.reflectance <= 1.0f)) return "reflectance must be in [0, 1]";
+    if (g.mirrored && g.samples < 1)
+        return plan ? "mirrorMapped needs a plan from the direct gather (gatherSamples > 0)"
+                    : "mirrorMap needs gatherSamples > 0 (the mirror gather adds to the direct gather's plane)";
+    return nullptr;
 }
 
 // ------------------------------------------------------------ the reflectance map (raytracer.h reflectMap)
@@ -400,8 +478,7 @@ void RayTracer::ComputeSegments()
     std::vector<RouteLaunch> sweeps;
     for (const RouteLaunch& l : Launches())
         if (l.kind == UVRT_LAUNCH_SWEEP) sweeps.push_back(l);
-    RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, gatherSamples, gatherSampling, false, gatherRelError, gatherMaxExtra,
-                reflectance, reflectSamples, reflectBounces, gatherBatch, reflectSided, HasReflectanceMap(), HasMirrors());
+    RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, OwnGather(), false);
 }
 
 // the uvrt_gather_params of a gather launch with seed `seed`
@@ -418,112 +495,79 @@ static uvrt_gather_params gather_params(const RouteLaunch& l, float lightLength,
     return g;
 }
 
-void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
-                            double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided,
-                            bool mapped, bool mirrored)
+void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, const GatherOptions& g, bool capture)
 {
-    if (batch < 0 || batch > UVRT_GATHER_BATCH_MAX) fatal("gatherBatch must be in [0, 64]");
-    if (sided != 0 && batch >= 2) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
+    if (const char* why = GatherRefusal(g, kBatchRefusals, false)) fatal(why);
     // (a refine that RunLaunch is about to refuse is left to it: its batch would be refused first, with another message)
-    const bool refineOk = relError == 0.0 || (samples >= 2 && relError > 0.0 && std::isfinite(relError));
-    if (batch < 2 || samples <= 0 || !refineOk) {
-        for (const RouteLaunch& l : list)
-            RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS, reflectK, -1,
-                      sided, mapped, mirrored);
+    const bool refineOk = g.relError == 0.0 || (g.samples >= 2 && g.relError > 0.0 && std::isfinite(g.relError));
+    if (g.batch < 2 || g.samples <= 0 || !refineOk) {
+        for (const RouteLaunch& l : list) RunLaunch(l, photons, triangleCount, g, capture ? l.column : -1, -1);
         return;
     }
-    // groups of up to `batch` consecutive launches: one shadow-ray pass each (include/uvrt.h uvrt_gather_direct_batch), then
+    // groups of up to g.batch consecutive launches: one shadow-ray pass each (include/uvrt.h uvrt_gather_direct_batch), then
     // every launch as RunLaunch runs it, with uvrt_gather_batch_select where uvrt_gather_direct stood
-    const long long want = std::min<long long>((long long)std::min<size_t>((size_t)batch, list.size()) * triangleCount * samples, 1ll << 23);
+    const size_t batch = (size_t)g.batch;
+    const long long want = std::min<long long>((long long)std::min(batch, list.size()) * triangleCount * g.samples, 1ll << 23);
     if (want > rayCapacity) {                                // results never depend on the capacity: the cap is a memory choice
         check(uvrt_resize_rays(ctx, want), "resize_rays");
         rayCapacity = want;
     }
     std::vector<uvrt_gather_params> params;
-    for (size_t first = 0; first < list.size(); first += (size_t)batch) {
-        const size_t cnt = std::min((size_t)batch, list.size() - first);
+    for (size_t first = 0; first < list.size(); first += batch) {
+        const size_t cnt = std::min(batch, list.size() - first);
         params.clear();
         for (size_t k = 0; k < cnt; ++k)                     // the seeds the launches take from gatherLaunches below
-            params.push_back(gather_params(list[first + k], lightLength, samples, gatherLaunches + (unsigned)k, photons));
-        check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
-        int32_t variance0 = 0;
-        if (relError != 0.0) {                               // the refine reads the variance plane (RunLaunch)
-            check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
-            check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
+            params.push_back(gather_params(list[first + k], lightLength, g.samples, gatherLaunches + (unsigned)k, photons));
+        check(uvrt_set_gather_sampling(ctx, g.sampling), "set_gather_sampling");
+        {
+            ScopedState variance(ctx, kVariancePlane, g.relError != 0.0);   // the refine reads the variance plane (RunLaunch)
+            check(uvrt_gather_direct_batch(ctx, params.data(), (int32_t)cnt, 0, triangleCount), "gather_direct_batch");
         }
-        check(uvrt_gather_direct_batch(ctx, params.data(), (int32_t)cnt, 0, triangleCount), "gather_direct_batch");
-        if (relError != 0.0) check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
         for (size_t k = 0; k < cnt; ++k) {
             const RouteLaunch& l = list[first + k];
-            RunLaunch(l, photons, triangleCount, samples, sampling, capture ? l.column : -1, relError, maxExtra, reflect, reflectS,
-                      reflectK, (int)k, 0, mapped, mirrored);
+            RunLaunch(l, photons, triangleCount, g, capture ? l.column : -1, (int)k);
         }
     }
 }
 
-void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                          double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot, int sided,
-                          bool mapped, bool mirrored)
+void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, const GatherOptions& opt, int captureColumn, int batchSlot)
 {
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
-    if (reflectK < 0 || reflectK > 16) fatal("reflectBounces must be in [0, 16]");
-    if (sided != 0) {
-        if (sided != 1) fatal("reflectSided must be 0 or 1");
-        if (reflect == 0.0f) fatal("reflectSided needs reflectance > 0 (without a bounce there are no faces to resolve)");
-        if (reflectK < 1) fatal("reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)");
-        if (batchSlot >= 0) fatal("reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
-    }
-    if (mapped && sided == 0) fatal("reflectMap needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)");
+    if (const char* why = GatherRefusal(opt, kLaunchRefusals, false)) fatal(why);
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
-    if (relError != 0.0 && samples < 2) fatal("gatherRelError > 0 needs gatherSamples >= 2 (the refine reads the variance plane)");
-    if (reflect != 0.0f && samples < 1) fatal("reflectance > 0 needs gatherSamples > 0 (the bounce gathers over the direct gather's plane)");
-    if (!(reflect >= 0.0f) || !(reflect <= 1.0f)) fatal("reflectance must be in [0, 1]");
-    if (mirrored && samples < 1) fatal("mirrorMap needs gatherSamples > 0 (the mirror gather adds to the direct gather's plane)");
+    const int samples = opt.samples, sided = opt.sided, reflectS = opt.reflectSamples, reflectK = opt.reflectBounces;
+    const float reflect = opt.reflectance;
     if (samples > 0) {
         // the direct gather: expected[t] for every triangle, then accumulate.cl on that plane (raytracer.h gatherSamples)
         if (shardWorld > 1) fatal("gatherSamples > 0 is not supported with launch sharding (shardWorld > 1)");
         const uvrt_gather_params g = gather_params(l, lightLength, samples, gatherLaunches++, photons);
-        check(uvrt_set_gather_sampling(ctx, sampling), "set_gather_sampling");
-        // the launch's planes: traced here, or taken from the batch that RunLaunches has traced (batchSlot >= 0)
-        // (reflectSided: with the faces state on around it, as the variance state is for the refine; the context's is put back)
-        auto gather = [&] {
-            if (batchSlot >= 0) { check(uvrt_gather_batch_select(ctx, batchSlot), "gather_batch_select"); return; }
-            int32_t faces0 = 0;
-            if (sided) {
-                check(uvrt_get_gather_faces(ctx, &faces0), "get_gather_faces");
-                check(uvrt_set_gather_faces(ctx, 1), "set_gather_faces");
+        check(uvrt_set_gather_sampling(ctx, opt.sampling), "set_gather_sampling");
+        {
+            // the adaptive gather (raytracer.h gatherRelError): the variance plane on around the launch's planes, the refine after
+            ScopedState variance(ctx, kVariancePlane, opt.relError != 0.0);
+            // the launch's planes: taken from the batch that RunLaunches has traced (batchSlot >= 0), or traced here
+            // (reflectSided: with the faces state on around it; the context's is put back)
+            if (batchSlot >= 0) {
+                check(uvrt_gather_batch_select(ctx, batchSlot), "gather_batch_select");
+            } else {
+                ScopedState faces(ctx, kFacePlanes, sided != 0);
+                check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
             }
-            check(uvrt_gather_direct(ctx, &g, 0, triangleCount), "gather_direct");
-            if (sided) check(uvrt_set_gather_faces(ctx, faces0), "set_gather_faces");
-        };
-        if (relError != 0.0) {
-            // the adaptive gather (raytracer.h gatherRelError): the variance plane on for this launch, then the refine
-            if (!(relError > 0.0) || !std::isfinite(relError)) fatal("gatherRelError must be finite and >= 0");
-            int32_t variance0 = 0;
-            check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
-            check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
-            gather();
-            check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
+        }
+        if (opt.relError != 0.0) {
             uvrt_refine_params rp;
             memset(&rp, 0, sizeof rp);
-            rp.rel_error = relError;
-            rp.max_extra = maxExtra;
+            rp.rel_error = opt.relError;
+            rp.max_extra = opt.maxExtra;
             rp.seed = ~g.seed;
             check(uvrt_gather_refine(ctx, &rp, 0, triangleCount, nullptr), "gather_refine");
-        } else {
-            gather();
         }
-        if (mirrored) {
+        if (opt.mirrored) {
             // the specular panels (raytracer.h mirrorMap): the lamp's light by way of every panel, added to the finished direct
             // plane -- and, under reflectSided, to the face planes, so that the bounces below see it as a source
             UploadMirrors(triangleCount);
-            int32_t faces0 = 0;
-            if (sided) {
-                check(uvrt_get_gather_faces(ctx, &faces0), "get_gather_faces");
-                check(uvrt_set_gather_faces(ctx, 1), "set_gather_faces");
-            }
+            ScopedState faces(ctx, kFacePlanes, sided != 0);
             check(uvrt_gather_mirror(ctx, &g, 1, 0, triangleCount), "gather_mirror");
-            if (sided) check(uvrt_set_gather_faces(ctx, faces0), "set_gather_faces");
         }
         if (reflect > 0.0f && reflectK > 0) {
             // reflectK bounces over recorded hit links (raytracer.h reflectBounces): traced once per scene and reflectS
@@ -543,7 +587,7 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
             kp.reflectance = reflect;
             kp.bounces = reflectK;
             kp.add = 1;
-            if (mapped) {
+            if (opt.mapped) {
                 // the face-resolved bounces with a reflectance per face (raytracer.h reflectMap): `reflect` is the map's base only
                 UploadReflectanceMap(triangleCount, reflect);
                 uvrt_mapped_params mp;
@@ -588,16 +632,12 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
 void RayTracer::ComputeSegmentDosageMap(LightPos a, LightPos b, int photonsPerLight, int triangleCount)
 {
     if (!(driveSpeed > 0.0f)) fatal("ComputeSegmentDosageMap: driveSpeed must be > 0");
-    RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided,
-              HasReflectanceMap(), HasMirrors());
+    RunLaunch(RouteLaunches({a, b}, mesh->floorHeight + lightHeight, driveSpeed).back(), photonsPerLight, triangleCount, OwnGather(), -1, -1);
 }
 
 void RayTracer::ComputeSingleLightDosageMap(LightPos lightPos, int photonsPerLight, int triangleCount)
 {
-    RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, gatherSamples,
-              gatherSampling, -1, gatherRelError, gatherMaxExtra, reflectance, reflectSamples, reflectBounces, -1, reflectSided,
-              HasReflectanceMap(), HasMirrors());
+    RunLaunch(RouteLaunches({lightPos}, mesh->floorHeight + lightHeight, 0.0f)[0], photonsPerLight, triangleCount, OwnGather(), -1, -1);
 }
 
 void RayTracer::SetRayRange(int rank, int world)
@@ -713,35 +753,25 @@ void RayTracer::PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols
     for (RayTracer* rt : group) rt->planCapture = false;
 }
 
-// capture from the direct gather: the launches of ComputeDosageMap with `samples`, launch by launch, every plane into its column
+// capture from the direct gather: the launches of ComputeDosageMap with `g`, every plane into its column
 // confidence z > 0: with the variance plane on and the exposure matrix's variance beside it, lowered to X - z sqrt(V) at the end
-void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                                  int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided, bool mapped, bool mirrored)
+void RayTracer::PlanCaptureGather(const std::vector<RouteLaunch>& list, const GatherOptions& g, double confidence)
 {
     if (shardWorld > 1 || reduceOverComm) fatal("PlanDurations: a plan from the direct gather does not shard (shardWorld > 1, reduceOverComm)");
     const bool bound = confidence > 0.0;
-    int32_t variance0 = 0;
-    if (bound) {
-        check(uvrt_get_gather_variance(ctx, &variance0), "get_gather_variance");
-        check(uvrt_set_gather_variance(ctx, 1), "set_gather_variance");
-        check(uvrt_plan_begin_expected_variance(ctx, (int)list.size()), "plan_begin_expected_variance");
-    } else {
-        check(uvrt_plan_begin_expected(ctx, (int)list.size()), "plan_begin_expected");
-    }
+    ScopedState variance(ctx, kVariancePlane, bound);        // put back after the lowering, when the function ends
+    if (bound) check(uvrt_plan_begin_expected_variance(ctx, (int)list.size()), "plan_begin_expected_variance");
+    else check(uvrt_plan_begin_expected(ctx, (int)list.size()), "plan_begin_expected");
     ClearBuffers(true);                                      // ResetDosageMap without the route save
     currIterations = 0;
     launchIndex = 0;
     gatherLaunches = 0;
     for (int it = 0; it < maxIterations; ++it) {
-        RunLaunches(list, photonsPerLight, mesh->triangleCount, samples, sampling, true, relError, maxExtra, reflect, reflectS, reflectK, batch, sided,
-                    mapped, mirrored);
+        RunLaunches(list, photonsPerLight, mesh->triangleCount, g, true);
         Shade();
         ++currIterations;
     }
-    if (bound) {
-        check(uvrt_plan_lower_confidence(ctx, confidence), "plan_lower_confidence");
-        check(uvrt_set_gather_variance(ctx, variance0), "set_gather_variance");
-    }
+    if (bound) check(uvrt_plan_lower_confidence(ctx, confidence), "plan_lower_confidence");
 }
 
 // every instance solves on its own; the durations must agree, and a sweep's column must come back as it went in
@@ -797,47 +827,27 @@ uvrt_plan_report RayTracer::PlanDurations(const std::vector<RayTracer*>& group, 
     if ((int)list.size() > L && L > 128) fatal("PlanDurations: a driving plan takes at most 128 positions (2L - 1 <= 256 columns)");
     if ((long long)r0->maxIterations * (long long)r0->photonsPerLight > 0xFFFFFFFFll)
         fatal("PlanDurations: iterations x photonsPerLight overflow the uint32 exposure counts");
+    // what only a plan can get wrong, then what a plan shares with every launch (GatherRefusal)
     if (opt.gatherConfidence != 0.0) {
         if (!(opt.gatherConfidence > 0.0) || !std::isfinite(opt.gatherConfidence)) fatal("PlanDurations: gatherConfidence must be finite and >= 0");
         if (opt.gatherSamples < 2) fatal("PlanDurations: gatherConfidence needs a plan from the direct gather with gatherSamples >= 2");
-    }
-    if (opt.gatherRelError != 0.0) {
-        if (!(opt.gatherRelError > 0.0) || !std::isfinite(opt.gatherRelError)) fatal("PlanDurations: gatherRelError must be finite and >= 0");
-        if (opt.gatherSamples < 2) fatal("PlanDurations: gatherRelError needs a plan from the direct gather with gatherSamples >= 2");
-    }
-    if (opt.reflectBounces < 0 || opt.reflectBounces > 16) fatal("PlanDurations: reflectBounces must be in [0, 16]");
-    if (opt.gatherBatch < 0 || opt.gatherBatch > UVRT_GATHER_BATCH_MAX) fatal("PlanDurations: gatherBatch must be in [0, 64]");
-    if (opt.reflectSided != 0) {
-        if (opt.reflectSided != 1) fatal("PlanDurations: reflectSided must be 0 or 1");
-        if (opt.reflectance == 0.0f) fatal("PlanDurations: reflectSided needs reflectance > 0 (without a bounce there are no faces to resolve)");
-        if (opt.reflectBounces < 1) fatal("PlanDurations: reflectSided needs reflectBounces >= 1 (the traced single bounce has no face-resolved form)");
-        if (opt.gatherBatch >= 2) fatal("PlanDurations: reflectSided is not supported with gatherBatch >= 2 (a gather batch keeps no face planes)");
-    }
-    if (opt.reflectMapped != 0) {
-        if (opt.reflectMapped != 1) fatal("PlanDurations: reflectMapped must be 0 or 1");
-        if (opt.reflectSided != 1) fatal("PlanDurations: reflectMapped needs reflectSided = 1 (only the face-resolved bounces know which face a reflectance belongs to)");
-        if (!r0->HasReflectanceMap()) fatal("PlanDurations: reflectMapped needs a reflectance map (RayTracer::reflectMap or SetReflectanceMap)");
-    }
-    if (opt.mirrorMapped != 0) {
-        if (opt.mirrorMapped != 1) fatal("PlanDurations: mirrorMapped must be 0 or 1");
-        if (opt.gatherSamples < 1) fatal("PlanDurations: mirrorMapped needs a plan from the direct gather (gatherSamples > 0)");
-        if (opt.gatherConfidence != 0.0)
+        if (opt.mirrorMapped != 0)
             fatal("PlanDurations: mirrorMapped is not supported with gatherConfidence (the variance plane knows nothing of the specular part)");
-        if (!r0->HasMirrors()) fatal("PlanDurations: mirrorMapped needs specular panels (RayTracer::mirrorMap or SetMirrors)");
-    }
-    if (opt.reflectance != 0.0f) {
-        if (!(opt.reflectance >= 0.0f) || !(opt.reflectance <= 1.0f)) fatal("PlanDurations: reflectance must be in [0, 1]");
-        if (opt.gatherSamples < 1) fatal("PlanDurations: reflectance needs a plan from the direct gather (gatherSamples > 0)");
-        if (opt.gatherConfidence != 0.0)
+        if (opt.reflectance != 0.0f)
             fatal("PlanDurations: reflectance is not supported with gatherConfidence (the variance plane knows nothing of the indirect part)");
     }
+    if (opt.reflectMapped != 0 && opt.reflectMapped != 1) fatal("PlanDurations: reflectMapped must be 0 or 1");
+    if (opt.mirrorMapped != 0 && opt.mirrorMapped != 1) fatal("PlanDurations: mirrorMapped must be 0 or 1");
+    const GatherOptions gather = PlanGather(opt);
+    if (const char* why = GatherRefusal(gather, kBatchRefusals | kLaunchRefusals, true)) fatal((std::string("PlanDurations: ") + why).c_str());
+    if (opt.reflectMapped != 0 && !r0->HasReflectanceMap())
+        fatal("PlanDurations: reflectMapped needs a reflectance map (RayTracer::reflectMap or SetReflectanceMap)");
+    if (opt.mirrorMapped != 0 && !r0->HasMirrors()) fatal("PlanDurations: mirrorMapped needs specular panels (RayTracer::mirrorMap or SetMirrors)");
     uint32_t seed0 = 0;
     check(uvrt_get_seed(r0->ctx, &seed0), "get_seed");
     if (opt.gatherSamples > 0) {
         if (group.size() != 1) fatal("PlanDurations: a plan from the direct gather runs on one context (no group)");
-        r0->PlanCaptureGather(list, opt.gatherSamples, opt.gatherSampling, opt.gatherConfidence, opt.gatherRelError, opt.gatherMaxExtra,
-                              opt.reflectance, opt.reflectSamples, opt.reflectBounces, opt.gatherBatch, opt.reflectSided,
-                              opt.reflectMapped != 0, opt.mirrorMapped != 0);
+        r0->PlanCaptureGather(list, gather, opt.gatherConfidence);
     } else {
         PlanCaptureCounts(group, (int)list.size());
     }

@@ -316,23 +316,34 @@ public:
     unsigned gatherLaunches = 0;                  // gather launches since ResetDosageMap: the next launch's seed
 private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
-    // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with samples > 0 the direct
+    // How a launch gathers: the knobs above as one value, so that a launch of ComputeDosageMap and a launch of a plan go
+    // through the same code.  samples = 0: photons, and nothing else is read.  relError / maxExtra: the refine; reflectance,
+    // reflectSamples, reflectBounces, sided, mapped: the bounces; mirrored: the mirror gather; batch: the gather batch.
+    // Made by OwnGather (the members; mapped and mirrored: there is a map, there are panels) or PlanGather (a plan's own).
+    struct GatherOptions {
+        int samples = 0, sampling = 0;
+        double relError = 0.0;
+        int maxExtra = 64;
+        float reflectance = 0.0f;
+        int reflectSamples = 16, reflectBounces = 0, sided = 0;
+        bool mapped = false, mirrored = false;
+        int batch = 0;
+    };
+    GatherOptions OwnGather() const;
+    static GatherOptions PlanGather(const PlanOptions& opt);
+    // Why a launch with these options is refused, or null: every condition that ComputeDosageMap's launches and
+    // PlanDurations both check, written once.  plan: PlanDurations' wording (it prints it behind "PlanDurations: ").
+    // checks: kBatchRefusals are those of a whole list (RunLaunches, on entry), kLaunchRefusals those of every launch.
+    enum { kBatchRefusals = 1, kLaunchRefusals = 2 };
+    static const char* GatherRefusal(const GatherOptions& g, int checks, bool plan);
+    // One launch, as ComputeDosageMap runs it: generate[_sweep] -> extend -> accumulate, or with g.samples > 0 the direct
     // gather -> accumulate_expected, its plane first captured into column captureColumn of a plan when that is >= 0.
     // A stop counts in launchIndex (the shard test) and photonMapSize, a sweep in neither.
-    // `sampling`: the gather sampling mode of a launch with samples > 0; relError > 0: the launch is refined (gatherRelError);
-    // reflect > 0: one diffuse bounce with reflectS samples is added to its plane (reflectance), or with reflectK > 0 that many
-    // bounces over recorded hit links (reflectBounces), face-resolved with `sided` (reflectSided), with the reflectance map in
-    // place of `reflect` with `mapped` (reflectMap).
-    // `mirrored`: the mirror gather over the specular panels follows the gather and its refine (mirrorMap).
     // batchSlot >= 0: the launch's planes are those of launch batchSlot of the context's gather batch (RunLaunches).
-    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, int samples, int sampling, int captureColumn,
-                   double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batchSlot = -1, int sided = 0,
-                   bool mapped = false, bool mirrored = false);
+    void RunLaunch(const RouteLaunch& launch, int photons, int triangleCount, const GatherOptions& g, int captureColumn, int batchSlot);
     // A list of launches through RunLaunch, in order (capture: every plane into its launch's column of a plan); with
-    // samples > 0 and batch >= 2 in groups of up to `batch` behind one uvrt_gather_direct_batch each (gatherBatch).
-    void RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, int samples, int sampling, bool capture,
-                     double relError, int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0,
-                     bool mapped = false, bool mirrored = false);
+    // g.samples > 0 and g.batch >= 2 in groups of up to g.batch behind one uvrt_gather_direct_batch each (gatherBatch).
+    void RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, const GatherOptions& g, bool capture);
     // the active map (the file's, read with `base` as every entry's start, or the caller's) into the context's planes when the
     // context has none or the map is not the one uploaded last (RunLaunch)
     void UploadReflectanceMap(int triangleCount, float base);
@@ -355,9 +366,7 @@ private:
     static void TraceBatched(const std::vector<RayTracer*>& group, int iterations);
     // the steps of PlanDurations: capture (photon counts or the direct gather), then bounds and solve
     static void PlanCaptureCounts(const std::vector<RayTracer*>& group, int cols);
-    void PlanCaptureGather(const std::vector<RouteLaunch>& list, int samples, int sampling, double confidence, double relError,
-                           int maxExtra, float reflect, int reflectS, int reflectK, int batch, int sided = 0, bool mapped = false,
-                           bool mirrored = false);
+    void PlanCaptureGather(const std::vector<RouteLaunch>& list, const GatherOptions& g, double confidence);
     static std::vector<float> PlanSolve(const std::vector<RayTracer*>& group, const PlanOptions& opt, const std::vector<RouteLaunch>& list,
                                         uvrt_plan_report* rep, uvrt_plan_bounds_report* brep);
 public:

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GLB, GOLDEN, ROOT
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_gather_direct_batch", "uvrt_gather_batch_select", "uvrt_gather_batch_info", "uvrt_read_gather_batch")
 
@@ -76,9 +77,8 @@ def test_cli_refuses_a_batch_it_cannot_run(pkg):
 
 def test_the_binding_carries_gather_batch(pkg):
     from uvrt_amd import host
-    assert [k for k, _, _ in host.SYMBOLS].count("uvrt_host_rt_plan_gather_batch") == 1
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather_batch")
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather_reflect_linked")           # the existing entry points stay
+    check_plan_option(host, "gather_batch", C.c_int, 0)
+    check_plan_option(host, "reflect_bounces", C.c_int, 0)                          # the options from before stay
     assert "gatherBatch" in host._FIELDS and "gatherBatch" in host._INT_FIELDS
     rt = host.RayTracer(init=False)
     try:

@@ -16,6 +16,7 @@ import pytest
 import gather_indirect_restate as gi
 import gather_restate as gr
 from conftest import GLB, GOLDEN, ROOT
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_closest_hits", "uvrt_indirect_source_from_expected", "uvrt_read_indirect_source", "uvrt_write_indirect_source",
        "uvrt_gather_indirect", "uvrt_gather_indirect_rays")
@@ -44,8 +45,9 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
               "gather_indirect_rays"):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
-    assert [k for k, _, _ in host.SYMBOLS].count("uvrt_host_rt_plan_gather_reflect") == 1
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather_reflect") and hasattr(host.RayTracer, "PlanDurationsReflect")
+    check_plan_option(host, "reflectance", C.c_float, 0.0)
+    check_plan_option(host, "reflect_samples", C.c_int, 16)
+    assert hasattr(host.RayTracer, "PlanDurationsReflect")
 
 
 def test_struct_layout_matches_the_c_compiler(pkg, tmp_path):

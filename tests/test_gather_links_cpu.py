@@ -15,6 +15,7 @@ import gather_indirect_restate as gi
 import gather_links_restate as gl
 import gather_restate as gr
 from conftest import GLB, GOLDEN, ROOT
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_indirect_links_build", "uvrt_indirect_links_info", "uvrt_read_indirect_links", "uvrt_gather_indirect_linked")
 f32 = np.float32
@@ -35,9 +36,8 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
     for m in ("indirect_links_build", "indirect_links_info", "read_indirect_links", "gather_indirect_linked"):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
-    assert [k for k, _, _ in host.SYMBOLS].count("uvrt_host_rt_plan_gather_reflect_linked") == 1
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather_reflect_linked")
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather_reflect")         # the existing entry point stays
+    check_plan_option(host, "reflect_bounces", C.c_int, 0)
+    check_plan_option(host, "reflectance", C.c_float, 0.0)                 # the option from before stays
     assert "reflectBounces" in host._FIELDS and "reflectBounces" in host._INT_FIELDS
 
 

@@ -21,6 +21,7 @@ import gather_restate as gr
 import gather_stratified_restate as gs
 import gather_variance_restate as gv
 from conftest import GLB, GOLDEN, ROOT
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_gather_refine", "uvrt_read_gather_extra", "uvrt_refine_counts")
 f32 = np.float32
@@ -41,10 +42,10 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
     hosts = {n: a for n, _, a in host.SYMBOLS}
-    for n in ("uvrt_host_rt_plan_gather_refine", "uvrt_host_rt_set_gather_refine"):
-        assert [k for k, _, _ in host.SYMBOLS].count(n) == 1 and hasattr(host.lib(), n)
-    assert len(hosts["uvrt_host_rt_plan_gather_refine"]) == len(hosts["uvrt_host_rt_plan_gather_confidence"]) + 2
-    assert hosts["uvrt_host_rt_plan_gather_refine"][10] is C.c_double and hosts["uvrt_host_rt_plan_gather_refine"][11] is C.c_int
+    n = "uvrt_host_rt_set_gather_refine"
+    assert [k for k, _, _ in host.SYMBOLS].count(n) == 1 and hasattr(host.lib(), n)
+    check_plan_option(host, "gather_rel_error", C.c_double, 0.0)
+    check_plan_option(host, "gather_max_extra", C.c_int, 64)
     assert hosts["uvrt_host_rt_set_gather_refine"][1:] == [C.c_double, C.c_int]
     assert hasattr(host.RayTracer, "set_gather_refine")
 

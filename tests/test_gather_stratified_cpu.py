@@ -12,6 +12,7 @@ import pytest
 import gather_restate as gr
 import gather_stratified_restate as gs
 from conftest import GLB, GOLDEN
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_set_gather_sampling", "uvrt_get_gather_sampling")
 f32 = np.float32
@@ -29,9 +30,7 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
     assert "gatherSampling" in host._FIELDS and "gatherSampling" in host._INT_FIELDS
-    assert [n for n, _, _ in host.SYMBOLS].count("uvrt_host_rt_plan_gather_sampling") == 1
-    by_name = {n: a for n, _, a in host.SYMBOLS}
-    assert len(by_name["uvrt_host_rt_plan_gather_sampling"]) == len(by_name["uvrt_host_rt_plan_gather"]) + 1
+    check_plan_option(host, "gather_sampling", C.c_int, 0)
 
 
 def test_a_null_context_is_refused_without_a_gpu(pkg):

@@ -25,6 +25,7 @@ import gather_restate as gr
 import gather_stratified_restate as gs
 import gather_variance_restate as gv
 from conftest import GLB, GOLDEN
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_set_gather_variance", "uvrt_get_gather_variance", "uvrt_read_variance", "uvrt_write_variance",
        "uvrt_plan_begin_expected_variance", "uvrt_plan_read_exposure_variance", "uvrt_plan_lower_confidence")
@@ -45,11 +46,7 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
               "plan_read_exposure_variance", "plan_lower_confidence"):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
-    assert [n for n, _, _ in host.SYMBOLS].count("uvrt_host_rt_plan_gather_confidence") == 1
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather_confidence")
-    hosts = {n: a for n, _, a in host.SYMBOLS}
-    assert len(hosts["uvrt_host_rt_plan_gather_confidence"]) == len(hosts["uvrt_host_rt_plan_gather_sampling"]) + 1
-    assert hosts["uvrt_host_rt_plan_gather_confidence"][9] is C.c_double
+    check_plan_option(host, "gather_confidence", C.c_double, 0.0)
 
 
 def test_null_arguments_are_refused_without_a_gpu(pkg):

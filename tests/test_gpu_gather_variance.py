@@ -421,11 +421,13 @@ SE = 16
 
 
 def _plan_through_the_new_entry(rt, min_dose, samples, sampling, z):
-    """uvrt_host_rt_plan_gather_confidence itself (host.py takes the earlier entry points at z = 0)"""
+    """uvrt_host_rt_plan itself, over a PlanOptions filled by hand with gather_confidence = z"""
     from uvrt_amd import host
     rep, seed = host.capi.PlanReport(), C.c_uint()
-    rt._L.uvrt_host_rt_plan_gather_confidence(rt._h, float(min_dose), 16, 1e-6, 1e-3, 200, None, int(samples), int(sampling),
-                                              float(z), C.byref(rep), C.byref(seed))
+    opt = host.PlanOptions()
+    opt.min_dose, opt.min_photons, opt.margin, opt.rel_gap, opt.max_iterations, opt.mask = float(min_dose), 16, 1e-6, 1e-3, 200, None
+    opt.gather_samples, opt.gather_sampling, opt.gather_confidence = int(samples), int(sampling), float(z)
+    rt._L.uvrt_host_rt_plan(rt._h, C.byref(opt), C.byref(rep), C.byref(seed))
     return host._plan_result(rt, rep, seed)
 
 

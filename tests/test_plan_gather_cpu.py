@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 
 from conftest import GLB, GOLDEN
+from plan_options_pin import check_plan_option
 
 NEW = ("uvrt_plan_begin_expected", "uvrt_plan_capture_expected", "uvrt_plan_read_exposure_expected", "uvrt_write_expected")
 
@@ -24,8 +25,7 @@ def test_symbols_are_bound_and_resolve_in_both_libraries(pkg):
     for m in ("plan_begin_expected", "plan_capture_expected", "plan_read_exposure_expected", "write_expected"):
         assert hasattr(pkg.capi.Ctx, m)
     from uvrt_amd import host
-    assert [n for n, _, _ in host.SYMBOLS].count("uvrt_host_rt_plan_gather") == 1
-    assert hasattr(host.lib(), "uvrt_host_rt_plan_gather")
+    check_plan_option(host, "gather_samples", C.c_int, 0)
 
 
 def test_a_null_context_is_refused_without_a_gpu(pkg):
@@ -61,7 +61,28 @@ def test_plan_durations_accepts_gather_samples(pkg):
     from uvrt_amd import host
     sig = inspect.signature(host.RayTracer.PlanDurations)
     assert sig.parameters["gather_samples"].default == 0
-    # the entry points from before keep their signatures
+    # the two entry points take the options as one struct; the arguments from before the gather are its first fields
     by_name = {n: a for n, _, a in host.SYMBOLS}
-    assert len(by_name["uvrt_host_rt_plan"]) == 9 and len(by_name["uvrt_host_rt_plan_group"]) == 10
-    assert len(by_name["uvrt_host_rt_plan_gather"]) == 10
+    assert len(by_name["uvrt_host_rt_plan"]) == 4 and len(by_name["uvrt_host_rt_plan_group"]) == 5
+    for name, ctype, default in (("min_dose", C.c_float, -1.0), ("min_photons", C.c_int, 16), ("margin", C.c_double, 1e-6),
+                                 ("rel_gap", C.c_double, 1e-3), ("max_iterations", C.c_int, 200), ("mask", C.c_void_p, None),
+                                 ("gather_samples", C.c_int, 0)):
+        check_plan_option(host, name, ctype, default)
+
+
+def test_plan_options_mirror_the_library_struct(pkg):
+    """host.PlanOptions against uvrt_host_plan_options: every offset and the size as the C++ compiler laid them out, and the
+    defaults of RayTracer::PlanOptions{} written over a struct that held something else"""
+    from uvrt_amd import host
+    names = [f for f, _ in host.PlanOptions._fields_]
+    want = [getattr(host.PlanOptions, f).offset for f in names] + [C.sizeof(host.PlanOptions)]
+    got = (C.c_int * 64)()
+    n = host.lib().uvrt_host_plan_options_layout(got, 64)
+    assert n == len(want) and list(got[:n]) == want
+    o = host.PlanOptions()
+    C.memset(C.byref(o), 0x5A, C.sizeof(o))
+    host.lib().uvrt_host_plan_options_init(C.byref(o))
+    defaults = dict(min_dose=-1.0, min_photons=16, margin=1e-6, rel_gap=1e-3, max_iterations=200, gather_max_extra=64,
+                    reflect_samples=16)
+    for f in names:
+        assert getattr(o, f) == (None if f == "mask" else defaults.get(f, 0)), f
