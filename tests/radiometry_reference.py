@@ -9,6 +9,7 @@ The claims that are checked against it:
   photons  tempPhotonMap[t] ~   Binomial(N, that same share)
   bounce   expected[t]      ->  rho A_t sum_f sum_h F^f_{t->h} e_h        (f: the face of t a sample leaves, F: a form factor)
   mirror   expected[t] / N  ->  rho * (solid angle, from the lamp's mirror image, of the part of t seen through the panel) / 4 pi
+  series   expected[t]      ->  E[A_t sum_{b <= K} (M^b e0)_t] over sets of links: M = rho n / S' with one multinomial n per leaving face
 and the spread of one sample of each, which gives the tests their tolerances.
 
 Conventions: a triangle is a (3, 3) array of vertices, a polygon a (k, 3) array of coplanar vertices in order, a lamp is
@@ -395,6 +396,120 @@ def bounce(tris, radiosity, tables):
         var += 2.0 * area * area * np.maximum(m2 - m1 * m1, 0.0)
         eps += area * np.sum(E[f] * np.abs(r), axis=1)
     return mu, np.sqrt(var), eps
+
+
+# ---------------------------------------------------------------- K bounces over recorded links
+# In a scene on the boundary of one convex body a sample that leaves face f of triangle t lands on triangle h with probability
+# F[f][t][h], on the face arrive[t][h], and misses with what remains.  Each face draws S' samples, so a set of links is one
+# independent multinomial per row r = (f, t), and a linked call is  A_t sum_{b = 1..K} (M^b e0)  summed over the two faces, with
+# M[r, c] = rho[c] n[r, c] / S', n the row's counts, c = (a, h) the emitting face, and e0 the irradiance the source planes hold.
+# The rows and columns are numbered f * T + t.
+def link_model(tables, area, rho, planes):
+    """(P[R, R], rho[R], e0[R], A[R]), R = 2 T: the rows' landing probabilities, the reflectance of every emitting face (`rho` one
+    number or f64[2][T]), the irradiance planes / area (`planes` f64[2][T], photons; 0 where the area is 0) and the rows' areas"""
+    F, _, arrive = tables
+    area = np.asarray(area, dtype=np.float64)
+    T = area.size
+    P = np.zeros((2 * T, 2 * T))
+    cols = arrive * T + np.arange(T)[None, :]
+    for f in (0, 1):
+        P[f * T + np.arange(T)[:, None], cols] = F[f]
+    assert np.all(np.diag(P) == 0.0) and np.all(P >= 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e0 = np.where(area > 0, np.asarray(planes, dtype=np.float64) / area, 0.0).reshape(2 * T)
+    rho = np.broadcast_to(np.asarray(rho, dtype=np.float64), (2, T)).reshape(2 * T)
+    return P, rho.copy(), e0, np.tile(area, 2)
+
+
+def fold_faces(v):
+    """[.., 2 T] -> [.., T]: the two faces of every triangle added"""
+    v = np.asarray(v)
+    T = v.shape[-1] // 2
+    return v[..., :T] + v[..., T:]
+
+
+def series(P, rho, e0, A, K):
+    """mu[K][R]: mu_b = A Mbar^b e0 with Mbar = rho P, the mean of M.  What the calls would give if a path never used a row twice"""
+    m = P * rho[None, :]
+    out, v = [], e0
+    for _ in range(K):
+        v = m @ v
+        out.append(A * v)
+    return np.array(out)
+
+
+def series_exact(P, rho, e0, A, K, Sp):
+    """E[A M^b e0][K][R] for K <= 4, exact: the sum over the paths r0 -> c1 -> .. -> cb.  Step i takes a count of row c_{i-1}; two
+    steps that take counts of the same multinomial have E[n_a n_b] = S'(S' - 1) p_a p_b + delta_ab S' p_a in place of
+    S'^2 p_a p_b.  P's diagonal is 0, so neighbouring steps never share a row and for b <= 4 no row is used three times; rows
+    are independent, so the factors of the pairs multiply.  The whole tensor of paths over the active rows (<= 16) is formed"""
+    assert 1 <= K <= 4
+    R = P.shape[0]
+    act = np.nonzero((P.sum(axis=1) > 0) | (P.sum(axis=0) > 0))[0]
+    n = act.size
+    assert n <= 16, "at most 16 active rows"
+    p = P[np.ix_(act, act)]
+    m = p * rho[act][None, :]
+    eye = np.eye(n, dtype=bool)
+    out = np.zeros((K, R))
+
+    def on(M, i, j, b):                    # the matrix M[x_i, x_j] laid along the axes i and j of the path tensor
+        shape = [1] * (b + 1)
+        shape[i], shape[j] = n, n
+        return M.reshape(shape) if i < j else M.T.reshape(shape)
+
+    for b in range(1, K + 1):
+        shape = [1] * (b + 1)
+        shape[b] = n
+        term = e0[act].reshape(shape)
+        for i in range(1, b + 1):
+            term = term * on(m, i - 1, i, b)
+        for i in range(1, b + 1):
+            for j in range(i + 2, b + 1):                            # steps i and j read the rows x_{i-1} and x_{j-1}
+                pi = on(p, i - 1, i, b)
+                with np.errstate(divide="ignore"):
+                    twice = np.where(on(eye, i, j, b) & (pi > 0), 1.0 / (Sp * pi), 0.0)
+                term = term * np.where(on(eye, i - 1, j - 1, b), (1.0 - 1.0 / Sp) + twice, 1.0)
+        out[b - 1, act] = A[act] * term.reshape(n, -1).sum(axis=1)
+    return out
+
+
+def series_sigma(P, rho, e0, area, Sp, bounces):
+    """sigma_call[T] of sum_{b in bounces} (g_b of a triangle, both faces), to first order in 1 / S': a change dM of row r moves
+    M^b e0 by sum_k Mbar^k dM Mbar^(b-1-k) e0, so with w_r = sum_b sum_{k < b} (Mbar^k)[t, r] Mbar^(b-1-k) e0 and x = rho w_r the
+    row contributes the variance of the mean of S' draws of x_j with probabilities p_rj (a miss is a draw of 0)"""
+    m = P * rho[None, :]
+    R = P.shape[0]
+    top = max(bounces)
+    pw = [np.eye(R)]
+    for _ in range(top):
+        pw.append(pw[-1] @ m)
+    w = np.zeros((R // 2, R, R))
+    for b in bounces:
+        for k in range(b):
+            w += fold_faces(pw[k].T).T[:, :, None] * (pw[b - 1 - k] @ e0)[None, None, :]
+    x = rho[None, None, :] * w
+    m1 = np.einsum("rj,trj->tr", P, x)
+    m2 = np.einsum("rj,trj->tr", P, x * x)
+    return np.asarray(area) * np.sqrt(np.maximum(m2 - m1 * m1, 0.0).sum(axis=1) / Sp)
+
+
+def series_wrong(P, rho, e0, A, K, which):
+    """g[K][R] under a wrong recursion: "no area" forgets the division by the area between bounces (e_b = g_b), "rho once"
+    applies the reflectance to the first bounce only, "receiver's rho" takes, from the second bounce on, the reflectance of
+    the receiving face"""
+    out, v = [], e0
+    for b in range(K):
+        if which == "rho once" and b > 0:
+            v = P @ v
+        elif which == "receiver's rho" and b > 0:
+            v = rho * (P @ v)
+        else:
+            v = (P * rho[None, :]) @ v
+        out.append(A * v)
+        if which == "no area":
+            v = A * v
+    return np.array(out)
 
 
 # ---------------------------------------------------------------- the mirror

@@ -4,7 +4,7 @@ closed forms).  Geometry and expected values only: no kernel, no restatement and
 cube and its wall panel are gather_indirect_restate.cube_tris and gather_mirror_restate.wall_panel, taken as geometry.
 
 Every coordinate is rounded to f32 before the reference sees it, so the reference and the kernels speak of the same triangles
-and the same lamp.  All scenes have at most 12 triangles."""
+and the same lamp.  All scenes have at most 14 triangles."""
 import functools
 import json
 import os
@@ -154,7 +154,8 @@ def direct_reference(name):
     tris = verts(direct_rows(name))
     half = np.array([0.0, 0.5 * length, 0.0])
     order = MOMENTS_ORDER.get(name, 12)
-    out = dict(share=[], eps=[], var=[], mu4=[], mom_err=[], mom_mean=[], no_cosine=[], midpoint=[])
+    moves = tuple(frm) != tuple(to)
+    out = dict(share=[], eps=[], var=[], mu4=[], mom_err=[], mom_mean=[], no_cosine=[], midpoint=[], still=[])
     for t in tris:
         p, e = rr.direct_mean(t, frm, to, length, occ)
         mo = rr.direct_moments(t, frm, to, length, occ, order)
@@ -166,12 +167,15 @@ def direct_reference(name):
         out["mom_mean"].append(N * mo["mean"])
         out["no_cosine"].append(N * rr.direct_moments(t, frm, to, length, occ, order, cosine=False)["mean"])
         out["midpoint"].append(N * rr.direct_mean(t, np.array(frm) + half, np.array(to) + half, 0.0, occ)[0])
+        out["still"].append(N * rr.direct_mean(t, frm, frm, length, occ)[0] if moves else 0.0)
     ref = {k: np.array(v) for k, v in out.items()}
     ref["mu"] = N * ref["share"]
     ref["sigma"] = np.sqrt(ref["var"])
     ref["variants"] = {"no cosine": ref["no_cosine"], "2 pi for 4 pi": 2.0 * ref["mu"]}
     if length != 0:
         ref["variants"]["rod at its midpoint"] = ref["midpoint"]
+    if moves:
+        ref["variants"]["the lamp does not move"] = ref["still"]
     return ref
 
 
@@ -297,6 +301,219 @@ def bounce_reference(call):
     return dict(mu=mu, sigma=sigma, eps=eps, variants={"uniform hemisphere": wrong})
 
 
+# ---------------------------------------------------------------- K bounces over links: the squares and the uneven box
+BOX = (1.0, 2.0, 3.0)
+BOX_CENTRE = (0.5, 1.0, 1.5)
+FAN = 0.25                                  # the fan's point (FAN, 0, 0) on the edge y = 0 of the wall z = 0
+SERIES_K = 4
+SERIES_SCENES = ("squares", "uneven box")
+SERIES_CALLS = ("linked", "sided", "mapped")
+
+
+def box_rows():
+    """The cuboid [0, 1] x [0, 2] x [0, 3]: the 1 x 2 wall z = 0 as a fan of three triangles from (FAN, 0, 0) (0..2), the other
+    five walls of two triangles each, wound both ways (3..12), and a triangle without area along the edge x = y = 0 (13).  The
+    areas run from 0.25 to 3"""
+    X, Y, Z = BOX
+    p = (FAN, 0, 0)
+    fan = [(p, (X, 0, 0), (X, Y, 0)), (p, (0, Y, 0), (X, Y, 0)), (p, (0, Y, 0), (0, 0, 0))]
+    walls = (quad((0, 0, Z), (X, 0, Z), (X, Y, Z), (0, Y, Z)) + quad((0, 0, 0), (0, Y, 0), (0, Y, Z), (0, 0, Z))
+             + quad((X, 0, 0), (X, Y, 0), (X, Y, Z), (X, 0, Z)) + quad((0, 0, 0), (X, 0, 0), (X, 0, Z), (0, 0, Z))
+             + quad((0, Y, 0), (X, Y, 0), (X, Y, Z), (0, Y, Z)))
+    return rows_of(fan + walls + [((0, 0, 0), (0, 0, 1.5), (0, 0, Z))])
+
+
+BOX_FLAT = 13
+# photons on the inward and the outward face of every triangle, and a reflectance for each: hand-written, unequal, the triangle
+# without area included (what it holds must go nowhere).  The light sits on the small wall z = 0 and the floor y = 0, so that
+# later bounces have to carry it to the large walls
+BOX_SOURCE = np.array([900.0, 700.0, 500.0, 60.0, 40.0, 150.0, 90.0, 30.0, 120.0, 800.0, 600.0, 20.0, 50.0, 333.0])
+BOX_OUTER = np.array([80.0, 950.0, 30.0, 410.0, 640.0, 25.0, 700.0, 55.0, 310.0, 15.0, 480.0, 860.0, 75.0, 222.0])
+BOX_RHO_INNER = np.array([0.875, 0.25, 1.0, 0.625, 0.75, 0.5, 0.9375, 0.375, 0.8125, 0.3125, 1.0, 0.6875, 0.4375, 0.5], dtype=f32)
+BOX_RHO_OUTER = np.array([0.375, 1.0, 0.0625, 0.5, 0.3125, 0.75, 0.125, 0.875, 0.25, 0.9375, 0.4375, 0.1875, 0.625, 0.75], dtype=f32)
+
+
+def series_rows(scene):
+    return squares_rows() if scene == "squares" else box_rows()
+
+
+def series_inputs(scene):
+    """(source, outer, rho_inner, rho_outer, centre) of a scene of the bounce series"""
+    if scene == "squares":
+        return SOURCE, OUTER, RHO_INNER, RHO_OUTER, SQUARES_CENTRE
+    return BOX_SOURCE, BOX_OUTER, BOX_RHO_INNER, BOX_RHO_OUTER, BOX_CENTRE
+
+
+def series_planes(scene, inner=None):
+    """(faces f64[2][T], rho f32[2][T]) of the sided and the mapped call; `inner` replaces the inward source"""
+    src, outer, ri, ro, centre = series_inputs(scene)
+    rows = series_rows(scene)
+    face = inner_faces(rows, centre)
+    T = face.size
+
+    def planes(a, b):
+        out = np.zeros((2, T), dtype=np.asarray(a).dtype)
+        out[face, np.arange(T)] = a
+        out[1 - face, np.arange(T)] = b
+        return out
+    return planes(src if inner is None else inner, outer), planes(ri, ro)
+
+
+@functools.lru_cache(maxsize=None)
+def series_tables(scene, uniform=False):
+    """form_factor_tables of the triangles with an area, laid into T x T: the one without is left out, nothing lands on it"""
+    if scene == "squares":
+        return squares_tables(uniform)
+    tris = verts(box_rows())
+    T = tris.shape[0]
+    keep = np.nonzero(areas(box_rows()) > 0)[0]
+    f, e, a = rr.form_factor_tables(tris[keep], 64, uniform)
+    F, E, arrive = np.zeros((2, T, T)), np.zeros((2, T, T)), np.zeros((T, T), dtype=np.int64)
+    F[:, keep[:, None], keep[None, :]] = f
+    E[:, keep[:, None], keep[None, :]] = e
+    arrive[keep[:, None], keep[None, :]] = a
+    return F, E, arrive
+
+
+def check_series_scene(scene):
+    """what the model of the bounce series rests on, asserted on the scene"""
+    rows = series_rows(scene)
+    tris = verts(rows)
+    A = areas(rows)
+    F, E, arrive = series_tables(scene)
+    inner = inner_faces(rows, series_inputs(scene)[4])
+    assert rr.on_convex_boundary(tris), "no triangle shades another"
+    assert set(inner[A > 0]) == {0, 1}, "both face 0 and face 1 look inwards somewhere"
+    if scene == "squares":
+        assert np.all(A > 0) and np.all(F.sum(axis=(0, 2)) < 0.9), "an open scene: many links miss"
+        return
+    T = A.size
+    assert T <= 16 and A.max() / A[A > 0].min() >= 8.0, "unequal areas"
+    assert (A == 0).sum() == 1 and A[BOX_FLAT] == 0, "exactly one triangle has nn == 0"
+    assert np.all(F[:, BOX_FLAT] == 0) and np.all(F[:, :, BOX_FLAT] == 0)
+    for t in np.nonzero(A > 0)[0]:
+        assert abs(F[inner[t], t].sum() - 1.0) <= E[inner[t], t].sum(), "a closed box: an inward row sums to 1"
+        assert F[1 - inner[t], t].sum() == 0.0, "an outward face sees nothing"
+        assert np.all(arrive[t][F[inner[t], t] > 0] == inner[F[inner[t], t] > 0]), "light arrives on inward faces"
+    src, outer, ri, ro, _ = series_inputs(scene)
+    assert min(ri.min(), ro.min()) <= 0.25 and max(ri.max(), ro.max()) >= 1.0, "the mapped planes span [0.25, 1]"
+    assert len(set(src)) == T and len(set(outer)) == T, "unequal sources"
+
+
+def series_model(call, scene, tables=None, away=False):
+    """rr.link_model of a call on a scene: one source on both faces and one rho for the plain call, the face planes and one rho for
+    the sided call, the face planes and a rho per face for the mapped call.  away: light on the outward faces only"""
+    rows = series_rows(scene)
+    src = series_inputs(scene)[0]
+    faces, rho = series_planes(scene, np.zeros(src.size) if away else None)
+    if call == "linked":
+        faces, rho = np.stack([src, src]), BOUNCE_RHO
+    elif call == "sided":
+        rho = BOUNCE_RHO
+    else:
+        rho = rho.astype(f64)
+    return rr.link_model(series_tables(scene) if tables is None else tables, areas(rows), rho, faces)
+
+
+def series_parts(g):
+    """{"total": sum of g_1..g_K, "g1": g_1, ..} of g[K][R], folded to triangles"""
+    g = rr.fold_faces(g)
+    out = {"total": g.sum(axis=0)}
+    out.update({"g%d" % (b + 1): g[b] for b in range(g.shape[0])})
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def series_reference(call, scene, S2=S, away=False):
+    """{part: dict(mu, series, sigma, eps, variants)} for part = "total" (K = 4) and "g1".."g4": mu the exact mean over link sets,
+    series the mean-field value A Mbar^b e0, sigma that of one call, eps the form factors' quadrature error carried through
+    (every entry of Mbar is >= 0, so the series is monotone in F: half the difference between F + E and F - E)"""
+    Kb, Sp = SERIES_K, S2 // 2
+    F, E, arrive = series_tables(scene)
+    model = series_model(call, scene, away=away)
+    P, rho, e0, A = model
+    area = areas(series_rows(scene))
+    exact = series_parts(rr.series_exact(P, rho, e0, A, Kb, Sp))
+    mean_field = series_parts(rr.series(P, rho, e0, A, Kb))
+    hi = series_parts(rr.series(*series_model(call, scene, (F + E, E, arrive), away), Kb))
+    lo = series_parts(rr.series(*series_model(call, scene, (np.maximum(F - E, 0.0), E, arrive), away), Kb))
+    wrong = {"uniform hemisphere": series_parts(rr.series(*series_model(call, scene, series_tables(scene, True), away), Kb))}
+    names = ["no area", "rho once"] + (["receiver's rho"] if call == "mapped" else [])
+    wrong.update({w: series_parts(rr.series_wrong(P, rho, e0, A, Kb, w)) for w in names})
+    out = {}
+    for part in exact:
+        bounces = tuple(range(1, Kb + 1)) if part == "total" else (int(part[1:]),)
+        variants = {w: v[part] for w, v in wrong.items() if not (w != "uniform hemisphere" and part == "g1")}
+        if part == "total":
+            variants["only the last bounce"] = mean_field["g%d" % Kb]
+            variants["K times the first bounce"] = Kb * mean_field["g1"]
+        out[part] = dict(mu=exact[part], series=mean_field[part], sigma=rr.series_sigma(P, rho, e0, area, Sp, bounces),
+                         eps=0.5 * (hi[part] - lo[part]), variants=variants)
+    return out
+
+
+SERIES_VARIANTS = ("uniform hemisphere", "no area", "rho once", "receiver's rho", "only the last bounce", "K times the first bounce")
+
+
+def series_bias(scene, S2):
+    """the largest |exact mean / series - 1| over the lit triangles of the plain call's total of four bounces"""
+    ref = series_reference("linked", scene, S2)["total"]
+    lit = ref["series"] > 0
+    return float(np.max(np.abs(ref["mu"][lit] / ref["series"][lit] - 1.0)))
+
+
+# ---------------------------------------------------------------- the refine, conditional on its first pass
+REFINE_CASE = "point lamp, plate"
+REFINE_S0 = 16
+REFINE_FIRST_SEED = 11
+REFINE_SETTINGS = {
+    # name: (rel_error, max_extra, refine seeds)
+    "every triangle at the cap": (1e-5, 4096, tuple(range(301, 309))),
+    "counts of their own": (0.1, 64, tuple(range(401, 465))),
+}
+
+
+def refine_reference(X0, V0, n, R):
+    """(on, expected, variance): for a fixed first pass (X0, V0 of S0 samples) the merge is linear in the n extra samples, so over R
+    refine seeds  E[expected'] = (a X0 + b mu) / (a + b)  and, with independent samples, E[variance'] = (a^2 V0 + b Var(x)) /
+    (a + b)^2, a = S0, b = n_t; mu, sigma, Var(x) and mu4 are the direct gather's reference.  `on` are the triangles with n_t > 0;
+    each is judged with its own b.  The variants: the two weights swapped, and the plain average of the two passes"""
+    ref = direct_reference(REFINE_CASE)
+    on = np.nonzero(np.asarray(n) > 0)[0]
+    a, b = float(REFINE_S0), np.asarray(n, dtype=f64)[on]
+    X0, V0 = np.asarray(X0, dtype=f64)[on], np.asarray(V0, dtype=f64)[on]
+    mu, sigma, eps, var = ref["mu"][on], ref["sigma"][on], ref["eps"][on], ref["var"][on]
+    w = b / (a + b)
+    expected = dict(mu=(a * X0 + b * mu) / (a + b), tol=w * (6.0 * sigma / np.sqrt(R * b) + eps + 1e-5 * mu),
+                    variants={"weights swapped": (b * X0 + a * mu) / (a + b), "plain average": 0.5 * (X0 + mu)})
+    variance = dict(mu=(a * a * V0 + b * var) / (a + b) ** 2,
+                    tol=w * w * rr.variance_tolerance(var, ref["mu4"][on], b, R, ref["mom_err"][on]))
+    return on, expected, variance
+
+
+def accept_refine(case, setting, X0, V0, e, v, n, independent):
+    """the refine's rule over the R seeds' planes e, v [R][T] and counts n [R][T], and the conditions of the setting"""
+    rel_error, max_extra, seeds = REFINE_SETTINGS[setting]
+    R = len(seeds)
+    e, v, n = np.asarray(e), np.asarray(v), np.asarray(n)
+    assert e.shape[0] == R and np.all(n == n[0]), "the counts follow from the first pass alone"
+    n = n[0]
+    can = (X0 > 0) & (V0 > 0)
+    assert np.all(n[~can] == 0) and can.sum() >= 8
+    if max_extra == 4096:
+        want = REFINE_S0 * (V0[can] / (rel_error * X0[can]) ** 2 - 1.0)
+        assert np.all(want >= max_extra) and np.all(n[can] == max_extra), "every triangle that can be refined is at the cap"
+    else:
+        assert (n >= 16).sum() >= 3 and len(set(n[n > 0].tolist())) >= 2, "several counts, some of them large"
+    off = n == 0
+    assert np.all(e[:, off].view(np.int64) == X0[off].view(np.int64)) and np.all(v[:, off].view(np.int64) == V0[off].view(np.int64)), \
+        "a triangle with n_t = 0 keeps every bit of both planes"
+    on, expected, variance = refine_reference(X0, V0, n, R)
+    accept("refine, %s, %s" % (setting, case), e.mean(axis=0)[on], expected, R, expected["tol"])
+    if independent:
+        accept("refine's variance, %s, %s" % (setting, case), v.mean(axis=0)[on], variance, R, variance["tol"])
+
+
 # ---------------------------------------------------------------- acceptance, power and the margins file
 MARGINS = {}
 
@@ -324,6 +541,40 @@ def accept(case, mean, ref, samples, tol=None):
     print("%s: |err| / tol = %.3f; variants %s" % (case, worst, {k: round(v, 1) for k, v in pw.items()}))
     print("   mean %s\n   ref  %s\n   tol  %s" % (np.asarray(mean), ref["mu"], tol))
     assert np.all(err <= tol), "%s: |err| / tol per triangle %s" % (case, ratio(err, tol))
+    return worst
+
+
+def series_power(ref):
+    """{variant: distance}: the largest distance over the total and the single bounces of a case of the bounce series"""
+    out = {}
+    for part in ref.values():
+        for name, d in power(part, rr.tolerance(part["sigma"], part["eps"], part["mu"], K)).items():
+            out[name] = max(out.get(name, 0.0), d)
+    return out
+
+
+def accept_series(case, totals, ref):
+    """The rule of the bounce series.  totals[seed][k - 1][t]: the call with k bounces on that seed's links.  The total of
+    SERIES_K bounces and every single bounce g_b = total(b) - total(b - 1), as means over the K seeds, against the exact mean with
+    6 sigma_call / sqrt(K) + eps_quad + 1e-5 mu; sigma_call is that of ONE call, so `samples` is K.  Every figure is printed first"""
+    totals = np.asarray(totals, dtype=f64)
+    assert totals.shape[:2] == (K, SERIES_K)
+    got = {"total": totals[:, -1], "g1": totals[:, 0]}
+    got.update({"g%d" % b: totals[:, b - 1] - totals[:, b - 2] for b in range(2, SERIES_K + 1)})
+    worst, failed = 0.0, []
+    for part, r in ref.items():
+        tol = rr.tolerance(r["sigma"], r["eps"], r["mu"], K)
+        mean = got[part].mean(axis=0)
+        q = ratio(np.abs(mean - r["mu"]), tol)
+        worst = max(worst, float(q.max()))
+        print("%s, %s: |err| / tol = %.3f\n   mean %s\n   ref  %s\n   tol  %s" % (case, part, q.max(), mean, r["mu"], tol))
+        if not np.all(q <= 1.0):
+            failed.append((part, q))
+    pw = series_power(ref)
+    MARGINS[case] = dict(err_over_tol=worst, min_variant_distance=min(pw.values()), variants=pw)
+    assert not failed, "%s: |err| / tol per triangle %s" % (case, failed)
+    dark = ref["total"]["mu"] == 0
+    assert np.all(totals[:, :, dark] == 0.0) and not np.signbit(totals[:, :, dark]).any(), "a reference of 0 demands +0.0 in every call"
     return worst
 
 
