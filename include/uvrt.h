@@ -624,6 +624,106 @@ int uvrt_read_mirrors(uvrt_ctx* ctx, uvrt_mirror* panels_out, uint8_t* panel_of_
 int uvrt_drop_mirrors(uvrt_ctx* ctx);
 int uvrt_gather_mirror(uvrt_ctx* ctx, const uvrt_gather_params* launch, int32_t add, int32_t first_tri, int32_t tri_count);
 
+/* ---- sensors: virtual dosimeters at points off the mesh ----
+ * Every gather above answers for a triangle of the scan.  A dosimeter card taped to a wall, a radiometer head on a stand and
+ * the fluence rate at a point in free air are receivers that are no triangle: a sensor is a point with either a normal (a
+ * planar, one-sided receiver: irradiance) or none (a spherical receiver: fluence rate).  Everything here is additive: with no
+ * sensors set every call above keeps its bits, results and call sequence.
+ *
+ * State.  The sensors belong to the context, not to the scene: they need no scene to be set, and uvrt_set_scene leaves them
+ * and their planes alone.  With K sensors the context holds five planes f64[K], numbered as uvrt_read_sensor_plane's `which`:
+ * 0 density, 1 variance, 2 dose_map, 3 max_map, 4 var_map.
+ *
+ * uvrt_set_sensors: count in [1, 2^24]; every position and normal finite, a planar sensor's normal not zero (a spherical
+ * sensor's is not read), kind one of the two, reserved 0.  The whole input is checked before anything is changed; then it
+ * replaces any earlier set and all five planes are zeroed.  uvrt_sensor_info: out4 = {count (0: none), 0, 0, 0}.
+ * uvrt_read_sensors: the records as they were set; UVRT_ERR_INVALID when there are none.  uvrt_drop_sensors: drops the sensors
+ * and the planes (UVRT_OK when there are none).
+ *
+ * uvrt_gather_sensors writes density[k] and variance[k] for k in [first, first + count), under the context's sampling mode
+ * (uvrt_set_gather_sampling), flavours 0 and 1.  Sensor k has p = pos; for sample s < S = launch->samples, j = k*S + s (uint32):
+ *     rng = WangHash(j ^ WangHash(seed));  xi_h, xi_m = RandomFloat(&rng) x 2
+ *     UVRT_GATHER_INDEPENDENT:  u_h = xi_h, u_m = xi_m
+ *     UVRT_GATHER_STRATIFIED:   u_h = fl(fl((float)s + xi_h) / (float)S);  h_k = WangHash(k ^ WangHash(seed ^ 0x9E3779B9u));
+ *                               u_m = (float)((s*0x9E3779B9u + h_k) >> 8) * 2^-24
+ *     o    = uvrt_generate_sweep's origin with r1 := u_h, u := u_m                              (as uvrt_gather_direct forms it)
+ *     d    = p - o,  r = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z),  dir = d / r,  tmax = r * (1 - 2^-10)        (f32)
+ *     D    = (double)d,  R2 = (D.x*D.x + D.y*D.y) + D.z*D.z,  R = sqrt(R2)
+ *     planar:     n = (double)normal,  nn = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z),  c = (n.x*D.x + n.y*D.y) + n.z*D.z
+ *                 w = c < 0 ? (-c) / (nn * (R2*R) * 12.566370614359172) : 0.0
+ *     spherical:  w = 1.0 / (R2 * 12.566370614359172)
+ * A planar sensor is one-sided: light travelling along D arrives on the side the normal points to iff n.D < 0.  A sample with
+ * r not finite or not > 0 weighs 0; a sample that weighs 0 is not traced (dir (0,1,0), tmax 0).  x_s = occluded ? 0 : w,
+ *     density[k]  = (double)photons_equiv * (sum_s x_s / (double)S)
+ * expected photons per square metre of a planar sensor, per square metre of cross-section of a spherical one: the unit of
+ * expected[t] / area_t.  variance[k] takes the two forms of uvrt_set_gather_variance with c = (double)photons_equiv (m, q, SS
+ * and v as there, variance[k] = (c*c) * v); it is written whenever S >= 2, whatever the context's variance state, and is 0 at
+ * S = 1.  Every operator one rounding, the sums in sample order, no atomics: a pure function of the arguments, whatever the
+ * capacity (sensors go in chunks of floor(capacity / S)) or the cut of a range into calls.
+ *
+ * uvrt_gather_sensors_indirect adds one diffuse bounce to density[k] of the range.  S2 = params->samples, j = k*S2 + s,
+ * rng = WangHash(j ^ WangHash(seed)); (x, y) in the unit disc by uvrt_gather_indirect's bounded rejection (up to 8 rounds of
+ * two draws, then x = y = 0), q = x*x + y*y, all in f64:
+ *     planar:     z = sqrt(1.0 - q);  a = the axis of the smallest |n| component (x before y before z on ties);
+ *                 C = cross(a, n) written out: a = x: (0.0, -n.z, n.y);  a = y: (n.z, 0.0, -n.x);  a = z: (-n.y, n.x, 0.0)
+ *                 T = C / sqrt((C.x*C.x + C.y*C.y) + C.z*C.z),  B = cross(n, T) / nn  (B.x = (n.y*T.z - n.z*T.y) / nn, ...)
+ *                 D.c = ((x*T.c) + (y*B.c)) + ((z/nn)*n.c)                              every sample leaves on the normal's side
+ *     spherical:  g = sqrt(1.0 - q);  D = ((2.0*x)*g, (2.0*y)*g, 1.0 - 2.0*q)            Marsaglia's map: uniform on the sphere
+ * dir = (float)D, origin p, tmax 1e30f; a direction that is not finite or is zero is not traced, as in uvrt_gather_indirect.
+ * A closest-hit query answers h.  With n_h = cross(e1, e2) of h and nn_h = |n_h| in f64, a miss or nn_h == 0 giving 0:
+ *     emitter 0:  y_s = (double)reflectance * (source[h] / (0.5*nn_h))                            the source plane
+ *     emitter 1:  a = ((n_h.x*dir.x + n_h.y*dir.y) + n_h.z*dir.z) < 0 ? 0 : 1                     the face the ray arrives on
+ *                 y_s = rho_a * (faces[a][h] / (0.5*nn_h)),  rho_a = use_map ? (double)rho[a][h] : (double)reflectance
+ *     planar:     density[k] += (sum_s y_s) / (double)S2           the mean radiosity over cosine samples is the irradiance
+ *     spherical:  density[k] += (4.0 * sum_s y_s) / (double)S2     the fluence is 4 pi times the mean radiance
+ * variance[k] is left alone: it is the direct part's.
+ *
+ * Both tracing calls run on the context's stream behind outstanding launches, leave SEED, tempPhotonMap, expected, variance,
+ * faces, source, the links, the reflectance map, the panels and the remembered gather of uvrt_gather_refine untouched, and
+ * drop "the last generate" as uvrt_gather_direct does.  Mirror panels do not reach a sensor.
+ *
+ * uvrt_accumulate_sensors is cl/accumulate.cl's rule per sensor, in this order: dose_map += density * (double)time_step;
+ * max_map = max(max_map, density); var_map += variance * ((double)time_step * (double)time_step); density = variance = 0.
+ * uvrt_reset_sensors zeroes the five planes.  uvrt_read_sensor_plane / uvrt_write_sensor_plane are uvrt_read_variance /
+ * uvrt_write_variance for plane `which` over [first, first + count) of [0, K]; they synchronise.  uvrt_sensor_dosage is
+ * uvrt_compute_dosage's arithmetic with area = 1.0f, read back:
+ *     out[i] = (float)(((double)scaled_power * map[first + i]) / (double)(1.0f * (float)photons_per_light))
+ * map = dose_map (UVRT_MAP_SUM) or max_map (UVRT_MAP_MAX); it synchronises.
+ *
+ * UVRT_ERR_INVALID with nothing changed: a null argument; no sensors; a range outside [0, K]; K*S >= 2^31; S outside
+ * [1, 4096] (S2: even, [2, 4096]) or above the capacity; photons_equiv <= 0; a non-zero reserved field; a kind or plane or
+ * map number out of range; a non-finite value or a planar sensor's zero normal; a reflectance outside [0, 1] or not finite;
+ * and for the two tracing calls no scene, flavour 2, emitter or use_map out of range, use_map with emitter 0 or without
+ * reflectance planes (uvrt_fill_reflectance / uvrt_write_reflectance). */
+enum { UVRT_SENSOR_PLANAR = 0, UVRT_SENSOR_SPHERICAL = 1 };
+#define UVRT_SENSOR_MAX (1 << 24)
+typedef struct {
+    float   pos[3];
+    float   normal[3];       /* planar: finite, not zero; the side it points to is the sensitive one.  spherical: finite, not read */
+    int32_t kind;
+    int32_t reserved;        /* 0 */
+} uvrt_sensor;               /* 32 bytes */
+typedef struct {
+    float    reflectance;    /* rho in [0, 1] */
+    int32_t  samples;        /* S2: even, in [2, 4096]; S2 <= capacity; K*S2 < 2^31 */
+    uint32_t seed;
+    int32_t  emitter;        /* 0: the source plane, 1: the face planes */
+    int32_t  use_map;        /* 0 / 1: the reflectance planes in place of `reflectance`; emitter 1 only */
+    int32_t  reserved;       /* 0 */
+} uvrt_sensor_indirect_params;
+int uvrt_set_sensors(uvrt_ctx* ctx, const uvrt_sensor* sensors, int32_t count);
+int uvrt_sensor_info(uvrt_ctx* ctx, int32_t out4[4]);
+int uvrt_read_sensors(uvrt_ctx* ctx, uvrt_sensor* sensors_out);
+int uvrt_drop_sensors(uvrt_ctx* ctx);
+int uvrt_gather_sensors(uvrt_ctx* ctx, const uvrt_gather_params* launch, int32_t first, int32_t count);
+int uvrt_gather_sensors_indirect(uvrt_ctx* ctx, const uvrt_sensor_indirect_params* params, int32_t first, int32_t count);
+int uvrt_accumulate_sensors(uvrt_ctx* ctx, float time_step);
+int uvrt_reset_sensors(uvrt_ctx* ctx);
+int uvrt_read_sensor_plane(uvrt_ctx* ctx, int32_t which, double* out, int32_t first, int32_t count);
+int uvrt_write_sensor_plane(uvrt_ctx* ctx, int32_t which, const double* in, int32_t first, int32_t count);
+int uvrt_sensor_dosage(uvrt_ctx* ctx, int32_t which_map, int32_t photons_per_light, float scaled_power, float* out,
+                       int32_t first, int32_t count);
+
 /* ---- batched tracing: several launches in one go, one count "plane" per launch ----
  *
  * A computation is iterations x lamps launches of generate -> extend -> accumulate (raytracer.cpp:66-88).

@@ -167,6 +167,17 @@ SYMBOLS = [
     ("uvrt_read_mirrors", C.c_int, [_vp, _vp, _vp]),
     ("uvrt_drop_mirrors", C.c_int, [_vp]),
     ("uvrt_gather_mirror", C.c_int, [_vp, _vp, _i32, _i32, _i32]),
+    ("uvrt_set_sensors", C.c_int, [_vp, _vp, _i32]),
+    ("uvrt_sensor_info", C.c_int, [_vp, _vp]),
+    ("uvrt_read_sensors", C.c_int, [_vp, _vp]),
+    ("uvrt_drop_sensors", C.c_int, [_vp]),
+    ("uvrt_gather_sensors", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_gather_sensors_indirect", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("uvrt_accumulate_sensors", C.c_int, [_vp, _f32]),
+    ("uvrt_reset_sensors", C.c_int, [_vp]),
+    ("uvrt_read_sensor_plane", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_write_sensor_plane", C.c_int, [_vp, _i32, _vp, _i32, _i32]),
+    ("uvrt_sensor_dosage", C.c_int, [_vp, _i32, _i32, _f32, _vp, _i32, _i32]),
 ]
 
 PLAN_CONVERGED, PLAN_ITERATION_CAP = 0, 1
@@ -218,6 +229,27 @@ MIRROR_DT = np.dtype([("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("reflect
 def mirror(point, normal, reflectance, reserved=0):
     """a uvrt_mirror record: the plane through `point` with `normal`, reflecting on the side the normal points to"""
     return (tuple(point), tuple(normal), reflectance, reserved)
+
+
+# uvrt_sensor (include/uvrt.h): a virtual dosimeter
+SENSOR_PLANAR, SENSOR_SPHERICAL = 0, 1
+SENSOR_MAX = 1 << 24
+SENSOR_DT = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("kind", "<i4"), ("reserved", "<i4")])
+# the five planes of uvrt_read_sensor_plane / uvrt_write_sensor_plane
+SENSOR_DENSITY, SENSOR_VARIANCE, SENSOR_DOSE_MAP, SENSOR_MAX_MAP, SENSOR_VAR_MAP = range(5)
+
+
+def sensor(pos, normal=None, kind=None, reserved=0):
+    """a uvrt_sensor record: planar with `normal` (the sensitive side), spherical without one"""
+    if kind is None:
+        kind = SENSOR_SPHERICAL if normal is None else SENSOR_PLANAR
+    return (tuple(pos), (0.0, 0.0, 0.0) if normal is None else tuple(normal), kind, reserved)
+
+
+class SensorIndirectParams(C.Structure):
+    """uvrt_sensor_indirect_params (include/uvrt.h)"""
+    _fields_ = [("reflectance", C.c_float), ("samples", C.c_int32), ("seed", C.c_uint32), ("emitter", C.c_int32),
+                ("use_map", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PlanParams(C.Structure):
@@ -865,6 +897,76 @@ class Ctx:
         prm.photons_equiv = int(photons_equiv)
         self._ck(self._L.uvrt_gather_mirror(self._h, C.byref(prm), int(add), int(first_tri),
                                             self.T - int(first_tri) if tri_count is None else int(tri_count)))
+
+    # ---- sensors: virtual dosimeters at points off the mesh ----
+    def set_sensors(self, sensors, count=None):
+        """sensors: uvrt_sensor records (capi.sensor) or a SENSOR_DT array; replaces any earlier set, zeroes the five planes"""
+        rec = np.ascontiguousarray(np.array(sensors, dtype=SENSOR_DT).reshape(-1))
+        self._ck(self._L.uvrt_set_sensors(self._h, _ptr(rec) if rec.size else None, rec.size if count is None else int(count)))
+
+    def sensor_count(self):
+        out = np.full(4, -1, dtype=np.int32)
+        self._ck(self._L.uvrt_sensor_info(self._h, _ptr(out)))
+        return int(out[0])
+
+    def read_sensors(self):
+        """the sensors as they were set, SENSOR_DT[count]; an error when there are none"""
+        rec = np.zeros(max(self.sensor_count(), 1), dtype=SENSOR_DT)
+        self._ck(self._L.uvrt_read_sensors(self._h, _ptr(rec)))
+        return rec[:self.sensor_count()].copy()
+
+    def drop_sensors(self):
+        self._ck(self._L.uvrt_drop_sensors(self._h))
+
+    def gather_sensors(self, frm, to, light_length, samples, seed, photons_equiv, first=0, count=None, reserved=(0, 0)):
+        """density and variance [first, +count) = the lamp's direct light at the sensors, per square metre"""
+        prm = GatherParams()
+        prm.from_ = _f3(frm)
+        prm.to = _f3(to)
+        prm.light_length = float(np.float32(light_length))
+        prm.samples = int(samples)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        prm.photons_equiv = int(photons_equiv)
+        prm.reserved[0], prm.reserved[1] = int(reserved[0]), int(reserved[1])
+        self._ck(self._L.uvrt_gather_sensors(self._h, C.byref(prm), int(first),
+                                             self.sensor_count() - int(first) if count is None else int(count)))
+
+    def gather_sensors_indirect(self, reflectance, samples, seed, emitter=0, use_map=0, first=0, count=None, reserved=0):
+        """density[first, +count) += one diffuse bounce of the source plane (emitter 0) or the face planes (emitter 1)"""
+        prm = SensorIndirectParams()
+        prm.reflectance = float(np.float32(reflectance))
+        prm.samples = int(samples)
+        prm.seed = int(seed) & 0xFFFFFFFF
+        prm.emitter = int(emitter)
+        prm.use_map = int(use_map)
+        prm.reserved = int(reserved)
+        self._ck(self._L.uvrt_gather_sensors_indirect(self._h, C.byref(prm), int(first),
+                                                      self.sensor_count() - int(first) if count is None else int(count)))
+
+    def accumulate_sensors(self, time_step):
+        self._ck(self._L.uvrt_accumulate_sensors(self._h, float(np.float32(time_step))))
+
+    def reset_sensors(self):
+        self._ck(self._L.uvrt_reset_sensors(self._h))
+
+    def read_sensor_plane(self, which, first=0, count=None):
+        """plane `which` (SENSOR_DENSITY .. SENSOR_VAR_MAP) of the sensors, float64"""
+        count = self.sensor_count() - first if count is None else count
+        out = np.empty(max(int(count), 0), dtype=np.float64)
+        self._ck(self._L.uvrt_read_sensor_plane(self._h, int(which), _ptr(out), int(first), int(count)))
+        return out
+
+    def write_sensor_plane(self, which, values, first=0):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        self._ck(self._L.uvrt_write_sensor_plane(self._h, int(which), _ptr(v), int(first), int(v.size)))
+
+    def sensor_dosage(self, which_map, photons_per_light, scaled_power, first=0, count=None):
+        """float32: uvrt_compute_dosage's value of dose_map (MAP_SUM) or max_map (MAP_MAX) with area 1"""
+        count = self.sensor_count() - first if count is None else count
+        out = np.empty(max(int(count), 0), dtype=np.float32)
+        self._ck(self._L.uvrt_sensor_dosage(self._h, int(which_map), int(photons_per_light), float(np.float32(scaled_power)),
+                                            _ptr(out), int(first), int(count)))
+        return out
 
     @property
     def seed(self):

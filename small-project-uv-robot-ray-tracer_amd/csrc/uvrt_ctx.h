@@ -15,6 +15,8 @@
 //                         uvrt_gather_indirect_linked) and their sided forms (uvrt_indirect_links_build_sided,
 //                         uvrt_gather_indirect_linked_sided)
 //   uvrt_capi_mirror.hip  specular panels and the mirror gather (uvrt_set_mirrors, uvrt_gather_mirror)
+//   uvrt_capi_sensors.hip virtual dosimeters (uvrt_set_sensors, uvrt_gather_sensors, uvrt_gather_sensors_indirect and the
+//                         sensors' own planes)
 //   uvrt_capi_comm.hip    the one collective of a sharded computation (RCCL, opened at run time)
 //
 // One context = one HIP device + one in-order stream + all device buffers of a RayTracer
@@ -161,6 +163,12 @@ struct uvrt_ctx {
     DevBuf g_face;                             // the face each sample arrives on, uint8[capacity] (uvrt_set_gather_faces)
     DevBuf g_hit;                              // closest hits (uvrt_capi_indirect.hip): every ray's (dist bits, triID), uint2[capacity]
     DevBuf g_point;                            // the mirror gather's receiver points (uvrt_capi_mirror.hip), float4[capacity]
+    // virtual dosimeters (uvrt_capi_sensors.hip): the context's, not the scene's, so uvrt_set_scene leaves them alone.  The
+    // caller's records as they came (host and device), the five planes f64[5][K] and the dosage read-back's f32[K];
+    // sensor_count 0: none
+    int32_t sensor_count = 0;
+    std::vector<uvrt_sensor> sensors;
+    DevBuf sensors_dev, sensor_planes, sensor_out;
     // uvrt_gather_refine (include/uvrt.h "adaptive gather"): the exclusive prefix sums of a refined range, int32[T + 1], and
     // the scan's per-block totals
     DevBuf g_offs, g_scan;

@@ -667,4 +667,53 @@ struct MirrorReduceParams {
 };
 void launch_mirror_reduce(const MirrorReduceParams& p, hipStream_t s);
 
+// ---- virtual dosimeters (uvrt_sensors.hip; include/uvrt.h "sensors") ----
+// The sensors on the device are the caller's 32-byte records as they came, read as two float4: {pos.xyz, normal.x},
+// {normal.y, normal.z, kind bits, reserved}.  The five planes are one array f64[5][K]: density, variance, dose_map, max_map,
+// var_map (the `which` of uvrt_read_sensor_plane).
+struct SensorGenParams {
+    const float4* sensors;   // [K * 2]
+    float4* rays;            // [count * samples] dir.xyz, orig.y
+    float2* oxz;             // orig.x, orig.z
+    float* tmax;
+    double* w;               // the sample's weight (0 for a sample that is not traced); the reflected generate leaves it alone
+    float fx, fy, fz, tx, ty, tz;
+    float light_length;
+    uint32_t seed_hash;      // WangHash(seed)
+    int32_t first, count, samples;
+    uint32_t seed;           // the raw seed (the stratified rule's rotation)
+    int32_t mode;            // UVRT_GATHER_INDEPENDENT / UVRT_GATHER_STRATIFIED: which instantiation is launched
+};
+void launch_sensor_generate(const SensorGenParams& p, hipStream_t s);
+void launch_sensor_indirect_generate(const SensorGenParams& p, hipStream_t s);
+// density[k] and variance[k] of the chunk's sensors from its weights and answers
+struct SensorReduceParams {
+    const double* w;
+    const uint8_t* occluded;
+    double* density;         // [K]
+    double* variance;        // [K]
+    int32_t first, count, samples, photons_equiv;
+    int32_t mode;
+};
+void launch_sensor_reduce(const SensorReduceParams& p, hipStream_t s);
+// density[k] += the reflected part of the chunk's sensors, from its hit records (and, emitter 1, its rays' directions)
+struct SensorIndirectReduceParams {
+    const float4* sensors;
+    const float4* gtris;
+    const float4* rays;
+    const uint2* hit;
+    const double* source;    // [T] (emitter 0)
+    const double* faces;     // [2 * T] (emitter 1)
+    const float* rho;        // [2 * T] (use_map) or null
+    double* density;         // [K]
+    int32_t first, count, samples, T;
+    float reflectance;
+    int32_t emitter, use_map;
+};
+void launch_sensor_indirect_reduce(const SensorIndirectReduceParams& p, hipStream_t s);
+// accumulate.cl's rule per sensor over planes f64[5][K]; out[k] = k_compute_dosage's value of map[first + k] with area 1.0f
+void launch_sensor_accumulate(double* planes, int32_t K, float time_step, hipStream_t s);
+void launch_sensor_dosage(const double* map, float* out, int32_t photons_per_light, float scaled_power, int32_t first, int32_t count,
+                          hipStream_t s);
+
 }  // namespace uvrt

@@ -81,6 +81,15 @@ SYMBOLS = [
     ("uvrt_host_rt_has_mirrors", C.c_int, [_vp]),
     ("uvrt_host_rt_prepare_mirror_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
     ("uvrt_host_mirror_rules", C.c_int, [C.c_char_p, _vp, C.c_int, _vp, C.POINTER(C.c_int), _vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_rt_set_sensor_map", None, [_vp, C.c_char_p]),
+    ("uvrt_host_rt_get_sensor_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_rt_set_sensors", None, [_vp, _vp, C.c_int]),
+    ("uvrt_host_rt_has_sensors", C.c_int, [_vp]),
+    ("uvrt_host_rt_prepare_sensor_map", C.c_int, [_vp, C.c_char_p, C.c_int]),
+    ("uvrt_host_rt_active_sensors", C.c_int, [_vp, _vp, C.c_int]),
+    ("uvrt_host_rt_read_sensors", C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    ("uvrt_host_rt_calibrate_at_sensor", None, [_vp, C.c_float, C.c_int, C.c_int]),
+    ("uvrt_host_sensor_rules", C.c_int, [C.c_char_p, _vp, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     ("uvrt_host_rt_plan_group", None, [C.POINTER(_vp), C.c_int, _vp, _vp, C.POINTER(C.c_uint)]),
     ("uvrt_host_rt_plan_bounds", None, [_vp, _vp]),
     ("uvrt_host_rt_plan_segments", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
@@ -97,10 +106,11 @@ _FIELDS = {"lightLength", "lightHeight", "maxPhotonCount", "photonCount", "maxIt
            "currIterations", "lightIntensity", "minDosage", "minPower", "photonsPerLight", "compTime",
            "progress", "finishedComputation", "thresholdView", "startedComputation", "calibratedPower",
            "photonMapSize", "viewMode", "driveSpeed", "gatherSamples", "gatherSampling", "gatherRelError",
-           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided"}
+           "gatherMaxExtra", "reflectance", "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided",
+           "sensorSamples", "sensorLaunches"}
 _INT_FIELDS = {"maxPhotonCount", "photonCount", "maxIterations", "currIterations", "photonsPerLight",
                "photonMapSize", "viewMode", "gatherSamples", "gatherSampling", "gatherMaxExtra",
-               "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided"}
+               "reflectSamples", "reflectBounces", "gatherBatch", "reflectSided", "sensorSamples", "sensorLaunches"}
 _BOOL_FIELDS = {"finishedComputation", "thresholdView", "startedComputation"}
 
 
@@ -163,6 +173,18 @@ def parse_mirror_rules(path, tris):
                                     C.byref(count), members.ctypes.data_as(_vp), err, len(err)) != 0:
         raise ValueError(err.value.decode(errors="replace"))
     return panels[:count.value].copy(), members
+
+
+def parse_sensor_rules(path):
+    """RayTracer::ParseSensorRules: the rules file `path` into capi.SENSOR_DT[count], in file order (a grid's cell centres x
+    fastest, then y, then z).  Host only: no GPU is touched.  A line that cannot be read raises ValueError("FILE:LINE: reason")."""
+    count = C.c_int(0)
+    err = C.create_string_buffer(1024)
+    if lib().uvrt_host_sensor_rules(os.fsencode(path), None, 0, C.byref(count), err, len(err)) != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    out = np.zeros(max(count.value, 1), dtype=capi.SENSOR_DT)
+    lib().uvrt_host_sensor_rules(os.fsencode(path), out.ctypes.data_as(_vp), count.value, C.byref(count), err, len(err))
+    return out[:count.value].copy()
 
 
 class Mesh:
@@ -392,29 +414,122 @@ class RayTracer:
         if self._L.uvrt_host_rt_prepare_mirror_map(self._h, err, len(err)) != 0:
             raise ValueError(err.value.decode(errors="replace"))
 
+    # ---- RayTracer::sensorMap: virtual dosimeters gathered beside every launch ----
+    @property
+    def sensorMap(self):
+        """the rules file of the sensors ("" for none); a relative name is resolved against the route directory"""
+        buf = C.create_string_buffer(4096)
+        self._L.uvrt_host_rt_get_sensor_map(self._h, buf, len(buf))
+        return os.fsdecode(buf.value)
+
+    @sensorMap.setter
+    def sensorMap(self, path):
+        path = path or ""
+        if any(ch in path for ch in "<>&"):
+            raise ValueError("sensorMap: a file name with <, > or & cannot stand in a route file")
+        self._L.uvrt_host_rt_set_sensor_map(self._h, os.fsencode(path))
+
+    def set_sensors(self, sensors):
+        """RayTracer::SetSensors: the sensors themselves (capi.sensor records or a capi.SENSOR_DT array), for a caller that
+        brings them; None forgets them"""
+        if sensors is None:
+            self._L.uvrt_host_rt_set_sensors(self._h, None, 0)
+            return
+        rec = np.ascontiguousarray(np.array(sensors, dtype=capi.SENSOR_DT).reshape(-1))
+        if not 1 <= rec.size <= capi.SENSOR_MAX:
+            raise ValueError("set_sensors takes 1 to 2^24 sensors")
+        if not (np.isfinite(rec["pos"]).all() and np.isfinite(rec["normal"]).all()):
+            raise ValueError("every sensor needs a finite position and normal")
+        if (~np.isin(rec["kind"], (capi.SENSOR_PLANAR, capi.SENSOR_SPHERICAL))).any() or (rec["reserved"] != 0).any():
+            raise ValueError("every sensor needs kind 0 (planar) or 1 (spherical) and reserved = 0")
+        if ((rec["kind"] == capi.SENSOR_PLANAR) & (np.abs(rec["normal"]).max(axis=1) == 0)).any():
+            raise ValueError("a planar sensor's normal is zero")
+        self._L.uvrt_host_rt_set_sensors(self._h, rec.ctypes.data_as(_vp), rec.size)
+
+    SetSensors = set_sensors
+
+    def _has_sensors(self):
+        return bool(self._L.uvrt_host_rt_has_sensors(self._h))
+
+    def _check_sensors(self, batched=False):
+        """what the host layer would end the process for: sensors beside mirror panels or in a batched computation, a rules file
+        with a line it cannot read (the file is read here, once per name, into the cache the launches use)"""
+        if not self._has_sensors():
+            return
+        if batched:
+            raise ValueError("sensors are not supported by ComputeIterationsBatched: they are gathered launch by launch")
+        if self._has_mirrors():
+            raise ValueError("sensors are not supported with mirror panels: a sensor would not see the panels' light")
+        err = C.create_string_buffer(1024)
+        if self._L.uvrt_host_rt_prepare_sensor_map(self._h, err, len(err)) != 0:
+            raise ValueError(err.value.decode(errors="replace"))
+
+    def sensors(self):
+        """the sensors a launch would gather now, capi.SENSOR_DT (the file's once it has been read, else set_sensors')"""
+        self._check_sensors()
+        n = self._L.uvrt_host_rt_active_sensors(self._h, None, 0)
+        out = np.zeros(max(n, 1), dtype=capi.SENSOR_DT)
+        self._L.uvrt_host_rt_active_sensors(self._h, out.ctypes.data_as(_vp), n)
+        return out[:n].copy()
+
+    def read_sensors(self):
+        """RayTracer::ReadSensors: (dose float32[K] in mJ/cm^2, peak float32[K] in microW/cm^2, one standard error of dose
+        float64[K]) under the divisors and scaled powers Shade uses for the dosage and the maxpower view"""
+        if not self._has_sensors():
+            raise ValueError("read_sensors: no sensors (sensorMap or set_sensors)")
+        self._check_sensors()
+        n = self._L.uvrt_host_rt_active_sensors(self._h, None, 0)
+        dose, peak, err = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float64)
+        self._L.uvrt_host_rt_read_sensors(self._h, dose.ctypes.data_as(_vp), peak.ctypes.data_as(_vp), err.ctypes.data_as(_vp), n)
+        return dose, peak, err
+
+    ReadSensors = read_sensors
+
+    def calibrate_power_at_sensor(self, measure_power, sensor, light_index=0):
+        """RayTracer::CalibratePowerAtSensor: lightIntensity from a reading of `measure_power` at sensor `sensor` with the lamp
+        at position `light_index`, in the room as it stands; returns the calibrated power"""
+        if not self._has_sensors():
+            raise ValueError("calibrate_power_at_sensor: no sensors (sensorMap or set_sensors)")
+        self._check_sensors()
+        self._check_reflect_map()
+        if not 0 <= int(sensor) < self._L.uvrt_host_rt_active_sensors(self._h, None, 0):
+            raise ValueError("calibrate_power_at_sensor: no such sensor")
+        if not 0 <= int(light_index) < self._L.uvrt_host_rt_lamp_count(self._h):
+            raise ValueError("calibrate_power_at_sensor: no such lamp position")
+        self._L.uvrt_host_rt_calibrate_at_sensor(self._h, float(measure_power), int(sensor), int(light_index))
+        return self.calibratedPower
+
+    CalibratePowerAtSensor = calibrate_power_at_sensor
+
     # reference method names
     def UpdatePhotonsPerLight(self): self._L.uvrt_host_rt_update_photons_per_light(self._h)
     def ComputeDosageMap(self):
+        self._check_sensors()
         self._check_reflect_map()
         self._check_mirrors()
         self._L.uvrt_host_rt_compute_dosage_map(self._h)
     def ComputeSingleLightDosageMap(self, lamp, photonsPerLight, triangleCount):
+        self._check_sensors()
         self._check_reflect_map()
         self._check_mirrors()
         self._L.uvrt_host_rt_compute_single(self._h, lamp[0], lamp[1], lamp[2], int(photonsPerLight),
                                             int(triangleCount))
     def ComputeSegmentDosageMap(self, a, b, photonsPerLight, triangleCount):
         """the dose of the drive from position a to position b ((x, z) pairs) at driveSpeed"""
+        self._check_sensors()
         self._check_reflect_map()
         self._check_mirrors()
         self._L.uvrt_host_rt_compute_segment(self._h, a[0], a[1], b[0], b[1], int(photonsPerLight), int(triangleCount))
     def ComputeSegments(self):
         """the segments of one iteration, in order (nothing at driveSpeed 0)"""
+        self._check_sensors()
         self._check_reflect_map()
         self._check_mirrors()
         self._L.uvrt_host_rt_compute_segments(self._h)
     def Shade(self): self._L.uvrt_host_rt_shade(self._h)
-    def ResetDosageMap(self): self._L.uvrt_host_rt_reset_dosage_map(self._h)
+    def ResetDosageMap(self):
+        self._check_sensors()
+        self._L.uvrt_host_rt_reset_dosage_map(self._h)
     def ClearBuffers(self, resetColor): self._L.uvrt_host_rt_clear_buffers(self._h, int(bool(resetColor)))
     def AddLamp(self): self._L.uvrt_host_rt_add_lamp(self._h)
     def CalibratePower(self, measurePower, measureHeight, measureDist):
@@ -426,7 +541,9 @@ class RayTracer:
     # headless additions
     def Sync(self): self._L.uvrt_host_rt_sync(self._h)
     def set_shard(self, rank, world): self._L.uvrt_host_rt_set_shard(self._h, int(rank), int(world))
-    def ComputeIterationsBatched(self, iterations): self._L.uvrt_host_rt_compute_batched(self._h, int(iterations))
+    def ComputeIterationsBatched(self, iterations):
+        self._check_sensors(batched=True)
+        self._L.uvrt_host_rt_compute_batched(self._h, int(iterations))
     def SetRayRange(self, rank, world): self._L.uvrt_host_rt_set_ray_range(self._h, int(rank), int(world))
     def set_reduce_over_comm(self, on): self._L.uvrt_host_rt_set_reduce_over_comm(self._h, int(bool(on)))
 

@@ -162,6 +162,53 @@ int uvrt_host_mirror_rules(const char* path, const void* tris64, int count, uvrt
     return report(RayTracer::ParseMirrorRules(path, (const Tri*)tris64, count, panels_out, panels_count, panel_of_tri_out), err, err_len);
 }
 
+// RayTracer::sensorMap (the rules file; "" for none) and the caller's sensors (SetSensors; count 0 forgets them);
+// uvrt_host_rt_prepare_sensor_map is PrepareSensorMap: 0, or -1 and the message in err; uvrt_host_rt_active_sensors returns the
+// number of active sensors (ActiveSensors) and copies at most n records
+void uvrt_host_rt_set_sensor_map(void* r, const char* file) { ((RayTracer*)r)->sensorMap = file ? file : ""; }
+int uvrt_host_rt_get_sensor_map(void* r, char* out, int n)
+{
+    const std::string& f = ((RayTracer*)r)->sensorMap;
+    if (n > 0) { strncpy(out, f.c_str(), (size_t)n - 1); out[n - 1] = 0; }
+    return (int)f.size();
+}
+void uvrt_host_rt_set_sensors(void* r, const uvrt_sensor* sensors, int count)
+{
+    ((RayTracer*)r)->SetSensors(std::vector<uvrt_sensor>(sensors, sensors + std::max(count, 0)));
+}
+int uvrt_host_rt_has_sensors(void* r) { return ((RayTracer*)r)->HasSensors() ? 1 : 0; }
+int uvrt_host_rt_prepare_sensor_map(void* r, char* err, int err_len)
+{
+    return report(((RayTracer*)r)->PrepareSensorMap(), err, err_len);
+}
+int uvrt_host_rt_active_sensors(void* r, uvrt_sensor* out, int n)
+{
+    const std::vector<uvrt_sensor>& v = ((RayTracer*)r)->ActiveSensors();
+    for (int i = 0; i < n && i < (int)v.size(); ++i) out[i] = v[i];
+    return (int)v.size();
+}
+// RayTracer::ReadSensors: returns the number of sensors and copies at most n entries of each
+int uvrt_host_rt_read_sensors(void* r, float* dose, float* peak, double* std_err, int n)
+{
+    std::vector<float> d, p;
+    std::vector<double> e;
+    ((RayTracer*)r)->ReadSensors(d, p, e);
+    for (int i = 0; i < n && i < (int)d.size(); ++i) { dose[i] = d[i]; peak[i] = p[i]; std_err[i] = e[i]; }
+    return (int)d.size();
+}
+void uvrt_host_rt_calibrate_at_sensor(void* r, float p, int sensor, int light) { ((RayTracer*)r)->CalibratePowerAtSensor(p, sensor, light); }
+// RayTracer::ParseSensorRules: 0, *count and at most `max` records in out, or -1 and the message in err
+int uvrt_host_sensor_rules(const char* path, uvrt_sensor* out, int max, int* count, char* err, int err_len)
+{
+    std::vector<uvrt_sensor> v;
+    const std::string e = RayTracer::ParseSensorRules(path, &v);
+    if (e.empty()) {
+        *count = (int)v.size();
+        for (int i = 0; i < max && i < (int)v.size(); ++i) out[i] = v[i];
+    }
+    return report(e, err, err_len);
+}
+
 // RayTracer::gatherRelError and gatherMaxExtra (the adaptive gather of every gather launch; rel_error 0: off)
 void uvrt_host_rt_set_gather_refine(void* r, double rel_error, int max_extra)
 {
@@ -276,7 +323,7 @@ static int field(RayTracer* rt, const char* n, double* v, int set)
     F(calibratedPower, float) F(photonMapSize, int) F(driveSpeed, float) F(gatherSamples, int)
     F(gatherSampling, int) F(gatherRelError, double) F(gatherMaxExtra, int)
     F(reflectance, float) F(reflectSamples, int) F(reflectBounces, int) F(gatherBatch, int)
-    F(reflectSided, int)
+    F(reflectSided, int) F(sensorSamples, int) F(sensorLaunches, unsigned)
 #undef F
     if (!strcmp(n, "viewMode")) { if (set) rt->viewMode = (ViewMode)(int)*v; else *v = (double)rt->viewMode; return 0; }
     return -1;

@@ -5,6 +5,7 @@
 // stream with no host synchronisation in between; Shade = computeDosage + dosageToColor;
 // errors of the device layer are fatal (the reference's CHECKCL -> FatalError, exit).
 #include "raytracer.h"
+#include "raytracer_internal.h"
 
 #include "../../include/uvrt.h"
 
@@ -18,21 +19,9 @@
 #include <sstream>
 
 using namespace Tmpl8;
+using namespace Tmpl8::host_internal;
 
 namespace {
-
-// template.cpp:904-917 FatalError: report and terminate
-void check(int rc, const char* what)
-{
-    if (rc == UVRT_OK) return;
-    fprintf(stderr, "Fatal error in %s: %s\n", what, uvrt_last_error());
-    exit(1);
-}
-void fatal(const char* what)
-{
-    fprintf(stderr, "Fatal error: %s\n", what);
-    exit(1);
-}
 
 // ------------------------------------------------------------ minimal XML for route files
 struct XmlElem {
@@ -222,6 +211,7 @@ RayTracer::GatherOptions RayTracer::OwnGather() const
     g.reflectance = reflectance; g.reflectSamples = reflectSamples; g.reflectBounces = reflectBounces;
     g.sided = reflectSided; g.mapped = HasReflectanceMap(); g.mirrored = HasMirrors();
     g.batch = gatherBatch;
+    g.sensors = HasSensors();
     return g;
 }
 
@@ -269,21 +259,6 @@ const char* RayTracer::GatherRefusal(const GatherOptions& g, int checks, bool pl
 }
 
 // ------------------------------------------------------------ the reflectance map (raytracer.h reflectMap)
-namespace {
-
-// a whole word as a number: a double, rounded once to f32
-bool rule_number(const std::string& w, float* out)
-{
-    if (w.empty()) return false;
-    char* end = nullptr;
-    const double v = strtod(w.c_str(), &end);
-    if (end != w.c_str() + w.size() || std::isnan(v)) return false;
-    *out = (float)v;
-    return true;
-}
-
-}  // namespace
-
 std::string RayTracer::ParseReflectRules(const char* path, const Tri* tris, int triangleCount, float base, float* out)
 {
     std::ifstream f(path, std::ios::binary);
@@ -473,26 +448,29 @@ void RayTracer::UploadMirrors(int triangleCount)
     mirrorUploaded = stamp;
 }
 
+// ------------------------------------------------------------ virtual dosimeters (raytracer.h sensorMap; raytracer_sensors.cpp)
+const RayTracer::SensorHooks* RayTracer::sensorHooks = nullptr;
+
+const RayTracer::SensorHooks& RayTracer::Sensors()
+{
+    if (!sensorHooks) fatal("sensors need host/raytracer_sensors.cpp in the program");
+    return *sensorHooks;
+}
+
+void RayTracer::CheckSensorsAlone(const char* who) const
+{
+    auto refuse = [&](const char* why) { fatal((std::string(who) + ": " + why).c_str()); };
+    if (shardWorld > 1) refuse("launch sharding (shardWorld > 1) is not supported with sensors");
+    if (reduceOverComm) refuse("reduceOverComm is not supported with sensors (their maps live on one context)");
+    if (HasMirrors()) refuse("mirror panels are not supported with sensors (a sensor would not see the panels' light)");
+}
+
 void RayTracer::ComputeSegments()
 {
     std::vector<RouteLaunch> sweeps;
     for (const RouteLaunch& l : Launches())
         if (l.kind == UVRT_LAUNCH_SWEEP) sweeps.push_back(l);
     RunLaunches(sweeps, photonsPerLight, mesh->triangleCount, OwnGather(), false);
-}
-
-// the uvrt_gather_params of a gather launch with seed `seed`
-static uvrt_gather_params gather_params(const RouteLaunch& l, float lightLength, int samples, unsigned seed, int photons)
-{
-    uvrt_gather_params g;
-    memset(&g, 0, sizeof g);
-    memcpy(g.from, l.from, 12);
-    memcpy(g.to, l.kind == UVRT_LAUNCH_SWEEP ? l.to : l.from, 12);       // from == to: a stop
-    g.light_length = lightLength;
-    g.samples = samples;
-    g.seed = seed;
-    g.photons_equiv = photons;
-    return g;
 }
 
 void RayTracer::RunLaunches(const std::vector<RouteLaunch>& list, int photons, int triangleCount, const GatherOptions& g, bool capture)
@@ -535,6 +513,7 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
     const bool sweep = l.kind == UVRT_LAUNCH_SWEEP;
     if (const char* why = GatherRefusal(opt, kLaunchRefusals, false)) fatal(why);
     if (sweep && shardWorld > 1) fatal("driveSpeed > 0 is not supported with launch sharding (shardWorld > 1)");
+    if (opt.sensors) CheckSensorsAlone("sensors");
     const int samples = opt.samples, sided = opt.sided, reflectS = opt.reflectSamples, reflectK = opt.reflectBounces;
     const float reflect = opt.reflectance;
     if (samples > 0) {
@@ -613,12 +592,14 @@ void RayTracer::RunLaunch(const RouteLaunch& l, int photons, int triangleCount, 
             check(uvrt_indirect_source_from_expected(ctx), "indirect_source_from_expected");
             check(uvrt_gather_indirect(ctx, &ip, 0, triangleCount), "gather_indirect");
         }
+        if (opt.sensors) (this->*Sensors().gather)(l, photons, opt, g.seed, true);
         if (captureColumn >= 0) check(uvrt_plan_capture_expected(ctx, captureColumn), "plan_capture_expected");
         check(uvrt_accumulate_expected(ctx, l.duration, triangleCount), "accumulate_expected");
     } else if (shardWorld <= 1 || (launchIndex % shardWorld) == shardRank) {
         if (sweep) check(uvrt_generate_sweep(ctx, l.from, l.to, lightLength, 0, photons), "generate_sweep");
         else check(uvrt_generate(ctx, l.from, lightLength, 0, photons), "generate");   // :78-80
         check(uvrt_extend(ctx, photons), "extend");                                    // :82
+        if (opt.sensors) (this->*Sensors().gather)(l, photons, opt, 0u, true);
         check(uvrt_accumulate(ctx, l.duration, triangleCount), "accumulate");          // :84-85
     } else {
         // another rank traces this launch; keep generate.cl's program-scope SEED in step
@@ -657,6 +638,9 @@ void RayTracer::ComputeIterationsBatched(int iterations)
 void RayTracer::ComputeIterationsBatched(const std::vector<RayTracer*>& group, int iterations)
 {
     RayTracer* r0 = group[0];
+    for (RayTracer* rt : group)
+        if (rt->HasSensors() && !rt->planCapture)            // (a plan's capture runs no sensor call and leaves their maps alone)
+            fatal("sensors are not supported by ComputeIterationsBatched (they are gathered launch by launch: ComputeDosageMap)");
     for (RayTracer* rt : group)
         if (rt->gatherSamples > 0) fatal("gatherSamples > 0 is not supported by ComputeIterationsBatched (the direct gather runs launch by launch: ComputeDosageMap)");
     bool driving = false;
@@ -921,6 +905,7 @@ void RayTracer::ResetDosageMap()                             // raytracer.cpp:12
     launchIndex = 0;
     gatherLaunches = 0;
     ClearBuffers(true);
+    if (HasSensors()) (this->*Sensors().reset)();             // the sensors' maps and their launch counter with the triangles'
 }
 
 void RayTracer::ClearBuffers(bool resetColor)                // raytracer.cpp:133-143
@@ -1016,6 +1001,11 @@ void RayTracer::SaveRoute(char fileName[32])                 // raytracer.cpp:23
         if (mirrorMap.find_first_of("<>&") != std::string::npos) fatal("mirrorMap: a file name with <, > or & cannot stand in a route file");
         o << "    <mirror_map>" << mirrorMap << "</mirror_map>\n";
     }
+    if (!sensorMap.empty()) {                                // (no gather tag: photon launches gather sensors too)
+        if (sensorMap.find_first_of("<>&") != std::string::npos) fatal("sensorMap: a file name with <, > or & cannot stand in a route file");
+        o << "    <sensor_map>" << sensorMap << "</sensor_map>\n";
+        o << "    <sensor_samples>" << sensorSamples << "</sensor_samples>\n";
+    }
     o << "    <lamp_lengte>" << float_str(lightLength) << "</lamp_lengte>\n";
     o << "    <lamp_hoogte>" << float_str(lightHeight) << "</lamp_hoogte>\n";
     if (lightPositions.empty()) o << "    <route/>\n";
@@ -1072,6 +1062,12 @@ void RayTracer::LoadRoute(char fileName[32])                 // raytracer.cpp:26
     mirrorFilePanelOfTri.clear();
     mirrorFileParsed.clear();
     if ((e = root.child("mirror_map"))) mirrorMap = trim(e->text);
+    sensorMap.clear();                                       // (likewise)
+    sensorFileList.clear();
+    sensorFileParsed.clear();
+    if ((e = root.child("sensor_map"))) sensorMap = trim(e->text);
+    sensorSamples = 64;
+    if ((e = root.child("sensor_samples"))) to_int(trim(e->text), &sensorSamples);
     if ((e = root.child("lamp_lengte"))) to_float(trim(e->text), &lightLength);
     if ((e = root.child("lamp_hoogte"))) to_float(trim(e->text), &lightHeight);
     if ((e = root.child("route"))) {

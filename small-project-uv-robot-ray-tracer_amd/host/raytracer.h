@@ -304,6 +304,57 @@ public:
     // in f32, bounds included.
     static std::string ParseMirrorRules(const char* path, const Tri* tris, int triangleCount, uvrt_mirror* panelsOut, int* countOut,
                                         uint8_t* panelOfTriOut);
+    // Virtual dosimeters (include/uvrt.h "sensors"): dose and fluence at points off the mesh.  sensorMap names a
+    // rules file (empty: none; a relative name is resolved against routeDir, as mirrorMap's):
+    //     sensor X Y Z planar NX NY NZ                         a one-sided receiver; the side (NX, NY, NZ) points to is sensitive
+    //     sensor X Y Z sphere                                  a spherical receiver: fluence rate
+    //     grid X0 Y0 Z0 X1 Y1 Z1 NX NY NZ sphere               the cell centres of an NX x NY x NZ lattice over the box, x fastest,
+    //     grid X0 Y0 Z0 X1 Y1 Z1 NX NY NZ planar MX MY MZ      then y, then z: X0 + (X1 - X0) * ((i + 0.5f) / NX) in f32
+    // Sensors come in file order (ParseSensorRules below).  SetSensors hands records over directly; an empty vector forgets
+    // them; a file, when one is named, goes before them.  With sensors active every launch of ComputeDosageMap and
+    // ComputeSegments -- photon launches and gather launches, stops and driven segments -- gathers them after its own tracing
+    // and gathers and before its capture or accumulate: uvrt_set_gather_sampling(gatherSampling), uvrt_gather_sensors with
+    // the launch's lamp, samples = sensorSamples, seed = sensorLaunches++ (a counter of their own since ResetDosageMap) and
+    // photons_equiv = the launch's photons; with reflectance > 0 uvrt_gather_sensors_indirect(reflectance, samples =
+    // reflectSamples, seed = the launch's gather seed ^ 0x85EBCA6B) with emitter 0 -- the source plane is the snapshot of the
+    // direct plane the launch's bounce has taken -- or, under reflectSided, emitter 1 with use_map = there is a reflectance
+    // map; then uvrt_accumulate_sensors(duration).  So a sensor sees the lamp and ONE diffuse bounce in both bounce models:
+    // bounces 2..K of reflectBounces do not reach sensors, and neither does a mirror panel's light.  The sensors are uploaded
+    // when uvrt_sensor_info says the context has none (a new context) or they are not the ones uploaded last; an upload
+    // zeroes their maps.  ResetDosageMap zeroes the maps and the counter.  A plan (PlanDurations) runs no sensor call and
+    // leaves the sensor maps alone.  Fatal with sensors active: shardWorld > 1, ComputeIterationsBatched, a group,
+    // reduceOverComm, and active mirror panels -- the sensors would not see the panels' light, and silently understating a
+    // dosimeter is worse than refusing.  No sensors: every path bit for bit and call for call as before.  Saved as
+    // <sensor_map>FILE</sensor_map> and <sensor_samples>S</sensor_samples> after <mirror_map> when a file is named; a name that
+    // holds <, > or & cannot stand in a route file and is fatal there.
+    std::string sensorMap;
+    int sensorSamples = 64;
+    std::vector<uvrt_sensor> sensorList;            // the caller's sensors (SetSensors); never the file's
+    void SetSensors(const std::vector<uvrt_sensor>& sensors);
+    bool HasSensors() const { return !sensorMap.empty() || !sensorList.empty(); }
+    // Reads sensorMap's file unless that is what the cache holds; nothing to do without a file name.  Returns an empty string
+    // or ParseSensorRules' message.
+    std::string PrepareSensorMap();
+    // the sensors a launch would gather now: the file's when a file is named (empty until it has been read), else the caller's
+    const std::vector<uvrt_sensor>& ActiveSensors() const;
+    // The rules file above into *out.  Host only.  Returns an empty string, or what is wrong as "FILE:LINE: reason": an unknown
+    // keyword or kind, a wrong count of words, a word that is no finite number, a planar sensor's zero normal, a lattice count
+    // that is no integer >= 1, more than 2^24 sensors (or "FILE: cannot be read").
+    static std::string ParseSensorRules(const char* path, std::vector<uvrt_sensor>* out);
+    // What the sensors have received, one entry per sensor: dose and peak through uvrt_sensor_dosage with exactly the divisor
+    // and the scaled power Shade hands to uvrt_shade for the dosage view (mJ/cm^2) and the maxpower view (microW/cm^2);
+    // stdErr = scaled_power * sqrt(var_map) / N with the dosage view's two values, in f64 on the host: one standard error of
+    // dose, from the direct part's shadow rays alone.
+    void ReadSensors(std::vector<float>& dose, std::vector<float>& peak, std::vector<double>& stdErr);
+    // Calibration in the room as it stands: the sensor maps are reset, one stop launch at lightPositions[lightIndex] runs for
+    // the sensors alone (photonCount photons_equiv, sensorSamples samples, the current reflect options; with reflectance > 0
+    // the direct gather and the snapshot or the face planes the bounce needs are made first, in gather mode only), sensor
+    // `sensor`'s uvrt_sensor_dosage(UVRT_MAP_MAX, photonCount, 1.0f) is read, calibratedPower = 0.01f * (measurePower / value)
+    // and lightIntensity = calibratedPower as CalibratePower sets them, and the sensor maps are reset again.  Fatal when the
+    // value is not > 0.  Touches neither the scene nor the triangle maps.
+    void CalibratePowerAtSensor(float measurePower, int sensor, int lightIndex);
+    unsigned sensorLaunches = 0;                    // sensor launches since ResetDosageMap: the next launch's seed
+    static bool InstallSensorHooks();               // (raytracer_sensors.cpp calls it when it is loaded)
     // The batched direct gather (include/uvrt.h "batched direct gather").  gatherBatch = B in [2, 64] with
     // gatherSamples > 0: ComputeDosageMap and ComputeSegments walk their launches in groups of up to B consecutive ones; a
     // group's shadow rays are traced in one uvrt_gather_direct_batch (the seeds the launches would have taken, the variance
@@ -318,7 +369,8 @@ private:
     std::vector<RouteLaunch> Launches() const;      // RouteLaunches of this instance's route
     // How a launch gathers: the knobs above as one value, so that a launch of ComputeDosageMap and a launch of a plan go
     // through the same code.  samples = 0: photons, and nothing else is read.  relError / maxExtra: the refine; reflectance,
-    // reflectSamples, reflectBounces, sided, mapped: the bounces; mirrored: the mirror gather; batch: the gather batch.
+    // reflectSamples, reflectBounces, sided, mapped: the bounces; mirrored: the mirror gather; batch: the gather batch;
+    // sensors: the virtual dosimeters.
     // Made by OwnGather (the members; mapped and mirrored: there is a map, there are panels) or PlanGather (a plan's own).
     struct GatherOptions {
         int samples = 0, sampling = 0;
@@ -328,6 +380,7 @@ private:
         int reflectSamples = 16, reflectBounces = 0, sided = 0;
         bool mapped = false, mirrored = false;
         int batch = 0;
+        bool sensors = false;                       // the launch gathers the sensors too; never set for a plan
     };
     GatherOptions OwnGather() const;
     static GatherOptions PlanGather(const PlanOptions& opt);
@@ -349,6 +402,25 @@ private:
     void UploadReflectanceMap(int triangleCount, float base);
     // the active panels (the file's or the caller's) into the context when it has none or they are not the ones uploaded last
     void UploadMirrors(int triangleCount);
+    // the active sensors into the context when it has none or they are not the ones uploaded last (an upload zeroes their maps)
+    void UploadSensors();
+    // the sensors' part of a launch: direct gather, one bounce under the launch's reflect options, accumulate (RunLaunch)
+    void GatherSensors(const RouteLaunch& launch, int photons, const GatherOptions& g, unsigned gatherSeed, bool accumulate);
+    void CheckSensorsAlone(const char* who) const;  // fatal where sensors cannot follow: sharding, a communicator, mirror panels
+    void ResetSensors();                            // upload, zero the sensors' maps and their launch counter (ResetDosageMap)
+    // How raytracer.cpp reaches raytracer_sensors.cpp, which makes every uvrt_* sensor call of the host layer: set by that file
+    // when it is part of the program, so that a program built from raytracer.cpp without it links and runs every path that
+    // has no sensors.  Sensors() is fatal without the hooks.
+    struct SensorHooks {
+        void (RayTracer::*gather)(const RouteLaunch&, int, const GatherOptions&, unsigned, bool);
+        void (RayTracer::*reset)();
+    };
+    static const SensorHooks* sensorHooks;
+    static const SensorHooks& Sensors();
+    std::string SensorMapPath() const;              // sensorMap as it is opened: a relative name is routeDir's
+    std::vector<uvrt_sensor> sensorFileList;        // the cache of sensorMap's file ...
+    std::string sensorFileParsed;                   // ... and the path it was read from (empty: nothing cached)
+    unsigned long long sensorStampNext = 1, sensorFileStamp = 0, sensorValuesStamp = 0, sensorUploaded = 0;
     std::string MirrorMapPath() const;              // mirrorMap as it is opened: a relative name is routeDir's
     std::vector<uvrt_mirror> mirrorFilePanels;      // the cache of mirrorMap's file ...
     std::vector<uint8_t> mirrorFilePanelOfTri;

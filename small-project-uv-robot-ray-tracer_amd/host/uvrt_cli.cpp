@@ -92,6 +92,13 @@
 //                                           toward PX PY PZ" (only the face that looks at P); later lines override earlier ones, #
 //                                           starts a comment, every face starts at --reflect's RHO.  A relative FILE is resolved
 //                                           against --route-dir.  Refused without --reflect-sided.  --save-route writes <reflect_map>
+//            [--sensors FILE]               virtual dosimeters (RayTracer::sensorMap): lines "sensor X Y Z planar NX NY NZ",
+//                                           "sensor X Y Z sphere" and "grid X0 Y0 Z0 X1 Y1 Z1 NX NY NZ sphere | planar MX MY MZ"; every
+//                                           launch, photons or gather, also gathers the lamp's light and one diffuse bounce at them.
+//                                           Refused with --mirror-map, --gpus > 1 and --batch.  --save-route writes <sensor_map>
+//            [--sensor-samples S]           shadow rays per sensor and launch (default 64)
+//            [--sensor-dump OUT.csv]        index, kind, position, normal, dose (mJ/cm^2), peak (uW/cm^2), standard error of dose
+//            [--calibrate-sensor P K I]     lamp power from a reading P at sensor K with the lamp at position I, in the room as it is
 //            [--mirror-map FILE]            with --gather S or --plan-gather S: specular reflector panels (RayTracer::mirrorMap,
 //                                           PlanOptions::mirrorMapped).  FILE holds lines "mirror X0 Y0 Z0 X1 Y1 Z1 RHO
 //                                           plane QX QY QZ MX MY MZ": the next panel (8 at most) is the plane through Q with normal
@@ -290,6 +297,11 @@ int main(int argc, char** argv)
     int reflectSided = 0;                   // --reflect-sided
     std::string reflectMapFile;             // --reflect-map
     std::string mirrorMapFile;              // --mirror-map
+    std::string sensorsFile, sensorDump;    // --sensors, --sensor-dump
+    int sensorSamples = -1;                 // --sensor-samples
+    bool calibrateSensor = false;           // --calibrate-sensor P K I
+    float calSensorP = 0;
+    int calSensorK = 0, calSensorI = 0;
     int gatherBatch = -1;                   // < 0: not given
     std::string verifyDump;
     float calP = 2909.0f, calH = 0.8f, calD = 1.0f;   // userinterface.cpp:107-109 defaults
@@ -413,6 +425,10 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--plan-verify")) planVerify = true;
         else if (!strcmp(argv[i], "--verify-dump")) { need(1); verifyDump = argv[++i]; }
         else if (!strcmp(argv[i], "--plan-holdout")) { need(1); planHoldout = true; holdoutSeed = (uint32_t)strtoul(argv[++i], nullptr, 0); }
+        else if (!strcmp(argv[i], "--sensors")) { need(1); sensorsFile = argv[++i]; if (sensorsFile.empty() || sensorsFile.find_first_of("<>&") != std::string::npos) { fprintf(stderr, "--sensors FILE: a file name without <, > and & (it goes into route files as it is)\n"); return 2; } }
+        else if (!strcmp(argv[i], "--sensor-samples")) { need(1); sensorSamples = atoi(argv[++i]); if (sensorSamples < 1 || sensorSamples > 4096) { fprintf(stderr, "--sensor-samples must be in [1, 4096]\n"); return 2; } }
+        else if (!strcmp(argv[i], "--sensor-dump")) { need(1); sensorDump = argv[++i]; }
+        else if (!strcmp(argv[i], "--calibrate-sensor")) { need(3); calibrateSensor = true; calSensorP = (float)atof(argv[++i]); calSensorK = atoi(argv[++i]); calSensorI = atoi(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (room.empty()) { fprintf(stderr, "usage: uvrt_cli --room file.glb [options]\n"); return 2; }
@@ -439,6 +455,9 @@ int main(int argc, char** argv)
     if (gather > 0 && batch > 0) { fprintf(stderr, "--gather cannot be combined with --batch (the direct gather runs launch by launch)\n"); return 2; }
     if (gather > 0 && gpus != 1) { fprintf(stderr, "--gather runs on one context (--gpus 1)\n"); return 2; }
     if (gather > 0 && plan) { fprintf(stderr, "--gather cannot be combined with --plan / --plan-drive (the planner's exposure matrix holds photon counts)\n"); return 2; }
+    if (!sensorsFile.empty() && !mirrorMapFile.empty()) { fprintf(stderr, "--sensors cannot be combined with --mirror-map (a sensor would not see the panels' light)\n"); return 2; }
+    if (!sensorsFile.empty() && gpus != 1) { fprintf(stderr, "--sensors runs on one context (--gpus 1)\n"); return 2; }
+    if (!sensorsFile.empty() && batch > 0) { fprintf(stderr, "--sensors cannot be combined with --batch (the sensors are gathered launch by launch)\n"); return 2; }
     if (!routeDir.empty() && routeDir.back() != '/') routeDir += '/';
 
     Mesh mesh;
@@ -473,11 +492,38 @@ int main(int argc, char** argv)
         fprintf(stderr, "the route gathers with %d samples: not supported with --batch, --gpus > 1 or --plan (give --gather 0)\n", rayTracer.gatherSamples);
         return 2;
     }
+    if (!sensorsFile.empty()) rayTracer.sensorMap = sensorsFile;
+    else if (batch > 0 || gpus != 1 || plan) rayTracer.sensorMap.clear();      // (the route file's own <sensor_map>)
+    if (sensorSamples > 0) rayTracer.sensorSamples = sensorSamples;
+    if (rayTracer.HasSensors() && rayTracer.HasMirrors()) {
+        fprintf(stderr, "sensors cannot be combined with mirror panels (a sensor would not see the panels' light)\n");
+        return 2;
+    }
+    if ((calibrateSensor || !sensorDump.empty() || sensorSamples > 0) && !rayTracer.HasSensors()) {
+        fprintf(stderr, "--sensor-samples, --sensor-dump and --calibrate-sensor need --sensors FILE\n");
+        return 2;
+    }
+    if (rayTracer.HasSensors()) {
+        const std::string err = rayTracer.PrepareSensorMap();
+        if (!err.empty()) { fprintf(stderr, "--sensors: %s\n", err.c_str()); return 2; }
+        if (calibrateSensor && (calSensorK < 0 || (size_t)calSensorK >= rayTracer.ActiveSensors().size() || calSensorI < 0 ||
+                                (size_t)calSensorI >= rayTracer.lightPositions.size())) {
+            fprintf(stderr, "--calibrate-sensor P K I: sensor K of %zu, lamp position I of %zu\n", rayTracer.ActiveSensors().size(),
+                    rayTracer.lightPositions.size());
+            return 2;
+        }
+    }
     rayTracer.UpdatePhotonsPerLight();
 
     if (calibrate) {
         rayTracer.CalibratePower(calP, calH, calD);          // userinterface.cpp:130-133
         std::cout << "Calibrated lamp power: " << rayTracer.lightIntensity << std::endl;
+    }
+
+    if (calibrateSensor) {
+        if (uvrt_set_flavour(rayTracer.ctx, flavour) != UVRT_OK) { fprintf(stderr, "--flavour: %s\n", uvrt_last_error()); return 2; }
+        rayTracer.CalibratePowerAtSensor(calSensorP, calSensorK, calSensorI);
+        std::cout << "Calibrated lamp power at sensor " << calSensorK << ": " << rayTracer.lightIntensity << std::endl;
     }
 
     if (plan) {
@@ -566,6 +612,23 @@ int main(int argc, char** argv)
            mesh.triangleCount, dose[0], dose.size() > 1 ? dose[1] : 0.f, dose.size() > 2 ? dose[2] : 0.f,
            dose.size() > 3 ? dose[3] : 0.f);
     if (!dump.empty()) write_f32(dump, dose);
+    if (rayTracer.HasSensors()) {
+        std::vector<float> sdose, speak;
+        std::vector<double> serr;
+        rayTracer.ReadSensors(sdose, speak, serr);
+        const std::vector<uvrt_sensor>& sens = rayTracer.ActiveSensors();
+        printf("sensors: %zu, dose[0] = %.9g mJ/cm^2, peak[0] = %.9g uW/cm^2\n", sens.size(), sdose[0], speak[0]);
+        if (!sensorDump.empty()) {
+            FILE* f = fopen(sensorDump.c_str(), "w");
+            if (!f) { fprintf(stderr, "--sensor-dump: cannot write %s\n", sensorDump.c_str()); return 1; }
+            fprintf(f, "index,kind,x,y,z,nx,ny,nz,dose,peak,std_err\n");
+            for (size_t k = 0; k < sens.size(); ++k)
+                fprintf(f, "%zu,%s,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.17g\n", k, sens[k].kind == UVRT_SENSOR_PLANAR ? "planar" : "sphere",
+                        sens[k].pos[0], sens[k].pos[1], sens[k].pos[2], sens[k].normal[0], sens[k].normal[1], sens[k].normal[2], sdose[k],
+                        speak[k], serr[k]);
+            fclose(f);
+        }
+    }
     if (!ply.empty()) {
         std::vector<float> color((size_t)mesh.triangleCount * 9);
         if (uvrt_read_color(rayTracer.ctx, color.data(), 0, mesh.triangleCount) != UVRT_OK) {
